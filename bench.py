@@ -390,6 +390,34 @@ def parity_sample(spec, topo, roots, fb, marg, n_graphs=4):
             'checker': 'oracle/lbp_oracle.py on the same tables (north star: <= 1e-5)'}
 
 
+DUMP_BYTES = 64 * 10 ** 6       # --dump-outputs writes at most this many bytes in all, .npy headers included
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(directory, per_graph, whole):
+    """--dump-outputs: writes every tensor as DIR/<name>.npy in float64.  `per_graph` holds [B, ...] tensors, `whole` the
+    batch-level ones.  When everything would exceed DUMP_BYTES, every per-graph array keeps the same fixed, seeded sample
+    of graphs (ascending indices), so two runs with the same arguments write the same graphs."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    B = next(iter(per_graph.values())).shape[0]
+    fixed = sum(t.numel() * 8 + 128 for t in whole.values()) + 128 * len(per_graph)
+    row = sum(t[0].numel() * 8 for t in per_graph.values())
+    keep = min(B, (DUMP_BYTES - fixed) // row)
+    if keep < 1:
+        raise SystemExit('--dump-outputs: the outputs of one graph exceed %d bytes' % DUMP_BYTES)
+    idx = None
+    if keep < B:
+        idx = np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).choice(B, keep, replace=False))
+    for name, t in per_graph.items():
+        if idx is not None:
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        np.save(os.path.join(directory, name + '.npy'), t.double().cpu().numpy())
+    for name, t in whole.items():
+        np.save(os.path.join(directory, name + '.npy'), t.double().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -407,7 +435,13 @@ def main():
     ap.add_argument('--no-train-epoch', action='store_true', help='leave out the train_epoch figures (the outer loop on a synthetic TI_DIR)')
     ap.add_argument('--traffic-bytes', type=float, default=None,
                     help='HBM bytes per sweep launch from a rocprofv3 --pmc pass (profiles/), if known')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the sweep call of the last timed step returned as DIR/<name>.npy '
+                         '(float64): marginals, log_posterior, log_posterior_total and, unless --no-writeback, messages; rank 0\'s '
+                         'batch.  At most 64 MB in all: past that, the per-graph arrays keep a fixed, seeded sample of graphs')
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     if 'WORLD_SIZE' not in os.environ and a.gpus > 1:
         return self_launch(a, sys.argv[1:])
@@ -591,6 +625,11 @@ def main():
     order = sorted(range(3), key=lambda i: windows[i][0])
     elapsed, ev, submit = windows[order[1]]
     assert fb.program(roots).status() == 0
+    if rank == 0 and a.dump_outputs:        # before the secondary figures below reuse marg and lp
+        per_graph = {'marginals': marg, 'log_posterior': lp}
+        if not a.no_writeback:
+            per_graph['messages'] = fb.msgs
+        dump_outputs(a.dump_outputs, per_graph, {'log_posterior_total': stats[(step_no[0] - 1) & 1][:1]})
 
     # Secondary figure, never `value`: the same launch under MLBP_SWEEP_SKIP_UNCHANGED (include/mlbp.h), which drops the
     # updates of the root sequence that recompute a message from unchanged inputs.  `value` above executes every update
