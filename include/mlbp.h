@@ -283,12 +283,15 @@ int mlbp_sweep_f64(const mlbp_program* prog, const mlbp_sweep_args* a, void* str
  *     capture records two parallel kernel nodes); groups that name the same tables and feature tensors share one set of
  *     fragment copies (written once per launch, owned by the first such group's program); a group WITHOUT pairwise factors (one
  *     predicted word) may be among them: all its graphs are flagged and redone by the fix-up launch; what follows per group is its fix-up
- *     pass over flagged graphs, its unary write-back when messages are kept, and its gradient when args[k].gradient is
- *     set -- a minibatch of mixed sentence shapes over the two shared pots (train_mp.py:220-299);
+ *     pass over flagged graphs, its unary write-back when messages are kept, its gradient when args[k].gradient is set and
+ *     its posterior (a launch of its own) when args[k].posterior is set -- a minibatch of mixed sentence shapes over the
+ *     two shared pots (train_mp.py:220-299);
  *   - otherwise, when every group qualifies for the lean X = 64 kernel (float64 tables, normalised messages, at most 8
  *     pairwise factors, the same init / write-back / read-out choices, distinct programs) that kernel runs ALL groups in
  *     a single launch, followed by one small fix-up launch (and the gradient, if any) per group;
  *   - otherwise group by group.
+ * Every group's arguments are checked as mlbp_sweep_f64 checks them before anything is enqueued: one bad group fails the call
+ * with that message and runs nothing.
  * progs / args are HOST arrays.  The group table is device memory owned by progs[0], uploaded only when its contents
  * differ from the previous call's (a stream capture of a repeated call records no copy). */
 int mlbp_sweep_groups_f64(const mlbp_program* const* progs, const mlbp_sweep_args* args, int32_t n_groups, void* stream);

@@ -223,6 +223,7 @@ class FactorGraphBatch:
             if tuple(marginals.shape) != (self.B, self.topo.n_vars, self.X) or marginals.dtype != torch.float64:
                 raise ValueError('marginals must be float64 [B][n_vars][X]')
             a.marginals = marginals.data_ptr()
+        ga = pa = None
         if gradient is not None:
             ga = self._gradient_args(*gradient)
             a.gradient = C.addressof(ga)
@@ -234,7 +235,7 @@ class FactorGraphBatch:
             pa.labels, pa.out, pa.sum_out = lab.data_ptr(), out.data_ptr(), None if tot is None else tot.data_ptr()
             a.posterior = C.addressof(pa)
         if _collect is not None:                  # sweep_groups(): gather instead of launching
-            _collect.append((prog, a, gradient and ga))
+            _collect.append((prog, a, (ga, pa)))      # (the argument structs a points to stay alive with it)
             return prog
         _ffi.check(_ffi.lib.mlbp_sweep_f64(prog.handle, C.byref(a), _stream_ptr(self.device)))
         return prog
@@ -464,13 +465,14 @@ class FactorGraphBatch:
         return out
 
 
-def sweep_groups(batches, roots, init=False, marginals=None, keep_messages=True, gradients=None):
+def sweep_groups(batches, roots, init=False, marginals=None, keep_messages=True, gradients=None, posteriors=None):
     """One minibatch of mixed graphs: batches[k] (a FactorGraphBatch: one topology, its tables and messages) is swept
     with its own root sequence roots[k] -- the reference draws roots per instance (LBP.py:223-225) and builds a
     different K_n per instance (train_mp.py:257-299).  Same results as batches[k].sweep(roots[k], ...) one by one; when
     every group qualifies, the fast kernel runs them all in ONE launch (mlbp_sweep_groups_f64).
     marginals: None or one [B_k][n_vars_k][X] tensor per group; gradients: None or one (g_en_en, g_en_de) pair per group
-    (each group's gradient launch follows its sweeps, as in FactorGraphBatch.sweep(gradient=...))."""
+    (each group's gradient launch follows its sweeps, as in FactorGraphBatch.sweep(gradient=...)); posteriors: None or one
+    (labels, out, sum_out) per group, as in FactorGraphBatch.sweep(posterior=...)."""
     if len(batches) != len(roots) or not batches:
         raise ValueError('one root sequence per batch')
     dev = batches[0].device
@@ -479,7 +481,8 @@ def sweep_groups(batches, roots, init=False, marginals=None, keep_messages=True,
         if fb.device != dev:
             raise ValueError('all groups live on one device')
         fb.sweep(roots[k], init=init, marginals=None if marginals is None else marginals[k], keep_messages=keep_messages,
-                 gradient=None if gradients is None else gradients[k], _collect=got)
+                 gradient=None if gradients is None else gradients[k], posterior=None if posteriors is None else posteriors[k],
+                 _collect=got)
     n = len(got)
     handles = (C.c_void_p * n)(*[p.handle for p, _, _ in got])
     args = (_ffi.SweepArgs * n)(*[a for _, a, _ in got])

@@ -41,7 +41,6 @@
 
 #include <cfloat>
 #include <cstdlib>
-#include <mutex>
 #include <vector>
 
 #include "mlbp_internal.h"
@@ -613,18 +612,6 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 1) void contract_chunked_ke
   }
 }
 
-int grant_lds(const void* k) {
-  static std::mutex mu;
-  static std::vector<const void*> granted;
-  std::lock_guard<std::mutex> lock(mu);
-  for (const void* g : granted)
-    if (g == k) return MLBP_OK;
-  if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)) != hipSuccess)
-    return fail(MLBP_EHIP, "contract_kernel: cannot raise the dynamic LDS limit");
-  granted.push_back(k);
-  return MLBP_OK;
-}
-
 template <typename TT, int RT, bool PADDED>
 int launch_contract_rt(const ContractDev& d, int nct, int n_sets, hipStream_t st) {
   const int XA = 64 * RT;
@@ -647,7 +634,7 @@ int launch_contract_rt(const ContractDev& d, int nct, int n_sets, hipStream_t st
     }
     if (!k) { nct = 1; k = sizeof(TT) == 8 ? contract_kernel<TT, RT, 1, 2, 8, false> : contract_kernel<TT, RT, 1, 4, 8, false>; }
   }
-  if (int e = grant_lds((const void*)k)) return e;
+  if (int e = grant_lds((const void*)k, 160 * 1024)) return e;
   const size_t lds_bytes = (size_t)16 * nct * (XA + 2) * sizeof(double);      // (the float32 image is reused as the float64 output image)
   hipLaunchKernelGGL(k, dim3((d.B + 16 * nct - 1) / (16 * nct), n_sets), dim3(threads), lds_bytes, st, d);
   return MLBP_OK;
@@ -659,7 +646,7 @@ int launch_chunked_rt(const ContractDev& d, int n_sets, hipStream_t st) {
   int threads = 512;
   if constexpr ((4 * RT) % 16 == 0) { k = contract_chunked_kernel<double, RT, 16>; threads = 1024; }
   else k = contract_chunked_kernel<double, RT, 8>;
-  if (int e = grant_lds((const void*)k)) return e;
+  if (int e = grant_lds((const void*)k, 160 * 1024)) return e;
   hipLaunchKernelGGL(k, dim3((d.B + 15) / 16, n_sets), dim3(threads), (size_t)16 * (64 * RT + 2) * sizeof(double), st, d);
   return MLBP_OK;
 }
@@ -837,6 +824,7 @@ int launch_gemm_pair_gradient(const mlbp_gradient_args* a, int32_t* status, void
              hipStreamSynchronize(st) != hipSuccess) {
     return fail(MLBP_EHIP, "shared-table gradient: reading the slot tables failed");
   }
+  launch_begin();
   for (int p = 0; p < a->P; ++p) {
     if ((unsigned)h_c[p] >= (unsigned)a->n_msgs || (unsigned)h_r[p] >= (unsigned)a->n_msgs ||
         (unsigned)a->pair_tab_host[p] >= (unsigned)a->n_pair_tables)
@@ -853,8 +841,7 @@ int launch_gemm_pair_gradient(const mlbp_gradient_args* a, int32_t* status, void
     hipLaunchKernelGGL(pair_gradient_combine_kernel, dim3((B + 255) / 256), dim3(256), 0, st, S, B, X, a->pair_label, a->P, p,
                        h_phi[p] ? a->phi_en_en_w1 : a->phi_en_en, a->grad_en_en, status);
   }
-  if (hipGetLastError() != hipSuccess) return fail(MLBP_EHIP, "shared-table gradient: a launch failed");
-  return MLBP_OK;
+  return launch_verdict("shared-table gradient");
 }
 
 int launch_gemm_sweep(const mlbp_program* prog, const mlbp_sweep_args* a, void* stream) {
@@ -883,6 +870,7 @@ int launch_gemm_sweep(const mlbp_program* prog, const mlbp_sweep_args* a, void* 
     if (int e = program_grow(mp, &mp->d_gxbuf, &mp->gxbuf_cap, (size_t)B * X * sizeof(double))) return e;
     xbuf = static_cast<double*>(mp->d_gxbuf);
   }
+  launch_begin();
   {
     HostRow row = {};
     for (int p = 0; p < prog->P; ++p) row.v[p] = a->pair_tab_host[p];
@@ -962,8 +950,7 @@ int launch_gemm_sweep(const mlbp_program* prog, const mlbp_sweep_args* a, void* 
     d.frag = f32 ? (const void*)((const float*)frag + off) : (const void*)((const double*)frag + off);
     if (int e = f32 ? launch_contract<float>(d, X, 1, st) : launch_contract<double>(d, X, 1, st)) return e;
   }
-  if (hipGetLastError() != hipSuccess) return fail(MLBP_EHIP, "shared-table contraction path: a launch failed");
-  return MLBP_OK;
+  return launch_verdict("shared-table contraction path");
 }
 
 }  // namespace mlbp

@@ -24,12 +24,6 @@ namespace {
 constexpr int WG = 256;
 constexpr int FMAX = 8;
 
-#define HIP_TRY(expr)                                                                      \
-  do {                                                                                     \
-    hipError_t _e = (expr);                                                                \
-    if (_e != hipSuccess) return fail(MLBP_EHIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
-  } while (0)
-
 template <int CTRL>
 __device__ __forceinline__ double dpp_mov(double v) {
   int lo = __double2loint(v), hi = __double2hiint(v);

@@ -15,6 +15,22 @@ namespace mlbp {
 // Records a printf-style message for mlbp_last_error() and returns `code`.
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
+// Returns MLBP_EHIP with the runtime's message when a HIP call fails.
+#define HIP_TRY(expr)                                                                      \
+  do {                                                                                     \
+    hipError_t _e = (expr);                                                                \
+    if (_e != hipSuccess) return mlbp::fail(MLBP_EHIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
+  } while (0)
+
+// Raises `kernel`'s dynamic-LDS limit to `bytes`.  hipFuncSetAttribute is a slow host call (~0.1 ms): the largest size granted
+// per kernel is remembered and the call repeated only when a launch needs more.  *fresh (optional): this call raised it.
+int grant_lds(const void* kernel, size_t bytes, bool* fresh = nullptr);
+// The verdict on the launches issued since launch_begin(), and only on them: launch_begin() drops what an earlier runtime call
+// of this thread -- the caller's, another library's -- may have left in the thread's last-error slot.  `what` names the launch
+// in the message, which carries the runtime's own words.
+void launch_begin();
+int launch_verdict(const char* what);
+
 // Fused program form of the X = 64 kernels (build_fused_program in mlbp_sweep.hip): 8-word op headers.
 enum { FOP_UNARY = 0, FOP_PAIR_TM = 1, FOP_PAIR_MT = 2, FOP_VAR = 3, FOP_VAR_PAIR_TM = 4, FOP_VAR_PAIR_MT = 5,
        FOP_BUNDLED = 0x100 /* flag: the next update touches disjoint slots and may share this one's barrier */ };

@@ -20,7 +20,6 @@
 // One barrier per bundle of (at most two independent) updates, as before.
 #include <hip/hip_runtime.h>
 
-#include <mutex>
 #include <vector>
 
 #include "mlbp_device.h"
@@ -57,12 +56,6 @@ typedef double nt_d2 __attribute__((ext_vector_type(2)));
 namespace {
 
 constexpr int WG = 256;
-
-#define HIP_TRY(expr)                                                                      \
-  do {                                                                                     \
-    hipError_t _e = (expr);                                                                \
-    if (_e != hipSuccess) return fail(MLBP_EHIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
-  } while (0)
 
 // micro-op word 0
 constexpr int UOP_VAR = 1;          // bit 0: variable product only (stored, no contraction)
@@ -844,17 +837,6 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
 #endif
 }
 
-int ensure_lds(const void* fn, size_t bytes) {
-  static std::vector<std::pair<const void*, size_t>> granted;
-  static std::mutex mu;
-  std::lock_guard<std::mutex> lock(mu);
-  for (auto& g : granted)
-    if (g.first == fn && g.second >= bytes) return MLBP_OK;
-  HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  granted.push_back({fn, bytes});
-  return MLBP_OK;
-}
-
 }  // namespace
 
 namespace mlbp {
@@ -1108,9 +1090,10 @@ int launch_lean_sweep(const mlbp_program* prog, const mlbp_sweep_args* a, const 
   if (int e = lean_plan(prog, a, gf != nullptr, &ok, &d, &f, &lds)) return e;
   if (!ok) return MLBP_OK;
   lean_fn k = gf ? pick_lean_grad(prog->P) : pick_lean<false>(prog->P, a->X < 64);
-  if (int e = ensure_lds((const void*)k, lds)) return e;
+  if (int e = grant_lds((const void*)k, lds)) return e;
+  launch_begin();
   hipLaunchKernelGGL(k, dim3(a->B), dim3(WG), lds, (hipStream_t)stream, d, f, nullptr, 0, gf ? *gf : GradFusedDev{});
-  HIP_TRY(hipGetLastError());
+  if (int e = launch_verdict("lean sweep")) return e;
   *launched = true;
   return MLBP_OK;
 }
@@ -1156,9 +1139,10 @@ int launch_lean_groups(const mlbp_program* const* progs, const mlbp_sweep_args* 
   int32_t* d_gtable = nullptr;
   if (int e = group_table_device(owner->gtables, table, stream, &d_gtable)) return e;
   lean_fn k = pick_lean<true>(p_max, false);
-  if (int e = ensure_lds((const void*)k, lds_max)) return e;
+  if (int e = grant_lds((const void*)k, lds_max)) return e;
+  launch_begin();
   hipLaunchKernelGGL(k, dim3(total), dim3(WG), lds_max, (hipStream_t)stream, d0, f0, d_gtable, n_groups, GradFusedDev{});
-  HIP_TRY(hipGetLastError());
+  if (int e = launch_verdict("grouped lean sweep")) return e;
   *launched = true;
   return MLBP_OK;
 }

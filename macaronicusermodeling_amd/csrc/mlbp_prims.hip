@@ -12,12 +12,6 @@ using mlbp::fail;
 
 namespace {
 
-#define HIP_TRY(expr)                                                                      \
-  do {                                                                                     \
-    hipError_t _e = (expr);                                                                \
-    if (_e != hipSuccess) return fail(MLBP_EHIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
-  } while (0)
-
 int need_device() {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
@@ -293,7 +287,8 @@ int mlbp_topk_f64(const double* v, int64_t stride, int32_t n, int32_t K, int32_t
   if (n > 16384) return fail(MLBP_EUNSUPPORTED, "mlbp_topk_f64: n=%d > 16384", n);
   if (int e = need_device()) return e;
   size_t lds = (size_t)n * sizeof(double);
-  if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (lds > 64 * 1024)
+    if (int e = mlbp::grant_lds((const void*)topk_kernel, lds)) return e;
   hipLaunchKernelGGL(topk_kernel, dim3(1), dim3(256), lds, (hipStream_t)stream, v, stride, n, K, idx, (int64_t)0);
   HIP_TRY(hipGetLastError());
   return MLBP_OK;
@@ -306,7 +301,8 @@ int mlbp_topk_rows_f64(const double* v, int64_t rows, int32_t n, int32_t K, int3
   if (rows > 0x7fffffff) return fail(MLBP_EINVAL, "mlbp_topk_rows_f64: too many rows");
   if (int e = need_device()) return e;
   size_t lds = (size_t)n * sizeof(double);
-  if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (lds > 64 * 1024)
+    if (int e = mlbp::grant_lds((const void*)topk_kernel, lds)) return e;
   hipLaunchKernelGGL(topk_kernel, dim3((unsigned)rows), dim3(256), lds, (hipStream_t)stream, v, (int64_t)1, n, K, idx, (int64_t)n);
   HIP_TRY(hipGetLastError());
   return MLBP_OK;

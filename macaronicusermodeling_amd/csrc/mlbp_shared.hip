@@ -32,7 +32,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <type_traits>
 #include <vector>
 
@@ -428,7 +427,7 @@ void build_shared_program(const FusedProgram& fp, int n_msgs, int P, int U, Shar
   //   [2] constant PRODUCT INDEX the result is multiplied by (0xFF none) | stash index << 8      [3] second input | kept tile << 8
   // Sections: map3 [n_live] LDS index of a tile (0x100 | product index for a constant product), kind3 [n_lds] 0 raw / 1 c (.) m /
   // 2 sqrt(c) (.) m, | 0x100 some update writes it; stash [n_lds]; back3 [n_back][2] the write-back list in LDS indices.
-  if (!out.pf_ok && out.max_sources == 3 && !getenv("MLBP_SHARED_NO_P3")) {
+  if (!out.pf_ok && out.max_sources == 3) {
     const int NL = out.n_live;
     std::vector<char> is_c(NL, 0);
     std::vector<int> prod_of_tile(NL, -1);
@@ -2306,8 +2305,6 @@ __global__ __launch_bounds__(WG) void gradient_shared_pairs_kernel(PairGradDev d
   }
 }
 
-std::mutex g_attr_mutex;
-
 typedef void (*sweep_fn)(SharedDev, const SharedDev*, const int32_t*, int);
 
 // the gradient-epilogue instances that exist: all-resident two-source, and spilling + wide
@@ -2360,21 +2357,12 @@ int pick_sweep_kernel(bool two, bool spill, bool wide, bool multi, bool grad, bo
   }
 #endif
   }
-  static std::vector<std::pair<const void*, size_t>> granted;
-  {
-    std::lock_guard<std::mutex> lock(g_attr_mutex);
-    bool have = false;
-    for (auto& g : granted) have |= g.first == (const void*)k && g.second >= lds;
-    if (!have) {
-      hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return fail(MLBP_EHIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      granted.push_back({(const void*)k, lds});
-      int per_cu = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, SWG, lds) == hipSuccess)
-        fail(MLBP_OK, "shared-table kernel <%d%s%s%s%s%s>: %zu bytes of LDS per workgroup, %d workgroups per CU", two ? 2 : 1,
-             spill ? ", spilling" : "", wide ? ", wide" : "", multi ? ", groups" : "", grad ? ", gradient" : "", p3 ? ", product-fused (three sources)" : (pf ? ", product-fused" : ""), lds, per_cu);
-    }
-  }
+  bool fresh = false;
+  if (int e = grant_lds((const void*)k, lds, &fresh)) return e;
+  int per_cu = 0;
+  if (fresh && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, SWG, lds) == hipSuccess)
+    fail(MLBP_OK, "shared-table kernel <%d%s%s%s%s%s>: %zu bytes of LDS per workgroup, %d workgroups per CU", two ? 2 : 1,
+         spill ? ", spilling" : "", wide ? ", wide" : "", multi ? ", groups" : "", grad ? ", gradient" : "", p3 ? ", product-fused (three sources)" : (pf ? ", product-fused" : ""), lds, per_cu);
   *out = k;
   return MLBP_OK;
 }
@@ -2445,9 +2433,8 @@ int shared_plan(const mlbp_program* prog, const mlbp_sweep_args* a, bool* ok, Sh
   if (n_cprod < 1 || n_cprod > 8) return fail(MLBP_OK, "shared-table kernel not used: %d constant products (1..8)", n_cprod);
   mlbp_program* mp = const_cast<mlbp_program*>(prog);
   const int n_groups = (a->B + G - 1) / G;
-  // the product-fused form (diagnostic switch: MLBP_SHARED_NO_PF in the environment keeps the general form)
-  static const bool no_pf = getenv("MLBP_SHARED_NO_PF") != nullptr;
-  const bool pf = sp.pf_ok && !no_pf && n_res == sp.n_live && sp.max_sources <= 2 && (!a->marginals || prog->sreadout_all_based) && prog->n_vars <= 8;     // (the read-out stages 8 variables' rows in the spent tiles)
+  // the product-fused form
+  const bool pf = sp.pf_ok && n_res == sp.n_live && sp.max_sources <= 2 && (!a->marginals || prog->sreadout_all_based) && prog->n_vars <= 8;     // (the read-out stages 8 variables' rows in the spent tiles)
   const size_t spill_doubles = (pf || p3) ? (size_t)n_groups * sp.n_stash * TILE : (size_t)n_groups * (sp.n_live - n_res) * TILE;
   // (first use at this size allocates -- a stream-capturing caller warms up or reserves first; a block that is outgrown stays
   // alive with the program: program_grow)
@@ -2522,20 +2509,13 @@ int shared_plan(const mlbp_program* prog, const mlbp_sweep_args* a, bool* ok, Sh
   return MLBP_OK;
 }
 
-// The verdict on the launch just issued (and only on it: launch_begin() drops what an earlier runtime call of this thread -- the
-// caller's, another library's -- may have left in the thread's last-error slot), with the runtime's own words.
-inline void launch_begin() { (void)hipGetLastError(); }
-inline int launch_verdict(const char* what) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? MLBP_OK : fail(MLBP_EHIP, "%s launch failed: %s", what, hipGetErrorString(e));
-}
-
 // unary factor -> variable messages of the call, written back behind the sweeps when the caller wants the message buffer
 int enqueue_unary_writeback(const mlbp_program* prog, const mlbp_sweep_args* a, const SharedDev& d, hipStream_t st) {
   const SharedProgram& sp = prog->shared;
   if (!(d.msgs && !d.vf_only && sp.n_cpw > 0)) return MLBP_OK;
   const int E = sp.n_cpw / 4;
   const long long rows = (long long)a->B * E;
+  launch_begin();
   hipLaunchKernelGGL(unary_writeback_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(WG), 0, st, a->unary_tables, a->unary_tab,
                      prog->d_simage + sp.off_ent, E, a->B, prog->U, a->n_unary_tables, prog->n_msgs, a->msgs);
   if (int e = launch_verdict("unary write-back")) return e;
@@ -2674,9 +2654,8 @@ int launch_shared_groups(const mlbp_program* const* progs, const mlbp_sweep_args
   // Two or more forms present: the product-fused groups' launch goes to a side stream of the owner program, forked behind the
   // prepare launch and joined in front of whatever follows -- the launches are independent, and the three-source form (one
   // workgroup per CU, its last round partly empty) leaves CUs the product-fused workgroups fill.  (In a captured graph: two
-  // parallel kernel nodes.)  MLBP_SHARED_GROUPS_SERIAL=1 in the environment keeps one stream.
-  static const bool serial = getenv("MLBP_SHARED_GROUPS_SERIAL") != nullptr;
-  const bool fork = !serial && first[1] > first[0] && first[3] > first[1];
+  // parallel kernel nodes.)
+  const bool fork = first[1] > first[0] && first[3] > first[1];
   hipStream_t side = st;
   if (fork) {
     if (!owner->side_stream) {
@@ -2745,10 +2724,11 @@ int launch_shared_pair_gradient(const mlbp_gradient_args* a, int32_t* status, vo
     wfrag = static_cast<double*>(blk);
   }
   d.wfrag = wfrag;
+  launch_begin();
   hipLaunchKernelGGL(pair_weight_fragments_kernel, dim3(a->n_pair_tables * 8), dim3(WG), 0, (hipStream_t)stream, a->pair_tables,
                      a->phi_en_en_p, a->phi_en_en_w1_p, wfrag);
   hipLaunchKernelGGL(gradient_shared_pairs_kernel, dim3((a->B + G - 1) / G), dim3(WG), 0, (hipStream_t)stream, d);
-  if (hipGetLastError() != hipSuccess) return fail(MLBP_EHIP, "shared-table pair gradient launch failed");
+  if (int e = launch_verdict("shared-table pair gradient")) return e;
   return MLBP_OK;
 }
 

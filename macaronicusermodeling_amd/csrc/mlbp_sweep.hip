@@ -37,12 +37,6 @@ namespace {
 
 constexpr int WG = 256;
 
-#define HIP_TRY(expr)                                                                      \
-  do {                                                                                     \
-    hipError_t _e = (expr);                                                                \
-    if (_e != hipSuccess) return fail(MLBP_EHIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
-  } while (0)
-
 // Uniform check of the graph's table indices; an out-of-range index would be an out-of-bounds
 // read, so the whole graph is skipped and the status word raised instead.
 __device__ __forceinline__ bool tables_in_range(const SweepDev& d, int g) {
@@ -1319,28 +1313,6 @@ bool exact_kernel_fuses_gradient(const mlbp_program* prog, const mlbp_sweep_args
 }  // namespace mlbp
 
 namespace {
-thread_local bool g_lean_predone = false;  // set by mlbp_sweep_groups_f64 around the per-group fix-up calls
-thread_local bool g_shared_predone = false;   // the same when the shared-table kernels ran the groups
-int sweep_variant() { return g_sweep_variant; }
-
-// hipFuncSetAttribute is a slow host call (~0.1 ms); remember the largest dynamic-LDS size already
-// granted per kernel and only call again when a launch needs more.
-int ensure_dynamic_lds(const void* fn, size_t bytes) {
-  static std::vector<std::pair<const void*, size_t>> granted;
-  static std::mutex mu;
-  std::lock_guard<std::mutex> lock(mu);
-  for (auto& g : granted)
-    if (g.first == fn) {
-      if (g.second >= bytes) return MLBP_OK;
-      HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-      g.second = bytes;
-      return MLBP_OK;
-    }
-  HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  granted.push_back({fn, bytes});
-  return MLBP_OK;
-}
-
 int check_device() {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
@@ -1624,14 +1596,13 @@ static int posterior_behind_sweeps(const mlbp_program* prog, const mlbp_sweep_ar
   return mlbp_log_posterior_sum_f64(a->marginals, pa->labels, a->B, prog->n_vars, a->X, pa->out, pa->sum_out, stream);
 }
 
-int mlbp_sweep_f64(const mlbp_program* prog, const mlbp_sweep_args* a, void* stream) {
-  g_last_fused_gradient = 0;
-  if (!prog || !a) return fail(MLBP_EINVAL, "mlbp_sweep_f64: NULL program or args");
-  prog = effective_program(prog, a);
+// Every argument check of a sweep call of (prog, a), prog the program the call runs, made before anything is enqueued.  A
+// grouped call makes them on all its groups first: one bad group fails it with the single call's message and launches nothing.
+static int check_sweep_args(const mlbp_program* prog, const mlbp_sweep_args* a) {
   if (a->B <= 0 || a->X <= 0) return fail(MLBP_EINVAL, "mlbp_sweep_f64: B=%d X=%d", a->B, a->X);
   if (!a->msgs) return fail(MLBP_EINVAL, "mlbp_sweep_f64: msgs is NULL");
-  if (prog->P > 0 && (!((a->flags & MLBP_SWEEP_PAIR_TABLES_F32) ? (const void*)a->pair_tables_f32 : (const void*)a->pair_tables) ||
-                      !a->pair_tab || a->n_pair_tables <= 0))
+  const bool f32_tables = (a->flags & MLBP_SWEEP_PAIR_TABLES_F32) != 0;
+  if (prog->P > 0 && (!(f32_tables ? (const void*)a->pair_tables_f32 : (const void*)a->pair_tables) || !a->pair_tab || a->n_pair_tables <= 0))
     return fail(MLBP_EINVAL, "mlbp_sweep_f64: program has %d pairwise factors but no pair tables", prog->P);
   if (prog->U > 0 && (!a->unary_tables || !a->unary_tab || a->n_unary_tables <= 0))
     return fail(MLBP_EINVAL, "mlbp_sweep_f64: program has %d unary factors but no unary tables", prog->U);
@@ -1640,120 +1611,147 @@ int mlbp_sweep_f64(const mlbp_program* prog, const mlbp_sweep_args* a, void* str
   if (approx && a->X < MLBP_APPROX_K)      // np.argpartition(-vec, K - 1) in the reference: "kth(=99) out of bounds"
     return fail(MLBP_EINVAL, "mlbp_sweep_f64: approximate inference keeps the %d largest entries; kth(=%d) out of bounds (%d)",
                 MLBP_APPROX_K, MLBP_APPROX_K - 1, a->X);
-  if (approx && !(a->X > 64 && a->X <= 1024 && a->normalize_messages && !(a->flags & MLBP_SWEEP_PAIR_TABLES_F32)))
+  if (approx && !(a->X > 64 && a->X <= 1024 && a->normalize_messages && !f32_tables))
     return fail(MLBP_EUNSUPPORTED, "mlbp_sweep_f64: batched approximate inference needs 100 <= X <= 1024, normalised messages, float64 tables");
+  if (f32_tables && !(a->X == 256 || a->X == 512))
+    return fail(MLBP_EUNSUPPORTED, "mlbp_sweep_f64: float32 pairwise tables need X = 256 or 512 (got %d)", a->X);
+  if (f32_tables && a->gradient) return fail(MLBP_EUNSUPPORTED, "mlbp_sweep_f64: no gradient with float32 pairwise tables");
   if (int e = check_device()) return e;
-  {
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != prog->device)
-      return fail(MLBP_EINVAL, "mlbp_sweep_f64: the program was created on device %d, the calling thread's current device is %d",
-                  prog->device, dev);
-  }
-  SweepDev d;
-  d.pair_tables = a->pair_tables; d.pair_tab = a->pair_tab;
-  d.unary_tables = a->unary_tables; d.unary_tab = a->unary_tab;
-  d.msgs = a->msgs;
-  d.ops = prog->d_ops; d.srcs = prog->d_srcs; d.sweeps = prog->d_sweeps; d.pairseq = prog->d_pairseq;
-  d.status = prog->d_status;
-  d.n_sweeps = prog->n_sweeps; d.n_msgs = prog->n_msgs; d.P = prog->P; d.U = prog->U; d.X = a->X;
-  d.n_pair_tables = a->n_pair_tables; d.n_unary_tables = a->n_unary_tables;
-  d.marginals = nullptr; d.readout = prog->d_readout; d.n_vars = prog->n_vars;
-  d.only = nullptr; d.fill_uniform = 0; d.approx_k = 0;
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev != prog->device)
+    return fail(MLBP_EINVAL, "mlbp_sweep_f64: the program was created on device %d, the calling thread's current device is %d",
+                prog->device, dev);
   if (a->marginals && !prog->d_readout)
     return fail(MLBP_EINVAL, "mlbp_sweep_f64: marginals requested but mlbp_program_set_readout was not called");
   if (a->posterior && (!a->marginals || !a->posterior->labels || !a->posterior->out))
     return fail(MLBP_EINVAL, "mlbp_sweep_f64: posterior needs marginals, labels and an output array");
+  const mlbp_gradient_args* ga = a->gradient;
+  if (ga && (ga->B != a->B || ga->X != a->X || ga->P != prog->P || ga->U != prog->U || ga->n_msgs != prog->n_msgs || ga->msgs != a->msgs))
+    return fail(MLBP_EINVAL, "mlbp_sweep_f64: gradient arguments do not describe the same batch");
+  return MLBP_OK;
+}
+
+// The per-graph kernels' description of (prog, a): the op list as given, no fused read-out, every graph.  Filled in place over
+// zeroed memory (a grouped call compares its descriptors word by word).
+static void fill_sweep_dev(const mlbp_program* prog, const mlbp_sweep_args* a, SweepDev* d) {
+  memset(d, 0, sizeof(*d));
+  d->pair_tables = a->pair_tables; d->pair_tab = a->pair_tab; d->unary_tables = a->unary_tables; d->unary_tab = a->unary_tab;
+  d->msgs = a->msgs; d->ops = prog->d_ops; d->srcs = prog->d_srcs; d->sweeps = prog->d_sweeps; d->pairseq = prog->d_pairseq;
+  d->status = prog->d_status;
+  d->n_sweeps = prog->n_sweeps; d->n_msgs = prog->n_msgs; d->P = prog->P; d->U = prog->U; d->X = a->X;
+  d->n_pair_tables = a->n_pair_tables; d->n_unary_tables = a->n_unary_tables;
+  d->readout = prog->d_readout; d->n_vars = prog->n_vars;
+}
+
+// The exact X = 64 kernel's description of (prog, a) -- the fused program, the marginals as its epilogue when the messages are
+// normalised -- for every graph and without a posterior (G->f.only, G->f.post and the grouped launch's block fields are the
+// caller's).  Returns the kernel's LDS bytes: above X64_LDS_MAX it does not apply.
+constexpr size_t X64_LDS_MAX = 160 * 1024;
+static size_t fill_fixup_group(const mlbp_program* prog, const mlbp_sweep_args* a, FixupGroup* G) {
+  memset(G, 0, sizeof(*G));
+  fill_sweep_dev(prog, a, &G->d);
+  G->d.pairseq = prog->d_fpairseq;
+  G->d.marginals = a->normalize_messages ? a->marginals : nullptr;
+  FusedDev& f = G->f;
+  f.image = prog->d_fops; f.fsweeps = prog->d_fsweeps;
+  f.n_fops = prog->n_fops; f.n_psrcs = prog->n_psrcs; f.n_hoist = prog->n_hoist; f.n_cprod = prog->n_cprod; f.n_cpw = prog->n_cpw;
+  f.n_ext = 1 + prog->n_cprod; f.init = a->init_messages; f.n_graphs = a->B;
+  const size_t img_words = (size_t)prog->n_fops * 8 + prog->n_psrcs + 2 * prog->n_hoist + prog->n_cpw + prog->n_written;
+  return ((size_t)(prog->n_msgs + f.n_ext) * 64 + 64 + 512) * sizeof(double) + (img_words + prog->P + 6 * prog->U + 8) * sizeof(int32_t);
+}
+
+// What follows the sweep kernels of a call and was not fused into them, in this order: the marginals, the gradient (behind a
+// shared-table epilogue: the flagged graphs' only), the posterior.
+struct SweepTail {
+  bool marginals = true;       // false: the sweep kernels wrote them
+  bool grad_done = false;      // the sweep kernels ran the gradient as their epilogue
+  bool grad_flagged = false;   // ... on every graph but the flagged ones
+  bool post_done = false;      // the fix-up pass took the posterior
+};
+static int sweep_tail(const mlbp_program* prog, const mlbp_sweep_args* a, const SweepTail& t, void* stream) {
+  if (a->marginals && t.marginals)
+    if (int e = mlbp_marginals_f64(a->msgs, a->B, prog->n_msgs, a->X, prog->n_vars, prog->d_readout, prog->d_readout + prog->n_vars + 1,
+                                   a->normalize_messages ? 1 : 0, a->marginals, stream)) return e;
+  if (a->gradient && !t.grad_done)
+    if (int e = t.grad_flagged ? mlbp::gradient_flagged_only(a->gradient, prog->d_bail, stream) : gradient_behind_sweeps(prog, a->gradient, stream))
+      return e;
+  return t.post_done ? MLBP_OK : posterior_behind_sweeps(prog, a, stream);
+}
+
+// The fast pass a grouped launch has already run over a group's graphs, leaving the flagged ones to the exact kernel.
+enum FastPass { FAST_NONE, FAST_LEAN, FAST_SHARED };
+
+// One sweep call of (prog, a) -- checked; prog the program it runs -- behind `pass` (FAST_NONE: the call runs its own).
+// variant: mlbp_set_sweep_variant's, read once per public call.
+static int run_sweep(const mlbp_program* prog, const mlbp_sweep_args* a, FastPass pass, int variant, void* stream) {
+  g_last_fused_gradient = 0;
   hipStream_t st = (hipStream_t)stream;
   const bool norm = a->normalize_messages != 0;
-  const size_t LDS_MAX = 160 * 1024;
-  const int variant = sweep_variant();
-  if (a->X == 64) {
-    const int n_ext = 1 + prog->n_cprod;
-    const size_t img_words = (size_t)prog->n_fops * 8 + prog->n_psrcs + 2 * prog->n_hoist + prog->n_cpw + prog->n_written;
+  FixupGroup G;
+  const size_t lds = fill_fixup_group(prog, a, &G);
+  if (a->X == 64 && lds <= X64_LDS_MAX) {
+    mlbp_program* mp = const_cast<mlbp_program*>(prog);
+    const bool fast = variant == 1;               // variant 3: the exact kernel on every graph
+    if (pass == FAST_NONE && fast) {              // shared-table batches: 16 graphs per workgroup on the matrix cores
+      bool launched = false;
+      if (int e = mlbp::launch_shared_sweep(prog, a, stream, &launched)) return e;
+      if (launched) pass = FAST_SHARED;
+    }
+    // The gradient runs as the sweep kernels' epilogue when the tables are on chip in BOTH the fast and the exact kernel (a grouped
+    // lean launch runs none).  Behind the shared-table kernel's epilogue the fix-up pass keeps its own for the graphs it redoes --
+    // or, with more than three pairwise factors, where the exact kernel streams its tables and has no epilogue, the per-graph
+    // gradient kernel follows on the flagged graphs only.
+    const bool exact_grad = mlbp::exact_kernel_fuses_gradient(prog, a) && pass != FAST_LEAN;
+    const bool shared_grad = pass == FAST_SHARED && mlbp::shared_gradient_fused(prog, a);
+    SweepTail tail;
+    tail.marginals = !norm;                       // (normalised: the read-out is the kernels' epilogue)
+    tail.grad_done = exact_grad && (pass != FAST_SHARED || shared_grad);
+    tail.grad_flagged = shared_grad && !exact_grad;
+    GradFusedDev gf = {};
+    if (tail.grad_done) {
+      const mlbp_gradient_args* ga = a->gradient;
+      gf.pair_c_slot = ga->pair_c_slot; gf.pair_r_slot = ga->pair_r_slot; gf.pair_phi = ga->pair_phi; gf.pair_label = ga->pair_label;
+      gf.unary_kind = ga->unary_kind; gf.unary_obs = ga->unary_obs; gf.unary_label = ga->unary_label;
+      gf.phi_en_en = ga->phi_en_en; gf.phi_en_en_w1 = ga->phi_en_en_w1;
+      gf.phi_en_en_t = ga->phi_en_en_t; gf.phi_en_en_w1_t = ga->phi_en_en_w1_t; gf.phi_en_de_t = ga->phi_en_de_t;
+      gf.grad_en_en = ga->grad_en_en; gf.grad_en_de = ga->grad_en_de; gf.Vde = ga->Vde; gf.enabled = 1;
+    }
+    // default path: the lean scale-free kernel (mlbp_lean.hip), up to 8 resident tables
+    if (pass == FAST_NONE && fast && norm && prog->sf_ok && prog->P >= 1 && prog->P <= 8) {
+      bool launched = false;
+      if (int e = mlbp::launch_lean_sweep(prog, a, tail.grad_done ? &gf : nullptr, stream, &launched)) return e;
+      if (launched) pass = FAST_LEAN;
+    }
+    g_last_kernel = pass == FAST_SHARED ? MLBP_KERNEL_SHARED_MFMA : (pass == FAST_LEAN ? MLBP_KERNEL_LEAN : MLBP_KERNEL_EXACT);
+    g_last_fused_gradient = (tail.grad_done || tail.grad_flagged) ? 1 : 0;
+    FusedDev& f = G.f;
+    f.only = pass != FAST_NONE ? mp->d_bail : nullptr;     // after a fast pass: flagged graphs only
+    // get_posterior_probs of the call: taken by the fix-up pass (it visits every graph's flag anyway); without a fix-up pass
+    // -- the exact kernel on every graph -- by its own launch behind the sweeps
+    const mlbp_posterior_args* pa = a->posterior;
+    tail.post_done = pa && f.only && norm && (a->B + FIXUP_GRAPHS_PER_WG - 1) / FIXUP_GRAPHS_PER_WG <= LP_MAX_BLOCKS;
+    if (tail.post_done) {
+      f.post.labels = pa->labels; f.post.out = pa->out; f.post.sum_out = pa->sum_out;
+      f.post.generation = pa->sum_out ? next_lp_generation() : 0u;
+    }
     // the exact kernel keeps the tables in registers when the graph has at most 3 of them, else it streams them
     const int nt = (prog->P >= 1 && prog->P <= 3) ? prog->P : 0;
-    const size_t lds = ((size_t)(prog->n_msgs + n_ext) * 64 + 64 + 512) * sizeof(double) +
-                       (img_words + prog->P + 6 * prog->U + 8) * sizeof(int32_t);
-    if (lds <= LDS_MAX) {
-      mlbp_program* mp = const_cast<mlbp_program*>(prog);
-      const bool fast = variant == 1;               // variant 3: the exact kernel on every graph
-      if (norm) d.marginals = a->marginals;         // read-out fused into the kernels' epilogue
-      // the gradient runs as the sweep kernels' epilogue when the tables are on chip in BOTH the fast and the exact kernel
-      GradFusedDev gf = {};
-      const mlbp_gradient_args* ga = a->gradient;
-      bool grad_fused = false;
-      if (ga) {
-        if (ga->B != a->B || ga->X != a->X || ga->P != prog->P || ga->U != prog->U || ga->n_msgs != prog->n_msgs || ga->msgs != a->msgs)
-          return fail(MLBP_EINVAL, "mlbp_sweep_f64: gradient arguments do not describe the same batch");
-        grad_fused = mlbp::exact_kernel_fuses_gradient(prog, a) && !g_lean_predone;
-        if (grad_fused) {
-          gf.pair_c_slot = ga->pair_c_slot; gf.pair_r_slot = ga->pair_r_slot; gf.pair_phi = ga->pair_phi; gf.pair_label = ga->pair_label;
-          gf.unary_kind = ga->unary_kind; gf.unary_obs = ga->unary_obs; gf.unary_label = ga->unary_label;
-          gf.phi_en_en = ga->phi_en_en; gf.phi_en_en_w1 = ga->phi_en_en_w1;
-          gf.phi_en_en_t = ga->phi_en_en_t; gf.phi_en_en_w1_t = ga->phi_en_en_w1_t; gf.phi_en_de_t = ga->phi_en_de_t;
-          gf.grad_en_en = ga->grad_en_en; gf.grad_en_de = ga->grad_en_de; gf.Vde = ga->Vde; gf.enabled = 1;
-        }
-      }
-      bool shared_done = false;                // shared-table batches: 16 graphs per workgroup on the matrix cores
-      if (g_shared_predone) shared_done = true;  // mlbp_sweep_groups_f64 ran the shared-table kernels for this group already
-      else if (fast && !g_lean_predone)
-        if (int e = mlbp::launch_shared_sweep(prog, a, stream, &shared_done)) return e;
-      // (the shared-table kernel ran the gradient as its epilogue: the fix-up pass keeps its own for the graphs it redoes -- or,
-      // with more than three pairwise factors, where the exact kernel streams its tables and has no epilogue, the per-graph
-      // gradient kernel follows on the flagged graphs only)
-      bool grad_flagged_fixup = false;
-      if (shared_done) {
-        const bool sg = ga && mlbp::shared_gradient_fused(prog, a);
-        if (sg && !grad_fused) grad_flagged_fixup = true;
-        if (!sg || !grad_fused) { grad_fused = false; gf = GradFusedDev{}; }
-      }
-      bool lean_done = false;                  // default path: the lean scale-free kernel (mlbp_lean.hip), up to 8 resident tables
-      if (g_lean_predone) lean_done = true;     // mlbp_sweep_groups_f64 ran the lean kernel for this group already
-      else if (fast && norm && prog->sf_ok && prog->P >= 1 && prog->P <= 8 && !shared_done)
-        if (int e = mlbp::launch_lean_sweep(prog, a, grad_fused ? &gf : nullptr, stream, &lean_done)) return e;
-      g_last_kernel = shared_done ? MLBP_KERNEL_SHARED_MFMA : (lean_done ? MLBP_KERNEL_LEAN : MLBP_KERNEL_EXACT);
-      g_last_fused_gradient = (grad_fused || grad_flagged_fixup) ? 1 : 0;
-      FusedDev f;
-      f.post = PosteriorDev{};
-      f.only = (shared_done || lean_done) ? mp->d_bail : nullptr;     // after a fast pass: flagged graphs only
-      // get_posterior_probs of the call: taken by the fix-up pass (it visits every graph's flag anyway); without a fix-up pass
-      // -- the exact kernel on every graph -- by its own launch below
-      const mlbp_posterior_args* pa = a->posterior;
-      const bool post_in_fixup = pa && f.only && norm && (a->B + FIXUP_GRAPHS_PER_WG - 1) / FIXUP_GRAPHS_PER_WG <= LP_MAX_BLOCKS;
-      if (post_in_fixup) {
-        f.post.labels = pa->labels; f.post.out = pa->out; f.post.sum_out = pa->sum_out;
-        f.post.generation = pa->sum_out ? next_lp_generation() : 0u;
-      }
-      f.image = prog->d_fops; f.fsweeps = prog->d_fsweeps;
-      f.n_fops = prog->n_fops; f.n_psrcs = prog->n_psrcs; f.n_hoist = prog->n_hoist;
-      f.n_cprod = prog->n_cprod; f.n_cpw = prog->n_cpw; f.n_ext = n_ext;
-      f.init = a->init_messages;
-      f.n_graphs = a->B;
-      d.pairseq = prog->d_fpairseq;
-      void (*k)(SweepDev, FusedDev, GradFusedDev) = nullptr;
-#define MLBP_PICK(N) k = grad_fused ? sweep_x64_fused_kernel<true, N, true> : (norm ? sweep_x64_fused_kernel<true, N, false> : sweep_x64_fused_kernel<false, N, false>)
-      switch (nt) {
-        case 1: MLBP_PICK(1); break;
-        case 2: MLBP_PICK(2); break;
-        case 3: MLBP_PICK(3); break;
-        default: MLBP_PICK(0); break;
-      }
-#undef MLBP_PICK
-      if (int e = ensure_dynamic_lds((const void*)k, lds)) return e;
-      hipLaunchKernelGGL(k, dim3(f.only ? (a->B + FIXUP_GRAPHS_PER_WG - 1) / FIXUP_GRAPHS_PER_WG : a->B), dim3(WG), lds, st, d, f, gf);
-      HIP_TRY(hipGetLastError());
-      if (ga && grad_flagged_fixup) {
-        if (int e = mlbp::gradient_flagged_only(ga, mp->d_bail, stream)) return e;
-      } else if (ga && !grad_fused) {
-        if (int e = gradient_behind_sweeps(prog, ga, stream)) return e;
-      }
-      if (a->marginals && !norm)
-        if (int e = mlbp_marginals_f64(a->msgs, a->B, prog->n_msgs, a->X, prog->n_vars, prog->d_readout,
-                                       prog->d_readout + prog->n_vars + 1, 0, a->marginals, stream)) return e;
-      if (pa && !post_in_fixup) return posterior_behind_sweeps(prog, a, stream);
-      return MLBP_OK;
+    void (*k)(SweepDev, FusedDev, GradFusedDev) = nullptr;
+#define MLBP_PICK(N) k = tail.grad_done ? sweep_x64_fused_kernel<true, N, true> : (norm ? sweep_x64_fused_kernel<true, N, false> : sweep_x64_fused_kernel<false, N, false>)
+    switch (nt) {
+      case 1: MLBP_PICK(1); break;
+      case 2: MLBP_PICK(2); break;
+      case 3: MLBP_PICK(3); break;
+      default: MLBP_PICK(0); break;
     }
+#undef MLBP_PICK
+    if (int e = mlbp::grant_lds((const void*)k, lds)) return e;
+    mlbp::launch_begin();
+    hipLaunchKernelGGL(k, dim3(f.only ? (a->B + FIXUP_GRAPHS_PER_WG - 1) / FIXUP_GRAPHS_PER_WG : a->B), dim3(WG), lds, st, G.d, f, gf);
+    if (int e = mlbp::launch_verdict("exact X = 64 sweep")) return e;
+    return sweep_tail(prog, a, tail, stream);
   }
+  const bool approx = (a->flags & MLBP_SWEEP_APPROX_INFERENCE) != 0;
   const bool small_lean_candidate = a->X < 64 && a->X >= 2 && norm && prog->sf_ok && prog->P >= 1 && prog->P <= 4 && variant == 1 &&
                                     !a->gradient && prog->lean.ok && prog->d_limage;
   if (a->init_messages && !small_lean_candidate) {
@@ -1763,25 +1761,16 @@ int mlbp_sweep_f64(const mlbp_program* prog, const mlbp_sweep_args* a, void* str
   if ((a->flags & MLBP_SWEEP_SHARED_PAIR_TABLES) && a->pair_tab_host && mlbp::gemm_path_supports(a->X) && !approx &&
       prog->P >= 1 && prog->P <= 16 && variant == 1) {
     // shared tables at a large state space: every contraction is one MFMA launch over the whole batch
-    if ((a->flags & MLBP_SWEEP_PAIR_TABLES_F32) && a->gradient)
-      return fail(MLBP_EUNSUPPORTED, "mlbp_sweep_f64: no gradient with float32 pairwise tables");
     const int eg = mlbp::launch_gemm_sweep(prog, a, stream);
     if (eg != MLBP_EUNSUPPORTED) {                 // unsupported shape: the per-graph kernels below
       if (eg) return eg;
       g_last_kernel = MLBP_KERNEL_SHARED_GEMM;
-      if (a->marginals)
-        if (int e = mlbp_marginals_f64(a->msgs, a->B, prog->n_msgs, a->X, prog->n_vars, prog->d_readout,
-                                       prog->d_readout + prog->n_vars + 1, norm ? 1 : 0, a->marginals, stream)) return e;
-      if (a->gradient)
-        if (int e = gradient_behind_sweeps(prog, a->gradient, stream)) return e;
-      return posterior_behind_sweeps(prog, a, stream);
+      return sweep_tail(prog, a, SweepTail(), stream);
     }
   }
+  SweepDev d;
+  fill_sweep_dev(prog, a, &d);
   const bool f32_tables = (a->flags & MLBP_SWEEP_PAIR_TABLES_F32) != 0;
-  if (f32_tables && !(a->X == 256 || a->X == 512))
-    return fail(MLBP_EUNSUPPORTED, "mlbp_sweep_f64: float32 pairwise tables need X = 256 or 512 (got %d)", a->X);
-  if (f32_tables && a->gradient)
-    return fail(MLBP_EUNSUPPORTED, "mlbp_sweep_f64: no gradient with float32 pairwise tables");
   // large state spaces: the wide kernel for X = 128 / 256 / 512 exactly, and (normalised messages, float64 tables) for
   // any X in (64, 1024] with the last pieces of each row masked
   d.approx_k = approx ? MLBP_APPROX_K : 0;
@@ -1811,14 +1800,10 @@ int mlbp_sweep_f64(const mlbp_program* prog, const mlbp_sweep_args* a, void* str
 #undef MLBP_WIDE_PAD
     }
     const size_t ldsw = ((size_t)6 * xp + 4) * sizeof(double);
+    mlbp::launch_begin();
     hipLaunchKernelGGL(kw, dim3(a->B), dim3(WG), ldsw, st, d);
-    HIP_TRY(hipGetLastError());
-    if (a->marginals)
-      if (int e = mlbp_marginals_f64(a->msgs, a->B, prog->n_msgs, a->X, prog->n_vars, prog->d_readout,
-                                     prog->d_readout + prog->n_vars + 1, norm ? 1 : 0, a->marginals, stream)) return e;
-    if (a->gradient)
-      if (int e = gradient_behind_sweeps(prog, a->gradient, stream)) return e;
-    return posterior_behind_sweeps(prog, a, stream);
+    if (int e = mlbp::launch_verdict("wide sweep")) return e;
+    return sweep_tail(prog, a, SweepTail(), stream);
   }
   // small state spaces (X < 64): the lean X = 64 kernel on zero-padded vectors and tables; the graphs it flags are redone
   // by the generic kernel below in its fix-up mode
@@ -1835,6 +1820,7 @@ int mlbp_sweep_f64(const mlbp_program* prog, const mlbp_sweep_args* a, void* str
   g_last_kernel = lean_small ? MLBP_KERNEL_LEAN : MLBP_KERNEL_GENERIC;
   size_t base = ((size_t)a->X + 4) * sizeof(double);
   size_t with_msgs = base + (size_t)prog->n_msgs * a->X * sizeof(double);
+  mlbp::launch_begin();
   if (with_msgs <= 64 * 1024) {
     auto k = norm ? sweep_generic_kernel<true, true> : sweep_generic_kernel<false, true>;
     hipLaunchKernelGGL(k, dim3(a->B), dim3(WG), with_msgs, st, d);
@@ -1842,61 +1828,47 @@ int mlbp_sweep_f64(const mlbp_program* prog, const mlbp_sweep_args* a, void* str
     auto k = norm ? sweep_generic_kernel<true, false> : sweep_generic_kernel<false, false>;
     hipLaunchKernelGGL(k, dim3(a->B), dim3(WG), base, st, d);
   }
-  HIP_TRY(hipGetLastError());
-  if (a->marginals)
-    if (int e = mlbp_marginals_f64(a->msgs, a->B, prog->n_msgs, a->X, prog->n_vars, prog->d_readout,
-                                   prog->d_readout + prog->n_vars + 1, norm ? 1 : 0, a->marginals, stream)) return e;
-  if (a->gradient)
-    if (int e = gradient_behind_sweeps(prog, a->gradient, stream)) return e;
-  return posterior_behind_sweeps(prog, a, stream);
+  if (int e = mlbp::launch_verdict("generic sweep")) return e;
+  return sweep_tail(prog, a, SweepTail(), stream);
+}
+
+int mlbp_sweep_f64(const mlbp_program* prog, const mlbp_sweep_args* a, void* stream) {
+  g_last_fused_gradient = 0;
+  if (!prog || !a) return fail(MLBP_EINVAL, "mlbp_sweep_f64: NULL program or args");
+  prog = effective_program(prog, a);
+  if (int e = check_sweep_args(prog, a)) return e;
+  return run_sweep(prog, a, FAST_NONE, g_sweep_variant, stream);
 }
 
 // Behind launch_shared_groups: every group's fix-up pass in ONE launch (and, when the call carries gradients, one launch of
-// the per-graph gradient kernel over the flagged graphs of all groups).  *done false: some group needs the per-group path
-// (messages kept -- the unary write-back ran already, but marginals without normalisation, an LDS image too large, a gradient
-// the shared-table kernel did not produce).
+// the per-graph gradient kernel over the flagged graphs of all groups), then each group's posterior by its own launch.
+// *done false: some group needs the per-group path (messages kept -- the unary write-back ran already, but marginals without
+// normalisation, an LDS image too large, a gradient the shared-table kernel did not produce).
 static int finish_shared_groups(const mlbp_program* const* progs, const mlbp_sweep_args* args, int n_groups, void* stream, bool* done) {
   *done = false;
-  const size_t LDS_MAX = 160 * 1024;
   std::vector<FixupGroup> table(n_groups);
   std::vector<mlbp_gradient_args> grads;
   std::vector<const uint8_t*> grad_flags;
   size_t lds_max = 0;
   int blocks = 0;
-  bool any_grad = false;
   for (int k = 0; k < n_groups; ++k) {
     const mlbp_program* prog = progs[k];
     const mlbp_sweep_args* a = &args[k];
     if (a->X != 64 || !a->normalize_messages || !a->init_messages) return MLBP_OK;
-    if (a->marginals && !prog->d_readout) return MLBP_OK;
-    const int n_ext = 1 + prog->n_cprod;
-    const size_t img_words = (size_t)prog->n_fops * 8 + prog->n_psrcs + 2 * prog->n_hoist + prog->n_cpw + prog->n_written;
-    const size_t lds = ((size_t)(prog->n_msgs + n_ext) * 64 + 64 + 512) * sizeof(double) + (img_words + prog->P + 6 * prog->U + 8) * sizeof(int32_t);
-    if (lds > LDS_MAX) return MLBP_OK;
+    FixupGroup& G = table[k];
+    const size_t lds = fill_fixup_group(prog, a, &G);
+    if (lds > X64_LDS_MAX) return MLBP_OK;
     lds_max = std::max(lds_max, lds);
     // (a group without pairwise factors -- one predicted word -- never ran the shared-table kernels: launch_shared_groups flagged
     // all of its graphs, so this pass and the flagged graphs' gradient below ARE its sweep call)
     if (a->gradient && prog->P > 0 && !mlbp::shared_gradient_fused(prog, a)) return MLBP_OK;
-    mlbp_program* mp = const_cast<mlbp_program*>(prog);
-    FixupGroup& G = table[k];
-    memset(&G, 0, sizeof(G));
-    SweepDev& d = G.d;
-    d.pair_tables = a->pair_tables; d.pair_tab = a->pair_tab; d.unary_tables = a->unary_tables; d.unary_tab = a->unary_tab;
-    d.msgs = a->msgs; d.ops = prog->d_ops; d.srcs = prog->d_srcs; d.sweeps = prog->d_sweeps; d.pairseq = prog->d_fpairseq;
-    d.status = prog->d_status;
-    d.n_sweeps = prog->n_sweeps; d.n_msgs = prog->n_msgs; d.P = prog->P; d.U = prog->U; d.X = a->X;
-    d.n_pair_tables = a->n_pair_tables; d.n_unary_tables = a->n_unary_tables;
-    d.marginals = a->marginals; d.readout = prog->d_readout; d.n_vars = prog->n_vars;
-    FusedDev& f = G.f;
-    f.only = mp->d_bail; f.image = prog->d_fops; f.fsweeps = prog->d_fsweeps;
-    f.n_fops = prog->n_fops; f.n_psrcs = prog->n_psrcs; f.n_hoist = prog->n_hoist; f.n_cprod = prog->n_cprod; f.n_cpw = prog->n_cpw;
-    f.n_ext = n_ext; f.init = a->init_messages; f.n_graphs = a->B;
+    G.f.only = prog->d_bail;
     G.first_block = blocks;
     G.per_wg = prog->P == 0 ? 1 : FIXUP_GRAPHS_PER_WG;          // (a pairwise-free group is all flagged: one workgroup per graph, not 64 graphs in a row)
     blocks += (a->B + G.per_wg - 1) / G.per_wg;
-    if (a->gradient) { any_grad = true; grads.push_back(*a->gradient); grad_flags.push_back(mp->d_bail); }
+    if (a->gradient) { grads.push_back(*a->gradient); grad_flags.push_back(prog->d_bail); }
   }
-  if (any_grad && (int)grads.size() != n_groups) return MLBP_OK;        // (all groups or none carry a gradient)
+  if (!grads.empty() && (int)grads.size() != n_groups) return MLBP_OK;        // (all groups or none carry a gradient)
   // the table as 32-bit words in the first program's group-table cache (one device copy per distinct contents)
   static_assert(sizeof(FixupGroup) % 4 == 0, "");
   std::vector<int32_t> words(sizeof(FixupGroup) / 4 * (size_t)n_groups + 1);
@@ -1905,48 +1877,54 @@ static int finish_shared_groups(const mlbp_program* const* progs, const mlbp_swe
   mlbp_program* owner = const_cast<mlbp_program*>(progs[0]);
   int32_t* d_table = nullptr;
   if (int e = mlbp::group_table_device(owner->stables, words, stream, &d_table)) return e;
-  if (int e = ensure_dynamic_lds((const void*)sweep_x64_fixup_groups_kernel, lds_max)) return e;
+  if (int e = mlbp::grant_lds((const void*)sweep_x64_fixup_groups_kernel, lds_max)) return e;
+  mlbp::launch_begin();
   hipLaunchKernelGGL(sweep_x64_fixup_groups_kernel, dim3(blocks), dim3(WG), lds_max, (hipStream_t)stream,
                      reinterpret_cast<const FixupGroup*>(d_table), n_groups);
-  HIP_TRY(hipGetLastError());
-  if (any_grad)
+  if (int e = mlbp::launch_verdict("grouped exact X = 64 fix-up")) return e;
+  if (!grads.empty())
     if (int e = mlbp::gradient_flagged_groups(grads.data(), grad_flags.data(), n_groups, owner, stream)) return e;
+  SweepTail tail;                                 // (the marginals are the kernels' epilogue, the gradient is done above)
+  tail.marginals = false;
+  tail.grad_done = true;
+  for (int k = 0; k < n_groups; ++k)
+    if (int e = sweep_tail(progs[k], &args[k], tail, stream)) return e;
   g_last_kernel = MLBP_KERNEL_SHARED_MFMA;
-  g_last_fused_gradient = any_grad ? 1 : 0;
+  g_last_fused_gradient = grads.empty() ? 0 : 1;
   *done = true;
   return MLBP_OK;
 }
 
 int mlbp_sweep_groups_f64(const mlbp_program* const* progs, const mlbp_sweep_args* args, int32_t n_groups, void* stream) {
   if (!progs || !args || n_groups < 1) return fail(MLBP_EINVAL, "mlbp_sweep_groups_f64: bad arguments");
-  bool one_launch = false;
   std::vector<const mlbp_program*> eff(n_groups);
   for (int k = 0; k < n_groups; ++k) {
     if (!progs[k]) return fail(MLBP_EINVAL, "mlbp_sweep_groups_f64: NULL program");
     eff[k] = effective_program(progs[k], &args[k]);
+    if (int e = check_sweep_args(eff[k], &args[k])) return e;
   }
   progs = eff.data();
-  bool shared_launch = false;
-  if (sweep_variant() == 1)
-    if (int e = mlbp::launch_shared_groups(progs, args, n_groups, stream, &shared_launch)) return e;
-  if (sweep_variant() == 1 && !shared_launch)
-    if (int e = mlbp::launch_lean_groups(progs, args, n_groups, stream, &one_launch)) return e;
+  const int variant = g_sweep_variant;
+  FastPass pass = FAST_NONE;
+  if (variant == 1) {
+    bool shared = false, lean = false;
+    if (int e = mlbp::launch_shared_groups(progs, args, n_groups, stream, &shared)) return e;
+    if (!shared)
+      if (int e = mlbp::launch_lean_groups(progs, args, n_groups, stream, &lean)) return e;
+    pass = shared ? FAST_SHARED : (lean ? FAST_LEAN : FAST_NONE);
+  }
   // the shared-table kernels have run every group, gradient included: ONE fix-up launch for the flagged graphs of all groups and
   // one more for their gradients (a mixed minibatch used to pay both per group)
-  if (shared_launch) {
+  if (pass == FAST_SHARED) {
     bool done = false;
     if (int e = finish_shared_groups(progs, args, n_groups, stream, &done)) return e;
     if (done) return MLBP_OK;
   }
-  // the fast kernel has run every group (one_launch): what is left per group is the fix-up pass over the graphs it
-  // flagged; otherwise the groups run one after the other exactly as separate calls would
-  int rc = MLBP_OK;
-  g_lean_predone = one_launch;
-  g_shared_predone = shared_launch;
-  for (int k = 0; k < n_groups && rc == MLBP_OK; ++k) rc = mlbp_sweep_f64(progs[k], &args[k], stream);
-  g_lean_predone = false;
-  g_shared_predone = false;
-  return rc;
+  // a fast kernel has run every group: what is left per group is the fix-up pass over the graphs it flagged; otherwise the
+  // groups run one after the other exactly as separate calls would
+  for (int k = 0; k < n_groups; ++k)
+    if (int e = run_sweep(progs[k], &args[k], pass, variant, stream)) return e;
+  return MLBP_OK;
 }
 
 #ifdef MLBP_ABLATE
@@ -1967,6 +1945,27 @@ int mlbp_debug_set_stamp_buffer(void* dev_ptr) {
 }  // extern "C"
 
 namespace mlbp {
+int grant_lds(const void* kernel, size_t bytes, bool* fresh) {
+  static std::vector<std::pair<const void*, size_t>> granted;
+  static std::mutex mu;
+  std::lock_guard<std::mutex> lock(mu);
+  if (fresh) *fresh = false;
+  auto g = std::find_if(granted.begin(), granted.end(), [&](const std::pair<const void*, size_t>& e) { return e.first == kernel; });
+  if (g != granted.end() && g->second >= bytes) return MLBP_OK;
+  HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  if (g != granted.end()) g->second = bytes;
+  else granted.push_back({kernel, bytes});
+  if (fresh) *fresh = true;
+  return MLBP_OK;
+}
+
+void launch_begin() { (void)hipGetLastError(); }
+
+int launch_verdict(const char* what) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? MLBP_OK : fail(MLBP_EHIP, "%s launch failed: %s", what, hipGetErrorString(e));
+}
+
 int program_grow(mlbp_program* prog, void** p, size_t* cap, size_t bytes, bool zero) {
   if (bytes <= *cap && *p) return MLBP_OK;
   void* fresh = nullptr;
@@ -2137,9 +2136,9 @@ int mlbp_init_messages_f64(double* msgs, int64_t n_rows, int32_t X, void* stream
   if (int e = check_device()) return e;
   int64_t n = n_rows * X;
   int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+  mlbp::launch_begin();
   hipLaunchKernelGGL(fill_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, msgs, n, 1.0 / (double)X);
-  HIP_TRY(hipGetLastError());
-  return MLBP_OK;
+  return mlbp::launch_verdict("message initialisation");
 }
 
 int mlbp_marginals_f64(const double* msgs, int32_t B, int32_t n_msgs, int32_t X, int32_t n_vars,
@@ -2148,10 +2147,10 @@ int mlbp_marginals_f64(const double* msgs, int32_t B, int32_t n_msgs, int32_t X,
   if (!msgs || !in_off || !in_slots || !out || B <= 0 || n_msgs <= 0 || X <= 0 || n_vars <= 0)
     return fail(MLBP_EINVAL, "mlbp_marginals_f64: bad arguments");
   if (int e = check_device()) return e;
+  mlbp::launch_begin();
   hipLaunchKernelGGL(marginals_kernel, dim3(B), dim3(WG), 0, (hipStream_t)stream, msgs, n_msgs, X, n_vars,
                      in_off, in_slots, normalize_messages, out);
-  HIP_TRY(hipGetLastError());
-  return MLBP_OK;
+  return mlbp::launch_verdict("marginals");
 }
 
 int mlbp_log_posterior_sum_f64(const double* marginals, const int32_t* labels, int32_t B, int32_t n_vars,
@@ -2167,10 +2166,10 @@ int mlbp_log_posterior_sum_f64(const double* marginals, const int32_t* labels, i
   // the block partials live in one device-wide scratch array: launches on DIFFERENT streams must not overlap.  Every
   // launch has its own generation number (the arrival word restarts with it: see the kernel)
   const unsigned gen = sum_out ? next_lp_generation() : 0u;
+  mlbp::launch_begin();
   hipLaunchKernelGGL(log_posterior_kernel, dim3(blocks), dim3(LP_WG), 0, (hipStream_t)stream, marginals, labels, B, n_vars, X, out,
                      sum_out, status, gen);
-  HIP_TRY(hipGetLastError());
-  return MLBP_OK;
+  return mlbp::launch_verdict("log-posterior");
 }
 
 int mlbp_log_posterior_groups_f64(const mlbp_posterior_group* groups, int32_t n_groups, int64_t n_total, int32_t X, double* out,
@@ -2179,10 +2178,10 @@ int mlbp_log_posterior_groups_f64(const mlbp_posterior_group* groups, int32_t n_
   if (int e = check_device()) return e;
   int32_t* status = nullptr;
   if (int e = global_status(&status)) return e;
+  mlbp::launch_begin();
   hipLaunchKernelGGL(log_posterior_groups_kernel, dim3((unsigned)((n_total + LP_WG - 1) / LP_WG)), dim3(LP_WG), 0, (hipStream_t)stream, groups,
                      n_groups, (long long)n_total, X, out, status);
-  HIP_TRY(hipGetLastError());
-  return MLBP_OK;
+  return mlbp::launch_verdict("grouped log-posterior");
 }
 
 int mlbp_log_posterior_f64(const double* marginals, const int32_t* labels, int32_t B, int32_t n_vars,

@@ -63,3 +63,13 @@ def random_spec(rs, name, X=4):
     return dict(name=name, style='explicit', X=X, var_ids=seen, labels=[0] * len(seen), factors=factors)
 
 
+
+
+def posterior_buffers(fb, seed):
+    """(labels, out, sum_out) for FactorGraphBatch.sweep(posterior=...): random int32 labels [B][n_vars] in [0, X) on fb's
+    device, NaN-filled outputs."""
+    import torch
+    labels = np.random.RandomState(seed).randint(0, fb.X, size=(fb.B, fb.topo.n_vars)).astype(np.int32)
+    nan = float('nan')
+    return (torch.from_numpy(labels).to(fb.device), torch.full((fb.B,), nan, dtype=torch.float64, device=fb.device),
+            torch.full((1,), nan, dtype=torch.float64, device=fb.device))

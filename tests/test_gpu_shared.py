@@ -454,29 +454,37 @@ def test_groups_of_mixed_shapes_in_one_shared_launch_sequence():
     """mlbp_sweep_groups_f64 over five topologies (K2, two K3, K4 -- three-source updates --, K5 -- the general form), each with its
     own roots, batch size (partial last groups of 16) and tables: ONE prepare launch and one sweep launch PER FORM of the
     shared-table kernel (product-fused: K2, K3; its three-source variant: K4; general: K5) behind a group table.  Same bits as the five
-    single launch sequences, the oracle's values, a degenerate graph of one group redone by the exact kernel."""
+    single launch sequences, the oracle's values, a degenerate graph of one group redone by the exact kernel; every group's
+    log-posteriors bit for bit, their batch sums to rounding.  A group with a posterior but no marginals fails the whole call
+    before anything runs."""
+    import ctypes
+    from helpers import posterior_buffers
     from macaronicusermodeling_amd import _ffi
-    from macaronicusermodeling_amd.batch import sweep_groups
+    from macaronicusermodeling_amd.batch import _stream_ptr, sweep_groups
     names, sizes = ['user_k2', 'user_k3_gaps_1_2_3', 'user_k4', 'user_k3_gaps_3_6', 'user_k5'], [5, 37, 18, 16, 21]      # (K5: the general form, a third launch)
 
     def mutate(inputs):
         inputs[3]['pot_en_de'] = inputs[3]['pot_en_de'].copy(); inputs[3]['pot_en_de'][:, :] = 0.0
     built = [_shared_batch(SPECS[n](), B, seed=11 + k, mutate=mutate if k == 1 else None) for k, (n, B) in enumerate(zip(names, sizes))]
     roots = [(list(topo.var_ids) * 3)[k:k + 3] for k, (_, topo, _) in enumerate(built)]
-    single_msgs, single_marg = [], []
-    for (fb, topo, _), r in zip(built, roots):
+    single_msgs, single_marg, single_post = [], [], []
+    for k, ((fb, topo, _), r) in enumerate(zip(built, roots)):
         m = torch.empty(fb.B, topo.n_vars, 64, dtype=torch.float64, device=fb.device)
-        fb.sweep(r, init=True, marginals=m)
+        post = posterior_buffers(fb, 90 + k)
+        fb.sweep(r, init=True, marginals=m, posterior=post)
         assert _ffi.lib.mlbp_last_sweep_kernel() == KERNEL_SHARED_MFMA
-        single_msgs.append(fb.msgs.clone()); single_marg.append(m)
+        single_msgs.append(fb.msgs.clone()); single_marg.append(m); single_post.append(post)
         fb.msgs.fill_(float('nan'))
     margs = [torch.full_like(m, float('nan')) for m in single_marg]
-    progs = sweep_groups([fb for fb, _, _ in built], roots, init=True, marginals=margs)
+    posts = [(lab, torch.full_like(out, float('nan')), torch.full_like(tot, float('nan'))) for lab, out, tot in single_post]
+    progs = sweep_groups([fb for fb, _, _ in built], roots, init=True, marginals=margs, posteriors=posts)
     assert _ffi.lib.mlbp_last_sweep_kernel() == KERNEL_SHARED_MFMA, _ffi.lib.mlbp_last_error()
     assert [p.exact_count(B) for p, B in zip(progs, sizes)] == [0, 1, 0, 0, 0]
     for k, (fb, topo, inputs) in enumerate(built):
         # (every group runs the form of the kernel its single launch took: the same bits)
         assert torch.equal(fb.msgs, single_msgs[k]) and torch.equal(margs[k], single_marg[k])
+        assert torch.equal(posts[k][1], single_post[k][1])
+        np.testing.assert_allclose(posts[k][2].item(), single_post[k][2].item(), rtol=1e-13)
         got = fb.msgs.cpu().numpy()
         with np.errstate(all='ignore'):
             for b in range(0, fb.B, 3):
@@ -496,3 +504,17 @@ def test_groups_of_mixed_shapes_in_one_shared_launch_sequence():
     sweep_groups([fb for fb, _, _ in built], roots, init=True, marginals=margs)
     for k, (fb, _, _) in enumerate(built):
         np.testing.assert_allclose(fb.msgs.cpu().numpy(), single_msgs[k].cpu().numpy(), rtol=1e-11, atol=1e-300)
+    # one group with a posterior but no marginals (a request the Python wrapper refuses, made in the collected arguments): the call
+    # fails with the single call's message and leaves every group's messages as they were
+    built[0][0].pair_tables_shared = True
+    got = []
+    for k, (fb, _, _) in enumerate(built):
+        fb.msgs.fill_(0.25)
+        fb.sweep(roots[k], init=True, marginals=margs[k], posterior=posts[k], _collect=got)
+    got[2][1].marginals = None
+    handles = (ctypes.c_void_p * len(got))(*[p.handle for p, _, _ in got])
+    args = (_ffi.SweepArgs * len(got))(*[a for _, a, _ in got])
+    rc = _ffi.lib.mlbp_sweep_groups_f64(handles, args, len(got), _stream_ptr(built[0][0].device))
+    assert rc == _ffi.MLBP_EINVAL and 'posterior needs marginals' in _ffi.last_error()
+    torch.cuda.synchronize()
+    assert all(bool((fb.msgs == 0.25).all()) for fb, _, _ in built)

@@ -1,6 +1,5 @@
 """Diagnostic: TiDirTrainer.epoch on a synthetic TI_DIR whose sentences have 2-4 predicted words (K2 / K3 / K4 buckets in one
-launch sequence: mlbp_sweep_groups_f64 runs one sweep launch per form of the shared-table kernel).  With
-MLBP_SHARED_NO_PF=1 MLBP_SHARED_NO_P3=1 in the environment every group takes the general form (what a mixed launch ran before)."""
+launch sequence: mlbp_sweep_groups_f64 runs one sweep launch per form of the shared-table kernel)."""
 import os, sys, time, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
