@@ -17,7 +17,6 @@ Pairwise tables are the two shared pots (`pot_en_en`, `pot_en_en_w1`) referenced
 table-index indirection; a unary factor's table is a COLUMN of a pot (LBP.py:702-703), read as a
 row of the transposed pot the potentials kernel also writes -- no per-instance copies.
 """
-import ctypes as C
 import os
 
 import numpy as np
@@ -27,11 +26,14 @@ from . import _ffi, dist as mdist
 from .batch import FactorGraphBatch, _stream_ptr
 from .topology import GraphTopology
 
+# params and prediction files carry the adapt mode in their name (train_mp.py:654-656, 688-690)
+ADAPT_EXT = {'user': '.user_adapt', 'experience': '.exp_adapt', None: ''}
+
 
 class UserGraphTrainer:
     def __init__(self, spec, var_labels, unary_obs, phi_en_en, phi_en_en_w1, phi_en_de, theta_en_en, theta_en_de,
                  device='cuda:0', sweeps=3, roots=None, planes=None, domains=None, theta_dom_en_en=None,
-                 theta_dom_en_de=None, skip_unchanged=False, shared=None, features_of=None):
+                 theta_dom_en_de=None, skip_unchanged=False, member=False, features_of=None):
         """spec: a 'trainmp'-style spec (tests/golden/cases.py: factors carry factor_type / gap);
         var_labels [B][n_vars], unary_obs [B][U]: this rank's shard of instances.
         planes: optional per-instance sparse feature planes, a list (one entry per instance) of
@@ -41,10 +43,10 @@ class UserGraphTrainer:
         (train_mp.py:162-171, 226-247): instance i builds its potentials from theta_dom[domains[i]] INSTEAD of the
         global theta; the global theta still receives every instance's step.  Instances of one domain should be
         contiguous (groups of 16 consecutive graphs that share their tables run on the matrix cores).
-        shared: a _SharedTables (the bucket trainers of one TiDirTrainer): the pots, their transposed rows, every bucket's private
-        rows and the per-instance outputs then live in arrays the SET owns -- one potentials launch, one patch launch and one
-        statistics launch per step for all sentence shapes instead of one each per shape; finish_shared() completes the
-        construction once the set has sized them.
+        The pots, their transposed rows, the private rows and the per-instance outputs live in a _SharedTables, the only owner
+        of per-step device state.  A standalone trainer is a set of one, built at the end of this constructor; member=True
+        leaves that to the caller, which builds ONE set over many trainers (_BucketSet: the bucket trainers of a TiDirTrainer,
+        one potentials launch, one patch launch and one statistics launch per step for all sentence shapes).
         skip_unchanged (off by default, like the C ABI: the default executes every update of the reference's schedule): the
         sweeps drop the updates of the root sequence that would recompute a message from unchanged inputs
         (MLBP_SWEEP_SKIP_UNCHANGED, include/mlbp.h) -- a third of a three-root user graph's contractions; statistics equal
@@ -105,23 +107,17 @@ class UserGraphTrainer:
         self.roots = list(roots) if roots is not None else [topo.var_ids[i % topo.n_vars] for i in range(self.sweeps)]
         fb.is_loopy = topo.has_loops(self.roots[0])
         self.n_sweeps_run = self.sweeps if fb.is_loopy else 1                            # LBP.py:219
-        self.shared = shared
-        if shared is None:
-            self.pair_tables = torch.empty(2 * nd, X, X, dtype=torch.float64, device=dev)
-            self.unary_tables = torch.empty(self.n_shared_rows + self.n_priv, X, dtype=torch.float64, device=dev)
-            self._finish(priv_row0=self.n_shared_rows, g_ee=torch.empty(B, self.F_ee, dtype=torch.float64, device=dev),
-                         g_ed=torch.empty(B, self.F_ed, dtype=torch.float64, device=dev))
+        if not member:
+            _SharedTables([self])
 
-    def finish_shared(self, priv_row0, g_ee, g_ed):
-        """Second half of the construction under a _SharedTables: the set's pots and rows, this bucket's private rows starting
-        at row priv_row0 of the set's row array, its per-instance gradient rows as views of the set's arrays."""
-        self.pair_tables, self.unary_tables = self.shared.pair_tables, self.shared.unary_tables
-        self._finish(priv_row0, g_ee, g_ed)
-
-    def _finish(self, priv_row0, g_ee, g_ed):
+    def _join(self, shared, priv_row0, inst0):
+        """The rest of the construction, called by the _SharedTables that takes this trainer in: the set's pots and rows, this
+        trainer's private rows from row priv_row0 of the set's row array, its per-instance gradient rows and log-posteriors from
+        instance inst0 of the set's arrays."""
         fb, topo, dev = self.batch, self.topo, self.device
         X, B = self.spec['X'], fb.B
-        self.priv_row0 = int(priv_row0)
+        self.shared, self.priv_row0 = shared, int(priv_row0)
+        self.pair_tables, self.unary_tables = shared.pair_tables, shared.unary_tables
         pair_phi, unary_kind = self._pair_phi, self._unary_kind_list
         fb.pair_tables = self.pair_tables
         ptab = np.tile(np.array(pair_phi or [0], dtype=np.int64), (B, 1)) + 2 * self._dom_host[:, None]
@@ -136,28 +132,12 @@ class UserGraphTrainer:
         for r, (b_i, u) in enumerate(self._priv_rows):          # patched factors read their private row
             utab[b_i, u] = self.priv_row0 + r
         fb.unary_tab = torch.from_numpy(utab.astype(np.int32)).to(dev)
-        self._g_ee, self._g_ed = g_ee, g_ed
+        self._g_ee, self._g_ed = shared.g_ee[inst0:inst0 + B], shared.g_ed[inst0:inst0 + B]
+        self._lp = shared.lp[inst0:inst0 + B]
         self._marg = torch.empty(B, topo.n_vars, X, dtype=torch.float64, device=dev)
-        self._lp = torch.empty(B, dtype=torch.float64, device=dev)
-        n_stat = self.F_ee + self.F_ed + 2
-        self._rows = torch.empty(B, n_stat, dtype=torch.float64, device=dev)
-        # one buffer for the single all-reduce of a step: [global statistics | per-domain statistics [D][n_stat]]
-        self.stats_all = torch.zeros(n_stat * (1 + self.n_dom), dtype=torch.float64, device=dev)
-        self.stats = self.stats_all[:n_stat]
-        self.stats_dom = self.stats_all[n_stat:].view(self.n_dom, n_stat) if self.n_dom else None
-        # X = 64, shared pots: the potentials launch also writes every shared row's expected features (the gradient's gather
-        # table); only the private (plane-patched) rows still go through mlbp_unary_expectations_f64
-        self._expect_in_potentials = False
-        if X == 64 and topo.U and self.F_ee == 3 and self.F_ed == 6:
-            if self.shared is not None:                 # the set states the rows' (kind, column) and fills every row's expectations
-                fb._row_kind, fb._row_obs, fb._uexp = self.shared.row_kind, self.shared.row_obs, self.shared.uexp
-                fb._uexp_rows_done = int(self.shared.unary_tables.shape[0])
-                self._expect_in_potentials = True
-            else:
-                fb._derive_unary_rows()
-                if getattr(fb, '_row_kind', None) is not None and fb._row_kind is not False:
-                    self._expect_in_potentials = True
-                    fb._uexp_rows_done = self.n_shared_rows
+        if shared.expect and topo.U:        # the set states the rows' (kind, column) and fills every row's expected features
+            fb._row_kind, fb._row_obs, fb._uexp = shared.row_kind, shared.row_obs, shared.uexp
+            fb._uexp_rows_done = int(shared.unary_tables.shape[0])
 
     def _plan_patches(self, planes, unary_kind, obs, labels):
         """Host-side integer work: which (instance, en_de factor) pairs see a plane cell in their
@@ -192,60 +172,11 @@ class UserGraphTrainer:
         for d in sorted(set(row_dom)):
             lo = row_dom.index(d)
             self._priv_dom_ranges.append((d, lo, lo + row_dom.count(d)))
-        self._p_host = (off, ix, ik, iv, rgraph, rlabel, rbase)      # (a _SharedTables joins the sets' plans into one launch)
-        if self.n_priv:
-            dev = self.device
-            as_i32 = lambda a: torch.tensor(a, dtype=torch.int32, device=dev)          # noqa: E731
-            self._p_off, self._p_x, self._p_k = as_i32(off), as_i32(ix), as_i32(ik)
-            self._p_val = torch.tensor(iv, dtype=torch.float64, device=dev)
-            self._p_graph, self._p_label, self._p_base = as_i32(rgraph), as_i32(rlabel), as_i32(rbase)
-
-    def _patch_tables(self):
-        if self.n_priv:
-            priv = self.unary_tables[self.priv_row0:]
-            for d, lo, hi in self._priv_dom_ranges:          # one launch per domain present (its theta in the exponent)
-                theta = self.theta_dom_en_de[d] if self.n_dom else self.theta_en_de
-                _ffi.check(_ffi.lib.mlbp_patch_unary_tables_f64(
-                    self.unary_tables.data_ptr(), self._p_base[lo:].data_ptr(), self._p_off[lo:].data_ptr(), self._p_x.data_ptr(),
-                    self._p_k.data_ptr(), self._p_val.data_ptr(), theta.data_ptr(), hi - lo, self.spec['X'],
-                    priv[lo:].data_ptr(), _stream_ptr(self.device)))
-
-    def _patch_gradient(self):
-        if self.n_priv:
-            priv = self.unary_tables[self.priv_row0:]
-            _ffi.check(_ffi.lib.mlbp_patch_gradient_f64(
-                priv.data_ptr(), self._p_off.data_ptr(), self._p_x.data_ptr(), self._p_k.data_ptr(), self._p_val.data_ptr(),
-                self._p_graph.data_ptr(), self._p_label.data_ptr(), self.n_priv, self.spec['X'], self.F_ed,
-                self._g_ed.data_ptr(), _stream_ptr(self.device)))
+        self._patch_plan = (off, ix, ik, iv, rgraph, rlabel, rbase)      # (the set joins its trainers' plans and uploads them once)
 
     def build_potentials(self):
-        if self.shared is not None:
-            return self.shared.build([self])
-        return self._build_potentials_into(self.pair_tables, self.unary_tables, self.batch._uexp if self._expect_in_potentials else None)
-
-    def _build_potentials_into(self, pt, ut, ue, patch=True):
-        fb, X, st = self.batch, self.spec['X'], _stream_ptr(self.device)
-        # all three pots, for the global theta or for every domain's (its theta REPLACES the global one,
-        # train_mp.py:226-247), in ONE launch: pot_en_en / pot_en_en_w1 as pairwise tables and transposed rows, pot_en_de
-        # as transposed rows only
-        nd = max(self.n_dom, 1)
-        t_ee = self.theta_dom_en_en if self.n_dom else self.theta_en_en
-        t_ed = self.theta_dom_en_de if self.n_dom else self.theta_en_de
-        # ... and, X = 64 (ue given), every shared row's expected features (what the gradient gathers per unary factor,
-        # mlbp_unary_expectations_f64) out of the same launch: a row of pot^T IS a unary factor's table
-        jobs = (_ffi.PotentialsJob * 3)()
-        for j, (phi, th, F, cols, pot, pot_t, row0) in enumerate((
-                (fb.phi_en_en, t_ee, self.F_ee, X, pt[0].data_ptr(), ut[0:X].data_ptr(), 0),
-                (fb.phi_en_en_w1, t_ee, self.F_ee, X, pt[1].data_ptr(), ut[X:2 * X].data_ptr(), X),
-                (fb.phi_en_de, t_ed, self.F_ed, self.Vde, None, ut[2 * X:].data_ptr(), 2 * X))):
-            jobs[j].phi, jobs[j].theta, jobs[j].pot, jobs[j].pot_t = phi.data_ptr(), th.data_ptr(), pot, pot_t
-            jobs[j].theta_stride, jobs[j].pot_stride, jobs[j].pot_t_stride = F, 2 * X * X, self.rows_per_dom * X
-            jobs[j].rows, jobs[j].cols, jobs[j].F = X, cols, F
-            if ue is not None:
-                jobs[j].expect, jobs[j].expect_stride = ue[row0:].data_ptr(), self.rows_per_dom * 8
-        _ffi.check(_ffi.lib.mlbp_potentials_multi_f64(jobs, 3, nd, st))
-        if patch:
-            self._patch_tables()
+        """The pots under the current thetas, then this trainer's private rows (_SharedTables.build)."""
+        self.shared.build([self])
 
     def capture(self):
         """Records local_statistics() into a HIP graph (torch.cuda.CUDAGraph over the library's stream-ordered
@@ -266,77 +197,19 @@ class UserGraphTrainer:
         [sum_i grad_en_en (F_ee) | sum_i grad_en_de (F_ed) | sum_i log-posterior | instance count]."""
         if getattr(self, '_graph', None) is not None:
             self._graph.replay()
-            return self.stats_all if self.n_dom else self.stats
+            return self.shared.stats_all
         return self._local_statistics_eager()
 
     def _sweep_with_gradient(self):
         self.batch.sweep(self.roots[:self.n_sweeps_run], init=True, marginals=self._marg, gradient=(self._g_ee, self._g_ed),
                          keep_messages=False)
 
-    def _local_statistics_eager(self, select=None, potentials=True):
-        if potentials:
-            self.build_potentials()
+    def _local_statistics_eager(self):
+        if len(self.shared.trainers) != 1:
+            raise RuntimeError('a bucket trainer has no statistics of its own: its set sums every bucket (TiDirTrainer)')
+        self.build_potentials()
         self._sweep_with_gradient()
-        return self._statistics_after_sweep(select=select)
-
-    def _statistics_after_sweep(self, gradient_from_messages=False, select=None):
-        """Everything of the step behind the sweeps: gradient (when the sweep launch did not produce it: from the
-        messages in memory), the per-instance plane shares, log-posteriors, the batch sums.
-        select: optional device bool [B] -- only THESE instances enter the sums (a minibatch of a resident shard: every instance
-        is evaluated, the statistics of the others are left out; TiDirTrainer's masked minibatches)."""
-        fb = self.batch
-        if gradient_from_messages:
-            fb.gradient(self._g_ee, self._g_ed)
-        self._patch_gradient()
-        if select is not None:
-            return self._selected_statistics(select)
-        if not self.n_dom:          # [sum g_ee | sum g_ed | sum log-posterior | count]: log-posteriors and sums in one launch
-            _ffi.check(_ffi.lib.mlbp_step_statistics_f64(self._g_ee.data_ptr(), self.F_ee, self._g_ed.data_ptr(), self.F_ed,
-                                                         self._marg.data_ptr(), fb._labels.data_ptr(), self.topo.n_vars, fb.X, fb.B,
-                                                         self._lp.data_ptr(), self.stats.data_ptr(), _stream_ptr(self.device)))
-            return self.stats
-        _ffi.check(_ffi.lib.mlbp_log_posterior_f64(self._marg.data_ptr(), fb._labels.data_ptr(), fb.B, self.topo.n_vars,
-                                                   fb.X, self._lp.data_ptr(), _stream_ptr(self.device)))
-        r = self._rows
-        r[:, :self.F_ee] = self._g_ee
-        r[:, self.F_ee:self.F_ee + self.F_ed] = self._g_ed
-        r[:, -2] = self._lp
-        r[:, -1] = 1.0
-        fb.sum_rows(r, out=self.stats)
-        if self.n_dom:
-            _ffi.check(_ffi.lib.mlbp_segment_sum_rows_f64(r.data_ptr(), fb.B, r.shape[1], self._dom.data_ptr(), self.n_dom,
-                                                          self.stats_dom.data_ptr(), _stream_ptr(self.device)))
-            return self.stats_all
-        return self.stats
-
-    def _selected_statistics(self, select):
-        """The statistics buffer over the instances with select[b] set: per-instance rows [g_ee | g_ed | log-posterior | 1],
-        summed by segment -- the instance's domain when selected, a dump segment otherwise (mlbp_segment_sum_rows_f64, fixed
-        order)."""
-        fb = self.batch
-        st = _stream_ptr(self.device)
-        _ffi.check(_ffi.lib.mlbp_log_posterior_f64(self._marg.data_ptr(), fb._labels.data_ptr(), fb.B, self.topo.n_vars,
-                                                   fb.X, self._lp.data_ptr(), st))
-        r = self._rows
-        r[:, :self.F_ee] = self._g_ee
-        r[:, self.F_ee:self.F_ee + self.F_ed] = self._g_ed
-        r[:, -2] = self._lp
-        r[:, -1] = 1.0
-        nd = max(self.n_dom, 1)
-        if getattr(self, '_segsum', None) is None:
-            self._segsum = torch.zeros(nd + 1, r.shape[1], dtype=torch.float64, device=self.device)
-            self._seg = torch.empty(fb.B, dtype=torch.int32, device=self.device)
-            self._dump = torch.full((fb.B,), nd, dtype=torch.int32, device=self.device)
-            self._zero_seg = torch.zeros(fb.B, dtype=torch.int32, device=self.device)
-        torch.where(select, self._dom if self.n_dom else self._zero_seg, self._dump, out=self._seg)
-        _ffi.check(_ffi.lib.mlbp_segment_sum_rows_f64(r.data_ptr(), fb.B, r.shape[1], self._seg.data_ptr(), nd + 1,
-                                                      self._segsum.data_ptr(), st))
-        if self.n_dom:
-            self.stats_dom.copy_(self._segsum[:nd])
-            torch.sum(self._segsum[:nd], dim=0, out=self.stats)
-            return self.stats_all
-        self.stats.copy_(self._segsum[0])
-        return self.stats
+        return self.shared.statistics()
 
     def step(self, learning_rate, reg_param, reg_param_ua_scale=1.0):
         """One synchronous optimisation step over ALL ranks' shards: returns (mean log-posterior,
@@ -344,11 +217,8 @@ class UserGraphTrainer:
         `--reg_param / N` (train_mp.py:160); with domains the per-domain thetas take their own instances' steps
         with the regulariser scaled by reg_param_ua_scale (train_mp.py:384-396, 413-415)."""
         stats = mdist.all_reduce_sum_(self.local_statistics())
+        update_thetas(self, stats, learning_rate, reg_param, reg_param_ua_scale)
         n_stat = self.F_ee + self.F_ed + 2
-        apply_update(self.theta_en_en, self.theta_en_de, stats[:n_stat], self.F_ee, self.F_ed, learning_rate, reg_param)
-        if self.n_dom:
-            apply_domain_update(self.theta_dom_en_en, self.theta_dom_en_de, stats[n_stat:].view(self.n_dom, n_stat),
-                                self.F_ee, self.F_ed, learning_rate, reg_param * reg_param_ua_scale)
         return float(stats[n_stat - 2].item() / stats[n_stat - 1].item()), self.theta_en_en, self.theta_en_de
 
     def predict(self, top=50, with_logs=False):
@@ -400,141 +270,179 @@ def apply_domain_update(theta_dom_en_en, theta_dom_en_de, stats_dom, F_ee, F_ed,
     return theta_dom_en_en, theta_dom_en_de
 
 
+def update_thetas(owner, stats, learning_rate, reg_param, reg_param_ua_scale):
+    """The step of a trainer's thetas (owner: a UserGraphTrainer or a TiDirTrainer) from its fused statistics buffer
+    [global statistics | per-domain statistics [D][F_ee+F_ed+2]]: apply_update, then apply_domain_update when the buffer
+    carries per-domain rows."""
+    F_ee, F_ed = len(owner.theta_en_en), len(owner.theta_en_de)
+    n = F_ee + F_ed + 2
+    apply_update(owner.theta_en_en, owner.theta_en_de, stats[:n], F_ee, F_ed, learning_rate, reg_param)
+    if stats.numel() > n:
+        apply_domain_update(owner.theta_dom_en_en, owner.theta_dom_en_de, stats[n:].view(-1, n), F_ee, F_ed, learning_rate,
+                            reg_param * reg_param_ua_scale)
+
+
 class _SharedTables:
-    """What the bucket trainers of one set have in common, held ONCE: the pots under the global theta (or every domain's) as
-    pairwise tables and as transposed rows (train_mp.py:220-255 builds them per instance; they depend on theta alone), behind
-    the shared rows every bucket's private plane-patched rows, the rows' expected features, and the per-instance gradient rows
-    of all buckets.  One potentials launch and one expectations launch per step serve every sentence shape."""
+    """The only owner of per-step device state, for one trainer (a standalone UserGraphTrainer) or the bucket trainers of one
+    TiDirTrainer: the pots under the global theta (or every domain's) as pairwise tables and as transposed rows
+    (train_mp.py:220-255 builds them per instance; they depend on theta alone), behind the shared rows every trainer's private
+    plane-patched rows and their joined patch plan, the rows' expected features, the per-instance gradient rows and
+    log-posteriors, and the statistics buffer.  One potentials launch and one expectations launch per step serve every sentence
+    shape."""
 
     def __init__(self, trainers):
         t0 = trainers[0]
         self.trainers = list(trainers)
-        dev, X = t0.device, t0.spec['X']
-        nd = max(t0.n_dom, 1)
+        self.device = dev = t0.device
+        self.X = X = t0.spec['X']
+        self.F_ee, self.F_ed, self.n_dom = t0.F_ee, t0.F_ed, t0.n_dom
+        nd = max(self.n_dom, 1)
         self.n_shared_rows = t0.n_shared_rows
-        n_priv = sum(t.n_priv for t in trainers)
+        self.n_priv = n_priv = sum(t.n_priv for t in trainers)
+        self.n_inst = n_inst = sum(t.batch.B for t in trainers)
         self.pair_tables = torch.empty(2 * nd, X, X, dtype=torch.float64, device=dev)
         self.unary_tables = torch.empty(self.n_shared_rows + n_priv, X, dtype=torch.float64, device=dev)
-        n_inst = sum(t.batch.B for t in trainers)
-        self.g_ee = torch.empty(n_inst, t0.F_ee, dtype=torch.float64, device=dev)
-        self.g_ed = torch.empty(n_inst, t0.F_ed, dtype=torch.float64, device=dev)
-        # every row's (phi selector, observed column): shared rows by their place in the layout, private rows their base row's
-        rk = np.zeros(self.n_shared_rows + n_priv, dtype=np.int32)
-        ro = np.zeros(self.n_shared_rows + n_priv, dtype=np.int32)
-        for d in range(nd):
-            o = d * t0.rows_per_dom
-            rk[o + X:o + 2 * X] = 1; rk[o + 2 * X:o + t0.rows_per_dom] = 2
-            ro[o:o + X] = np.arange(X); ro[o + X:o + 2 * X] = np.arange(X); ro[o + 2 * X:o + t0.rows_per_dom] = np.arange(t0.Vde)
-        row, inst = self.n_shared_rows, 0
-        self._plans = []
-        for t in trainers:
-            rk[row:row + t.n_priv] = 2
-            ro[row:row + t.n_priv] = np.asarray(t._priv_cols, dtype=np.int32).reshape(-1)
-            self._plans.append((row, inst))
-            row += t.n_priv; inst += t.batch.B
-        self.row_kind = torch.from_numpy(rk).to(dev)
-        self.row_obs = torch.from_numpy(ro).to(dev)
-        self.uexp = torch.zeros(self.n_shared_rows + n_priv, 8, dtype=torch.float64, device=dev)
-        for t, (row, inst) in zip(trainers, self._plans):
-            t.shared = self
-            t.finish_shared(row, self.g_ee[inst:inst + t.batch.B], self.g_ed[inst:inst + t.batch.B])
-        self.n_inst, self.n_priv, self.n_dom = n_inst, n_priv, t0.n_dom
-        self.F_ee, self.F_ed, self.X = t0.F_ee, t0.F_ed, X
-        # the buckets' patch plans joined: one mlbp_patch_unary_tables_f64 (one theta: no per-domain thetas) and one
-        # mlbp_patch_gradient_f64 launch for every sentence shape
+        self.g_ee = torch.empty(n_inst, self.F_ee, dtype=torch.float64, device=dev)
+        self.g_ed = torch.empty(n_inst, self.F_ed, dtype=torch.float64, device=dev)
+        self.lp = torch.empty(n_inst, dtype=torch.float64, device=dev)
+        # where every trainer's private rows and instances start, and the trainers' patch plans joined (item offsets, base rows
+        # and graphs absolute): one upload for the set
+        starts, row, inst = [], self.n_shared_rows, 0
         off, ix, ik, iv, rg, rl, rb = [0], [], [], [], [], [], []
-        for t, (row, inst) in zip(trainers, self._plans):
-            o, x, k, v, g, l, b = t._p_host
+        for t in trainers:
+            starts.append((row, inst))
+            o, x, k, v, g, l, b = t._patch_plan
             off += [len(ix) + e for e in o[1:]]
             ix += x; ik += k; iv += v; rl += l; rb += b
             rg += [inst + gi for gi in g]
+            row += t.n_priv; inst += t.batch.B
         if n_priv:
             as_i32 = lambda a: torch.tensor(a, dtype=torch.int32, device=dev)          # noqa: E731
             self._p_off, self._p_x, self._p_k = as_i32(off), as_i32(ix), as_i32(ik)
             self._p_val = torch.tensor(iv, dtype=torch.float64, device=dev)
             self._p_graph, self._p_label, self._p_base = as_i32(rg), as_i32(rl), as_i32(rb)
-        # per-instance outputs of the whole set and the group table of mlbp_log_posterior_groups_f64
-        self.lp = torch.empty(n_inst, dtype=torch.float64, device=dev)
+        # X = 64, shared pots: the potentials launch also writes every shared row's expected features (the gradient's gather
+        # table), build() those of the private rows -- decided once, for every trainer of the set
+        self.expect = X == 64 and (self.F_ee, self.F_ed) == (3, 6) and any(t.topo.U for t in trainers)
+        if self.expect:
+            # every row's (phi selector, observed column): shared rows by their place in the layout, private rows their base row's
+            rk = np.zeros(self.n_shared_rows + n_priv, dtype=np.int32)
+            ro = np.zeros(self.n_shared_rows + n_priv, dtype=np.int32)
+            for d in range(nd):
+                o = d * t0.rows_per_dom
+                rk[o + X:o + 2 * X] = 1; rk[o + 2 * X:o + t0.rows_per_dom] = 2
+                ro[o:o + X] = np.arange(X); ro[o + X:o + 2 * X] = np.arange(X); ro[o + 2 * X:o + t0.rows_per_dom] = np.arange(t0.Vde)
+            for t, (row, _) in zip(trainers, starts):
+                rk[row:row + t.n_priv] = 2
+                ro[row:row + t.n_priv] = np.asarray(t._priv_cols, dtype=np.int32).reshape(-1)
+            self.row_kind = torch.from_numpy(rk).to(dev)
+            self.row_obs = torch.from_numpy(ro).to(dev)
+            self.uexp = torch.zeros(self.n_shared_rows + n_priv, 8, dtype=torch.float64, device=dev)
+        for t, (row, inst) in zip(trainers, starts):
+            t._join(self, row, inst)
+        # one buffer for the single all-reduce of a step: [global statistics | per-domain statistics [D][n_stat]]
         n_stat = self.F_ee + self.F_ed + 2
-        self.rows = torch.empty(n_inst, n_stat, dtype=torch.float64, device=dev)
         self.stats_all = torch.zeros(n_stat * (1 + self.n_dom), dtype=torch.float64, device=dev)
+        # the group table of mlbp_log_posterior_groups_f64
         gt = np.zeros(len(trainers), dtype=[('m', '<u8'), ('l', '<u8'), ('nv', '<i4'), ('B', '<i4'), ('start', '<i8')])
-        for i, (t, (row, inst)) in enumerate(zip(trainers, self._plans)):
+        for i, (t, (row, inst)) in enumerate(zip(trainers, starts)):
             gt[i] = (t._marg.data_ptr(), t.batch._labels.data_ptr(), t.topo.n_vars, t.batch.B, inst)
         self._groups = torch.from_numpy(gt.view(np.uint8).reshape(-1).copy()).to(dev)
-        nd = max(self.n_dom, 1)
-        self._segsum = torch.zeros(nd + 1, n_stat, dtype=torch.float64, device=dev)
-        self._seg = torch.empty(n_inst, dtype=torch.int32, device=dev)
-        self._dump = torch.full((n_inst,), nd, dtype=torch.int32, device=dev)
-        self._seg0 = torch.zeros(n_inst, dtype=torch.int32, device=dev)
-        if self.n_dom:
+        if self.n_dom:      # per-instance rows summed by segment: the instance's domain, or a dump segment when not selected
+            self.rows = torch.empty(n_inst, n_stat, dtype=torch.float64, device=dev)
             self._dom = torch.cat([t._dom for t in trainers])
-
-    def patch_gradient(self):
-        if self.n_priv:
-            priv = self.unary_tables[self.n_shared_rows:]
-            _ffi.check(_ffi.lib.mlbp_patch_gradient_f64(
-                priv.data_ptr(), self._p_off.data_ptr(), self._p_x.data_ptr(), self._p_k.data_ptr(), self._p_val.data_ptr(),
-                self._p_graph.data_ptr(), self._p_label.data_ptr(), self.n_priv, self.X, self.F_ed,
-                self.g_ed.data_ptr(), _stream_ptr(self.trainers[0].device)))
+            self._segsum = torch.zeros(nd + 1, n_stat, dtype=torch.float64, device=dev)
+            self._seg = torch.empty(n_inst, dtype=torch.int32, device=dev)
+            self._dump = torch.full((n_inst,), nd, dtype=torch.int32, device=dev)
 
     def statistics(self, select=None):
         """[sum g_ee | sum g_ed | sum log-posterior | count] (then the per-domain rows) over every instance of the set -- or over
         the instances select = (key, value) picks: key device int32 [n_inst], value device int32 [1], instance i counts when
-        key[i] == value (a masked minibatch) -- behind the sweeps of all buckets: the planes' gradient share, the
-        log-posteriors of every group and the sums, one launch each."""
-        st = _stream_ptr(self.trainers[0].device)
-        self.patch_gradient()
+        key[i] == value (a masked minibatch) -- behind the sweeps of all trainers: the planes' gradient share, the
+        log-posteriors of every group and the sums, one launch each (one for the last two with a single trainer, every
+        instance and no domains)."""
+        st = _stream_ptr(self.device)
+        if self.n_priv:
+            _ffi.check(_ffi.lib.mlbp_patch_gradient_f64(
+                self.unary_tables[self.n_shared_rows:].data_ptr(), self._p_off.data_ptr(), self._p_x.data_ptr(), self._p_k.data_ptr(),
+                self._p_val.data_ptr(), self._p_graph.data_ptr(), self._p_label.data_ptr(), self.n_priv, self.X, self.F_ed,
+                self.g_ed.data_ptr(), st))
+        if len(self.trainers) == 1 and select is None and not self.n_dom:
+            t = self.trainers[0]
+            _ffi.check(_ffi.lib.mlbp_step_statistics_f64(self.g_ee.data_ptr(), self.F_ee, self.g_ed.data_ptr(), self.F_ed,
+                                                         t._marg.data_ptr(), t.batch._labels.data_ptr(), t.topo.n_vars, self.X,
+                                                         self.n_inst, self.lp.data_ptr(), self.stats_all.data_ptr(), st))
+            return self.stats_all
         _ffi.check(_ffi.lib.mlbp_log_posterior_groups_f64(self._groups.data_ptr(), len(self.trainers), self.n_inst, self.X, self.lp.data_ptr(), st))
-        n_stat = self.F_ee + self.F_ed + 2
         if not self.n_dom:
             key, value = (None, None) if select is None else (select[0].data_ptr(), select[1].data_ptr())
             _ffi.check(_ffi.lib.mlbp_select_sum_rows_cat_f64(self.g_ee.data_ptr(), self.F_ee, self.g_ed.data_ptr(), self.F_ed, self.lp.data_ptr(), 1,
                                                              self.n_inst, key, value, 1, self.stats_all.data_ptr(), st))
             return self.stats_all
+        n_stat, nd = self.F_ee + self.F_ed + 2, self.n_dom
         r = self.rows
         r[:, :self.F_ee] = self.g_ee
         r[:, self.F_ee:self.F_ee + self.F_ed] = self.g_ed
         r[:, -2] = self.lp
         r[:, -1] = 1.0
-        nd = max(self.n_dom, 1)
-        code = self._dom if self.n_dom else self._seg0
+        code = self._dom
         if select is not None:
             torch.where(select[0] == select[1], code, self._dump, out=self._seg)
             code = self._seg
         _ffi.check(_ffi.lib.mlbp_segment_sum_rows_f64(r.data_ptr(), self.n_inst, n_stat, code.data_ptr(), nd + 1, self._segsum.data_ptr(), st))
-        if self.n_dom:
-            self.stats_all[n_stat:].view(nd, n_stat).copy_(self._segsum[:nd])
-            torch.sum(self._segsum[:nd], dim=0, out=self.stats_all[:n_stat])
-        else:
-            self.stats_all.copy_(self._segsum[0])
+        self.stats_all[n_stat:].view(nd, n_stat).copy_(self._segsum[:nd])
+        torch.sum(self._segsum[:nd], dim=0, out=self.stats_all[:n_stat])
         return self.stats_all
 
     def build(self, trainers=None):
         """The pots (and the shared rows' expected features) under the current thetas, then the private rows of `trainers`
         (default: all) and THEIR expected features."""
-        t0 = self.trainers[0]
-        expect = t0._expect_in_potentials
-        t0._build_potentials_into(self.pair_tables, self.unary_tables, self.uexp if expect else None, patch=False)
+        self._potentials()
+        t0, X, st = self.trainers[0], self.X, _stream_ptr(self.device)
+
+        def patch(r0, n, theta):        # private rows r0 .. r0 + n of the joined plan
+            _ffi.check(_ffi.lib.mlbp_patch_unary_tables_f64(
+                self.unary_tables.data_ptr(), self._p_base[r0:].data_ptr(), self._p_off[r0:].data_ptr(), self._p_x.data_ptr(),
+                self._p_k.data_ptr(), self._p_val.data_ptr(), theta.data_ptr(), n, X,
+                self.unary_tables[self.n_shared_rows + r0:].data_ptr(), st))
         trs = self.trainers if trainers is None else trainers
         if trainers is None and self.n_priv and not self.n_dom:      # every private row of every shape in one launch
-            priv = self.unary_tables[self.n_shared_rows:]
-            _ffi.check(_ffi.lib.mlbp_patch_unary_tables_f64(
-                self.unary_tables.data_ptr(), self._p_base.data_ptr(), self._p_off.data_ptr(), self._p_x.data_ptr(), self._p_k.data_ptr(),
-                self._p_val.data_ptr(), t0.theta_en_de.data_ptr(), self.n_priv, self.X, priv.data_ptr(), _stream_ptr(t0.device)))
+            patch(0, self.n_priv, t0.theta_en_de)
         else:
             for t in trs:
-                t._patch_tables()
-        if not expect:
+                for d, lo, hi in t._priv_dom_ranges:        # one launch per domain present (its theta in the exponent)
+                    patch(t.priv_row0 - self.n_shared_rows + lo, hi - lo, t.theta_dom_en_de[d] if self.n_dom else t.theta_en_de)
+        if not self.expect:
             return
         spans = [(self.n_shared_rows, int(self.unary_tables.shape[0]))] if trainers is None else [(t.priv_row0, t.priv_row0 + t.n_priv) for t in trs]
         fb = t0.batch
         for lo, hi in spans:
             if hi > lo:
                 _ffi.check(_ffi.lib.mlbp_unary_expectations_f64(
-                    self.unary_tables[lo:].data_ptr(), hi - lo, fb.X, self.row_kind[lo:].data_ptr(), self.row_obs[lo:].data_ptr(),
-                    fb._phi_t[0].data_ptr(), fb._phi_t[1].data_ptr(), fb._phi_t[2].data_ptr(), t0.F_ee, t0.F_ed, t0.Vde,
-                    self.uexp[lo:].data_ptr(), _stream_ptr(t0.device)))
+                    self.unary_tables[lo:].data_ptr(), hi - lo, X, self.row_kind[lo:].data_ptr(), self.row_obs[lo:].data_ptr(),
+                    fb._phi_t[0].data_ptr(), fb._phi_t[1].data_ptr(), fb._phi_t[2].data_ptr(), self.F_ee, self.F_ed, t0.Vde,
+                    self.uexp[lo:].data_ptr(), st))
+
+    def _potentials(self):
+        """All three pots, for the global theta or for every domain's (its theta REPLACES the global one, train_mp.py:226-247),
+        in ONE launch: pot_en_en / pot_en_en_w1 as pairwise tables and transposed rows, pot_en_de as transposed rows only --
+        and, self.expect, every shared row's expected features (what the gradient gathers per unary factor,
+        mlbp_unary_expectations_f64) out of the same launch: a row of pot^T IS a unary factor's table."""
+        t0, X = self.trainers[0], self.X
+        fb, pt, ut, rpd = t0.batch, self.pair_tables, self.unary_tables, t0.rows_per_dom
+        t_ee = t0.theta_dom_en_en if self.n_dom else t0.theta_en_en
+        t_ed = t0.theta_dom_en_de if self.n_dom else t0.theta_en_de
+        jobs = (_ffi.PotentialsJob * 3)()
+        for j, (phi, th, F, cols, pot, pot_t, row0) in enumerate((
+                (fb.phi_en_en, t_ee, self.F_ee, X, pt[0].data_ptr(), ut[0:X].data_ptr(), 0),
+                (fb.phi_en_en_w1, t_ee, self.F_ee, X, pt[1].data_ptr(), ut[X:2 * X].data_ptr(), X),
+                (fb.phi_en_de, t_ed, self.F_ed, t0.Vde, None, ut[2 * X:].data_ptr(), 2 * X))):
+            jobs[j].phi, jobs[j].theta, jobs[j].pot, jobs[j].pot_t = phi.data_ptr(), th.data_ptr(), pot, pot_t
+            jobs[j].theta_stride, jobs[j].pot_stride, jobs[j].pot_t_stride = F, 2 * X * X, rpd * X
+            jobs[j].rows, jobs[j].cols, jobs[j].F = X, cols, F
+            if self.expect:
+                jobs[j].expect, jobs[j].expect_stride = self.uexp[row0:].data_ptr(), rpd * 8
+        _ffi.check(_ffi.lib.mlbp_potentials_multi_f64(jobs, 3, max(self.n_dom, 1), _stream_ptr(self.device)))
 
 
 class _BucketSet:
@@ -567,7 +475,7 @@ class _BucketSet:
                     planes.append(cells)
             self.trainers[key] = UserGraphTrainer(b['spec'], b['var_labels'], b['unary_obs'], o.phi_ee, o.phi_w1, o.phi_ed_t,
                                                   o.theta_en_en, o.theta_en_de, device=o.device, sweeps=o.sweeps, roots=roots,
-                                                  planes=planes, skip_unchanged=o.skip_unchanged, shared=True,
+                                                  planes=planes, skip_unchanged=o.skip_unchanged, member=True,
                                                   features_of=next(iter(self.trainers.values()), None), **extra)
         self.shared = _SharedTables(list(self.trainers.values())) if self.trainers else None
 
@@ -575,8 +483,8 @@ class _BucketSet:
         """Adds the set's statistics to `stats`.  grouped_sweeps: the sweeps of ALL sentence shapes with pairwise factors
         in one launch sequence (batch.sweep_groups -> mlbp_sweep_groups_f64: every bucket its own topology and roots;
         the shared-table kernels take a group table) instead of one launch sequence per bucket; 'auto' groups whenever
-        two or more buckets qualify.  select: optional device bool over the set's instances (bucket order): only the selected
-        ones enter the sums (masked minibatches).  One potentials launch in front of the sweeps and three launches behind them
+        two or more buckets qualify.  select: optional (key, value) -- key device int32 over the set's instances (bucket order),
+        value device int32 [1]: only the instances with key == value enter the sums (masked minibatches).  One potentials launch in front of the sweeps and three launches behind them
         (planes' gradient share, log-posteriors, sums) serve every shape."""
         trs = list(self.trainers.values())
         if not trs:
@@ -703,8 +611,7 @@ class TiDirTrainer:
         """Starts from a params file (train_mp.py:528-542): '<path><ext>' with the adapt mode's extension first, then
         '<path>'.  Global thetas, and every adapted domain's thetas the file holds for a domain this run knows."""
         from . import tidir
-        ext = {'user': '.user_adapt', 'experience': '.exp_adapt', None: ''}[self.adapt]
-        import os
+        ext = ADAPT_EXT[self.adapt]
         chosen = path + ext if os.path.exists(path + ext) else path
         een, eet, edn, edt, d2t = tidir.read_params(chosen)
         if list(een) != list(tidir.EE_NAMES) or list(edn) != list(tidir.ED_NAMES):
@@ -755,11 +662,8 @@ class TiDirTrainer:
     def _update(self, learning_rate, reg_param):
         """One all-reduce of the fused buffer (global and per-domain statistics), one update of every theta."""
         mdist.all_reduce_sum_(self.stats)
-        n, F_ee, F_ed = self.n_stat, len(self.theta_en_en), len(self.theta_en_de)
-        apply_update(self.theta_en_en, self.theta_en_de, self.stats[:n], F_ee, F_ed, learning_rate, reg_param)
-        if self.domains:
-            apply_domain_update(self.theta_dom_en_en, self.theta_dom_en_de, self.stats[n:].view(len(self.domains), n), F_ee, F_ed,
-                                learning_rate, reg_param * self.reg_param_ua_scale)
+        update_thetas(self, self.stats, learning_rate, reg_param, self.reg_param_ua_scale)
+        n = self.n_stat
         return float(self.stats[n - 2].item()), float(self.stats[n - 1].item())
 
     def epoch_order(self, epoch):
@@ -817,12 +721,8 @@ class TiDirTrainer:
     def _update_on_device(self, learning_rate, reg_param):
         """_update() without its host read-back: all-reduce, theta updates, the running [sum log-posterior, count]."""
         mdist.all_reduce_sum_(self.stats)
-        n, F_ee, F_ed = self.n_stat, len(self.theta_en_en), len(self.theta_en_de)
-        apply_update(self.theta_en_en, self.theta_en_de, self.stats[:n], F_ee, F_ed, learning_rate, reg_param)
-        if self.domains:
-            apply_domain_update(self.theta_dom_en_en, self.theta_dom_en_de, self.stats[n:].view(len(self.domains), n), F_ee, F_ed,
-                                learning_rate, reg_param * self.reg_param_ua_scale)
-        self._acc += self.stats[n - 2:n]
+        update_thetas(self, self.stats, learning_rate, reg_param, self.reg_param_ua_scale)
+        self._acc += self.stats[self.n_stat - 2:self.n_stat]
 
     def epoch(self, learning_rate, reg_param):
         """One pass over the instances; returns the mean log-posterior (at the thetas each instance was evaluated under)."""
@@ -865,7 +765,7 @@ class TiDirTrainer:
                 epochs * ((self.n_total + self.minibatch - 1) // self.minibatch) >= 3:
             self.capture_masked()
         if save_params:
-            save_params = save_params + {'user': '.user_adapt', 'experience': '.exp_adapt', None: ''}[self.adapt]
+            save_params = save_params + ADAPT_EXT[self.adapt]
         history = []
         tuner = self.tune_evaluator(tune) if isinstance(tune, str) else tune
         self.tune_history = []
@@ -891,6 +791,7 @@ class TiDirTrainer:
         from . import tidir
         lp, counts = 0.0, np.zeros(4, dtype=np.int64)
         blocks = {}
+        ext = ADAPT_EXT[self.adapt]
         for key, tr in self.trainers.items():
             l, idx, logs, c, logm, label_logs = tr.predict(top=min(50, tr.batch.X), with_logs=True)
             lp += float(l.sum()); counts += np.array(c)
@@ -904,7 +805,6 @@ class TiDirTrainer:
         n = self._shard[1] - self._shard[0]
         if save_predictions:
             import codecs
-            ext = {'user': '.user_adapt', 'experience': '.exp_adapt', None: ''}[self.adapt]
             tail = '.rank%d' % self.rank if self.world > 1 else ''
             with codecs.open(save_predictions + ext + tail, 'w', 'utf8') as w, codecs.open(save_predictions + ext + '.dist' + tail, 'w', 'utf8') as wd:
                 for i in sorted(blocks):
@@ -918,7 +818,6 @@ class TiDirTrainer:
             # get_acc.py read them: the shards are contiguous, so rank order is instance order.  (The all-reduce above is the
             # barrier: every rank has closed its files.)
             import shutil
-            ext = {'user': '.user_adapt', 'experience': '.exp_adapt', None: ''}[self.adapt]
             if self.rank == 0:
                 for suffix in ('', '.dist'):
                     with open(save_predictions + ext + suffix, 'wb') as out:

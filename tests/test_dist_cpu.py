@@ -44,7 +44,7 @@ def _worker(rank, world, port, n_items, q):
     spec = C.user_spec(6, [0, 2, 3], 8, 8, seed=3)
     inputs = C.make_inputs(spec, 11)
     lo, hi = mdist.shard_range(n_items, rank, world)
-    # the trainer's fused buffer (train.UserGraphTrainer.stats_all): [global statistics | per-domain statistics [D][n_stat]],
+    # the trainer's fused buffer (train._SharedTables.stats_all): [global statistics | per-domain statistics [D][n_stat]],
     # ONE all-reduce for both halves; item i belongs to domain i % D
     n_stat, D = C.F_EE + C.F_ED + 2, 3
     fused = torch.zeros(n_stat * (1 + D), dtype=torch.float64)
