@@ -17,6 +17,7 @@ Pairwise tables are the two shared pots (`pot_en_en`, `pot_en_en_w1`) referenced
 table-index indirection; a unary factor's table is a COLUMN of a pot (LBP.py:702-703), read as a
 row of the transposed pot the potentials kernel also writes -- no per-instance copies.
 """
+import functools
 import os
 
 import numpy as np
@@ -199,6 +200,12 @@ class UserGraphTrainer:
             self._graph.replay()
             return self.shared.stats_all
         return self._local_statistics_eager()
+
+    @functools.cached_property
+    def shared_table_form(self):
+        """True when this trainer's sweeps qualify for the shared-table matrix-core kernels: X = 64 and a program the
+        library's planner accepts (at most 16 pairwise factors, topology.plan's shared_ok)."""
+        return self.batch.X == 64 and self.topo.P >= 1 and self.topo.plan(self.roots[:self.n_sweeps_run])['shared_ok'] == 1
 
     def _sweep_with_gradient(self):
         self.batch.sweep(self.roots[:self.n_sweeps_run], init=True, marginals=self._marg, gradient=(self._g_ee, self._g_ed),
@@ -490,7 +497,9 @@ class _BucketSet:
         if not trs:
             return
         self.shared.build()                           # ONE potentials launch (and one expectations launch) for every shape
-        together = [tr for tr in trs if tr.topo.P >= 1 and tr.batch.X == 64] if grouped_sweeps else []
+        # only shapes the shared-table kernels take: the library declines a grouped call as a whole when one group does not
+        # qualify, so a single K7+ bucket in it would move every other bucket off the matrix cores
+        together = [tr for tr in trs if tr.shared_table_form] if grouped_sweeps else []
         if len(together) < 2 and grouped_sweeps is not True:
             together = []
         if together:

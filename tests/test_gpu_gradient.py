@@ -7,7 +7,7 @@ import pytest
 
 import cases as C
 from conftest import load_golden
-from helpers import batch_tables, case_inputs
+from helpers import batch_tables, case_inputs, tidir_oracle_graph, write_tidir
 from oracle import lbp_oracle as O
 
 torch = pytest.importorskip('torch')
@@ -305,7 +305,6 @@ def test_tidir_trainer_epochs_and_predictions(tmp_path):
     """End to end over files: three epochs of TiDirTrainer (all shape buckets, shared theta) against
     the same loop driven by the oracle; params file written in the reference's format; prediction
     counts against the oracle's precision counts."""
-    import copy
     from macaronicusermodeling_amd import tidir
     from macaronicusermodeling_amd.train import TiDirTrainer
     paths = tidir.synthesize(str(tmp_path), n_instances=24, X=64, Vde=64, sent_len=(4, 6), n_predicted=(1, 3), seed=9)
@@ -318,29 +317,13 @@ def test_tidir_trainer_epochs_and_predictions(tmp_path):
     phi_ee, phi_w1, phi_ed = tidir.load_features(paths['phi_pmi'], paths['phi_pmi_w1'], paths['phi_ed'], paths['phi_ped'])
     th_ee, th_ed = np.zeros((1, 3)), np.zeros((1, 6))
 
-    feat = {'correct': 2, 'full_history': 3, 'hit_history': 4}
-
     def oracle_pass(th_ee, th_ed, want_counts=False):
-        pot_ee = np.exp(phi_ee.dot(th_ee.T).reshape(64, 64)); pot_w1 = np.exp(phi_w1.dot(th_ee.T).reshape(64, 64))
         tot = np.zeros(11); counts = np.zeros(4, dtype=np.int64); n_cells = 0
         for key, b in sorted(tt.buckets.items()):
-            unary = [f for f in sorted(b['spec']['factors'], key=lambda f: f['id']) if len(f['vars']) == 1]
-            roots = [key[1][i % len(key[1])] for i in range(3)]
             for i in range(len(b['rows'])):
-                s = copy.deepcopy(b['spec'])
-                s['labels'] = [int(v) for v in b['var_labels'][i]]
-                for u, f in enumerate(unary):
-                    s['factors'][f['id']]['observed_dim'] = int(b['unary_obs'][i, u])
-                # the reference writes the three planes into phi_en_de for this instance (train_mp.py:178-217)
-                phi_i = phi_ed.copy()
-                for name, k in feat.items():
-                    plane = np.zeros((64, 64))
-                    for ci, cj, cv in b['rows'][i]['planes'][name]:
-                        plane[ci, cj] += cv; n_cells += 1
-                    phi_i[:, :, k] = plane
-                inputs = dict(phi_en_en=phi_ee, phi_en_en_w1=phi_w1, phi_en_de=phi_i, theta_en_en=th_ee, theta_en_de=th_ed,
-                              pot_en_en=pot_ee, pot_en_en_w1=pot_w1, pot_en_de=np.exp(phi_i.dot(th_ed.T).reshape(64, 64)))
-                g = O.Graph(s); msgs = O.init_messages(g)
+                g, inputs, roots, cells = tidir_oracle_graph(key, b, i, phi_ee, phi_w1, phi_ed, th_ee, th_ed)
+                n_cells += cells
+                msgs = O.init_messages(g)
                 O.treelike_inference(g, inputs, msgs, 3, roots, O.has_loops(g, roots[0]))
                 ee, ed = O.unregularized_gradient(g, inputs, msgs)
                 tot[:3] += ee.reshape(-1); tot[3:9] += ed.reshape(-1); tot[9] += O.log_posterior(g, msgs); tot[10] += 1
@@ -870,17 +853,6 @@ def test_two_threads_run_large_state_steps_on_two_streams():
         assert torch.equal(out[k], alone[k])
 
 
-def _write_tidir(gold, d):
-    import os
-    paths = {k: os.path.join(d, k) for k in ('ti', 'vocab.en', 'vocab.de', 'phi.pmi', 'phi.pmi_w1', 'phi.ed', 'phi.ped')}
-    open(paths['ti'], 'w', encoding='utf8').write('\n'.join(gold['instances']) + '\n')
-    open(paths['vocab.en'], 'w', encoding='utf8').write('\n'.join(gold['vocab_en']) + '\n')
-    open(paths['vocab.de'], 'w', encoding='utf8').write('\n'.join(gold['vocab_de']) + '\n')
-    for k, name in (('phi.pmi', 'phi_pmi'), ('phi.pmi_w1', 'phi_pmi_w1'), ('phi.ed', 'phi_ed'), ('phi.ped', 'phi_ped')):
-        np.savetxt(paths[k], np.array(gold[name]))
-    return paths
-
-
 def _batch_gold():
     import json
     import os
@@ -907,7 +879,7 @@ def test_minibatched_shuffled_epoch_equals_the_reference_sequence(tmp_path):
     its instances' statistics -- eager, and replayed from ONE HIP graph) and 'rebuild' (bucket trainers built per minibatch)."""
     gold = _batch_gold()
     mb = gold['minibatch']
-    paths = _write_tidir(gold, str(tmp_path))
+    paths = write_tidir(gold, str(tmp_path))
     for grouped, mode, graph in ((True, 'rebuild', False), (False, 'rebuild', False), (True, 'masked', False), (False, 'masked', False),
                                  (True, 'masked', True)):
         tt = _trainer(paths, gold, minibatch=mb['size'], shuffle_seed=3, grouped_sweeps=grouped, minibatch_mode=mode)
@@ -953,7 +925,7 @@ def test_batched_prediction_files_equal_the_reference_text(tmp_path):
     returned for the same 12 instances (tidir_batch_reference.json['predictions']), and the precision counts and mean
     log-posterior the sums of its per-instance values."""
     gold = _batch_gold()
-    paths = _write_tidir(gold, str(tmp_path))
+    paths = write_tidir(gold, str(tmp_path))
     tt = _trainer(paths, gold)
     out = str(tmp_path / 'pred')
     mean_lp, counts = tt.predict(save_predictions=out)
@@ -969,7 +941,7 @@ def test_resume_from_a_params_file(tmp_path, adapt):
     """--load_params (train_mp.py:528-542): a run that starts from the file another run saved continues from its thetas --
     global and, with --user_adapt, every user's -- and the adapt mode's extension is tried before the bare name."""
     gold = _batch_gold()
-    paths = _write_tidir(gold, str(tmp_path))
+    paths = write_tidir(gold, str(tmp_path))
     a = _trainer(paths, gold, adapt=adapt, minibatch=5, shuffle_seed=1)
     a.train(epochs=2, reg_param=0.2, save_params=str(tmp_path / 'params'))
     ext = '.user_adapt' if adapt else ''
@@ -1037,7 +1009,7 @@ def test_two_rank_trainer_epoch_equals_one_process_and_the_reference(tmp_path):
     import torch.multiprocessing as mp
     gold_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'tidir_reference.json')
     gold = json.load(open(gold_path, encoding='utf8'))
-    paths = _write_tidir(gold, str(tmp_path))
+    paths = write_tidir(gold, str(tmp_path))
     s = socket.socket(); s.bind(('127.0.0.1', 0)); port = s.getsockname()[1]; s.close()
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
@@ -1111,7 +1083,7 @@ def test_two_ranks_write_one_prediction_file_in_instance_order(tmp_path):
     import torch.multiprocessing as mp
     gold = _batch_gold()
     gold_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'tidir_batch_reference.json')
-    paths = _write_tidir(gold, str(tmp_path))
+    paths = write_tidir(gold, str(tmp_path))
     out = str(tmp_path / 'pred')
     s = socket.socket(); s.bind(('127.0.0.1', 0)); port = s.getsockname()[1]; s.close()
     ctx = mp.get_context('spawn')
@@ -1141,7 +1113,7 @@ def test_tune_set_is_evaluated_after_every_epoch(tmp_path):
     that epoch's saved params file predicts."""
     from macaronicusermodeling_amd.train import TiDirTrainer
     gold = _batch_gold()
-    paths = _write_tidir(gold, str(tmp_path))
+    paths = write_tidir(gold, str(tmp_path))
     want = gold['predictions']
     tt = _trainer(paths, gold)
     tuner = tt.tune_evaluator(paths['ti'])

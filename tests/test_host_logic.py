@@ -180,3 +180,55 @@ def test_random_graphs_schedule_loop_test_and_compiled_sweeps_equal_the_oracle_w
             else:
                 mine.append(('tm' if kind == _ffi.OP_PAIR_TM else 'mt', a, b, c))
         assert mine == _oracle_ops(spec, root)
+
+
+def _clique_shapes():
+    """The sentence shapes of tests/golden/tidir_cliques_reference.json.gz (1 to 12 predicted words at X = 64), each with the
+    batched trainer's roots (predicted positions in order, cyclic, three sweeps)."""
+    from helpers import tidir_gold
+    from macaronicusermodeling_amd import tidir
+    gold = tidir_gold('tidir_cliques_reference')
+    buckets = tidir.bucket_instances([tidir.parse_instance(l) for l in gold['instances']], gold['vocab_en'], gold['vocab_de'])
+    return [(b['spec'], [key[1][i % len(key[1])] for i in range(3)]) for key, b in sorted(buckets.items())]
+
+
+def test_large_clique_schedules_loop_tests_and_compiled_sweeps_equal_the_oracle_walk():
+    """K7 to K10 and K12 (21 to 66 pairwise factors, 288 message slots for K12): the C++ schedule, loop test and compiled sweep of
+    every root against the oracle's walk -- slot indices past 255 and factor indices past 16 included."""
+    seen = set()
+    for spec, _ in _clique_shapes():
+        topo = GraphTopology.from_spec(spec)
+        if topo.P < 21:
+            continue
+        seen.add(topo.P)
+        g = O.Graph(spec)
+        assert topo.slot_keys() == C.msg_keys(spec)
+        for root in topo.var_ids:
+            assert topo.has_loops(root) and O.has_loops(g, root)
+            assert [(topo.node_name(a), topo.node_name(b)) for a, b in topo.message_schedule(root)] == \
+                [(O.name(a), O.name(b)) for a, b in O.message_schedule(g, root)]
+            ops, srcs = topo.compile_sweep(root)
+            got = []
+            for kind, a, b, c in ops.tolist():
+                if kind == _ffi.OP_VAR:
+                    got.append(('var', tuple(srcs[a:a + b].tolist()), c))
+                elif kind == _ffi.OP_UNARY:
+                    got.append(('unary', a, c))
+                else:
+                    got.append(('tm' if kind == _ffi.OP_PAIR_TM else 'mt', a, b, c))
+            assert got == _oracle_ops(spec, root)
+    assert seen == {21, 28, 36, 45, 66}
+    assert max(GraphTopology.from_spec(s).n_msgs for s, _ in _clique_shapes()) == 288
+
+
+def test_shared_table_form_covers_cliques_up_to_sixteen_pairwise_factors():
+    """The limit the X = 64 dispatch rests on: the shared-table (matrix-core) form plans K2 to K6 (P <= 16) and declines K7
+    and larger, which the exact kernel (or, once its LDS image is too large, the generic kernel) runs instead."""
+    by_p = {}
+    for spec, roots in _clique_shapes():
+        topo = GraphTopology.from_spec(spec)
+        if topo.P >= 1:
+            by_p.setdefault(topo.P, set()).add(topo.plan(roots)['shared_ok'])
+    assert set(by_p) == {1, 3, 6, 10, 15, 21, 28, 36, 45, 66}
+    for P, ok in by_p.items():
+        assert ok == {1 if P <= 16 else 0}, (P, ok)

@@ -186,3 +186,37 @@ def test_au_error_behaviour_matches_recorded_reference_errors():
         j = _au_inputs(X, seed)
         assert rec(lambda: au.sparse_vec_mat_dot(j['c'], j['T'])) == errs[tag + '/sparse_vec_mat_dot_col']
         assert rec(lambda: au.sparse_dot(j['c'], j['r'])) == errs[tag + '/sparse_dot']
+
+
+def test_oracle_equals_the_reference_pipeline_on_large_cliques(tmp_path):
+    """tests/golden/tidir_cliques_reference.json.gz (make_clique_golden.py): the reference's create_factor_graph, three sweeps,
+    get_posterior_probs and return_gradient() on one sentence of each of K1 to K10 and K12 at X = 64 (K12: 66 pairwise
+    factors).  The oracle, fed the same instances through the reader and shape compiler, must give the same marginals,
+    log-posterior and step to 1e-12 -- the GPU tests of these shapes lean on it."""
+    from helpers import tidir_gold, tidir_oracle_graph, write_tidir
+    from macaronicusermodeling_amd import tidir
+    gold = tidir_gold('tidir_cliques_reference')
+    en, de = gold['vocab_en'], gold['vocab_de']
+    paths = write_tidir(gold, str(tmp_path))
+    phi_ee, phi_w1, phi_ed = tidir.load_features(paths['phi.pmi'], paths['phi.pmi_w1'], paths['phi.ed'], paths['phi.ped'])
+    th_ee, th_ed = np.array(gold['theta_en_en']), np.array(gold['theta_en_de'])
+    o = gold['options']
+    reg = o['reg_param'] / len(gold['instances'])                                              # train_mp.py:160
+    instances = [tidir.parse_instance(l) for l in gold['instances']]
+    by_sent = {ti['current_sent'][0]['sent_id']: r for ti, r in zip(instances, gold['reference'])}
+    seen = set()
+    for key, b in tidir.bucket_instances(instances, en, de).items():
+        for i, row in enumerate(b['rows']):
+            ref = by_sent[row['sent_id']]
+            g, inputs, roots, _ = tidir_oracle_graph(key, b, i, phi_ee, phi_w1, phi_ed, th_ee, th_ed)
+            assert roots == ref['roots']
+            msgs = O.init_messages(g)
+            O.treelike_inference(g, inputs, msgs, o['sweeps'], roots, True)
+            marg = np.stack([O.marginal(g, msgs, v) for v in g.var_order])
+            np.testing.assert_allclose(marg, np.array(ref['marginals']), rtol=RTOL, atol=1e-300)
+            np.testing.assert_allclose(O.log_posterior(g, msgs), ref['log_posterior'], rtol=RTOL)
+            ee, ed = O.return_gradient(g, inputs, msgs, reg, o['learning_rate'])
+            np.testing.assert_allclose(ee.reshape(-1), ref['step'][0], rtol=RTOL, atol=1e-15)
+            np.testing.assert_allclose(ed.reshape(-1), ref['step'][1], rtol=RTOL, atol=1e-15)
+            seen.add(len(key[1]))
+    assert seen >= {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12}

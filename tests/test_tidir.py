@@ -136,7 +136,19 @@ def test_reader_and_shape_compiler_equal_the_reference_graph_builder():
     TrainingInstance.from_dict and create_factor_graph (train_mp.py:105-306, run by make_tidir_golden.py against the
     reference's LBP.py) give the normalised guesses and nodes, the variables that enter the graph and the factor list in
     creation order; parse_instance / instance_shape / shape_spec / bucket_instances must give the same."""
-    gold = _tidir_gold()
+    assert _check_graph_builder(_tidir_gold()) > 60
+
+
+def test_reader_and_shape_compiler_equal_the_reference_graph_builder_on_large_cliques():
+    """The same on tests/golden/tidir_cliques_reference.json.gz (make_clique_golden.py): one sentence of each of K1 to K10 and
+    K12 at X = 64 -- up to 66 pairwise factors in the reference's creation order."""
+    from helpers import tidir_gold
+    gold = tidir_gold('tidir_cliques_reference')
+    assert {len(r['variables']) for r in gold['reference']} >= {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12}
+    assert _check_graph_builder(gold) == sum(len(r['factors']) for r in gold['reference']) == 515
+
+
+def _check_graph_builder(gold):
     en, de = gold['vocab_en'], gold['vocab_de']
     en2id = {w: i for i, w in enumerate(en)}
     de2id = {w: i for i, w in enumerate(de)}
@@ -166,7 +178,7 @@ def test_reader_and_shape_compiler_equal_the_reference_graph_builder():
             elif len(fvars) == 1:
                 assert en[obs[fid]] == word_label
             n_checked += 1
-    assert n_checked > 60
+    return n_checked
 
 
 def test_prediction_writer_reproduces_the_reference_text_from_its_own_distributions():
