@@ -23,8 +23,8 @@
  *     MLBP_ENODEVICE.
  *
  * Concurrency (what the deployment model -- one process per GPU, train_mp.py:634 -- needs, stated exactly)
- *   - host functions and mlbp_last_error() are thread-safe; the sweep-kernel diagnostic mlbp_last_sweep_kernel() is
- *     per calling thread;
+ *   - host functions and mlbp_last_error() are thread-safe; the diagnostics mlbp_last_sweep_kernel() and the launch log
+ *     (mlbp_launch_log) are per calling thread: a launch is logged in the thread that enqueued it;
  *   - a mlbp_program belongs to the device that was current when it was created (mlbp_sweep_f64 checks this) and owns
  *     per-program device state (status word, per-graph redo flags): calls that use the SAME program must be enqueued
  *     on one stream, or be ordered by the caller;
@@ -321,6 +321,14 @@ int mlbp_last_sweep_kernel(void);
  * tables and final messages still on chip: MLBP_KERNEL_LEAN and MLBP_KERNEL_SHARED_MFMA with F = (3, 6) and at most three
  * pairwise factors -- 0 when a separate gradient launch followed the sweeps (or none was asked for). */
 int mlbp_last_sweep_fused_gradient(void);
+
+/* Diagnostic: the launch log.  Every kernel launch the library enqueues from the calling thread appends that kernel's handle
+ * (the host-side address HIP launches it by) to the thread's log; mlbp_launch_log_reset empties it.  mlbp_launch_log copies
+ * the first min(max, 4096) handles, in launch order, to handles (host; NULL: copy none) and returns how many launches were
+ * logged since the reset, which may exceed 4096.  Like mlbp_last_sweep_kernel it is a host-side record: it is written when a
+ * launch is enqueued, also during stream capture, and says nothing about execution. */
+void mlbp_launch_log_reset(void);
+int mlbp_launch_log(const void** handles, int max);
 
 /* Fills msgs[B][n_msgs][X] with 1/X: FactorGraph.initialize (LBP.py:211-216). */
 int mlbp_init_messages_f64(double* msgs, int64_t n_rows, int32_t X, void* stream);

@@ -83,6 +83,8 @@ SIGNATURES = {
     'mlbp_device_count': (C.c_int, []),
     'mlbp_last_sweep_kernel': (C.c_int, []),
     'mlbp_last_sweep_fused_gradient': (C.c_int, []),
+    'mlbp_launch_log_reset': (None, []),
+    'mlbp_launch_log': (C.c_int, [C.POINTER(_vp), C.c_int]),
     'mlbp_has_loops': (C.c_int, [C.POINTER(Topology), _i32]),
     'mlbp_message_schedule': (C.c_int, [C.POINTER(Topology), _i32, _i32p, _i32]),
     'mlbp_message_slots': (C.c_int, [C.POINTER(Topology), _i32p, _i32p, _i32p, _i32p]),

@@ -614,30 +614,35 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 1) void contract_chunked_ke
 
 template <typename TT, int RT, bool PADDED>
 int launch_contract_rt(const ContractDev& d, int nct, int n_sets, hipStream_t st) {
-  const int XA = 64 * RT;
-  void (*k)(ContractDev) = nullptr;
-  int threads = 512;
-  if constexpr (RT > 8) {
-    // 640 .. 1024 states: one workgroup per CU (its image is 82 .. 131 KiB); 16 waves when the row tiles divide among them
-    static_assert(PADDED && sizeof(TT) == 8, "");
-    if constexpr ((4 * RT) % 16 == 0) { k = contract_kernel<TT, RT, 1, 2, 16, true>; threads = 1024; }
-    else k = contract_kernel<TT, RT, 1, 2, 8, true>;
-    nct = 1;
-  } else if constexpr (PADDED) {
-    k = contract_kernel<TT, RT, 1, 2, 8, true>;
-    nct = 1;
+  if constexpr (sizeof(TT) == 4 && RT != 4 && RT != 8) {
+    // (float32 tables are accepted at X = 256 and 512 only: check_sweep_args, launch_gemm_sweep)
+    return fail(MLBP_EUNSUPPORTED, "shared-table contraction: X = %d with float32 tables (256 or 512)", d.X);
   } else {
-    // 32 graphs per workgroup (float64, small tables, big batches): 4 waves, deep fragment prefetch; else 16 graphs per
-    // workgroup and 8 waves (two workgroups = 4 waves per SIMD hide each other's stalls; measured 3-7 % over 4 waves)
-    if constexpr (RT <= 4 && sizeof(TT) == 8) {
-      if (nct == 2) { k = contract_kernel<TT, RT, 2, 4, 4, false>; threads = WG; }
+    const int XA = 64 * RT;
+    void (*k)(ContractDev) = nullptr;
+    int threads = 512;
+    if constexpr (RT > 8) {
+      // 640 .. 1024 states: one workgroup per CU (its image is 82 .. 131 KiB); 16 waves when the row tiles divide among them
+      static_assert(PADDED && sizeof(TT) == 8, "");
+      if constexpr ((4 * RT) % 16 == 0) { k = contract_kernel<TT, RT, 1, 2, 16, true>; threads = 1024; }
+      else k = contract_kernel<TT, RT, 1, 2, 8, true>;
+      nct = 1;
+    } else if constexpr (PADDED) {
+      k = contract_kernel<TT, RT, 1, 2, 8, true>;
+      nct = 1;
+    } else {
+      // 32 graphs per workgroup (float64, small tables, big batches): 4 waves, deep fragment prefetch; else 16 graphs per
+      // workgroup and 8 waves (two workgroups = 4 waves per SIMD hide each other's stalls; measured 3-7 % over 4 waves)
+      if constexpr (RT <= 4 && sizeof(TT) == 8) {
+        if (nct == 2) { k = contract_kernel<TT, RT, 2, 4, 4, false>; threads = WG; }
+      }
+      if (!k) { nct = 1; k = sizeof(TT) == 8 ? contract_kernel<TT, RT, 1, 2, 8, false> : contract_kernel<TT, RT, 1, 4, 8, false>; }
     }
-    if (!k) { nct = 1; k = sizeof(TT) == 8 ? contract_kernel<TT, RT, 1, 2, 8, false> : contract_kernel<TT, RT, 1, 4, 8, false>; }
+    if (int e = grant_lds((const void*)k, 160 * 1024)) return e;
+    const size_t lds_bytes = (size_t)16 * nct * (XA + 2) * sizeof(double);      // (the float32 image is reused as the float64 output image)
+    MLBP_LAUNCH(k, dim3((d.B + 16 * nct - 1) / (16 * nct), n_sets), dim3(threads), lds_bytes, st, d);
+    return MLBP_OK;
   }
-  if (int e = grant_lds((const void*)k, 160 * 1024)) return e;
-  const size_t lds_bytes = (size_t)16 * nct * (XA + 2) * sizeof(double);      // (the float32 image is reused as the float64 output image)
-  hipLaunchKernelGGL(k, dim3((d.B + 16 * nct - 1) / (16 * nct), n_sets), dim3(threads), lds_bytes, st, d);
-  return MLBP_OK;
 }
 
 template <int RT>
@@ -647,7 +652,7 @@ int launch_chunked_rt(const ContractDev& d, int n_sets, hipStream_t st) {
   if constexpr ((4 * RT) % 16 == 0) { k = contract_chunked_kernel<double, RT, 16>; threads = 1024; }
   else k = contract_chunked_kernel<double, RT, 8>;
   if (int e = grant_lds((const void*)k, 160 * 1024)) return e;
-  hipLaunchKernelGGL(k, dim3((d.B + 15) / 16, n_sets), dim3(threads), (size_t)16 * (64 * RT + 2) * sizeof(double), st, d);
+  MLBP_LAUNCH(k, dim3((d.B + 15) / 16, n_sets), dim3(threads), (size_t)16 * (64 * RT + 2) * sizeof(double), st, d);
   return MLBP_OK;
 }
 
@@ -783,7 +788,7 @@ template <typename TT>
 void launch_table_frag(const TT* T, const double* planes, int n_planes, int n_sets, int X, int transpose, TT* frag, hipStream_t st) {
   constexpr int E = sizeof(TT) == 8 ? 2 : 4;
   const size_t XA = (size_t)padded_states(X);
-  hipLaunchKernelGGL((table_frag_kernel<TT, E>), dim3((unsigned)((XA * XA + 255) / 256), n_sets), dim3(256), 0, st, T, planes, n_planes, X, (int)XA,
+  MLBP_LAUNCH((table_frag_kernel<TT, E>), dim3((unsigned)((XA * XA + 255) / 256), n_sets), dim3(256), 0, st, T, planes, n_planes, X, (int)XA,
                      transpose, frag);
 }
 
@@ -838,7 +843,7 @@ int launch_gemm_pair_gradient(const mlbp_gradient_args* a, int32_t* status, void
     d.n_src = 0; d.in_slot = h_r[p]; d.vf_slot = -1; d.dst_slot = 0; d.B = B; d.normalize = 0;
     d.dot_slot = h_c[p]; d.dots = S;
     if (int e = launch_contract<double>(d, X, 4, st)) return e;
-    hipLaunchKernelGGL(pair_gradient_combine_kernel, dim3((B + 255) / 256), dim3(256), 0, st, S, B, X, a->pair_label, a->P, p,
+    MLBP_LAUNCH(pair_gradient_combine_kernel, dim3((B + 255) / 256), dim3(256), 0, st, S, B, X, a->pair_label, a->P, p,
                        h_phi[p] ? a->phi_en_en_w1 : a->phi_en_en, a->grad_en_en, status);
   }
   return launch_verdict("shared-table gradient");
@@ -874,7 +879,7 @@ int launch_gemm_sweep(const mlbp_program* prog, const mlbp_sweep_args* a, void* 
   {
     HostRow row = {};
     for (int p = 0; p < prog->P; ++p) row.v[p] = a->pair_tab_host[p];
-    hipLaunchKernelGGL(check_shared_claim_kernel, dim3((B * prog->P + 255) / 256), dim3(256), 0, st, a->pair_tab, B, prog->P,
+    MLBP_LAUNCH(check_shared_claim_kernel, dim3((B * prog->P + 255) / 256), dim3(256), 0, st, a->pair_tab, B, prog->P,
                        a->n_pair_tables, row, prog->d_status);
   }
   for (int p = 0; p < prog->P; ++p)
@@ -884,10 +889,10 @@ int launch_gemm_sweep(const mlbp_program* prog, const mlbp_sweep_args* a, void* 
       else launch_table_frag<double>(a->pair_tables + (size_t)a->pair_tab_host[p] * X * X, nullptr, 0, 1, X, tr, (double*)frag + off, st);
     }
   if (a->init_messages)
-    hipLaunchKernelGGL(fill_uniform_kernel, dim3(1024), dim3(256), 0, st, a->msgs, (size_t)B * n_msgs * X, 1.0 / (double)X);
+    MLBP_LAUNCH(fill_uniform_kernel, dim3(1024), dim3(256), 0, st, a->msgs, (size_t)B * n_msgs * X, 1.0 / (double)X);
   // unary messages the program could hoist are constants (LBP.py:494-498): once per call
   for (size_t h = 0; h + 1 < fp.hoist.size(); h += 2)
-    hipLaunchKernelGGL(unary_update_kernel, dim3(B), dim3(WG), 0, st, a->msgs, n_msgs, X, a->unary_tables, a->unary_tab, prog->U,
+    MLBP_LAUNCH(unary_update_kernel, dim3(B), dim3(WG), 0, st, a->msgs, n_msgs, X, a->unary_tables, a->unary_tab, prog->U,
                        a->n_unary_tables, fp.hoist[h], fp.hoist[h + 1], norm, prog->d_status);
   const size_t ld = (size_t)n_msgs * X;
   const int n_fops = (int)fp.fops.size() / 8;
@@ -917,12 +922,12 @@ int launch_gemm_sweep(const mlbp_program* prog, const mlbp_sweep_args* a, void* 
     const int32_t* w = &fp.fops[8 * (size_t)i];
     const int kind = w[0] & 0xFF;
     if (kind == FOP_UNARY) {
-      hipLaunchKernelGGL(unary_update_kernel, dim3(B), dim3(WG), 0, st, a->msgs, n_msgs, X, a->unary_tables, a->unary_tab, prog->U,
+      MLBP_LAUNCH(unary_update_kernel, dim3(B), dim3(WG), 0, st, a->msgs, n_msgs, X, a->unary_tables, a->unary_tab, prog->U,
                          a->n_unary_tables, w[1], w[3], norm, prog->d_status);
       continue;
     }
     if (kind == FOP_VAR) {          // exact source list: psrcs[w[6] .. w[6] + w[7])
-      hipLaunchKernelGGL(variable_update_kernel, dim3(B), dim3(WG), (size_t)X * sizeof(double), st, a->msgs, n_msgs, X,
+      MLBP_LAUNCH(variable_update_kernel, dim3(B), dim3(WG), (size_t)X * sizeof(double), st, a->msgs, n_msgs, X,
                          (prog->d_fops + 8 * (size_t)prog->n_fops) + w[6], w[7], w[3], norm);
       continue;
     }
@@ -937,7 +942,7 @@ int launch_gemm_sweep(const mlbp_program* prog, const mlbp_sweep_args* a, void* 
       pslot = w[4]; tm = kind == FOP_VAR_PAIR_TM;
       d.n_src = w[7]; d.in_slot = 0; d.vf_slot = w[3]; d.dst_slot = w[5];
       if (d.n_src == 0 || d.n_src > 8) {      // no other factor (the message is the uniform vector), or a long list: its own launch
-        hipLaunchKernelGGL(variable_update_kernel, dim3(B), dim3(WG), (size_t)X * sizeof(double), st, a->msgs, n_msgs, X,
+        MLBP_LAUNCH(variable_update_kernel, dim3(B), dim3(WG), (size_t)X * sizeof(double), st, a->msgs, n_msgs, X,
                            (prog->d_fops + 8 * (size_t)prog->n_fops) + w[6], w[7], w[3], norm);
         d.n_src = 0; d.in_slot = w[3]; d.vf_slot = -1;
       } else {

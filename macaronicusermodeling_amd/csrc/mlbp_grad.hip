@@ -710,7 +710,7 @@ int gradient_flagged_only(const mlbp_gradient_args* a, const uint8_t* flags, voi
   d.skip_pairs = 0;
   d.only = flags;
   if (int e = status_word(&d.status)) return e;
-  hipLaunchKernelGGL((gradient_x64_kernel<3, 6>), dim3(a->B), dim3(WG), 0, (hipStream_t)stream, d);
+  MLBP_LAUNCH((gradient_x64_kernel<3, 6>), dim3(a->B), dim3(WG), 0, (hipStream_t)stream, d);
   if (hipGetLastError() != hipSuccess) return fail(MLBP_EHIP, "gradient fix-up launch failed");
   return MLBP_OK;
 }
@@ -733,7 +733,7 @@ int gradient_flagged_groups(const mlbp_gradient_args* args, const uint8_t* const
   words.back() = 0x47524144;
   int32_t* d_table = nullptr;
   if (int e = group_table_device(owner->stables, words, stream, &d_table)) return e;
-  hipLaunchKernelGGL(gradient_x64_groups_kernel, dim3(blocks), dim3(WG), 0, (hipStream_t)stream, reinterpret_cast<const GradGroup*>(d_table), n_groups);
+  MLBP_LAUNCH(gradient_x64_groups_kernel, dim3(blocks), dim3(WG), 0, (hipStream_t)stream, reinterpret_cast<const GradGroup*>(d_table), n_groups);
   if (hipGetLastError() != hipSuccess) return fail(MLBP_EHIP, "gradient fix-up launch failed");
   return MLBP_OK;
 }
@@ -776,9 +776,9 @@ int mlbp_gradient_f64(const mlbp_gradient_args* a, void* stream) {
     d.skip_pairs = shared ? 1 : 0;
     if (shared && a->unary_expect && a->F_ed == 6)               // unary part by gather inside the pair kernel
       return mlbp::launch_shared_pair_gradient(a, d.status, stream);
-    if (a->F_ee == 3) hipLaunchKernelGGL((gradient_x64_kernel<3, 6>), dim3(a->B), dim3(WG), 0, st, d);
-    else if (a->F_ee == 2) hipLaunchKernelGGL((gradient_x64_kernel<2, 2>), dim3(a->B), dim3(WG), 0, st, d);
-    else hipLaunchKernelGGL((gradient_x64_kernel<1, 1>), dim3(a->B), dim3(WG), 0, st, d);
+    if (a->F_ee == 3) MLBP_LAUNCH((gradient_x64_kernel<3, 6>), dim3(a->B), dim3(WG), 0, st, d);
+    else if (a->F_ee == 2) MLBP_LAUNCH((gradient_x64_kernel<2, 2>), dim3(a->B), dim3(WG), 0, st, d);
+    else MLBP_LAUNCH((gradient_x64_kernel<1, 1>), dim3(a->B), dim3(WG), 0, st, d);
     HIP_TRY(hipGetLastError());
     if (shared) return mlbp::launch_shared_pair_gradient(a, d.status, stream);
     return MLBP_OK;
@@ -791,9 +791,9 @@ int mlbp_gradient_f64(const mlbp_gradient_args* a, void* stream) {
   // shared pairwise tables at a large state space: pairwise part as MFMA contractions over the whole batch (mlbp_gemm.hip)
   const bool gemm_pairs = takes_gemm_pairs(a);
   d.skip_pairs = gemm_pairs ? 1 : 0;
-  if (a->F_ee == 3) hipLaunchKernelGGL((gradient_kernel<3, 6>), dim3(a->B), dim3(WG), dyn, st, d);
-  else if (a->F_ee == 2) hipLaunchKernelGGL((gradient_kernel<2, 2>), dim3(a->B), dim3(WG), dyn, st, d);
-  else hipLaunchKernelGGL((gradient_kernel<1, 1>), dim3(a->B), dim3(WG), dyn, st, d);
+  if (a->F_ee == 3) MLBP_LAUNCH((gradient_kernel<3, 6>), dim3(a->B), dim3(WG), dyn, st, d);
+  else if (a->F_ee == 2) MLBP_LAUNCH((gradient_kernel<2, 2>), dim3(a->B), dim3(WG), dyn, st, d);
+  else MLBP_LAUNCH((gradient_kernel<1, 1>), dim3(a->B), dim3(WG), dyn, st, d);
   HIP_TRY(hipGetLastError());
   if (gemm_pairs) return mlbp::launch_gemm_pair_gradient(a, d.status, stream);
   return MLBP_OK;
@@ -810,7 +810,7 @@ int mlbp_unary_expectations_f64(const double* unary_tables, int32_t n_rows, int3
   if (int e = need_device()) return e;
   int32_t* status = nullptr;
   if (int e = status_word(&status)) return e;
-  hipLaunchKernelGGL(unary_expectations_kernel, dim3((n_rows + 3) / 4), dim3(WG), 0, (hipStream_t)stream, unary_tables, n_rows,
+  MLBP_LAUNCH(unary_expectations_kernel, dim3((n_rows + 3) / 4), dim3(WG), 0, (hipStream_t)stream, unary_tables, n_rows,
                      row_kind, row_obs, phi_en_en_t, phi_en_en_w1_t, phi_en_de_t, F_ee, F_ed, Vde, out, status);
   HIP_TRY(hipGetLastError());
   return MLBP_OK;
@@ -824,7 +824,7 @@ int mlbp_pair_beliefs_f64(const double* msgs, int32_t B, int32_t n_msgs, int32_t
   if (int e = need_device()) return e;
   int32_t* status = nullptr;
   if (int e = status_word(&status)) return e;
-  hipLaunchKernelGGL(pair_beliefs_kernel, dim3(B * P), dim3(WG), 0, (hipStream_t)stream, msgs, n_msgs, X, P, pair_tables,
+  MLBP_LAUNCH(pair_beliefs_kernel, dim3(B * P), dim3(WG), 0, (hipStream_t)stream, msgs, n_msgs, X, P, pair_tables,
                      pair_tab, n_pair_tables, c_slot, r_slot, out, status);
   HIP_TRY(hipGetLastError());
   return MLBP_OK;
@@ -849,7 +849,7 @@ int mlbp_select_sum_rows_cat_f64(const double* in0, int32_t cols0, const double*
     return fail(MLBP_EUNSUPPORTED, "mlbp_sum_rows: at most 64 columns, the appended count included (got %d)", cols0 + cols1 + cols2);
   SumCat cat = {{in0, in1, in2}, {cols0, cols1, cols2}, nullptr, nullptr, 0, 0, nullptr, nullptr, key, key_value};
   // the partials live in one device-wide scratch array: launches on DIFFERENT streams must not overlap
-  hipLaunchKernelGGL(sum_rows_kernel, dim3(SUM_PARTS), dim3(WG), 0, (hipStream_t)stream, cat, rows, append_count ? 1 : 0, out);
+  MLBP_LAUNCH(sum_rows_kernel, dim3(SUM_PARTS), dim3(WG), 0, (hipStream_t)stream, cat, rows, append_count ? 1 : 0, out);
   HIP_TRY(hipGetLastError());
   return MLBP_OK;
 }
@@ -863,8 +863,8 @@ int mlbp_step_statistics_f64(const double* grad_en_en, int32_t F_ee, const doubl
   SumCat cat = {{grad_en_en, grad_en_de, marginals}, {F_ee, F_ed, 1}, marginals, labels, n_vars, X, lp_out, nullptr, nullptr, nullptr};
   if (int e = status_word(&cat.status)) return e;
   // (the partials live in one device-wide scratch array, as for mlbp_sum_rows_cat_f64)
-  if (F_ee == 3 && F_ed == 6) hipLaunchKernelGGL((step_statistics_kernel<3, 6>), dim3(SUM_PARTS), dim3(WG), 0, (hipStream_t)stream, cat, B, out);
-  else hipLaunchKernelGGL(sum_rows_kernel, dim3(SUM_PARTS), dim3(WG), 0, (hipStream_t)stream, cat, B, 1, out);
+  if (F_ee == 3 && F_ed == 6) MLBP_LAUNCH((step_statistics_kernel<3, 6>), dim3(SUM_PARTS), dim3(WG), 0, (hipStream_t)stream, cat, B, out);
+  else MLBP_LAUNCH(sum_rows_kernel, dim3(SUM_PARTS), dim3(WG), 0, (hipStream_t)stream, cat, B, 1, out);
   HIP_TRY(hipGetLastError());
   return MLBP_OK;
 }
@@ -879,7 +879,7 @@ int mlbp_segment_sum_rows_f64(const double* in, int64_t rows, int32_t cols, cons
   if (!in || !out || !seg_id || rows <= 0 || cols <= 0 || n_seg <= 0)
     return fail(MLBP_EINVAL, "mlbp_segment_sum_rows_f64: bad arguments");
   if (int e = need_device()) return e;
-  hipLaunchKernelGGL(segment_sum_rows_kernel, dim3(n_seg), dim3(WG), 0, (hipStream_t)stream, in, rows, cols, seg_id, out);
+  MLBP_LAUNCH(segment_sum_rows_kernel, dim3(n_seg), dim3(WG), 0, (hipStream_t)stream, in, rows, cols, seg_id, out);
   HIP_TRY(hipGetLastError());
   return MLBP_OK;
 }
@@ -890,7 +890,7 @@ int mlbp_patch_unary_tables_f64(const double* base_tables, const int32_t* base_r
   if (!base_tables || !base_row || !item_off || !item_x || !item_k || !item_val || !theta || !out || n_rows <= 0 || X <= 0)
     return fail(MLBP_EINVAL, "mlbp_patch_unary_tables_f64: bad arguments");
   if (int e = need_device()) return e;
-  hipLaunchKernelGGL(patch_tables_kernel, dim3(n_rows), dim3(64), 0, (hipStream_t)stream, base_tables, base_row, item_off,
+  MLBP_LAUNCH(patch_tables_kernel, dim3(n_rows), dim3(64), 0, (hipStream_t)stream, base_tables, base_row, item_off,
                      item_x, item_k, item_val, theta, X, out);
   HIP_TRY(hipGetLastError());
   return MLBP_OK;
@@ -903,7 +903,7 @@ int mlbp_patch_gradient_f64(const double* priv_tables, const int32_t* item_off, 
       X <= 0 || F <= 0)
     return fail(MLBP_EINVAL, "mlbp_patch_gradient_f64: bad arguments");
   if (int e = need_device()) return e;
-  hipLaunchKernelGGL(patch_gradient_kernel, dim3(n_rows), dim3(64), 0, (hipStream_t)stream, priv_tables, item_off, item_x,
+  MLBP_LAUNCH(patch_gradient_kernel, dim3(n_rows), dim3(64), 0, (hipStream_t)stream, priv_tables, item_off, item_x,
                      item_k, item_val, row_graph, row_label, n_rows, X, F, grad);
   HIP_TRY(hipGetLastError());
   return MLBP_OK;

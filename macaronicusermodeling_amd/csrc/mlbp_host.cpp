@@ -159,6 +159,23 @@ static void emit(const mlbp_topology* t, const Slots& s, int frm, int to, OpSink
   }
 }
 
+// The calling thread's launch log (mlbp_launch_log): the first LOG_CAP kernel handles since the last reset, and how many
+// launches there were in all.
+namespace {
+enum { LOG_CAP = 4096 };
+struct LaunchLog {
+  const void* handles[LOG_CAP];
+  int count;
+};
+thread_local LaunchLog g_launch_log;
+}  // namespace
+
+void launch_log_record(const void* kernel) {
+  LaunchLog& l = g_launch_log;
+  if (l.count < LOG_CAP) l.handles[l.count] = kernel;
+  if (l.count < 0x7fffffff) ++l.count;
+}
+
 }  // namespace mlbp
 
 using namespace mlbp;
@@ -168,6 +185,16 @@ extern "C" {
 int mlbp_version(void) { return MLBP_VERSION_MAJOR * 100 + MLBP_VERSION_MINOR; }
 const char* mlbp_arch(void) { return "gfx950"; }
 const char* mlbp_last_error(void) { return g_last_error.c_str(); }
+
+void mlbp_launch_log_reset(void) { g_launch_log.count = 0; }
+
+int mlbp_launch_log(const void** handles, int max) {
+  const LaunchLog& l = g_launch_log;
+  int n = l.count < (int)LOG_CAP ? l.count : (int)LOG_CAP;
+  if (handles)
+    for (int i = 0; i < n && i < max; ++i) handles[i] = l.handles[i];
+  return l.count;
+}
 
 int mlbp_has_loops(const mlbp_topology* t, int32_t root) {
   if (int e = check_topology(t)) return e;

@@ -31,6 +31,15 @@ int grant_lds(const void* kernel, size_t bytes, bool* fresh = nullptr);
 void launch_begin();
 int launch_verdict(const char* what);
 
+// Every kernel launch of the library goes through MLBP_LAUNCH: it appends the kernel's handle to the calling thread's launch
+// log (mlbp_launch_log) and then launches.  The log is host-side bookkeeping only, like mlbp_last_sweep_kernel().
+void launch_log_record(const void* kernel);
+#define MLBP_LAUNCH(kernel, ...)                                                           \
+  do {                                                                                     \
+    mlbp::launch_log_record((const void*)(kernel));                                        \
+    hipLaunchKernelGGL(kernel, __VA_ARGS__);                                               \
+  } while (0)
+
 // Fused program form of the X = 64 kernels (build_fused_program in mlbp_sweep.hip): 8-word op headers.
 enum { FOP_UNARY = 0, FOP_PAIR_TM = 1, FOP_PAIR_MT = 2, FOP_VAR = 3, FOP_VAR_PAIR_TM = 4, FOP_VAR_PAIR_MT = 5,
        FOP_BUNDLED = 0x100 /* flag: the next update touches disjoint slots and may share this one's barrier */ };

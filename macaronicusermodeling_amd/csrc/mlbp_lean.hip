@@ -1055,12 +1055,14 @@ typedef void (*lean_fn)(SweepDev, LeanDev, const int32_t*, int, GradFusedDev);
 
 template <bool MULTI>
 static lean_fn pick_lean(int P, bool padx) {
-  if (padx) {
-    switch (P) {
-      case 1: return sweep_x64_lean_kernel<1, true, MULTI, 0, false>;
-      case 2: return sweep_x64_lean_kernel<2, true, MULTI, 0, false>;
-      case 3: return sweep_x64_lean_kernel<3, true, MULTI, 0, false>;
-      default: return sweep_x64_lean_kernel<4, true, MULTI, 0, false>;
+  if constexpr (!MULTI) {       // (a grouped launch is X = 64 only: launch_lean_groups never pads)
+    if (padx) {
+      switch (P) {
+        case 1: return sweep_x64_lean_kernel<1, true, false, 0, false>;
+        case 2: return sweep_x64_lean_kernel<2, true, false, 0, false>;
+        case 3: return sweep_x64_lean_kernel<3, true, false, 0, false>;
+        default: return sweep_x64_lean_kernel<4, true, false, 0, false>;
+      }
     }
   }
   switch (P) {
@@ -1092,7 +1094,7 @@ int launch_lean_sweep(const mlbp_program* prog, const mlbp_sweep_args* a, const 
   lean_fn k = gf ? pick_lean_grad(prog->P) : pick_lean<false>(prog->P, a->X < 64);
   if (int e = grant_lds((const void*)k, lds)) return e;
   launch_begin();
-  hipLaunchKernelGGL(k, dim3(a->B), dim3(WG), lds, (hipStream_t)stream, d, f, nullptr, 0, gf ? *gf : GradFusedDev{});
+  MLBP_LAUNCH(k, dim3(a->B), dim3(WG), lds, (hipStream_t)stream, d, f, nullptr, 0, gf ? *gf : GradFusedDev{});
   if (int e = launch_verdict("lean sweep")) return e;
   *launched = true;
   return MLBP_OK;
@@ -1141,7 +1143,7 @@ int launch_lean_groups(const mlbp_program* const* progs, const mlbp_sweep_args* 
   lean_fn k = pick_lean<true>(p_max, false);
   if (int e = grant_lds((const void*)k, lds_max)) return e;
   launch_begin();
-  hipLaunchKernelGGL(k, dim3(total), dim3(WG), lds_max, (hipStream_t)stream, d0, f0, d_gtable, n_groups, GradFusedDev{});
+  MLBP_LAUNCH(k, dim3(total), dim3(WG), lds_max, (hipStream_t)stream, d0, f0, d_gtable, n_groups, GradFusedDev{});
   if (int e = launch_verdict("grouped lean sweep")) return e;
   *launched = true;
   return MLBP_OK;

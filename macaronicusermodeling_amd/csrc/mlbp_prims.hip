@@ -249,11 +249,11 @@ int mlbp_dense_dot_f64(int32_t batch, int32_t M, int32_t K, int32_t N, const dou
   const int64_t n_out = (int64_t)batch * M * N;
   if (K < 32) {
     int blocks = (int)((n_out + 255) / 256 < 8192 ? (n_out + 255) / 256 : 8192);
-    hipLaunchKernelGGL(dense_dot_thin_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, batch, M, K, N, A,
+    MLBP_LAUNCH(dense_dot_thin_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, batch, M, K, N, A,
                        a_batch, a_row, a_col, B, b_batch, b_row, b_col, C, c_batch, c_row);
   } else {
     int blocks = (int)((n_out + 3) / 4 < 16384 ? (n_out + 3) / 4 : 16384);
-    hipLaunchKernelGGL(dense_dot_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, batch, M, K, N, A, a_batch,
+    MLBP_LAUNCH(dense_dot_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, batch, M, K, N, A, a_batch,
                        a_row, a_col, B, b_batch, b_row, b_col, C, c_batch, c_row);
   }
   HIP_TRY(hipGetLastError());
@@ -265,7 +265,7 @@ int mlbp_pointwise_multiply_f64(const double* a, const double* b, double* out, i
   if (!a || !b || !out || n <= 0) return fail(MLBP_EINVAL, "mlbp_pointwise_multiply_f64: bad arguments");
   if (int e = need_device()) return e;
   int blocks = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
-  hipLaunchKernelGGL(pointwise_multiply_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, b, out, n,
+  MLBP_LAUNCH(pointwise_multiply_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, b, out, n,
                      nan_to_num);
   HIP_TRY(hipGetLastError());
   return MLBP_OK;
@@ -276,7 +276,7 @@ int mlbp_normalize_f64(const double* in, double* out, int32_t batch, int64_t n, 
   if (!in || !out || batch <= 0 || n <= 0 || (mode != MLBP_NORM_ZERO && mode != MLBP_NORM_UNIFORM))
     return fail(MLBP_EINVAL, "mlbp_normalize_f64: bad arguments");
   if (int e = need_device()) return e;
-  hipLaunchKernelGGL(normalize_kernel, dim3(batch), dim3(256), 0, (hipStream_t)stream, in, out, n, mode, positive);
+  MLBP_LAUNCH(normalize_kernel, dim3(batch), dim3(256), 0, (hipStream_t)stream, in, out, n, mode, positive);
   HIP_TRY(hipGetLastError());
   return MLBP_OK;
 }
@@ -289,7 +289,7 @@ int mlbp_topk_f64(const double* v, int64_t stride, int32_t n, int32_t K, int32_t
   size_t lds = (size_t)n * sizeof(double);
   if (lds > 64 * 1024)
     if (int e = mlbp::grant_lds((const void*)topk_kernel, lds)) return e;
-  hipLaunchKernelGGL(topk_kernel, dim3(1), dim3(256), lds, (hipStream_t)stream, v, stride, n, K, idx, (int64_t)0);
+  MLBP_LAUNCH(topk_kernel, dim3(1), dim3(256), lds, (hipStream_t)stream, v, stride, n, K, idx, (int64_t)0);
   HIP_TRY(hipGetLastError());
   return MLBP_OK;
 }
@@ -303,7 +303,7 @@ int mlbp_topk_rows_f64(const double* v, int64_t rows, int32_t n, int32_t K, int3
   size_t lds = (size_t)n * sizeof(double);
   if (lds > 64 * 1024)
     if (int e = mlbp::grant_lds((const void*)topk_kernel, lds)) return e;
-  hipLaunchKernelGGL(topk_kernel, dim3((unsigned)rows), dim3(256), lds, (hipStream_t)stream, v, (int64_t)1, n, K, idx, (int64_t)n);
+  MLBP_LAUNCH(topk_kernel, dim3((unsigned)rows), dim3(256), lds, (hipStream_t)stream, v, (int64_t)1, n, K, idx, (int64_t)n);
   HIP_TRY(hipGetLastError());
   return MLBP_OK;
 }
@@ -314,7 +314,7 @@ int mlbp_sparse_vec_mat_dot_f64(const double* vec, int64_t vstride, const double
   if (!vec || !mat || !idx || !out || n_out <= 0 || K <= 0)
     return fail(MLBP_EINVAL, "mlbp_sparse_vec_mat_dot_f64: bad arguments");
   if (int e = need_device()) return e;
-  hipLaunchKernelGGL(gather_dot_kernel, dim3((n_out + 127) / 128), dim3(128), 0, (hipStream_t)stream, vec, vstride, mat,
+  MLBP_LAUNCH(gather_dot_kernel, dim3((n_out + 127) / 128), dim3(128), 0, (hipStream_t)stream, vec, vstride, mat,
                      m_row, m_col, n_out, idx, K, vec_is_row, out);
   HIP_TRY(hipGetLastError());
   return MLBP_OK;
@@ -324,7 +324,7 @@ static int launch_block_op(int mode, const double* a, const double* b, const dou
                            const int32_t* cidx, int Kc, const int32_t* ridx, int Kr, double* out, void* stream) {
   int n = Kc * Kr;
   int blocks = (n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096;
-  hipLaunchKernelGGL(block_op_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, mode, a, b, total, n_cols, cidx,
+  MLBP_LAUNCH(block_op_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, mode, a, b, total, n_cols, cidx,
                      Kc, ridx, Kr, out);
   HIP_TRY(hipGetLastError());
   return MLBP_OK;
@@ -332,7 +332,7 @@ static int launch_block_op(int mode, const double* a, const double* b, const dou
 
 static int launch_zero(double* p, int64_t n, void* stream) {
   int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-  hipLaunchKernelGGL(zero_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, n);
+  MLBP_LAUNCH(zero_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, n);
   HIP_TRY(hipGetLastError());
   return MLBP_OK;
 }
@@ -360,7 +360,7 @@ int mlbp_sparse_normalize_f64(double* m, int32_t n_cols, const int32_t* cidx, in
   if (!m || !cidx || !ridx || !scratch1 || n_cols <= 0 || Kc <= 0 || Kr <= 0)
     return fail(MLBP_EINVAL, "mlbp_sparse_normalize_f64: bad arguments");
   if (int e = need_device()) return e;
-  hipLaunchKernelGGL(block_sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, m, n_cols, cidx, Kc, ridx, Kr, scratch1);
+  MLBP_LAUNCH(block_sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, m, n_cols, cidx, Kc, ridx, Kr, scratch1);
   HIP_TRY(hipGetLastError());
   return launch_block_op(2, m, nullptr, scratch1, n_cols, cidx, Kc, ridx, Kr, m, stream);
 }
@@ -382,7 +382,7 @@ int mlbp_potentials_multi_f64(const mlbp_potentials_job* jobs, int32_t n_jobs, i
   for (int j = n_jobs; j < MLBP_POTENTIALS_MAX_JOBS; ++j) js.j[j] = jobs[0];
   if (int e = need_device()) return e;
   const int blocks = (int)std::min<int64_t>((n_max + 255) / 256, 4096);
-  hipLaunchKernelGGL(potentials_multi_kernel, dim3(blocks, n_jobs, n_rep), dim3(256), 0, (hipStream_t)stream, js);
+  MLBP_LAUNCH(potentials_multi_kernel, dim3(blocks, n_jobs, n_rep), dim3(256), 0, (hipStream_t)stream, js);
   HIP_TRY(hipGetLastError());
   return MLBP_OK;
 }
@@ -394,7 +394,7 @@ int mlbp_potentials_f64(const double* phi, const double* theta, int32_t rows, in
   if (int e = need_device()) return e;
   const int64_t n = (int64_t)rows * cols;
   int blocks = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
-  hipLaunchKernelGGL(potentials_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, phi, theta, rows, cols, F, pot,
+  MLBP_LAUNCH(potentials_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, phi, theta, rows, cols, F, pot,
                      pot_t);
   HIP_TRY(hipGetLastError());
   return MLBP_OK;
@@ -404,7 +404,7 @@ int mlbp_log_f64(const double* in, double* out, int64_t n, void* stream) {
   if (!in || !out || n <= 0) return fail(MLBP_EINVAL, "mlbp_log_f64: bad arguments");
   if (int e = need_device()) return e;
   int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-  hipLaunchKernelGGL(log_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, in, out, n);
+  MLBP_LAUNCH(log_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, in, out, n);
   HIP_TRY(hipGetLastError());
   return MLBP_OK;
 }
@@ -413,7 +413,7 @@ int mlbp_observed_minus_f64(const double* beliefs, int64_t n, int64_t cell, doub
   if (!beliefs || !out || n <= 0 || cell < 0 || cell >= n) return fail(MLBP_EINVAL, "mlbp_observed_minus_f64: bad arguments");
   if (int e = need_device()) return e;
   int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-  hipLaunchKernelGGL(observed_minus_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, beliefs, n, cell, out);
+  MLBP_LAUNCH(observed_minus_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, beliefs, n, cell, out);
   HIP_TRY(hipGetLastError());
   return MLBP_OK;
 }

@@ -2318,12 +2318,15 @@ sweep_fn grad_instance() {
 int pick_sweep_kernel(bool two, bool spill, bool wide, bool multi, bool grad, bool pf, size_t lds, sweep_fn* out, bool p3 = false) {
   sweep_fn k = nullptr;
   if (spill || wide) pf = false;
+  // A one-table program (P = 1) gives no variable two pairwise factors: no update multiplies more than two tiles, every tile fits
+  // LDS and the three-source form does not apply.  Should that change, the two-table instances run it (both hold the same table).
+  if (spill || wide || p3) two = true;
   if (p3) {                                                      // three-source product-fused form
 #ifdef MLBP_STAMPS
     return fail(MLBP_EUNSUPPORTED, "stamps build: no three-source instance");
 #else
 #define MLBP_P3(T, M) (grad ? (sweep_fn)sweep_x64_shared_kernel<T, false, false, M, true, true, true> : (sweep_fn)sweep_x64_shared_kernel<T, false, false, M, false, true, true>)
-    k = two ? (multi ? MLBP_P3(2, true) : MLBP_P3(2, false)) : (multi ? MLBP_P3(1, true) : MLBP_P3(1, false));
+    k = multi ? MLBP_P3(2, true) : MLBP_P3(2, false);
 #undef MLBP_P3
 #endif
   } else {
@@ -2349,7 +2352,7 @@ int pick_sweep_kernel(bool two, bool spill, bool wide, bool multi, bool grad, bo
 #define MLBP_SK_M(T, S, W) (multi ? MLBP_SK(T, S, W, true) : MLBP_SK(T, S, W, false))
 #define MLBP_SK_W(T, S) (wide ? MLBP_SK_M(T, S, true) : MLBP_SK_M(T, S, false))
 #define MLBP_SK_S(T) (spill ? MLBP_SK_W(T, true) : MLBP_SK_W(T, false))
-  k = two ? MLBP_SK_S(2) : MLBP_SK_S(1);
+  k = two ? MLBP_SK_S(2) : MLBP_SK_M(1, false, false);
 #undef MLBP_SK_S
 #undef MLBP_SK_W
 #undef MLBP_SK_M
@@ -2516,7 +2519,7 @@ int enqueue_unary_writeback(const mlbp_program* prog, const mlbp_sweep_args* a, 
   const int E = sp.n_cpw / 4;
   const long long rows = (long long)a->B * E;
   launch_begin();
-  hipLaunchKernelGGL(unary_writeback_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(WG), 0, st, a->unary_tables, a->unary_tab,
+  MLBP_LAUNCH(unary_writeback_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(WG), 0, st, a->unary_tables, a->unary_tab,
                      prog->d_simage + sp.off_ent, E, a->B, prog->U, a->n_unary_tables, prog->n_msgs, a->msgs);
   if (int e = launch_verdict("unary write-back")) return e;
   return MLBP_OK;
@@ -2532,12 +2535,12 @@ int launch_shared_sweep(const mlbp_program* prog, const mlbp_sweep_args* a, void
   if (!ok) return MLBP_OK;
   hipStream_t st = (hipStream_t)stream;
   launch_begin();
-  hipLaunchKernelGGL(shared_prepare_kernel<false>, dim3(pl.n_prep_blocks), dim3(PWG), (size_t)pl.q.n_cprod * TILE * sizeof(double), st, pl.q, nullptr, nullptr, 0);
+  MLBP_LAUNCH(shared_prepare_kernel<false>, dim3(pl.n_prep_blocks), dim3(PWG), (size_t)pl.q.n_cprod * TILE * sizeof(double), st, pl.q, nullptr, nullptr, 0);
   if (int e = launch_verdict("shared-table prepare")) return e;
   sweep_fn k = nullptr;
   if (int e = pick_sweep_kernel(prog->P >= 2, pl.spill, pl.wide, false, pl.d.gr.enabled != 0, pl.pf, pl.lds, &k, pl.p3)) return e;
   launch_begin();
-  hipLaunchKernelGGL(k, dim3(pl.n_wg), dim3(SWG), pl.lds, st, pl.d, nullptr, nullptr, 0);
+  MLBP_LAUNCH(k, dim3(pl.n_wg), dim3(SWG), pl.lds, st, pl.d, nullptr, nullptr, 0);
   if (int e = launch_verdict("shared-table sweep")) return e;
   if (int e = enqueue_unary_writeback(prog, a, pl.d, st)) return e;
   *launched = true;
@@ -2649,7 +2652,7 @@ int launch_shared_groups(const mlbp_program* const* progs, const mlbp_sweep_args
   const int32_t* d_pstarts = d_stable + (w_sd + w_pd) * n_tab;
   const int32_t* d_sstarts = d_pstarts + n_tab + 1;
   launch_begin();
-  hipLaunchKernelGGL(shared_prepare_kernel<true>, dim3(pb), dim3(PWG), (size_t)max_cprod * TILE * sizeof(double), st, launch_job, d_pd, d_pstarts, n_tab);
+  MLBP_LAUNCH(shared_prepare_kernel<true>, dim3(pb), dim3(PWG), (size_t)max_cprod * TILE * sizeof(double), st, launch_job, d_pd, d_pstarts, n_tab);
   if (int e = launch_verdict("shared-table prepare")) return e;
   // Two or more forms present: the product-fused groups' launch goes to a side stream of the owner program, forked behind the
   // prepare launch and joined in front of whatever follows -- the launches are independent, and the three-source form (one
@@ -2685,7 +2688,7 @@ int launch_shared_groups(const mlbp_program* const* progs, const mlbp_sweep_args
     sweep_fn k = nullptr;
     if (int e = pick_sweep_kernel(two, spill, wide, true, grad, c == 0, lds, &k, c == 1)) return e;
     launch_begin();
-    hipLaunchKernelGGL(k, dim3(grid[c]), dim3(SWG), lds, (fork && c == 0) ? side : st, plans[order[first[c]]].d, d_sd + first[c], d_sstarts + first[c] + c, n);
+    MLBP_LAUNCH(k, dim3(grid[c]), dim3(SWG), lds, (fork && c == 0) ? side : st, plans[order[first[c]]].d, d_sd + first[c], d_sstarts + first[c] + c, n);
     if (int e = launch_verdict("shared-table sweep")) return e;
   }
   if (fork) {
@@ -2725,9 +2728,9 @@ int launch_shared_pair_gradient(const mlbp_gradient_args* a, int32_t* status, vo
   }
   d.wfrag = wfrag;
   launch_begin();
-  hipLaunchKernelGGL(pair_weight_fragments_kernel, dim3(a->n_pair_tables * 8), dim3(WG), 0, (hipStream_t)stream, a->pair_tables,
+  MLBP_LAUNCH(pair_weight_fragments_kernel, dim3(a->n_pair_tables * 8), dim3(WG), 0, (hipStream_t)stream, a->pair_tables,
                      a->phi_en_en_p, a->phi_en_en_w1_p, wfrag);
-  hipLaunchKernelGGL(gradient_shared_pairs_kernel, dim3((a->B + G - 1) / G), dim3(WG), 0, (hipStream_t)stream, d);
+  MLBP_LAUNCH(gradient_shared_pairs_kernel, dim3((a->B + G - 1) / G), dim3(WG), 0, (hipStream_t)stream, d);
   if (int e = launch_verdict("shared-table pair gradient")) return e;
   return MLBP_OK;
 }

@@ -1747,7 +1747,7 @@ static int run_sweep(const mlbp_program* prog, const mlbp_sweep_args* a, FastPas
 #undef MLBP_PICK
     if (int e = mlbp::grant_lds((const void*)k, lds)) return e;
     mlbp::launch_begin();
-    hipLaunchKernelGGL(k, dim3(f.only ? (a->B + FIXUP_GRAPHS_PER_WG - 1) / FIXUP_GRAPHS_PER_WG : a->B), dim3(WG), lds, st, G.d, f, gf);
+    MLBP_LAUNCH(k, dim3(f.only ? (a->B + FIXUP_GRAPHS_PER_WG - 1) / FIXUP_GRAPHS_PER_WG : a->B), dim3(WG), lds, st, G.d, f, gf);
     if (int e = mlbp::launch_verdict("exact X = 64 sweep")) return e;
     return sweep_tail(prog, a, tail, stream);
   }
@@ -1801,7 +1801,7 @@ static int run_sweep(const mlbp_program* prog, const mlbp_sweep_args* a, FastPas
     }
     const size_t ldsw = ((size_t)6 * xp + 4) * sizeof(double);
     mlbp::launch_begin();
-    hipLaunchKernelGGL(kw, dim3(a->B), dim3(WG), ldsw, st, d);
+    MLBP_LAUNCH(kw, dim3(a->B), dim3(WG), ldsw, st, d);
     if (int e = mlbp::launch_verdict("wide sweep")) return e;
     return sweep_tail(prog, a, SweepTail(), stream);
   }
@@ -1823,10 +1823,10 @@ static int run_sweep(const mlbp_program* prog, const mlbp_sweep_args* a, FastPas
   mlbp::launch_begin();
   if (with_msgs <= 64 * 1024) {
     auto k = norm ? sweep_generic_kernel<true, true> : sweep_generic_kernel<false, true>;
-    hipLaunchKernelGGL(k, dim3(a->B), dim3(WG), with_msgs, st, d);
+    MLBP_LAUNCH(k, dim3(a->B), dim3(WG), with_msgs, st, d);
   } else {
     auto k = norm ? sweep_generic_kernel<true, false> : sweep_generic_kernel<false, false>;
-    hipLaunchKernelGGL(k, dim3(a->B), dim3(WG), base, st, d);
+    MLBP_LAUNCH(k, dim3(a->B), dim3(WG), base, st, d);
   }
   if (int e = mlbp::launch_verdict("generic sweep")) return e;
   return sweep_tail(prog, a, SweepTail(), stream);
@@ -1879,7 +1879,7 @@ static int finish_shared_groups(const mlbp_program* const* progs, const mlbp_swe
   if (int e = mlbp::group_table_device(owner->stables, words, stream, &d_table)) return e;
   if (int e = mlbp::grant_lds((const void*)sweep_x64_fixup_groups_kernel, lds_max)) return e;
   mlbp::launch_begin();
-  hipLaunchKernelGGL(sweep_x64_fixup_groups_kernel, dim3(blocks), dim3(WG), lds_max, (hipStream_t)stream,
+  MLBP_LAUNCH(sweep_x64_fixup_groups_kernel, dim3(blocks), dim3(WG), lds_max, (hipStream_t)stream,
                      reinterpret_cast<const FixupGroup*>(d_table), n_groups);
   if (int e = mlbp::launch_verdict("grouped exact X = 64 fix-up")) return e;
   if (!grads.empty())
@@ -2137,7 +2137,7 @@ int mlbp_init_messages_f64(double* msgs, int64_t n_rows, int32_t X, void* stream
   int64_t n = n_rows * X;
   int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
   mlbp::launch_begin();
-  hipLaunchKernelGGL(fill_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, msgs, n, 1.0 / (double)X);
+  MLBP_LAUNCH(fill_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, msgs, n, 1.0 / (double)X);
   return mlbp::launch_verdict("message initialisation");
 }
 
@@ -2148,7 +2148,7 @@ int mlbp_marginals_f64(const double* msgs, int32_t B, int32_t n_msgs, int32_t X,
     return fail(MLBP_EINVAL, "mlbp_marginals_f64: bad arguments");
   if (int e = check_device()) return e;
   mlbp::launch_begin();
-  hipLaunchKernelGGL(marginals_kernel, dim3(B), dim3(WG), 0, (hipStream_t)stream, msgs, n_msgs, X, n_vars,
+  MLBP_LAUNCH(marginals_kernel, dim3(B), dim3(WG), 0, (hipStream_t)stream, msgs, n_msgs, X, n_vars,
                      in_off, in_slots, normalize_messages, out);
   return mlbp::launch_verdict("marginals");
 }
@@ -2167,7 +2167,7 @@ int mlbp_log_posterior_sum_f64(const double* marginals, const int32_t* labels, i
   // launch has its own generation number (the arrival word restarts with it: see the kernel)
   const unsigned gen = sum_out ? next_lp_generation() : 0u;
   mlbp::launch_begin();
-  hipLaunchKernelGGL(log_posterior_kernel, dim3(blocks), dim3(LP_WG), 0, (hipStream_t)stream, marginals, labels, B, n_vars, X, out,
+  MLBP_LAUNCH(log_posterior_kernel, dim3(blocks), dim3(LP_WG), 0, (hipStream_t)stream, marginals, labels, B, n_vars, X, out,
                      sum_out, status, gen);
   return mlbp::launch_verdict("log-posterior");
 }
@@ -2179,7 +2179,7 @@ int mlbp_log_posterior_groups_f64(const mlbp_posterior_group* groups, int32_t n_
   int32_t* status = nullptr;
   if (int e = global_status(&status)) return e;
   mlbp::launch_begin();
-  hipLaunchKernelGGL(log_posterior_groups_kernel, dim3((unsigned)((n_total + LP_WG - 1) / LP_WG)), dim3(LP_WG), 0, (hipStream_t)stream, groups,
+  MLBP_LAUNCH(log_posterior_groups_kernel, dim3((unsigned)((n_total + LP_WG - 1) / LP_WG)), dim3(LP_WG), 0, (hipStream_t)stream, groups,
                      n_groups, (long long)n_total, X, out, status);
   return mlbp::launch_verdict("grouped log-posterior");
 }
