@@ -45,6 +45,20 @@ __device__ __forceinline__ double wave_sum(double v) {
   return (read_lane(v, 0) + read_lane(v, 16)) + (read_lane(v, 32) + read_lane(v, 48));
 }
 
+// Sum over the 64 lanes by a __shfl_xor butterfly (ds_bpermute through the LDS crossbar), the same bits in every lane.  It
+// adds in a different order from wave_sum, so the two are not interchangeable where results are compared bitwise.
+__device__ __forceinline__ double wave_sum_xor(double v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+// LDS traffic only: wait for this wave's LDS ops, then the workgroup barrier.  Outstanding global loads (table prefetch)
+// stay in flight across it.
+__device__ __forceinline__ void lds_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
 // acc * m followed by nan_to_num; the three compares only run when some lane of the wave saw a
 // non-finite product (wave-uniform branch).
 __device__ __forceinline__ double mul_nan_to_num(double m, double acc) {
@@ -71,6 +85,17 @@ __device__ __forceinline__ const_i32p as_const(const int32_t* p) {
 typedef const double __attribute__((address_space(4))) * const_f64p;
 __device__ __forceinline__ const_f64p as_const_f64(const double* p) {
   return (const_f64p)(uintptr_t)p;
+}
+
+// 16 consecutive words through the scalar data cache (s_load_dwordx16): wave-uniform program data lands in SGPRs.
+struct Words16 { int32_t w[16]; };
+typedef int v16i __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ Words16 sload16(const int32_t* p) {
+  const v16i v = *(const v16i __attribute__((address_space(4)))*)(uintptr_t)p;
+  Words16 r;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) r.w[i] = v[i];
+  return r;
 }
 
 __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {

@@ -35,14 +35,13 @@
 // the four tables of a factor (k = 0..2 and the normaliser) are one launch (blockIdx.y).
 //
 // Same updates in the same order as every other path (the fused program of build_fused_program); only the summation
-// order inside a contraction differs.  The round-3 overlap experiments that did not pay live in
-// tools/experiments/contract_kernel_r03_variants.hip.
+// order inside a contraction differs.
 #include <hip/hip_runtime.h>
 
-#include <cfloat>
 #include <cstdlib>
 #include <vector>
 
+#include "mlbp_device.h"
 #include "mlbp_internal.h"
 
 namespace mlbp {
@@ -50,20 +49,11 @@ namespace {
 
 constexpr int WG = 256;
 
-__device__ __forceinline__ double nan_to_num(double x) {
-  if (x != x) return 0.0;
-  if (x == __builtin_huge_val()) return DBL_MAX;
-  if (x == -__builtin_huge_val()) return -DBL_MAX;
-  return x;
-}
-
-__device__ __forceinline__ double wave_sum64(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
+using mlbp_dev::nan_to_num;
+using mlbp_dev::wave_sum_xor;
 
 __device__ __forceinline__ double block_sum(double v, double* scratch /*[4]*/) {
-  v = wave_sum64(v);
+  v = wave_sum_xor(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -237,13 +227,10 @@ __device__ __forceinline__ void tiles_to_image(const double4_t (&acc)[RTW][NCT],
 
 // The contraction runs at XA = 64 * RT states; N_T = 16 * NCT graphs per workgroup.  PADDED: the messages have d.X <= XA
 // states (rows of d.X doubles in memory, any parity: 8-byte accesses), the operands are zero beyond.
-// Cache policy of the message traffic of the one-image kernel (MLBP_GEMM_NT: bit 0 source messages by non-temporal loads, bit 1
-// results by non-temporal stores).  Every message of the batch passes through once per update (134 MB at X = 512, B = 8192) and
+// Cache policy of the message traffic of the one-image kernel: source messages by non-temporal loads, results by non-temporal
+// stores.  Every message of the batch passes through once per update (134 MB at X = 512, B = 8192) and
 // the launch is one round of workgroups, all of them in the memory phase at the same time: X = 512 float32 tables 60.9 -> 58.5 us
 // per update, float64 87.1 -> 85.9 (round 4; with the reciprocal-multiply normalisation: from 62.0 / 90.1).
-#ifndef MLBP_GEMM_NT
-#define MLBP_GEMM_NT 3
-#endif
 template <typename TT, int RT, int NCT, int DEPTH, int NW, bool PADDED>
 __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 1) void contract_kernel(ContractDev d) {
   constexpr int XA = 64 * RT, NT_G = 16 * NCT, XP = XA + 2;
@@ -270,12 +257,8 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 1) void contract_kernel(Con
   typedef double nt_d2 __attribute__((ext_vector_type(2)));
   auto load2 = [&](const double* row, int j) {
     if (!PADDED) {
-#if MLBP_GEMM_NT & 1
       const nt_d2 v_ = __builtin_nontemporal_load(reinterpret_cast<const nt_d2*>(row) + lane + 64 * j);
       return make_double2(v_.x, v_.y);
-#else
-      return reinterpret_cast<const double2*>(row)[lane + 64 * j];
-#endif
     }
     const int x0 = 2 * (lane + 64 * j);
     return make_double2(x0 < X ? row[x0] : 0.0, x0 + 1 < X ? row[x0 + 1] : 0.0);
@@ -286,12 +269,8 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 1) void contract_kernel(Con
   };
   auto store2 = [&](double* row, int j, double2 val) {
     if (!PADDED) {
-#if MLBP_GEMM_NT & 2
       nt_d2 x_; x_.x = val.x; x_.y = val.y;
       __builtin_nontemporal_store(x_, reinterpret_cast<nt_d2*>(row) + lane + 64 * j);
-#else
-      reinterpret_cast<double2*>(row)[lane + 64 * j] = val;
-#endif
       return;
     }
     const int x0 = 2 * (lane + 64 * j);
@@ -357,7 +336,7 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 1) void contract_kernel(Con
           double part = 0.0;
 #pragma unroll
           for (int j = 0; j < H; ++j) part += v[u][j].x + v[u][j].y;
-          tot[u] = wave_sum64(part);
+          tot[u] = wave_sum_xor(part);
         }
         // (one division per graph and a multiplication per state: the eight-to-sixteen divisions per lane this was are ~100
         // float64 instructions each side of a launch whose every wave is in this phase at the same time)
@@ -391,11 +370,6 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 1) void contract_kernel(Con
     }
   };
 
-#ifdef MLBP_CONTRACT_NOLOOP          // diagnostic build (tools/contract_probe.py): prologue + epilogue only
-  constexpr int KB_RUN = 4;
-#else
-  constexpr int KB_RUN = KB;
-#endif
   {
     double2 m[PF][GU][H];
     for (int g4 = 0; g4 < GPW; g4 += GU) {
@@ -410,7 +384,7 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 1) void contract_kernel(Con
 #pragma unroll
     for (int c = 0; c < NCT; ++c) acc[r][c] = double4_t{0.0, 0.0, 0.0, 0.0};
   const avec* Af = reinterpret_cast<const avec*>(d.frag) + (size_t)blockIdx.y * d.frag_set / (sizeof(avec) / sizeof(TT));
-  contract_tiles<TT, RTW, NCT, DEPTH, NW, XP>(acc, Af, 0, 0, KB, KB_RUN, Mt, lane, wave);
+  contract_tiles<TT, RTW, NCT, DEPTH, NW, XP>(acc, Af, 0, 0, KB, KB, Mt, lane, wave);
   __syncthreads();
   // ---- epilogue: accumulators -> LDS transposed, renormalise, store whole rows (every wave has read its last message
   //      fragment: the image becomes the output) -- or, `dot` mode, the dot product with another stored message ----
@@ -431,7 +405,7 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 1) void contract_kernel(Con
           const double2 cv = load2(c, j);
           part += cv.x * row[2 * lane + 128 * j] + cv.y * row[2 * lane + 128 * j + 1];
         }
-        tot[u] = wave_sum64(part);
+        tot[u] = wave_sum_xor(part);
       }
 #pragma unroll
       for (int u = 0; u < GU; ++u)
@@ -447,7 +421,7 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 1) void contract_kernel(Con
         v[u][j] = make_double2(row[2 * lane + 128 * j], row[2 * lane + 128 * j + 1]);
         part += v[u][j].x + v[u][j].y;
       }
-      tot[u] = d.normalize ? wave_sum64(part) : 1.0;
+      tot[u] = d.normalize ? wave_sum_xor(part) : 1.0;
     }
 #pragma unroll
     for (int u = 0; u < GU; ++u) {
@@ -529,7 +503,7 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 1) void contract_chunked_ke
       for (int j = 0; j < H; ++j) { part += v[j].x + v[j].y; store2(xo, c * CH, j, v[j]); }
     }
     if (d.normalize) {
-      const double tot = wave_sum64(part), inv = 1.0 / tot;
+      const double tot = wave_sum_xor(part), inv = 1.0 / tot;
       for (int c = 0; c < RP; ++c)
 #pragma unroll
         for (int j = 0; j < H; ++j) {
@@ -595,7 +569,7 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : 1) void contract_chunked_ke
   for (int u = 0; u < GPW; ++u) {
     const int b = b0 + wave * GPW + u;
     if (b >= d.B) continue;
-    const double total = wave_sum64(tot[u]);
+    const double total = wave_sum_xor(tot[u]);
     if (d.dot_slot >= 0) {
       if (lane == 0) d.dots[(size_t)blockIdx.y * d.B + b] = total;
       continue;

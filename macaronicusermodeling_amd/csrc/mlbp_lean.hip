@@ -28,34 +28,15 @@
 using mlbp::fail;
 using namespace mlbp_dev;
 
-// Cache policy (MLBP_LEAN_NT: bit 0 the pairwise tables by non-temporal loads -- per-graph tables are read once: 12.5 -> 13.0 k
-// iterations/s on the default workload --, bit 1 write-back and marginals by non-temporal stores (no effect measured), bit 2 the
-// unary rows by non-temporal loads)
-#ifndef MLBP_LEAN_NT
-#define MLBP_LEAN_NT 1
-#endif
-typedef double nt_d2 __attribute__((ext_vector_type(2)));
-#if MLBP_LEAN_NT & 1
-#define NT_LOAD2(p) ([&] { const nt_d2 v_ = __builtin_nontemporal_load(reinterpret_cast<const nt_d2*>(p)); return make_double2(v_.x, v_.y); }())
-#else
-#define NT_LOAD2(p) (*reinterpret_cast<const double2*>(p))
-#endif
-#if MLBP_LEAN_NT & 4
-#define NT_LOAD1(p) __builtin_nontemporal_load(p)
-#else
-#define NT_LOAD1(p) (*(p))
-#endif
-#if MLBP_LEAN_NT & 2
-#define NT_STORE2(p, v) { const double2 w_ = (v); nt_d2 x_; x_.x = w_.x; x_.y = w_.y; __builtin_nontemporal_store(x_, reinterpret_cast<nt_d2*>(p)); }
-#define NT_STORE1(p, v) __builtin_nontemporal_store((v), (p))
-#else
-#define NT_STORE2(p, v) (*(p) = (v))
-#define NT_STORE1(p, v) (*(p) = (v))
-#endif
-
 namespace {
 
 constexpr int WG = 256;
+
+// Per-graph pairwise tables are read once: non-temporal loads, 12.5 -> 13.0 k iterations/s on the default workload.  (The
+// write-back and marginals by non-temporal stores had no measured effect; the unary rows stay plain loads.)  An immediately
+// invoked lambda: as a __forceinline__ function the same load leaves the kernels with a different register allocation.
+typedef double nt_d2 __attribute__((ext_vector_type(2)));
+#define NT_LOAD2(p) ([&] { const nt_d2 v_ = __builtin_nontemporal_load(reinterpret_cast<const nt_d2*>(p)); return make_double2(v_.x, v_.y); }())
 
 // micro-op word 0
 constexpr int UOP_VAR = 1;          // bit 0: variable product only (stored, no contraction)
@@ -76,39 +57,6 @@ struct LeanDev {
   uint8_t* bail;          // [B]
   int32_t n_bundles, HL, n_cprod, WL, n_ext, init, dense, keep;
 };
-
-// 16 consecutive words through the scalar data cache (s_load_dwordx16): wave-uniform program data lands in SGPRs.
-struct Words16 { int32_t w[16]; };
-typedef int v16i __attribute__((ext_vector_type(16)));
-__device__ __forceinline__ Words16 sload16(const int32_t* p) {
-  const v16i v = *(const v16i __attribute__((address_space(4)))*)(uintptr_t)p;
-  Words16 r;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) r.w[i] = v[i];
-  return r;
-}
-
-// Diagnostic build only (-DMLBP_LEAN_PROBE, tools/lean_probe.py): phase ablation by mask and shader-clock stamps of
-// wave 0 of selected workgroups into a side buffer no other code reads.  Never defined in the shipped library.
-#ifdef MLBP_LEAN_PROBE
-__device__ int g_probe_mask = 0;
-__device__ unsigned long long* g_probe_buf = nullptr;
-#define PROBE_DECL const int probe_mask_ = __builtin_amdgcn_readfirstlane(g_probe_mask); unsigned long long pst_[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; int pn_ = 0;
-#define PROBED(bit) (probe_mask_ & (1 << (bit)))
-#define PSTAMP { unsigned long long _t; __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t) :: "memory"); __builtin_amdgcn_sched_barrier(0); pst_[pn_++] = _t; }
-#define PSTAMP_VM { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); PSTAMP }
-#define PFLUSH if (g_probe_buf && threadIdx.x == 0 && (blockIdx.x & 63) == 0) { unsigned long long _rt; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_rt) :: "memory"); for (int _i = 0; _i < 10; ++_i) g_probe_buf[(blockIdx.x >> 6) * 12 + _i] = pst_[_i]; g_probe_buf[(blockIdx.x >> 6) * 12 + 10] = _rt; }
-#else
-#define PROBE_DECL
-#define PROBED(bit) 0
-#define PSTAMP
-#define PSTAMP_VM
-#define PFLUSH
-#endif
-
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
 
 // a' = [a.row0, b.row0, a.row2, b.row2], b' = [a.row1, b.row1, a.row3, b.row3] (rows of 16 lanes); a' + b'
 __device__ __forceinline__ double swapadd16(double a, double b) {
@@ -518,8 +466,6 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
     G.wr_tm = (lane & 3) == 0;
   }
 
-  PROBE_DECL
-  PSTAMP          // 0: start
   if (t == 0) f.bail[g] = 0;
   int g_kind = 0, g_obs = 0, g_lab = 0;           // GRAD: unary factor t's kind / observed column / label, parked until the
   if (GRAD && t < d.U) {                          // unary rows have landed (the loads retire in order ahead of them)
@@ -542,7 +488,7 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
       if (u >= 0) {
         const int row = f.dense ? g * d.U + u : as_const(d.unary_tab)[(size_t)g * d.U + u];
         if ((unsigned)row >= (unsigned)d.n_unary_tables) ok = false;
-        else if (!PROBED(5) && (!PADX || lane < X)) ur[j] = NT_LOAD1(&d.unary_tables[(size_t)row * X + lane]);
+        else if (!PADX || lane < X) ur[j] = d.unary_tables[(size_t)row * X + lane];
       }
     }
   }
@@ -552,7 +498,6 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
     if (p < d.P) {
       const int ti = f.dense ? g * d.P + p : as_const(d.pair_tab)[(size_t)g * d.P + p];
       if ((unsigned)ti >= (unsigned)d.n_pair_tables) { ok = false; continue; }
-      if (PROBED(4)) continue;
       if (!PADX) {
         const double* T = d.pair_tables + (size_t)ti * 4096 + (size_t)(4 * R_) * 64 + 2 * c_;
 #pragma unroll
@@ -630,7 +575,6 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
     if (t < 32) dst[d.n_msgs * 32 + t] = uni2;                                           // ext slot 0: the uniform vector
     if (t >= 32 && t < 64) dst[(d.n_msgs + f.n_ext - 1) * 32 + (t - 32)] = make_double2(1.0, 1.0);   // last ext slot: ones
   }
-  PSTAMP          // 1: every load issued
   lds_barrier();        // the fill above and the unary messages below write the same slots from different waves
   // hoisted unary messages (exact values: they are outputs); further rounds only when a wave has more than HB rows
 #pragma unroll
@@ -666,7 +610,6 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
       for (int i = t; i < d.n_msgs * X; i += WG) gm[i] = uniform;
     return;
   }
-  PSTAMP          // 2: unary messages normalised
   // constant products: uniform x the hoisted messages a variable multiplies in, in facset order (LBP.py:381-386);
   // lists are 16 words (count, 15 slots padded with the all-ones slot), wave k & 3 takes list k
   for (int k = wave; k < f.n_cprod; k += 4) {
@@ -689,12 +632,6 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
     if (t == 0) f.bail[g] = 1;                    // bail codes: 1 prologue, 2 main loop, 3 final pass
     return;
   }
-  PSTAMP          // 3: constant products
-#ifdef MLBP_LEAN_PROBE
-  PSTAMP_VM       // 4: tables arrived
-#else
-  PSTAMP
-#endif
 
   // ---- main loop: identical in all four waves; one barrier per bundle.  The micro-ops sit in LDS; a bundle's 16 words
   //      are read (broadcast) one bundle ahead ----
@@ -709,7 +646,7 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
   double carry = 1.0;
   const int4* li = reinterpret_cast<const int4*>(limg);
   int4 A0 = li[0], A1 = li[1], B0 = li[2], B1 = li[3];
-  for (int k = 0; k < f.n_bundles && !PROBED(0); ++k) {
+  for (int k = 0; k < f.n_bundles; ++k) {
     const int4 nA0 = li[4 * k + 4], nA1 = li[4 * k + 5], nB0 = li[4 * k + 6], nB1 = li[4 * k + 7];     // the image is padded by one bundle
     const int fA = __builtin_amdgcn_readfirstlane(A0.x), fB = __builtin_amdgcn_readfirstlane(B0.x);
     if (fA & UOP_VAR) {
@@ -749,12 +686,11 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
     return;
   }
   lds_barrier();
-  PSTAMP          // 5: main loop
   // ---- read-out (VariableNode.get_marginal, LBP.py:392-400) straight from the scaled messages: the marginal is
   //      normalised, so the scales cancel; constant part = the variable's constant product ----
   double marg[2] = {0.0, 0.0};
   bool bad_out = !dense_ok;
-  if (f.readout && !PROBED(3)) {
+  if (f.readout) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int v = wave + 4 * j;
@@ -788,7 +724,7 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
   lds_barrier();        // the normalisation below rewrites slots the read-out above has just read
   // ---- the deferred normalisations (only when the messages go back to memory): exactly the slots the program wrote,
   //      wave w takes its WL-entry list, four at a time ----
-  if ((f.keep || GRAD) && !PROBED(1)) {      // (GRAD: the same validity check guards the messages the gradient reads)
+  if (f.keep || GRAD) {      // (GRAD: the same validity check guards the messages the gradient reads)
     for (int j0 = 0; j0 < f.WL; j0 += 4) {
       const const_i32p wl = as_const(img_written + wave * f.WL + j0);
       int slot[4];
@@ -806,7 +742,6 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
         if (slot[j] >= 0) work[slot[j] * 64 + lane] = v[j] / s[j];
     }
   }
-  PSTAMP          // 6: read-out + final normalisation
   if (__syncthreads_or(bad_out ? 1 : 0)) {         // nothing of a flagged graph is written back
     if (t == 0) f.bail[g] = 3;
     return;
@@ -814,27 +749,21 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
   if (f.keep && !PADX) {
     const double2* src = reinterpret_cast<const double2*>(work);
     double2* dst = reinterpret_cast<double2*>(gm);
-    for (int i = t; i < d.n_msgs * 32 && !PROBED(2); i += WG) NT_STORE2(dst + i, src[i]);
+    for (int i = t; i < d.n_msgs * 32; i += WG) dst[i] = src[i];
   } else if (f.keep) {
     for (int i = t; i < d.n_msgs * 64; i += WG)
       if ((i & 63) < X) gm[(size_t)(i >> 6) * X + (i & 63)] = work[i];
   }
-  PSTAMP          // 7: write-back issued
-  if (f.readout && !PROBED(3)) {
+  if (f.readout) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int v = wave + 4 * j;
-      if (v < d.n_vars) NT_STORE1(&d.marginals[((size_t)g * d.n_vars + v) * 64 + lane], marg[j]);
+      if (v < d.n_vars) d.marginals[((size_t)g * d.n_vars + v) * 64 + lane] = marg[j];
     }
   }
-  PSTAMP          // 8: marginals issued
   if (GRAD) {                 // (the verdict barrier above has published the final normalisation)
     gradient_epilogue<NT>(d, gf, tab, reinterpret_cast<const char*>(work), gst, reinterpret_cast<double*>(red), G, g, R_, c_, b3_);
   }
-#ifdef MLBP_LEAN_PROBE
-  PSTAMP_VM       // 9: stores drained
-  PFLUSH
-#endif
 }
 
 }  // namespace
@@ -995,15 +924,6 @@ bool build_lean_readout(const LeanProgram& lp, int n_msgs, int n_vars, const int
   return true;
 }
 
-#ifdef MLBP_LEAN_PROBE
-extern "C" int mlbp_debug_lean_probe(int mask, void* buf) {
-  unsigned long long* p = (unsigned long long*)buf;
-  HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_probe_mask), &mask, sizeof(mask)));
-  HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_probe_buf), &p, sizeof(p)));
-  return MLBP_OK;
-}
-#endif
-
 // Does the lean kernel apply to this (program, arguments) pair?  Fills the device-side descriptions when it does.
 // grad: the call's gradient is fused into the launch (the caller has checked that it can be); a gradient request without
 // it is served by the standalone kernel afterwards, from the messages in memory.
@@ -1021,9 +941,6 @@ static int lean_plan(const mlbp_program* prog, const mlbp_sweep_args* a, bool gr
   *lds = ((size_t)(prog->n_msgs + n_ext) * 64 + 4 * 256) * sizeof(double) + 16 * (size_t)(lp.n_bundles + 1) * sizeof(int32_t);
   if (prog->P == 7 && !padx) *lds += 32 * 1024;   // the seventh table lives in LDS
   if (grad) *lds += 5 * (size_t)prog->U * sizeof(int32_t);
-#ifdef MLBP_LEAN_EXTRA_LDS            // diagnostic build (tools/lean_occupancy.py): fewer workgroups per CU, same kernel
-  *lds += MLBP_LEAN_EXTRA_LDS;
-#endif
   if (*lds > 80 * 1024) return MLBP_OK;           // large graphs: the generic kernel's rules apply
   const bool dense = (a->flags & MLBP_SWEEP_DENSE_TABLES) != 0;
   if (dense && ((int64_t)a->B * prog->P > a->n_pair_tables || (int64_t)a->B * prog->U > a->n_unary_tables))

@@ -6,6 +6,7 @@
 
 #include <cfloat>
 
+#include "mlbp_device.h"
 #include "mlbp_internal.h"
 
 using mlbp::fail;
@@ -21,11 +22,7 @@ int need_device() {
   return MLBP_OK;
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
+using mlbp_dev::wave_sum_xor;
 
 // C[b][i][j] = sum_k A[b][i][k] * B[b][k][j].  One wavefront per output element: lanes stride over
 // k (coalesced when the contraction axis is the contiguous one, as in T.m), then a wave reduction.
@@ -43,7 +40,7 @@ __global__ __launch_bounds__(256) void dense_dot_kernel(int batch, int M, int K,
     const double* bp = B + b * bb + j * bc;
     double acc = 0.0;
     for (int k = lane; k < K; k += 64) acc += a[k * ac] * bp[k * br];
-    acc = wave_sum(acc);
+    acc = wave_sum_xor(acc);
     if (lane == 0) C[b * cb + i * cr + j] = acc;
   }
 }
@@ -83,7 +80,7 @@ __global__ __launch_bounds__(256) void normalize_kernel(const double* in, double
   double* y = out + (int64_t)blockIdx.x * n;
   double acc = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += 256) acc += x[i];
-  acc = wave_sum(acc);
+  acc = wave_sum_xor(acc);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
   __syncthreads();
   const double total = part[0] + part[1] + part[2] + part[3];
@@ -160,7 +157,7 @@ __global__ __launch_bounds__(256) void block_sum_kernel(const double* a, int n_c
   __shared__ double part[4];
   double acc = 0.0;
   for (int e = threadIdx.x; e < Kc * Kr; e += 256) acc += a[(int64_t)cidx[e / Kr] * n_cols + ridx[e % Kr]];
-  acc = wave_sum(acc);
+  acc = wave_sum_xor(acc);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) *total = part[0] + part[1] + part[2] + part[3];
@@ -205,9 +202,9 @@ __global__ void potentials_multi_kernel(PotentialsJobs js) {
       const double v = exp(acc);
       if (pot) pot[e] = v;
       if (pot_t) pot_t[(int64_t)j * 64 + lane] = v;
-      const double Z = wave_sum(v);
+      const double Z = wave_sum_xor(v);
       for (int k = 0; k < J.F && k < 8; ++k) {          // (the features are read again, from L1: kept in an array indexed at run time they live in scratch)
-        const double s = wave_sum(v * ph[k]);
+        const double s = wave_sum_xor(v * ph[k]);
         if (lane == 0) ex[(int64_t)j * 8 + k] = Z > 0.0 ? s / Z : 0.0;          // au.normalize: zero-sum -> 0
       }
     }

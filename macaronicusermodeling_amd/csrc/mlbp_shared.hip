@@ -35,6 +35,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "mlbp_device.h"
 #include "mlbp_internal.h"
 
 namespace mlbp {
@@ -594,24 +595,10 @@ constexpr int G = 16;                 // graphs per workgroup = the N of v_mfma_
 constexpr int TILE = 64 * G;          // doubles per message tile
 constexpr int MW = 4;                 // words per packed member record (build_shared_program); a bundle = 8 words
 
-template <int CTRL>
-__device__ __forceinline__ double dpp_mov(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xF, 0xF, true);
-  hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double read_lane(double v, int lane) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane),
-                          __builtin_amdgcn_readlane(__double2loint(v), lane));
-}
-__device__ __forceinline__ double wave_sum(double v) {      // all 64 lanes, same bits everywhere
-  v += dpp_mov<0xB1>(v);
-  v += dpp_mov<0x4E>(v);
-  v += dpp_mov<0x141>(v);
-  v += dpp_mov<0x140>(v);
-  return (read_lane(v, 0) + read_lane(v, 16)) + (read_lane(v, 32) + read_lane(v, 48));
-}
+using mlbp_dev::as_const;
+using mlbp_dev::const_i32p;
+using mlbp_dev::wave_sum;
+
 // Sum over the four lanes l, l^16, l^32, l^48 (= the four k-rows of one graph column), the same bits in all
 // four: v_permlane16_swap / v_permlane32_swap (gfx950) exchange whole rows of 16 / halves of 32 lanes in the
 // VALU -- with both operands equal the two results are the value of the even and of the odd partner row.
@@ -629,8 +616,6 @@ __device__ __forceinline__ double column_sum(double v) {
 __device__ __forceinline__ bool total_ok(double t) { return t >= 1e-280 && t <= 1e280; }
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
-typedef const int32_t __attribute__((address_space(4))) * const_i32p;
-__device__ __forceinline__ const_i32p as_const(const int32_t* p) { return (const_i32p)(uintptr_t)p; }
 
 // The gradient as the sweep kernel's epilogue (FactorGraph.get_unregularized_gradeint, LBP.py:301-320, beliefs fused in): what
 // gradient_shared_pairs_kernel reads, minus the message buffer -- the final messages are the workgroup's own.
@@ -702,35 +687,6 @@ struct SharedDev {
     acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(A[s_ + 1], b[s_ + 1], acc1, 0, 0, 0); \
   }
 
-#ifdef MLBP_STAMPS
-__device__ unsigned long long* g_sh_stamp = nullptr;
-__device__ int g_sh_ablate = 0;      // timing experiments of tools/stamp_shared.py (results become wrong): 1 no MFMAs, 2 no tile reads, 4 no result stores,
-                                     // 8 / 16 prepare kernel without its row loads / copy-out, 512 no marginal read-out, 1024 no fragment loads, 2048 no main loop
-#define ABL(bit) (abl_ & (bit))
-#define ABL_DECL const int abl_ = __builtin_amdgcn_readfirstlane(g_sh_ablate);
-#ifdef MLBP_STAMPS_LIGHT      // ablations only: no clock reads in the kernel
-#define STAMP_DECL
-#define STAMP_START
-#define STAMP(i)
-#define STAMP_FLUSH
-#define STAMP_FLUSH_GRAD
-#else
-#define STAMP_DECL unsigned long long _t0 = 0, _ph[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#define STAMP_START { __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t0) :: "memory"); __builtin_amdgcn_sched_barrier(0); }
-#define STAMP(i) { unsigned long long _t1; __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t1) :: "memory"); __builtin_amdgcn_sched_barrier(0); _ph[i] += _t1 - _t0; _t0 = _t1; }
-#define STAMP_FLUSH if (g_sh_stamp && blockIdx.x < 64 && (threadIdx.x & 63) == 0) { for (int _i = 0; _i < 8; ++_i) g_sh_stamp[(blockIdx.x * 8 + (threadIdx.x >> 6)) * 12 + _i] = _ph[_i]; }
-#define STAMP_FLUSH_GRAD if (g_sh_stamp && blockIdx.x < 64 && (threadIdx.x & 63) == 0) { for (int _i = 8; _i < 12; ++_i) g_sh_stamp[(blockIdx.x * 8 + (threadIdx.x >> 6)) * 12 + _i] = _ph[_i]; }
-#endif
-#else
-#define ABL(bit) 0
-#define ABL_DECL
-#define STAMP_DECL
-#define STAMP_START
-#define STAMP(i)
-#define STAMP_FLUSH
-#define STAMP_FLUSH_GRAD
-#endif
-
 // Message tiles: 64 states x 16 graphs as [k-step pair sp][lane][2] doubles -- lane l = (state & 3) * 16 + graph, k-step
 // s = state >> 2 -- so that one 16-byte LDS read per lane is two k-steps of the MFMA B operand (the D fragment of row block
 // rb, registers r = 0..3 = k-steps 4 rb + r, goes back as two 16-byte writes).  8-byte accesses in ds_read2 form run at
@@ -787,7 +743,6 @@ constexpr int HDR = 8;
 template <bool MULTI>
 __global__ __launch_bounds__(PWG, 8) void shared_prepare_kernel(PrepareDev d, const PrepareDev* gtab, const int32_t* gstart, int n_groups) {
   extern __shared__ double ptile_lds[];                          // [n_cprod][1024] the group's product tiles, assembled here and stored as whole lines
-  ABL_DECL
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   int block = blockIdx.x, n_blocks = gridDim.x;
   const PrepareDev launch_job = d;
@@ -800,7 +755,7 @@ __global__ __launch_bounds__(PWG, 8) void shared_prepare_kernel(PrepareDev d, co
   // (MULTI: the launch's shared job first -- the by-value description, spread over ALL blocks of the launch: the groups of a
   // minibatch read the same pots, and a table's copies are written once per launch, not once per group -- then the group's own)
   auto fragment_jobs = [&](const PrepareDev& d, const int block, const int n_blocks) {
-    for (int q = block; q < (ABL(16384) ? 0 : 2 * d.n_frag_tables); q += n_blocks) {
+    for (int q = block; q < 2 * d.n_frag_tables; q += n_blocks) {
       const int ti = q >> 1, mt = q & 1;
       const double* T = d.pair_tables + (size_t)ti * 4096;
       double* o = d.tfrag + ((size_t)ti * 2 + mt) * 4096;
@@ -853,11 +808,11 @@ __global__ __launch_bounds__(PWG, 8) void shared_prepare_kernel(PrepareDev d, co
   // (one register -- lanes 0..P-1: this graph's row, lanes 16..16+P-1: the group's first graph's; P <= 16 -- requested here, looked
   // at behind the products: nothing below waits for it, and the kernel's 64 registers hold it without a spill)
   int pair_rows = 0;
-  if (d.header && (lane & 15) < d.P && lane < 32 && !ABL(32768))
+  if (d.header && (lane & 15) < d.P && lane < 32)
     pair_rows = d.pair_tab[(size_t)(lane < 16 ? min(g, d.B - 1) : block * PGB) * d.P + (lane & 15)];
   // lane u holds the table row of the graph's unary factor u (U <= 64: build_shared_program), lane e entry e of the
   // constant-product list; both loads are independent, the entry's row then comes through the lane crossbar
-  int my_row = (on && lane < d.U && !ABL(4096)) ? d.unary_tab[(size_t)g * d.U + lane] : 0;
+  int my_row = (on && lane < d.U) ? d.unary_tab[(size_t)g * d.U + lane] : 0;
   if (on) {
   constexpr int RB = 8;
   constexpr unsigned KEY_LIMIT = 0x7A11A0FCu;                    // high word of 1e280
@@ -887,7 +842,7 @@ __global__ __launch_bounds__(PWG, 8) void shared_prepare_kernel(PrepareDev d, co
       if (kind == 2) u_ed += v; else u_ee += v;
     }
   }
-  for (int c0 = 0; c0 < (ABL(8192) ? 0 : d.E); c0 += 64) {        // (more than 64 entries: a chunk at a time)
+  for (int c0 = 0; c0 < d.E; c0 += 64) {        // (more than 64 entries: a chunk at a time)
     const int el = min(c0 + lane, d.E - 1), n_here = min(64, d.E - c0);
     const int ent_u = c0 == 0 ? ent_u0 : d.ent[4 * el], ent_flags = c0 == 0 ? ent_flags0 : d.ent[4 * el + 3];
     const int row = __shfl(my_row, ent_u);
@@ -911,7 +866,7 @@ __global__ __launch_bounds__(PWG, 8) void shared_prepare_kernel(PrepareDev d, co
 #pragma unroll
       for (int j = 0; j < RB; ++j) {
         const int rj = __builtin_amdgcn_readlane(row, min(b0 + j, b1));
-        r[j] = ABL(8) ? 0.5 : d.unary_tables[(size_t)rj * 64 + lane];
+        r[j] = d.unary_tables[(size_t)rj * 64 + lane];
       }
     };
     auto reduce = [&](const double (&r)[RB], int b0, int b1, bool first, bool last) {
@@ -931,7 +886,7 @@ __global__ __launch_bounds__(PWG, 8) void shared_prepare_kernel(PrepareDev d, co
         // be 1 when it writes the tile out as a message)
         double inv_sum = __builtin_amdgcn_rcp(sum);
         inv_sum = __builtin_fma(__builtin_fma(-sum, inv_sum, 1.0), inv_sum, inv_sum);
-        if (!ABL(65536)) ptile_lds[(size_t)k_out * TILE + tile_index(lane, col)] = cur * inv_sum;
+        ptile_lds[(size_t)k_out * TILE + tile_index(lane, col)] = cur * inv_sum;
         ++k_out;
       }
     };
@@ -972,22 +927,20 @@ __global__ __launch_bounds__(PWG, 8) void shared_prepare_kernel(PrepareDev d, co
     if (lane == 0) { hdr_ok[wave] = all_in_range ? 1 : 0; hdr_same[wave] = all_same ? 1 : 0; }
   }
   __syncthreads();
-  if (!ABL(16)) {
-    const double2* src = reinterpret_cast<const double2*>(ptile_lds);
-    double2* dst = reinterpret_cast<double2*>(d.ptiles + (size_t)block * d.n_cprod * TILE);
-    if (d.sqrt_mask == 0) {
-      for (int i = t; i < d.n_cprod * (TILE / 2); i += PWG) dst[i] = src[i];        // (columns of graphs beyond B: whatever LDS held; never read as results)
-    } else {
-      // a variable with three pairwise factors: the sweep kernel stores sqrt(c) (.) message (build_shared_program, three-source
-      // product-fused form) and wants sqrt(c) here -- taken on the way out, not in the products' loop
-      for (int i = t; i < d.n_cprod * (TILE / 2); i += PWG) {
-        double2 v = src[i];
-        if ((d.sqrt_mask >> (i / (TILE / 2))) & 1) { v.x = sqrt(v.x); v.y = sqrt(v.y); }
-        dst[i] = v;
-      }
+  const double2* src = reinterpret_cast<const double2*>(ptile_lds);
+  double2* dst = reinterpret_cast<double2*>(d.ptiles + (size_t)block * d.n_cprod * TILE);
+  if (d.sqrt_mask == 0) {
+    for (int i = t; i < d.n_cprod * (TILE / 2); i += PWG) dst[i] = src[i];        // (columns of graphs beyond B: whatever LDS held; never read as results)
+  } else {
+    // a variable with three pairwise factors: the sweep kernel stores sqrt(c) (.) message (build_shared_program, three-source
+    // product-fused form) and wants sqrt(c) here -- taken on the way out, not in the products' loop
+    for (int i = t; i < d.n_cprod * (TILE / 2); i += PWG) {
+      double2 v = src[i];
+      if ((d.sqrt_mask >> (i / (TILE / 2))) & 1) { v.x = sqrt(v.x); v.y = sqrt(v.y); }
+      dst[i] = v;
     }
   }
-  if (d.header && wave == PWG / 64 - 1 && !ABL(32768)) {
+  if (d.header && wave == PWG / 64 - 1) {
     // ... and wave 0 finishes it: the distinct tables, which factor reads which, and the partition that splits most bundles
     const bool ok = __all(lane >= PGB || hdr_ok[lane & (PGB - 1)] != 0), same = __all(lane >= PGB || hdr_same[lane & (PGB - 1)] != 0);
     const int d0 = __builtin_amdgcn_readfirstlane(first_row);
@@ -1021,17 +974,6 @@ __global__ __launch_bounds__(PWG, 8) void shared_prepare_kernel(PrepareDev d, co
   }
 }
 
-// 16 consecutive words through the scalar data cache (s_load_dwordx16): wave-uniform program data lands in SGPRs.
-struct Words16 { int32_t w[16]; };
-typedef int v16i __attribute__((ext_vector_type(16)));
-__device__ __forceinline__ Words16 sload16(const int32_t* p) {
-  const v16i v = *(const v16i __attribute__((address_space(4)))*)(uintptr_t)p;
-  Words16 r;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) r.w[i] = v[i];
-  return r;
-}
-
 // The gradient epilogue of the sweep kernel (below).  It forms every lane-derived value again from the thread id: values shared with
 // the code in front of the main loop would be held in registers across it, and the loop's fragments would go to scratch inside the
 // MFMA sequences.  (As a real function call it paid the ABI's callee-saved registers and spills of its own: 70 -> 95 us.)
@@ -1051,9 +993,6 @@ __device__ __forceinline__ void shared_gradient_epilogue(Dev& d, const int wg) {
   const const_i32p img = as_const(d.image);
   const const_i32p row0 = as_const(d.pair_tab + (size_t)g0 * d.P);
   double fr0[16], fr1[16];
-  STAMP_DECL
-  ABL_DECL
-  STAMP_START
   if (DIRECT && t == 0) *reinterpret_cast<double2*>(reinterpret_cast<char*>(lds) + d.lds_bytes - 16) = make_double2(uniform, uniform);
   __syncthreads();
   // factors per pass -- memory form: two tiles each, one tile of partial sums; direct form: what the totals' rows and the spare LDS
@@ -1095,7 +1034,7 @@ __device__ __forceinline__ void shared_gradient_epilogue(Dev& d, const int wg) {
       const int k = 2 * (j / np) + half;
       const double* W = d.gr.wfrag + ((size_t)key(j) * 4 + k) * 4096 + rb * 1024 + lane;
 #pragma unroll
-      for (int s = 0; s < 16; ++s) fr[s] = ABL(256) ? 0.5 : W[64 * s];
+      for (int s = 0; s < 16; ++s) fr[s] = W[64 * s];
     };
     auto run_end = [&](int j) {                                  // first item behind the run that starts at j
       int e = j + 1;
@@ -1115,7 +1054,7 @@ __device__ __forceinline__ void shared_gradient_epilogue(Dev& d, const int wg) {
 #pragma unroll
     for (int j = 0; j < 4 * NPMAX; ++j) {                                // row i = wave + 8 j: tile i >> 4 = j >> 1, graph wave + 8 (j & 1)
       sv[j] = uniform;                                            // never updated: still uniform (LBP.py:211-216)
-      if (j < 4 * np && slots[j >> 1] >= 0 && !ABL(32)) {
+      if (j < 4 * np && slots[j >> 1] >= 0) {
         const int ggc = min(g0 + wave + 8 * (j & 1), d.B - 1);
         sv[j] = d.msgs[((size_t)ggc * d.n_msgs + slots[j >> 1]) * 64 + lane];
       }
@@ -1137,7 +1076,6 @@ __device__ __forceinline__ void shared_gradient_epilogue(Dev& d, const int wg) {
       }
     __syncthreads();
     }
-    STAMP(8)
     // tile q = 2 * factor + side of this pass: where it is read from (16 bytes per lane and k-step pair), and the strides of a read
     auto tile_ptr = [&](int q) -> const double2* {
       if constexpr (DIRECT) {
@@ -1206,7 +1144,7 @@ __device__ __forceinline__ void shared_gradient_epilogue(Dev& d, const int wg) {
       finish(acc, pp, k);
       finish(bcc, pp + 1, k);
     };
-    for (int j = ABL(64) ? n_items : j_first; j < n_items;) {
+    for (int j = j_first; j < n_items;) {
       int e = run_end(j), nx = next_run(e);
       if (nx < n_items) fetchw(fr1, nx);
 #pragma unroll 1
@@ -1222,7 +1160,6 @@ __device__ __forceinline__ void shared_gradient_epilogue(Dev& d, const int wg) {
       j = nx;
     }
     __syncthreads();
-    STAMP(9)
     if (t < np * G) {                                            // label features minus expected features, per (factor, graph)
       const double* rp = red + (size_t)(t >> 4) * 16 * G + (t & 15);
       const double Z = (rp[(12 + 0) * G] + rp[(12 + 1) * G]) + (rp[(12 + 2) * G] + rp[(12 + 3) * G]);
@@ -1243,15 +1180,12 @@ __device__ __forceinline__ void shared_gradient_epilogue(Dev& d, const int wg) {
         for (int k = 0; k < 3; ++k) out3[k] += pc[(pp * G + t) * 3 + k];
       }
     __syncthreads();
-    STAMP(10)
   }
   // the unary factors' terms are in the output already (shared_prepare_kernel: they do not depend on the sweeps)
   if (t < G && g0 + t < d.B) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) d.gr.grad_en_en[(size_t)(g0 + t) * 3 + k] += out3[k];
   }
-  STAMP(11)
-  STAMP_FLUSH_GRAD
 }
 
 // One workgroup = 16 graphs x 8 waves.  Wave w: half h = w >> 2, row block r = w & 3.  Each half keeps TWO of the four
@@ -1290,9 +1224,6 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
   const double uniform = 1.0 / 64.0;
   const const_i32p img = as_const(d.image);
 
-  STAMP_DECL
-  ABL_DECL
-  STAMP_START
   // ---- prologue: ONE round of loads.  shared_prepare_kernel has left the group's header (verdict on the 16 graphs' table
   //      indices, the distinct tables, which factor reads which, the partition of the fragment sets over the halves -- read through
   //      the scalar cache), the constant products as tiles and the per-graph verdicts; the bundle records, the product tiles
@@ -1381,7 +1312,7 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
       // copies in operand order (shared_prepare_kernel): one contiguous 512-byte read per fragment
       const double* F = d.tfrag + ((size_t)ti * 2 + mt) * 4096 + rb * 1024 + lane;
 #pragma unroll
-      for (int s = 0; s < 16; ++s) fr[s] = ABL(1024) ? 0.5 : F[64 * s];
+      for (int s = 0; s < 16; ++s) fr[s] = F[64 * s];
     } else if (ok) {
       const double* T = d.pair_tables + (size_t)ti * 4096;
 #pragma unroll
@@ -1431,10 +1362,8 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
       const int x = i & 63, gg = (i >> 6) & (G - 1), k = i >> 10;
       if (g0 + gg < d.B) d.msgs[((size_t)(g0 + gg) * d.n_msgs + d.image[d.off_fill + k]) * 64 + x] = uniform;
     }
-  STAMP(0)
   __syncthreads();
   if (SPILL) __syncthreads();                                    // (spilled tiles were written through global memory)
-  STAMP(1)
 
   // ---- main loop: one barrier per bundle; a bundle's members go to the halves that hold their fragments ----
   // One member, run by the four waves of a half.  The K = 64 contraction goes in four quarters of four k-steps: a
@@ -1456,7 +1385,7 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
     const bool want = (flags & (4 | 8 | 16)) != 0, mm = (flags & 1) != 0;
     const bool second_set = (flags & 0x80) != 0;                 // (resolved by the prologue)
     const int s0 = w3 & 0xFF, s1 = (w3 >> 8) & 0xFF;
-    const bool has0 = s0 != 0xFF && !ABL(2), has1 = nsrc > 1 && !ABL(2);
+    const bool has0 = s0 != 0xFF, has1 = nsrc > 1;
     // an absent source reads a 16-byte constant instead (every lane the same address, stride 0): {1/64, 1/64} for a first
     // source nothing has updated yet (LBP.py:211-216), {1, 1} for a second one -- so that every read below is
     // unconditional (conditional reads double the live registers)
@@ -1489,7 +1418,6 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
         }
       }
     }
-    STAMP(6)
     double4_t acc = {0.0, 0.0, 0.0, 0.0};
     double part = 0.0;
 #pragma unroll
@@ -1510,7 +1438,7 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
           b[0] = v0.x * scale; b[1] = v0.y * scale; b[2] = v1.x * scale; b[3] = v1.y * scale;
         }
 #pragma unroll 1
-        for (int q = 1; q < nsrc && !ABL(2); ++q) {
+        for (int q = 1; q < nsrc; ++q) {
           const int tl = ((q < 4 ? w3 : w4) >> (8 * (q & 3))) & 0xFF;
           const double2* sq = reinterpret_cast<const double2*>(TP(tl)) + lane + 128 * h;
           const double2 u0 = sq[0], u1 = sq[64];
@@ -1524,10 +1452,8 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
           o[0] = make_double2(b[0], b[1]); o[64] = make_double2(b[2], b[3]);
         }
       }
-      STAMP(2)
       // factor -> variable (LBP.py:500-524): v_mfma_f64_16x16x4_f64 against the resident fragments
-      if (mm && ABL(1)) { acc.x += b[0]; acc.y += b[1]; acc.z += b[2]; acc.w += b[3]; }
-      else if (mm) {
+      if (mm) {
         if (!second_set) {
 #pragma unroll
           for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(fr0[4 * h + i], b[i], acc, 0, 0, 0);
@@ -1536,7 +1462,6 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
           for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(fr1[4 * h + i], b[i], acc, 0, 0, 0);
         }
       }
-      STAMP(7)
     }
     if (want) {
       const double tb = column_sum(part);
@@ -1565,10 +1490,9 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
     if (!mm) return;
     const int dst = w1 & 0xFF;
     double2* out = reinterpret_cast<double2*>(TP(dst)) + 128 * rb + lane;        // D: state 16 rb + (l >> 4) + 4 r = k-step 4 rb + r
-    if (!ABL(4)) { out[0] = make_double2(acc.x, acc.y); out[64] = make_double2(acc.z, acc.w); }
+    out[0] = make_double2(acc.x, acc.y); out[64] = make_double2(acc.z, acc.w);
     const double colsum = column_sum((acc.x + acc.y) + (acc.z + acc.w));
     if (cq == 0) tot[dst * 64 + gl * 4 + rb] = colsum;
-    STAMP(3)
   };
   // Product-fused member (SharedProgram::pf_ok; record layout: build_shared_program).  The input S -- c (.) message, stored by
   // the message's producer -- goes from LDS straight into the matrix cores; the result is multiplied by this wave's 16 rows of
@@ -1592,7 +1516,6 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
     const double2* cs = noC ? dummy + 1 : reinterpret_cast<const double2*>(tiles + (size_t)cd * TILE) + 128 * rb + lane;
     const int cof = noC ? 0 : 64;
     double2 qa0 = src[0], qa1 = src[64], qb0 = src[128], qb1 = src[192], ta = tp[0], tb = tp[1], c0, c1;
-    STAMP(6)
     double4_t acc = {0.0, 0.0, 0.0, 0.0};
     double s = 1.0;
     double k0, k1, k2, k3;
@@ -1622,7 +1545,7 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
     MLBP_PF_QUARTER(FR, 3, qb0, qb1)                                                           \
     __builtin_amdgcn_sched_barrier(0);                                                         \
     k0 = c0.x * s; k1 = c0.y * s; k2 = c1.x * s; k3 = c1.y * s;
-    if (mm && !ABL(1)) {
+    if (mm) {
       if (!second_set) { MLBP_PF_BODY(fr0) } else { MLBP_PF_BODY(fr1) }
     } else {
       MLBP_PF_TOTAL
@@ -1630,7 +1553,6 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
 #undef MLBP_PF_BODY
 #undef MLBP_PF_TOTAL
 #undef MLBP_PF_QUARTER
-    STAMP(7)
     if ((flags & 8) && d.msgs && !(GRAD && d.vf_direct && d.vf_only) && g0 + gl < d.B && !bad) {        // S, normalised, is the last value of a variable->factor slot: to memory
       // (not when only the gradient epilogue wanted it and reads the tiles themselves: vf_direct)
       const double2 v0 = src[128 * rb], v1 = src[128 * rb + 64], t0 = tp[0], t1 = tp[1];      // this wave's rows once more (states 16 rb + cq + 4 r = k-steps 4 rb + r)
@@ -1643,7 +1565,7 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
     if (flags & 64) {
       const double p0 = acc.x * k0, p1 = acc.y * k1, p2 = acc.z * k2, p3 = acc.w * k3;
       double2* out = reinterpret_cast<double2*>(tiles + (size_t)dst * TILE) + 128 * rb + lane;
-      if (!ABL(4)) { out[0] = make_double2(p0, p1); out[64] = make_double2(p2, p3); }
+      out[0] = make_double2(p0, p1); out[64] = make_double2(p2, p3);
       const double colsum = column_sum((p0 + p1) + (p2 + p3));
       if (cq == 0) tot[dst * 64 + gl * 4 + rb] = colsum;
     }
@@ -1651,7 +1573,6 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
       double2* out = stash_g + (size_t)(w2 >> 8) * (TILE / 2) + 128 * rb + lane;
       out[0] = make_double2(acc.x, acc.y); out[64] = make_double2(acc.z, acc.w);
     }
-    STAMP(3)
   };
   // Three-source product-fused member (SharedProgram::p3_ok; record layout: build_shared_program).  The input is the product of
   // one or two tiles (sqrt(c) (.) m_a times sqrt(c) (.) m_b), formed a quarter ahead of the matrix instructions that take it; the
@@ -1694,7 +1615,7 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
           o[0] = make_double2(b0, b1); o[64] = make_double2(b2, b3);
         }
       }
-      if (mm && !ABL(1)) {
+      if (mm) {
 #define MLBP_P3_QUARTER(FR)                                                                    \
           acc = __builtin_amdgcn_mfma_f64_16x16x4f64(FR[4 * h], b0, acc, 0, 0, 0);             \
           acc = __builtin_amdgcn_mfma_f64_16x16x4f64(FR[4 * h + 1], b1, acc, 0, 0, 0);         \
@@ -1741,7 +1662,7 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
   // cost the tile reads behind them nothing (a scalar load from memory would be waited for with them: one counter)
   const int4* li = reinterpret_cast<const int4*>(limg) + half;  // this half's slot of bundle k: li[2 k]
   int4 nx = li[0];
-  for (int k = 0; k < (ABL(2048) ? 0 : d.n_bundles); ++k) {
+  for (int k = 0; k < d.n_bundles; ++k) {
     int cf = __builtin_amdgcn_readfirstlane(nx.x), c1 = __builtin_amdgcn_readfirstlane(nx.y), c2 = __builtin_amdgcn_readfirstlane(nx.z),
         c3 = __builtin_amdgcn_readfirstlane(nx.w);
     const bool chain = (cf & CHAIN) != 0;
@@ -1769,7 +1690,6 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
     } else {
       __syncthreads();
     }
-    STAMP(4)
   }
 
   // ---- epilogue: marginals, message write-back, verdicts ----
@@ -1789,7 +1709,7 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
     if (stash_g) __syncthreads();
     const const_i32p rd = as_const(d.readout);
     double* meet = reinterpret_cast<double*>(reinterpret_cast<char*>(lds) + d.lds_bytes) - 64 * d.n_vars;      // [variable][quarter][graph] partial sums
-    if (d.marginals && !ABL(512)) {
+    if (d.marginals) {
       constexpr int JW = 4;                                      // (4 n_vars <= 32 jobs: n_vars <= 8, shared_plan)
       const int n_jobs = 4 * d.n_vars;
       double m[JW][4];
@@ -1904,7 +1824,7 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
     // results the members stashed in memory: the workgroup's own stores, visible behind the fence of a full barrier.)
     if (stash_g) __syncthreads();
     const const_i32p rd = as_const(d.readout);
-    if (d.marginals && !ABL(512)) {
+    if (d.marginals) {
       // jobs (variable v, quarter h of its states: k-steps 4 h .. 4 h + 3) over the eight waves; a job's values stay in registers
       // while the quarters' column sums meet in LDS (the totals row of the variable's c tile is free: 4 x 16 doubles)
       constexpr int JW = 4;                                      // jobs a wave may hold (4 n_vars <= 32 jobs: n_vars <= 8; beyond, the rest in a second pass)
@@ -2057,14 +1977,13 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
   }
   }   // !PF
   if (bad && gvalid) d.bail[gi] = 2;                             // any wave that saw it says so (idempotent)
-  STAMP(5)
   if constexpr (PF) {
     // the gradient epilogue in front of the marginals' way out: it reads the message tiles (intact: the marginals are staged in
     // the constant products' tiles) and nothing it waits for is behind 12.6 MB of stores
     if constexpr (GRAD) {
       if (d.gr.enabled && d.vf_direct) shared_gradient_epilogue<true, 4>(d, wg);
     }
-    if (d.marginals && !ABL(512)) {
+    if (d.marginals) {
       const const_i32p rd = as_const(d.readout);
       const unsigned long long flagged = __ballot(bad);
       for (int row = wave; row < d.n_vars * G; row += SWG / 64) {
@@ -2076,7 +1995,6 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
     }
   }
   if (!GRAD || !d.gr.enabled) {                                  // (GRAD is a template parameter: the sweeps-only instances do not carry the epilogue's registers)
-    STAMP_FLUSH
     return;
   }
   // ---- gradient epilogue (LBP.py:301-320 over beliefs of LBP.py:528-574): per pairwise factor and feature k
@@ -2086,7 +2004,6 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
   //      Every wave of the workgroup waits for every load here, so the gathers are issued a phase AHEAD of their use: a
   //      pass's labels and first fragment before its messages, its label features behind them.  (The unary factors'
   //      terms do not depend on the sweeps: shared_prepare_kernel has written them, this adds to them.) ----
-  STAMP_FLUSH
   if (!(PF && d.vf_direct)) shared_gradient_epilogue<false, P3 ? 6 : 4>(d, wg);      // (three-source form: 256 registers a wave, six factors -- K4 -- in one pass)
   };
   tail();
@@ -2322,43 +2239,27 @@ int pick_sweep_kernel(bool two, bool spill, bool wide, bool multi, bool grad, bo
   // LDS and the three-source form does not apply.  Should that change, the two-table instances run it (both hold the same table).
   if (spill || wide || p3) two = true;
   if (p3) {                                                      // three-source product-fused form
-#ifdef MLBP_STAMPS
-    return fail(MLBP_EUNSUPPORTED, "stamps build: no three-source instance");
-#else
 #define MLBP_P3(T, M) (grad ? (sweep_fn)sweep_x64_shared_kernel<T, false, false, M, true, true, true> : (sweep_fn)sweep_x64_shared_kernel<T, false, false, M, false, true, true>)
     k = multi ? MLBP_P3(2, true) : MLBP_P3(2, false);
 #undef MLBP_P3
-#endif
-  } else {
-#ifdef MLBP_STAMPS      // the diagnostic build instantiates the all-resident two-source kernels only
-  if (spill || wide || multi) return fail(MLBP_EUNSUPPORTED, "stamps build: no spilling / wide / grouped instance");
-  if (pf)
-    k = two ? (grad ? sweep_x64_shared_kernel<2, false, false, false, true, true> : sweep_x64_shared_kernel<2, false, false, false, false, true>)
-            : (grad ? sweep_x64_shared_kernel<1, false, false, false, true, true> : sweep_x64_shared_kernel<1, false, false, false, false, true>);
-  else
-  k = two ? (grad ? sweep_x64_shared_kernel<2, false, false, false, true> : sweep_x64_shared_kernel<2, false, false, false, false>)
-          : (grad ? sweep_x64_shared_kernel<1, false, false, false, true> : sweep_x64_shared_kernel<1, false, false, false, false>);
-#else
-  if (pf) {
+  } else if (pf) {
 #define MLBP_PK(T, M) (grad ? (sweep_fn)sweep_x64_shared_kernel<T, false, false, M, true, true> : (sweep_fn)sweep_x64_shared_kernel<T, false, false, M, false, true>)
     k = two ? (multi ? MLBP_PK(2, true) : MLBP_PK(2, false)) : (multi ? MLBP_PK(1, true) : MLBP_PK(1, false));
 #undef MLBP_PK
   } else {
-  // (the gradient epilogue comes in two forms: every tile in LDS and two-source updates -- K2, K3 --, or spilled tiles AND
-  // wide updates -- K4 and larger cliques, train_mp.py:272-282: a variable with three pairwise factors has three neighbours, and
-  // four variables' tiles do not fit.  A launch of mixed groups takes the second.)
-  if (grad && spill != wide) { spill = true; wide = true; }
+    // (the gradient epilogue comes in two forms: every tile in LDS and two-source updates -- K2, K3 --, or spilled tiles AND
+    // wide updates -- K4 and larger cliques, train_mp.py:272-282: a variable with three pairwise factors has three neighbours, and
+    // four variables' tiles do not fit.  A launch of mixed groups takes the second.)
+    if (grad && spill != wide) { spill = true; wide = true; }
 #define MLBP_SK(T, S, W, M) (grad ? grad_instance<T, S, W, M>() : (sweep_fn)sweep_x64_shared_kernel<T, S, W, M, false>)
 #define MLBP_SK_M(T, S, W) (multi ? MLBP_SK(T, S, W, true) : MLBP_SK(T, S, W, false))
 #define MLBP_SK_W(T, S) (wide ? MLBP_SK_M(T, S, true) : MLBP_SK_M(T, S, false))
 #define MLBP_SK_S(T) (spill ? MLBP_SK_W(T, true) : MLBP_SK_W(T, false))
-  k = two ? MLBP_SK_S(2) : MLBP_SK_M(1, false, false);
+    k = two ? MLBP_SK_S(2) : MLBP_SK_M(1, false, false);
 #undef MLBP_SK_S
 #undef MLBP_SK_W
 #undef MLBP_SK_M
 #undef MLBP_SK
-  }
-#endif
   }
   bool fresh = false;
   if (int e = grant_lds((const void*)k, lds, &fresh)) return e;
@@ -2735,11 +2636,4 @@ int launch_shared_pair_gradient(const mlbp_gradient_args* a, int32_t* status, vo
   return MLBP_OK;
 }
 
-#ifdef MLBP_STAMPS
-extern "C" int mlbp_debug_set_shared_stamp_buffer(void* dev_ptr, int ablate_mask) {
-  unsigned long long* p = (unsigned long long*)dev_ptr;
-  if (hipMemcpyToSymbol(HIP_SYMBOL(g_sh_ablate), &ablate_mask, sizeof(int)) != hipSuccess) return -1;
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_sh_stamp), &p, sizeof(p)) == hipSuccess ? 0 : -1;
-}
-#endif
 }  // namespace mlbp

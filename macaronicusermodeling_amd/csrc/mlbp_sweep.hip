@@ -70,33 +70,6 @@ __device__ __forceinline__ bool tables_in_range(const SweepDev& d, int g) {
 //     register prefetch as before;
 //   * init != 0 starts from uniform messages instead of reading them (FactorGraph.initialize fused).
 // ------------------------------------------------------------------------------------------------
-// Diagnostic build only (-DMLBP_STAMPS, tools/stamp_profile.py): per-phase shader-clock sums of
-// workgroup 0..15's wave 0 go to a side buffer that no other code reads.  Never defined in the
-// shipped library.
-#ifdef MLBP_STAMPS
-__device__ unsigned long long* g_stamp_buf = nullptr;
-#define STAMP_DECL unsigned long long _t0 = 0, _ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define STAMP_START { __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t0) :: "memory"); __builtin_amdgcn_sched_barrier(0); }
-#define STAMP(i) { unsigned long long _t1; __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t1) :: "memory"); __builtin_amdgcn_sched_barrier(0); _ph[i] += _t1 - _t0; _t0 = _t1; }
-#define STAMP_FLUSH if (g_stamp_buf && blockIdx.x < 64 && threadIdx.x == 0) { for (int _i = 0; _i < 8; ++_i) g_stamp_buf[blockIdx.x * 8 + _i] = _ph[_i]; }
-#else
-#define STAMP_DECL
-#define STAMP_START
-#define STAMP(i)
-#define STAMP_FLUSH
-#endif
-
-// Diagnostic build only (-DMLBP_ABLATE, tools/ablate_profile.py): MLBP_ABLATE_MASK removes one phase
-// of the fused kernel at a time (results become wrong; only the timing delta matters).
-#ifdef MLBP_ABLATE
-__device__ int g_ablate_mask = 0;
-#define ABLATED(bit) (ablate_mask_ & (1 << (bit)))
-#define ABLATE_DECL const int ablate_mask_ = __builtin_amdgcn_readfirstlane(g_ablate_mask);
-#else
-#define ABLATED(bit) 0
-#define ABLATE_DECL
-#endif
-
 // VariableNode.get_marginal (LBP.py:392-400) for every variable of the graph, straight from the
 // normalised messages in LDS: uniform x incoming messages in facset order, nan_to_num after each
 // product, renormalise.  Wave w takes variables w, w+4, ...
@@ -137,12 +110,6 @@ struct FusedDev {
   int32_t n_graphs;        // B
 };
 constexpr int FIXUP_GRAPHS_PER_WG = 64;
-
-__device__ __forceinline__ void wg_barrier() {
-  // LDS traffic only: wait for this wave's LDS ops, then the workgroup barrier.  Outstanding
-  // global loads (table prefetch) stay in flight across it.
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
 
 template <bool MT>
 __device__ __forceinline__ void pair_partials(const double2 (&T)[8], const double* m, double* red, int rg, int cp,
@@ -295,7 +262,7 @@ __device__ __forceinline__ void gradient_epilogue_x64(const SweepDev& d, const G
 #pragma unroll
     for (int f = 0; f < FED; ++f) o[NT * (FEE + 1) + FEE + f] = ued[f];
   }
-  wg_barrier();
+  lds_barrier();
   if (t == 0) {
     double tot[PER];
 #pragma unroll
@@ -350,9 +317,6 @@ __device__ __forceinline__ void sweep_x64_fused_body(const SweepDev& d, const Fu
   int32_t* umsg = flags + 4;                            // [U] message slot of each unary factor's message
   int32_t* upos = umsg + d.U;                           // [U] 1 when that factor's table total was positive
 
-  STAMP_DECL
-  ABLATE_DECL
-  STAMP_START
   const int t = threadIdx.x;
   const int lane = t & 63, wave = t >> 6;
   const int rg = t >> 5, cp = t & 31;
@@ -434,7 +398,7 @@ __device__ __forceinline__ void sweep_x64_fused_body(const SweepDev& d, const Fu
       }
     }
   }
-  wg_barrier();
+  lds_barrier();
   // constant products: uniform times the hoisted messages a variable multiplies in, in facset
   // order with nan_to_num after each product (the constant prefix of LBP.py:381-386)
   {
@@ -455,8 +419,7 @@ __device__ __forceinline__ void sweep_x64_fused_body(const SweepDev& d, const Fu
       at += 1 + cnt;
     }
   }
-  wg_barrier();
-  STAMP(0)   // prologue
+  lds_barrier();
 
   // Main loop.  Wave 0 is the graph's "vector wave": it alone runs the 64-element work on the
   // critical path of every update (variable product, gathering the partial sums, normalising the
@@ -468,8 +431,6 @@ __device__ __forceinline__ void sweep_x64_fused_body(const SweepDev& d, const Fu
       const int4 h0 = reinterpret_cast<const int4*>(prog)[2 * o];
       const int4 h1 = reinterpret_cast<const int4*>(prog)[2 * o + 1];
       const int kind = __builtin_amdgcn_readfirstlane(h0.x) & 0xFF;
-      STAMP(1)   // op header
-      if (ABLATED(5)) continue;
       if (kind == FOP_UNARY) {
         if (wave == 0) {
           const int us = __builtin_amdgcn_readfirstlane(h0.y), c = __builtin_amdgcn_readfirstlane(h0.w);
@@ -488,24 +449,15 @@ __device__ __forceinline__ void sweep_x64_fused_body(const SweepDev& d, const Fu
           // finite and non-negative and the product is not identically zero; then the product's
           // scale cancels in the normalised pairwise update, so the contraction takes it
           // unnormalised and wave 1 normalises and stores the variable->factor message meanwhile
-          const int a = __builtin_amdgcn_readfirstlane(h0.y), n = ABLATED(0) ? 0 : __builtin_amdgcn_readfirstlane(h0.z);
+          const int a = __builtin_amdgcn_readfirstlane(h0.y), n = __builtin_amdgcn_readfirstlane(h0.z);
           const int4 s4 = *reinterpret_cast<const int4*>(psrcs + a);
-          double acc = ABLATED(0) ? uniform : msg[s4.x * 64 + lane];
+          double acc = msg[s4.x * 64 + lane];
           if (n > 1) acc *= msg[s4.y * 64 + lane];
           if (n > 2) acc *= msg[s4.z * 64 + lane];
           if (n > 3) acc *= msg[s4.w * 64 + lane];
           for (int q = 4; q < n; ++q) acc *= msg[psrcs[a + q] * 64 + lane];
-          const bool fast = ABLATED(6) ? true : (__all(acc >= 0.0 && acc < __builtin_huge_val()) && __any(acc > 0.0));
-          STAMP(2)   // variable product
-#ifdef MLBP_STAMPS
-          if (!fast) _ph[2] += (1ULL << 40);
-          if (!__all(acc >= 0.0)) _ph[2] += (1ULL << 44);
-          if (!__all(acc < __builtin_huge_val())) _ph[2] += (1ULL << 48);
-          if (!__any(acc > 0.0)) _ph[2] += (1ULL << 52);
-#endif
-          if (ABLATED(7)) {
-            asm volatile("" ::"v"(acc));
-          } else if (fast && kind != FOP_VAR) {
+          const bool fast = __all(acc >= 0.0 && acc < __builtin_huge_val()) && __any(acc > 0.0);
+          if (fast && kind != FOP_VAR) {
             gin[lane] = acc;
             if (lane == 0) flags[0] = 0;
           } else {
@@ -518,7 +470,6 @@ __device__ __forceinline__ void sweep_x64_fused_body(const SweepDev& d, const Fu
             gin[lane] = mn;
             if (lane == 0) flags[0] = 1;
           }
-          STAMP(3)   // (slow path only) normalisation
         }
         if (kind == FOP_VAR) continue;
         m = gin;
@@ -530,10 +481,8 @@ __device__ __forceinline__ void sweep_x64_fused_body(const SweepDev& d, const Fu
         dst = c;
       }
       const bool mt = (kind == FOP_PAIR_MT || kind == FOP_VAR_PAIR_MT);
-      if (!ABLATED(4)) wg_barrier();          // the input vector (and every earlier vector-wave store) is visible
-      STAMP(5)   // barrier
-      if (ABLATED(1)) {
-      } else if (NT > 0) {
+      lds_barrier();         // the input vector (and every earlier vector-wave store) is visible
+      if (NT > 0) {
 #pragma unroll
         for (int p = 0; p < NT; ++p) {
           if (p == pslot) {
@@ -556,17 +505,13 @@ __device__ __forceinline__ void sweep_x64_fused_body(const SweepDev& d, const Fu
         if (mt) pair_partials<true>(cur, m, red, rg, cp, lane);
         else pair_partials<false>(cur, m, red, rg, cp, lane);
       }
-      if (!ABLATED(3) && from_var && wave == 1 && flags[0] == 0) {
+      if (from_var && wave == 1 && flags[0] == 0) {
         // off the critical path: normalise and store the variable->factor message (LBP.py:387-389)
         const double v = gin[lane];
         msg[c * 64 + lane] = renorm(v, wave_sum(v), uniform, NORM);
       }
-      STAMP(4)   // partial sums
-      if (!ABLATED(4)) wg_barrier();          // partial sums are in LDS
-      STAMP(5)   // barrier
-      if (wave == 0 && ABLATED(2)) {
-        if (!ABLATED(8)) msg[dst * 64 + lane] = uniform;
-      } else if (wave == 0) {
+      lds_barrier();         // partial sums are in LDS
+      if (wave == 0) {
         double r;
         if (mt) {
           r = 0.0;
@@ -575,14 +520,11 @@ __device__ __forceinline__ void sweep_x64_fused_body(const SweepDev& d, const Fu
         } else {
           r = red[lane] + red[64 + lane];
         }
-        STAMP(6)   // gather partials
         msg[dst * 64 + lane] = renorm(r, wave_sum(r), uniform, NORM);
-        STAMP(7)   // normalise
       }
     }
   }
-  STAMP_FLUSH
-  wg_barrier();
+  lds_barrier();
   {
     const double2* src = reinterpret_cast<const double2*>(msg);
     double2* dst = reinterpret_cast<double2*>(gm);
@@ -1926,21 +1868,6 @@ int mlbp_sweep_groups_f64(const mlbp_program* const* progs, const mlbp_sweep_arg
     if (int e = run_sweep(progs[k], &args[k], pass, variant, stream)) return e;
   return MLBP_OK;
 }
-
-#ifdef MLBP_ABLATE
-int mlbp_debug_set_ablate_mask(int mask) {
-  HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_ablate_mask), &mask, sizeof(mask)));
-  return MLBP_OK;
-}
-#endif
-
-#ifdef MLBP_STAMPS
-int mlbp_debug_set_stamp_buffer(void* dev_ptr) {
-  unsigned long long* p = (unsigned long long*)dev_ptr;
-  HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_buf), &p, sizeof(p)));
-  return MLBP_OK;
-}
-#endif
 
 }  // extern "C"
 
