@@ -274,26 +274,29 @@ int mlbp_sweep_f64(const mlbp_program* prog, const mlbp_sweep_args* a, void* str
 /* A minibatch of mixed graphs in one go: n_groups (program, arguments) pairs -- every group its own topology, root
  * sequence (the reference draws a fresh root per instance and sweep, LBP.py:223-225, and builds a different K_n per
  * instance, train_mp.py:257-299), tables and message buffer.  Equivalent to calling mlbp_sweep_f64 on the groups one
- * after the other, in fewer launches:
- *   - every group states MLBP_SWEEP_SHARED_PAIR_TABLES and qualifies for the shared-table kernel (X = 64, normalised and
- *     initialised messages, distinct programs): ONE prepare launch and one sweep launch per FORM of the kernel present
- *     among the groups (product-fused / its three-source variant / general; MLBP_KERNEL_SHARED_MFMA behind a group table: a
- *     workgroup looks its group up by block index) cover ALL groups -- with more than one form the product-fused launch runs on
- *     a side stream of progs[0], forked behind the prepare launch and joined before the call returns to `stream` (a stream
- *     capture records two parallel kernel nodes); groups that name the same tables and feature tensors share one set of
- *     fragment copies (written once per launch, owned by the first such group's program); a group WITHOUT pairwise factors (one
- *     predicted word) may be among them: all its graphs are flagged and redone by the fix-up launch; what follows per group is its fix-up
- *     pass over flagged graphs, its unary write-back when messages are kept, its gradient when args[k].gradient is set and
- *     its posterior (a launch of its own) when args[k].posterior is set -- a minibatch of mixed sentence shapes over the
- *     two shared pots (train_mp.py:220-299);
- *   - otherwise, when every group qualifies for the lean X = 64 kernel (float64 tables, normalised messages, at most 8
- *     pairwise factors, the same init / write-back / read-out choices, distinct programs) that kernel runs ALL groups in
- *     a single launch, followed by one small fix-up launch (and the gradient, if any) per group;
- *   - otherwise group by group.
+ * after the other, in fewer launches.  The library decides group by group which path takes it, and runs the groups in
+ * three disjoint sets, in this order:
+ *   1. the shared-table launch: the groups that state MLBP_SWEEP_SHARED_PAIR_TABLES and qualify for the shared-table kernel
+ *      (X = 64, normalised and initialised messages), with the groups WITHOUT pairwise factors (one predicted word; X = 64,
+ *      normalised and initialised messages) riding along -- used when at least one group with pairwise factors qualifies.
+ *      ONE prepare launch and one sweep launch per FORM of the kernel present among them (product-fused / its three-source
+ *      variant / general; MLBP_KERNEL_SHARED_MFMA behind a group table: a workgroup looks its group up by block index) -- with
+ *      more than one form the product-fused launch runs on a side stream of progs[0], forked behind the prepare launch and
+ *      joined before the call returns to `stream` (a stream capture records two parallel kernel nodes); groups that name the
+ *      same tables and feature tensors share one set of fragment copies (written once per launch, owned by the first such
+ *      group's program); a rider's graphs are all flagged and redone by the fix-up launch; what follows per group is its
+ *      fix-up pass over flagged graphs, its unary write-back when messages are kept, its gradient when args[k].gradient is set
+ *      and its posterior (a launch of its own) when args[k].posterior is set -- a minibatch of mixed sentence shapes over the
+ *      two shared pots (train_mp.py:220-299);
+ *   2. the grouped lean launch: of the groups left, those that qualify for the lean X = 64 kernel (float64 tables, normalised
+ *      messages, 1 to 8 pairwise factors) and make the same init / write-back / read-out choices as the first of them, in a
+ *      single launch, followed by one small fix-up launch (and the gradient, if any) per group;
+ *   3. every other group, as a separate call, in group order.
+ * A program joins the first two sets once at most: a later group naming the same program is in the third.
  * Every group's arguments are checked as mlbp_sweep_f64 checks them before anything is enqueued: one bad group fails the call
  * with that message and runs nothing.
- * progs / args are HOST arrays.  The group table is device memory owned by progs[0], uploaded only when its contents
- * differ from the previous call's (a stream capture of a repeated call records no copy). */
+ * progs / args are HOST arrays.  The group tables are device memory owned by progs[0] (whichever set that group is in),
+ * uploaded only when their contents differ from the previous call's (a stream capture of a repeated call records no copy). */
 int mlbp_sweep_groups_f64(const mlbp_program* const* progs, const mlbp_sweep_args* args, int32_t n_groups, void* stream);
 
 /* Kernel selector for the parity tests (process-wide; not needed in normal use):
@@ -308,7 +311,9 @@ int mlbp_sweep_groups_f64(const mlbp_program* const* progs, const mlbp_sweep_arg
 int mlbp_set_sweep_variant(int32_t variant);
 
 /* Diagnostic: which kernel family the calling thread's last mlbp_sweep_f64 enqueued first (the exact
- * kernel may follow it for flagged graphs); -1 before the first call.  (0 and 1 were the first-generation and the first
+ * kernel may follow it for flagged graphs); -1 before the first call.  After mlbp_sweep_groups_f64: the family of the call's
+ * last launch sequence, in the order it runs them (shared-table, grouped lean, the others) -- a call that one path takes whole
+ * reports that path.  mlbp_last_sweep_fused_gradient follows the same rule.  (0 and 1 were the first-generation and the first
  * scale-free kernel, retired.) */
 #define MLBP_KERNEL_EXACT 2
 #define MLBP_KERNEL_SHARED_MFMA 3

@@ -468,8 +468,9 @@ class FactorGraphBatch:
 def sweep_groups(batches, roots, init=False, marginals=None, keep_messages=True, gradients=None, posteriors=None):
     """One minibatch of mixed graphs: batches[k] (a FactorGraphBatch: one topology, its tables and messages) is swept
     with its own root sequence roots[k] -- the reference draws roots per instance (LBP.py:223-225) and builds a
-    different K_n per instance (train_mp.py:257-299).  Same results as batches[k].sweep(roots[k], ...) one by one; when
-    every group qualifies, the fast kernel runs them all in ONE launch (mlbp_sweep_groups_f64).
+    different K_n per instance (train_mp.py:257-299).  Same results as batches[k].sweep(roots[k], ...) one by one, in fewer
+    launches: the library (mlbp_sweep_groups_f64) decides group by group which fast kernel takes it, runs the groups each kernel
+    takes in ONE launch sequence and the others as separate calls behind them.
     marginals: None or one [B_k][n_vars_k][X] tensor per group; gradients: None or one (g_en_en, g_en_de) pair per group
     (each group's gradient launch follows its sweeps, as in FactorGraphBatch.sweep(gradient=...)); posteriors: None or one
     (labels, out, sum_out) per group, as in FactorGraphBatch.sweep(posterior=...)."""

@@ -64,8 +64,9 @@ bool build_lean_readout(const LeanProgram& lp, int n_msgs, int n_vars, const int
 // Enqueues the lean scale-free kernel when it applies (sets *launched); flagged graphs are left in prog->d_bail.
 // gf != NULL: the call's gradient runs as the kernel's epilogue (P <= 3, every unary message hoisted, F = (3, 6)).
 int launch_lean_sweep(const mlbp_program* prog, const mlbp_sweep_args* a, const mlbp_dev::GradFusedDev* gf, void* stream, bool* launched);
-// The same for several (program, arguments) groups in one launch; *launched false = some group does not qualify.
-int launch_lean_groups(const mlbp_program* const* progs, const mlbp_sweep_args* args, int n_groups, void* stream, bool* launched);
+// The same for several (program, arguments) groups in one launch.  member: in, the groups offered; out, the groups launched
+// (a group that does not qualify is left out, not the call).
+int launch_lean_groups(const mlbp_program* const* progs, const mlbp_sweep_args* args, int n_groups, void* stream, std::vector<char>& member);
 
 // Shared-table (MFMA) form, mlbp_shared.hip: 16 graphs per workgroup, messages kept as [state][graph]
 // tiles in LDS, only the "live" slots (read or written inside the sweeps) resident.
@@ -107,8 +108,9 @@ bool exact_kernel_fuses_gradient(const mlbp_program* prog, const mlbp_sweep_args
 int gradient_flagged_only(const mlbp_gradient_args* a, const uint8_t* flags, void* stream);
 // The same for n_groups groups in ONE launch (table cached with `owner`'s group tables).
 int gradient_flagged_groups(const mlbp_gradient_args* args, const uint8_t* const* flags, int n_groups, mlbp_program* owner, void* stream);
-// The same for several (program, arguments) groups in one launch sequence; *launched false = some group does not qualify.
-int launch_shared_groups(const mlbp_program* const* progs, const mlbp_sweep_args* args, int n_groups, void* stream, bool* launched);
+// The same for several (program, arguments) groups in one launch sequence.  member: in, the groups offered; out, the groups
+// launched (a group that does not qualify is left out, not the call).
+int launch_shared_groups(const mlbp_program* const* progs, const mlbp_sweep_args* args, int n_groups, void* stream, std::vector<char>& member);
 // Pairwise part of the gradient for shared tables (X = 64, F_ee = 3), ADDED to a->grad_en_en.
 int launch_shared_pair_gradient(const mlbp_gradient_args* a, int32_t* status, void* stream);
 // Shared tables at X = 128 .. 512: the sweeps update by update over the whole batch, every contraction one launch of the

@@ -1017,34 +1017,35 @@ int launch_lean_sweep(const mlbp_program* prog, const mlbp_sweep_args* a, const 
   return MLBP_OK;
 }
 
-// Several (program, arguments) groups in ONE launch of the lean kernel.  *launched stays false when some group does not
-// qualify (the caller then runs the groups one by one).  The group table lives in a device buffer owned by the FIRST
-// program of the call (like its redo flags: one stream at a time per program) and is uploaded only when its contents
-// differ from the last call's, so a repeated call -- the trainer's every step -- is enqueue-only and can be captured
-// into a HIP graph after one warm-up call.
-int launch_lean_groups(const mlbp_program* const* progs, const mlbp_sweep_args* args, int n_groups, void* stream, bool* launched) {
-  *launched = false;
-  if (n_groups < 1) return MLBP_OK;
-  std::vector<int32_t> table((size_t)n_groups * GROUP_WORDS, 0);
+// Several (program, arguments) groups in ONE launch of the lean kernel.  member: in, the groups offered (distinct programs);
+// out, the groups the launch runs -- those the kernel takes that make the same init / write-back / read-out choices as the first
+// of them (none: nothing is launched).  The group table lives in a device buffer owned by the FIRST program of the call (like
+// its redo flags: one stream at a time per program) and is uploaded only when its contents differ from the last call's, so a
+// repeated call -- the trainer's every step -- is enqueue-only and can be captured into a HIP graph after one warm-up call.
+int launch_lean_groups(const mlbp_program* const* progs, const mlbp_sweep_args* args, int n_groups, void* stream, std::vector<char>& member) {
+  std::vector<int32_t> table;
   size_t lds_max = 0;
-  int p_max = 0, total = 0;
+  int p_max = 0, total = 0, n_in = 0;
   SweepDev d0;
   LeanDev f0;
   for (int k = 0; k < n_groups; ++k) {
-    if (!progs[k] || args[k].X != 64) return MLBP_OK;
-    for (int j = 0; j < k; ++j)
-      if (progs[j] == progs[k]) return MLBP_OK;      // two groups would share one set of redo flags
+    if (!member[k]) continue;
+    member[k] = 0;
+    if (args[k].X != 64) continue;
     SweepDev d;
     LeanDev f;
     size_t lds = 0;
     bool ok = false;
     if (int e = lean_plan(progs[k], &args[k], false, &ok, &d, &f, &lds)) return e;
-    if (!ok) return MLBP_OK;
-    if (k == 0) { d0 = d; f0 = f; }
-    else if (f.init != f0.init || f.keep != f0.keep || (f.readout != nullptr) != (f0.readout != nullptr)) return MLBP_OK;
+    if (!ok) continue;
+    if (n_in == 0) { d0 = d; f0 = f; }
+    else if (f.init != f0.init || f.keep != f0.keep || (f.readout != nullptr) != (f0.readout != nullptr)) continue;
+    member[k] = 1;
+    ++n_in;
     lds_max = std::max(lds_max, lds + (progs[k]->P < 7 ? 32 * 1024 : 0));      // (a 7-table group may sit beside it: its LDS table)
     p_max = std::max(p_max, (int)progs[k]->P);
-    int32_t* w = &table[(size_t)k * GROUP_WORDS];
+    table.resize(table.size() + GROUP_WORDS, 0);
+    int32_t* w = &table[table.size() - GROUP_WORDS];
     auto put = [&](int at, const void* p) { const uintptr_t v = (uintptr_t)p; w[at] = (int32_t)(uint32_t)v; w[at + 1] = (int32_t)(uint32_t)(v >> 32); };
     w[0] = total; w[1] = args[k].B;
     put(2, f.image); put(4, f.readout); put(6, f.bail); put(8, d.msgs); put(10, d.marginals); put(12, d.pair_tables);
@@ -1053,6 +1054,7 @@ int launch_lean_groups(const mlbp_program* const* progs, const mlbp_sweep_args* 
     w[30] = d.n_vars; w[31] = d.n_pair_tables; w[32] = d.n_unary_tables; w[33] = f.dense;
     total += args[k].B;
   }
+  if (n_in == 0) return MLBP_OK;
   // one device copy per distinct table (stream-ordered upload on first sight, none afterwards): a captured graph keeps its own
   mlbp_program* owner = const_cast<mlbp_program*>(progs[0]);
   int32_t* d_gtable = nullptr;
@@ -1060,10 +1062,8 @@ int launch_lean_groups(const mlbp_program* const* progs, const mlbp_sweep_args* 
   lean_fn k = pick_lean<true>(p_max, false);
   if (int e = grant_lds((const void*)k, lds_max)) return e;
   launch_begin();
-  MLBP_LAUNCH(k, dim3(total), dim3(WG), lds_max, (hipStream_t)stream, d0, f0, d_gtable, n_groups, GradFusedDev{});
-  if (int e = launch_verdict("grouped lean sweep")) return e;
-  *launched = true;
-  return MLBP_OK;
+  MLBP_LAUNCH(k, dim3(total), dim3(WG), lds_max, (hipStream_t)stream, d0, f0, d_gtable, n_in, GradFusedDev{});
+  return launch_verdict("grouped lean sweep");
 }
 
 }  // namespace mlbp

@@ -2449,36 +2449,36 @@ int launch_shared_sweep(const mlbp_program* prog, const mlbp_sweep_args* a, void
 }
 
 // Several (program, arguments) groups in ONE launch sequence (prepare + sweeps) of the shared-table kernels -- a minibatch of
-// mixed sentence shapes whose pairwise factors all read the two shared pots (train_mp.py:220-255, 257-299).  *launched stays
-// false when some group does not qualify.  The group tables live in a device buffer owned by the first program and are
-// uploaded only when their contents change (like the lean kernel's).
-int launch_shared_groups(const mlbp_program* const* progs, const mlbp_sweep_args* args, int n_groups, void* stream, bool* launched) {
-  *launched = false;
-  if (n_groups < 1) return MLBP_OK;
+// mixed sentence shapes whose pairwise factors all read the two shared pots (train_mp.py:220-255, 257-299).  member: in, the
+// groups offered (distinct programs); out, the groups the sequence runs -- those shared_plan accepts, and the pairwise-free ones
+// that ride along -- or none when no group with pairwise factors qualifies.  The group tables live in a device buffer owned by
+// the first program of the call and are uploaded only when their contents change (like the lean kernel's).
+int launch_shared_groups(const mlbp_program* const* progs, const mlbp_sweep_args* args, int n_groups, void* stream, std::vector<char>& member) {
   std::vector<SharedPlan> plans(n_groups);
   int max_cprod = 1, n_planned = 0;
   for (int k = 0; k < n_groups; ++k) {
-    if (!progs[k]) return MLBP_OK;
-    for (int j = 0; j < k; ++j)
-      if (progs[j] == progs[k]) return MLBP_OK;      // two groups would share one set of redo flags and scratch
+    if (!member[k]) continue;
+    const mlbp_sweep_args* a = &args[k];
     if (progs[k]->P == 0) {
       // a sentence shape with ONE predicted word: no pairwise factor, nothing for the matrix cores.  Every graph of such a group is
       // handed to the fix-up pass of the call (the exact kernel over all groups' flagged graphs, and the flagged graphs' gradient:
       // finish_shared_groups) -- its launches are shared with every other group instead of two launches per such shape
-      const mlbp_sweep_args* a = &args[k];
-      if (a->X != 64 || !a->normalize_messages || !a->init_messages) return MLBP_OK;
-      memset(&plans[k], 0, sizeof(plans[k]));
+      member[k] = a->X == 64 && a->normalize_messages && a->init_messages;
       continue;
     }
     bool ok = false;
-    if (int e = shared_plan(progs[k], &args[k], &ok, &plans[k])) return e;
-    if (!ok) return MLBP_OK;
+    if (int e = shared_plan(progs[k], a, &ok, &plans[k])) return e;
+    member[k] = ok;
+    if (!ok) continue;
     ++n_planned;
     max_cprod = std::max(max_cprod, (int)plans[k].q.n_cprod);
   }
-  if (n_planned == 0) return MLBP_OK;                            // (nothing for these kernels: the per-group path)
+  if (n_planned == 0) {                                          // (nothing for these kernels: no rider runs here either)
+    std::fill(member.begin(), member.end(), 0);
+    return MLBP_OK;
+  }
   for (int k = 0; k < n_groups; ++k)
-    if (progs[k]->P == 0) {
+    if (member[k] && progs[k]->P == 0) {
       mlbp_program* mp = const_cast<mlbp_program*>(progs[k]);
       if (mp->bail_cap < args[k].B)
         if (int e = mlbp_program_reserve(mp, args[k].B)) return e;
@@ -2494,7 +2494,7 @@ int launch_shared_groups(const mlbp_program* const* progs, const mlbp_sweep_args
     std::vector<int> owners;
     for (int k = 0; k < n_groups; ++k) {
       PrepareDev& q = plans[k].q;
-      if (q.n_frag_tables == 0 && q.n_wfrag_tables == 0) continue;
+      if (!member[k] || (q.n_frag_tables == 0 && q.n_wfrag_tables == 0)) continue;
       int own = -1;
       for (int j : owners) {
         const PrepareDev& o = plans[j].q;
@@ -2516,7 +2516,7 @@ int launch_shared_groups(const mlbp_program* const* progs, const mlbp_sweep_args
   // keeps its own, faster instance (and its gradient epilogue that reads the message tiles).  One prepare launch in front of all.
   // table image: [SharedDev x n][PrepareDev x n][prepare starts n + 1][sweep starts of class 0 | 1 | 2, each (its groups) + 1], as 32-bit
   // words; the groups in class order
-  auto cls = [&](int k) { return progs[k]->P == 0 ? 3 : (plans[k].pf ? 0 : (plans[k].p3 ? 1 : 2)); };      // (3: not in these launches)
+  auto cls = [&](int k) { return !member[k] || progs[k]->P == 0 ? 3 : (plans[k].pf ? 0 : (plans[k].p3 ? 1 : 2)); };      // (3: not in these launches)
   std::vector<int> order;
   int first[4] = {0, 0, 0, 0};
   for (int c = 0; c < 3; ++c) {
@@ -2597,8 +2597,8 @@ int launch_shared_groups(const mlbp_program* const* progs, const mlbp_sweep_args
       return fail(MLBP_EHIP, "side stream for grouped launches: join failed");
   }
   for (int g = 0; g < n_groups; ++g)
-    if (int e = enqueue_unary_writeback(progs[g], &args[g], plans[g].d, st)) return e;
-  *launched = true;
+    if (member[g])
+      if (int e = enqueue_unary_writeback(progs[g], &args[g], plans[g].d, st)) return e;
   return MLBP_OK;
 }
 

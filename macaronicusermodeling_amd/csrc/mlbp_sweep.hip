@@ -1782,22 +1782,25 @@ int mlbp_sweep_f64(const mlbp_program* prog, const mlbp_sweep_args* a, void* str
   return run_sweep(prog, a, FAST_NONE, g_sweep_variant, stream);
 }
 
-// Behind launch_shared_groups: every group's fix-up pass in ONE launch (and, when the call carries gradients, one launch of
-// the per-graph gradient kernel over the flagged graphs of all groups), then each group's posterior by its own launch.
-// *done false: some group needs the per-group path (messages kept -- the unary write-back ran already, but marginals without
-// normalisation, an LDS image too large, a gradient the shared-table kernel did not produce).
-static int finish_shared_groups(const mlbp_program* const* progs, const mlbp_sweep_args* args, int n_groups, void* stream, bool* done) {
+// Behind launch_shared_groups: every member's fix-up pass in ONE launch (and, when the call carries gradients, one launch of
+// the per-graph gradient kernel over the flagged graphs of all members), then each member's posterior by its own launch.
+// *done false: some member needs the per-group path (messages kept -- the unary write-back ran already, but marginals without
+// normalisation, an LDS image too large, a gradient the shared-table kernel did not produce).  Tables cached with progs[0].
+static int finish_shared_groups(const mlbp_program* const* progs, const mlbp_sweep_args* args, int n_groups, const std::vector<char>& member,
+                                void* stream, bool* done) {
   *done = false;
-  std::vector<FixupGroup> table(n_groups);
+  std::vector<FixupGroup> table;
   std::vector<mlbp_gradient_args> grads;
   std::vector<const uint8_t*> grad_flags;
   size_t lds_max = 0;
   int blocks = 0;
   for (int k = 0; k < n_groups; ++k) {
+    if (!member[k]) continue;
     const mlbp_program* prog = progs[k];
     const mlbp_sweep_args* a = &args[k];
     if (a->X != 64 || !a->normalize_messages || !a->init_messages) return MLBP_OK;
-    FixupGroup& G = table[k];
+    table.emplace_back();
+    FixupGroup& G = table.back();
     const size_t lds = fill_fixup_group(prog, a, &G);
     if (lds > X64_LDS_MAX) return MLBP_OK;
     lds_max = std::max(lds_max, lds);
@@ -1810,11 +1813,12 @@ static int finish_shared_groups(const mlbp_program* const* progs, const mlbp_swe
     blocks += (a->B + G.per_wg - 1) / G.per_wg;
     if (a->gradient) { grads.push_back(*a->gradient); grad_flags.push_back(prog->d_bail); }
   }
-  if (!grads.empty() && (int)grads.size() != n_groups) return MLBP_OK;        // (all groups or none carry a gradient)
+  const int n_in = (int)table.size();
+  if (!grads.empty() && (int)grads.size() != n_in) return MLBP_OK;           // (all members or none carry a gradient)
   // the table as 32-bit words in the first program's group-table cache (one device copy per distinct contents)
   static_assert(sizeof(FixupGroup) % 4 == 0, "");
-  std::vector<int32_t> words(sizeof(FixupGroup) / 4 * (size_t)n_groups + 1);
-  memcpy(words.data(), table.data(), sizeof(FixupGroup) * (size_t)n_groups);
+  std::vector<int32_t> words(sizeof(FixupGroup) / 4 * (size_t)n_in + 1);
+  memcpy(words.data(), table.data(), sizeof(FixupGroup) * (size_t)n_in);
   words.back() = 0x46495855;                                                  // (keeps this table apart from the sweep kernels' own)
   mlbp_program* owner = const_cast<mlbp_program*>(progs[0]);
   int32_t* d_table = nullptr;
@@ -1822,15 +1826,16 @@ static int finish_shared_groups(const mlbp_program* const* progs, const mlbp_swe
   if (int e = mlbp::grant_lds((const void*)sweep_x64_fixup_groups_kernel, lds_max)) return e;
   mlbp::launch_begin();
   MLBP_LAUNCH(sweep_x64_fixup_groups_kernel, dim3(blocks), dim3(WG), lds_max, (hipStream_t)stream,
-                     reinterpret_cast<const FixupGroup*>(d_table), n_groups);
+                     reinterpret_cast<const FixupGroup*>(d_table), n_in);
   if (int e = mlbp::launch_verdict("grouped exact X = 64 fix-up")) return e;
   if (!grads.empty())
-    if (int e = mlbp::gradient_flagged_groups(grads.data(), grad_flags.data(), n_groups, owner, stream)) return e;
+    if (int e = mlbp::gradient_flagged_groups(grads.data(), grad_flags.data(), n_in, owner, stream)) return e;
   SweepTail tail;                                 // (the marginals are the kernels' epilogue, the gradient is done above)
   tail.marginals = false;
   tail.grad_done = true;
   for (int k = 0; k < n_groups; ++k)
-    if (int e = sweep_tail(progs[k], &args[k], tail, stream)) return e;
+    if (member[k])
+      if (int e = sweep_tail(progs[k], &args[k], tail, stream)) return e;
   g_last_kernel = MLBP_KERNEL_SHARED_MFMA;
   g_last_fused_gradient = grads.empty() ? 0 : 1;
   *done = true;
@@ -1847,25 +1852,34 @@ int mlbp_sweep_groups_f64(const mlbp_program* const* progs, const mlbp_sweep_arg
   }
   progs = eff.data();
   const int variant = g_sweep_variant;
-  FastPass pass = FAST_NONE;
+  // The fast kernels take what they can, in this order: the shared-table launch sequence, then one grouped lean launch over the
+  // groups left; each is followed by the fix-up pass over the graphs it flagged.  The rest run one after the other exactly as
+  // separate calls would.  A program joins one grouped launch at most (with its first group): two groups would share one set of
+  // redo flags and scratch -- the later one runs as a separate call behind the grouped launches.
+  std::vector<char> shared(n_groups, 0), lean(n_groups, 0);
   if (variant == 1) {
-    bool shared = false, lean = false;
-    if (int e = mlbp::launch_shared_groups(progs, args, n_groups, stream, &shared)) return e;
-    if (!shared)
-      if (int e = mlbp::launch_lean_groups(progs, args, n_groups, stream, &lean)) return e;
-    pass = shared ? FAST_SHARED : (lean ? FAST_LEAN : FAST_NONE);
+    std::vector<char> first(n_groups);
+    for (int k = 0; k < n_groups; ++k) first[k] = std::find(progs, progs + k, progs[k]) == progs + k;
+    shared = first;
+    if (int e = mlbp::launch_shared_groups(progs, args, n_groups, stream, shared)) return e;
+    // the shared-table kernels have run every member, gradient included: ONE fix-up launch for the flagged graphs of all members
+    // and one more for their gradients (a mixed minibatch used to pay both per group)
+    if (std::find(shared.begin(), shared.end(), 1) != shared.end()) {
+      bool done = false;
+      if (int e = finish_shared_groups(progs, args, n_groups, shared, stream, &done)) return e;
+      for (int k = 0; k < n_groups && !done; ++k)
+        if (shared[k])
+          if (int e = run_sweep(progs[k], &args[k], FAST_SHARED, variant, stream)) return e;
+    }
+    for (int k = 0; k < n_groups; ++k) lean[k] = first[k] && !shared[k];      // (lean_plan takes no pairwise-free group)
+    if (int e = mlbp::launch_lean_groups(progs, args, n_groups, stream, lean)) return e;
+    for (int k = 0; k < n_groups; ++k)
+      if (lean[k])
+        if (int e = run_sweep(progs[k], &args[k], FAST_LEAN, variant, stream)) return e;
   }
-  // the shared-table kernels have run every group, gradient included: ONE fix-up launch for the flagged graphs of all groups and
-  // one more for their gradients (a mixed minibatch used to pay both per group)
-  if (pass == FAST_SHARED) {
-    bool done = false;
-    if (int e = finish_shared_groups(progs, args, n_groups, stream, &done)) return e;
-    if (done) return MLBP_OK;
-  }
-  // a fast kernel has run every group: what is left per group is the fix-up pass over the graphs it flagged; otherwise the
-  // groups run one after the other exactly as separate calls would
   for (int k = 0; k < n_groups; ++k)
-    if (int e = run_sweep(progs[k], &args[k], pass, variant, stream)) return e;
+    if (!shared[k] && !lean[k])
+      if (int e = run_sweep(progs[k], &args[k], FAST_NONE, variant, stream)) return e;
   return MLBP_OK;
 }
 

@@ -17,7 +17,6 @@ Pairwise tables are the two shared pots (`pot_en_en`, `pot_en_en_w1`) referenced
 table-index indirection; a unary factor's table is a COLUMN of a pot (LBP.py:702-703), read as a
 row of the transposed pot the potentials kernel also writes -- no per-instance copies.
 """
-import functools
 import os
 
 import numpy as np
@@ -200,12 +199,6 @@ class UserGraphTrainer:
             self._graph.replay()
             return self.shared.stats_all
         return self._local_statistics_eager()
-
-    @functools.cached_property
-    def shared_table_form(self):
-        """True when this trainer's sweeps qualify for the shared-table matrix-core kernels: X = 64 and a program the
-        library's planner accepts (at most 16 pairwise factors, topology.plan's shared_ok)."""
-        return self.batch.X == 64 and self.topo.P >= 1 and self.topo.plan(self.roots[:self.n_sweeps_run])['shared_ok'] == 1
 
     def _sweep_with_gradient(self):
         self.batch.sweep(self.roots[:self.n_sweeps_run], init=True, marginals=self._marg, gradient=(self._g_ee, self._g_ed),
@@ -487,34 +480,23 @@ class _BucketSet:
         self.shared = _SharedTables(list(self.trainers.values())) if self.trainers else None
 
     def statistics_into(self, stats, grouped_sweeps, select=None):
-        """Adds the set's statistics to `stats`.  grouped_sweeps: the sweeps of ALL sentence shapes with pairwise factors
-        in one launch sequence (batch.sweep_groups -> mlbp_sweep_groups_f64: every bucket its own topology and roots;
-        the shared-table kernels take a group table) instead of one launch sequence per bucket; 'auto' groups whenever
-        two or more buckets qualify.  select: optional (key, value) -- key device int32 over the set's instances (bucket order),
-        value device int32 [1]: only the instances with key == value enter the sums (masked minibatches).  One potentials launch in front of the sweeps and three launches behind them
-        (planes' gradient share, log-posteriors, sums) serve every shape."""
+        """Adds the set's statistics to `stats`.  grouped_sweeps: the sweeps of ALL sentence shapes in one call
+        (batch.sweep_groups -> mlbp_sweep_groups_f64: every bucket its own topology and roots; the library runs the buckets
+        its fast kernels take in shared launches, the others one by one) instead of one call per bucket.  select: optional
+        (key, value) -- key device int32 over the set's instances (bucket order), value device int32 [1]: only the instances
+        with key == value enter the sums (masked minibatches).  One potentials launch in front of the sweeps and three launches
+        behind them (planes' gradient share, log-posteriors, sums) serve every shape."""
         trs = list(self.trainers.values())
         if not trs:
             return
         self.shared.build()                           # ONE potentials launch (and one expectations launch) for every shape
-        # only shapes the shared-table kernels take: the library declines a grouped call as a whole when one group does not
-        # qualify, so a single K7+ bucket in it would move every other bucket off the matrix cores
-        together = [tr for tr in trs if tr.shared_table_form] if grouped_sweeps else []
-        if len(together) < 2 and grouped_sweeps is not True:
-            together = []
-        if together:
-            # shapes with ONE predicted word (no pairwise factor) join the call: the library hands all their graphs to the launches
-            # it runs behind the matrix-core kernels anyway (the exact kernel over flagged graphs, their gradient) -- two launches
-            # per such shape otherwise
-            together = [tr for tr in trs if any(tr is t for t in together) or (tr.topo.P == 0 and tr.batch.X == 64)]
-        for tr in trs:
-            if not any(tr is t for t in together):
-                tr._sweep_with_gradient()
-        if together:
+        if grouped_sweeps and len(trs) >= 2:
             from .batch import sweep_groups
-            sweep_groups([tr.batch for tr in together], [tr.roots[:tr.n_sweeps_run] for tr in together], init=True,
-                         marginals=[tr._marg for tr in together], gradients=[(tr._g_ee, tr._g_ed) for tr in together],
-                         keep_messages=False)
+            sweep_groups([tr.batch for tr in trs], [tr.roots[:tr.n_sweeps_run] for tr in trs], init=True,
+                         marginals=[tr._marg for tr in trs], gradients=[(tr._g_ee, tr._g_ed) for tr in trs], keep_messages=False)
+        else:
+            for tr in trs:
+                tr._sweep_with_gradient()
         stats += self.shared.statistics(select)
 
 
@@ -528,7 +510,7 @@ class TiDirTrainer:
 
     def __init__(self, ti_path, en_vocab, de_vocab, phi_pmi, phi_pmi_w1, phi_ed, phi_ped, device='cuda:0', sweeps=3,
                  rank=0, world=1, use_planes=True, adapt=None, domains=None, reg_param_ua_scale=1.0,
-                 use_correct_feat=True, history=True, session_history=True, grouped_sweeps='auto', skip_unchanged=False,
+                 use_correct_feat=True, history=True, session_history=True, grouped_sweeps=True, skip_unchanged=False,
                  minibatch=None, shuffle_seed=None, load_params=None, share_params_with=None, minibatch_mode='masked'):
         """use_planes switches the three per-instance feature planes on as a whole; use_correct_feat / history /
         session_history gate them one by one as the reference's options of the same names do (train_mp.py:178, 192,
@@ -560,7 +542,7 @@ class TiDirTrainer:
         if adapt not in (None, 'user', 'experience'):
             raise ValueError("adapt is None, 'user' or 'experience'")
         self.adapt, self.reg_param_ua_scale = adapt, float(reg_param_ua_scale)
-        self.grouped_sweeps, self.sweeps, self.skip_unchanged = grouped_sweeps, int(sweeps), bool(skip_unchanged)
+        self.grouped_sweeps, self.sweeps, self.skip_unchanged = bool(grouped_sweeps), int(sweeps), bool(skip_unchanged)
         self.rank, self.world = int(rank), int(world)
         self.device = dev = torch.device(device)
         self.en, self.de = tidir.read_vocab(en_vocab), tidir.read_vocab(de_vocab)

@@ -13,12 +13,13 @@ import json
 import numpy as np
 import pytest
 
+import kernel_inventory as K
 from helpers import tidir_gold, write_tidir
 
 torch = pytest.importorskip('torch')
 pytestmark = pytest.mark.gpu
 
-KERNEL_EXACT, KERNEL_SHARED_MFMA, KERNEL_GENERIC = 2, 3, 5          # mlbp.h MLBP_KERNEL_*
+KERNEL_EXACT, KERNEL_GENERIC = 2, 5          # mlbp.h MLBP_KERNEL_*
 LARGE = {7: KERNEL_EXACT, 8: KERNEL_EXACT, 9: KERNEL_EXACT, 10: KERNEL_GENERIC, 12: KERNEL_GENERIC}     # predicted words -> sweep kernel at X = 64
 
 
@@ -53,17 +54,35 @@ def _check_buckets(tt, by_sent):
     return seen
 
 
+def _check_grouped_then_large(log, words):
+    """A grouped statistics call's launch log (words: predicted words per bucket, in bucket order): the shared-table kernels
+    ran as grouped launches only, and every K7+ bucket's sweep kernel followed them -- the exact kernel streaming its tables
+    for K7 to K9, the generic kernel for K10 and K12 -- the last of them reported as the call's kernel."""
+    from macaronicusermodeling_amd import _ffi
+    shared = [e for e in log if e[0] in ('shared_prepare_kernel', 'sweep_x64_shared_kernel')]
+    assert ('shared_prepare_kernel', (True,)) in shared and ('shared_prepare_kernel', (False,)) not in shared
+    assert all(e[1][3] for e in shared if e[0] == 'sweep_x64_shared_kernel')           # (MULTI: the grouped instances)
+    behind = log[max(i for i, e in enumerate(log) if e[0] == 'sweep_x64_shared_kernel'):]
+    large = [k for k in words if k in LARGE]
+    assert large
+    if any(k <= 9 for k in large):
+        assert ('sweep_x64_fused_kernel', (True, 0, False)) in behind
+    if any(k >= 10 for k in large):
+        assert ('sweep_generic_kernel', (True, False)) in behind
+    assert _ffi.lib.mlbp_last_sweep_kernel() == LARGE[large[-1]]
+
+
 @pytest.mark.parametrize('grouped', [True, False], ids=['grouped', 'per_bucket'])
 def test_large_cliques_equal_the_reference_pipeline(tmp_path, grouped):
     """TiDirTrainer on the fixture's files, with and without grouped sweeps: per-bucket marginals and log-posteriors of K1 to
     K12 equal the reference's, and one epoch moves theta by the sum of the reference's steps."""
-    from macaronicusermodeling_amd import _ffi
     gold = _gold()
     tt = _trainer(write_tidir(gold, str(tmp_path)), gold, grouped_sweeps=grouped)
     assert {len(k[1]) for k in tt.trainers} >= {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12}
+    K.reset()
     tt.local_statistics()
-    if grouped:          # the K2 to K6 buckets ran as one grouped call on the matrix cores, behind the K7+ buckets' own launches
-        assert _ffi.lib.mlbp_last_sweep_kernel() == KERNEL_SHARED_MFMA
+    if grouped:          # the K2 to K6 buckets ran in the grouped launches on the matrix cores, the K7+ buckets' own launches behind them
+        _check_grouped_then_large(K.launched(), [len(key[1]) for key in tt.trainers])
     by_sent = {_sent_id(l): r for l, r in zip(gold['instances'], gold['reference'])}
     assert _check_buckets(tt, by_sent) == len(gold['reference']) == 11
     o = gold['options']
@@ -94,7 +113,7 @@ def test_each_large_clique_takes_its_kernel_and_equals_the_reference(tmp_path, s
         d.mkdir()
         tt = _trainer(write_tidir(dict(gold, instances=[line]), str(d)), gold)
         (tr,) = tt.trainers.values()
-        assert tr.topo.P == k * (k - 1) // 2 and not tr.shared_table_form
+        assert tr.topo.P == k * (k - 1) // 2 and tr.topo.plan(tr.roots[:tr.n_sweeps_run])['shared_ok'] == 0
         tr.batch.use_shared_gradient = shared_gradient
         tt.local_statistics()
         assert (_ffi.lib.mlbp_last_sweep_kernel(), _ffi.lib.mlbp_last_sweep_fused_gradient()) == (LARGE[k], 0), k
@@ -205,19 +224,18 @@ def test_large_cliques_with_theta_far_out_agree_grouped_and_per_bucket(tmp_path)
 
 
 def test_one_large_clique_leaves_the_other_shapes_on_the_matrix_cores(tmp_path):
-    """A file of K2 to K4 sentences and one K7 sentence: the K7 bucket does not qualify for the shared-table kernels, so it
-    runs its own launches and the grouped call keeps K2 to K4 on the matrix cores (the library declines a grouped call as a
-    whole when one group does not qualify).  The grouped call is issued last, so the last sweep kernel is its.  Statistics
-    equal the per-bucket run's."""
-    from macaronicusermodeling_amd import _ffi
+    """A file of K2 to K4 sentences and one K7 sentence: the K7 bucket does not qualify for the shared-table kernels, and the
+    library leaves it out of the grouped launches, not the call: K2 to K4 stay on the matrix cores and the K7 bucket's exact
+    kernel runs behind them.  Statistics equal the per-bucket run's."""
     gold = _gold()
     k = [len(r['variables']) for r in gold['reference']]
     k7 = k.index(7)
     lines = [l for l, n in zip(gold['instances'], k) if 2 <= n <= 4] + [gold['instances'][k7]]
     paths = write_tidir(dict(gold, instances=lines), str(tmp_path))
-    a, b = _trainer(paths, gold, grouped_sweeps='auto'), _trainer(paths, gold, grouped_sweeps=False)
+    a, b = _trainer(paths, gold, grouped_sweeps=True), _trainer(paths, gold, grouped_sweeps=False)
     assert sorted({tr.topo.P for tr in a.trainers.values()}) == [1, 3, 6, 21]
-    assert [tr.shared_table_form for tr in a.trainers.values()].count(False) == 1
+    assert [tr.topo.plan(tr.roots[:tr.n_sweeps_run])['shared_ok'] for tr in a.trainers.values()].count(0) == 1
+    K.reset()
     sa = a.local_statistics().cpu().numpy()
-    assert _ffi.lib.mlbp_last_sweep_kernel() == KERNEL_SHARED_MFMA
+    _check_grouped_then_large(K.launched(), [len(key[1]) for key in a.trainers])
     np.testing.assert_allclose(sa, b.local_statistics().cpu().numpy(), rtol=1e-9, atol=1e-12)

@@ -455,9 +455,11 @@ def test_groups_of_mixed_shapes_in_one_shared_launch_sequence():
     own roots, batch size (partial last groups of 16) and tables: ONE prepare launch and one sweep launch PER FORM of the
     shared-table kernel (product-fused: K2, K3; its three-source variant: K4; general: K5) behind a group table.  Same bits as the five
     single launch sequences, the oracle's values, a degenerate graph of one group redone by the exact kernel; every group's
-    log-posteriors bit for bit, their batch sums to rounding.  A group with a posterior but no marginals fails the whole call
-    before anything runs."""
+    log-posteriors bit for bit, their batch sums to rounding.  A group that does not qualify leaves the others in the grouped
+    launches; a program named twice runs its second group on its own.  A group with a posterior but no marginals fails the
+    whole call before anything runs."""
     import ctypes
+    import kernel_inventory as K
     from helpers import posterior_buffers
     from macaronicusermodeling_amd import _ffi
     from macaronicusermodeling_amd.batch import _stream_ptr, sweep_groups
@@ -498,15 +500,34 @@ def test_groups_of_mixed_shapes_in_one_shared_launch_sequence():
     assert _ffi.lib.mlbp_last_sweep_kernel() == KERNEL_SHARED_MFMA, _ffi.lib.mlbp_last_error()
     for k in few:
         assert torch.equal(built[k][0].msgs, single_msgs[k]) and torch.equal(margs[k], single_marg[k])
-    # a second call with other batch contents re-uses the uploaded group table; one group that does not qualify
-    # (no shared-table claim) sends the whole call to the per-group path
+    # a second call with other batch contents re-uses the uploaded group table; one group that does not qualify (no shared-table
+    # claim) leaves the other four in ONE prepare launch and one sweep launch per form, and runs behind them
     built[0][0].pair_tables_shared = False
+    K.reset()
     sweep_groups([fb for fb, _, _ in built], roots, init=True, marginals=margs)
+    log = K.launched()
+    assert [i for i in log if i[0] == 'shared_prepare_kernel'] == [('shared_prepare_kernel', (True,))]
+    forms = [i[1] for i in log if i[0] == 'sweep_x64_shared_kernel']
+    assert all(f[3] for f in forms) and sorted((f[5], f[6]) for f in forms) == [(False, False), (True, False), (True, True)]
     for k, (fb, _, _) in enumerate(built):
         np.testing.assert_allclose(fb.msgs.cpu().numpy(), single_msgs[k].cpu().numpy(), rtol=1e-11, atol=1e-300)
+    # one program named twice: the second group runs as a call of its own behind the grouped launches; both groups equal
+    # their single calls
+    built[0][0].pair_tables_shared = True
+    twin, _, _ = _shared_batch(SPECS[names[1]](), 9, seed=71)
+    twin._programs = built[1][0]._programs
+    m_twin = torch.empty(twin.B, built[1][1].n_vars, 64, dtype=torch.float64, device=twin.device)
+    twin.sweep(roots[1], init=True, marginals=m_twin)
+    alone = (twin.msgs.clone(), m_twin.clone())
+    pair = [built[1][0], twin]
+    for fb, m in zip(pair, (margs[1], m_twin)):
+        fb.msgs.fill_(float('nan')); m.fill_(float('nan'))
+    progs = sweep_groups(pair, [roots[1], roots[1]], init=True, marginals=[margs[1], m_twin])
+    assert progs[0] is progs[1]
+    assert torch.equal(built[1][0].msgs, single_msgs[1]) and torch.equal(margs[1], single_marg[1])
+    assert torch.equal(twin.msgs, alone[0]) and torch.equal(m_twin, alone[1])
     # one group with a posterior but no marginals (a request the Python wrapper refuses, made in the collected arguments): the call
     # fails with the single call's message and leaves every group's messages as they were
-    built[0][0].pair_tables_shared = True
     got = []
     for k, (fb, _, _) in enumerate(built):
         fb.msgs.fill_(0.25)

@@ -221,7 +221,7 @@ def test_large_clique_schedules_loop_tests_and_compiled_sweeps_equal_the_oracle_
     assert max(GraphTopology.from_spec(s).n_msgs for s, _ in _clique_shapes()) == 288
 
 
-def test_shared_table_form_covers_cliques_up_to_sixteen_pairwise_factors():
+def test_shared_form_plans_cliques_up_to_sixteen_pairwise_factors():
     """The limit the X = 64 dispatch rests on: the shared-table (matrix-core) form plans K2 to K6 (P <= 16) and declines K7
     and larger, which the exact kernel (or, once its LDS image is too large, the generic kernel) runs instead."""
     by_p = {}
