@@ -534,8 +534,10 @@ int mlbp_normalize_f64(const double* in, double* out, int32_t batch, int64_t n, 
 /* Top-K selection used by the reference's approximate ("sparse") primitives, K = 100
  * (c_array_utils.pyx:118,194; np.argpartition(-v, K-1)[:K]).  Writes the indices of the K largest
  * entries of the strided vector v to idx (device int32 [K]) in descending value order, ties broken
- * by lower index (the reference leaves tie order unspecified).  K > n fails with MLBP_EINVAL and the
- * text of NumPy's error, "kth(=K-1) out of bounds (n)". */
+ * by lower index (the reference leaves tie order unspecified).  NaN ranks below every number and NaNs
+ * tie among themselves (lower index first), so idx is always K distinct indices in [0, n): the K
+ * largest numbers when v holds at least K of them, as np.argpartition(-v), which sorts NaN last.
+ * K > n fails with MLBP_EINVAL and the text of NumPy's error, "kth(=K-1) out of bounds (n)". */
 int mlbp_topk_f64(const double* v, int64_t stride, int32_t n, int32_t K, int32_t* idx, void* stream);
 
 /* The same selection for every row of a contiguous [rows][n] matrix (idx: device int32 [rows][K]):

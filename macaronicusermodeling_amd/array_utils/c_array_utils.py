@@ -208,7 +208,8 @@ def sparse_normalize(m1, c_idx, r_idx):
 # host-side NumPy bodies with the reference's argument meaning, in-place behaviour, return types and errors, so that code
 # which imports the module finds every name doing what it did.  Pinned on outputs of the reference's own module
 # (tests/golden/au_dormant_functions.npz, generated by make_golden.py; tests/test_au_dormant.py).  Top-K selections: the K
-# largest entries, ties by lower index (the rule of mlbp_topk_f64; np.argpartition leaves the order open).
+# largest entries, ties by lower index, NaN below every number and NaNs tied among themselves (the rule of mlbp_topk_f64;
+# np.argpartition also sorts NaN last, and leaves the order of ties open).
 def _top_k(flat, k):
     """Indices of the k largest entries of a 1-D array (ties: lower index first), ascending by index."""
     order = np.lexsort((np.arange(flat.size), -flat))

@@ -90,11 +90,12 @@ __global__ __launch_bounds__(256) void normalize_kernel(const double* in, double
   if (positive && threadIdx.x == 0) positive[blockIdx.x] = pos ? 1 : 0;
 }
 
-// Rank-select of the K largest entries of v[0..n) (ties: lower index first).  One workgroup;
-// rank_i = #{j : v_j > v_i or (v_j == v_i and j < i)}; entries with rank < K are written to
-// idx[rank], i.e. in descending value order.  O(n^2 / 256) compares per thread -- n is a vocabulary
-// size (hundreds to a few thousand).  NaNs compare false everywhere and rank first among equals;
-// the reference's np.argpartition leaves their place unspecified.
+// Rank-select of the K largest entries of v[0..n) (ties: lower index first).  One workgroup per row.  The order is total:
+// numbers by value, every NaN below every number, NaNs tied among themselves, ties to the lower index, so
+//   rank_i = #{j : j ranks above i}
+// is a permutation of 0..n-1 and entries with rank < K are written to idx[rank] -- every slot of idx exactly once, in
+// descending value order, NaNs only after all numbers (np.argpartition(-v) sorts NaN last too).  O(n^2 / 256) compares per
+// thread -- n is a vocabulary size (hundreds to a few thousand).
 __global__ __launch_bounds__(256) void topk_kernel(const double* v0, int64_t stride, int n, int K, int32_t* idx0,
                                                    int64_t row_stride) {
   extern __shared__ double sv[];
@@ -105,9 +106,16 @@ __global__ __launch_bounds__(256) void topk_kernel(const double* v0, int64_t str
   for (int i = threadIdx.x; i < n; i += 256) {
     const double x = sv[i];
     int rank = 0;
-    for (int j = 0; j < n; ++j) {
-      const double y = sv[j];
-      rank += (y > x) || (y == x && j < i);
+    if (x != x) {                                               // NaN: below every number, after the NaNs of lower index
+      for (int j = 0; j < n; ++j) {
+        const double y = sv[j];
+        rank += (y == y) || j < i;
+      }
+    } else {                                                    // (a NaN y compares false: never above a number)
+      for (int j = 0; j < n; ++j) {
+        const double y = sv[j];
+        rank += (y > x) || (y == x && j < i);
+      }
     }
     if (rank < K) idx[rank] = i;
   }

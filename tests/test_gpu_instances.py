@@ -1,7 +1,8 @@
 """GPU parity per compiled kernel instance: every instance of the sweep and contraction families that the dispatch code can
 reach has a case here (COVERED; tests/test_kernel_inventory.py checks the list against the built library).  Each case runs a
 workload that reaches its instance, checks in the launch log (mlbp_launch_log) that the instance ran, and compares the
-call's outputs with the float64 oracle (oracle/lbp_oracle.py):
+call's outputs with the float64 oracle (oracle/lbp_oracle.py); the kernels that run only inside such calls (COMPOUND) are
+checked the same way, through the all-kernel launch log.  Tolerances:
 
 - messages, marginals, log-posteriors and their batch sum: 1e-10 relative;
 - gradients (unregularized_gradient): 1e-8;
@@ -185,6 +186,9 @@ for _f in ((1, 1), (2, 2), (3, 6)):
     _w('gradient_x128_f%d%d' % _f, kind='gradient', spec='user_k3', X=128, B=5, layout='unique', F=_f)
 _w('gradient_b1_x64', kind='gradient', spec='user_k3', X=64, B=1, layout='unique', F=(3, 6), unshared=True)
 _w('gradient_b1_x128', kind='gradient', spec='user_k3', X=128, B=1, layout='unique', F=(3, 6))
+# ... with shared pairwise tables: the pairwise part on the matrix cores (X = 64) or as contractions (X = 128)
+_w('gradient_shared_x64', kind='gradient', spec='user_k3', X=64, B=19, layout='shared', F=(3, 6))
+_w('gradient_shared_x128', kind='gradient', spec='user_k3', X=128, B=19, layout='shared', F=(3, 6))
 
 
 # ---- running a workload ----------------------------------------------------------------------------------------------
@@ -370,7 +374,7 @@ def _with_variant(variant, fn):
 
 @functools.lru_cache(maxsize=None)
 def run_workload(name):
-    """Runs workload `name` once: (instances launched, exact-kernel redo counts, failure or None)."""
+    """Runs workload `name` once: (instances launched, exact-kernel redo counts, failure or None, every kernel launched)."""
     from macaronicusermodeling_amd import _ffi
     from macaronicusermodeling_amd import batch as batch_mod
     w = WORKLOADS[name]
@@ -388,7 +392,7 @@ def run_workload(name):
             _with_variant(variant, lambda: gr.fb.sweep(gr.roots, init=True, marginals=gr.marg))
             K.reset()
             gr.fb.gradient(gr.g_ee, gr.g_ed)
-            launched = K.launched()
+            launched, everything = K.launched(), K.all_launched()
             torch.cuda.synchronize()
             assert _ffi.lib.mlbp_gradient_status() == 0
         elif w['kind'] == 'groups':
@@ -397,14 +401,14 @@ def run_workload(name):
                 [g.fb for g in groups], [g.roots for g in groups], init=True, marginals=[k['marginals'] for k in kws],
                 gradients=[k['gradient'] for k in kws] if groups[0].grad else None,
                 posteriors=[k['posterior'] for k in kws] if groups[0].post is not None else None))
-            launched = K.launched()
+            launched, everything = K.launched(), K.all_launched()
             torch.cuda.synchronize()
             for p in progs:
                 assert p.status() == 0
         else:
             gr = groups[0]
             prog = _with_variant(variant, lambda: gr.fb.sweep(gr.roots, **gr.sweep_kwargs()))
-            launched = K.launched()
+            launched, everything = K.launched(), K.all_launched()
             torch.cuda.synchronize()
             assert prog.status() == 0, _ffi.lib.mlbp_last_error()
         redo = []
@@ -418,9 +422,9 @@ def run_workload(name):
             got = gr.fb.msgs.clone()
             _with_variant(3, lambda: gr.fb.sweep(gr.roots, init=True))
             np.testing.assert_allclose(got.cpu().numpy(), gr.fb.msgs.cpu().numpy(), rtol=1e-11, atol=1e-300)
-        return frozenset(launched), tuple(redo), None
+        return frozenset(launched), tuple(redo), None, frozenset(everything)
     except Exception as e:         # (kept for every instance case of this workload)
-        return frozenset(K.launched()), (), e
+        return frozenset(K.launched()), (), e, frozenset(K.all_launched())
 
 
 # ---- the instance table ----------------------------------------------------------------------------------------------
@@ -547,11 +551,26 @@ COVERED = {
 }
 FAST = ('sweep_x64_shared_kernel', 'sweep_x64_lean_kernel')
 
+# kernels that run only inside a sweep or gradient call (no entry of their own) -> workloads above that launch them: the
+# workload's outputs are compared with the oracle as for COVERED (tests/test_kernel_inventory.py checks this list too)
+COMPOUND = {
+    ('check_shared_claim_kernel', ()): ['gemm_x128'],
+    ('fill_uniform_kernel', ()): ['gemm_x128'],
+    ('unary_update_kernel', ()): ['gemm_x128'],
+    ('variable_update_kernel', ()): ['gemm_x128'],
+    ('pair_gradient_combine_kernel', ()): ['gemm_grad_x128', 'gradient_shared_x128'],
+    ('unary_writeback_kernel', ()): ['shared_user_k3'],
+    ('pair_weight_fragments_kernel', ()): ['gradient_shared_x64'],
+    ('gradient_shared_pairs_kernel', ()): ['gradient_shared_x64'],
+    ('gradient_x64_groups_kernel', ()): ['shared_groups_grad_k2_k3'],
+    ('sweep_x64_fixup_groups_kernel', ()): ['shared_groups_k2_k3'],
+}
+
 
 @pytest.mark.parametrize('instance', sorted(COVERED, key=repr), ids=lambda i: '%s%s' % (i[0], i[1]))
 def test_instance_matches_oracle(instance):
     for name in COVERED[instance]:
-        launched, redo, err = run_workload(name)
+        launched, redo, err, _ = run_workload(name)
         if err is not None:
             raise err
         assert instance in launched, '%s did not launch %s (launched: %s)' % (name, instance, sorted(launched, key=repr))
@@ -560,3 +579,13 @@ def test_instance_matches_oracle(instance):
             assert sum(redo) == 1, '%s: %s graphs redone by the exact kernel, want 1' % (name, redo)
         elif instance[0] in FAST:              # the fast kernel's own results were compared, not the exact kernel's
             assert not any(redo), '%s: %s graphs redone by the exact kernel' % (name, redo)
+
+
+@pytest.mark.parametrize('kernel', sorted(COMPOUND), ids=lambda k: k[0])
+def test_compound_kernel_matches_oracle(kernel):
+    """A kernel without an entry of its own ran inside each of its workloads, whose outputs match the oracle."""
+    for name in COMPOUND[kernel]:
+        _, _, err, everything = run_workload(name)
+        if err is not None:
+            raise err
+        assert kernel in everything, '%s did not launch %s (launched: %s)' % (name, kernel, sorted(everything, key=repr))
