@@ -240,6 +240,51 @@ class FactorGraphBatch:
         _ffi.check(_ffi.lib.mlbp_sweep_f64(prog.handle, C.byref(a), _stream_ptr(self.device)))
         return prog
 
+    # ---- max-product: the jointly most probable assignment (include/mlbp_map.h) ------------------
+    def map_sweep(self, roots, init=True, max_marginals=None, keep_messages=True):
+        """Runs len(roots) MAX-product sweeps -- sweep()'s schedule with max_j in place of sum_j in every pairwise update --
+        and decodes: returns (assignment int32 [B][n_vars], score float64 [B]) device tensors, variables in
+        GraphTopology.var_ids order.  assignment[v] is the argmax of v's max-marginal (ties to the lowest index); score is
+        the sum over factors of the log table entry at the assignment (the tables as given).  Exact MAP on a tree whenever
+        it is unique, the usual max-product approximation on a loopy graph.  Tables and self.msgs are used as sweep() uses
+        them; max_marginals: optional [B][n_vars][X] device tensor; keep_messages=False leaves self.msgs undefined."""
+        from . import mapdecode as M
+        if self.use_approx_inference:
+            raise NotImplementedError('max-product has no top-100 approximate form')
+        if self.pair_tables is not None and self.pair_tables.dtype != torch.float64:
+            raise NotImplementedError('max-product needs float64 pairwise tables')
+        topo = self.topo
+        prog = M.program(topo, roots, self.device)
+        a = M.MapArgs()
+        a.B, a.X, a.n_msgs, a.P, a.U, a.n_vars = self.B, self.X, topo.n_msgs, topo.P, topo.U, topo.n_vars
+        a.n_ops, a.n_srcs, a.n_sweeps = prog.n_ops, prog.n_srcs, prog.n_sweeps
+        a.ops, a.srcs, a.sweeps = prog.ops.data_ptr(), prog.srcs.data_ptr(), prog.sweeps.data_ptr()
+        if topo.P:
+            if self.pair_tables is None:
+                raise RuntimeError('set_pair_tables() first')
+            a.n_pair_tables = self.pair_tables.shape[0]
+            a.pair_tables, a.pair_tab = self.pair_tables.data_ptr(), self.pair_tab.data_ptr()
+            a.pair_axis_var = prog.pair_axis_var.data_ptr()
+        if topo.U:
+            if self.unary_tables is None:
+                raise RuntimeError('set_unary_tables() first')
+            a.n_unary_tables = self.unary_tables.shape[0]
+            a.unary_tables, a.unary_tab = self.unary_tables.data_ptr(), self.unary_tab.data_ptr()
+            a.unary_var = prog.unary_var.data_ptr()
+        a.msgs = self.msgs.data_ptr()
+        a.init_messages, a.normalize_messages = (1 if init else 0), (1 if self.normalize_messages else 0)
+        a.write_messages = 1 if keep_messages else 0
+        a.in_off, a.in_slots = prog.in_off.data_ptr(), prog.in_slots.data_ptr()
+        if max_marginals is not None:
+            if tuple(max_marginals.shape) != (self.B, topo.n_vars, self.X) or max_marginals.dtype != torch.float64:
+                raise ValueError('max_marginals must be float64 [B][n_vars][X]')
+            a.max_marginals = max_marginals.data_ptr()
+        assignment = torch.empty(self.B, topo.n_vars, dtype=torch.int32, device=self.device)
+        score = torch.empty(self.B, dtype=torch.float64, device=self.device)
+        a.assignment, a.score = assignment.data_ptr(), score.data_ptr()
+        M.check(M.lib.mlbp_map_sweep_f64(C.byref(a), _stream_ptr(self.device)))
+        return assignment, score
+
     def treelike_inference(self, iterations, roots):
         """`iterations` sweeps if the graph is loopy, else one (LBP.py:219); `roots` replaces the
         per-sweep random.sample draw (LBP.py:223).  Returns the number of sweeps run."""

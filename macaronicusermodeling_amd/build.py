@@ -1,4 +1,4 @@
-"""Builds libmlbp.so (gfx950 only) in-tree with hipcc.  `python -m macaronicusermodeling_amd.build`.
+"""Builds libmlbp.so and libmlbp_map.so (gfx950 only) in-tree with hipcc.  `python -m macaronicusermodeling_amd.build`.
 
 hipcc cross-compiles without a GPU, so this runs in the build container; the resulting .so is
 git-ignored but travels to the GPU box with the working-tree snapshot.
@@ -11,6 +11,10 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, 'csrc')
 LIB = os.path.join(PKG, 'libmlbp.so')
 SOURCES = ['mlbp_host.cpp', 'mlbp_sweep.hip', 'mlbp_lean.hip', 'mlbp_shared.hip', 'mlbp_gemm.hip', 'mlbp_prims.hip', 'mlbp_grad.hip']
+# the max-product / MAP library (include/mlbp_map.h): its own sources, its own kernel inventory, the same flags
+CSRC_MAP = os.path.join(PKG, 'csrc_map')
+LIB_MAP = os.path.join(PKG, 'libmlbp_map.so')
+SOURCES_MAP = ['mlbp_map.hip']
 FLAGS = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-fno-fast-math', '-Wall',
          '-Wno-unused-function']
 
@@ -22,13 +26,11 @@ def _stale(obj, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build(force=False, verbose=False):
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    headers = [os.path.join(CSRC, 'mlbp_internal.h'), os.path.join(CSRC, 'mlbp_device.h'), os.path.join(PKG, '..', 'include', 'mlbp.h')]
+def _build_one(hipcc, csrc, sources, headers, lib, force, verbose):
     objs = []
-    for src in SOURCES:
-        path = os.path.join(CSRC, src)
-        obj = os.path.join(CSRC, os.path.splitext(src)[0] + '.o')
+    for src in sources:
+        path = os.path.join(csrc, src)
+        obj = os.path.join(csrc, os.path.splitext(src)[0] + '.o')
         if force or _stale(obj, [path] + headers):
             cmd = [hipcc] + FLAGS + ['-x', 'hip', '-c', path, '-o', obj]
             if verbose:
@@ -36,9 +38,19 @@ def build(force=False, verbose=False):
                 print(' '.join(cmd))
             subprocess.check_call(cmd)
         objs.append(obj)
-    if force or _stale(LIB, objs):
-        subprocess.check_call([hipcc, '-shared', '-fPIC', '--offload-arch=gfx950', '-o', LIB] + objs)
-    return LIB
+    if force or _stale(lib, objs):
+        subprocess.check_call([hipcc, '-shared', '-fPIC', '--offload-arch=gfx950', '-o', lib] + objs)
+    return lib
+
+
+def build(force=False, verbose=False):
+    """Builds both libraries; returns the path of libmlbp.so (libmlbp_map.so lies beside it: LIB_MAP)."""
+    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+    headers = [os.path.join(CSRC, 'mlbp_internal.h'), os.path.join(CSRC, 'mlbp_device.h'), os.path.join(PKG, '..', 'include', 'mlbp.h')]
+    lib = _build_one(hipcc, CSRC, SOURCES, headers, LIB, force, verbose)
+    headers_map = [os.path.join(CSRC, 'mlbp_device.h'), os.path.join(PKG, '..', 'include', 'mlbp_map.h')]
+    _build_one(hipcc, CSRC_MAP, SOURCES_MAP, headers_map, LIB_MAP, force, verbose)
+    return lib
 
 
 if __name__ == '__main__':

@@ -250,6 +250,14 @@ class UserGraphTrainer:
             return self._lp.cpu().numpy(), idx_h, logs, counts, logm_h, np.take_along_axis(logm_h, labels[:, :, None], axis=2)[:, :, 0]
         return self._lp.cpu().numpy(), idx_h, logs, counts
 
+    def decode(self):
+        """The jointly most probable set of guesses of every instance under the current thetas (max-product sweeps over the
+        predict() schedule, FactorGraphBatch.map_sweep): host (assignment int64 [B][n_vars] word indices in var_ids order,
+        score float64 [B] -- the log-potential of the assignment)."""
+        self.build_potentials()
+        assignment, score = self.batch.map_sweep(self.roots[:self.n_sweeps_run], init=True, keep_messages=False)
+        return assignment.cpu().numpy().astype(np.int64), score.cpu().numpy()
+
 
 def apply_update(theta_en_en, theta_en_de, stats, F_ee, F_ed, learning_rate, reg_param):
     """theta += sum_i lr (g_i - reg theta) = lr (sum_i g_i - n reg theta): the sum of the per-instance
@@ -771,6 +779,26 @@ class TiDirTrainer:
             tidir.save_params(save_params, self.theta_en_en.cpu().numpy().reshape(1, -1),
                               self.theta_en_de.cpu().numpy().reshape(1, -1), d2t=self.domain_thetas())
         return history
+
+    # ---- joint decoding (max-product; the reference has none) ---------------------------------------
+    def decode(self):
+        """-> (guesses, counts).  guesses[i], for instance i of this rank's shard in file order: (predicted positions, [en
+        words], score) -- the whole set of guesses the model finds jointly most probable for the sentence
+        (UserGraphTrainer.decode) and its log-potential; an instance without a predicted word builds no graph and gives
+        ((), [], 0.0).  counts = (sentences whose every predicted word equals the user's guess, sentences with a predicted
+        word, predicted words equal to the user's guess, predicted words) over ALL ranks' instances, reduced once."""
+        n = self._shard[1] - self._shard[0]
+        guesses = [((), [], 0.0)] * n
+        counts = np.zeros(4, dtype=np.int64)
+        for key, tr in self.trainers.items():
+            x, score = tr.decode()
+            hit = x == self.buckets[key]['var_labels']
+            counts += np.array([int(hit.all(axis=1).sum()), hit.shape[0], int(hit.sum()), hit.size], dtype=np.int64)
+            for b, row in enumerate(self.buckets[key]['rows']):
+                guesses[row['index']] = (tuple(key[1]), [self.en[w] for w in x[b]], float(score[b]))
+        tot = torch.tensor([float(v) for v in counts], dtype=torch.float64, device=self.device)
+        mdist.all_reduce_sum_(tot)
+        return guesses, tuple(int(v) for v in tot.cpu().numpy())
 
     # ---- prediction pass (train_mp.py:310-343, 692-770) -------------------------------------------
     def predict(self, save_predictions=None):
