@@ -285,6 +285,68 @@ class FactorGraphBatch:
         M.check(M.lib.mlbp_map_sweep_f64(C.byref(a), _stream_ptr(self.device)))
         return assignment, score
 
+    # ---- log Z and the joint log-likelihood (include/mlbp_logz.h) -----------------------------------
+    def log_partition(self, roots=None, init=True, labels=None, sum_out=None, score=None):
+        """log Z of every graph from the factor->variable messages: exact on a tree, the Bethe value on a loopy graph.
+        With `roots` it first runs self.sweep(roots, init=init) with the messages kept; without, it reads self.msgs as the
+        last sweep (sum-product, exact or approximate) left them.  Returns log_z [B], or (log_z, joint_logp) when `labels`
+        ([B][n_vars] integers, GraphTopology.var_ids order; an int32 device tensor is used as it is) is given:
+        joint_logp = score(labels) - log_z, the log-probability of the whole assignment, where score is map_sweep's -- the sum
+        over factors of the log table entry.  Device tensors.  A label outside [0, X) gives NaN for that graph, a zero table
+        entry at the labels -inf.  sum_out: optional [2] float64 device tensor that receives the batch sums of log_z and
+        joint_logp (added in a fixed order by one more launch); score: optional [B] float64 device tensor that receives
+        score(labels)."""
+        from . import logz as L
+        if self.pair_tables is not None and self.pair_tables.dtype != torch.float64:
+            raise NotImplementedError('log_partition needs float64 pairwise tables')
+        topo = self.topo
+        if roots is not None:
+            self.sweep(roots, init=init, keep_messages=True)
+        ro = L.readout(topo, self.device)
+        a = L.LogzArgs()
+        a.B, a.X, a.n_msgs, a.P, a.U, a.n_vars = self.B, self.X, topo.n_msgs, topo.P, topo.U, topo.n_vars
+        if topo.P:
+            if self.pair_tables is None:
+                raise RuntimeError('set_pair_tables() first')
+            a.n_pair_tables = self.pair_tables.shape[0]
+            a.pair_tables, a.pair_tab = self.pair_tables.data_ptr(), self.pair_tab.data_ptr()
+            a.pair_axis_var, a.pair_in_slot = ro.pair_axis_var.data_ptr(), ro.pair_in_slot.data_ptr()
+            if getattr(self, 'pair_tables_shared', False):
+                a.flags |= L.SHARED_PAIR_TABLES
+        if topo.U:
+            if self.unary_tables is None:
+                raise RuntimeError('set_unary_tables() first')
+            a.n_unary_tables = self.unary_tables.shape[0]
+            a.unary_tables, a.unary_tab = self.unary_tables.data_ptr(), self.unary_tab.data_ptr()
+            a.unary_var, a.unary_in_slot = ro.unary_var.data_ptr(), ro.unary_in_slot.data_ptr()
+        a.msgs = self.msgs.data_ptr()
+        a.in_off, a.in_slots = ro.in_off.data_ptr(), ro.in_slots.data_ptr()
+        log_z = torch.empty(self.B, dtype=torch.float64, device=self.device)
+        a.log_z = log_z.data_ptr()
+        joint = lab = None
+        if labels is not None:
+            if torch.is_tensor(labels) and labels.dtype == torch.int32 and labels.device == self.device and labels.is_contiguous():
+                lab = labels
+            else:
+                host = labels.cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
+                lab = torch.from_numpy(np.ascontiguousarray(host.astype(np.int64).astype(np.int32))).to(self.device)
+            if tuple(lab.shape) != (self.B, topo.n_vars):
+                raise ValueError('labels must be [B][n_vars]')
+            joint = torch.empty(self.B, dtype=torch.float64, device=self.device)
+            a.labels, a.joint_logp = lab.data_ptr(), joint.data_ptr()
+            if score is not None:
+                if score.dtype != torch.float64 or score.numel() < self.B or score.device != self.device:
+                    raise ValueError('score must be a float64 device tensor of B elements')
+                a.score = score.data_ptr()
+        elif score is not None:
+            raise ValueError('score needs labels')
+        if sum_out is not None:
+            if sum_out.dtype != torch.float64 or sum_out.numel() < 2 or sum_out.device != self.device:
+                raise ValueError('sum_out must be a float64 device tensor of two elements')
+            a.sum_out = sum_out.data_ptr()
+        L.check(L.lib.mlbp_logz_f64(C.byref(a), _stream_ptr(self.device)))
+        return log_z if labels is None else (log_z, joint)
+
     def treelike_inference(self, iterations, roots):
         """`iterations` sweeps if the graph is loopy, else one (LBP.py:219); `roots` replaces the
         per-sweep random.sample draw (LBP.py:223).  Returns the number of sweeps run."""

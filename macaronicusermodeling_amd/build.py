@@ -1,4 +1,4 @@
-"""Builds libmlbp.so and libmlbp_map.so (gfx950 only) in-tree with hipcc.  `python -m macaronicusermodeling_amd.build`.
+"""Builds libmlbp.so, libmlbp_map.so and libmlbp_logz.so (gfx950 only) in-tree with hipcc.  `python -m macaronicusermodeling_amd.build`.
 
 hipcc cross-compiles without a GPU, so this runs in the build container; the resulting .so is
 git-ignored but travels to the GPU box with the working-tree snapshot.
@@ -15,6 +15,10 @@ SOURCES = ['mlbp_host.cpp', 'mlbp_sweep.hip', 'mlbp_lean.hip', 'mlbp_shared.hip'
 CSRC_MAP = os.path.join(PKG, 'csrc_map')
 LIB_MAP = os.path.join(PKG, 'libmlbp_map.so')
 SOURCES_MAP = ['mlbp_map.hip']
+# the log-partition / joint-likelihood library (include/mlbp_logz.h): again its own sources and inventory, the same flags
+CSRC_LOGZ = os.path.join(PKG, 'csrc_logz')
+LIB_LOGZ = os.path.join(PKG, 'libmlbp_logz.so')
+SOURCES_LOGZ = ['mlbp_logz.hip']
 FLAGS = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-fno-fast-math', '-Wall',
          '-Wno-unused-function']
 
@@ -44,12 +48,14 @@ def _build_one(hipcc, csrc, sources, headers, lib, force, verbose):
 
 
 def build(force=False, verbose=False):
-    """Builds both libraries; returns the path of libmlbp.so (libmlbp_map.so lies beside it: LIB_MAP)."""
+    """Builds the three libraries; returns the path of libmlbp.so (the others lie beside it: LIB_MAP, LIB_LOGZ)."""
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     headers = [os.path.join(CSRC, 'mlbp_internal.h'), os.path.join(CSRC, 'mlbp_device.h'), os.path.join(PKG, '..', 'include', 'mlbp.h')]
     lib = _build_one(hipcc, CSRC, SOURCES, headers, LIB, force, verbose)
     headers_map = [os.path.join(CSRC, 'mlbp_device.h'), os.path.join(PKG, '..', 'include', 'mlbp_map.h')]
     _build_one(hipcc, CSRC_MAP, SOURCES_MAP, headers_map, LIB_MAP, force, verbose)
+    headers_logz = [os.path.join(CSRC, 'mlbp_device.h'), os.path.join(PKG, '..', 'include', 'mlbp_logz.h')]
+    _build_one(hipcc, CSRC_LOGZ, SOURCES_LOGZ, headers_logz, LIB_LOGZ, force, verbose)
     return lib
 
 

@@ -258,6 +258,16 @@ class UserGraphTrainer:
         assignment, score = self.batch.map_sweep(self.roots[:self.n_sweeps_run], init=True, keep_messages=False)
         return assignment.cpu().numpy().astype(np.int64), score.cpu().numpy()
 
+    def joint_log_likelihood(self):
+        """How probable the model finds each instance's whole set of stored labels, under the current thetas: host
+        (joint_logp float64 [B], log_z float64 [B]).  Sum-product sweeps over the predict() schedule with the messages kept,
+        then FactorGraphBatch.log_partition: joint_logp = score(labels) - log Z, exact where the graph is a tree (one
+        predicted word: the log-posterior predict() reports), the Bethe value otherwise."""
+        fb = self.batch
+        self.build_potentials()
+        log_z, joint = fb.log_partition(self.roots[:self.n_sweeps_run], init=True, labels=fb._labels)
+        return joint.cpu().numpy(), log_z.cpu().numpy()
+
 
 def apply_update(theta_en_en, theta_en_de, stats, F_ee, F_ed, learning_rate, reg_param):
     """theta += sum_i lr (g_i - reg theta) = lr (sum_i g_i - n reg theta): the sum of the per-instance
@@ -799,6 +809,27 @@ class TiDirTrainer:
         tot = torch.tensor([float(v) for v in counts], dtype=torch.float64, device=self.device)
         mdist.all_reduce_sum_(tot)
         return guesses, tuple(int(v) for v in tot.cpu().numpy())
+
+    # ---- joint log-likelihood (log Z; the reference has only the sum of per-word log-marginals) ------
+    def joint_log_likelihood(self):
+        """-> (per_instance, totals).  per_instance[i], for instance i of this rank's shard in file order: (predicted
+        positions, joint_logp, log_z) -- the log-probability of the user's whole set of guesses for the sentence
+        (UserGraphTrainer.joint_log_likelihood) and the sentence graph's log Z; an instance without a predicted word builds
+        no graph and gives ((), 0.0, 0.0).  totals = (sum of joint_logp, sentences with a predicted word) over ALL ranks'
+        instances, reduced once."""
+        n = self._shard[1] - self._shard[0]
+        per_instance = [((), 0.0, 0.0)] * n
+        total, seen = 0.0, 0
+        for key, tr in self.trainers.items():
+            joint, log_z = tr.joint_log_likelihood()
+            total += float(joint.sum())
+            seen += joint.shape[0]
+            for b, row in enumerate(self.buckets[key]['rows']):
+                per_instance[row['index']] = (tuple(key[1]), float(joint[b]), float(log_z[b]))
+        tot = torch.tensor([total, float(seen)], dtype=torch.float64, device=self.device)
+        mdist.all_reduce_sum_(tot)
+        tot = tot.cpu().numpy()
+        return per_instance, (float(tot[0]), int(tot[1]))
 
     # ---- prediction pass (train_mp.py:310-343, 692-770) -------------------------------------------
     def predict(self, save_predictions=None):
