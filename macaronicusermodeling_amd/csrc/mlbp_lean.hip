@@ -71,6 +71,18 @@ __device__ __forceinline__ double swapadd32(double a, double b) {
   return __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
 }
 
+// Workgroup-wide "any" with ONE barrier: each wave's ballot into its word of `votes`, the barrier, every thread reads the four
+// words.  (__syncthreads_or / __syncthreads_and compile to three barriers each; the three votes of a launch cost 1.0-1.4 %
+// of it that way.)  The four words must not be written again, by a later vote or as anything else, before every wave has
+// passed one more barrier.
+__device__ __forceinline__ bool vote_any(bool p, int32_t* votes, int wave, int lane) {
+  const int mine = __ballot(p) != 0 ? 1 : 0;
+  if (lane == 0) votes[wave] = mine;
+  lds_barrier();
+  const int4 v = *reinterpret_cast<const int4*>(votes);
+  return (v.x | v.y | v.z | v.w) != 0;
+}
+
 struct LaneGeo {
   int tm0, tm1;   // byte offsets inside a message of the lane's column pairs held in table registers k = 0, 1
   int mt;         // byte offset of the lane's four rows
@@ -450,6 +462,13 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
   const int32_t* img_hoist = f.image + 16 * (size_t)f.n_bundles;
   const int32_t* img_cprod = img_hoist + 8 * (size_t)f.HL;
   const int32_t* img_written = img_cprod + 16 * (size_t)f.n_cprod;
+  // the words of the workgroup votes (vote_any) lie in red, idle outside the sweeps: the first and the last vote at its start
+  // (next written by the first bundle, behind the second vote's barrier; after the last vote by the gradient epilogue, behind
+  // its own barrier), the second vote, which leads straight into the sweeps, in the half the SECOND bundle writes
+  int32_t* votes = reinterpret_cast<int32_t*>(red);
+  // (the GRAD instances keep the library's votes and the micro-ops' own barrier: they sit at their register limit, and this
+  // form costs them two more spilled registers and 2.4 % of the train step)
+  constexpr bool LEAN_SYNC = !GRAD;
 
   LaneGeo G;
   const int c_ = (lane & 7) | ((lane >> 1) & 8), b3_ = (lane >> 3) & 1, R_ = 4 * wave + (b3_ | ((lane >> 5) << 1));
@@ -576,13 +595,16 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
     if (t >= 32 && t < 64) dst[(d.n_msgs + f.n_ext - 1) * 32 + (t - 32)] = make_double2(1.0, 1.0);   // last ext slot: ones
   }
   lds_barrier();        // the fill above and the unary messages below write the same slots from different waves
-  // hoisted unary messages (exact values: they are outputs); further rounds only when a wave has more than HB rows
+  // hoisted unary messages (exact values: they are outputs); further rounds only when a wave has more than HB rows.  A row
+  // whose total is not positive (all zero, or NaN) flags its graph like a zero-total update inside the sweeps (rescale): the
+  // zero-sum -> uniform rule of LBP.py:655-657 acts, and every graph it acts on goes to the exact kernel -- one rule for the
+  // prologue and the main loop, and exact_count counts all such graphs
 #pragma unroll
   for (int j = 0; j < HB; ++j) {
     if (uslot[j] >= 0) {
       const double s = wave_sum(ur[j]);
       const double m = renorm(ur[j], s, uni_l, true);
-      bad_key = max(bad_key, mag_key(m));
+      bad_key = max(bad_key, s > 0.0 ? mag_key(m) : KEY_BAD);
       work[uslot[j] * 64 + lane] = m;
       if (GRAD && lane == 0) { gst[ufac[j]] = uslot[j]; gst[d.U + ufac[j]] = s > 0.0 ? 1 : 0; }
     }
@@ -598,11 +620,11 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
     else if (!PADX || lane < X) r = d.unary_tables[(size_t)row * X + lane];
     const double s = wave_sum(r);
     const double m = renorm(r, s, uni_l, true);
-    bad_key = max(bad_key, mag_key(m));
+    bad_key = max(bad_key, s > 0.0 ? mag_key(m) : KEY_BAD);
     work[slot * 64 + lane] = m;
     if (GRAD && lane == 0) { gst[u] = slot; gst[d.U + u] = s > 0.0 ? 1 : 0; }
   }
-  if (!__syncthreads_and(ok ? 1 : 0)) {       // an out-of-range table index: skip the graph, raise the status word
+  if (LEAN_SYNC ? vote_any(!ok, votes, wave, lane) : !__syncthreads_and(ok ? 1 : 0)) {       // an out-of-range table index: skip the graph, raise the status word
     if (t == 0) atomicExch(d.status, 1);
     // "skipped" means untouched -- except that a call which was asked to initialise leaves the graph initialised
     // (FactorGraph.initialize, LBP.py:211-216), not holding whatever the caller's buffer held
@@ -628,19 +650,24 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
     bad_key = max(bad_key, mag_key(acc));               // a non-finite intermediate stays non-finite: nan_to_num territory
     work[(d.n_msgs + 1 + k) * 64 + lane] = acc;
   }
-  if (__syncthreads_or(bad_key >= KEY_BAD ? 1 : 0)) {
+  // the micro-ops go into LDS ahead of the prologue's verdict: the vote's barrier publishes them, and the LDS-DMA tables that
+  // have landed, for the main loop (a barrier of their own cost what a bundle's does)
+  auto fill_limg = [&]() {
+    if (NL > 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int q = 0; q < PW; ++q)
+      if (t + q * WG < 16 * (f.n_bundles + 1)) limg[t + q * WG] = pre[q];
+    for (int i = t + PW * WG; i < 16 * (f.n_bundles + 1); i += WG) limg[i] = f.image[i];
+  };
+  if (LEAN_SYNC) fill_limg();
+  if (LEAN_SYNC ? vote_any(bad_key >= KEY_BAD, votes + 1024, wave, lane) : __syncthreads_or(bad_key >= KEY_BAD ? 1 : 0) != 0) {
     if (t == 0) f.bail[g] = 1;                    // bail codes: 1 prologue, 2 main loop, 3 final pass
     return;
   }
+  if (!LEAN_SYNC) { fill_limg(); lds_barrier(); }
 
   // ---- main loop: identical in all four waves; one barrier per bundle.  The micro-ops sit in LDS; a bundle's 16 words
   //      are read (broadcast) one bundle ahead ----
-  if (NL > 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the LDS-DMA tables have landed (the barrier below publishes them)
-#pragma unroll
-  for (int q = 0; q < PW; ++q)
-    if (t + q * WG < 16 * (f.n_bundles + 1)) limg[t + q * WG] = pre[q];
-  for (int i = t + PW * WG; i < 16 * (f.n_bundles + 1); i += WG) limg[i] = f.image[i];
-  lds_barrier();
   char* wb = reinterpret_cast<char*>(work);
   int parity = 0, bad = 0;
   double carry = 1.0;
@@ -742,7 +769,7 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
         if (slot[j] >= 0) work[slot[j] * 64 + lane] = v[j] / s[j];
     }
   }
-  if (__syncthreads_or(bad_out ? 1 : 0)) {         // nothing of a flagged graph is written back
+  if (LEAN_SYNC ? vote_any(bad_out, votes, wave, lane) : __syncthreads_or(bad_out ? 1 : 0) != 0) {         // nothing of a flagged graph is written back
     if (t == 0) f.bail[g] = 3;
     return;
   }
