@@ -7,7 +7,8 @@
 // update -- the old kernel spent ~275 wave instructions and ~10 dependent LDS round trips around 16 useful FMAs:
 //
 //   * the program is compiled on the host into 8-word micro-ops whose operands are LDS byte offsets, so an
-//     update reads one descriptor and issues its message loads at once (no source lists, no slot arithmetic);
+//     update reads one descriptor and issues its message loads at once (no source lists, no slot arithmetic; the
+//     list is padded with an all-ones slot, so two sources -- four with one branch -- are fetched without a count);
 //   * a thread owns a 4 x 4 block of each table (rows 4R..4R+3, column pairs {2c,2c+1} and {32+2c,33+2c}), so BOTH
 //     directions of an update are 16 FMAs followed by a short select-light reduction:
 //        T.m   (reduce over columns): v_permlane16_swap (4 -> 2 values), one DPP step with a select (2 -> 1), two
@@ -49,7 +50,8 @@ constexpr int UOP_CARRY_IN = 0x1000;   // a link of a long variable product: sta
 constexpr int UOP_CARRY_OUT = 0x2000;  // ... and hands it on instead of storing it
 constexpr int GROUP_WORDS = 48;     // one group descriptor of a MULTI launch (see launch_lean_groups)
 // micro-op words: 0 flags | 1-4 source byte offsets | 5 byte offset of the variable->factor message to store, or -1 |
-// 6 destination byte offset | 7 unused.  A bundle = two micro-ops = 16 words = one s_load_dwordx16.
+// 6 destination byte offset | 7 unused.  Source words past the count hold the all-ones ext slot.
+// A bundle = two micro-ops = 16 words = one s_load_dwordx16.
 
 struct LeanDev {
   const int32_t* image;   // bundles [n_bundles][16] | hoist [4][HL][2] | cprod lists [n_cprod][16] | written [4][WL] | pad
@@ -106,20 +108,29 @@ struct LdsTable {
   __device__ __forceinline__ double2 operator()(int r, int k) const { return base[(r * 2 + k) * WG]; }
 };
 
-template <bool MT, typename TB>
+// WIDE: sources 3-4 are fetched together (else one after the other: the one-table instances, whose updates rarely have them,
+// would pay eight registers and a fifth workgroup per CU for it)
+template <bool MT, bool WIDE, typename TB>
 __device__ __forceinline__ void contract(const TB T, char* wb, int u0, int s1, int s2, int s3, int s4, int vf,
                                          const LaneGeo& G, char* redA) {
   const int nsrc = (u0 >> UOP_NSRC_SHIFT) & 15;
   const bool has_vf = (u0 & UOP_STORE_VF) != 0;
   if (MT) {
+    // sources 1-2 in one round trip, 3-4 in a second one: the host pads the list with the all-ones slot (x * 1.0 is exact)
     double2 ma = lds2(wb + s1 + G.mt), mb = lds2(wb + s1 + G.mt + 16);
-    if (nsrc > 1) {
+    {
       const double2 a = lds2(wb + s2 + G.mt), b = lds2(wb + s2 + G.mt + 16);
       mul2(ma, a); mul2(mb, b);
-      if (nsrc > 2) {
+    }
+    if (nsrc > 2) {
+      if (WIDE) {
         const double2 a2 = lds2(wb + s3 + G.mt), b2 = lds2(wb + s3 + G.mt + 16);
+        const double2 a3 = lds2(wb + s4 + G.mt), b3 = lds2(wb + s4 + G.mt + 16);
         mul2(ma, a2); mul2(mb, b2);
-        if (nsrc > 3) { const double2 a3 = lds2(wb + s4 + G.mt), b3 = lds2(wb + s4 + G.mt + 16); mul2(ma, a3); mul2(mb, b3); }
+        mul2(ma, a3); mul2(mb, b3);
+      } else {
+        mul2(ma, lds2(wb + s3 + G.mt)); mul2(mb, lds2(wb + s3 + G.mt + 16));
+        if (nsrc > 3) { mul2(ma, lds2(wb + s4 + G.mt)); mul2(mb, lds2(wb + s4 + G.mt + 16)); }
       }
     }
     if (has_vf && G.st_mt) {
@@ -137,13 +148,19 @@ __device__ __forceinline__ void contract(const TB T, char* wb, int u0, int s1, i
     *reinterpret_cast<double*>(redA + G.red_mt) = swapadd32(a00, a01);
   } else {
     double2 m0 = lds2(wb + s1 + G.tm0), m1 = lds2(wb + s1 + G.tm1);
-    if (nsrc > 1) {
+    {
       const double2 a = lds2(wb + s2 + G.tm0), b = lds2(wb + s2 + G.tm1);
       mul2(m0, a); mul2(m1, b);
-      if (nsrc > 2) {
+    }
+    if (nsrc > 2) {
+      if (WIDE) {
         const double2 a2 = lds2(wb + s3 + G.tm0), b2 = lds2(wb + s3 + G.tm1);
+        const double2 a3 = lds2(wb + s4 + G.tm0), b3 = lds2(wb + s4 + G.tm1);
         mul2(m0, a2); mul2(m1, b2);
-        if (nsrc > 3) { const double2 a3 = lds2(wb + s4 + G.tm0), b3 = lds2(wb + s4 + G.tm1); mul2(m0, a3); mul2(m1, b3); }
+        mul2(m0, a3); mul2(m1, b3);
+      } else {
+        mul2(m0, lds2(wb + s3 + G.tm0)); mul2(m1, lds2(wb + s3 + G.tm1));
+        if (nsrc > 3) { mul2(m0, lds2(wb + s4 + G.tm0)); mul2(m1, lds2(wb + s4 + G.tm1)); }
       }
     }
     if (has_vf && G.st_tm) {
@@ -176,14 +193,14 @@ __device__ __forceinline__ void front(const double2 (&tab)[NT][4][2], const doub
 #pragma unroll
   for (int p = 0; p < NT; ++p) {
     if (p == pslot) {
-      if (u0 & UOP_MT) contract<true>(RegTable{tab[p]}, wb, u0, lo.y, lo.z, lo.w, hi.x, hi.y, G, redA);
-      else contract<false>(RegTable{tab[p]}, wb, u0, lo.y, lo.z, lo.w, hi.x, hi.y, G, redA);
+      if (u0 & UOP_MT) contract<true, (NT > 1)>(RegTable{tab[p]}, wb, u0, lo.y, lo.z, lo.w, hi.x, hi.y, G, redA);
+      else contract<false, (NT > 1)>(RegTable{tab[p]}, wb, u0, lo.y, lo.z, lo.w, hi.x, hi.y, G, redA);
     }
   }
   if (NL > 0 && pslot >= NT) {
     const LdsTable T = {tl + (size_t)(pslot - NT) * 8 * WG};
-    if (u0 & UOP_MT) contract<true>(T, wb, u0, lo.y, lo.z, lo.w, hi.x, hi.y, G, redA);
-    else contract<false>(T, wb, u0, lo.y, lo.z, lo.w, hi.x, hi.y, G, redA);
+    if (u0 & UOP_MT) contract<true, (NT > 1)>(T, wb, u0, lo.y, lo.z, lo.w, hi.x, hi.y, G, redA);
+    else contract<false, (NT > 1)>(T, wb, u0, lo.y, lo.z, lo.w, hi.x, hi.y, G, redA);
   }
 }
 
@@ -469,6 +486,10 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
   // (the GRAD instances keep the library's votes and the micro-ops' own barrier: they sit at their register limit, and this
   // form costs them two more spilled registers and 2.4 % of the train step)
   constexpr bool LEAN_SYNC = !GRAD;
+  // (likewise the counted wait of phase A: its unconditional loads and the parked index word double <3, GRAD>'s spills, so the
+  // GRAD instances keep conditional loads and the index check in a loop, and with them one wait for everything)
+  constexpr bool EARLY = !GRAD;
+  static_assert(!(GRAD && PADX), "the GRAD form of phase A loads whole rows: X = 64 only");
 
   LaneGeo G;
   const int c_ = (lane & 7) | ((lane >> 1) & 8), b3_ = (lane >> 3) & 1, R_ = 4 * wave + (b3_ | ((lane >> 5) << 1));
@@ -491,8 +512,13 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
     g_kind = gf.unary_kind[t]; g_obs = gf.unary_obs[(size_t)g * d.U + t]; g_lab = gf.unary_label[(size_t)g * d.U + t];
   }
   // ---- phase A: every HBM load of the graph is issued before anything waits: unary rows first (they are needed
-  //      first and vmcnt retires in order), then the tables, then the (dense) index check ----
+  //      first and vmcnt retires in order), then the tables, then the (dense) index check and the micro-op image.
+  //      Every load after the rows is issued unconditionally -- one that has nothing to fetch reads the head of the
+  //      micro-op image (padded to 2 KB by build_lean_program) and its value is never looked at -- so that the number
+  //      of loads behind the rows is the same on every path and the wait for the rows is a counted one: the fill, the
+  //      hoisted unary messages, the first vote and the constant products run while the tables are still arriving ----
   bool ok = true;
+  const double* nowhere = reinterpret_cast<const double*>(f.image);
   constexpr int HB = 8;                       // unary rows per wave held in registers; more go round again below
   double ur[HB];
   int uslot[HB], ufac[HB];
@@ -503,18 +529,41 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
       const int u = hl.w[2 * j];
       uslot[j] = hl.w[2 * j + 1];
       ufac[j] = u;
-      ur[j] = 0.0;
-      if (u >= 0) {
-        const int row = f.dense ? g * d.U + u : as_const(d.unary_tab)[(size_t)g * d.U + u];
-        if ((unsigned)row >= (unsigned)d.n_unary_tables) ok = false;
-        else if (!PADX || lane < X) ur[j] = d.unary_tables[(size_t)row * X + lane];
+      if (EARLY) {
+        // the index word of an entry that exists only (a scalar load, outside the count; a graph without unary factors brings
+        // no unary_tab); an empty entry or a row out of range loads a value nobody uses -- uslot < 0 skips it, !ok skips the
+        // graph; PADX lanes past X are zeroed where the row is used
+        int row = -1;
+        if (u >= 0) row = f.dense ? g * d.U + u : as_const(d.unary_tab)[(size_t)g * d.U + u];
+        const bool in = (unsigned)row < (unsigned)d.n_unary_tables;
+        if (u >= 0 && !in) ok = false;
+        const double* at = in ? d.unary_tables + (size_t)row * X + (PADX ? min(lane, X - 1) : lane) : nowhere;
+        ur[j] = *at;
+      } else {
+        ur[j] = 0.0;
+        if (u >= 0) {
+          const int row = f.dense ? g * d.U + u : as_const(d.unary_tab)[(size_t)g * d.U + u];
+          if ((unsigned)row >= (unsigned)d.n_unary_tables) ok = false;
+          else ur[j] = d.unary_tables[(size_t)row * X + lane];
+        }
       }
     }
   }
   double2 tab[NT][4][2];
 #pragma unroll
   for (int p = 0; p < NT; ++p) {
-    if (p < d.P) {
+    if (!PADX && EARLY) {
+      const int pc = p < d.P ? p : 0;
+      const int ti = f.dense ? g * d.P + pc : as_const(d.pair_tab)[(size_t)g * d.P + pc];
+      const bool in = (unsigned)ti < (unsigned)d.n_pair_tables;
+      if (p < d.P && !in) ok = false;
+      const double* T = (p < d.P && in) ? d.pair_tables + (size_t)ti * 4096 + (size_t)(4 * R_) * 64 + 2 * c_ : nowhere;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        tab[p][r][0] = NT_LOAD2(T + r * 64 + 32 * b3_);
+        tab[p][r][1] = NT_LOAD2(T + r * 64 + 32 * (1 - b3_));
+      }
+    } else if (p < d.P) {
       const int ti = f.dense ? g * d.P + p : as_const(d.pair_tab)[(size_t)g * d.P + p];
       if ((unsigned)ti >= (unsigned)d.n_pair_tables) { ok = false; continue; }
       if (!PADX) {
@@ -556,19 +605,26 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
         }
     }
   }
-  // MLBP_SWEEP_DENSE_TABLES is a statement about the index arrays; it is checked off the critical path (the loads
-  // queue behind the tables and are looked at after the sweeps): a false one sends the graph to the exact kernel,
-  // which reads the arrays.
+  // MLBP_SWEEP_DENSE_TABLES is a statement about the index arrays; it is checked off the critical path: thread i < P + U
+  // (lean_plan keeps P + U within the workgroup) requests word i behind the tables, parks it in a register and compares it
+  // after the sweeps: a false statement sends the graph to the exact kernel, which reads the arrays.
+  int dense_word = 0;
   bool dense_ok = true;
-  if (f.dense)
+  if (EARLY) {
+    const int i = min(t, d.P + d.U - 1);
+    const int32_t* at = i < d.P ? d.pair_tab + (size_t)g * d.P + i : d.unary_tab + (size_t)g * d.U + (i - d.P);
+    dense_word = *(f.dense ? at : f.image);
+  } else if (f.dense) {
     for (int i = t; i < d.P + d.U; i += WG)
       dense_ok &= i < d.P ? d.pair_tab[(size_t)g * d.P + i] == g * d.P + i : d.unary_tab[(size_t)g * d.U + (i - d.P)] == g * d.U + (i - d.P);
+  }
   // the micro-op image, requested behind the tables (it is first read when the sweeps start, i.e. when the tables are
   // there) and parked in registers until then
   constexpr int PW = 2;
   int32_t pre[PW];
 #pragma unroll
-  for (int q = 0; q < PW; ++q) pre[q] = (t + q * WG < 16 * (f.n_bundles + 1)) ? f.image[t + q * WG] : 0;
+  for (int q = 0; q < PW; ++q)
+    pre[q] = EARLY ? f.image[min(t + q * WG, 16 * (f.n_bundles + 1) - 1)] : ((t + q * WG < 16 * (f.n_bundles + 1)) ? f.image[t + q * WG] : 0);
   unsigned bad_key = 0;
   {
     double2* dst = reinterpret_cast<double2*>(work);
@@ -602,8 +658,9 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
 #pragma unroll
   for (int j = 0; j < HB; ++j) {
     if (uslot[j] >= 0) {
-      const double s = wave_sum(ur[j]);
-      const double m = renorm(ur[j], s, uni_l, true);
+      const double r = (!PADX || lane < X) ? ur[j] : 0.0;
+      const double s = wave_sum(r);
+      const double m = renorm(r, s, uni_l, true);
       bad_key = max(bad_key, s > 0.0 ? mag_key(m) : KEY_BAD);
       work[uslot[j] * 64 + lane] = m;
       if (GRAD && lane == 0) { gst[ufac[j]] = uslot[j]; gst[d.U + ufac[j]] = s > 0.0 ? 1 : 0; }
@@ -683,10 +740,14 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
       // that another wave may still be writing)
       const int nsrc = (fA >> UOP_NSRC_SHIFT) & 15;
       double m = work[(A0.y >> 3) + lane];
+      const double m2 = work[(A0.z >> 3) + lane];          // (padded with the all-ones slot, like a contraction's list)
       if (fA & UOP_CARRY_IN) m *= carry;
-      if (nsrc > 1) m *= work[(A0.z >> 3) + lane];
-      if (nsrc > 2) m *= work[(A0.w >> 3) + lane];
-      if (nsrc > 3) m *= work[(A1.x >> 3) + lane];
+      m *= m2;
+      if (nsrc > 2) {
+        const double m3 = work[(A0.w >> 3) + lane], m4 = work[(A1.x >> 3) + lane];
+        m *= m3;
+        m *= m4;
+      }
       if (fA & UOP_CARRY_OUT) carry = m;
       else work[(A1.y >> 3) + lane] = m;
     } else {
@@ -716,6 +777,7 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
   // ---- read-out (VariableNode.get_marginal, LBP.py:392-400) straight from the scaled messages: the marginal is
   //      normalised, so the scales cancel; constant part = the variable's constant product ----
   double marg[2] = {0.0, 0.0};
+  if (EARLY) dense_ok = !f.dense || t >= d.P + d.U || dense_word == (t < d.P ? g * d.P + t : g * d.U + (t - d.P));
   bool bad_out = !dense_ok;
   if (f.readout) {
 #pragma unroll
@@ -801,16 +863,19 @@ namespace mlbp {
 // than four sources is split into a chain of variable-only micro-ops ("links") that hand the running product on in a
 // register (UOP_CARRY_OUT / UOP_CARRY_IN); only the last link stores.
 // Image: bundles [n_bundles][16] | per-wave hoist lists [4][HL][2] | constant-product lists [n_cprod][16] |
-// per-wave written-slot lists [4][WL] | one bundle of padding (the loop prefetches one bundle past the end).
+// per-wave written-slot lists [4][WL] | one bundle of padding (the loop prefetches one bundle past the end), zeros up to 2 KB.
 void build_lean_program(const FusedProgram& fp, int n_msgs, LeanProgram& out) {
   out = LeanProgram();
   if (fp.has_unary_fops) { out.why = "in-loop unary updates (not hoistable)"; return; }
   std::vector<int32_t> U;                            // micro-ops, 8 words each
+  // every source list is padded to four entries with the all-ones ext slot: the kernel fetches sources 1-2, and 3-4 when
+  // there are more than two, without looking at the count in between
+  const int32_t ones = (n_msgs + 1 + fp.n_cprod) * 512;
   std::vector<char> second;                          // micro-op i is the second member of a bundle
   auto emit_var = [&](const int32_t* src, int n, int c) {      // work[c] = prod(src[0..n))
     int done = 0;
     do {
-      int32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      int32_t w[8] = {0, ones, ones, ones, ones, 0, 0, 0};
       int k = 0;
       const bool first = done == 0;
       while (k < 4 && done < n) w[1 + k++] = src[done++] * 512;
@@ -835,7 +900,7 @@ void build_lean_program(const FusedProgram& fp, int n_msgs, LeanProgram& out) {
     for (int m = 0; m < members; ++m) {
       const int32_t* q = &fp.fops[8 * (size_t)(i + m)];
       const int kd = q[0] & 0xFF;
-      int32_t u[8] = {0, 0, 0, 0, 0, -1, 0, 0};
+      int32_t u[8] = {0, ones, ones, ones, ones, -1, 0, 0};
       if (kd == FOP_PAIR_TM || kd == FOP_PAIR_MT) {
         u[0] = (kd == FOP_PAIR_MT ? UOP_MT : 0) | (q[1] << UOP_PSLOT_SHIFT) | (1 << UOP_NSRC_SHIFT);
         u[1] = q[2] * 512;
@@ -899,14 +964,13 @@ void build_lean_program(const FusedProgram& fp, int n_msgs, LeanProgram& out) {
   }
   // constant-product lists, 16 words each, padded with the all-ones ext slot
   out.n_cprod = fp.n_cprod;
-  const int ones = n_msgs + 1 + fp.n_cprod;
   out.cprods.clear();
   for (size_t at = 0; at < fp.cpw.size();) {
     const int cnt = fp.cpw[at];
     if (cnt > 15) { out.why = "a constant product of more than 15 messages"; out.image.clear(); return; }
     int32_t l[16];
     l[0] = cnt;
-    for (int q = 0; q < 15; ++q) l[1 + q] = q < cnt ? fp.cpw[at + 1 + q] : ones;
+    for (int q = 0; q < 15; ++q) l[1 + q] = q < cnt ? fp.cpw[at + 1 + q] : ones / 512;
     I.insert(I.end(), l, l + 16);
     out.cprods.push_back(std::vector<int32_t>(fp.cpw.begin() + at + 1, fp.cpw.begin() + at + 1 + cnt));
     at += 1 + cnt;
@@ -922,6 +986,7 @@ void build_lean_program(const FusedProgram& fp, int n_msgs, LeanProgram& out) {
     I.insert(I.end(), wl.begin(), wl.end());
   }
   for (int q = 0; q < 16; ++q) I.push_back(q == 0 || q == 8 ? UOP_NOP : 0);
+  if (I.size() < 512) I.resize(512, 0);              // 2 KB at least: where the kernel's loads with nothing to fetch point (a table's 4 x 4 block spans 1.8 KB)
   out.ok = true;
 }
 
@@ -969,6 +1034,7 @@ static int lean_plan(const mlbp_program* prog, const mlbp_sweep_args* a, bool gr
   if (prog->P == 7 && !padx) *lds += 32 * 1024;   // the seventh table lives in LDS
   if (grad) *lds += 5 * (size_t)prog->U * sizeof(int32_t);
   if (*lds > 80 * 1024) return MLBP_OK;           // large graphs: the generic kernel's rules apply
+  if (prog->P + prog->U > WG) return MLBP_OK;     // the dense-layout check is one index word per thread
   const bool dense = (a->flags & MLBP_SWEEP_DENSE_TABLES) != 0;
   if (dense && ((int64_t)a->B * prog->P > a->n_pair_tables || (int64_t)a->B * prog->U > a->n_unary_tables))
     return fail(MLBP_EINVAL, "mlbp_sweep_f64: MLBP_SWEEP_DENSE_TABLES needs B*P pair tables and B*U unary columns");
