@@ -614,6 +614,8 @@ __device__ __forceinline__ double column_sum(double v) {
 }
 // A total a reader may divide by: finite, positive and far from the ends of the exponent range.
 __device__ __forceinline__ bool total_ok(double t) { return t >= 1e-280 && t <= 1e280; }
+// floor(log2 t) of a total that passes total_ok (anything else flags its graph, and what is computed from it is discarded)
+__device__ __forceinline__ int total_exponent(double t) { return (int)(((unsigned)__double2hiint(t) >> 20) & 0x7FFu) - 1023; }
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
@@ -873,10 +875,19 @@ __global__ __launch_bounds__(PWG, 8) void shared_prepare_kernel(PrepareDev d, co
       if (first) { cur = 1.0; key = 0; }
 #pragma unroll
       for (int j = 0; j < RB; ++j)
-        if (b0 + j <= b1) { key = max(key, (unsigned)__double2hiint(r[j])); cur *= r[j]; }
+        if (b0 + j <= b1) {
+          // a column enters the product with its largest entry in [1, 2): an exact power-of-two scale, so the product of any
+          // number of columns neither overflows nor loses an entry the reference's product of normalised columns keeps,
+          // whatever the columns' own magnitudes (eight columns near 2^500 are a trained model, not a degenerate graph)
+          const unsigned hi = (unsigned)__double2hiint(r[j]);
+          key = max(key, hi);
+          const int top = (int)(mlbp_dev::wave_max_u32(hi & 0x7FFFFFFFu) >> 20);
+          flagged |= top == 0;                                   // no normal entry: the exact kernel's division decides what is left of it
+          cur *= __builtin_ldexp(r[j], 1023 - top);
+        }
       if (last) {
         // The scale of a unary message cancels in everything downstream (only its normalised form is ever stored, by
-        // unary_writeback_kernel), so the raw columns are multiplied and the PRODUCT is normalised once.  A column
+        // unary_writeback_kernel), so the rescaled columns are multiplied and the PRODUCT is normalised once.  A column
         // Message.renormalize would replace by the uniform vector (total <= 0, LBP.py:655-657) zeroes the product, and an entry
         // that is negative, not finite or huge shows in the high words: either sends the graph to the exact kernel, decided once
         // per product.
@@ -1394,6 +1405,12 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
     const int st0 = has0 ? 128 : 0, of0 = has0 ? 64 : 0, st1 = has1 ? 128 : 0, of1 = has1 ? 64 : 0;
     double2 r0a, r0b, r1a, r1b;
     double scale = 1.0;
+    // WIDE: sixteen bits per source, floor(log2) of its total + 1023 (1023: nothing to undo).  A product of three or more tiles
+    // that each carry their table's magnitude, and the product of their totals' reciprocals, leave the range long before any
+    // single tile does: every source enters the product scaled by the power of two of its own total, and its reciprocal
+    // scaled back (exact both ways: the product has the bits it had, at unit magnitude throughout)
+    unsigned long long ex_lo = 0x03FF03FF03FF03FFull, ex_hi = 0x03FF03FF03FF03FFull;
+    auto source_shift = [&](int q) { return 1023 - (int)(((q < 4 ? ex_lo : ex_hi) >> (16 * (q & 3))) & 0xFFFFu); };
     if (!WIDE) {
       // all first reads of the member at once: the sources' partial totals and their first quarter.  The scale of the
       // product cancels downstream (every stored message is normalised by its own total); the reciprocals only keep the
@@ -1414,7 +1431,10 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
           const double* tp = tot + tl * 64 + gl * 4;
           const double total = (tp[0] + tp[1]) + (tp[2] + tp[3]);
           bad |= !total_ok(total);
-          scale *= __builtin_amdgcn_rcp(total);
+          const int e = total_exponent(total);
+          scale *= __builtin_ldexp(__builtin_amdgcn_rcp(total), e);
+          const unsigned long long field = (unsigned long long)(unsigned)((e + 1023) ^ 1023) << (16 * (q & 3));
+          if (q < 4) ex_lo ^= field; else ex_hi ^= field;
         }
       }
     }
@@ -1435,14 +1455,17 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
       } else {
         {
           const double2 v0 = src0[st0 * h], v1 = src0[st0 * h + of0];
-          b[0] = v0.x * scale; b[1] = v0.y * scale; b[2] = v1.x * scale; b[3] = v1.y * scale;
+          const int sh = source_shift(0);
+          b[0] = __builtin_ldexp(v0.x, sh) * scale; b[1] = __builtin_ldexp(v0.y, sh) * scale;
+          b[2] = __builtin_ldexp(v1.x, sh) * scale; b[3] = __builtin_ldexp(v1.y, sh) * scale;
         }
 #pragma unroll 1
         for (int q = 1; q < nsrc; ++q) {
           const int tl = ((q < 4 ? w3 : w4) >> (8 * (q & 3))) & 0xFF;
           const double2* sq = reinterpret_cast<const double2*>(TP(tl)) + lane + 128 * h;
           const double2 u0 = sq[0], u1 = sq[64];
-          b[0] *= u0.x; b[1] *= u0.y; b[2] *= u1.x; b[3] *= u1.y;
+          const int sh = source_shift(q);
+          b[0] *= __builtin_ldexp(u0.x, sh); b[1] *= __builtin_ldexp(u0.y, sh); b[2] *= __builtin_ldexp(u1.x, sh); b[3] *= __builtin_ldexp(u1.y, sh);
         }
       }
       if (want) {                                                // the message itself is wanted: its total, and this wave's quarter
@@ -1472,13 +1495,16 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
         double kq[4];                                            // this wave's quarter is formed once more now that the total is known
         {
           const double2 v0 = src0[st0 * rb], v1 = src0[st0 * rb + of0];
-          kq[0] = v0.x * scale; kq[1] = v0.y * scale; kq[2] = v1.x * scale; kq[3] = v1.y * scale;
+          const int sh = source_shift(0);
+          kq[0] = __builtin_ldexp(v0.x, sh) * scale; kq[1] = __builtin_ldexp(v0.y, sh) * scale;
+          kq[2] = __builtin_ldexp(v1.x, sh) * scale; kq[3] = __builtin_ldexp(v1.y, sh) * scale;
         }
 #pragma unroll 1
         for (int q = 1; q < nsrc; ++q) {
           const double2* sq = reinterpret_cast<const double2*>(TP(((q < 4 ? w3 : w4) >> (8 * (q & 3))) & 0xFF)) + lane + 128 * rb;
           const double2 v0 = sq[0], v1 = sq[64];
-          kq[0] *= v0.x; kq[1] *= v0.y; kq[2] *= v1.x; kq[3] *= v1.y;
+          const int sh = source_shift(q);
+          kq[0] *= __builtin_ldexp(v0.x, sh); kq[1] *= __builtin_ldexp(v0.y, sh); kq[2] *= __builtin_ldexp(v1.x, sh); kq[3] *= __builtin_ldexp(v1.y, sh);
         }
         const int gcv = g0 + gl;
         double* out = d.msgs + ((size_t)gcv * d.n_msgs + ((w1 >> 16) & 0xFFFF)) * 64 + 16 * rb + cq;
@@ -1599,9 +1625,16 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
     double2 q0 = src[0], q1 = src[64], r0 = src2[0], r1 = src2[of2];
     double4_t acc = {0.0, 0.0, 0.0, 0.0};
     double part = 0.0;
+    // The stored tiles carry their tables' magnitude, the product of two of them its square, and the contraction a third factor
+    // of it: the inputs' totals give the power of two that takes the product back to unit magnitude BEFORE the matrix cores see
+    // it (exact, and undone in `sc` below: no bit of a result changes, and tables near 2^-400 no longer run the accumulators
+    // into the subnormals)
+    const double t0 = (ta.x + ta.y) + (tb.x + tb.y), t1 = (tc.x + tc.y) + (td.x + td.y);
+    const int ex = total_exponent(t0) + total_exponent(t1);
 #pragma unroll
     for (int h = 0; h < 4; ++h) {
-      const double b0 = q0.x * r0.x, b1 = q0.y * r0.y, b2 = q1.x * r1.x, b3 = q1.y * r1.y;
+      const double b0 = __builtin_ldexp(q0.x * r0.x, -ex), b1 = __builtin_ldexp(q0.y * r0.y, -ex), b2 = __builtin_ldexp(q1.x * r1.x, -ex),
+                   b3 = __builtin_ldexp(q1.y * r1.y, -ex);
       __builtin_amdgcn_sched_barrier(0);
       if (h < 3) {                                               // the next quarter's reads go out ahead of this quarter's MFMAs
         q0 = src[128 * (h + 1)]; q1 = src[128 * (h + 1) + 64];
@@ -1628,7 +1661,6 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
 #undef MLBP_P3_QUARTER
       }
     }
-    const double t0 = (ta.x + ta.y) + (tb.x + tb.y), t1 = (tc.x + tc.y) + (td.x + td.y);
     bad |= (int)!total_ok(t0) | (int)!total_ok(t1);
     if (want) {
       const double tprod = column_sum(part);
@@ -1639,14 +1671,15 @@ __device__ __forceinline__ void sweep_x64_shared_body(Dev& d, const int wg) {
         const double2 v0 = src[128 * rb], v1 = src[128 * rb + 64], u0 = src2[st2 * rb], u1 = src2[st2 * rb + of2];
         double* out = d.msgs + ((size_t)(g0 + gl) * d.n_msgs + ((w1 >> 16) & 0xFFFF)) * 64 + 16 * rb + cq;
         const double it = 1.0 / tprod;
-        out[0] = (v0.x * u0.x) * it; out[4] = (v0.y * u0.y) * it; out[8] = (v1.x * u1.x) * it; out[12] = (v1.y * u1.y) * it;
+        out[0] = __builtin_ldexp(v0.x * u0.x, -ex) * it; out[4] = __builtin_ldexp(v0.y * u0.y, -ex) * it;
+        out[8] = __builtin_ldexp(v1.x * u1.x, -ex) * it; out[12] = __builtin_ldexp(v1.y * u1.y, -ex) * it;
       }
     }
     if (!mm) return;
     const int dst = w1 & 0xFF;
     if (flags & 64) {
       // (any positive per-graph scale cancels downstream; 1 / (the inputs' totals) keeps the magnitudes where they are)
-      const double sc = __builtin_amdgcn_rcp(t0) * __builtin_amdgcn_rcp(t1);
+      const double sc = __builtin_ldexp(__builtin_amdgcn_rcp(t0) * __builtin_amdgcn_rcp(t1), ex);
       const double p0 = acc.x * (c0.x * sc), p1 = acc.y * (c0.y * sc), p2 = acc.z * (c1.x * sc), p3 = acc.w * (c1.y * sc);
       double2* out = reinterpret_cast<double2*>(tiles + (size_t)dst * TILE) + 128 * rb + lane;
       out[0] = make_double2(p0, p1); out[64] = make_double2(p2, p3);

@@ -544,15 +544,28 @@ def test_tidir_trainer_groups_with_larger_cliques_share_the_launch(tmp_path):
     ha, hb = a.train(epochs=3, reg_param=0.2), b.train(epochs=3, reg_param=0.2)       # (three epochs: replayed from a HIP graph)
     np.testing.assert_allclose(ha, hb, rtol=1e-9)
     np.testing.assert_allclose(a.theta_en_de.cpu().numpy(), b.theta_en_de.cpu().numpy(), rtol=1e-8, atol=1e-12)
-    # theta far out: constant products past 1e280 -- the matrix-core kernels flag such graphs, the exact kernel redoes them, and
-    # the K4 ones get their gradient from the per-graph kernel (grouped: ONE launch over every group's flagged graphs, sixteen
-    # graphs of a group per block).  Finite, and the same statistics either way (the replayed graphs read theta from the device).
-    for t in (a, b):         # (the bias plane of the en_en features: every en_en entry e^200, four given words' unary factors overflow a product)
+    def redone_by_shape():
+        redone = {tr.topo.P: 0 for tr in a._full.trainers.values()}
+        for tr in a._full.trainers.values():
+            redone[tr.topo.P] += tr.batch.program(tr.roots[:tr.n_sweeps_run]).exact_count(tr.batch.B)
+        return redone
+    # theta out: every en_en entry e^200 (the bias plane of the en_en features), so four given words' unary factors multiply past
+    # 1e280.  The prepare launch carries each column's power of two, so the matrix-core kernels KEEP these graphs (such a product
+    # used to flag them): nothing is redone, finite, and the same statistics either way.
+    for t in (a, b):
         t.theta_en_en.copy_(torch.tensor([0.3, -0.2, 200.0], dtype=torch.float64, device=t.theta_en_en.device))
+    sa1, sb1 = a.local_statistics().cpu().numpy(), b.local_statistics().cpu().numpy()
+    assert not any(redone_by_shape().values()), redone_by_shape()
+    assert np.isfinite(sa1).all()
+    np.testing.assert_allclose(sa1, sb1, rtol=1e-9, atol=1e-9)
+    # theta far out: every en_en entry e^650 = 1e282, unary entries past 1e280 -- the matrix-core kernels flag such graphs, the
+    # exact kernel redoes them, and the K4 ones get their gradient from the per-graph kernel (grouped: ONE launch over every
+    # group's flagged graphs, sixteen graphs of a group per block).  Finite, and the same statistics either way (the replayed
+    # graphs read theta from the device).
+    for t in (a, b):
+        t.theta_en_en.copy_(torch.tensor([0.3, -0.2, 650.0], dtype=torch.float64, device=t.theta_en_en.device))
     sa2, sb2 = a.local_statistics().cpu().numpy(), b.local_statistics().cpu().numpy()
-    redone = {tr.topo.P: 0 for tr in a._full.trainers.values()}
-    for tr in a._full.trainers.values():
-        redone[tr.topo.P] += tr.batch.program(tr.roots[:tr.n_sweeps_run]).exact_count(tr.batch.B)
+    redone = redone_by_shape()
     assert redone[6] > 0, redone
     assert np.isfinite(sa2).all()
     np.testing.assert_allclose(sa2, sb2, rtol=1e-9, atol=1e-9)
