@@ -148,6 +148,28 @@ int mlbp_program_plan(const int32_t* ops, int32_t n_ops, const int32_t* srcs, in
                       const int32_t* sweeps, int32_t n_sweeps, int32_t n_msgs, int32_t P, int32_t U,
                       int32_t* out8);
 
+/* HOST only (no device needed): the integer images the program compilers make of an op list -- every word a launcher or an
+ * X = 64 kernel reads -- as one flat int32 serialisation selected by `which`.  A scalar is one word; a vector is its length,
+ * then its words; a list of vectors is each vector in turn (their number is a scalar given earlier).
+ *   MLBP_IMAGE_FUSED          fops, psrcs, fsweeps, hoist, cpw, pairseq, written, n_cprod, has_unary_fops
+ *   MLBP_IMAGE_LEAN           ok, n_bundles, HL, n_cprod, WL, image, hoisted, the constant products' slot lists
+ *   MLBP_IMAGE_SHARED         ok; when 0, the length of the reason and nothing else; else n_ops, n_live, n_cpw, n_back, n_fill,
+ *                             n_init, n_bundles, off_ent, off_back, off_fill, off_init, off_ptile, off_written, max_sources, pf_ok,
+ *                             off_pfb, off_stash, off_pinit, n_stash, n_pinit, off_vftile, vf_direct, p3_ok, n_lds, sqrt_mask,
+ *                             off_map3, off_kind3, off_back3, then sweeps, image, live_of_slot, hoisted, written, the constant
+ *                             products' slot lists
+ *   MLBP_IMAGE_LEAN_READOUT   success flag, the lean kernel's read-out image      (need n_vars, in_off, in_slots as
+ *   MLBP_IMAGE_SHARED_READOUT success flag, the shared-table read-out image        mlbp_program_set_readout takes them)
+ *   MLBP_IMAGE_PRUNED         the op list and sweep table MLBP_SWEEP_SKIP_UNCHANGED runs, the number of updates dropped
+ * n_vars = 0 and NULL in_off / in_slots are fine for the images that need no read-out.  Returns the word count and writes
+ * min(count, cap) words to out; same validation and error codes as mlbp_program_plan. */
+enum { MLBP_IMAGE_FUSED = 0, MLBP_IMAGE_LEAN = 1, MLBP_IMAGE_SHARED = 2, MLBP_IMAGE_LEAN_READOUT = 3,
+       MLBP_IMAGE_SHARED_READOUT = 4, MLBP_IMAGE_PRUNED = 5 };
+int mlbp_program_image(const int32_t* ops, int32_t n_ops, const int32_t* srcs, int32_t n_srcs,
+                       const int32_t* sweeps, int32_t n_sweeps, int32_t n_msgs, int32_t P, int32_t U,
+                       int32_t n_vars, const int32_t* in_off, const int32_t* in_slots,
+                       int32_t which, int32_t* out, int32_t cap);
+
 /* Attaches the variable read-out tables to a program so that mlbp_sweep_f64 can write the
  * variable marginals straight from the on-chip messages (mlbp_sweep_args.marginals): in_off
  * [n_vars+1] / in_slots are HOST arrays, variable v multiplies the messages in slots

@@ -11,6 +11,7 @@ LIB_PATH = os.path.join(_PKG, 'libmlbp.so')
 
 MLBP_OK, MLBP_EINVAL, MLBP_EHIP, MLBP_ENODEVICE, MLBP_ENOMEM, MLBP_EUNSUPPORTED = 0, -1, -2, -3, -4, -5
 OP_UNARY, OP_PAIR_TM, OP_PAIR_MT, OP_VAR = 0, 1, 2, 3
+IMAGES = ('fused', 'lean', 'shared', 'lean_readout', 'shared_readout', 'pruned')      # MLBP_IMAGE_*: mlbp_program_image's `which`, in order
 NORM_ZERO, NORM_UNIFORM = 0, 1
 
 
@@ -93,6 +94,7 @@ SIGNATURES = {
                                       C.POINTER(_vp)]),
     'mlbp_program_destroy': (C.c_int, [_vp]),
     'mlbp_program_plan': (C.c_int, [_i32p, _i32, _i32p, _i32, _i32p, _i32, _i32, _i32, _i32, _i32p]),
+    'mlbp_program_image': (C.c_int, [_i32p, _i32, _i32p, _i32, _i32p, _i32, _i32, _i32, _i32, _i32, _i32p, _i32p, _i32, _i32p, _i32]),
     'mlbp_program_reserve': (C.c_int, [_vp, _i32]),
     'mlbp_program_set_readout': (C.c_int, [_vp, _i32, _i32p, _i32p]),
     'mlbp_program_exact_count': (C.c_int, [_vp, _i32]),

@@ -1,5 +1,5 @@
-// Internal declarations shared by the host (mlbp_host.cpp) and device (mlbp_*.hip) translation
-// units of libmlbp.so.  Not part of the ABI.
+// Internal declarations shared by the host (mlbp_host.cpp, mlbp_compile*.cpp) and device (mlbp_*.hip) translation
+// units of libmlbp.so.  Not part of the ABI.  Includes no device header itself: the host-only units compile without one.
 #ifndef MLBP_INTERNAL_H
 #define MLBP_INTERNAL_H
 
@@ -40,7 +40,17 @@ void launch_log_record(const void* kernel);
     hipLaunchKernelGGL(kernel, __VA_ARGS__);                                               \
   } while (0)
 
-// Fused program form of the X = 64 kernels (build_fused_program in mlbp_sweep.hip): 8-word op headers.
+// The program compilers (mlbp_compile.cpp, mlbp_compile_shared.cpp): pure host code.  mlbp_program_create runs the chain
+// validate_program -> build_fused_program -> build_shared_program / build_lean_program (and drop_unchanged_updates for the
+// pruned twin); mlbp_program_plan and mlbp_program_image run the same chain without a device.
+int validate_program(const int32_t* ops, int32_t n_ops, const int32_t* srcs, int32_t n_srcs, const int32_t* sweeps,
+                     int32_t n_sweeps, int32_t n_msgs, int32_t P, int32_t U, int* max_srcs_out);
+int drop_unchanged_updates(const int32_t* ops, const int32_t* srcs, const int32_t* sweeps, int n_sweeps, int n_msgs,
+                           std::vector<int32_t>& ops_out, std::vector<int32_t>& sweeps_out);
+// Index of the constant product whose hoisted message slots are exactly `consts`, or -1.
+int find_cprod(const std::vector<std::vector<int32_t>>& cprods, const std::vector<int32_t>& consts);
+
+// Fused program form of the X = 64 kernels (build_fused_program): 8-word op headers.
 enum { FOP_UNARY = 0, FOP_PAIR_TM = 1, FOP_PAIR_MT = 2, FOP_VAR = 3, FOP_VAR_PAIR_TM = 4, FOP_VAR_PAIR_MT = 5,
        FOP_BUNDLED = 0x100 /* flag: the next update touches disjoint slots and may share this one's barrier */ };
 struct FusedProgram {
@@ -48,8 +58,21 @@ struct FusedProgram {
   int n_cprod = 0;
   bool has_unary_fops = false;
 };
+void build_fused_program(const int32_t* ops, const int32_t* srcs, const int32_t* sweeps, int n_sweeps, int n_msgs, FusedProgram& out);
 
 // Micro-op form of the lean X = 64 kernel (mlbp_lean.hip): operands are LDS byte offsets.
+// micro-op word 0
+constexpr int UOP_VAR = 1;          // bit 0: variable product only (stored, no contraction)
+constexpr int UOP_MT = 2;           // bit 1: out = m^T . T (else T . m)
+constexpr int UOP_PSLOT_SHIFT = 2;  // bits 2-4: pair slot (register-resident table; 0..7)
+constexpr int UOP_NOP = 32;         // bit 5: empty second slot of a bundle
+constexpr int UOP_STORE_VF = 64;    // bit 6: the variable->factor message is stored (word 5)
+constexpr int UOP_NSRC_SHIFT = 8;   // bits 8-11: number of sources (1..4)
+constexpr int UOP_CARRY_IN = 0x1000;   // a link of a long variable product: starts from the running product in registers
+constexpr int UOP_CARRY_OUT = 0x2000;  // ... and hands it on instead of storing it
+// micro-op words: 0 flags | 1-4 source byte offsets | 5 byte offset of the variable->factor message to store, or -1 |
+// 6 destination byte offset | 7 unused.  Source words past the count hold the all-ones ext slot.
+// A bundle = two micro-ops = 16 words = one s_load_dwordx16.
 struct LeanProgram {
   bool ok = false;
   const char* why = "";
@@ -81,11 +104,13 @@ struct SharedProgram {
   bool pf_ok = false;
   int off_pfb = 0, off_stash = 0, off_pinit = 0, n_stash = 0, n_pinit = 0, off_vftile = 0;
   bool vf_direct = false;             // the gradient epilogue may read the final variable->factor messages from the message tiles
-  // ... its three-source variant (K4 cliques: messages stored as sqrt(c) (.) m, constant products in memory; build_shared_program)
+  // ... its three-source variant (K4 cliques: messages stored as sqrt(c) (.) m, constant products in memory; mlbp_compile_shared.cpp)
   bool p3_ok = false;
   int n_lds = 0, sqrt_mask = 0, off_map3 = 0, off_kind3 = 0, off_back3 = 0;
   std::vector<int32_t> sweeps;         // {first op, count} of the transformed op list (one sequence: sweep boundaries mean nothing here)
-  std::vector<int32_t> image;          // bundles [n_bundles + 1][2][16] | cprod entries [n_cpw] | write-back pairs [n_back][2] | fill slots [n_fill] | uniform tiles [n_init]
+  // bundles [n_bundles + 1][2][4] | cprod entries [n_cpw] | write-back pairs [n_back][2] | fill slots [n_fill] | uniform tiles [n_init] |
+  // product tiles [n_cprod] | written bits | 16 zeros | the sections of the product-fused form in use (mlbp_compile_shared.cpp) | 16 zeros
+  std::vector<int32_t> image;
   std::vector<int32_t> live_of_slot;   // [n_msgs + 1 + n_cprod] LDS tile of a slot (ext slots included) or -1
   std::vector<int32_t> hoisted;        // [n_msgs] unary factor whose constant message the slot holds, or -1
   std::vector<char> written;           // [n_msgs] some update of the program writes the slot
@@ -158,7 +183,7 @@ struct mlbp_program {
   int32_t* d_sweeps;      // [n_sweeps][2]
   int32_t* d_pairseq;     // [n_pairseq + 1] pair slot of the k-th executed pair op (-1 terminated)
   int32_t* d_status;      // [1] set non-zero by a kernel that met an out-of-range table index
-  // fused form used by the X = 64 kernel (build_fused_program in mlbp_sweep.hip)
+  // fused form used by the X = 64 kernel (build_fused_program)
   int32_t n_fops, n_hoist, n_psrcs, n_cprod, n_cpw, n_written;
   bool sf_ok;             // the scale-free kernel applies (no in-loop unary ops)
   unsigned char* d_bail;  // [bail_cap] per-graph "redo with the exact kernel" flags

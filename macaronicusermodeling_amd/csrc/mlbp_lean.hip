@@ -39,19 +39,10 @@ constexpr int WG = 256;
 typedef double nt_d2 __attribute__((ext_vector_type(2)));
 #define NT_LOAD2(p) ([&] { const nt_d2 v_ = __builtin_nontemporal_load(reinterpret_cast<const nt_d2*>(p)); return make_double2(v_.x, v_.y); }())
 
-// micro-op word 0
-constexpr int UOP_VAR = 1;          // bit 0: variable product only (stored, no contraction)
-constexpr int UOP_MT = 2;           // bit 1: out = m^T . T (else T . m)
-constexpr int UOP_PSLOT_SHIFT = 2;  // bits 2-4: pair slot (register-resident table; 0..7)
-constexpr int UOP_NOP = 32;         // bit 5: empty second slot of a bundle
-constexpr int UOP_STORE_VF = 64;    // bit 6: the variable->factor message is stored (word 5)
-constexpr int UOP_NSRC_SHIFT = 8;   // bits 8-11: number of sources (1..4)
-constexpr int UOP_CARRY_IN = 0x1000;   // a link of a long variable product: starts from the running product in registers
-constexpr int UOP_CARRY_OUT = 0x2000;  // ... and hands it on instead of storing it
 constexpr int GROUP_WORDS = 48;     // one group descriptor of a MULTI launch (see launch_lean_groups)
-// micro-op words: 0 flags | 1-4 source byte offsets | 5 byte offset of the variable->factor message to store, or -1 |
-// 6 destination byte offset | 7 unused.  Source words past the count hold the all-ones ext slot.
-// A bundle = two micro-ops = 16 words = one s_load_dwordx16.
+// (micro-op words and the UOP_* bits of word 0: mlbp_internal.h, shared with build_lean_program in mlbp_compile.cpp)
+using mlbp::UOP_VAR; using mlbp::UOP_MT; using mlbp::UOP_PSLOT_SHIFT; using mlbp::UOP_NOP; using mlbp::UOP_STORE_VF;
+using mlbp::UOP_NSRC_SHIFT; using mlbp::UOP_CARRY_IN; using mlbp::UOP_CARRY_OUT;
 
 struct LeanDev {
   const int32_t* image;   // bundles [n_bundles][16] | hoist [4][HL][2] | cprod lists [n_cprod][16] | written [4][WL] | pad
@@ -858,163 +849,6 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
 }  // namespace
 
 namespace mlbp {
-
-// FusedProgram -> micro-ops.  Every operand becomes an LDS byte offset (slot * 512); a variable product with more
-// than four sources is split into a chain of variable-only micro-ops ("links") that hand the running product on in a
-// register (UOP_CARRY_OUT / UOP_CARRY_IN); only the last link stores.
-// Image: bundles [n_bundles][16] | per-wave hoist lists [4][HL][2] | constant-product lists [n_cprod][16] |
-// per-wave written-slot lists [4][WL] | one bundle of padding (the loop prefetches one bundle past the end), zeros up to 2 KB.
-void build_lean_program(const FusedProgram& fp, int n_msgs, LeanProgram& out) {
-  out = LeanProgram();
-  if (fp.has_unary_fops) { out.why = "in-loop unary updates (not hoistable)"; return; }
-  std::vector<int32_t> U;                            // micro-ops, 8 words each
-  // every source list is padded to four entries with the all-ones ext slot: the kernel fetches sources 1-2, and 3-4 when
-  // there are more than two, without looking at the count in between
-  const int32_t ones = (n_msgs + 1 + fp.n_cprod) * 512;
-  std::vector<char> second;                          // micro-op i is the second member of a bundle
-  auto emit_var = [&](const int32_t* src, int n, int c) {      // work[c] = prod(src[0..n))
-    int done = 0;
-    do {
-      int32_t w[8] = {0, ones, ones, ones, ones, 0, 0, 0};
-      int k = 0;
-      const bool first = done == 0;
-      while (k < 4 && done < n) w[1 + k++] = src[done++] * 512;
-      w[0] = UOP_VAR | (k << UOP_NSRC_SHIFT) | (first ? 0 : UOP_CARRY_IN) | (done < n ? UOP_CARRY_OUT : 0);
-      w[5] = c * 512;
-      U.insert(U.end(), w, w + 8);
-      second.push_back(0);
-    } while (done < n);
-  };
-  const int n_fops = (int)fp.fops.size() / 8;
-  for (int i = 0; i < n_fops; ++i) {
-    const int32_t* w = &fp.fops[8 * (size_t)i];
-    const int kind = w[0] & 0xFF;
-    if (kind == FOP_VAR) { emit_var(&fp.psrcs[w[1]], w[2], w[3]); continue; }
-    // a bundle: pre-chains of both members first (they touch slots disjoint from the partner's), then the members
-    const int members = (w[0] & FOP_BUNDLED) ? 2 : 1;
-    for (int m = 0; m < members; ++m) {
-      const int32_t* q = &fp.fops[8 * (size_t)(i + m)];
-      const int kd = q[0] & 0xFF;
-      if ((kd == FOP_VAR_PAIR_TM || kd == FOP_VAR_PAIR_MT) && q[2] > 4) emit_var(&fp.psrcs[q[1]], q[2], q[3]);
-    }
-    for (int m = 0; m < members; ++m) {
-      const int32_t* q = &fp.fops[8 * (size_t)(i + m)];
-      const int kd = q[0] & 0xFF;
-      int32_t u[8] = {0, ones, ones, ones, ones, -1, 0, 0};
-      if (kd == FOP_PAIR_TM || kd == FOP_PAIR_MT) {
-        u[0] = (kd == FOP_PAIR_MT ? UOP_MT : 0) | (q[1] << UOP_PSLOT_SHIFT) | (1 << UOP_NSRC_SHIFT);
-        u[1] = q[2] * 512;
-        u[6] = q[3] * 512;
-      } else {
-        const bool chained = q[2] > 4;
-        const int n = chained ? 1 : q[2];
-        u[0] = (kd == FOP_VAR_PAIR_MT ? UOP_MT : 0) | (q[4] << UOP_PSLOT_SHIFT) | (n << UOP_NSRC_SHIFT);
-        if (chained) u[1] = q[3] * 512;
-        else for (int k = 0; k < n; ++k) u[1 + k] = fp.psrcs[q[1] + k] * 512;
-        u[5] = chained ? -1 : q[3] * 512;           // the variable->factor message itself (dropped below when dead)
-        u[6] = q[5] * 512;
-      }
-      U.insert(U.end(), u, u + 8);
-      second.push_back(m == 1);
-    }
-    i += members - 1;
-  }
-  const int n_uops = (int)U.size() / 8;
-  // a fused variable->factor message is stored only when something reads the slot before its next write, or when it
-  // is the slot's final value (the messages are an output of the call)
-  for (int i = 0; i < n_uops; ++i) {
-    int32_t* u = &U[8 * (size_t)i];
-    if ((u[0] & UOP_VAR) || u[5] < 0) continue;
-    const int c = u[5];
-    bool needed = true;
-    for (int j = i + 1; j < n_uops; ++j) {
-      const int32_t* v = &U[8 * (size_t)j];
-      const int n = (v[0] >> UOP_NSRC_SHIFT) & 15;
-      bool reads = false;
-      for (int k = 0; k < n; ++k) reads |= v[1 + k] == c;
-      if (reads) break;
-      const bool writes = v[5] == c || (!(v[0] & UOP_VAR) && v[6] == c);
-      if (writes) { needed = false; break; }
-    }
-    if (!needed) u[5] = -1;
-  }
-  for (int i = 0; i < n_uops; ++i) {
-    int32_t* u = &U[8 * (size_t)i];
-    if (!(u[0] & UOP_VAR) && u[5] >= 0) u[0] |= UOP_STORE_VF;
-    if (u[5] < 0) u[5] = 0;
-  }
-  std::vector<int32_t>& I = out.image;
-  const int32_t nop[8] = {UOP_NOP, 0, 0, 0, 0, -1, 0, 0};
-  for (int i = 0; i < n_uops; ++i) {
-    I.insert(I.end(), U.begin() + 8 * (size_t)i, U.begin() + 8 * (size_t)i + 8);
-    if (i + 1 < n_uops && second[i + 1]) { ++i; I.insert(I.end(), U.begin() + 8 * (size_t)i, U.begin() + 8 * (size_t)i + 8); }
-    else I.insert(I.end(), nop, nop + 8);
-  }
-  out.n_bundles = (int)I.size() / 16;
-  // per-wave hoist lists: entry h goes to wave h & 3
-  const int n_hoist = (int)fp.hoist.size() / 2;
-  out.HL = std::max(8, ((n_hoist + 3) / 4 + 7) / 8 * 8);
-  {
-    std::vector<int32_t> hl(4 * (size_t)out.HL * 2, -1);
-    for (int h = 0; h < n_hoist; ++h) {
-      hl[((size_t)(h & 3) * out.HL + (h >> 2)) * 2] = fp.hoist[2 * h];
-      hl[((size_t)(h & 3) * out.HL + (h >> 2)) * 2 + 1] = fp.hoist[2 * h + 1];
-    }
-    I.insert(I.end(), hl.begin(), hl.end());
-  }
-  // constant-product lists, 16 words each, padded with the all-ones ext slot
-  out.n_cprod = fp.n_cprod;
-  out.cprods.clear();
-  for (size_t at = 0; at < fp.cpw.size();) {
-    const int cnt = fp.cpw[at];
-    if (cnt > 15) { out.why = "a constant product of more than 15 messages"; out.image.clear(); return; }
-    int32_t l[16];
-    l[0] = cnt;
-    for (int q = 0; q < 15; ++q) l[1 + q] = q < cnt ? fp.cpw[at + 1 + q] : ones / 512;
-    I.insert(I.end(), l, l + 16);
-    out.cprods.push_back(std::vector<int32_t>(fp.cpw.begin() + at + 1, fp.cpw.begin() + at + 1 + cnt));
-    at += 1 + cnt;
-  }
-  out.hoisted.assign(n_msgs, 0);
-  for (int h = 0; h < n_hoist; ++h) out.hoisted[fp.hoist[2 * h + 1]] = 1;
-  // per-wave written-slot lists
-  const int n_written = (int)fp.written.size();
-  out.WL = std::max(4, ((n_written + 3) / 4 + 3) / 4 * 4);
-  {
-    std::vector<int32_t> wl(4 * (size_t)out.WL, -1);
-    for (int i = 0; i < n_written; ++i) wl[(size_t)(i & 3) * out.WL + (i >> 2)] = fp.written[i];
-    I.insert(I.end(), wl.begin(), wl.end());
-  }
-  for (int q = 0; q < 16; ++q) I.push_back(q == 0 || q == 8 ? UOP_NOP : 0);
-  if (I.size() < 512) I.resize(512, 0);              // 2 KB at least: where the kernel's loads with nothing to fetch point (a table's 4 x 4 block spans 1.8 KB)
-  out.ok = true;
-}
-
-// Read-out lists of the lean kernel: per variable 16 words -- count (base included), base slot (the variable's constant
-// product, or the uniform vector), then the varying incoming slots.  False when a variable has more than 15 entries.
-bool build_lean_readout(const LeanProgram& lp, int n_msgs, int n_vars, const int32_t* in_off, const int32_t* in_slots,
-                        std::vector<int32_t>& image) {
-  image.assign(16 * (size_t)n_vars, n_msgs);
-  for (int v = 0; v < n_vars; ++v) {
-    std::vector<int32_t> consts, vars;
-    for (int q = in_off[v]; q < in_off[v + 1]; ++q) (lp.hoisted[in_slots[q]] ? consts : vars).push_back(in_slots[q]);
-    int base = n_msgs;                               // the uniform vector
-    if (!consts.empty()) {
-      size_t k = 0;
-      for (; k < lp.cprods.size(); ++k)
-        if (lp.cprods[k] == consts) break;
-      if (k < lp.cprods.size()) base = n_msgs + 1 + (int)k;
-      else { vars.insert(vars.begin(), consts.begin(), consts.end()); }      // no matching product: multiply them in
-    }
-    if (vars.size() > 14) return false;
-    int32_t* l = &image[16 * (size_t)v];
-    l[0] = 1 + (int)vars.size();
-    l[1] = base;
-    const int ones = n_msgs + 1 + lp.n_cprod;
-    for (int q = 0; q < 14; ++q) l[2 + q] = q < (int)vars.size() ? vars[q] : ones;
-  }
-  return true;
-}
 
 // Does the lean kernel apply to this (program, arguments) pair?  Fills the device-side descriptions when it does.
 // grad: the call's gradient is fused into the launch (the caller has checked that it can be); a gradient request without

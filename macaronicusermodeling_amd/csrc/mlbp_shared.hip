@@ -22,14 +22,13 @@
 // Degenerate graphs (zero / non-finite totals, where Message.renormalize and nan_to_num take their
 // special branches) are flagged per graph and redone by the exact kernel, like the scale-free path.
 // Where every variable has at most two pairwise factors (K2, K3, chains, rings) the kernel runs its PRODUCT-FUSED
-// form (template parameter PF; build_shared_program, "product-fused form"): the producer of a message stores
+// form (template parameter PF; mlbp_compile_shared.cpp, "product-fused form"): the producer of a message stores
 // c (.) message, a contraction reads one tile straight into the matrix cores, read-out and gradient from LDS.
 //
 // Flops per pairwise update per graph: 2 * 64 * 64 = 8192 (shared-table mode).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
@@ -40,560 +39,13 @@
 
 namespace mlbp {
 
-// ------------------------------------------------------------------------------------------------
-// host: live-tile form of the fused program
-// ------------------------------------------------------------------------------------------------
-void build_shared_program(const FusedProgram& fp, int n_msgs, int P, int U, SharedProgram& out) {
-  out = SharedProgram();
-  const int n_hoist = (int)fp.hoist.size() / 2;
-  out.why = "unary messages are not all constant, or no / too many pairwise factors";
-  if (fp.has_unary_fops || n_hoist != U || P < 1 || P > 16 || U > 64) return;
-  const int n_all = n_msgs + 1 + fp.n_cprod;
-  out.hoisted.assign(n_msgs, -1);
-  for (int h = 0; h < n_hoist; ++h) out.hoisted[fp.hoist[2 * h + 1]] = fp.hoist[2 * h];
-  out.why = "a unary message is folded into no variable update";
-  {
-    std::vector<char> in_list(n_msgs, 0);
-    size_t at = 0;
-    for (int k = 0; k < fp.n_cprod; ++k) {
-      const int cnt = fp.cpw[at];
-      out.cprods.emplace_back(fp.cpw.begin() + at + 1, fp.cpw.begin() + at + 1 + cnt);
-      for (int c : out.cprods.back()) {
-        if (c < 0 || c >= n_msgs || out.hoisted[c] < 0) return;
-        in_list[c] = 1;
-      }
-      at += 1 + cnt;
-    }
-    for (int c = 0; c < n_msgs; ++c)
-      if (out.hoisted[c] >= 0 && !in_list[c]) return;     // a unary message no variable update folds in
-  }
-  // Sweep boundaries mean nothing to this kernel (it runs the updates in order), so the whole call is one
-  // sequence.  Two rewrites keep the variable->factor messages out of LDS:
-  //   1. a pairwise update whose input message c was produced by a variable->factor update whose own inputs
-  //      have not changed since RECOMPUTES c in registers (fused pair) instead of reading a stored tile --
-  //      the up pass of a loopy schedule (LBP.py:227-233) emits "X7->F17, X4->F14, F17->X1, F14->X1", and the
-  //      sweep that follows may read X4->F14 once more;
-  //   2. a lone variable->factor update whose output is rewritten later and not read before that is dropped.
-  // Both leave every stored value exactly what the original order computes.
-  std::vector<int32_t> fops;                                   // transformed op list, 8 words each
-  {
-    std::vector<std::vector<int32_t>> seq;
-    for (size_t sw = 0; sw + 1 < fp.fsweeps.size(); sw += 2)
-      for (int i = fp.fsweeps[sw]; i < fp.fsweeps[sw] + fp.fsweeps[sw + 1]; ++i) {
-        seq.emplace_back(fp.fops.begin() + 8 * (size_t)i, fp.fops.begin() + 8 * (size_t)i + 8);
-        seq.back()[0] &= 0xFF;
-      }
-    auto is_pair = [](const std::vector<int32_t>& w) { return w[0] == FOP_PAIR_TM || w[0] == FOP_PAIR_MT; };
-    auto writes = [&](const std::vector<int32_t>& w, int slot) {
-      if (is_pair(w) || w[0] == FOP_VAR) return w[3] == slot;
-      return w[3] == slot || w[5] == slot;
-    };
-    for (size_t j = 0; j < seq.size(); ++j) {
-      if (!is_pair(seq[j])) continue;
-      const int c = seq[j][2];
-      int i = (int)j - 1;
-      while (i >= 0 && !writes(seq[i], c)) --i;
-      if (i < 0 || is_pair(seq[i]) || seq[i][3] != c) continue;               // never written, or not by a variable update
-      const std::vector<int32_t> v = seq[i];
-      bool legal = true;
-      for (size_t k = i + 1; k < j && legal; ++k) {
-        for (int q = 0; q < v[2] && legal; ++q) if (writes(seq[k], fp.psrcs[v[1] + q])) legal = false;
-        for (int q = 0; q < v[7] && legal; ++q) if (writes(seq[k], fp.psrcs[v[6] + q])) legal = false;
-      }
-      if (!legal) continue;
-      const std::vector<int32_t> pr = seq[j];
-      seq[j] = {pr[0] == FOP_PAIR_TM ? FOP_VAR_PAIR_TM : FOP_VAR_PAIR_MT, v[1], v[2], c, pr[1], pr[3], v[6], v[7]};
-    }
-    for (size_t i = 0; i < seq.size();) {
-      if (seq[i][0] != FOP_VAR) { ++i; continue; }
-      const int c = seq[i][3];
-      bool dead = false;
-      for (size_t k = i + 1; k < seq.size(); ++k) {
-        if (is_pair(seq[k]) && seq[k][2] == c) break;                          // still read from its tile
-        if (writes(seq[k], c)) { dead = true; break; }
-      }
-      if (dead) seq.erase(seq.begin() + i);
-      else ++i;
-    }
-    out.sweeps.push_back(0);
-    out.sweeps.push_back((int)seq.size());
-    for (auto& w : seq) fops.insert(fops.end(), w.begin(), w.end());
-  }
-  const int n_ops = (int)fops.size() / 8;
-  out.why = "unsupported update kind or slot use";
-  std::vector<char> live(n_all, 0), written(n_msgs, 0);
-  for (int i = 0; i < n_ops; ++i) {
-    const int32_t* w = &fops[8 * i];
-    const int kind = w[0] & 0xFF;
-    if (kind == FOP_PAIR_TM || kind == FOP_PAIR_MT) {
-      if (written[w[2]]) live[w[2]] = 1;        // else: still the initial uniform message, no tile needed
-      else fops[8 * i + 2] = -1;
-      live[w[3]] = 1; written[w[3]] = 1;
-    } else if (kind == FOP_VAR || kind == FOP_VAR_PAIR_TM || kind == FOP_VAR_PAIR_MT) {
-      for (int q = 0; q < w[2]; ++q) live[fp.psrcs[w[1] + q]] = 1;
-      written[w[3]] = 1;
-      if (kind != FOP_VAR) { live[w[5]] = 1; written[w[5]] = 1; }
-    } else {
-      return;
-    }
-  }
-  for (int c = 0; c < n_msgs; ++c)
-    if (out.hoisted[c] >= 0 && (live[c] || written[c])) return;
-  out.written = written;
-  // tile numbering: constant products and factor->variable messages first, stored variable->factor messages
-  // (each read once, by a later pairwise update) last -- when LDS cannot hold every tile the tail lives in
-  // global memory (launcher: n_res resident tiles)
-  out.live_of_slot.assign(n_all, -1);
-  {
-    std::vector<char> is_vf(n_all, 0);
-    for (int i = 0; i < n_ops; ++i)
-      if ((fops[8 * i] & 0xFF) >= FOP_VAR) is_vf[fops[8 * i + 3]] = 1;
-    for (int pass = 0; pass < 2; ++pass)
-      for (int s = 0; s < n_all; ++s)
-        if (live[s] && (is_vf[s] ? 1 : 0) == pass) out.live_of_slot[s] = out.n_live++;
-  }
-  // Members: one record per update, MW words --
-  //   [0] flags: 1 contraction, 2 m^T.T (else T.m), 4 the variable->factor product is kept as tile [3], 8 it is this
-  //       slot's last value and goes straight to memory (message slot [4]), 16 variable update only; bits 8-11 = number of
-  //       source tiles   [1] pair slot   [2] destination tile   [3] product tile or -1   [4] message slot of the product
-  //   [8..15] source tiles (the first one -1: a message nothing has updated yet, i.e. the uniform vector)
-  // (packed into 8 words for the device, pack_member below).
-  // Bundles: two members that touch disjoint tiles share one barrier; the kernel runs them on different halves of its
-  // eight waves when their (table, orientation) pairs live in different halves (it decides: the tables are device data).
-  constexpr int MW = 16;
-  std::vector<int32_t> mem((size_t)n_ops * MW, 0);
-  std::vector<int> last_var_write(n_msgs, -1);
-  std::vector<char> pair_kind(n_ops, 0);                        // a factor update that reads a STORED variable->factor message
-  out.why = "more than 254 live tiles or 65535 message slots";
-  if (out.n_live > 254 || n_msgs > 65535) return;
-  out.why = "a variable update multiplies more than 8 tiles";
-  for (int i = 0; i < n_ops; ++i) {
-    const int32_t* w = &fops[8 * i];
-    int32_t* m = &mem[(size_t)i * MW];
-    const int kind = w[0] & 0xFF;
-    for (int q = 0; q < 8; ++q) m[8 + q] = -1;
-    m[2] = m[3] = -1;
-    if (kind == FOP_PAIR_TM || kind == FOP_PAIR_MT) {
-      m[0] = 1 | (kind == FOP_PAIR_MT ? 2 : 0) | (1 << 8);
-      pair_kind[i] = 1;
-      m[1] = w[1]; m[2] = out.live_of_slot[w[3]];
-      m[8] = w[2] < 0 ? -1 : out.live_of_slot[w[2]];
-    } else {
-      if (w[2] > 8 || w[2] < 1) return;
-      out.max_sources = std::max(out.max_sources, (int)w[2]);
-      for (int q = 0; q < w[2]; ++q) m[8 + q] = out.live_of_slot[fp.psrcs[w[1] + q]];
-      m[0] = (w[2] << 8) | (kind == FOP_VAR ? 16 : (1 | (kind == FOP_VAR_PAIR_MT ? 2 : 0)));
-      m[3] = out.live_of_slot[w[3]]; m[4] = w[3];
-      if (m[3] >= 0) m[0] |= 4;
-      else last_var_write[w[3]] = i;
-      if (kind != FOP_VAR) { m[1] = w[4]; m[2] = out.live_of_slot[w[5]]; }
-    }
-  }
-  for (int c = 0; c < n_msgs; ++c)
-    if (last_var_write[c] >= 0) mem[(size_t)last_var_write[c] * MW] |= 8;        // write this v->f message out here
-  // tiles read before anything in the program has written them start as the uniform vector (FactorGraph.initialize)
-  std::vector<int32_t> init_tiles;
-  {
-    std::vector<char> have(out.n_live, 0);
-    for (int k = 0; k < fp.n_cprod; ++k) have[out.live_of_slot[n_msgs + 1 + k]] = 1;        // written by the prologue
-    for (int i = 0; i < n_ops; ++i) {
-      const int32_t* m = &mem[(size_t)i * MW];
-      const int n = (m[0] >> 8) & 15;
-      for (int q = 0; q < n; ++q)
-        if (m[8 + q] >= 0 && !have[m[8 + q]]) { have[m[8 + q]] = 1; init_tiles.push_back(m[8 + q]); }
-      if (m[2] >= 0) have[m[2]] = 1;
-      if (m[3] >= 0) have[m[3]] = 1;
-    }
-  }
-  std::vector<int32_t> bundles;
-  const int32_t nop[MW] = {0, 0, -1, -1, 0, 0, 0, 0, -1, -1, -1, -1, -1, -1, -1, -1};
-  // device form, 4 words: [0] flags | nsrc << 8 | pair slot << 16   [1] destination tile | product tile << 8 (0xFF = none) |
-  // message slot of the product << 16   [2] source tiles 0-3, [3] 4-7, one byte each (0xFF = none)
-  auto pack_member = [&](const int32_t* m) {
-    int32_t w[4] = {0, 0, 0, 0};
-    w[0] = m[0] | (m[1] << 16);
-    w[1] = (m[2] & 0xFF) | ((m[3] & 0xFF) << 8) | (m[4] << 16);
-    for (int q = 0; q < 8; ++q) w[2 + (q >> 2)] |= (m[8 + q] & 0xFF) << (8 * (q & 3));
-    bundles.insert(bundles.end(), w, w + 4);
-  };
-  auto disjoint = [&](const int32_t* x, const int32_t* y) {
-    // y reads nothing x writes, and writes nothing x reads or writes
-    auto writes = [](const int32_t* m, int tile) { return tile >= 0 && (m[2] == tile || m[3] == tile); };
-    for (int q = 0; q < 8; ++q) if (writes(x, y[8 + q]) || writes(y, x[8 + q])) return false;
-    return !(writes(x, y[2]) || writes(x, y[3]));
-  };
-  std::vector<int> pairing;                                      // per bundle: its members' indices (the second -1: alone)
-  for (int i = 0; i < n_ops;) {
-    const int32_t* x = &mem[(size_t)i * MW];
-    pack_member(x);
-    if (i + 1 < n_ops && disjoint(x, &mem[(size_t)(i + 1) * MW])) {
-      pack_member(&mem[(size_t)(i + 1) * MW]);
-      pairing.push_back(i); pairing.push_back(i + 1);
-      i += 2;
-    } else {
-      pack_member(nop);
-      pairing.push_back(i); pairing.push_back(-1);
-      i += 1;
-    }
-  }
-  out.n_bundles = (int)bundles.size() / 8;
-  if (getenv("MLBP_DEBUG_SHARED_PROGRAM")) {                     // diagnostic: the member records, one line each
-    for (int i = 0; i < n_ops; ++i) {
-      const int32_t* m = &mem[(size_t)i * MW];
-      fprintf(stderr, "member %2d: flags 0x%03x pair %d dst %d ptile %d pslot %d src", i, m[0], m[1], m[2], m[3], m[4]);
-      for (int q = 0; q < 8; ++q) if (m[8 + q] >= 0 || q == 0) fprintf(stderr, " %d", m[8 + q]);
-      fprintf(stderr, "\n");
-    }
-    fprintf(stderr, "n_live %d n_bundles %d n_cprod %d\n", out.n_live, out.n_bundles, fp.n_cprod);
-  }
-  pack_member(nop); pack_member(nop);                            // the kernel prefetches one bundle past the end
-  // constant products, flattened: {unary factor, message slot, tile, 1 = first | 2 = last of its product}
-  std::vector<int32_t> ent;
-  out.why = "unsupported update kind or slot use";
-  for (int k = 0; k < fp.n_cprod; ++k) {
-    const int tile = out.live_of_slot[n_msgs + 1 + k];
-    if (tile < 0 || out.cprods[k].empty()) return;
-    for (size_t q = 0; q < out.cprods[k].size(); ++q) {
-      const int c = out.cprods[k][q];
-      ent.insert(ent.end(), {out.hoisted[c], c, tile, (q == 0 ? 1 : 0) | (q + 1 == out.cprods[k].size() ? 2 : 0)});
-    }
-  }
-  std::vector<char> is_vf(n_msgs, 0);                          // slots some variable->factor update writes
-  for (int i = 0; i < n_ops; ++i)
-    if ((fops[8 * i] & 0xFF) >= FOP_VAR) is_vf[fops[8 * i + 3]] = 1;
-  std::vector<int32_t> back, fill;
-  for (int c = 0; c < n_msgs; ++c) {
-    if (out.hoisted[c] >= 0) continue;
-    if (written[c] && out.live_of_slot[c] >= 0) { back.push_back(out.live_of_slot[c]); back.push_back(c | (is_vf[c] ? 0x40000000 : 0)); }
-    else if (!written[c]) fill.push_back(c);
-  }
-  out.n_ops = n_ops; out.n_cpw = (int)ent.size();
-  out.n_back = (int)back.size() / 2; out.n_fill = (int)fill.size(); out.n_init = (int)init_tiles.size();
-  // device image: bundles [n_bundles + 1][2][4] | cprod entries | write-back pairs | fill slots | uniform tiles | product tiles | written bits
-  out.image = bundles;
-  out.off_ent = (int)out.image.size();
-  out.image.insert(out.image.end(), ent.begin(), ent.end());
-  out.off_back = (int)out.image.size();
-  out.image.insert(out.image.end(), back.begin(), back.end());
-  out.off_fill = (int)out.image.size();
-  out.image.insert(out.image.end(), fill.begin(), fill.end());
-  out.off_init = (int)out.image.size();
-  out.image.insert(out.image.end(), init_tiles.begin(), init_tiles.end());
-  out.off_ptile = (int)out.image.size();                         // tile of constant product k
-  for (int k = 0; k < fp.n_cprod; ++k) out.image.push_back(out.live_of_slot[n_msgs + 1 + k]);
-  out.off_written = (int)out.image.size();                       // bit c: some update of the program writes slot c
-  for (int c0 = 0; c0 < n_msgs; c0 += 32) {
-    uint32_t w = 0;
-    for (int c = c0; c < n_msgs && c < c0 + 32; ++c) w |= (written[c] ? 1u : 0u) << (c - c0);
-    out.image.push_back((int32_t)w);
-  }
-  for (int q = 0; q < 16; ++q) out.image.push_back(0);
-  // ---- product-fused form.  When every variable update of the program multiplies at most one constant product and one
-  // factor->variable message (variables with at most two pairwise factors: K2, K3, chains, rings), the message F->X is only
-  // ever read as the product  c_X (.) m_{F->X}  (LBP.py:377-389).  The PRODUCER then stores that product -- its 16 rows of the
-  // D fragment times its 16 rows of c_X: four multiplications -- and every contraction reads ONE tile straight into the matrix
-  // cores: no products, half the tile reads, and (float64 vector operations share the matrix cores' pipe) some fifty
-  // operations per update off the dependent chain.  The raw result of the LAST update of each slot goes to a scratch tile
-  // in memory for the read-out.  Member record, 4 words:
-  //   [0] flags | pair slot << 16: 1 contraction, 2 m^T.T, 8 the input S, normalised, is this variable->factor slot's last value:
-  //       to memory, 16 no contraction, 32 last update of the destination slot: raw result to stash [2] >> 8 (when the call writes
-  //       the messages back), 64 store the product
-  //   [1] destination tile | S tile << 8 (0xFF: the uniform vector) | message slot of S << 16   [2] constant-product tile the
-  //       result is multiplied by (0xFF none) | stash index << 8
-  {
-    std::vector<char> is_c(out.n_live, 0);
-    std::vector<int> prod_of_tile(out.n_live, -1);
-    for (int k = 0; k < fp.n_cprod; ++k) { is_c[out.live_of_slot[n_msgs + 1 + k]] = 1; prod_of_tile[out.live_of_slot[n_msgs + 1 + k]] = k; }
-    bool okp = out.max_sources <= 2;
-    std::vector<int> cp(out.n_live, -2);                          // constant product a message tile is read with: -2 never read, -1 none
-    std::vector<int> s_of(n_ops, 0xFF), last_writer(out.n_live, -1);
-    for (int i = 0; i < n_ops && okp; ++i) {
-      const int32_t* m = &mem[(size_t)i * MW];
-      const int n = (m[0] >> 8) & 15;
-      if (m[0] & 4) okp = false;                                  // a variable->factor message kept as a tile of its own
-      int c = -1, mt = -1, nc = 0, nm = 0;
-      for (int q = 0; q < n; ++q) {
-        const int tl = m[8 + q];
-        if (tl < 0) continue;
-        if (is_c[tl]) { c = tl; ++nc; } else { mt = tl; ++nm; }
-      }
-      if (nc > 1 || nm > 1) okp = false;
-      if (nm) {
-        if (cp[mt] == -2) cp[mt] = c; else if (cp[mt] != c) okp = false;
-        s_of[i] = mt;
-      } else if (nc) {
-        s_of[i] = c;
-      }
-      if ((m[0] & 1) && m[2] >= 0) { if (is_c[m[2]]) okp = false; last_writer[m[2]] = i; }
-    }
-    // every stored product needs its constant product (a variable without unary factors: the general form), and a member whose
-    // input is still the uniform vector reads a tile nothing touches before a later bundle writes it, filled by the prologue
-    for (int tl = 0; tl < out.n_live && okp; ++tl)
-      if (!is_c[tl] && cp[tl] == -1) okp = false;
-    std::vector<int32_t> uinit;                                   // tiles the prologue fills with the uniform vector
-    if (okp) {
-      std::vector<int> bundle_of(n_ops, 0), first_touch(out.n_live, n_ops + 1);
-      for (size_t b = 0; b < pairing.size(); b += 2) { bundle_of[pairing[b]] = (int)b / 2; if (pairing[b + 1] >= 0) bundle_of[pairing[b + 1]] = (int)b / 2; }
-      for (int i = n_ops - 1; i >= 0; --i) {
-        const int32_t* m = &mem[(size_t)i * MW];
-        if ((m[0] & 1) && m[2] >= 0) first_touch[m[2]] = bundle_of[i];
-        if (s_of[i] != 0xFF) first_touch[s_of[i]] = bundle_of[i];
-      }
-      for (int q : init_tiles) first_touch[q] = -1;              // (holds c (.) uniform from the start)
-      for (int i = 0; i < n_ops && okp; ++i) {
-        if (s_of[i] != 0xFF) continue;
-        int pick = -1;
-        for (int tl = 0; tl < out.n_live && pick < 0; ++tl)
-          if (!is_c[tl] && first_touch[tl] > bundle_of[i]) pick = tl;
-        if (pick < 0) { okp = false; break; }
-        s_of[i] = pick;
-        if (std::find(uinit.begin(), uinit.end(), pick) == uinit.end()) uinit.push_back(pick);
-      }
-    }
-    out.pf_ok = okp;
-    if (okp) {
-      std::vector<int32_t> stash(out.n_live, -1), pfb, pinit;
-      for (int tl : uinit) { pinit.push_back(tl); pinit.push_back(-1); }
-      for (int tl = 0; tl < out.n_live; ++tl) if (last_writer[tl] >= 0) stash[tl] = out.n_stash++;
-      auto pack_pf = [&](int i) {
-        int32_t w[4] = {0, 0xFFFF, 0xFF, 0};
-        if (i >= 0) {
-          const int32_t* m = &mem[(size_t)i * MW];
-          const int dst = (m[0] & 1) ? m[2] : -1;
-          w[0] = (m[0] & (1 | 2 | 8 | 16)) | (m[1] << 16);
-          if (dst >= 0 && last_writer[dst] == i) w[0] |= 32;
-          if (dst >= 0) w[0] |= 64;                              // (a slot nothing reads as an input is kept for the read-out: the raw result, c absent)
-          w[1] = (dst & 0xFF) | ((s_of[i] & 0xFF) << 8) | (m[4] << 16);
-          w[2] = ((dst >= 0 && cp[dst] >= 0 ? cp[dst] : 0xFF) & 0xFF) | ((dst >= 0 ? stash[dst] : 0) << 8);
-        }
-        pfb.insert(pfb.end(), w, w + 4);
-      };
-      for (size_t b = 0; b < pairing.size(); b += 2) { pack_pf(pairing[b]); pack_pf(pairing[b + 1]); }
-      pack_pf(-1); pack_pf(-1);
-      // message tiles read before the program writes them: c (.) uniform, i.e. a copy of the constant product (or uniform)
-      for (int q = 0; q < (int)init_tiles.size(); ++q) {
-        const int tl = init_tiles[q];
-        if (is_c[tl]) continue;
-        pinit.push_back(tl); pinit.push_back(cp[tl] >= 0 ? prod_of_tile[cp[tl]] : -1);
-      }
-      out.n_pinit = (int)pinit.size() / 2;
-      // The gradient epilogue takes a factor's two variable->factor messages straight from LDS when every such slot's last value
-      // (the input S of its flag-8 member) is a message tile no later member rewrites: vftile[slot] = that tile, -1 = never updated
-      // (uniform), and the form is off (vf_direct false) when some slot has no such tile or its S is a constant-product tile (the
-      // read-out stages the marginals there).
-      std::vector<int32_t> vftile(n_msgs, -1);
-      out.vf_direct = true;
-      for (int i = 0; i < n_ops; ++i) {
-        const int32_t* m = &mem[(size_t)i * MW];
-        if (!(m[0] & 8)) continue;
-        const int tl = s_of[i];
-        bool intact = tl != 0xFF && !is_c[tl];
-        for (int j = i; j < n_ops && intact; ++j) {               // (member i itself included: its own result must land elsewhere)
-          const int32_t* mj = &mem[(size_t)j * MW];
-          if ((mj[0] & 1) && mj[2] == tl) intact = false;
-        }
-        if (!intact) { out.vf_direct = false; break; }
-        vftile[m[4]] = tl;
-      }
-      for (int c = 0; c < n_msgs && out.vf_direct; ++c)
-        if (out.hoisted[c] < 0 && is_vf[c] && vftile[c] < 0) out.vf_direct = false;      // (a slot some variable update writes but no flag-8 member hands out)
-      out.off_pfb = (int)out.image.size();
-      out.image.insert(out.image.end(), pfb.begin(), pfb.end());
-      out.off_stash = (int)out.image.size();
-      out.image.insert(out.image.end(), stash.begin(), stash.end());
-      for (int tl = 0; tl < out.n_live; ++tl) out.image.push_back(cp[tl] >= 0 ? 1 : 0);       // [n_live] behind it: the tile holds c (.) message (else the message)
-      out.off_pinit = (int)out.image.size();
-      out.image.insert(out.image.end(), pinit.begin(), pinit.end());
-      out.off_vftile = (int)out.image.size();
-      out.image.insert(out.image.end(), vftile.begin(), vftile.end());
-      for (int q = 0; q < 16; ++q) out.image.push_back(0);
-      if (getenv("MLBP_DEBUG_SHARED_PROGRAM")) {
-        for (size_t i = 0; i + 3 < pfb.size(); i += 4) fprintf(stderr, "pf member: flags 0x%02x pair %d dst %d S %d slot %d c %d stash %d\n", pfb[i] & 0xFF,
-                                                                pfb[i] >> 16, pfb[i + 1] & 0xFF, (pfb[i + 1] >> 8) & 0xFF, pfb[i + 1] >> 16, pfb[i + 2] & 0xFF, pfb[i + 2] >> 8);
-        fprintf(stderr, "pf: n_stash %d n_pinit %d\n", out.n_stash, out.n_pinit);
-      }
-    }
-  }
-  // ---- product-fused form, variables with THREE pairwise factors (K4 cliques: every variable update multiplies the constant
-  // product c and two factor->variable messages).  The producer of a message into such a variable stores  sqrt(c) (.) m  (the
-  // prepare kernel writes sqrt(c) for these products): the input of a contraction is then the PRODUCT OF TWO TILES,
-  // sqrt(c) m_a (.) sqrt(c) m_b = c (.) m_a (.) m_b -- two tile reads and one multiplication per element instead of three reads
-  // and two, and 12 message tiles + the stored variable->factor messages instead of 21 tiles: everything stays in LDS (one
-  // workgroup per CU; the constant products themselves stay in memory: a producer asks for its sixteen rows of them in front of
-  // its matrix instructions).  A variable with two pairwise factors in the same program keeps the c (.) m form above (the
-  // exponent is per constant product: sqrt_mask).  Stored variable->factor messages (members with flag 4, read by a later
-  // plain factor update) are raw tiles.  Record, 4 words:
-  //   [0] flags | pair slot << 16: as above, and 4 the input product is kept as tile [3] >> 8, 0x100 a second input tile [3] & 0xFF
-  //   [1] destination | input tile << 8 | message slot of the input product << 16      (tiles: LDS indices, the constant products left out)
-  //   [2] constant PRODUCT INDEX the result is multiplied by (0xFF none) | stash index << 8      [3] second input | kept tile << 8
-  // Sections: map3 [n_live] LDS index of a tile (0x100 | product index for a constant product), kind3 [n_lds] 0 raw / 1 c (.) m /
-  // 2 sqrt(c) (.) m, | 0x100 some update writes it; stash [n_lds]; back3 [n_back][2] the write-back list in LDS indices.
-  if (!out.pf_ok && out.max_sources == 3) {
-    const int NL = out.n_live;
-    std::vector<char> is_c(NL, 0);
-    std::vector<int> prod_of_tile(NL, -1);
-    for (int k = 0; k < fp.n_cprod; ++k) { is_c[out.live_of_slot[n_msgs + 1 + k]] = 1; prod_of_tile[out.live_of_slot[n_msgs + 1 + k]] = k; }
-    bool ok3 = true;
-    std::vector<int> kind(NL, -2), cp(NL, -1), last_writer(NL, -1), ckind(NL, 0);
-    std::vector<int> s1(n_ops, 0xFF), s2(n_ops, 0xFF);
-    for (int i = 0; i < n_ops && ok3; ++i) {
-      const int32_t* m = &mem[(size_t)i * MW];
-      const int n = (m[0] >> 8) & 15;
-      if (pair_kind[i]) {
-        const int tl = m[8];
-        if (tl >= 0) {
-          if (is_c[tl] || (kind[tl] != -2 && kind[tl] != 0)) ok3 = false;
-          else { kind[tl] = 0; s1[i] = tl; }
-        }
-      } else {
-        int c = -1, nc = 0, nm = 0, mt[2] = {-1, -1};
-        for (int q = 0; q < n; ++q) {
-          const int tl = m[8 + q];
-          if (tl < 0) { ok3 = false; break; }
-          if (is_c[tl]) { c = tl; ++nc; }
-          else if (nm < 2) mt[nm++] = tl;
-          else ok3 = false;
-        }
-        if (nc != 1 || nm < 1) ok3 = false;
-        for (int q = 0; q < nm && ok3; ++q) {
-          if (kind[mt[q]] == -2) { kind[mt[q]] = nm; cp[mt[q]] = c; }
-          else if (kind[mt[q]] != nm || cp[mt[q]] != c) ok3 = false;
-        }
-        if (ok3) {
-          if (ckind[c] == 0) ckind[c] = nm; else if (ckind[c] != nm) ok3 = false;
-          s1[i] = mt[0]; s2[i] = nm == 2 ? mt[1] : 0xFF;
-        }
-        if (ok3 && (m[0] & 4)) {
-          const int K = m[3];
-          if (K < 0 || is_c[K] || (kind[K] != -2 && kind[K] != 0)) ok3 = false; else kind[K] = 0;
-        }
-      }
-      if (ok3 && (m[0] & 1) && m[2] >= 0) { if (is_c[m[2]]) ok3 = false; last_writer[m[2]] = i; }
-    }
-    std::vector<int32_t> uinit;
-    if (ok3) {
-      std::vector<int> bundle_of(n_ops, 0), first_touch(NL, n_ops + 1);
-      for (size_t b = 0; b < pairing.size(); b += 2) { bundle_of[pairing[b]] = (int)b / 2; if (pairing[b + 1] >= 0) bundle_of[pairing[b + 1]] = (int)b / 2; }
-      for (int i = n_ops - 1; i >= 0; --i) {
-        const int32_t* m = &mem[(size_t)i * MW];
-        if ((m[0] & 1) && m[2] >= 0) first_touch[m[2]] = bundle_of[i];
-        if (m[0] & 4) first_touch[m[3]] = bundle_of[i];
-        if (s1[i] != 0xFF) first_touch[s1[i]] = bundle_of[i];
-        if (s2[i] != 0xFF) first_touch[s2[i]] = bundle_of[i];
-      }
-      for (int q : init_tiles) first_touch[q] = -1;
-      for (int i = 0; i < n_ops && ok3; ++i) {
-        if (s1[i] != 0xFF) continue;                              // (only a plain factor update whose input nothing has written yet)
-        int pick = -1;
-        for (int tl = 0; tl < NL && pick < 0; ++tl)
-          if (!is_c[tl] && first_touch[tl] > bundle_of[i]) pick = tl;
-        if (pick < 0) { ok3 = false; break; }
-        s1[i] = pick;
-        if (std::find(uinit.begin(), uinit.end(), pick) == uinit.end()) uinit.push_back(pick);
-      }
-    }
-    out.p3_ok = ok3;
-    if (ok3) {
-      std::vector<int> lds_of(NL, -1);
-      out.n_lds = 0;
-      for (int tl = 0; tl < NL; ++tl) if (!is_c[tl]) lds_of[tl] = out.n_lds++;
-      out.sqrt_mask = 0;
-      for (int tl = 0; tl < NL; ++tl) if (is_c[tl] && ckind[tl] == 2) out.sqrt_mask |= 1 << prod_of_tile[tl];
-      std::vector<int32_t> stash(out.n_lds, -1), pfb, pinit, map3(NL, 0), kind3(out.n_lds, 0), back3;
-      out.n_stash = 0;
-      for (int tl = 0; tl < NL; ++tl) {
-        map3[tl] = is_c[tl] ? (0x100 | prod_of_tile[tl]) : lds_of[tl];
-        if (is_c[tl]) continue;
-        if (last_writer[tl] >= 0) stash[lds_of[tl]] = out.n_stash++;
-        kind3[lds_of[tl]] = std::max(kind[tl], 0) | (last_writer[tl] >= 0 ? 0x100 : 0);
-      }
-      for (int tl : uinit) { pinit.push_back(lds_of[tl]); pinit.push_back(-1); }
-      for (int q = 0; q < (int)init_tiles.size(); ++q) {
-        const int tl = init_tiles[q];
-        if (is_c[tl]) continue;
-        pinit.push_back(lds_of[tl]); pinit.push_back(cp[tl] >= 0 ? prod_of_tile[cp[tl]] : -1);
-      }
-      auto pack3 = [&](int i) {
-        int32_t w[4] = {0, 0xFFFF, 0xFF, 0xFFFF};
-        if (i >= 0) {
-          const int32_t* m = &mem[(size_t)i * MW];
-          const int dst = (m[0] & 1) ? m[2] : -1;
-          w[0] = (m[0] & (1 | 2 | 4 | 8 | 16)) | (m[1] << 16);
-          if (dst >= 0 && last_writer[dst] == i) w[0] |= 32;
-          if (dst >= 0) w[0] |= 64;
-          if (s2[i] != 0xFF) w[0] |= 0x100;
-          w[1] = ((dst >= 0 ? lds_of[dst] : 0xFF) & 0xFF) | ((lds_of[s1[i]] & 0xFF) << 8) | (m[4] << 16);
-          w[2] = ((dst >= 0 && cp[dst] >= 0 ? prod_of_tile[cp[dst]] : 0xFF) & 0xFF) | ((dst >= 0 ? stash[lds_of[dst]] : 0) << 8);
-          w[3] = ((s2[i] != 0xFF ? lds_of[s2[i]] : 0xFF) & 0xFF) | ((((m[0] & 4) ? lds_of[m[3]] : 0xFF) & 0xFF) << 8);
-        }
-        pfb.insert(pfb.end(), w, w + 4);
-      };
-      for (size_t b = 0; b < pairing.size(); b += 2) { pack3(pairing[b]); pack3(pairing[b + 1]); }
-      pack3(-1); pack3(-1);
-      for (size_t q = 0; q + 1 < back.size(); q += 2) { back3.push_back(lds_of[back[q]]); back3.push_back(back[q + 1]); }
-      out.n_pinit = (int)pinit.size() / 2;
-      out.vf_direct = false;
-      out.off_pfb = (int)out.image.size();
-      out.image.insert(out.image.end(), pfb.begin(), pfb.end());
-      out.off_stash = (int)out.image.size();
-      out.image.insert(out.image.end(), stash.begin(), stash.end());
-      out.off_pinit = (int)out.image.size();
-      out.image.insert(out.image.end(), pinit.begin(), pinit.end());
-      out.off_map3 = (int)out.image.size();
-      out.image.insert(out.image.end(), map3.begin(), map3.end());
-      out.off_kind3 = (int)out.image.size();
-      out.image.insert(out.image.end(), kind3.begin(), kind3.end());
-      out.off_back3 = (int)out.image.size();
-      out.image.insert(out.image.end(), back3.begin(), back3.end());
-      for (int q = 0; q < 16; ++q) out.image.push_back(0);
-      if (getenv("MLBP_DEBUG_SHARED_PROGRAM")) {
-        for (size_t i = 0; i + 3 < pfb.size(); i += 4)
-          fprintf(stderr, "p3 member: flags 0x%03x pair %d dst %d S %d S2 %d keep %d slot %d cprod %d stash %d\n", pfb[i] & 0xFFF, pfb[i] >> 16, pfb[i + 1] & 0xFF,
-                  (pfb[i + 1] >> 8) & 0xFF, pfb[i + 3] & 0xFF, (pfb[i + 3] >> 8) & 0xFF, pfb[i + 1] >> 16, pfb[i + 2] & 0xFF, pfb[i + 2] >> 8);
-        fprintf(stderr, "p3: n_lds %d n_stash %d n_pinit %d sqrt_mask 0x%x\n", out.n_lds, out.n_stash, out.n_pinit, out.sqrt_mask);
-      }
-    }
-  }
-  out.why = "";
-  out.ok = true;
-}
-
-bool build_shared_readout(const SharedProgram& sp, int n_msgs, int n_vars, const int32_t* in_off, const int32_t* in_slots,
-                          std::vector<int32_t>& image) {
-  // layout: offset of variable v's list [n_vars], then per variable {base tile or -1, n, tiles...}
-  image.assign(n_vars, 0);
-  while (image.size() % 4) image.push_back(0);
-  for (int v = 0; v < n_vars; ++v) {
-    std::vector<int32_t> consts, tiles;
-    for (int q = in_off[v]; q < in_off[v + 1]; ++q) {
-      const int c = in_slots[q];
-      if (sp.hoisted[c] >= 0) consts.push_back(c);
-      else if (sp.live_of_slot[c] >= 0) tiles.push_back(sp.live_of_slot[c]);
-      else if (sp.written[c]) return false;            // written but not resident: not an incoming message we can read
-      // else: never read and never written inside the sweeps -> still uniform, cancels in the normalisation
-    }
-    int base = -1;
-    if (!consts.empty()) {
-      for (size_t k = 0; k < sp.cprods.size(); ++k)
-        if (sp.cprods[k] == consts) base = sp.live_of_slot[n_msgs + 1 + (int)k];
-      if (base < 0) return false;
-    }
-    image[v] = (int)image.size();
-    image.push_back(base);
-    image.push_back((int)tiles.size());
-    image.insert(image.end(), tiles.begin(), tiles.end());
-    while (image.size() % 4) image.push_back(0);
-  }
-  return true;
-}
-
 namespace {
 
 constexpr int WG = 256;                // the gradient kernels and the small helpers
 constexpr int SWG = 512;               // the sweep kernel: eight waves
 constexpr int G = 16;                 // graphs per workgroup = the N of v_mfma_f64_16x16x4_f64
 constexpr int TILE = 64 * G;          // doubles per message tile
-constexpr int MW = 4;                 // words per packed member record (build_shared_program); a bundle = 8 words
+constexpr int MW = 4;                 // words per packed member record (pack_member in mlbp_compile_shared.cpp); a bundle = 8 words
 
 using mlbp_dev::as_const;
 using mlbp_dev::const_i32p;

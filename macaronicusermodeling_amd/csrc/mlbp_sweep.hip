@@ -51,7 +51,7 @@ __device__ __forceinline__ bool tables_in_range(const SweepDev& d, int g) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// X = 64, float64, the EXACT kernel ("fused" program form, see build_fused_program): thread t holds rows 8k + (t >> 5),
+// X = 64, float64, the EXACT kernel ("fused" program form, see build_fused_program in mlbp_compile.cpp): thread t holds rows 8k + (t >> 5),
 // columns 2 (t & 31) .. +1 of a resident table (as double2 element k * 256 + t).  It normalises after every update like the
 // reference and is the fix-up pass behind the fast kernels (mlbp_lean.hip, mlbp_shared.hip), the kernel for
 // normalize_messages = False and for programs whose unary updates cannot be hoisted:
@@ -1032,208 +1032,6 @@ __global__ __launch_bounds__(LP_WG) void log_posterior_groups_kernel(const mlbp_
   out[i] = total;
 }
 
-// Fused program form (see sweep_x64_fused_kernel).  Input: the validated 4-word op list.
-using mlbp::FusedProgram;
-
-void build_fused_program(const int32_t* ops_in, const int32_t* srcs, const int32_t* sweeps, int n_sweeps, int n_msgs,
-                         FusedProgram& out) {
-  // 0. inside each sweep, sink every variable->factor update down to just before the pairwise update that
-  //    consumes it when nothing in between writes one of its inputs or touches its output.  The up pass of a
-  //    loopy schedule (LBP.py:227-233) emits "X7->F17, X4->F14, F17->X1, F14->X1": neither pair is adjacent, so
-  //    without this no fusion happens.  Updates keep their inputs, hence their values; only the order of
-  //    independent updates changes.
-  int n_total = 0;
-  for (int s = 0; s < n_sweeps; ++s) n_total = std::max(n_total, sweeps[2 * s] + sweeps[2 * s + 1]);
-  std::vector<int32_t> ops_v(ops_in, ops_in + 4 * (size_t)n_total);
-  for (int s = 0; s < n_sweeps; ++s) {
-    const int first = sweeps[2 * s], cnt = sweeps[2 * s + 1];
-    int32_t* q = ops_v.data() + 4 * (size_t)first;
-    auto is_pair = [&](int i) { return q[4 * i] == MLBP_OP_PAIR_TM || q[4 * i] == MLBP_OP_PAIR_MT; };
-    for (int i = 0; i < cnt; ++i) {
-      if (q[4 * i] != MLBP_OP_VAR) continue;
-      const int a = q[4 * i + 1], b = q[4 * i + 2], c = q[4 * i + 3];
-      int j = i + 1;
-      bool legal = true;
-      for (; j < cnt && legal; ++j) {
-        if (is_pair(j) && q[4 * j + 2] == c) break;                                  // the consumer
-        const int w = q[4 * j + 3];
-        if (w == c) legal = false;
-        for (int k = a; k < a + b && legal; ++k) if (srcs[k] == w) legal = false;
-        if (q[4 * j] == MLBP_OP_VAR)
-          for (int k = q[4 * j + 1]; k < q[4 * j + 1] + q[4 * j + 2] && legal; ++k) if (srcs[k] == c) legal = false;
-      }
-      if (!legal || j >= cnt || j == i + 1) continue;
-      const int32_t v[4] = {q[4 * i], a, b, c};
-      for (int k = i; k < j - 1; ++k)
-        for (int e = 0; e < 4; ++e) q[4 * k + e] = q[4 * (k + 1) + e];
-      for (int e = 0; e < 4; ++e) q[4 * (j - 1) + e] = v[e];
-      --i;                                                                           // the op that slid into place i
-    }
-  }
-  const int32_t* ops = ops_v.data();
-  // 1. may the unary messages be hoisted?  Every read of a unary factor's message slot must come
-  //    after a UNARY op has written that slot (then the value read is always the same constant).
-  std::vector<char> is_unary_dst(n_msgs, 0), written(n_msgs, 0);
-  std::vector<int> unary_of(n_msgs, -1);
-  bool hoistable = true;
-  for (int s = 0; s < n_sweeps; ++s)
-    for (int o = sweeps[2 * s]; o < sweeps[2 * s] + sweeps[2 * s + 1]; ++o)
-      if (ops[4 * o] == MLBP_OP_UNARY) {
-        int c = ops[4 * o + 3];
-        if (is_unary_dst[c] && unary_of[c] != ops[4 * o + 1]) hoistable = false;  // two tables, one slot
-        is_unary_dst[c] = 1;
-        unary_of[c] = ops[4 * o + 1];
-      }
-  for (int s = 0; s < n_sweeps && hoistable; ++s)
-    for (int o = sweeps[2 * s]; o < sweeps[2 * s] + sweeps[2 * s + 1] && hoistable; ++o) {
-      const int kind = ops[4 * o], a = ops[4 * o + 1], b = ops[4 * o + 2], c = ops[4 * o + 3];
-      if (kind == MLBP_OP_UNARY) {
-        written[c] = 1;
-      } else if (kind == MLBP_OP_VAR) {
-        for (int q = a; q < a + b; ++q)
-          if (is_unary_dst[srcs[q]] && !written[srcs[q]]) hoistable = false;
-        if (is_unary_dst[c]) hoistable = false;
-      } else {
-        if ((is_unary_dst[b] && !written[b]) || is_unary_dst[c]) hoistable = false;
-      }
-    }
-  if (hoistable)
-    for (int c = 0; c < n_msgs; ++c)
-      if (is_unary_dst[c]) { out.hoist.push_back(unary_of[c]); out.hoist.push_back(c); }
-  // 2. per variable update: fast source list = [base slot, varying sources...] where the base is the
-  //    uniform vector (ext slot 0) or the constant product of the hoisted sources (ext slot 1+k);
-  //    exact source list = the original one.  Lists start on multiples of 4 words (int4 reads).
-  std::vector<std::vector<int>> cprods;                      // distinct constant-source lists
-  auto pad4 = [&]() { while (out.psrcs.size() % 4) out.psrcs.push_back(n_msgs); };
-  auto var_lists = [&](int a, int b, int& fa, int& fn, int& ea, int& en) {
-    std::vector<int> consts, vars;
-    for (int q = a; q < a + b; ++q) (hoistable && is_unary_dst[srcs[q]] ? consts : vars).push_back(srcs[q]);
-    int base = n_msgs;                                        // uniform
-    if (!consts.empty()) {
-      int k = 0;
-      for (; k < (int)cprods.size(); ++k)
-        if (cprods[k] == consts) break;
-      if (k == (int)cprods.size()) cprods.push_back(consts);
-      base = n_msgs + 1 + k;
-    }
-    pad4();
-    fa = (int)out.psrcs.size();
-    out.psrcs.push_back(base);
-    for (int v : vars) out.psrcs.push_back(v);
-    fn = 1 + (int)vars.size();
-    pad4();
-    ea = (int)out.psrcs.size();
-    for (int q = a; q < a + b; ++q) out.psrcs.push_back(srcs[q]);
-    en = b;
-  };
-  // 3. fuse "variable -> factor" into the pairwise update it feeds; drop hoisted unary ops.
-  for (int s = 0; s < n_sweeps; ++s) {
-    const int first = sweeps[2 * s], cnt = sweeps[2 * s + 1];
-    const int f0 = (int)out.fops.size() / 8;
-    for (int o = first; o < first + cnt; ++o) {
-      const int kind = ops[4 * o], a = ops[4 * o + 1], b = ops[4 * o + 2], c = ops[4 * o + 3];
-      if (kind == MLBP_OP_UNARY) {
-        if (!hoistable) out.fops.insert(out.fops.end(), {FOP_UNARY, a, 0, c, 0, 0, 0, 0});
-      } else if (kind == MLBP_OP_VAR) {
-        int fa, fn, ea, en;
-        var_lists(a, b, fa, fn, ea, en);
-        const bool next_is_pair = o + 1 < first + cnt &&
-                                  (ops[4 * (o + 1)] == MLBP_OP_PAIR_TM || ops[4 * (o + 1)] == MLBP_OP_PAIR_MT) &&
-                                  ops[4 * (o + 1) + 2] == c;
-        if (next_is_pair) {
-          const int pk = ops[4 * (o + 1)];
-          out.fops.insert(out.fops.end(), {pk == MLBP_OP_PAIR_TM ? FOP_VAR_PAIR_TM : FOP_VAR_PAIR_MT, fa, fn, c,
-                                           ops[4 * (o + 1) + 1], ops[4 * (o + 1) + 3], ea, en});
-          out.pairseq.push_back(ops[4 * (o + 1) + 1]);
-          ++o;
-        } else {
-          out.fops.insert(out.fops.end(), {FOP_VAR, fa, fn, c, 0, 0, ea, en});
-        }
-      } else {
-        out.fops.insert(out.fops.end(), {kind == MLBP_OP_PAIR_TM ? FOP_PAIR_TM : FOP_PAIR_MT, a, b, c, 0, 0, 0, 0});
-        out.pairseq.push_back(a);
-      }
-    }
-    out.fsweeps.push_back(f0);
-    out.fsweeps.push_back((int)out.fops.size() / 8 - f0);
-  }
-  // 3b. drop lone variable->factor updates whose result is overwritten before anything reads it (the last two of a
-  //     sweep when the next sweep's root differs: the new schedule recomputes those messages first).  Backward
-  //     liveness over the whole call; every slot is live at the end (the messages are an output).
-  {
-    const int n = (int)out.fops.size() / 8;
-    std::vector<char> live(n_msgs + 1 + (int)cprods.size(), 1), dead(n, 0);
-    for (int i = n - 1; i >= 0; --i) {
-      const int32_t* w = &out.fops[8 * (size_t)i];
-      const int kd = w[0] & 0xFF;
-      if (kd == FOP_VAR && !live[w[3]]) { dead[i] = 1; continue; }
-      if (kd == FOP_UNARY) { live[w[3]] = 0; continue; }
-      if (kd == FOP_PAIR_TM || kd == FOP_PAIR_MT) { live[w[3]] = 0; live[w[2]] = 1; continue; }
-      live[w[3]] = 0;
-      if (kd != FOP_VAR) live[w[5]] = 0;
-      for (int q = 0; q < w[2]; ++q) live[out.psrcs[w[1] + q]] = 1;
-      for (int q = 0; q < w[7]; ++q) live[out.psrcs[w[6] + q]] = 1;
-    }
-    std::vector<int32_t> kept;
-    std::vector<int32_t> fs;
-    for (size_t sw = 0; sw + 1 < out.fsweeps.size(); sw += 2) {
-      const int f0 = (int)kept.size() / 8;
-      for (int i = out.fsweeps[sw]; i < out.fsweeps[sw] + out.fsweeps[sw + 1]; ++i)
-        if (!dead[i]) kept.insert(kept.end(), out.fops.begin() + 8 * (size_t)i, out.fops.begin() + 8 * (size_t)i + 8);
-      fs.push_back(f0); fs.push_back((int)kept.size() / 8 - f0);
-    }
-    out.fops.swap(kept);
-    out.fsweeps.swap(fs);
-  }
-  // 3c. bundles
-  for (size_t sw = 0; sw + 1 < out.fsweeps.size(); sw += 2) {
-    const int f0 = out.fsweeps[sw];
-    // bundle adjacent pairwise updates that touch disjoint message slots
-    {
-      const int f1 = f0 + out.fsweeps[sw + 1];
-      auto is_pair = [&](int i) { int kd = out.fops[8 * i] & 0xFF; return kd == FOP_PAIR_TM || kd == FOP_PAIR_MT || kd == FOP_VAR_PAIR_TM || kd == FOP_VAR_PAIR_MT; };
-      auto sets = [&](int i, std::vector<int>& rd, std::vector<int>& wr) {
-        const int32_t* w = &out.fops[8 * i];
-        const int kd = w[0] & 0xFF;
-        rd.clear(); wr.clear();
-        if (kd == FOP_PAIR_TM || kd == FOP_PAIR_MT) { rd.push_back(w[2]); wr.push_back(w[3]); }
-        else { for (int q = 0; q < w[7]; ++q) rd.push_back(out.psrcs[w[6] + q]); wr.push_back(w[3]); wr.push_back(w[5]); }
-      };
-      auto meets = [](const std::vector<int>& x, const std::vector<int>& y) {
-        for (int u : x) for (int v : y) if (u == v) return true;
-        return false;
-      };
-      std::vector<int> ra, wa, rb, wb;
-      for (int i = f0; i + 1 < f1; ++i) {
-        if (!is_pair(i) || !is_pair(i + 1)) continue;
-        sets(i, ra, wa); sets(i + 1, rb, wb);
-        if (meets(wa, rb) || meets(wb, ra) || meets(wa, wb)) continue;
-        out.fops[8 * i] |= FOP_BUNDLED;
-        ++i;                                       // bundles hold two updates
-      }
-    }
-  }
-  out.pairseq.push_back(-1);
-  {
-    std::vector<char> w(n_msgs, 0);
-    for (size_t i = 0; i < out.fops.size(); i += 8) {
-      const int kind = out.fops[i] & 0xFF;
-      if (kind == FOP_UNARY) { out.has_unary_fops = true; continue; }
-      w[out.fops[i + 3]] = 1;                                            // VAR dst / standalone PAIR dst
-      if (kind == FOP_VAR_PAIR_TM || kind == FOP_VAR_PAIR_MT) w[out.fops[i + 5]] = 1;
-    }
-    for (int c = 0; c < n_msgs; ++c)
-      if (w[c]) out.written.push_back(c);
-  }
-  for (int q = 0; q < 8; ++q) out.psrcs.push_back(n_msgs);   // tail padding for the int4 reads
-  pad4();
-  out.n_cprod = (int)cprods.size();
-  for (auto& l : cprods) {
-    out.cpw.push_back((int)l.size());
-    for (int v : l) out.cpw.push_back(v);
-  }
-}
-
 // mlbp_set_sweep_variant: 1 = the fast kernels with the exact kernel as fix-up (default), 3 = the exact / per-graph
 // kernels on every graph (the tests' reference on the same inputs).
 int g_sweep_variant = 1;
@@ -1288,107 +1086,6 @@ int mlbp_device_count(void) {
   return n;
 }
 
-// Range checks shared by mlbp_program_create and mlbp_program_plan; every later routine indexes freely.
-static int validate_program(const int32_t* ops, int32_t n_ops, const int32_t* srcs, int32_t n_srcs, const int32_t* sweeps,
-                            int32_t n_sweeps, int32_t n_msgs, int32_t P, int32_t U, int* max_srcs_out) {
-  if (!ops || !sweeps || n_ops <= 0 || n_sweeps <= 0 || n_msgs <= 0 || P < 0 || U < 0 || n_srcs < 0 ||
-      (n_srcs > 0 && !srcs))
-    return fail(MLBP_EINVAL, "program: bad sizes or NULL arrays");
-  int max_srcs = 0;
-  for (int o = 0; o < n_ops; ++o) {
-    const int kind = ops[4 * o], a = ops[4 * o + 1], b = ops[4 * o + 2], c = ops[4 * o + 3];
-    if (c < 0 || c >= n_msgs) return fail(MLBP_EINVAL, "op %d: destination slot %d out of [0,%d)", o, c, n_msgs);
-    switch (kind) {
-      case MLBP_OP_UNARY:
-        if (a < 0 || a >= U) return fail(MLBP_EINVAL, "op %d: unary slot %d out of [0,%d)", o, a, U);
-        break;
-      case MLBP_OP_PAIR_TM:
-      case MLBP_OP_PAIR_MT:
-        if (a < 0 || a >= P) return fail(MLBP_EINVAL, "op %d: pair slot %d out of [0,%d)", o, a, P);
-        if (b < 0 || b >= n_msgs) return fail(MLBP_EINVAL, "op %d: source slot %d out of range", o, b);
-        if (b == c) return fail(MLBP_EINVAL, "op %d: source and destination slot coincide", o);
-        break;
-      case MLBP_OP_VAR:
-        if (a < 0 || b < 0 || (int64_t)a + b > n_srcs) return fail(MLBP_EINVAL, "op %d: srcs range [%d,%d) out of [0,%d)", o, a, a + b, n_srcs);
-        for (int q = a; q < a + b; ++q)
-          if (srcs[q] < 0 || srcs[q] >= n_msgs) return fail(MLBP_EINVAL, "op %d: source slot %d out of range", o, srcs[q]);
-        if (b > max_srcs) max_srcs = b;
-        break;
-      default:
-        return fail(MLBP_EINVAL, "op %d: unknown kind %d", o, kind);
-    }
-  }
-  for (int s = 0; s < n_sweeps; ++s) {
-    const int first = sweeps[2 * s], cnt = sweeps[2 * s + 1];
-    if (first < 0 || cnt < 0 || (int64_t)first + cnt > n_ops)
-      return fail(MLBP_EINVAL, "sweep %d: op range [%d,%d) out of [0,%d)", s, first, first + cnt, n_ops);
-  }
-  if (max_srcs_out) *max_srcs_out = max_srcs;
-  return MLBP_OK;
-}
-
-/* Host only: what the program rewrites make of an op list (no device needed). */
-int mlbp_program_plan(const int32_t* ops, int32_t n_ops, const int32_t* srcs, int32_t n_srcs, const int32_t* sweeps,
-                      int32_t n_sweeps, int32_t n_msgs, int32_t P, int32_t U, int32_t* out8) {
-  if (!out8) return fail(MLBP_EINVAL, "mlbp_program_plan: out8 is NULL");
-  if (int e = validate_program(ops, n_ops, srcs, n_srcs, sweeps, n_sweeps, n_msgs, P, U, nullptr)) return e;
-  FusedProgram fp;
-  build_fused_program(ops, srcs, sweeps, n_sweeps, n_msgs, fp);
-  int lone = 0, fused = 0, bundled = 0;
-  for (size_t i = 0; i < fp.fops.size(); i += 8) {
-    const int k = fp.fops[i] & 0xFF;
-    lone += k == FOP_VAR;
-    fused += k == FOP_VAR_PAIR_TM || k == FOP_VAR_PAIR_MT;
-    bundled += (fp.fops[i] & FOP_BUNDLED) != 0;
-  }
-  mlbp::SharedProgram sp;
-  mlbp::build_shared_program(fp, n_msgs, P, U, sp);
-  out8[0] = (int)fp.fops.size() / 8; out8[1] = lone; out8[2] = fused; out8[3] = bundled;
-  out8[4] = (sp.ok ? 1 : 0) | (sp.ok && sp.pf_ok ? 2 : 0) | (sp.ok && sp.pf_ok && sp.vf_direct ? 4 : 0) | (sp.ok && sp.p3_ok ? 8 : 0); out8[5] = sp.n_live; out8[6] = sp.n_ops; out8[7] = sp.n_live * (64 * 16 + 64) * 8;
-  return MLBP_OK;
-}
-
-// MLBP_SWEEP_SKIP_UNCHANGED: the op list with every update dropped whose inputs -- and therefore whose result, bit for
-// bit -- are what they were when the destination slot was last computed.  Value numbering over the whole call: a slot's
-// value is named by (kind, table / factor, names of the source values); what the call starts from is opaque.  A root
-// sequence re-walks messages that the previous sweep left final (the whole of a tree after its first sweep; the part of a
-// loopy graph upstream of the first changed message), LBP.py:223-233 recomputes them, this list does not.  Returns the
-// number of updates dropped; sweeps_out are ranges into ops_out (no sharing between equal roots any more).
-static int drop_unchanged_updates(const int32_t* ops, const int32_t* srcs, const int32_t* sweeps, int n_sweeps, int n_msgs,
-                                  std::vector<int32_t>& ops_out, std::vector<int32_t>& sweeps_out) {
-  std::map<std::vector<int64_t>, int64_t> names;
-  std::vector<int64_t> val(n_msgs);
-  for (int c = 0; c < n_msgs; ++c) val[c] = -(int64_t)c - 1;
-  int dropped = 0;
-  std::vector<int64_t> key;
-  for (int s = 0; s < n_sweeps; ++s) {
-    const int first = sweeps[2 * s], cnt = sweeps[2 * s + 1];
-    const int start = (int)ops_out.size() / 4;
-    for (int o = first; o < first + cnt; ++o) {
-      const int kind = ops[4 * o], a = ops[4 * o + 1], b = ops[4 * o + 2], c = ops[4 * o + 3];
-      key.clear();
-      key.push_back(kind);
-      if (kind == MLBP_OP_VAR) {
-        for (int q = a; q < a + b; ++q) key.push_back(val[srcs[q]]);
-      } else if (kind == MLBP_OP_UNARY) {
-        key.push_back(a);
-      } else {
-        key.push_back(a);
-        key.push_back(val[b]);
-      }
-      auto it = names.find(key);
-      const int64_t name = it != names.end() ? it->second : (int64_t)names.size();
-      if (it == names.end()) names.emplace(key, name);
-      if (val[c] == name) { ++dropped; continue; }
-      val[c] = name;
-      ops_out.insert(ops_out.end(), ops + 4 * o, ops + 4 * o + 4);
-    }
-    sweeps_out.push_back(start);
-    sweeps_out.push_back((int)ops_out.size() / 4 - start);
-  }
-  return dropped;
-}
-
 static int create_program(const int32_t* ops, int32_t n_ops, const int32_t* srcs, int32_t n_srcs,
                           const int32_t* sweeps, int32_t n_sweeps, int32_t n_msgs, int32_t P, int32_t U,
                           mlbp_program** out, bool with_pruned);
@@ -1405,7 +1102,7 @@ static int create_program(const int32_t* ops, int32_t n_ops, const int32_t* srcs
   if (!out) return fail(MLBP_EINVAL, "out is NULL");
   *out = nullptr;
   int max_srcs = 0;
-  if (int e = validate_program(ops, n_ops, srcs, n_srcs, sweeps, n_sweeps, n_msgs, P, U, &max_srcs)) return e;
+  if (int e = mlbp::validate_program(ops, n_ops, srcs, n_srcs, sweeps, n_sweeps, n_msgs, P, U, &max_srcs)) return e;
   std::vector<int32_t> pairseq;
   for (int s = 0; s < n_sweeps; ++s) {
     const int first = sweeps[2 * s], cnt = sweeps[2 * s + 1];
@@ -1434,8 +1131,8 @@ static int create_program(const int32_t* ops, int32_t n_ops, const int32_t* srcs
   if (e == hipSuccess) e = up(&p->d_pairseq, pairseq.data(), pairseq.size());
   int32_t zero = 0;
   if (e == hipSuccess) e = up(&p->d_status, &zero, 1);
-  FusedProgram fp;
-  build_fused_program(ops, srcs, sweeps, n_sweeps, n_msgs, fp);
+  mlbp::FusedProgram fp;
+  mlbp::build_fused_program(ops, srcs, sweeps, n_sweeps, n_msgs, fp);
   p->n_fops = (int)fp.fops.size() / 8;
   p->n_hoist = (int)fp.hoist.size() / 2;
   p->n_psrcs = (int)fp.psrcs.size();
@@ -1472,7 +1169,7 @@ static int create_program(const int32_t* ops, int32_t n_ops, const int32_t* srcs
   }
   if (with_pruned) {
     std::vector<int32_t> ops2, sweeps2;
-    p->n_dropped = drop_unchanged_updates(ops, srcs, sweeps, n_sweeps, n_msgs, ops2, sweeps2);
+    p->n_dropped = mlbp::drop_unchanged_updates(ops, srcs, sweeps, n_sweeps, n_msgs, ops2, sweeps2);
     if (p->n_dropped > 0) {
       if (int rc = create_program(ops2.data(), (int)ops2.size() / 4, srcs, n_srcs, sweeps2.data(), n_sweeps, n_msgs, P, U, &p->pruned, false)) {
         mlbp_program_destroy(p);

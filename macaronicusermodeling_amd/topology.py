@@ -171,7 +171,35 @@ class GraphTopology:
         plan['shared_ok'] &= 1
         return plan
 
+    def images(self, roots):
+        """Every integer image the program compilers make of this root sequence (no GPU needed): program_images of its op list."""
+        ops, srcs, sweeps = self.compile_program(roots)
+        return program_images(ops, srcs, sweeps, self.n_msgs, self.P, self.U, self.n_vars, self.in_off, self.in_slots)
+
     @classmethod
     def from_spec(cls, spec):
         """From the plain-data specs used by the tests and the benchmark (tests/golden/cases.py)."""
         return cls([(f['id'], f['vars'], f['dims']) for f in spec['factors']])
+
+
+
+def program_images(ops, srcs, sweeps, n_msgs, P, U, n_vars, in_off, in_slots):
+    """{name: int32 array} for the names of _ffi.IMAGES: what the host-side compilers make of an op list (as compile_program
+    returns it) and a read-out table, each in mlbp_program_image's serialisation (include/mlbp.h).  No GPU needed."""
+    def arr(a):
+        a = np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+        return a if len(a) else np.zeros(1, dtype=np.int32)
+    n_ops, n_srcs, n_sweeps = len(np.reshape(ops, (-1, 4))), len(srcs), len(np.reshape(sweeps, (-1, 2)))
+    ops, srcs, sweeps, in_off, in_slots = arr(ops), arr(srcs), arr(sweeps), arr(in_off), arr(in_slots)
+
+    def call(which, buf, cap):
+        return _ffi.check(_ffi.lib.mlbp_program_image(
+            _ffi.i32ptr(ops), n_ops, _ffi.i32ptr(srcs), n_srcs, _ffi.i32ptr(sweeps), n_sweeps, n_msgs, P, U, n_vars,
+            _ffi.i32ptr(in_off), _ffi.i32ptr(in_slots), which, _ffi.i32ptr(buf), cap))
+    out = {}
+    for which, name in enumerate(_ffi.IMAGES):
+        n = call(which, np.zeros(1, dtype=np.int32), 0)                # the word count first, then the words
+        buf = np.zeros(max(n, 1), dtype=np.int32)
+        call(which, buf, n)
+        out[name] = buf[:n]
+    return out
