@@ -770,7 +770,6 @@ bool contract_supports(int X) { return X > 64 && X <= 4096; }
 
 }  // namespace
 
-int gemm_path_ready() { return MLBP_OK; }          // hand-written: nothing to load
 bool gemm_path_supports(int X) { return contract_supports(X); }
 
 // workspace of the pairwise gradient: the four weighted fragment sets of one factor [4][XA][XA], the dot products [4][B]
@@ -823,7 +822,7 @@ int launch_gemm_pair_gradient(const mlbp_gradient_args* a, int32_t* status, void
   return launch_verdict("shared-table gradient");
 }
 
-int launch_gemm_sweep(const mlbp_program* prog, const mlbp_sweep_args* a, void* stream) {
+static int gemm_sweep(mlbp_program* prog, const mlbp_sweep_args* a, void* stream) {
   if (!a->pair_tab_host) return fail(MLBP_EINVAL, "shared-table contraction path: pair_tab_host (host int32 [P]) is required");
   if (prog->P > 16) return fail(MLBP_EUNSUPPORTED, "shared-table contraction path: at most 16 pairwise factors (got %d)", prog->P);
   if (!contract_supports(a->X)) return fail(MLBP_EUNSUPPORTED, "shared-table contraction path: X = %d", a->X);
@@ -841,13 +840,12 @@ int launch_gemm_sweep(const mlbp_program* prog, const mlbp_sweep_args* a, void* 
     return fail(MLBP_EUNSUPPORTED, "shared-table contraction path: float32 tables need X = 256 or 512");
   // fragment-ordered copies of the distinct tables, both orientations: [P][2][XA * XA] -- scratch the PROGRAM owns (calls with
   // different programs run on different streams; an outgrown block stays alive, so a captured graph stays valid)
-  mlbp_program* mp = const_cast<mlbp_program*>(prog);
-  if (int e = program_grow(mp, &mp->d_gfrag, &mp->gfrag_cap, (size_t)prog->P * 2 * XA * XA * elem)) return e;
-  void* frag = mp->d_gfrag;
+  if (int e = prog->d_gfrag.grow(prog, (size_t)prog->P * 2 * XA * XA * elem)) return e;
+  void* frag = prog->d_gfrag;
   double* xbuf = nullptr;
   if (sh.passes > 1) {                             // the chunked kernel parks a fused update's input message in memory
-    if (int e = program_grow(mp, &mp->d_gxbuf, &mp->gxbuf_cap, (size_t)B * X * sizeof(double))) return e;
-    xbuf = static_cast<double*>(mp->d_gxbuf);
+    if (int e = prog->d_gxbuf.grow(prog, (size_t)B * X * sizeof(double))) return e;
+    xbuf = reinterpret_cast<double*>(prog->d_gxbuf.p);
   }
   launch_begin();
   {
@@ -930,6 +928,17 @@ int launch_gemm_sweep(const mlbp_program* prog, const mlbp_sweep_args* a, void* 
     if (int e = f32 ? launch_contract<float>(d, X, 1, st) : launch_contract<double>(d, X, 1, st)) return e;
   }
   return launch_verdict("shared-table contraction path");
+}
+
+int launch_gemm_sweep(mlbp_program* prog, const mlbp_sweep_args* a, void* stream, bool* launched) {
+  *launched = false;
+  if (!(a->flags & MLBP_SWEEP_SHARED_PAIR_TABLES) || !a->pair_tab_host || !contract_supports(a->X) || (a->flags & MLBP_SWEEP_APPROX_INFERENCE) ||
+      prog->P < 1 || prog->P > 16)
+    return MLBP_OK;
+  const int e = gemm_sweep(prog, a, stream);
+  if (e == MLBP_EUNSUPPORTED) return MLBP_OK;     // unsupported shape: the per-graph kernels
+  *launched = e == MLBP_OK;
+  return e;
 }
 
 }  // namespace mlbp

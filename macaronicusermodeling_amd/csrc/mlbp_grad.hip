@@ -653,24 +653,8 @@ __global__ __launch_bounds__(64) void patch_gradient_kernel(const double* priv_t
   }
 }
 
-int32_t* g_status = nullptr;
-int status_word(int32_t** out) {
-  if (!g_status) {
-    HIP_TRY(hipMalloc(&g_status, sizeof(int32_t)));
-    HIP_TRY(hipMemset(g_status, 0, sizeof(int32_t)));
-  }
-  *out = g_status;
-  return MLBP_OK;
-}
-
-int need_device() {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-    (void)hipGetLastError();
-    return fail(MLBP_ENODEVICE, "no HIP device visible: libmlbp.so has no CPU fallback");
-  }
-  return MLBP_OK;
-}
+using mlbp::status_word;
+constexpr auto need_device = mlbp::check_device;
 
 }  // namespace
 
@@ -896,11 +880,7 @@ int mlbp_patch_gradient_f64(const double* priv_tables, const int32_t* item_off, 
 int mlbp_gradient_status(void) {
   // Synchronising read-and-reset: 1 when a gradient / belief kernel skipped a factor because a table,
   // label or observed-column index was out of range.
-  if (!g_status) return 0;
-  int32_t v = 0, zero = 0;
-  HIP_TRY(hipMemcpy(&v, g_status, sizeof(v), hipMemcpyDeviceToHost));
-  if (v) HIP_TRY(hipMemcpy(g_status, &zero, sizeof(zero), hipMemcpyHostToDevice));
-  return v;
+  return mlbp::status_word_read();
 }
 
 }  // extern "C"

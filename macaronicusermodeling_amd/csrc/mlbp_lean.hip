@@ -853,7 +853,7 @@ namespace mlbp {
 // Does the lean kernel apply to this (program, arguments) pair?  Fills the device-side descriptions when it does.
 // grad: the call's gradient is fused into the launch (the caller has checked that it can be); a gradient request without
 // it is served by the standalone kernel afterwards, from the messages in memory.
-static int lean_plan(const mlbp_program* prog, const mlbp_sweep_args* a, bool grad, bool* ok, SweepDev* d, LeanDev* f, size_t* lds) {
+static int lean_plan(mlbp_program* prog, const mlbp_sweep_args* a, bool grad, bool* ok, SweepDev* d, LeanDev* f, size_t* lds) {
   *ok = false;
   const LeanProgram& lp = prog->lean;
   if (!lp.ok || !prog->d_limage || a->X > 64 || a->X < 2 || !a->normalize_messages || prog->P < 1 || prog->P > 8) return MLBP_OK;
@@ -872,9 +872,8 @@ static int lean_plan(const mlbp_program* prog, const mlbp_sweep_args* a, bool gr
   const bool dense = (a->flags & MLBP_SWEEP_DENSE_TABLES) != 0;
   if (dense && ((int64_t)a->B * prog->P > a->n_pair_tables || (int64_t)a->B * prog->U > a->n_unary_tables))
     return fail(MLBP_EINVAL, "mlbp_sweep_f64: MLBP_SWEEP_DENSE_TABLES needs B*P pair tables and B*U unary columns");
-  mlbp_program* mp = const_cast<mlbp_program*>(prog);
-  if (mp->bail_cap < a->B)
-    if (int e = mlbp_program_reserve(mp, a->B)) return e;
+  if (prog->d_bail.bytes < (size_t)a->B)
+    if (int e = mlbp_program_reserve(prog, a->B)) return e;
   d->pair_tables = a->pair_tables; d->pair_tab = a->pair_tab;
   d->unary_tables = a->unary_tables; d->unary_tab = a->unary_tab;
   d->msgs = a->msgs;
@@ -884,7 +883,7 @@ static int lean_plan(const mlbp_program* prog, const mlbp_sweep_args* a, bool gr
   d->n_pair_tables = a->n_pair_tables; d->n_unary_tables = a->n_unary_tables;
   d->marginals = padx ? nullptr : a->marginals; d->readout = nullptr; d->n_vars = prog->n_vars;
   d->only = nullptr; d->fill_uniform = 0; d->approx_k = 0;
-  f->image = prog->d_limage; f->readout = (a->marginals && !padx) ? prog->d_lreadout : nullptr; f->bail = mp->d_bail;
+  f->image = prog->d_limage; f->readout = (a->marginals && !padx) ? prog->d_lreadout : nullptr; f->bail = prog->d_bail;
   f->n_bundles = lp.n_bundles; f->HL = lp.HL; f->n_cprod = lp.n_cprod; f->WL = lp.WL;
   f->n_ext = n_ext; f->init = a->init_messages; f->dense = dense ? 1 : 0;
   // the messages go back to memory unless the caller waives them and takes the fused read-outs instead (a gradient that
@@ -927,18 +926,20 @@ static lean_fn pick_lean_grad(int P) {
   }
 }
 
-int launch_lean_sweep(const mlbp_program* prog, const mlbp_sweep_args* a, const GradFusedDev* gf, void* stream, bool* launched) {
+int launch_lean_sweep(mlbp_program* prog, const mlbp_sweep_args* a, bool fuse_gradient, void* stream, bool* launched) {
   *launched = false;
   SweepDev d;
   LeanDev f;
   size_t lds = 0;
   bool ok = false;
-  if (int e = lean_plan(prog, a, gf != nullptr, &ok, &d, &f, &lds)) return e;
+  if (int e = lean_plan(prog, a, fuse_gradient, &ok, &d, &f, &lds)) return e;
   if (!ok) return MLBP_OK;
-  lean_fn k = gf ? pick_lean_grad(prog->P) : pick_lean<false>(prog->P, a->X < 64);
+  GradFusedDev gf = {};
+  if (fuse_gradient) fill_grad_fused(a->gradient, &gf);
+  lean_fn k = fuse_gradient ? pick_lean_grad(prog->P) : pick_lean<false>(prog->P, a->X < 64);
   if (int e = grant_lds((const void*)k, lds)) return e;
   launch_begin();
-  MLBP_LAUNCH(k, dim3(a->B), dim3(WG), lds, (hipStream_t)stream, d, f, nullptr, 0, gf ? *gf : GradFusedDev{});
+  MLBP_LAUNCH(k, dim3(a->B), dim3(WG), lds, (hipStream_t)stream, d, f, nullptr, 0, gf);
   if (int e = launch_verdict("lean sweep")) return e;
   *launched = true;
   return MLBP_OK;
@@ -949,7 +950,7 @@ int launch_lean_sweep(const mlbp_program* prog, const mlbp_sweep_args* a, const 
 // of them (none: nothing is launched).  The group table lives in a device buffer owned by the FIRST program of the call (like
 // its redo flags: one stream at a time per program) and is uploaded only when its contents differ from the last call's, so a
 // repeated call -- the trainer's every step -- is enqueue-only and can be captured into a HIP graph after one warm-up call.
-int launch_lean_groups(const mlbp_program* const* progs, const mlbp_sweep_args* args, int n_groups, void* stream, std::vector<char>& member) {
+int launch_lean_groups(mlbp_program* const* progs, const mlbp_sweep_args* args, int n_groups, void* stream, std::vector<char>& member) {
   std::vector<int32_t> table;
   size_t lds_max = 0;
   int p_max = 0, total = 0, n_in = 0;
@@ -983,9 +984,8 @@ int launch_lean_groups(const mlbp_program* const* progs, const mlbp_sweep_args* 
   }
   if (n_in == 0) return MLBP_OK;
   // one device copy per distinct table (stream-ordered upload on first sight, none afterwards): a captured graph keeps its own
-  mlbp_program* owner = const_cast<mlbp_program*>(progs[0]);
   int32_t* d_gtable = nullptr;
-  if (int e = group_table_device(owner->gtables, table, stream, &d_gtable)) return e;
+  if (int e = group_table_device(progs[0]->gtables, table, stream, &d_gtable)) return e;
   lean_fn k = pick_lean<true>(p_max, false);
   if (int e = grant_lds((const void*)k, lds_max)) return e;
   launch_begin();

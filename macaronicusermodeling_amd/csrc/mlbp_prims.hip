@@ -13,14 +13,7 @@ using mlbp::fail;
 
 namespace {
 
-int need_device() {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-    (void)hipGetLastError();
-    return fail(MLBP_ENODEVICE, "no HIP device visible: libmlbp.so has no CPU fallback");
-  }
-  return MLBP_OK;
-}
+constexpr auto need_device = mlbp::check_device;
 
 using mlbp_dev::wave_sum_xor;
 

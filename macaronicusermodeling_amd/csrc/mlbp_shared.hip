@@ -1789,7 +1789,7 @@ namespace {
 // What a shared-table sweep of (prog, a) needs: the two device descriptions, the LDS size, the grid sizes.  *ok false: the
 // kernel does not apply (mlbp_last_error says why).  Allocates the program's scratch on first use.
 struct SharedPlan { SharedDev d; PrepareDev q; size_t lds; int n_wg, n_prep_blocks; bool wide, spill, pf, p3; };
-int shared_plan(const mlbp_program* prog, const mlbp_sweep_args* a, bool* ok, SharedPlan* out, bool allow_p3 = true) {
+int shared_plan(mlbp_program* prog, const mlbp_sweep_args* a, bool* ok, SharedPlan* out, bool allow_p3 = true) {
   *ok = false;
   memset(out, 0, sizeof(*out));
   const SharedProgram& sp = prog->shared;
@@ -1820,38 +1820,37 @@ int shared_plan(const mlbp_program* prog, const mlbp_sweep_args* a, bool* ok, Sh
   if (n_res < 1 || (!p3 && sp.n_live - n_res > MAX_SPILLED_TILES) || lds > 160 * 1024)
     return fail(MLBP_OK, "shared-table kernel not used: %d live message tiles, %d fit LDS", sp.n_live, n_res);
   if (n_cprod < 1 || n_cprod > 8) return fail(MLBP_OK, "shared-table kernel not used: %d constant products (1..8)", n_cprod);
-  mlbp_program* mp = const_cast<mlbp_program*>(prog);
   const int n_groups = (a->B + G - 1) / G;
   // the product-fused form
   const bool pf = sp.pf_ok && n_res == sp.n_live && sp.max_sources <= 2 && (!a->marginals || prog->sreadout_all_based) && prog->n_vars <= 8;     // (the read-out stages 8 variables' rows in the spent tiles)
   const size_t spill_doubles = (pf || p3) ? (size_t)n_groups * sp.n_stash * TILE : (size_t)n_groups * (sp.n_live - n_res) * TILE;
   // (first use at this size allocates -- a stream-capturing caller warms up or reserves first; a block that is outgrown stays
-  // alive with the program: program_grow)
+  // alive with the program: DeviceArray::grow)
   if (spill_doubles > 0)
-    if (int e = program_grow(mp, reinterpret_cast<void**>(&mp->d_spill), &mp->spill_cap, spill_doubles * sizeof(double))) return e;
+    if (int e = prog->d_spill.grow(prog, spill_doubles * sizeof(double))) return e;
   const size_t ptile_doubles = (size_t)n_groups * n_cprod * TILE;
-  if (int e = program_grow(mp, reinterpret_cast<void**>(&mp->d_ptiles), &mp->ptiles_cap, ptile_doubles * sizeof(double))) return e;
-  if (int e = program_grow(mp, reinterpret_cast<void**>(&mp->d_header), &mp->header_cap, (size_t)n_groups * HDR * sizeof(int32_t))) return e;
-  if (mp->bail_cap < a->B)
-    if (int e = mlbp_program_reserve(mp, a->B)) return e;
+  if (int e = prog->d_ptiles.grow(prog, ptile_doubles * sizeof(double))) return e;
+  if (int e = prog->d_header.grow(prog, (size_t)n_groups * HDR * sizeof(int32_t))) return e;
+  if (prog->d_bail.bytes < (size_t)a->B)
+    if (int e = mlbp_program_reserve(prog, a->B)) return e;
   SharedDev& d = out->d;
   d.pair_tables = a->pair_tables; d.pair_tab = a->pair_tab; d.unary_tables = a->unary_tables; d.unary_tab = a->unary_tab;
   d.msgs = ((a->flags & MLBP_SWEEP_NO_MESSAGE_WRITEBACK) && !a->gradient) ? nullptr : a->msgs;
   d.vf_only = ((a->flags & MLBP_SWEEP_NO_MESSAGE_WRITEBACK) && a->gradient) ? 1 : 0;
-  d.marginals = a->marginals; d.status = prog->d_status; d.bail = mp->d_bail;
+  d.marginals = a->marginals; d.status = prog->d_status; d.bail = prog->d_bail;
   d.image = prog->d_simage; d.readout = prog->d_sreadout;
   d.B = a->B; d.n_msgs = prog->n_msgs; d.P = prog->P; d.U = prog->U;
   d.n_pair_tables = a->n_pair_tables; d.n_unary_tables = a->n_unary_tables; d.n_vars = prog->n_vars;
   d.n_bundles = sp.n_bundles; d.n_live = p3 ? sp.n_lds : sp.n_live; d.n_cprod = n_cprod; d.n_back = sp.n_back;
   d.n_fill = sp.n_fill; d.n_init = sp.n_init;
   d.off_back = sp.off_back; d.off_fill = sp.off_fill; d.off_init = sp.off_init; d.off_ptile = sp.off_ptile;
-  d.ptiles = mp->d_ptiles;
-  d.n_res = n_res; d.spill = (!p3 && n_res < sp.n_live) ? mp->d_spill : nullptr;
+  d.ptiles = prog->d_ptiles;
+  d.n_res = n_res; d.spill = (!p3 && n_res < sp.n_live) ? prog->d_spill : nullptr;
   d.off_map3 = sp.off_map3; d.off_kind3 = sp.off_kind3; d.off_back3 = sp.off_back3; d.sqrt_mask = p3 ? sp.sqrt_mask : 0;
   d.off_written = sp.off_written;
   d.off_pfb = sp.off_pfb; d.off_stash = sp.off_stash; d.off_pinit = sp.off_pinit; d.n_pinit = sp.n_pinit; d.n_stash = sp.n_stash;
-  d.stash = (pf || p3) ? mp->d_spill : nullptr;
-  d.header = mp->d_header;
+  d.stash = (pf || p3) ? prog->d_spill : nullptr;
+  d.header = prog->d_header;
   d.off_vftile = sp.off_vftile;
   d.vf_direct = 0;                                 // (set below when the gradient is this launch's epilogue)
   // the product-fused form takes the whole half of the CU's LDS: the spare bytes behind the totals are the gradient epilogue's
@@ -1860,30 +1859,28 @@ int shared_plan(const mlbp_program* prog, const mlbp_sweep_args* a, bool* ok, Sh
   out->pf = pf; out->p3 = p3;
   d.tfrag = nullptr;
   if (a->n_pair_tables <= FRAG_TABLES) {
-    if (!mp->d_tfrag) {                            // first use (a stream-capturing caller warms up or reserves first)
-      if (hipMalloc(&mp->d_tfrag, sizeof(double) * FRAG_TABLES * 2 * 4096) != hipSuccess)
-        return fail(MLBP_EHIP, "fragment scratch allocation failed");
-    }
-    d.tfrag = mp->d_tfrag;
+    // (allocated on first use: a stream-capturing caller warms up or reserves first)
+    if (int e = prog->d_tfrag.grow(prog, sizeof(double) * FRAG_TABLES * 2 * 4096)) return e;
+    d.tfrag = prog->d_tfrag;
   }
   // one launch in front of the sweeps: constant products as tiles, the per-graph flags (cleared or raised), table fragments
   PrepareDev& q = out->q;
-  q.pair_tables = a->pair_tables; q.tfrag = d.tfrag ? mp->d_tfrag : nullptr; q.n_frag_tables = d.tfrag ? a->n_pair_tables : 0;
+  q.pair_tables = a->pair_tables; q.tfrag = d.tfrag ? prog->d_tfrag : nullptr; q.n_frag_tables = d.tfrag ? a->n_pair_tables : 0;
   q.unary_tables = a->unary_tables; q.unary_tab = a->unary_tab; q.ent = prog->d_simage + sp.off_ent;
-  q.ptiles = mp->d_ptiles; q.bail = mp->d_bail; q.status = prog->d_status;
+  q.ptiles = prog->d_ptiles; q.bail = prog->d_bail; q.status = prog->d_status;
   q.B = a->B; q.U = prog->U; q.n_unary_tables = a->n_unary_tables; q.E = sp.n_cpw / 4; q.n_cprod = n_cprod; q.n_groups = n_groups;
-  q.pair_tab = a->pair_tab; q.image = prog->d_simage; q.header = mp->d_header; q.P = prog->P; q.n_pair_tables = a->n_pair_tables; q.n_bundles = sp.n_bundles;
+  q.pair_tab = a->pair_tab; q.image = prog->d_simage; q.header = prog->d_header; q.P = prog->P; q.n_pair_tables = a->n_pair_tables; q.n_bundles = sp.n_bundles;
   q.sqrt_mask = p3 ? sp.sqrt_mask : 0;
   // the gradient as the sweep kernel's epilogue (the prepare launch also writes its weighted table fragments)
   if (shared_gradient_fused(prog, a)) {
     const mlbp_gradient_args* ga = a->gradient;
     const size_t need = (size_t)a->n_pair_tables * 8 * 4096 + 8;      // + the eight plane flags (as doubles' worth of bytes)
-    if (int e = program_grow(mp, reinterpret_cast<void**>(&mp->d_wfrag), &mp->wfrag_cap, need * sizeof(double))) return e;
-    q.n_wfrag_tables = a->n_pair_tables; q.wfrag = mp->d_wfrag; q.phi_p0 = ga->phi_en_en_p; q.phi_p1 = ga->phi_en_en_w1_p;
-    q.plane_flags = reinterpret_cast<int32_t*>(mp->d_wfrag + (size_t)a->n_pair_tables * 8 * 4096);
+    if (int e = prog->d_wfrag.grow(prog, need * sizeof(double))) return e;
+    q.n_wfrag_tables = a->n_pair_tables; q.wfrag = prog->d_wfrag; q.phi_p0 = ga->phi_en_en_p; q.phi_p1 = ga->phi_en_en_w1_p;
+    q.plane_flags = reinterpret_cast<int32_t*>(prog->d_wfrag + (size_t)a->n_pair_tables * 8 * 4096);
     SharedGradDev& gr = d.gr;
     gr.c_slot = ga->pair_c_slot; gr.r_slot = ga->pair_r_slot; gr.pair_phi = ga->pair_phi; gr.pair_label = ga->pair_label;
-    gr.phi[0] = ga->phi_en_en; gr.phi[1] = ga->phi_en_en_w1; gr.wfrag = mp->d_wfrag; gr.plane_flags = q.plane_flags;
+    gr.phi[0] = ga->phi_en_en; gr.phi[1] = ga->phi_en_en_w1; gr.wfrag = prog->d_wfrag; gr.plane_flags = q.plane_flags;
     gr.grad_en_en = ga->grad_en_en; gr.enabled = 1;
     q.unary_expect = prog->U > 0 ? ga->unary_expect : nullptr;
     q.unary_kind = ga->unary_kind; q.unary_obs = ga->unary_obs; q.unary_label = ga->unary_label;
@@ -1913,7 +1910,7 @@ int enqueue_unary_writeback(const mlbp_program* prog, const mlbp_sweep_args* a, 
 
 }  // namespace
 
-int launch_shared_sweep(const mlbp_program* prog, const mlbp_sweep_args* a, void* stream, bool* launched) {
+int launch_shared_sweep(mlbp_program* prog, const mlbp_sweep_args* a, void* stream, bool* launched) {
   *launched = false;
   SharedPlan pl;
   bool ok = false;
@@ -1938,7 +1935,7 @@ int launch_shared_sweep(const mlbp_program* prog, const mlbp_sweep_args* a, void
 // groups offered (distinct programs); out, the groups the sequence runs -- those shared_plan accepts, and the pairwise-free ones
 // that ride along -- or none when no group with pairwise factors qualifies.  The group tables live in a device buffer owned by
 // the first program of the call and are uploaded only when their contents change (like the lean kernel's).
-int launch_shared_groups(const mlbp_program* const* progs, const mlbp_sweep_args* args, int n_groups, void* stream, std::vector<char>& member) {
+int launch_shared_groups(mlbp_program* const* progs, const mlbp_sweep_args* args, int n_groups, void* stream, std::vector<char>& member) {
   std::vector<SharedPlan> plans(n_groups);
   int max_cprod = 1, n_planned = 0;
   for (int k = 0; k < n_groups; ++k) {
@@ -1964,8 +1961,8 @@ int launch_shared_groups(const mlbp_program* const* progs, const mlbp_sweep_args
   }
   for (int k = 0; k < n_groups; ++k)
     if (member[k] && progs[k]->P == 0) {
-      mlbp_program* mp = const_cast<mlbp_program*>(progs[k]);
-      if (mp->bail_cap < args[k].B)
+      mlbp_program* mp = progs[k];
+      if (mp->d_bail.bytes < (size_t)args[k].B)
         if (int e = mlbp_program_reserve(mp, args[k].B)) return e;
       if (hipMemsetAsync(mp->d_bail, 1, (size_t)args[k].B, (hipStream_t)stream) != hipSuccess) return fail(MLBP_EHIP, "flagging a pairwise-free group failed");
     }
@@ -2029,7 +2026,7 @@ int launch_shared_groups(const mlbp_program* const* progs, const mlbp_sweep_args
     sstarts[first[c + 1] + c] = wg;
     grid[c] = wg;
   }
-  mlbp_program* owner = const_cast<mlbp_program*>(progs[0]);
+  mlbp_program* owner = progs[0];
   hipStream_t st = (hipStream_t)stream;
   int32_t* d_stable = nullptr;               // one device copy per distinct table: a captured graph keeps replaying against its own
   if (int e = group_table_device(owner->stables, table, stream, &d_stable)) return e;

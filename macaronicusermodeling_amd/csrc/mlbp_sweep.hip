@@ -16,15 +16,9 @@
 // Algorithmic HBM bytes per pairwise update: (X*X + 2X) * 8.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #include <algorithm>
-#include <cfloat>
-#include <cstdlib>
+#include <atomic>
 #include <cstring>
-#include <mutex>
-#include <utility>
-#include <map>
 #include <vector>
 
 #include "mlbp_internal.h"
@@ -1032,11 +1026,6 @@ __global__ __launch_bounds__(LP_WG) void log_posterior_groups_kernel(const mlbp_
   out[i] = total;
 }
 
-// mlbp_set_sweep_variant: 1 = the fast kernels with the exact kernel as fix-up (default), 3 = the exact / per-graph
-// kernels on every graph (the tests' reference on the same inputs).
-int g_sweep_variant = 1;
-thread_local int g_last_kernel = -1;       // mlbp_last_sweep_kernel()
-thread_local int g_last_fused_gradient = 0; // mlbp_last_sweep_fused_gradient()
 }  // namespace
 
 namespace mlbp {
@@ -1050,224 +1039,20 @@ bool exact_kernel_fuses_gradient(const mlbp_program* prog, const mlbp_sweep_args
   return ga->F_ee == 3 && ga->F_ed == 6 && prog->P >= 0 && prog->P <= 3 && prog->n_hoist == prog->U && prog->U <= WG &&
          ga->phi_en_en_t && ga->phi_en_en_w1_t && ga->phi_en_de_t && !(ga->flags & MLBP_GRADIENT_APPROX_BELIEFS);
 }
+
+void fill_grad_fused(const mlbp_gradient_args* ga, GradFusedDev* gf) {
+  *gf = GradFusedDev{};
+  gf->pair_c_slot = ga->pair_c_slot; gf->pair_r_slot = ga->pair_r_slot; gf->pair_phi = ga->pair_phi; gf->pair_label = ga->pair_label;
+  gf->unary_kind = ga->unary_kind; gf->unary_obs = ga->unary_obs; gf->unary_label = ga->unary_label;
+  gf->phi_en_en = ga->phi_en_en; gf->phi_en_en_w1 = ga->phi_en_en_w1;
+  gf->phi_en_en_t = ga->phi_en_en_t; gf->phi_en_en_w1_t = ga->phi_en_en_w1_t; gf->phi_en_de_t = ga->phi_en_de_t;
+  gf->grad_en_en = ga->grad_en_en; gf->grad_en_de = ga->grad_en_de; gf->Vde = ga->Vde; gf->enabled = 1;
+}
 }  // namespace mlbp
-
-namespace {
-int check_device() {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-    (void)hipGetLastError();
-    return fail(MLBP_ENODEVICE, "no HIP device visible: libmlbp.so has no CPU fallback");
-  }
-  return MLBP_OK;
-}
-
-// status words for the kernels that have no program attached
-int32_t* g_status = nullptr;
-int global_status(int32_t** out) {
-  if (!g_status) {
-    HIP_TRY(hipMalloc(&g_status, sizeof(int32_t)));
-    HIP_TRY(hipMemset(g_status, 0, sizeof(int32_t)));
-  }
-  *out = g_status;
-  return MLBP_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int mlbp_device_count(void) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess) {
-    (void)hipGetLastError();
-    return 0;
-  }
-  return n;
-}
-
-static int create_program(const int32_t* ops, int32_t n_ops, const int32_t* srcs, int32_t n_srcs,
-                          const int32_t* sweeps, int32_t n_sweeps, int32_t n_msgs, int32_t P, int32_t U,
-                          mlbp_program** out, bool with_pruned);
-
-int mlbp_program_create(const int32_t* ops, int32_t n_ops, const int32_t* srcs, int32_t n_srcs,
-                        const int32_t* sweeps, int32_t n_sweeps, int32_t n_msgs, int32_t P, int32_t U,
-                        mlbp_program** out) {
-  return create_program(ops, n_ops, srcs, n_srcs, sweeps, n_sweeps, n_msgs, P, U, out, true);
-}
-
-static int create_program(const int32_t* ops, int32_t n_ops, const int32_t* srcs, int32_t n_srcs,
-                          const int32_t* sweeps, int32_t n_sweeps, int32_t n_msgs, int32_t P, int32_t U,
-                          mlbp_program** out, bool with_pruned) {
-  if (!out) return fail(MLBP_EINVAL, "out is NULL");
-  *out = nullptr;
-  int max_srcs = 0;
-  if (int e = mlbp::validate_program(ops, n_ops, srcs, n_srcs, sweeps, n_sweeps, n_msgs, P, U, &max_srcs)) return e;
-  std::vector<int32_t> pairseq;
-  for (int s = 0; s < n_sweeps; ++s) {
-    const int first = sweeps[2 * s], cnt = sweeps[2 * s + 1];
-    for (int o = first; o < first + cnt; ++o)
-      if (ops[4 * o] == MLBP_OP_PAIR_TM || ops[4 * o] == MLBP_OP_PAIR_MT) pairseq.push_back(ops[4 * o + 1]);
-  }
-  if (int e = check_device()) return e;
-  mlbp_program* p = new mlbp_program();
-  p->n_ops = n_ops; p->n_srcs = n_srcs; p->n_sweeps = n_sweeps; p->n_msgs = n_msgs; p->P = P; p->U = U;
-  p->n_pairseq = (int)pairseq.size();
-  p->max_srcs = max_srcs;
-  pairseq.push_back(-1);
-  p->d_ops = p->d_srcs = p->d_sweeps = p->d_pairseq = p->d_status = nullptr;
-  p->d_fops = p->d_fsweeps = p->d_fpairseq = nullptr;
-  (void)hipGetDevice(&p->device);
-  auto up = [&](int32_t** dst, const int32_t* src, size_t n) -> hipError_t {
-    hipError_t e = hipMalloc(dst, (n ? n : 1) * sizeof(int32_t));
-    if (e != hipSuccess) return e;
-    return n ? hipMemcpy(*dst, src, n * sizeof(int32_t), hipMemcpyHostToDevice) : hipSuccess;
-  };
-  hipError_t e = up(&p->d_ops, ops, (size_t)n_ops * 4);
-  std::vector<int32_t> srcs_padded(srcs ? srcs : nullptr, srcs ? srcs + n_srcs : nullptr);
-  srcs_padded.resize(((size_t)n_srcs + 16 + 3) / 4 * 4, 0);   // the fused kernel reads sources 16 at a time
-  if (e == hipSuccess) e = up(&p->d_srcs, srcs_padded.data(), srcs_padded.size());
-  if (e == hipSuccess) e = up(&p->d_sweeps, sweeps, (size_t)n_sweeps * 2);
-  if (e == hipSuccess) e = up(&p->d_pairseq, pairseq.data(), pairseq.size());
-  int32_t zero = 0;
-  if (e == hipSuccess) e = up(&p->d_status, &zero, 1);
-  mlbp::FusedProgram fp;
-  mlbp::build_fused_program(ops, srcs, sweeps, n_sweeps, n_msgs, fp);
-  p->n_fops = (int)fp.fops.size() / 8;
-  p->n_hoist = (int)fp.hoist.size() / 2;
-  p->n_psrcs = (int)fp.psrcs.size();
-  p->n_cprod = fp.n_cprod;
-  p->n_cpw = (int)fp.cpw.size();
-  std::vector<int32_t> image(fp.fops);
-  image.insert(image.end(), fp.psrcs.begin(), fp.psrcs.end());
-  image.insert(image.end(), fp.hoist.begin(), fp.hoist.end());
-  image.insert(image.end(), fp.cpw.begin(), fp.cpw.end());
-  image.insert(image.end(), fp.written.begin(), fp.written.end());
-  p->n_written = (int)fp.written.size();
-  p->sf_ok = !fp.has_unary_fops;
-  p->d_bail = nullptr;
-  p->bail_cap = 0;
-  p->d_readout = nullptr;
-  p->n_vars = 0;
-  p->n_readout = 0;
-  p->d_simage = p->d_sreadout = nullptr;
-  p->d_tfrag = nullptr;
-  p->h_ops.assign(ops, ops + 4 * (size_t)n_ops);
-  p->h_sweeps.assign(sweeps, sweeps + 2 * (size_t)n_sweeps);
-  p->n_sreadout = 0;
-  mlbp::build_shared_program(fp, n_msgs, P, U, p->shared);
-  if (p->shared.ok && e == hipSuccess) e = up(&p->d_simage, p->shared.image.data(), p->shared.image.size());
-  p->fused = fp;
-  mlbp::build_lean_program(fp, n_msgs, p->lean);
-  if (p->lean.ok && e == hipSuccess) e = up(&p->d_limage, p->lean.image.data(), p->lean.image.size());
-  if (e == hipSuccess) e = up(&p->d_fops, image.data(), image.size());
-  if (e == hipSuccess) e = up(&p->d_fsweeps, fp.fsweeps.data(), fp.fsweeps.size());
-  if (e == hipSuccess) e = up(&p->d_fpairseq, fp.pairseq.data(), fp.pairseq.size());
-  if (e != hipSuccess) {
-    mlbp_program_destroy(p);
-    return fail(MLBP_EHIP, "mlbp_program_create: device upload failed: %s", hipGetErrorString(e));
-  }
-  if (with_pruned) {
-    std::vector<int32_t> ops2, sweeps2;
-    p->n_dropped = mlbp::drop_unchanged_updates(ops, srcs, sweeps, n_sweeps, n_msgs, ops2, sweeps2);
-    if (p->n_dropped > 0) {
-      if (int rc = create_program(ops2.data(), (int)ops2.size() / 4, srcs, n_srcs, sweeps2.data(), n_sweeps, n_msgs, P, U, &p->pruned, false)) {
-        mlbp_program_destroy(p);
-        return rc;
-      }
-      p->pruned->is_twin = true;
-    }
-  }
-  *out = p;
-  return MLBP_OK;
-}
-
-// the program a call runs: the pruned twin under MLBP_SWEEP_SKIP_UNCHANGED (a fused gradient reads the final messages and
-// the resident tables only, so it follows either list)
-static const mlbp_program* effective_program(const mlbp_program* p, const mlbp_sweep_args* a) {
-  const bool pruned = p && a && (a->flags & MLBP_SWEEP_SKIP_UNCHANGED) && p->pruned;
-  if (p && a && !p->is_twin) const_cast<mlbp_program*>(p)->last_was_pruned = pruned;
-  return pruned ? p->pruned : p;
-}
-
-int mlbp_program_destroy(mlbp_program* p) {
-  if (!p) return MLBP_OK;
-  if (p->pruned) (void)mlbp_program_destroy(p->pruned);
-  (void)hipFree(p->d_ops); (void)hipFree(p->d_srcs); (void)hipFree(p->d_sweeps);
-  (void)hipFree(p->d_pairseq); (void)hipFree(p->d_status);
-  (void)hipFree(p->d_fops); (void)hipFree(p->d_fsweeps); (void)hipFree(p->d_fpairseq); (void)hipFree(p->d_bail); (void)hipFree(p->d_readout);
-  (void)hipFree(p->d_limage); (void)hipFree(p->d_lreadout); (void)hipFree(p->d_simage); (void)hipFree(p->d_sreadout); (void)hipFree(p->d_tfrag); (void)hipFree(p->d_spill); (void)hipFree(p->d_ptiles); (void)hipFree(p->d_wfrag); (void)hipFree(p->d_header);
-  if (p->side_stream) (void)hipStreamDestroy((hipStream_t)p->side_stream);
-  if (p->ev_fork) (void)hipEventDestroy((hipEvent_t)p->ev_fork);
-  if (p->ev_join) (void)hipEventDestroy((hipEvent_t)p->ev_join);
-  (void)hipFree(p->d_gfrag); (void)hipFree(p->d_gxbuf); (void)hipFree(p->d_gwork);
-  for (void* q : p->retired) (void)hipFree(q);
-  mlbp::group_tables_free(p->gtables); mlbp::group_tables_free(p->stables);
-  delete p;
-  return MLBP_OK;
-}
-
-// mlbp_gradient_f64 behind the sweeps of a call: a gradient that was given no workspace gets scratch the PROGRAM owns
-// (grown by new blocks only), so that the call is safe on its own stream and inside a captured graph
-static int gradient_behind_sweeps(const mlbp_program* prog, const mlbp_gradient_args* ga, void* stream) {
-  mlbp_gradient_args g = *ga;
-  if (!g.workspace) {
-    const int64_t need = mlbp_gradient_workspace_bytes(&g);
-    if (need > 0) {
-      mlbp_program* mp = const_cast<mlbp_program*>(prog);
-      if (int e = mlbp::program_grow(mp, &mp->d_gwork, &mp->gwork_cap, (size_t)need)) return e;
-      g.workspace = mp->d_gwork;
-      g.workspace_bytes = (int64_t)mp->gwork_cap;
-    }
-  }
-  return mlbp_gradient_f64(&g, stream);
-}
 
 static unsigned next_lp_generation() {
   static std::atomic<unsigned> generation{0};
   return generation.fetch_add(1u) + 1u;
-}
-
-// mlbp_sweep_args.posterior by its own launch (no fix-up pass took it)
-static int posterior_behind_sweeps(const mlbp_program* prog, const mlbp_sweep_args* a, void* stream) {
-  const mlbp_posterior_args* pa = a->posterior;
-  if (!pa) return MLBP_OK;
-  return mlbp_log_posterior_sum_f64(a->marginals, pa->labels, a->B, prog->n_vars, a->X, pa->out, pa->sum_out, stream);
-}
-
-// Every argument check of a sweep call of (prog, a), prog the program the call runs, made before anything is enqueued.  A
-// grouped call makes them on all its groups first: one bad group fails it with the single call's message and launches nothing.
-static int check_sweep_args(const mlbp_program* prog, const mlbp_sweep_args* a) {
-  if (a->B <= 0 || a->X <= 0) return fail(MLBP_EINVAL, "mlbp_sweep_f64: B=%d X=%d", a->B, a->X);
-  if (!a->msgs) return fail(MLBP_EINVAL, "mlbp_sweep_f64: msgs is NULL");
-  const bool f32_tables = (a->flags & MLBP_SWEEP_PAIR_TABLES_F32) != 0;
-  if (prog->P > 0 && (!(f32_tables ? (const void*)a->pair_tables_f32 : (const void*)a->pair_tables) || !a->pair_tab || a->n_pair_tables <= 0))
-    return fail(MLBP_EINVAL, "mlbp_sweep_f64: program has %d pairwise factors but no pair tables", prog->P);
-  if (prog->U > 0 && (!a->unary_tables || !a->unary_tab || a->n_unary_tables <= 0))
-    return fail(MLBP_EINVAL, "mlbp_sweep_f64: program has %d unary factors but no unary tables", prog->U);
-  if (a->X > 4096) return fail(MLBP_EUNSUPPORTED, "mlbp_sweep_f64: X=%d > 4096", a->X);
-  const bool approx = (a->flags & MLBP_SWEEP_APPROX_INFERENCE) != 0;
-  if (approx && a->X < MLBP_APPROX_K)      // np.argpartition(-vec, K - 1) in the reference: "kth(=99) out of bounds"
-    return fail(MLBP_EINVAL, "mlbp_sweep_f64: approximate inference keeps the %d largest entries; kth(=%d) out of bounds (%d)",
-                MLBP_APPROX_K, MLBP_APPROX_K - 1, a->X);
-  if (approx && !(a->X > 64 && a->X <= 1024 && a->normalize_messages && !f32_tables))
-    return fail(MLBP_EUNSUPPORTED, "mlbp_sweep_f64: batched approximate inference needs 100 <= X <= 1024, normalised messages, float64 tables");
-  if (f32_tables && !(a->X == 256 || a->X == 512))
-    return fail(MLBP_EUNSUPPORTED, "mlbp_sweep_f64: float32 pairwise tables need X = 256 or 512 (got %d)", a->X);
-  if (f32_tables && a->gradient) return fail(MLBP_EUNSUPPORTED, "mlbp_sweep_f64: no gradient with float32 pairwise tables");
-  if (int e = check_device()) return e;
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess || dev != prog->device)
-    return fail(MLBP_EINVAL, "mlbp_sweep_f64: the program was created on device %d, the calling thread's current device is %d",
-                prog->device, dev);
-  if (a->marginals && !prog->d_readout)
-    return fail(MLBP_EINVAL, "mlbp_sweep_f64: marginals requested but mlbp_program_set_readout was not called");
-  if (a->posterior && (!a->marginals || !a->posterior->labels || !a->posterior->out))
-    return fail(MLBP_EINVAL, "mlbp_sweep_f64: posterior needs marginals, labels and an output array");
-  const mlbp_gradient_args* ga = a->gradient;
-  if (ga && (ga->B != a->B || ga->X != a->X || ga->P != prog->P || ga->U != prog->U || ga->n_msgs != prog->n_msgs || ga->msgs != a->msgs))
-    return fail(MLBP_EINVAL, "mlbp_sweep_f64: gradient arguments do not describe the same batch");
-  return MLBP_OK;
 }
 
 // The per-graph kernels' description of (prog, a): the op list as given, no fused read-out, every graph.  Filled in place over
@@ -1282,10 +1067,16 @@ static void fill_sweep_dev(const mlbp_program* prog, const mlbp_sweep_args* a, S
   d->readout = prog->d_readout; d->n_vars = prog->n_vars;
 }
 
+// LDS bytes of the exact X = 64 kernel on prog's graphs: above X64_LDS_MAX it does not apply.
+constexpr size_t X64_LDS_MAX = 160 * 1024;
+static size_t exact_x64_lds(const mlbp_program* prog) {
+  const size_t img_words = (size_t)prog->n_fops * 8 + prog->n_psrcs + 2 * prog->n_hoist + prog->n_cpw + prog->n_written;
+  return ((size_t)(prog->n_msgs + 1 + prog->n_cprod) * 64 + 64 + 512) * sizeof(double) + (img_words + prog->P + 6 * prog->U + 8) * sizeof(int32_t);
+}
+
 // The exact X = 64 kernel's description of (prog, a) -- the fused program, the marginals as its epilogue when the messages are
 // normalised -- for every graph and without a posterior (G->f.only, G->f.post and the grouped launch's block fields are the
-// caller's).  Returns the kernel's LDS bytes: above X64_LDS_MAX it does not apply.
-constexpr size_t X64_LDS_MAX = 160 * 1024;
+// caller's).  Returns the kernel's LDS bytes.
 static size_t fill_fixup_group(const mlbp_program* prog, const mlbp_sweep_args* a, FixupGroup* G) {
   memset(G, 0, sizeof(*G));
   fill_sweep_dev(prog, a, &G->d);
@@ -1295,483 +1086,154 @@ static size_t fill_fixup_group(const mlbp_program* prog, const mlbp_sweep_args* 
   f.image = prog->d_fops; f.fsweeps = prog->d_fsweeps;
   f.n_fops = prog->n_fops; f.n_psrcs = prog->n_psrcs; f.n_hoist = prog->n_hoist; f.n_cprod = prog->n_cprod; f.n_cpw = prog->n_cpw;
   f.n_ext = 1 + prog->n_cprod; f.init = a->init_messages; f.n_graphs = a->B;
-  const size_t img_words = (size_t)prog->n_fops * 8 + prog->n_psrcs + 2 * prog->n_hoist + prog->n_cpw + prog->n_written;
-  return ((size_t)(prog->n_msgs + f.n_ext) * 64 + 64 + 512) * sizeof(double) + (img_words + prog->P + 6 * prog->U + 8) * sizeof(int32_t);
+  return exact_x64_lds(prog);
 }
 
-// What follows the sweep kernels of a call and was not fused into them, in this order: the marginals, the gradient (behind a
-// shared-table epilogue: the flagged graphs' only), the posterior.
-struct SweepTail {
-  bool marginals = true;       // false: the sweep kernels wrote them
-  bool grad_done = false;      // the sweep kernels ran the gradient as their epilogue
-  bool grad_flagged = false;   // ... on every graph but the flagged ones
-  bool post_done = false;      // the fix-up pass took the posterior
-};
-static int sweep_tail(const mlbp_program* prog, const mlbp_sweep_args* a, const SweepTail& t, void* stream) {
-  if (a->marginals && t.marginals)
-    if (int e = mlbp_marginals_f64(a->msgs, a->B, prog->n_msgs, a->X, prog->n_vars, prog->d_readout, prog->d_readout + prog->n_vars + 1,
-                                   a->normalize_messages ? 1 : 0, a->marginals, stream)) return e;
-  if (a->gradient && !t.grad_done)
-    if (int e = t.grad_flagged ? mlbp::gradient_flagged_only(a->gradient, prog->d_bail, stream) : gradient_behind_sweeps(prog, a->gradient, stream))
-      return e;
-  return t.post_done ? MLBP_OK : posterior_behind_sweeps(prog, a, stream);
-}
+namespace mlbp {
 
-// The fast pass a grouped launch has already run over a group's graphs, leaving the flagged ones to the exact kernel.
-enum FastPass { FAST_NONE, FAST_LEAN, FAST_SHARED };
+bool exact_x64_applies(const mlbp_program* prog, const mlbp_sweep_args* a) { return a->X == 64 && exact_x64_lds(prog) <= X64_LDS_MAX; }
 
-// One sweep call of (prog, a) -- checked; prog the program it runs -- behind `pass` (FAST_NONE: the call runs its own).
-// variant: mlbp_set_sweep_variant's, read once per public call.
-static int run_sweep(const mlbp_program* prog, const mlbp_sweep_args* a, FastPass pass, int variant, void* stream) {
-  g_last_fused_gradient = 0;
-  hipStream_t st = (hipStream_t)stream;
+int launch_exact_x64(mlbp_program* prog, const mlbp_sweep_args* a, bool flagged_only, bool fuse_gradient, void* stream, bool* post_done) {
   const bool norm = a->normalize_messages != 0;
   FixupGroup G;
   const size_t lds = fill_fixup_group(prog, a, &G);
-  if (a->X == 64 && lds <= X64_LDS_MAX) {
-    mlbp_program* mp = const_cast<mlbp_program*>(prog);
-    const bool fast = variant == 1;               // variant 3: the exact kernel on every graph
-    if (pass == FAST_NONE && fast) {              // shared-table batches: 16 graphs per workgroup on the matrix cores
-      bool launched = false;
-      if (int e = mlbp::launch_shared_sweep(prog, a, stream, &launched)) return e;
-      if (launched) pass = FAST_SHARED;
-    }
-    // The gradient runs as the sweep kernels' epilogue when the tables are on chip in BOTH the fast and the exact kernel (a grouped
-    // lean launch runs none).  Behind the shared-table kernel's epilogue the fix-up pass keeps its own for the graphs it redoes --
-    // or, with more than three pairwise factors, where the exact kernel streams its tables and has no epilogue, the per-graph
-    // gradient kernel follows on the flagged graphs only.
-    const bool exact_grad = mlbp::exact_kernel_fuses_gradient(prog, a) && pass != FAST_LEAN;
-    const bool shared_grad = pass == FAST_SHARED && mlbp::shared_gradient_fused(prog, a);
-    SweepTail tail;
-    tail.marginals = !norm;                       // (normalised: the read-out is the kernels' epilogue)
-    tail.grad_done = exact_grad && (pass != FAST_SHARED || shared_grad);
-    tail.grad_flagged = shared_grad && !exact_grad;
-    GradFusedDev gf = {};
-    if (tail.grad_done) {
-      const mlbp_gradient_args* ga = a->gradient;
-      gf.pair_c_slot = ga->pair_c_slot; gf.pair_r_slot = ga->pair_r_slot; gf.pair_phi = ga->pair_phi; gf.pair_label = ga->pair_label;
-      gf.unary_kind = ga->unary_kind; gf.unary_obs = ga->unary_obs; gf.unary_label = ga->unary_label;
-      gf.phi_en_en = ga->phi_en_en; gf.phi_en_en_w1 = ga->phi_en_en_w1;
-      gf.phi_en_en_t = ga->phi_en_en_t; gf.phi_en_en_w1_t = ga->phi_en_en_w1_t; gf.phi_en_de_t = ga->phi_en_de_t;
-      gf.grad_en_en = ga->grad_en_en; gf.grad_en_de = ga->grad_en_de; gf.Vde = ga->Vde; gf.enabled = 1;
-    }
-    // default path: the lean scale-free kernel (mlbp_lean.hip), up to 8 resident tables
-    if (pass == FAST_NONE && fast && norm && prog->sf_ok && prog->P >= 1 && prog->P <= 8) {
-      bool launched = false;
-      if (int e = mlbp::launch_lean_sweep(prog, a, tail.grad_done ? &gf : nullptr, stream, &launched)) return e;
-      if (launched) pass = FAST_LEAN;
-    }
-    g_last_kernel = pass == FAST_SHARED ? MLBP_KERNEL_SHARED_MFMA : (pass == FAST_LEAN ? MLBP_KERNEL_LEAN : MLBP_KERNEL_EXACT);
-    g_last_fused_gradient = (tail.grad_done || tail.grad_flagged) ? 1 : 0;
-    FusedDev& f = G.f;
-    f.only = pass != FAST_NONE ? mp->d_bail : nullptr;     // after a fast pass: flagged graphs only
-    // get_posterior_probs of the call: taken by the fix-up pass (it visits every graph's flag anyway); without a fix-up pass
-    // -- the exact kernel on every graph -- by its own launch behind the sweeps
-    const mlbp_posterior_args* pa = a->posterior;
-    tail.post_done = pa && f.only && norm && (a->B + FIXUP_GRAPHS_PER_WG - 1) / FIXUP_GRAPHS_PER_WG <= LP_MAX_BLOCKS;
-    if (tail.post_done) {
-      f.post.labels = pa->labels; f.post.out = pa->out; f.post.sum_out = pa->sum_out;
-      f.post.generation = pa->sum_out ? next_lp_generation() : 0u;
-    }
-    // the exact kernel keeps the tables in registers when the graph has at most 3 of them, else it streams them
-    const int nt = (prog->P >= 1 && prog->P <= 3) ? prog->P : 0;
-    void (*k)(SweepDev, FusedDev, GradFusedDev) = nullptr;
-#define MLBP_PICK(N) k = tail.grad_done ? sweep_x64_fused_kernel<true, N, true> : (norm ? sweep_x64_fused_kernel<true, N, false> : sweep_x64_fused_kernel<false, N, false>)
-    switch (nt) {
-      case 1: MLBP_PICK(1); break;
-      case 2: MLBP_PICK(2); break;
-      case 3: MLBP_PICK(3); break;
-      default: MLBP_PICK(0); break;
-    }
+  FusedDev& f = G.f;
+  f.only = flagged_only ? prog->d_bail.p : nullptr;
+  GradFusedDev gf = {};
+  if (fuse_gradient) fill_grad_fused(a->gradient, &gf);
+  const int fixup_blocks = (a->B + FIXUP_GRAPHS_PER_WG - 1) / FIXUP_GRAPHS_PER_WG;
+  const mlbp_posterior_args* pa = a->posterior;
+  *post_done = pa && f.only && norm && fixup_blocks <= LP_MAX_BLOCKS;
+  if (*post_done) {
+    f.post.labels = pa->labels; f.post.out = pa->out; f.post.sum_out = pa->sum_out;
+    f.post.generation = pa->sum_out ? next_lp_generation() : 0u;
+  }
+  // the kernel keeps the tables in registers when the graph has at most 3 of them, else it streams them
+  const int nt = (prog->P >= 1 && prog->P <= 3) ? prog->P : 0;
+  void (*k)(SweepDev, FusedDev, GradFusedDev) = nullptr;
+#define MLBP_PICK(N) k = fuse_gradient ? sweep_x64_fused_kernel<true, N, true> : (norm ? sweep_x64_fused_kernel<true, N, false> : sweep_x64_fused_kernel<false, N, false>)
+  switch (nt) {
+    case 1: MLBP_PICK(1); break;
+    case 2: MLBP_PICK(2); break;
+    case 3: MLBP_PICK(3); break;
+    default: MLBP_PICK(0); break;
+  }
 #undef MLBP_PICK
-    if (int e = mlbp::grant_lds((const void*)k, lds)) return e;
-    mlbp::launch_begin();
-    MLBP_LAUNCH(k, dim3(f.only ? (a->B + FIXUP_GRAPHS_PER_WG - 1) / FIXUP_GRAPHS_PER_WG : a->B), dim3(WG), lds, st, G.d, f, gf);
-    if (int e = mlbp::launch_verdict("exact X = 64 sweep")) return e;
-    return sweep_tail(prog, a, tail, stream);
-  }
-  const bool approx = (a->flags & MLBP_SWEEP_APPROX_INFERENCE) != 0;
-  const bool small_lean_candidate = a->X < 64 && a->X >= 2 && norm && prog->sf_ok && prog->P >= 1 && prog->P <= 4 && variant == 1 &&
-                                    !a->gradient && prog->lean.ok && prog->d_limage;
-  if (a->init_messages && !small_lean_candidate) {
-    int e = mlbp_init_messages_f64(a->msgs, (int64_t)a->B * prog->n_msgs, a->X, stream);
-    if (e) return e;
-  }
-  if ((a->flags & MLBP_SWEEP_SHARED_PAIR_TABLES) && a->pair_tab_host && mlbp::gemm_path_supports(a->X) && !approx &&
-      prog->P >= 1 && prog->P <= 16 && variant == 1) {
-    // shared tables at a large state space: every contraction is one MFMA launch over the whole batch
-    const int eg = mlbp::launch_gemm_sweep(prog, a, stream);
-    if (eg != MLBP_EUNSUPPORTED) {                 // unsupported shape: the per-graph kernels below
-      if (eg) return eg;
-      g_last_kernel = MLBP_KERNEL_SHARED_GEMM;
-      return sweep_tail(prog, a, SweepTail(), stream);
-    }
-  }
-  SweepDev d;
-  fill_sweep_dev(prog, a, &d);
-  const bool f32_tables = (a->flags & MLBP_SWEEP_PAIR_TABLES_F32) != 0;
-  // large state spaces: the wide kernel for X = 128 / 256 / 512 exactly, and (normalised messages, float64 tables) for
-  // any X in (64, 1024] with the last pieces of each row masked
-  d.approx_k = approx ? MLBP_APPROX_K : 0;
-  const bool wide_exact = a->X == 128 || a->X == 256 || a->X == 512;
-  const bool wide_padded = !wide_exact && !f32_tables && norm && a->X > 64 && a->X <= 1024;
-  if (wide_exact || wide_padded) {
-    g_last_kernel = MLBP_KERNEL_WIDE;
-    void (*kw)(SweepDev) = nullptr;
-    int xp = a->X;
-    if (f32_tables) {
-      d.pair_tables = reinterpret_cast<const double*>(a->pair_tables_f32);
-      if (a->X == 256) kw = norm ? sweep_wide_kernel<true, 1, float, 4, 0> : sweep_wide_kernel<false, 1, float, 4, 0>;
-      else kw = norm ? sweep_wide_kernel<true, 2, float, 4, 0> : sweep_wide_kernel<false, 2, float, 4, 0>;
-    } else if (a->X == 128) kw = norm ? sweep_wide_kernel<true, 1, double, 2, 0> : sweep_wide_kernel<false, 1, double, 2, 0>;
-    else if (a->X == 256) kw = norm ? sweep_wide_kernel<true, 2, double, 2, 0> : sweep_wide_kernel<false, 2, double, 2, 0>;
-    else if (a->X == 512) kw = norm ? sweep_wide_kernel<true, 4, double, 2, 0> : sweep_wide_kernel<false, 4, double, 2, 0>;
-    else {
-      const int q = (a->X + 127) / 128;              // 128-column pieces per row
-      const bool odd = (a->X & 1) != 0;
-#define MLBP_WIDE_PAD(QQ) (kw = odd ? sweep_wide_kernel<true, QQ, double, 2, 2> : sweep_wide_kernel<true, QQ, double, 2, 1>, xp = 128 * QQ)
-      if (q <= 1) MLBP_WIDE_PAD(1);
-      else if (q <= 2) MLBP_WIDE_PAD(2);
-      else if (q <= 3) MLBP_WIDE_PAD(3);
-      else if (q <= 4) MLBP_WIDE_PAD(4);
-      else if (q <= 6) MLBP_WIDE_PAD(6);
-      else MLBP_WIDE_PAD(8);
-#undef MLBP_WIDE_PAD
-    }
-    const size_t ldsw = ((size_t)6 * xp + 4) * sizeof(double);
-    mlbp::launch_begin();
-    MLBP_LAUNCH(kw, dim3(a->B), dim3(WG), ldsw, st, d);
-    if (int e = mlbp::launch_verdict("wide sweep")) return e;
-    return sweep_tail(prog, a, SweepTail(), stream);
-  }
-  // small state spaces (X < 64): the lean X = 64 kernel on zero-padded vectors and tables; the graphs it flags are redone
-  // by the generic kernel below in its fix-up mode
-  bool lean_small = false;
-  if (a->X < 64 && a->X >= 2 && norm && prog->sf_ok && prog->P >= 1 && prog->P <= 4 && variant == 1 && !a->gradient) {
-    if (int e = mlbp::launch_lean_sweep(prog, a, nullptr, stream, &lean_small)) return e;
-    if (lean_small) {
-      d.only = const_cast<mlbp_program*>(prog)->d_bail;
-      d.fill_uniform = a->init_messages;
-    } else if (small_lean_candidate && a->init_messages) {       // the lean kernel declined after all: initialise here
-      if (int e = mlbp_init_messages_f64(a->msgs, (int64_t)a->B * prog->n_msgs, a->X, stream)) return e;
-    }
-  }
-  g_last_kernel = lean_small ? MLBP_KERNEL_LEAN : MLBP_KERNEL_GENERIC;
-  size_t base = ((size_t)a->X + 4) * sizeof(double);
-  size_t with_msgs = base + (size_t)prog->n_msgs * a->X * sizeof(double);
-  mlbp::launch_begin();
-  if (with_msgs <= 64 * 1024) {
-    auto k = norm ? sweep_generic_kernel<true, true> : sweep_generic_kernel<false, true>;
-    MLBP_LAUNCH(k, dim3(a->B), dim3(WG), with_msgs, st, d);
-  } else {
-    auto k = norm ? sweep_generic_kernel<true, false> : sweep_generic_kernel<false, false>;
-    MLBP_LAUNCH(k, dim3(a->B), dim3(WG), base, st, d);
-  }
-  if (int e = mlbp::launch_verdict("generic sweep")) return e;
-  return sweep_tail(prog, a, SweepTail(), stream);
+  if (int e = grant_lds((const void*)k, lds)) return e;
+  launch_begin();
+  MLBP_LAUNCH(k, dim3(f.only ? fixup_blocks : a->B), dim3(WG), lds, (hipStream_t)stream, G.d, f, gf);
+  return launch_verdict("exact X = 64 sweep");
 }
 
-int mlbp_sweep_f64(const mlbp_program* prog, const mlbp_sweep_args* a, void* stream) {
-  g_last_fused_gradient = 0;
-  if (!prog || !a) return fail(MLBP_EINVAL, "mlbp_sweep_f64: NULL program or args");
-  prog = effective_program(prog, a);
-  if (int e = check_sweep_args(prog, a)) return e;
-  return run_sweep(prog, a, FAST_NONE, g_sweep_variant, stream);
-}
-
-// Behind launch_shared_groups: every member's fix-up pass in ONE launch (and, when the call carries gradients, one launch of
-// the per-graph gradient kernel over the flagged graphs of all members), then each member's posterior by its own launch.
-// *done false: some member needs the per-group path (messages kept -- the unary write-back ran already, but marginals without
-// normalisation, an LDS image too large, a gradient the shared-table kernel did not produce).  Tables cached with progs[0].
-static int finish_shared_groups(const mlbp_program* const* progs, const mlbp_sweep_args* args, int n_groups, const std::vector<char>& member,
-                                void* stream, bool* done) {
-  *done = false;
+int launch_exact_x64_groups(mlbp_program* const* progs, const mlbp_sweep_args* args, int n_groups, const std::vector<char>& member,
+                            void* stream, bool* launched) {
+  *launched = false;
   std::vector<FixupGroup> table;
-  std::vector<mlbp_gradient_args> grads;
-  std::vector<const uint8_t*> grad_flags;
   size_t lds_max = 0;
-  int blocks = 0;
+  int blocks = 0, n_grads = 0;
   for (int k = 0; k < n_groups; ++k) {
     if (!member[k]) continue;
     const mlbp_program* prog = progs[k];
     const mlbp_sweep_args* a = &args[k];
-    if (a->X != 64 || !a->normalize_messages || !a->init_messages) return MLBP_OK;
+    if (!exact_x64_applies(prog, a) || !a->normalize_messages || !a->init_messages) return MLBP_OK;
     table.emplace_back();
     FixupGroup& G = table.back();
-    const size_t lds = fill_fixup_group(prog, a, &G);
-    if (lds > X64_LDS_MAX) return MLBP_OK;
-    lds_max = std::max(lds_max, lds);
+    lds_max = std::max(lds_max, fill_fixup_group(prog, a, &G));
     // (a group without pairwise factors -- one predicted word -- never ran the shared-table kernels: launch_shared_groups flagged
-    // all of its graphs, so this pass and the flagged graphs' gradient below ARE its sweep call)
-    if (a->gradient && prog->P > 0 && !mlbp::shared_gradient_fused(prog, a)) return MLBP_OK;
+    // all of its graphs, so this pass and the flagged graphs' gradient behind it ARE its sweep call)
+    if (a->gradient && prog->P > 0 && !shared_gradient_fused(prog, a)) return MLBP_OK;
     G.f.only = prog->d_bail;
     G.first_block = blocks;
     G.per_wg = prog->P == 0 ? 1 : FIXUP_GRAPHS_PER_WG;          // (a pairwise-free group is all flagged: one workgroup per graph, not 64 graphs in a row)
     blocks += (a->B + G.per_wg - 1) / G.per_wg;
-    if (a->gradient) { grads.push_back(*a->gradient); grad_flags.push_back(prog->d_bail); }
+    n_grads += a->gradient ? 1 : 0;
   }
   const int n_in = (int)table.size();
-  if (!grads.empty() && (int)grads.size() != n_in) return MLBP_OK;           // (all members or none carry a gradient)
+  if (n_grads != 0 && n_grads != n_in) return MLBP_OK;                        // (all members or none carry a gradient)
   // the table as 32-bit words in the first program's group-table cache (one device copy per distinct contents)
   static_assert(sizeof(FixupGroup) % 4 == 0, "");
   std::vector<int32_t> words(sizeof(FixupGroup) / 4 * (size_t)n_in + 1);
   memcpy(words.data(), table.data(), sizeof(FixupGroup) * (size_t)n_in);
   words.back() = 0x46495855;                                                  // (keeps this table apart from the sweep kernels' own)
-  mlbp_program* owner = const_cast<mlbp_program*>(progs[0]);
   int32_t* d_table = nullptr;
-  if (int e = mlbp::group_table_device(owner->stables, words, stream, &d_table)) return e;
-  if (int e = mlbp::grant_lds((const void*)sweep_x64_fixup_groups_kernel, lds_max)) return e;
-  mlbp::launch_begin();
+  if (int e = group_table_device(progs[0]->stables, words, stream, &d_table)) return e;
+  if (int e = grant_lds((const void*)sweep_x64_fixup_groups_kernel, lds_max)) return e;
+  launch_begin();
   MLBP_LAUNCH(sweep_x64_fixup_groups_kernel, dim3(blocks), dim3(WG), lds_max, (hipStream_t)stream,
                      reinterpret_cast<const FixupGroup*>(d_table), n_in);
-  if (int e = mlbp::launch_verdict("grouped exact X = 64 fix-up")) return e;
-  if (!grads.empty())
-    if (int e = mlbp::gradient_flagged_groups(grads.data(), grad_flags.data(), n_in, owner, stream)) return e;
-  SweepTail tail;                                 // (the marginals are the kernels' epilogue, the gradient is done above)
-  tail.marginals = false;
-  tail.grad_done = true;
-  for (int k = 0; k < n_groups; ++k)
-    if (member[k])
-      if (int e = sweep_tail(progs[k], &args[k], tail, stream)) return e;
-  g_last_kernel = MLBP_KERNEL_SHARED_MFMA;
-  g_last_fused_gradient = grads.empty() ? 0 : 1;
-  *done = true;
+  if (int e = launch_verdict("grouped exact X = 64 fix-up")) return e;
+  *launched = true;
   return MLBP_OK;
 }
 
-int mlbp_sweep_groups_f64(const mlbp_program* const* progs, const mlbp_sweep_args* args, int32_t n_groups, void* stream) {
-  if (!progs || !args || n_groups < 1) return fail(MLBP_EINVAL, "mlbp_sweep_groups_f64: bad arguments");
-  std::vector<const mlbp_program*> eff(n_groups);
-  for (int k = 0; k < n_groups; ++k) {
-    if (!progs[k]) return fail(MLBP_EINVAL, "mlbp_sweep_groups_f64: NULL program");
-    eff[k] = effective_program(progs[k], &args[k]);
-    if (int e = check_sweep_args(eff[k], &args[k])) return e;
+int launch_wide_sweep(mlbp_program* prog, const mlbp_sweep_args* a, void* stream, bool* launched) {
+  *launched = false;
+  const bool norm = a->normalize_messages != 0, f32_tables = (a->flags & MLBP_SWEEP_PAIR_TABLES_F32) != 0;
+  const bool wide_exact = a->X == 128 || a->X == 256 || a->X == 512;
+  const bool wide_padded = !wide_exact && !f32_tables && norm && a->X > 64 && a->X <= 1024;
+  if (!wide_exact && !wide_padded) return MLBP_OK;
+  SweepDev d;
+  fill_sweep_dev(prog, a, &d);
+  d.approx_k = (a->flags & MLBP_SWEEP_APPROX_INFERENCE) ? MLBP_APPROX_K : 0;
+  void (*kw)(SweepDev) = nullptr;
+  int xp = a->X;
+  if (f32_tables) {
+    d.pair_tables = reinterpret_cast<const double*>(a->pair_tables_f32);
+    if (a->X == 256) kw = norm ? sweep_wide_kernel<true, 1, float, 4, 0> : sweep_wide_kernel<false, 1, float, 4, 0>;
+    else kw = norm ? sweep_wide_kernel<true, 2, float, 4, 0> : sweep_wide_kernel<false, 2, float, 4, 0>;
+  } else if (a->X == 128) kw = norm ? sweep_wide_kernel<true, 1, double, 2, 0> : sweep_wide_kernel<false, 1, double, 2, 0>;
+  else if (a->X == 256) kw = norm ? sweep_wide_kernel<true, 2, double, 2, 0> : sweep_wide_kernel<false, 2, double, 2, 0>;
+  else if (a->X == 512) kw = norm ? sweep_wide_kernel<true, 4, double, 2, 0> : sweep_wide_kernel<false, 4, double, 2, 0>;
+  else {
+    const int q = (a->X + 127) / 128;              // 128-column pieces per row
+    const bool odd = (a->X & 1) != 0;
+#define MLBP_WIDE_PAD(QQ) (kw = odd ? sweep_wide_kernel<true, QQ, double, 2, 2> : sweep_wide_kernel<true, QQ, double, 2, 1>, xp = 128 * QQ)
+    if (q <= 1) MLBP_WIDE_PAD(1);
+    else if (q <= 2) MLBP_WIDE_PAD(2);
+    else if (q <= 3) MLBP_WIDE_PAD(3);
+    else if (q <= 4) MLBP_WIDE_PAD(4);
+    else if (q <= 6) MLBP_WIDE_PAD(6);
+    else MLBP_WIDE_PAD(8);
+#undef MLBP_WIDE_PAD
   }
-  progs = eff.data();
-  const int variant = g_sweep_variant;
-  // The fast kernels take what they can, in this order: the shared-table launch sequence, then one grouped lean launch over the
-  // groups left; each is followed by the fix-up pass over the graphs it flagged.  The rest run one after the other exactly as
-  // separate calls would.  A program joins one grouped launch at most (with its first group): two groups would share one set of
-  // redo flags and scratch -- the later one runs as a separate call behind the grouped launches.
-  std::vector<char> shared(n_groups, 0), lean(n_groups, 0);
-  if (variant == 1) {
-    std::vector<char> first(n_groups);
-    for (int k = 0; k < n_groups; ++k) first[k] = std::find(progs, progs + k, progs[k]) == progs + k;
-    shared = first;
-    if (int e = mlbp::launch_shared_groups(progs, args, n_groups, stream, shared)) return e;
-    // the shared-table kernels have run every member, gradient included: ONE fix-up launch for the flagged graphs of all members
-    // and one more for their gradients (a mixed minibatch used to pay both per group)
-    if (std::find(shared.begin(), shared.end(), 1) != shared.end()) {
-      bool done = false;
-      if (int e = finish_shared_groups(progs, args, n_groups, shared, stream, &done)) return e;
-      for (int k = 0; k < n_groups && !done; ++k)
-        if (shared[k])
-          if (int e = run_sweep(progs[k], &args[k], FAST_SHARED, variant, stream)) return e;
-    }
-    for (int k = 0; k < n_groups; ++k) lean[k] = first[k] && !shared[k];      // (lean_plan takes no pairwise-free group)
-    if (int e = mlbp::launch_lean_groups(progs, args, n_groups, stream, lean)) return e;
-    for (int k = 0; k < n_groups; ++k)
-      if (lean[k])
-        if (int e = run_sweep(progs[k], &args[k], FAST_LEAN, variant, stream)) return e;
+  const size_t ldsw = ((size_t)6 * xp + 4) * sizeof(double);
+  launch_begin();
+  MLBP_LAUNCH(kw, dim3(a->B), dim3(WG), ldsw, (hipStream_t)stream, d);
+  if (int e = launch_verdict("wide sweep")) return e;
+  *launched = true;
+  return MLBP_OK;
+}
+
+int launch_generic_sweep(mlbp_program* prog, const mlbp_sweep_args* a, bool flagged_only, void* stream) {
+  const bool norm = a->normalize_messages != 0;
+  SweepDev d;
+  fill_sweep_dev(prog, a, &d);
+  d.approx_k = (a->flags & MLBP_SWEEP_APPROX_INFERENCE) ? MLBP_APPROX_K : 0;
+  if (flagged_only) {                                // the graphs the padded lean pass flagged; it initialised none of them
+    d.only = prog->d_bail;
+    d.fill_uniform = a->init_messages;
   }
-  for (int k = 0; k < n_groups; ++k)
-    if (!shared[k] && !lean[k])
-      if (int e = run_sweep(progs[k], &args[k], FAST_NONE, variant, stream)) return e;
-  return MLBP_OK;
-}
-
-}  // extern "C"
-
-namespace mlbp {
-int grant_lds(const void* kernel, size_t bytes, bool* fresh) {
-  static std::vector<std::pair<const void*, size_t>> granted;
-  static std::mutex mu;
-  std::lock_guard<std::mutex> lock(mu);
-  if (fresh) *fresh = false;
-  auto g = std::find_if(granted.begin(), granted.end(), [&](const std::pair<const void*, size_t>& e) { return e.first == kernel; });
-  if (g != granted.end() && g->second >= bytes) return MLBP_OK;
-  HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  if (g != granted.end()) g->second = bytes;
-  else granted.push_back({kernel, bytes});
-  if (fresh) *fresh = true;
-  return MLBP_OK;
-}
-
-void launch_begin() { (void)hipGetLastError(); }
-
-int launch_verdict(const char* what) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? MLBP_OK : fail(MLBP_EHIP, "%s launch failed: %s", what, hipGetErrorString(e));
-}
-
-int program_grow(mlbp_program* prog, void** p, size_t* cap, size_t bytes, bool zero) {
-  if (bytes <= *cap && *p) return MLBP_OK;
-  void* fresh = nullptr;
-  if (hipMalloc(&fresh, bytes ? bytes : 1) != hipSuccess) return fail(MLBP_EHIP, "program scratch: allocation of %zu bytes failed", bytes);
-  if (zero && hipMemset(fresh, 0, bytes) != hipSuccess) { (void)hipFree(fresh); return fail(MLBP_EHIP, "program scratch: memset failed"); }
-  if (*p) prog->retired.push_back(*p);     // a captured graph may still name it: freed with the program
-  *p = fresh;
-  *cap = bytes;
-  return MLBP_OK;
-}
-
-int fallback_scratch(int purpose, size_t bytes, void** out) {
-  struct Block { void* p = nullptr; size_t cap = 0; };
-  static std::mutex mu;
-  static std::vector<std::vector<Block>> per_device;      // [device][purpose]; replaced blocks are never freed (process lifetime)
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return fail(MLBP_EHIP, "hipGetDevice failed");
-  std::lock_guard<std::mutex> lock(mu);
-  if ((int)per_device.size() <= dev) per_device.resize(dev + 1, std::vector<Block>(SCRATCH_PURPOSES));
-  Block& b = per_device[dev][purpose];
-  if (bytes > b.cap) {
-    void* fresh = nullptr;
-    const size_t want = bytes > 2 * b.cap ? bytes : 2 * b.cap;
-    if (hipMalloc(&fresh, want) != hipSuccess) return fail(MLBP_EHIP, "scratch allocation of %zu bytes failed", want);
-    b.p = fresh; b.cap = want;
+  // the messages live in LDS when they fit
+  const size_t base = ((size_t)a->X + 4) * sizeof(double);
+  const size_t with_msgs = base + (size_t)prog->n_msgs * a->X * sizeof(double);
+  launch_begin();
+  if (with_msgs <= 64 * 1024) {
+    auto k = norm ? sweep_generic_kernel<true, true> : sweep_generic_kernel<false, true>;
+    MLBP_LAUNCH(k, dim3(a->B), dim3(WG), with_msgs, (hipStream_t)stream, d);
+  } else {
+    auto k = norm ? sweep_generic_kernel<true, false> : sweep_generic_kernel<false, false>;
+    MLBP_LAUNCH(k, dim3(a->B), dim3(WG), base, (hipStream_t)stream, d);
   }
-  *out = b.p;
-  return MLBP_OK;
+  return launch_verdict("generic sweep");
 }
 
-int group_table_device(GroupTables& gt, const std::vector<int32_t>& table, void* stream, int32_t** out) {
-  for (auto& e : gt.entries)
-    if (e.words == table) { *out = e.dev; return MLBP_OK; }
-  if (getenv("MLBP_DEBUG_GROUP_TABLE")) {
-    fprintf(stderr, "group table miss: %zu words, %zu cached\n", table.size(), gt.entries.size());
-    for (auto& e : gt.entries)
-      if (e.words.size() == table.size())
-        for (size_t i = 0; i < table.size(); ++i)
-          if (e.words[i] != table[i]) { fprintf(stderr, "  first difference to a cached table at word %zu: %d vs %d\n", i, e.words[i], table[i]); break; }
-  }
-  GroupTables::Entry* slot = nullptr;
-  if (gt.entries.size() < (size_t)GroupTables::MAX) { gt.entries.emplace_back(); slot = &gt.entries.back(); }
-  else { slot = &gt.entries[gt.next_evict]; gt.next_evict = (gt.next_evict + 1) % GroupTables::MAX; }
-  if (table.size() > slot->cap_words) {
-    int32_t* fresh = nullptr;
-    if (hipMalloc(&fresh, table.size() * sizeof(int32_t)) != hipSuccess) return fail(MLBP_EHIP, "group table allocation failed");
-    (void)hipFree(slot->dev);               // (only a recycled slot has one: its table is being replaced anyway)
-    slot->dev = fresh; slot->cap_words = table.size();
-  }
-  slot->words = table;
-  if (hipMemcpyAsync(slot->dev, slot->words.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess)
-    return fail(MLBP_EHIP, "group table upload failed");
-  *out = slot->dev;
-  return MLBP_OK;
-}
-
-void group_tables_free(GroupTables& gt) {
-  for (auto& e : gt.entries) (void)hipFree(e.dev);
-  gt.entries.clear();
-}
 }  // namespace mlbp
 
 extern "C" {
 
-int mlbp_program_reserve(mlbp_program* p, int32_t max_graphs) {
-  if (!p || max_graphs <= 0) return fail(MLBP_EINVAL, "mlbp_program_reserve: bad arguments");
-  if (p->pruned)
-    if (int e = mlbp_program_reserve(p->pruned, max_graphs)) return e;
-  if (p->bail_cap >= max_graphs) return MLBP_OK;
-  size_t cap = (size_t)p->bail_cap;                        // (cleared: mlbp_program_exact_count before any fast-path launch reads 0)
-  if (int e = mlbp::program_grow(p, reinterpret_cast<void**>(&p->d_bail), &cap, (size_t)max_graphs, true)) return e;
-  p->bail_cap = max_graphs;
-  return MLBP_OK;
-}
-
-int mlbp_program_set_readout(mlbp_program* p, int32_t n_vars, const int32_t* in_off, const int32_t* in_slots) {
-  if (!p || n_vars <= 0 || !in_off || !in_slots) return fail(MLBP_EINVAL, "mlbp_program_set_readout: bad arguments");
-  if (in_off[0] != 0) return fail(MLBP_EINVAL, "in_off[0] must be 0");
-  for (int v = 0; v < n_vars; ++v)
-    if (in_off[v + 1] < in_off[v]) return fail(MLBP_EINVAL, "in_off must be non-decreasing");
-  const int n_in = in_off[n_vars];
-  for (int q = 0; q < n_in; ++q)
-    if (in_slots[q] < 0 || in_slots[q] >= p->n_msgs) return fail(MLBP_EINVAL, "in_slots[%d] = %d out of [0,%d)", q, in_slots[q], p->n_msgs);
-  if (p->pruned)
-    if (int e = mlbp_program_set_readout(p->pruned, n_vars, in_off, in_slots)) return e;
-  std::vector<int32_t> img(in_off, in_off + n_vars + 1);
-  img.insert(img.end(), in_slots, in_slots + n_in);
-  img.push_back(0);
-  (void)hipFree(p->d_readout);
-  p->d_readout = nullptr;
-  HIP_TRY(hipMalloc(&p->d_readout, img.size() * sizeof(int32_t)));
-  HIP_TRY(hipMemcpy(p->d_readout, img.data(), img.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  p->n_vars = n_vars;
-  p->n_readout = (int)img.size();
-  (void)hipFree(p->d_lreadout);
-  p->d_lreadout = nullptr;
-  std::vector<int32_t> limg;
-  if (p->lean.ok && mlbp::build_lean_readout(p->lean, p->n_msgs, n_vars, in_off, in_slots, limg)) {
-    HIP_TRY(hipMalloc(&p->d_lreadout, limg.size() * sizeof(int32_t)));
-    HIP_TRY(hipMemcpy(p->d_lreadout, limg.data(), limg.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  }
-  (void)hipFree(p->d_sreadout);
-  p->d_sreadout = nullptr;
-  p->n_sreadout = 0;
-  std::vector<int32_t> simg;
-  p->sreadout_all_based = false; p->sreadout_all_tiled = false;
-  if (p->shared.ok && mlbp::build_shared_readout(p->shared, p->n_msgs, n_vars, in_off, in_slots, simg)) {
-    p->sreadout_all_based = true; p->sreadout_all_tiled = true;
-    for (int v = 0; v < n_vars; ++v) {
-      p->sreadout_all_based &= simg[simg[v]] >= 0;
-      p->sreadout_all_tiled &= simg[simg[v] + 1] >= 1;       // (the three-source product-fused read-out stages a variable's rows in its first message tile)
-      for (int u = 0; u < v; ++u) p->sreadout_all_based &= simg[simg[u]] != simg[simg[v]];      // (and its own: the read-out stages a variable's rows there)
-    }
-    HIP_TRY(hipMalloc(&p->d_sreadout, simg.size() * sizeof(int32_t)));
-    HIP_TRY(hipMemcpy(p->d_sreadout, simg.data(), simg.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    p->n_sreadout = (int)simg.size();
-  }
-  return MLBP_OK;
-}
-
-int mlbp_set_sweep_variant(int32_t variant) {
-  const bool known = variant == 1 || variant == 3;
-  if (!known) return fail(MLBP_EINVAL, "unknown sweep variant %d", variant);
-  g_sweep_variant = variant;
-  return MLBP_OK;
-}
-
-int mlbp_last_sweep_kernel(void) { return g_last_kernel; }
-int mlbp_last_sweep_fused_gradient(void) { return g_last_fused_gradient; }
-
-int mlbp_program_exact_count(const mlbp_program* prog, int32_t B) {
-  // Synchronising: how many of the first B graphs of the last default-variant launch were handed
-  // to the exact kernel (0 when the scale-free kernel was not used).
-  if (!prog || B < 0) return fail(MLBP_EINVAL, "mlbp_program_exact_count: bad arguments");
-  if (prog->last_was_pruned && prog->pruned) prog = prog->pruned;
-  if (!prog->d_bail || B == 0) return 0;
-  if (B > prog->bail_cap) B = prog->bail_cap;
-  std::vector<unsigned char> h((size_t)B);
-  HIP_TRY(hipMemcpy(h.data(), prog->d_bail, (size_t)B, hipMemcpyDeviceToHost));
-  int n = 0, hist[4] = {0, 0, 0, 0};
-  for (unsigned char c : h) { n += c ? 1 : 0; hist[c & 3]++; }
-  fail(0, "exact-kernel graphs by reason: prologue %d, main loop %d, final pass %d (shared-table kernel: 2 = degenerate total, 4 -> counted under 0 = tables not shared)", hist[1], hist[2], hist[3]);
-  return n;
-}
-
-int mlbp_program_status(const mlbp_program* prog) {
-  // Synchronising read of the status word: 0 = clean, 1 = a kernel skipped a graph because a
-  // table index was out of range.  Resets the word.
-  if (!prog) return fail(MLBP_EINVAL, "NULL program");
-  int32_t v = 0, zero = 0;
-  HIP_TRY(hipMemcpy(&v, prog->d_status, sizeof(v), hipMemcpyDeviceToHost));
-  if (v) HIP_TRY(hipMemcpy(prog->d_status, &zero, sizeof(zero), hipMemcpyHostToDevice));
-  if (prog->pruned) {
-    const int w = mlbp_program_status(prog->pruned);
-    if (w < 0) return w;
-    v |= w;
-  }
-  return v;
-}
-
-int mlbp_program_skippable_updates(const mlbp_program* prog) {
-  if (!prog) return fail(MLBP_EINVAL, "NULL program");
-  return prog->n_dropped;
-}
-
 int mlbp_init_messages_f64(double* msgs, int64_t n_rows, int32_t X, void* stream) {
   if (!msgs || n_rows <= 0 || X <= 0) return fail(MLBP_EINVAL, "mlbp_init_messages_f64: bad arguments");
-  if (int e = check_device()) return e;
+  if (int e = mlbp::check_device()) return e;
   int64_t n = n_rows * X;
   int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
   mlbp::launch_begin();
@@ -1784,7 +1246,7 @@ int mlbp_marginals_f64(const double* msgs, int32_t B, int32_t n_msgs, int32_t X,
                        double* out, void* stream) {
   if (!msgs || !in_off || !in_slots || !out || B <= 0 || n_msgs <= 0 || X <= 0 || n_vars <= 0)
     return fail(MLBP_EINVAL, "mlbp_marginals_f64: bad arguments");
-  if (int e = check_device()) return e;
+  if (int e = mlbp::check_device()) return e;
   mlbp::launch_begin();
   MLBP_LAUNCH(marginals_kernel, dim3(B), dim3(WG), 0, (hipStream_t)stream, msgs, n_msgs, X, n_vars,
                      in_off, in_slots, normalize_messages, out);
@@ -1795,9 +1257,9 @@ int mlbp_log_posterior_sum_f64(const double* marginals, const int32_t* labels, i
                                int32_t X, double* out, double* sum_out, void* stream) {
   if (!marginals || !labels || !out || B <= 0 || n_vars <= 0 || X <= 0)
     return fail(MLBP_EINVAL, "mlbp_log_posterior_f64: bad arguments");
-  if (int e = check_device()) return e;
+  if (int e = mlbp::check_device()) return e;
   int32_t* status = nullptr;
-  if (int e = global_status(&status)) return e;
+  if (int e = mlbp::status_word(&status)) return e;
   const int blocks = (B + LP_WG - 1) / LP_WG;
   if (sum_out && blocks > LP_MAX_BLOCKS)
     return fail(MLBP_EUNSUPPORTED, "mlbp_log_posterior_sum_f64: at most %d graphs with sum_out", LP_MAX_BLOCKS * LP_WG);
@@ -1813,9 +1275,9 @@ int mlbp_log_posterior_sum_f64(const double* marginals, const int32_t* labels, i
 int mlbp_log_posterior_groups_f64(const mlbp_posterior_group* groups, int32_t n_groups, int64_t n_total, int32_t X, double* out,
                                   void* stream) {
   if (!groups || !out || n_groups <= 0 || n_total <= 0 || X <= 0) return fail(MLBP_EINVAL, "mlbp_log_posterior_groups_f64: bad arguments");
-  if (int e = check_device()) return e;
+  if (int e = mlbp::check_device()) return e;
   int32_t* status = nullptr;
-  if (int e = global_status(&status)) return e;
+  if (int e = mlbp::status_word(&status)) return e;
   mlbp::launch_begin();
   MLBP_LAUNCH(log_posterior_groups_kernel, dim3((unsigned)((n_total + LP_WG - 1) / LP_WG)), dim3(LP_WG), 0, (hipStream_t)stream, groups,
                      n_groups, (long long)n_total, X, out, status);
