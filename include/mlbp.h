@@ -277,7 +277,8 @@ typedef struct mlbp_sweep_args {
 #define MLBP_SWEEP_DENSE_TABLES 8
 /* flags: FactorGraph.use_approx_inference (LBP.py:506-507, 515-516): a pairwise factor->variable update uses only the
  * MLBP_APPROX_K = 100 largest entries of the incoming message (au.sparse_vec_mat_dot, c_array_utils.pyx:193-205).
- * Batched: the selection runs on the device inside the sweep launch (rank by value, ties by lower index).
+ * Batched: the selection runs on the device inside the sweep launch (rank by value, NaN below every number, ties by
+ * lower index: the order of mlbp_topk_f64).
  * 100 <= X <= 1024; smaller X fails like the reference's argpartition ("kth out of bounds"). */
 #define MLBP_SWEEP_APPROX_INFERENCE 16
 #define MLBP_APPROX_K 100
@@ -465,8 +466,12 @@ int64_t mlbp_gradient_workspace_bytes(const mlbp_gradient_args* a);
 #define MLBP_GRADIENT_SHARED_PAIR_TABLES 1
 /* flags: FactorGraph.use_approx_beliefs (LBP.py:554-563): a pairwise factor's beliefs live on the block of the
  * MLBP_APPROX_K largest entries of its two incoming messages (au.sparse_dot, sparse_pointwise_multiply,
- * sparse_normalize, c_array_utils.pyx:108-129, 23-26).  X >= MLBP_APPROX_K. */
+ * sparse_normalize, c_array_utils.pyx:108-129, 23-26).  MLBP_APPROX_K <= X <= MLBP_APPROX_BELIEFS_MAX_X: the two
+ * selected messages are held on chip (2 X doubles beside the kernel's own 800 bytes, 64 KiB in all); a larger X is
+ * refused with MLBP_EUNSUPPORTED before anything is enqueued.  The selection is the order of mlbp_topk_f64: by value,
+ * NaN below every number, ties to the lower index. */
 #define MLBP_GRADIENT_APPROX_BELIEFS 2
+#define MLBP_APPROX_BELIEFS_MAX_X 4046
 int mlbp_gradient_f64(const mlbp_gradient_args* a, void* stream);
 
 /* A unary factor's belief is normalize(table) (LBP.py:540) whatever the messages say, so its expected

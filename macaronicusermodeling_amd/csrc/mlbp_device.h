@@ -73,6 +73,15 @@ __device__ __forceinline__ double renorm(double v, double total, double uniform,
   return total > 0.0 ? v / total : uniform;
 }
 
+// The order of every top-K selection of the library (mlbp_topk_f64, use_approx_inference, use_approx_beliefs): does entry
+// (y, index i) rank above entry (x, index j)?  Numbers by value, descending; every NaN below every number; ties -- NaNs among
+// themselves too -- to the lower index.  The order is total, so rank_j = #{i : ranks_above(v_i, i, v_j, j)} is a permutation
+// of 0..n-1.  (A NaN y compares false with a number x: never above it.)
+__device__ __forceinline__ bool ranks_above(double y, int i, double x, int j) {
+  if (x != x) return (y == y) || i < j;
+  return (y > x) || (y == x && i < j);
+}
+
 // Program data (op headers, source lists, sweep table) is read-only for the whole launch and
 // wave-uniform.  Reading it through the CONSTANT address space lets the compiler use scalar loads
 // (s_load -> SGPRs, lgkmcnt) instead of per-lane vector loads that queue behind the table stream

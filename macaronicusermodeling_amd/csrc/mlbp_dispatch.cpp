@@ -59,6 +59,9 @@ int check_sweep_args(const mlbp_program* prog, const mlbp_sweep_args* a) {
   const mlbp_gradient_args* ga = a->gradient;
   if (ga && (ga->B != a->B || ga->X != a->X || ga->P != prog->P || ga->U != prog->U || ga->n_msgs != prog->n_msgs || ga->msgs != a->msgs))
     return fail(MLBP_EINVAL, "mlbp_sweep_f64: gradient arguments do not describe the same batch");
+  if (ga && (ga->flags & MLBP_GRADIENT_APPROX_BELIEFS) && a->X > MLBP_APPROX_BELIEFS_MAX_X)      // (mlbp_gradient_f64's own refusal, before the sweeps)
+    return fail(MLBP_EUNSUPPORTED, "mlbp_sweep_f64: approximate beliefs hold both selected messages on chip; X=%d > %d", a->X,
+                MLBP_APPROX_BELIEFS_MAX_X);
   return MLBP_OK;
 }
 

@@ -25,6 +25,7 @@ namespace {
 constexpr int WG = 256;
 constexpr int FMAX = 8;
 
+using mlbp_dev::ranks_above;
 using mlbp_dev::wave_sum;
 
 struct GradDev {
@@ -66,7 +67,8 @@ __device__ void pair_gradient(const GradDev& d, int g, int p, double* scratch, d
   const double* r = a.msgs + ((size_t)g * a.n_msgs + a.pair_r_slot[p]) * X;
   if (a.flags & MLBP_GRADIENT_APPROX_BELIEFS) {
     // use_approx_beliefs (LBP.py:554-563; au.sparse_dot / sparse_pointwise_multiply / sparse_normalize): beliefs live on
-    // the block of the K largest entries of c times the K largest of r -- the other entries of both vectors are dropped
+    // the block of the K largest entries of c times the K largest of r (ranks_above: NaN below every number) -- the other
+    // entries of both vectors are dropped
     extern __shared__ double kept[];                 // [2][X]
     __syncthreads();
     for (int j = threadIdx.x; j < 2 * X; j += WG) {
@@ -74,10 +76,7 @@ __device__ void pair_gradient(const GradDev& d, int g, int p, double* scratch, d
       const int jj = j < X ? j : j - X;
       const double x = v[jj];
       int rank = 0;
-      for (int i = 0; i < X; ++i) {
-        const double y = v[i];
-        rank += (y > x) || (y == x && i < jj);
-      }
+      for (int i = 0; i < X; ++i) rank += ranks_above(v[i], i, x, jj);
       kept[j] = rank < MLBP_APPROX_K ? x : 0.0;
     }
     __syncthreads();
@@ -137,10 +136,18 @@ __device__ void unary_gradient(const GradDev& d, int g, int u, const double* phi
   }
 }
 
+// use_approx_beliefs adds 2 X doubles of dynamic LDS (pair_gradient's kept[]) to the kernel's own two arrays; together they
+// must fit the 64 KiB a launch may ask for without opting in to more: MLBP_APPROX_BELIEFS_MAX_X is the largest such X.
+constexpr size_t GRAD_STATIC_LDS = (4 * (FMAX + 1) + 4 * 2 * FMAX) * sizeof(double);
+constexpr size_t GRAD_LDS_LIMIT = 64 * 1024;
+static_assert(GRAD_STATIC_LDS + 2 * (size_t)MLBP_APPROX_BELIEFS_MAX_X * sizeof(double) <= GRAD_LDS_LIMIT &&
+              GRAD_STATIC_LDS + 2 * (size_t)(MLBP_APPROX_BELIEFS_MAX_X + 1) * sizeof(double) > GRAD_LDS_LIMIT, "");
+
 template <int FEE, int FED>
 __global__ __launch_bounds__(WG) void gradient_kernel(GradDev d) {
   __shared__ double scratch[4 * (FMAX + 1)];
   __shared__ double wave_out[4][2 * FMAX];
+  static_assert(sizeof(scratch) + sizeof(wave_out) == GRAD_STATIC_LDS, "");
   const mlbp_gradient_args& a = d.a;
   const int g = blockIdx.x;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -729,6 +736,14 @@ int mlbp_gradient_f64(const mlbp_gradient_args* a, void* stream) {
   if (a->U > 0 && (!a->unary_tables || !a->unary_tab || !a->unary_kind || !a->unary_obs || !a->unary_label ||
                    !a->phi_en_en || !a->phi_en_en_w1 || !a->phi_en_de || a->Vde <= 0))
     return fail(MLBP_EINVAL, "mlbp_gradient_f64: unary inputs missing");
+  // the size limits of approximate beliefs, before the device is touched (the status word's first use allocates)
+  const bool approx = (a->flags & MLBP_GRADIENT_APPROX_BELIEFS) != 0;
+  if (approx && a->X < MLBP_APPROX_K)
+    return fail(MLBP_EINVAL, "mlbp_gradient_f64: approximate beliefs keep the %d largest entries; kth(=%d) out of bounds (%d)",
+                MLBP_APPROX_K, MLBP_APPROX_K - 1, a->X);
+  if (approx && a->X > MLBP_APPROX_BELIEFS_MAX_X)
+    return fail(MLBP_EUNSUPPORTED, "mlbp_gradient_f64: approximate beliefs hold both selected messages on chip; X=%d > %d", a->X,
+                MLBP_APPROX_BELIEFS_MAX_X);
   if (int e = need_device()) return e;
   GradDev d;
   d.a = *a;
@@ -736,8 +751,6 @@ int mlbp_gradient_f64(const mlbp_gradient_args* a, void* stream) {
   d.only = nullptr;
   if (int e = status_word(&d.status)) return e;
   hipStream_t st = (hipStream_t)stream;
-  if (a->X == 64 && (a->flags & MLBP_GRADIENT_APPROX_BELIEFS))
-    return fail(MLBP_EINVAL, "mlbp_gradient_f64: approximate beliefs keep the %d largest entries; kth(=%d) out of bounds (64)", MLBP_APPROX_K, MLBP_APPROX_K - 1);
   if (a->X == 64) {
     // shared pairwise tables: the pairwise factors of 16 graphs at a time on the matrix cores, after the unary part
     const bool shared = takes_shared_x64(a);
@@ -751,10 +764,6 @@ int mlbp_gradient_f64(const mlbp_gradient_args* a, void* stream) {
     if (shared) return mlbp::launch_shared_pair_gradient(a, d.status, stream);
     return MLBP_OK;
   }
-  const bool approx = (a->flags & MLBP_GRADIENT_APPROX_BELIEFS) != 0;
-  if (approx && a->X < MLBP_APPROX_K)
-    return fail(MLBP_EINVAL, "mlbp_gradient_f64: approximate beliefs keep the %d largest entries; kth(=%d) out of bounds (%d)",
-                MLBP_APPROX_K, MLBP_APPROX_K - 1, a->X);
   const size_t dyn = approx ? 2 * (size_t)a->X * sizeof(double) : 0;
   // shared pairwise tables at a large state space: pairwise part as MFMA contractions over the whole batch (mlbp_gemm.hip)
   const bool gemm_pairs = takes_gemm_pairs(a);

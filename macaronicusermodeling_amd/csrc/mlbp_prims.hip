@@ -15,6 +15,7 @@ namespace {
 
 constexpr auto need_device = mlbp::check_device;
 
+using mlbp_dev::ranks_above;
 using mlbp_dev::wave_sum_xor;
 
 // C[b][i][j] = sum_k A[b][i][k] * B[b][k][j].  One wavefront per output element: lanes stride over
@@ -83,8 +84,9 @@ __global__ __launch_bounds__(256) void normalize_kernel(const double* in, double
   if (positive && threadIdx.x == 0) positive[blockIdx.x] = pos ? 1 : 0;
 }
 
-// Rank-select of the K largest entries of v[0..n) (ties: lower index first).  One workgroup per row.  The order is total:
-// numbers by value, every NaN below every number, NaNs tied among themselves, ties to the lower index, so
+// Rank-select of the K largest entries of v[0..n) (ties: lower index first).  One workgroup per row.  The order is total
+// (ranks_above, mlbp_device.h): numbers by value, every NaN below every number, NaNs tied among themselves, ties to the
+// lower index, so
 //   rank_i = #{j : j ranks above i}
 // is a permutation of 0..n-1 and entries with rank < K are written to idx[rank] -- every slot of idx exactly once, in
 // descending value order, NaNs only after all numbers (np.argpartition(-v) sorts NaN last too).  O(n^2 / 256) compares per
@@ -99,17 +101,7 @@ __global__ __launch_bounds__(256) void topk_kernel(const double* v0, int64_t str
   for (int i = threadIdx.x; i < n; i += 256) {
     const double x = sv[i];
     int rank = 0;
-    if (x != x) {                                               // NaN: below every number, after the NaNs of lower index
-      for (int j = 0; j < n; ++j) {
-        const double y = sv[j];
-        rank += (y == y) || j < i;
-      }
-    } else {                                                    // (a NaN y compares false: never above a number)
-      for (int j = 0; j < n; ++j) {
-        const double y = sv[j];
-        rank += (y > x) || (y == x && j < i);
-      }
-    }
+    for (int j = 0; j < n; ++j) rank += ranks_above(sv[j], j, x, i);
     if (rank < K) idx[rank] = i;
   }
 }

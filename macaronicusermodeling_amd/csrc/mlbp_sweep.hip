@@ -801,16 +801,13 @@ __global__ __launch_bounds__(WG) void sweep_wide_kernel(SweepDev d) {
         for (int j = t; j < XP; j += WG) vin[j] = j < X ? m[j] : 0.0;
         __syncthreads();
         if (d.approx_k > 0) {
-          // use_approx_inference: keep the K largest entries of the message (rank by value, ties by index: the rule of
-          // mlbp_topk_f64), zero the rest -- sum over the index set, as au.sparse_vec_mat_dot does
+          // use_approx_inference: keep the K largest entries of the message (ranks_above: the rule of mlbp_topk_f64, NaN
+          // below every number), zero the rest -- sum over the index set, as au.sparse_vec_mat_dot does
           double* keep = part;
           for (int j = t; j < X; j += WG) {
             const double x = vin[j];
             int rank = 0;
-            for (int i = 0; i < X; ++i) {
-              const double y = vin[i];
-              rank += (y > x) || (y == x && i < j);
-            }
+            for (int i = 0; i < X; ++i) rank += ranks_above(vin[i], i, x, j);
             keep[j] = rank < d.approx_k ? x : 0.0;
           }
           __syncthreads();
@@ -1208,7 +1205,6 @@ int launch_generic_sweep(mlbp_program* prog, const mlbp_sweep_args* a, bool flag
   const bool norm = a->normalize_messages != 0;
   SweepDev d;
   fill_sweep_dev(prog, a, &d);
-  d.approx_k = (a->flags & MLBP_SWEEP_APPROX_INFERENCE) ? MLBP_APPROX_K : 0;
   if (flagged_only) {                                // the graphs the padded lean pass flagged; it initialised none of them
     d.only = prog->d_bail;
     d.fill_uniform = a->init_messages;

@@ -124,6 +124,21 @@ def test_every_case_names_existing_workloads():
             assert len(roots) >= 3 and len(set(roots)) < len(roots), name    # three sweeps or more, a root repeated
 
 
+def test_every_wide_instance_that_can_select_has_an_approximate_case():
+    """The top-100 selection is fused into sweep_wide_kernel and approximate calls are normalised float64 ones: every
+    compiled sweep_wide_kernel<true, Q, double, 2, PAD> has a case of tests/test_gpu_approx.py that runs it with approx_k > 0.
+    A new padded instance without one fails here, without a GPU."""
+    import test_gpu_approx as GA
+    selecting = {i for i in K.compiled() if i[0] == 'sweep_wide_kernel' and i[1][0] is True and i[1][2:4] == ('double', 2)}
+    assert len(selecting) >= 15
+    assert selecting - set(GA.APPROX_CASES) == set(), 'wide instances without an approximate case: %s' % sorted(selecting - set(GA.APPROX_CASES), key=repr)
+    assert set(GA.APPROX_CASES) - selecting == set(), 'approximate cases for instances the library does not hold: %s' % sorted(set(GA.APPROX_CASES) - selecting, key=repr)
+    for inst, names in GA.APPROX_CASES.items():
+        assert names, inst
+        for n in names:
+            assert n in GA.CASES and GA.wide_instance(GA.CASES[n]['X']) == inst, (inst, n)
+
+
 @pytest.mark.parametrize('mangled,want', [
     ('_ZN12_GLOBAL__N_121sweep_x64_lean_kernelILi3ELb0ELb0ELi0ELb1EEEvN8mlbp_dev8SweepDevENS_7LeanDevEPKiiNS1_12GradFusedDevE',
      ('sweep_x64_lean_kernel', (3, False, False, 0, True))),
