@@ -347,6 +347,78 @@ class FactorGraphBatch:
         L.check(L.lib.mlbp_logz_f64(C.byref(a), _stream_ptr(self.device)))
         return log_z if labels is None else (log_z, joint)
 
+    # ---- posterior sampling of whole assignments (include/mlbp_sample.h) -----------------------------
+    def sample(self, roots, n_samples=1, seed=None, uniforms=None, order=None, given=None, cond_marginals=None):
+        """Draws n_samples whole assignments per graph by sequential conditioning: draw a variable from its marginal, clamp it,
+        run sweep(roots, init=True) again on the clamped model, draw the next.  Returns (samples int32 [S][B][n_vars] in
+        GraphTopology.var_ids order, logq float64 [S][B]) device tensors; logq is the exact log-probability of the draw under
+        the sampler -- score - log Z on a tree, a proper proposal distribution on a loopy graph.  Exactly one of `seed` and
+        `uniforms`: uniforms is a float64 [S][B][n_vars] device tensor of numbers in [0, 1), indexed by step; seed means
+        torch.rand((S, B, n_vars), dtype=float64, device=..., generator=torch.Generator(device).manual_seed(seed)).  order: a
+        list of variable ids (default: var_ids order), step k handles order[k]; given: [B][n_vars] integers, a state fixes
+        the variable, -1 draws it; cond_marginals: optional float64 [S][B][n_vars][X] device tensor that receives, per
+        variable, the conditional marginal it was drawn from.  self.msgs is left untouched."""
+        from . import sample as S_
+        if self.use_approx_inference:
+            raise NotImplementedError('sampling has no top-100 approximate form')
+        if self.pair_tables is not None and self.pair_tables.dtype != torch.float64:
+            raise NotImplementedError('sampling needs float64 pairwise tables')
+        if (seed is None) == (uniforms is None):
+            raise ValueError('give exactly one of seed and uniforms')
+        topo, S = self.topo, int(n_samples)
+        if S <= 0:
+            raise ValueError('n_samples must be positive')
+        if uniforms is None:
+            gen = torch.Generator(self.device).manual_seed(int(seed))
+            uniforms = torch.rand((S, self.B, topo.n_vars), dtype=torch.float64, device=self.device, generator=gen)
+        elif (not torch.is_tensor(uniforms) or uniforms.dtype != torch.float64 or uniforms.device != self.device
+              or tuple(uniforms.shape) != (S, self.B, topo.n_vars) or not uniforms.is_contiguous()):
+            raise ValueError('uniforms must be a contiguous float64 device tensor [n_samples][B][n_vars]')
+        prog = S_.program(topo, roots, self.device)
+        a = S_.SampleArgs()
+        a.B, a.X, a.n_msgs, a.P, a.U, a.n_vars = self.B, self.X, topo.n_msgs, topo.P, topo.U, topo.n_vars
+        a.n_ops, a.n_srcs, a.n_sweeps, a.S = prog.n_ops, prog.n_srcs, prog.n_sweeps, S
+        a.ops, a.srcs, a.sweeps = prog.ops.data_ptr(), prog.srcs.data_ptr(), prog.sweeps.data_ptr()
+        if topo.P:
+            if self.pair_tables is None:
+                raise RuntimeError('set_pair_tables() first')
+            a.n_pair_tables = self.pair_tables.shape[0]
+            a.pair_tables, a.pair_tab = self.pair_tables.data_ptr(), self.pair_tab.data_ptr()
+        if topo.U:
+            if self.unary_tables is None:
+                raise RuntimeError('set_unary_tables() first')
+            a.n_unary_tables = self.unary_tables.shape[0]
+            a.unary_tables, a.unary_tab = self.unary_tables.data_ptr(), self.unary_tab.data_ptr()
+        a.normalize_messages = 1 if self.normalize_messages else 0
+        a.in_off, a.in_slots, a.slot_var = prog.in_off.data_ptr(), prog.in_slots.data_ptr(), prog.slot_var.data_ptr()
+        a.order = prog.order(order).data_ptr()
+        a.uniforms = uniforms.data_ptr()
+        giv = None
+        if given is not None:
+            if torch.is_tensor(given) and given.dtype == torch.int32 and given.device == self.device and given.is_contiguous():
+                giv = given
+            else:
+                host = given.cpu().numpy() if torch.is_tensor(given) else np.asarray(given)
+                giv = torch.from_numpy(np.ascontiguousarray(host.astype(np.int64).astype(np.int32))).to(self.device)
+            if tuple(giv.shape) != (self.B, topo.n_vars):
+                raise ValueError('given must be [B][n_vars]')
+            a.given = giv.data_ptr()
+        need = S_.workspace_bytes(self.B, S, self.X, topo.n_msgs, topo.n_vars)
+        work = None
+        if need:
+            work = torch.empty(need // 8, dtype=torch.float64, device=self.device)
+            a.workspace, a.workspace_bytes = work.data_ptr(), need
+        if cond_marginals is not None:
+            if tuple(cond_marginals.shape) != (S, self.B, topo.n_vars, self.X) or cond_marginals.dtype != torch.float64 \
+                    or cond_marginals.device != self.device or not cond_marginals.is_contiguous():
+                raise ValueError('cond_marginals must be a contiguous float64 device tensor [n_samples][B][n_vars][X]')
+            a.cond_marginals = cond_marginals.data_ptr()
+        samples = torch.empty(S, self.B, topo.n_vars, dtype=torch.int32, device=self.device)
+        logq = torch.empty(S, self.B, dtype=torch.float64, device=self.device)
+        a.samples, a.logq = samples.data_ptr(), logq.data_ptr()
+        S_.check(S_.lib.mlbp_sample_f64(C.byref(a), _stream_ptr(self.device)))
+        return samples, logq
+
     def treelike_inference(self, iterations, roots):
         """`iterations` sweeps if the graph is loopy, else one (LBP.py:219); `roots` replaces the
         per-sweep random.sample draw (LBP.py:223).  Returns the number of sweeps run."""

@@ -1,4 +1,4 @@
-"""Builds libmlbp.so, libmlbp_map.so and libmlbp_logz.so (gfx950 only) in-tree with hipcc.  `python -m macaronicusermodeling_amd.build`.
+"""Builds libmlbp.so, libmlbp_map.so, libmlbp_logz.so and libmlbp_sample.so (gfx950 only) in-tree with hipcc.  `python -m macaronicusermodeling_amd.build`.
 
 hipcc cross-compiles without a GPU, so this runs in the build container; the resulting .so is
 git-ignored but travels to the GPU box with the working-tree snapshot.
@@ -19,6 +19,10 @@ SOURCES_MAP = ['mlbp_map.hip']
 CSRC_LOGZ = os.path.join(PKG, 'csrc_logz')
 LIB_LOGZ = os.path.join(PKG, 'libmlbp_logz.so')
 SOURCES_LOGZ = ['mlbp_logz.hip']
+# the posterior-sampling library (include/mlbp_sample.h): its own sources and inventory, the same flags
+CSRC_SAMPLE = os.path.join(PKG, 'csrc_sample')
+LIB_SAMPLE = os.path.join(PKG, 'libmlbp_sample.so')
+SOURCES_SAMPLE = ['mlbp_sample.hip']
 FLAGS = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-fno-fast-math', '-Wall',
          '-Wno-unused-function']
 
@@ -48,7 +52,7 @@ def _build_one(hipcc, csrc, sources, headers, lib, force, verbose):
 
 
 def build(force=False, verbose=False):
-    """Builds the three libraries; returns the path of libmlbp.so (the others lie beside it: LIB_MAP, LIB_LOGZ)."""
+    """Builds the four libraries; returns the path of libmlbp.so (the others lie beside it: LIB_MAP, LIB_LOGZ, LIB_SAMPLE)."""
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     headers = [os.path.join(CSRC, 'mlbp_internal.h'), os.path.join(CSRC, 'mlbp_device.h'), os.path.join(PKG, '..', 'include', 'mlbp.h')]
     lib = _build_one(hipcc, CSRC, SOURCES, headers, LIB, force, verbose)
@@ -56,6 +60,8 @@ def build(force=False, verbose=False):
     _build_one(hipcc, CSRC_MAP, SOURCES_MAP, headers_map, LIB_MAP, force, verbose)
     headers_logz = [os.path.join(CSRC, 'mlbp_device.h'), os.path.join(PKG, '..', 'include', 'mlbp_logz.h')]
     _build_one(hipcc, CSRC_LOGZ, SOURCES_LOGZ, headers_logz, LIB_LOGZ, force, verbose)
+    headers_sample = [os.path.join(CSRC, 'mlbp_device.h'), os.path.join(PKG, '..', 'include', 'mlbp_sample.h')]
+    _build_one(hipcc, CSRC_SAMPLE, SOURCES_SAMPLE, headers_sample, LIB_SAMPLE, force, verbose)
     return lib
 
 

@@ -258,6 +258,15 @@ class UserGraphTrainer:
         assignment, score = self.batch.map_sweep(self.roots[:self.n_sweeps_run], init=True, keep_messages=False)
         return assignment.cpu().numpy().astype(np.int64), score.cpu().numpy()
 
+    def sample(self, n_samples=1, seed=None, uniforms=None, given=None):
+        """Whole sets of guesses drawn from the model under the current thetas (sequential conditioning over the predict()
+        schedule, FactorGraphBatch.sample): host (samples int64 [S][B][n_vars] word indices in var_ids order, logq float64
+        [S][B] -- the exact log-probability of each draw under the sampler).  Exactly one of seed and uniforms; given:
+        [B][n_vars] word indices that are known, -1 for the words to draw."""
+        self.build_potentials()
+        samples, logq = self.batch.sample(self.roots[:self.n_sweeps_run], n_samples=n_samples, seed=seed, uniforms=uniforms, given=given)
+        return samples.cpu().numpy().astype(np.int64), logq.cpu().numpy()
+
     def joint_log_likelihood(self):
         """How probable the model finds each instance's whole set of stored labels, under the current thetas: host
         (joint_logp float64 [B], log_z float64 [B]).  Sum-product sweeps over the predict() schedule with the messages kept,
@@ -809,6 +818,22 @@ class TiDirTrainer:
         tot = torch.tensor([float(v) for v in counts], dtype=torch.float64, device=self.device)
         mdist.all_reduce_sum_(tot)
         return guesses, tuple(int(v) for v in tot.cpu().numpy())
+
+    # ---- posterior sampling of whole sets of guesses (the reference has none) --------------------------
+    def sample(self, n_samples=1, seed=0):
+        """-> per_instance.  per_instance[i], for instance i of this rank's shard in file order: (predicted positions, [[en
+        words] per sample], [logq per sample]) -- n_samples whole sets of guesses drawn from the model for the sentence
+        (UserGraphTrainer.sample) and the log-probability of each draw under the sampler; an instance without a predicted
+        word builds no graph and gives ((), [], []).  The i-th sentence shape in self.trainers order draws with seed
+        `seed + i`.  Every rank draws for its own shard: nothing is reduced."""
+        n = self._shard[1] - self._shard[0]
+        per_instance = [((), [], [])] * n
+        for i, (key, tr) in enumerate(self.trainers.items()):
+            x, logq = tr.sample(n_samples=n_samples, seed=int(seed) + i)
+            for b, row in enumerate(self.buckets[key]['rows']):
+                per_instance[row['index']] = (tuple(key[1]), [[self.en[w] for w in x[s, b]] for s in range(x.shape[0])],
+                                              [float(logq[s, b]) for s in range(x.shape[0])])
+        return per_instance
 
     # ---- joint log-likelihood (log Z; the reference has only the sum of per-word log-marginals) ------
     def joint_log_likelihood(self):
