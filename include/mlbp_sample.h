@@ -32,7 +32,9 @@
  *   3. m = renorm(uniform * msgs[in_slots[in_off[v]]] * ...), nan_to_num after every product, always normalised;
  *   4. x_v = given[g][v] when that is >= 0; otherwise, with c_i the inclusive prefix sum of m in index order,
  *      u = uniforms[s][g][k] and t = u * c_{X-1}:  x_v = the lowest i with c_i > t; when there is none, the highest i with
- *      m_i > 0.  A state of probability zero is never drawn;
+ *      m_i > 0.  A state of probability zero is never drawn -- except from the empty marginal: when no state has m_i > 0 (every
+ *      m_i is 0: with unnormalised messages a +inf table entry survives as DBL_MAX and the total of step 3 overflows),
+ *      x_v = 0 and, by step 5, logq = -inf; the later variables are drawn as usual;
  *   5. logq += log m[x_v]  (natural log; -inf for a given state of probability zero, after which step 2's renorm rule makes
  *      the emptied messages uniform);
  *   6. v is clamped to x_v.

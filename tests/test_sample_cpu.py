@@ -78,11 +78,15 @@ def step_marginal(g, inputs, roots, clamp, v, normalize=True):
 
 def draw(m, u):
     """Step 4 -> (state, margin): the lowest i with cumsum(m)_i > u * cumsum(m)_{X-1}, else the highest i with m_i > 0;
-    margin = min_i |c_i - t|."""
+    margin = min_i |c_i - t|.  The empty marginal (no m_i > 0) gives state 0 whatever u is: margin inf, as for a given
+    variable."""
     c = np.cumsum(m)
     t = u * c[-1]
     above = np.nonzero(c > t)[0]
-    x = int(above[0]) if len(above) else int(np.nonzero(m > 0)[0][-1])
+    positive = np.nonzero(m > 0)[0]
+    if not len(above) and not len(positive):
+        return 0, np.inf
+    x = int(above[0]) if len(above) else int(positive[-1])
     return x, float(np.abs(c - t).min())
 
 
@@ -515,11 +519,13 @@ def test_sample_library_kernels_are_the_sources_kernels_and_each_has_a_case():
     compiled = sample_kernels()
     assert {name for name, _ in compiled} == src
     assert compiled == {('sample_x64_kernel', (True,)), ('sample_x64_kernel', (False,)), ('sample_generic_kernel', ())}
-    assert set(G.CASES) == compiled, set(G.CASES) ^ compiled
-    for kern, tests in G.CASES.items():
-        assert tests, kern
-        for t in tests:
-            assert callable(getattr(G, t, None)), (kern, t)
+    import test_gpu_sample_edges as E
+    for module in (G, E):                                       # every instance has a case in each of the two GPU modules
+        assert set(module.CASES) == compiled, set(module.CASES) ^ compiled
+        for kern, tests in module.CASES.items():
+            assert tests, kern
+            for t in tests:
+                assert callable(getattr(module, t, None)), (kern, t)
 
 
 def test_the_other_libraries_hold_no_sample_kernel_and_the_sources_stay_apart():
