@@ -26,7 +26,9 @@
  *   always normalised;  assignment[v] = its argmax, ties to the LOWEST index;
  *   score = sum over pairwise factors p of log T_p[x[pair_axis_var[p][0]]][x[pair_axis_var[p][1]]]
  *         + sum over unary factors u of log row_u[x[unary_var[u]]]      (natural log, tables as given).
- * A maximum ignores NaN table entries (fmax); potentials are exp(.) and never NaN.
+ * A maximum ignores NaN table entries (fmax); potentials are exp(.) and never NaN.  The maximum over a row or column that
+ * holds no entry other than NaN is unspecified (NaN or -inf, by kernel); with normalize_messages != 0 either has no positive
+ * total and gives the uniform message.
  */
 #ifndef MLBP_MAP_H
 #define MLBP_MAP_H
@@ -47,7 +49,8 @@ enum { MLBP_OP_UNARY = 0, MLBP_OP_PAIR_TM = 1, MLBP_OP_PAIR_MT = 2, MLBP_OP_VAR 
  *   MLBP_MAP_KERNEL_X64      X == 64 and the graph's messages fit the kernel's LDS budget:
  *                              n_msgs * 512  (messages)  +  4608  (partial maxima and one raw vector)
  *                              +  4 * round_up(n_vars, 4)  (the assignment)   <=   MLBP_MAP_X64_LDS_BYTES
- *                            i.e. up to 151 message slots: two workgroups share a CU's 160 KB.  Messages stay in LDS for the
+ *                            i.e. up to 150 message slots (151 slots and the assignment make 81 936 bytes): two workgroups
+ *                            share a CU's 160 KB.  Messages stay in LDS for the
  *                            whole launch; with P <= 3 the pairwise tables stay in registers (read once per launch),
  *                            beyond that they are streamed per update.
  *   MLBP_MAP_KERNEL_GENERIC  every other shape (2 <= X <= 1024): messages in global memory, tables streamed.

@@ -64,12 +64,13 @@ def _run(fb, roots, init=True, keep_messages=True):
     return dict(x=x.cpu().numpy(), score=score.cpu().numpy(), mm=mm.cpu().numpy(), msgs=fb.msgs.cpu().numpy(), kernel=kernel)
 
 
-def _compare(name, spec, topo, inputs_list, roots, got, graphs=None, may_omit=0, normalize=True, messages=True):
-    """Device results against the walk, graph by graph; returns the walks.  Prints the figures before it asserts."""
+def _compare(name, spec, topo, inputs_list, roots, got, graphs=None, may_omit=0, normalize=True, messages=True, ref=None):
+    """Device results against the walk, graph by graph; returns the walks.  Prints the figures before it asserts.
+    ref: {graph: walk} computed beforehand on the same inputs, roots and `normalize` (read, never written)."""
     keys = C.msg_keys(spec)
     omitted, min_gap, wrong, walks = 0, np.inf, [], {}
     for b in (range(len(inputs_list)) if graphs is None else graphs):
-        w = walks[b] = W.walk(spec, inputs_list[b], roots, normalize=normalize)
+        w = walks[b] = W.walk(spec, inputs_list[b], roots, normalize=normalize) if ref is None else ref[b]
         if messages:
             np.testing.assert_allclose(got['msgs'][b], np.stack([w['msgs'][k] for k in keys]), rtol=1e-10, atol=1e-300, err_msg='%s graph %d' % (name, b))
         np.testing.assert_allclose(got['mm'][b], np.stack([w['mm'][v] for v in topo.var_ids]), rtol=1e-10, atol=1e-300, err_msg='%s graph %d' % (name, b))

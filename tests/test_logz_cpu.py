@@ -379,11 +379,13 @@ def test_logz_library_kernels_are_the_sources_kernels_and_each_has_a_case():
     assert src == {'logz_x64_kernel', 'logz_x64_shared_kernel', 'logz_generic_kernel', 'logz_sum_kernel'}
     compiled = logz_kernels()
     assert {name for name, _ in compiled} == src and len(compiled) == len(src)
-    assert set(G.CASES) == compiled, set(G.CASES) ^ compiled
-    for kern, tests in G.CASES.items():
-        assert tests, kern
-        for t in tests:
-            assert callable(getattr(G, t, None)), (kern, t)
+    import test_gpu_logz_edges as E
+    for module in (G, E):                                       # every kernel has a case in each of the two GPU modules
+        assert set(module.CASES) == compiled, set(module.CASES) ^ compiled
+        for kern, tests in module.CASES.items():
+            assert tests, kern
+            for t in tests:
+                assert callable(getattr(module, t, None)), (kern, t)
 
 
 def test_the_other_libraries_hold_no_logz_kernel_and_the_sources_stay_apart():

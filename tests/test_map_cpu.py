@@ -28,7 +28,8 @@ def _finish(v, normalize):
 
 
 def mp_factor_to_var(g, inputs, msgs, fid, v, normalize=True):
-    """O.factor_to_var with max in place of the contraction's sum."""
+    """O.factor_to_var with max in place of the contraction's sum.  The maximum is the header's: it ignores NaN entries
+    (np.fmax; on NaN-free input np.fmax.reduce and ndarray.max return the same bits)."""
     f = g.by_id[fid]
     T = O.factor_table(g, inputs, f)
     if len(f['vars']) == 1:
@@ -37,9 +38,9 @@ def mp_factor_to_var(g, inputs, msgs, fid, v, normalize=True):
         other = [u for u in f['vars'] if u != v][0]
         m = msgs['X_%d' % other, 'F_%d' % fid]
         if g.dim_of(f, other) == 1:
-            out = (T * m[None, :]).max(1)
+            out = np.fmax.reduce(T * m[None, :], axis=1)
         else:
-            out = (m[:, None] * T).max(0)
+            out = np.fmax.reduce(m[:, None] * T, axis=0)
     msgs['F_%d' % fid, 'X_%d' % v] = _finish(out, normalize)
 
 
@@ -264,10 +265,11 @@ def test_kernel_choice_is_the_rule_of_the_header():
     def rule(X, n_msgs, n_vars):
         fits = n_msgs * 512 + 4608 + 4 * ((n_vars + 3) // 4 * 4) <= M.X64_LDS_BYTES
         return M.KERNEL_X64 if X == 64 and fits else M.KERNEL_GENERIC
-    for X, n_msgs, n_vars in ((64, 27, 3), (64, 126, 7), (64, 151, 4), (64, 152, 4), (64, 288, 12), (63, 27, 3), (128, 27, 3),
+    for X, n_msgs, n_vars in ((64, 27, 3), (64, 126, 7), (64, 150, 4), (64, 151, 4), (64, 152, 4), (64, 288, 12), (63, 27, 3), (128, 27, 3),
                               (2, 1, 1), (1024, 5, 2), (8, 13, 5)):
         assert M.pick_kernel(X, n_msgs, n_vars) == rule(X, n_msgs, n_vars), (X, n_msgs, n_vars)
     assert M.pick_kernel(64, 126, 7) == M.KERNEL_X64 and M.pick_kernel(64, 288, 12) == M.KERNEL_GENERIC      # K7, K12
+    assert M.pick_kernel(64, 150, 4) == M.KERNEL_X64 and M.pick_kernel(64, 151, 4) == M.KERNEL_GENERIC       # 151 slots + the assignment: 81 936 B
     assert M.lib.mlbp_map_pick_kernel(1025, 5, 2) == _ffi.MLBP_EUNSUPPORTED
     assert M.lib.mlbp_map_pick_kernel(1, 5, 2) == _ffi.MLBP_EINVAL
 
@@ -353,11 +355,13 @@ def test_map_library_kernels_are_the_sources_kernels_and_each_has_a_case():
     assert src == {'map_sweep_x64_kernel', 'map_sweep_generic_kernel'}
     compiled = map_kernels()
     assert {name for name, _ in compiled} == src
-    assert set(G.CASES) == compiled, set(G.CASES) ^ compiled
-    for kern, tests in G.CASES.items():
-        assert tests, kern
-        for t in tests:
-            assert callable(getattr(G, t, None)), (kern, t)
+    import test_gpu_map_edges as E
+    for module in (G, E):                                       # every instance has a case in each of the two GPU modules
+        assert set(module.CASES) == compiled, set(module.CASES) ^ compiled
+        for kern, tests in module.CASES.items():
+            assert tests, kern
+            for t in tests:
+                assert callable(getattr(module, t, None)), (kern, t)
 
 
 def test_first_library_holds_no_map_kernel_and_the_sources_stay_apart():
