@@ -419,6 +419,60 @@ class FactorGraphBatch:
         S_.check(S_.lib.mlbp_sample_f64(C.byref(a), _stream_ptr(self.device)))
         return samples, logq
 
+    # ---- sweeps to convergence (include/mlbp_converge.h) ---------------------------------------------
+    def converge(self, roots=None, tol=1e-6, max_rounds=50, init=True, marginals=None, history=False):
+        """Repeats the sum-product sweeps of `roots` (default: every variable once, GraphTopology.var_ids order) -- one ROUND --
+        until a whole round changes no message entry by more than tol, graph by graph, in one launch; a graph that has
+        settled stops on its own.  Returns (rounds int32 [B], residual float64 [B]) device tensors -- the rounds each graph ran
+        (at most max_rounds) and its last round's residual, so residual <= tol says it converged -- or (rounds, residual,
+        history float64 [B][max_rounds]) with history=True: the residual of every round run, -1.0 beyond rounds.  The final
+        messages are left in self.msgs: marginals(), log_partition(roots=None), pair_beliefs() and gradient() then read the
+        converged messages.  init=False continues from what self.msgs holds; marginals: optional [B][n_vars][X] device tensor.
+        tol = 0 stops only at an exact fixed point (a tree reaches one in its second round)."""
+        from . import converge as V
+        if self.use_approx_inference:
+            raise NotImplementedError('converge has no top-100 approximate form')
+        if self.pair_tables is not None and self.pair_tables.dtype != torch.float64:
+            raise NotImplementedError('converge needs float64 pairwise tables')
+        if not self.normalize_messages:
+            raise ValueError('converge needs normalised messages: a residual on unnormalised messages has no scale')
+        topo = self.topo
+        prog = V.program(topo, topo.var_ids if roots is None else roots, self.device)
+        a = V.ConvergeArgs()
+        a.B, a.X, a.n_msgs, a.P, a.U, a.n_vars = self.B, self.X, topo.n_msgs, topo.P, topo.U, topo.n_vars
+        a.n_ops, a.n_srcs, a.n_sweeps = prog.n_ops, prog.n_srcs, prog.n_sweeps
+        a.ops, a.srcs, a.sweeps = prog.ops.data_ptr(), prog.srcs.data_ptr(), prog.sweeps.data_ptr()
+        if topo.P:
+            if self.pair_tables is None:
+                raise RuntimeError('set_pair_tables() first')
+            a.n_pair_tables = self.pair_tables.shape[0]
+            a.pair_tables, a.pair_tab = self.pair_tables.data_ptr(), self.pair_tab.data_ptr()
+        if topo.U:
+            if self.unary_tables is None:
+                raise RuntimeError('set_unary_tables() first')
+            a.n_unary_tables = self.unary_tables.shape[0]
+            a.unary_tables, a.unary_tab = self.unary_tables.data_ptr(), self.unary_tab.data_ptr()
+        a.normalize_messages, a.init_messages = 1, (1 if init else 0)
+        a.max_rounds, a.tol = int(max_rounds), float(tol)
+        a.in_off, a.in_slots = prog.in_off.data_ptr(), prog.in_slots.data_ptr()
+        a.msgs = self.msgs.data_ptr()
+        if marginals is not None:
+            if tuple(marginals.shape) != (self.B, topo.n_vars, self.X) or marginals.dtype != torch.float64 \
+                    or marginals.device != self.device or not marginals.is_contiguous():
+                raise ValueError('marginals must be a contiguous float64 device tensor [B][n_vars][X]')
+            a.marginals = marginals.data_ptr()
+        rounds = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        residual = torch.empty(self.B, dtype=torch.float64, device=self.device)
+        a.rounds, a.residual = rounds.data_ptr(), residual.data_ptr()
+        hist = None
+        if history:
+            if not 1 <= int(max_rounds) <= V.MAX_ROUNDS:
+                raise ValueError('max_rounds must be in [1, %d]' % V.MAX_ROUNDS)
+            hist = torch.empty(self.B, int(max_rounds), dtype=torch.float64, device=self.device)
+            a.history = hist.data_ptr()
+        V.check(V.lib.mlbp_converge_f64(C.byref(a), _stream_ptr(self.device)))
+        return (rounds, residual, hist) if history else (rounds, residual)
+
     def treelike_inference(self, iterations, roots):
         """`iterations` sweeps if the graph is loopy, else one (LBP.py:219); `roots` replaces the
         per-sweep random.sample draw (LBP.py:223).  Returns the number of sweeps run."""

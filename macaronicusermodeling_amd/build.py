@@ -1,4 +1,4 @@
-"""Builds libmlbp.so, libmlbp_map.so, libmlbp_logz.so and libmlbp_sample.so (gfx950 only) in-tree with hipcc.  `python -m macaronicusermodeling_amd.build`.
+"""Builds libmlbp.so, libmlbp_map.so, libmlbp_logz.so, libmlbp_sample.so and libmlbp_converge.so (gfx950 only) in-tree with hipcc.  `python -m macaronicusermodeling_amd.build`.
 
 hipcc cross-compiles without a GPU, so this runs in the build container; the resulting .so is
 git-ignored but travels to the GPU box with the working-tree snapshot.
@@ -23,6 +23,10 @@ SOURCES_LOGZ = ['mlbp_logz.hip']
 CSRC_SAMPLE = os.path.join(PKG, 'csrc_sample')
 LIB_SAMPLE = os.path.join(PKG, 'libmlbp_sample.so')
 SOURCES_SAMPLE = ['mlbp_sample.hip']
+# the sweeps-to-convergence library (include/mlbp_converge.h): its own sources and inventory, the same flags
+CSRC_CONVERGE = os.path.join(PKG, 'csrc_converge')
+LIB_CONVERGE = os.path.join(PKG, 'libmlbp_converge.so')
+SOURCES_CONVERGE = ['mlbp_converge.hip']
 FLAGS = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-fno-fast-math', '-Wall',
          '-Wno-unused-function']
 
@@ -52,7 +56,8 @@ def _build_one(hipcc, csrc, sources, headers, lib, force, verbose):
 
 
 def build(force=False, verbose=False):
-    """Builds the four libraries; returns the path of libmlbp.so (the others lie beside it: LIB_MAP, LIB_LOGZ, LIB_SAMPLE)."""
+    """Builds the five libraries; returns the path of libmlbp.so (the others lie beside it: LIB_MAP, LIB_LOGZ, LIB_SAMPLE,
+    LIB_CONVERGE)."""
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     headers = [os.path.join(CSRC, 'mlbp_internal.h'), os.path.join(CSRC, 'mlbp_device.h'), os.path.join(PKG, '..', 'include', 'mlbp.h')]
     lib = _build_one(hipcc, CSRC, SOURCES, headers, LIB, force, verbose)
@@ -62,6 +67,8 @@ def build(force=False, verbose=False):
     _build_one(hipcc, CSRC_LOGZ, SOURCES_LOGZ, headers_logz, LIB_LOGZ, force, verbose)
     headers_sample = [os.path.join(CSRC, 'mlbp_device.h'), os.path.join(PKG, '..', 'include', 'mlbp_sample.h')]
     _build_one(hipcc, CSRC_SAMPLE, SOURCES_SAMPLE, headers_sample, LIB_SAMPLE, force, verbose)
+    headers_converge = [os.path.join(CSRC, 'mlbp_device.h'), os.path.join(PKG, '..', 'include', 'mlbp_converge.h')]
+    _build_one(hipcc, CSRC_CONVERGE, SOURCES_CONVERGE, headers_converge, LIB_CONVERGE, force, verbose)
     return lib
 
 

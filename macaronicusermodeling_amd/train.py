@@ -267,6 +267,20 @@ class UserGraphTrainer:
         samples, logq = self.batch.sample(self.roots[:self.n_sweeps_run], n_samples=n_samples, seed=seed, uniforms=uniforms, given=given)
         return samples.cpu().numpy().astype(np.int64), logq.cpu().numpy()
 
+    def convergence(self, tol=1e-6, max_rounds=50):
+        """What stopping at the trainer's own n_sweeps_run sweeps cost each instance, under the current thetas: host (rounds
+        int32 [B], residual float64 [B], gap float64 [B]).  rounds and residual are FactorGraphBatch.converge's over rounds of
+        every predicted variable as a root once (residual <= tol: the instance converged within max_rounds); gap is the
+        largest |marginal after the predict() schedule - marginal at convergence| over variables and states."""
+        fb = self.batch
+        self.build_potentials()
+        fb.sweep(self.roots[:self.n_sweeps_run], init=True, marginals=self._marg)
+        stopped = self._marg.cpu().numpy()
+        settled = torch.empty_like(self._marg)
+        rounds, residual = fb.converge(tol=tol, max_rounds=max_rounds, init=True, marginals=settled)
+        gap = np.abs(stopped - settled.cpu().numpy()).reshape(fb.B, -1).max(axis=1)
+        return rounds.cpu().numpy(), residual.cpu().numpy(), gap
+
     def joint_log_likelihood(self):
         """How probable the model finds each instance's whole set of stored labels, under the current thetas: host
         (joint_logp float64 [B], log_z float64 [B]).  Sum-product sweeps over the predict() schedule with the messages kept,
@@ -834,6 +848,29 @@ class TiDirTrainer:
                 per_instance[row['index']] = (tuple(key[1]), [[self.en[w] for w in x[s, b]] for s in range(x.shape[0])],
                                               [float(logq[s, b]) for s in range(x.shape[0])])
         return per_instance
+
+    # ---- sweeps to convergence (the reference stops at three sweeps and never looks) -------------------
+    def convergence_report(self, tol=1e-6, max_rounds=50):
+        """-> (per_instance, totals).  per_instance[i], for instance i of this rank's shard in file order: (predicted
+        positions, rounds, residual, gap) as UserGraphTrainer.convergence gives them; an instance without a predicted word
+        builds no graph and gives ((), 0, 0.0, 0.0).  totals = (sentences with a predicted word, sentences whose residual is
+        still above tol after max_rounds, sum of rounds, sum of gap) over ALL ranks' instances, reduced once."""
+        n = self._shard[1] - self._shard[0]
+        per_instance = [((), 0, 0.0, 0.0)] * n
+        seen = open_ = total_rounds = 0
+        total_gap = 0.0
+        for key, tr in self.trainers.items():
+            rounds, residual, gap = tr.convergence(tol=tol, max_rounds=max_rounds)
+            seen += rounds.shape[0]
+            open_ += int((~(residual <= tol)).sum())
+            total_rounds += int(rounds.sum())
+            total_gap += float(gap.sum())
+            for b, row in enumerate(self.buckets[key]['rows']):
+                per_instance[row['index']] = (tuple(key[1]), int(rounds[b]), float(residual[b]), float(gap[b]))
+        tot = torch.tensor([float(seen), float(open_), float(total_rounds), total_gap], dtype=torch.float64, device=self.device)
+        mdist.all_reduce_sum_(tot)
+        tot = tot.cpu().numpy()
+        return per_instance, (int(tot[0]), int(tot[1]), int(tot[2]), float(tot[3]))
 
     # ---- joint log-likelihood (log Z; the reference has only the sum of per-word log-marginals) ------
     def joint_log_likelihood(self):

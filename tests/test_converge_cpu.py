@@ -1,0 +1,520 @@
+"""Sweeps to convergence without a GPU: the float64 NumPy walk the GPU tests compare against, pinned on things it does not
+define itself; the inputs of the GPU cases and the margin their exact `rounds` comparison relies on; the C ABI of
+libmlbp_converge.so and its host checks; and the kernel inventory rule applied to the fifth library.
+
+The walk is the semantics of include/mlbp_converge.h written with the oracle's own functions: schedule, initial messages and
+every update are oracle/lbp_oracle.py's (O._send, untouched); the walk only looks at a slot before and after each update.
+A round runs O.sweep's two passes for every root in turn; delta = max_i |new_i - old_i| (NaN on both sides: 0, on one: +inf);
+the residual of a round is the largest delta; a graph stops after the first round with residual <= tol.
+
+Why `rounds` may be compared exactly on the GPU.  Every GPU case uses tol = 1e-6.  The project's bar of 1e-10 relative on
+messages (entries in [0, 1]) bounds the disagreement of a residual -- a difference of two entries -- by 2e-10 = 2e-4 * tol.
+So the device takes the walk's stop decision in every round whenever no residual of any round of the walk lies within
+MARGIN = 1e-3 * tol of tol.  test_no_residual_of_a_gpu_case_is_near_tol asserts that for every graph and round of every case
+before any device is involved; no graph may be left out."""
+import ctypes
+import functools
+import os
+import re
+
+import numpy as np
+import pytest
+
+import cases as C
+import helpers
+import kernel_inventory as K
+import test_map_cpu as W
+from conftest import ROOT
+from oracle import lbp_oracle as O
+
+TOL = 1e-6
+MARGIN = 1e-3 * TOL
+
+
+# ------------------------------------------------------------------------------------------------
+# the NumPy walk
+# ------------------------------------------------------------------------------------------------
+def _delta(new, old):
+    """max_i |new_i - old_i|; an entry that is NaN before and after has not moved, NaN on one side only counts as +inf."""
+    with np.errstate(all='ignore'):
+        d = np.abs(new - old)
+    both, either = np.isnan(new) & np.isnan(old), np.isnan(new) | np.isnan(old)
+    if (either & ~both).any() or (np.isnan(d) & ~either).any():
+        return float('inf')
+    return float(np.where(both, 0.0, d).max())
+
+
+def _send(g, inputs, msgs, frm, to):
+    """O._send, and the delta of the slot it wrote (0.0 for the send the reference skips: a variable to a unary factor)."""
+    if to[0] == O.FAC and len(g.by_id[to[1]]['vars']) < 2:
+        return 0.0
+    key = (O.name(frm), O.name(to))
+    old = msgs[key].copy()
+    with np.errstate(all='ignore'):
+        O._send(g, inputs, msgs, frm, to, False)
+    return _delta(msgs[key], old)
+
+
+def one_round(g, inputs, msgs, roots):
+    """The program's sweeps in order (O.sweep's two passes per root); -> the round's residual."""
+    res = 0.0
+    for r in roots:
+        sched = O.message_schedule(g, r)
+        for child, parent in reversed(sched):
+            res = max(res, _send(g, inputs, msgs, child, parent))
+        for child, parent in sched:
+            res = max(res, _send(g, inputs, msgs, parent, child))
+    return res
+
+
+def walk(spec, inputs, roots=None, tol=TOL, max_rounds=50, msgs=None, extra=0):
+    """One graph.  roots: variable ids (default: every variable once, g.var_order); msgs: continue from these (a dict as
+    O.init_messages gives it; it is updated in place), default uniform.  -> dict(g, msgs, rounds, residual, history
+    [residual of every round run], marginals {v: vector}, after [the residuals of `extra` further rounds, run on a copy])."""
+    g = O.Graph(spec)
+    roots = list(g.var_order) if roots is None else list(roots)
+    msgs = O.init_messages(g) if msgs is None else msgs
+    history = []
+    while True:
+        history.append(one_round(g, inputs, msgs, roots))
+        if history[-1] <= tol or len(history) >= max_rounds:
+            break
+    with np.errstate(all='ignore'):
+        marginals = {v: O.marginal(g, msgs, v) for v in g.var_order}
+    more, after = {k: v.copy() for k, v in msgs.items()}, []
+    for _ in range(extra):
+        after.append(one_round(g, inputs, more, roots))
+    return dict(g=g, msgs=msgs, rounds=len(history), residual=history[-1], history=history, marginals=marginals, after=after)
+
+
+def exact_marginals(g, inputs):
+    """{v: marginal} by summing all X^n assignments."""
+    _, _, grid = W.brute_force(g, inputs)
+    w = np.exp(grid - grid.max())
+    out = {}
+    for i, v in enumerate(g.var_order):
+        m = w.sum(axis=tuple(k for k in range(w.ndim) if k != i))
+        out[v] = m / m.sum()
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# graphs and inputs
+# ------------------------------------------------------------------------------------------------
+def clique_spec(n, X, name=None):
+    """K_n: n unary factors (ids 0..n-1), then one pairwise factor per pair a < b with a on table axis 0."""
+    factors = [dict(id=i, vars=[i], dims=[0], table=i) for i in range(n)]
+    for a in range(n):
+        for b in range(a + 1, n):
+            factors.append(dict(id=len(factors), vars=[a, b], dims=[0, 1], table=len(factors)))
+    return dict(name=name or 'k%d_x%d' % (n, X), style='explicit', X=X, var_ids=list(range(n)), labels=[0] * n, factors=factors)
+
+
+def scaled_inputs(spec, s, seed):
+    """Explicit tables exp(s * N(0,1)): the coupling grows with s."""
+    rs = np.random.RandomState(seed)
+    X = spec['X']
+    tables = [None] * (1 + max(f['table'] for f in spec['factors']))
+    for f in sorted(spec['factors'], key=lambda f: f['table']):
+        tables[f['table']] = np.exp(s * rs.randn(*((X, X) if len(f['vars']) == 2 else (X, 1))))
+    return dict(tables=tables)
+
+
+# name -> (spec, [(s, seed) per graph], max_rounds); tests/test_gpu_converge.py runs exactly these, roots = every variable once
+GPU_CASES = {
+    'k3_x64': (lambda: clique_spec(3, 64), [(0.5, 0), (0.5, 1), (2, 0), (2, 1), (4, 0), (4, 1)], 12),
+    'k4_x64': (lambda: clique_spec(4, 64), [(0.5, 0), (2, 0), (4, 2), (4, 0)], 12),
+    'ring4_x4': (lambda: C.ring_spec(4, 4), [(0.5, 0), (2, 0), (4, 0)], 12),
+    'k3_x65': (lambda: clique_spec(3, 65), [(0.5, 0), (2, 0), (4, 0)], 12),
+    'k3_x301': (lambda: clique_spec(3, 301), [(0.5, 0), (2, 0), (4, 0)], 12),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def gpu_case(name):
+    """(spec, [inputs per graph], [walk per graph (with one further round)], max_rounds) -- computed once, shared, never changed."""
+    make, graphs, max_rounds = GPU_CASES[name]
+    spec = make()
+    inputs = [scaled_inputs(spec, s, seed) for s, seed in graphs]
+    walks = [walk(spec, inp, tol=TOL, max_rounds=max_rounds, extra=1) for inp in inputs]
+    return spec, inputs, walks, max_rounds
+
+
+def nearest_to_tol(walks):
+    return min(abs(r - TOL) for w in walks for r in w['history'])
+
+
+# ------------------------------------------------------------------------------------------------
+# the walk, pinned
+# ------------------------------------------------------------------------------------------------
+def _trees():
+    out = [('chain4_x4', C.chain_spec(4, 4)), ('star4_x4', C.star_spec(4, 4)), ('star5_x3', C.star_spec(5, 3))]
+    return out + [(s['name'], s) for s in W.random_trees()[:6]]
+
+
+def test_trees_converge_in_two_rounds_to_the_exact_marginals():
+    """On a tree one sweep already reaches the fixed point; the second round recomputes every message from the same inputs:
+    rounds == 2 and residual == 0.0 at tol = 0, and the marginals are those of exhaustive enumeration."""
+    trees = _trees()
+    assert len(trees) >= 6
+    for i, (name, spec) in enumerate(trees):
+        for kind in ('uniform', 'lognormal'):
+            inputs = C.make_inputs(spec, 10 + i, kind)
+            w = walk(spec, inputs, tol=0.0, max_rounds=5)
+            assert not O.has_loops(w['g'], w['g'].var_order[0])
+            assert w['rounds'] == 2 and w['residual'] == 0.0 and w['history'][0] > 0.0, (name, w['history'])
+            exact = exact_marginals(w['g'], inputs)
+            for v in w['g'].var_order:
+                np.testing.assert_allclose(w['marginals'][v], exact[v], rtol=1e-12, atol=1e-12, err_msg='%s variable %d' % (name, v))
+
+
+def test_one_round_is_the_oracles_sweeps_bit_for_bit():
+    for name in ('k3_x64', 'ring4_x4'):
+        spec, inputs, _, _ = gpu_case(name)
+        for roots in (None, [spec['var_ids'][-1], spec['var_ids'][0]]):
+            w = walk(spec, inputs[1], roots=roots, max_rounds=1)
+            _, want, _ = helpers.oracle_msgs(spec, inputs[1], list(w['g'].var_order) if roots is None else roots)
+            assert w['rounds'] == 1 and set(w['msgs']) == set(want)
+            for k in want:
+                assert np.array_equal(w['msgs'][k], want[k]), (name, k)
+
+
+def test_continuing_is_the_same_walk():
+    """max_rounds = 3, then msgs handed back for more rounds == one walk: the history is the concatenation, bit for bit."""
+    spec, inputs, walks, max_rounds = gpu_case('k3_x64')
+    first = walk(spec, inputs[2], max_rounds=3)
+    assert first['rounds'] == 3 and first['residual'] > TOL
+    rest = walk(spec, inputs[2], max_rounds=max_rounds - 3, msgs=first['msgs'])
+    assert first['history'] + rest['history'] == walks[2]['history']
+
+
+def test_the_round_after_the_last_moves_no_more_than_the_last():
+    for name in GPU_CASES:
+        _, _, walks, max_rounds = gpu_case(name)
+        for b, w in enumerate(walks):
+            assert w['after'][0] <= w['residual'], (name, b, w['residual'], w['after'])
+
+
+def test_no_residual_of_a_gpu_case_is_near_tol():
+    for name in GPU_CASES:
+        _, _, walks, max_rounds = gpu_case(name)
+        rounds = [w['rounds'] for w in walks]
+        print('%s: rounds %r, last residuals %s, nearest residual to tol %.3e (margin %.0e)'
+              % (name, rounds, ['%.2e' % w['residual'] for w in walks], nearest_to_tol(walks), MARGIN))
+        for b, w in enumerate(walks):                    # every graph, every round
+            for r in w['history']:
+                assert np.isfinite(r) and abs(r - TOL) > MARGIN, (name, b, w['history'])
+            assert 1 <= w['rounds'] <= max_rounds and (w['residual'] <= TOL or w['rounds'] == max_rounds)
+    # the mixed batch is mixed: weakly coupled graphs stop early, a strongly coupled one is still moving at max_rounds
+    _, _, walks, max_rounds = gpu_case('k3_x64')
+    rounds = [w['rounds'] for w in walks]
+    assert min(rounds) <= 4 and len(set(rounds)) >= 3, rounds
+    assert any(w['rounds'] == max_rounds and w['residual'] > TOL for w in walks), rounds
+
+
+def test_the_wider_sweep_of_couplings_keeps_the_margin():
+    """K3 / K4 at X = 64 and ring n = 4 / K4 at X = 4 / 2, s in {0.5, 2, 4}, seeds 0..5: how many rounds three sweeps are
+    short of, and that the margin condition is not an accident of the GPU cases' seeds."""
+    shapes = [clique_spec(3, 64), clique_spec(4, 64), C.ring_spec(4, 4), C.ring_spec(4, 2), clique_spec(4, 4), clique_spec(4, 2)]
+    nearest = np.inf
+    for spec in shapes:
+        for s in (0.5, 2, 4):
+            walks = [walk(spec, scaled_inputs(spec, s, seed), max_rounds=12) for seed in range(6)]
+            nearest = min(nearest, nearest_to_tol(walks))
+            print('%s s=%g: rounds %r' % (spec['name'], s, [w['rounds'] if w['residual'] <= TOL else '>12' for w in walks]))
+    print('nearest residual to tol: %.3e (%.2f %% of tol away)' % (nearest, 100 * nearest / TOL))
+    assert nearest > MARGIN
+
+
+def test_non_finite_and_empty_tables():
+    """NaN or all-zero pairwise table: the emptied message becomes uniform and every message stays finite.  +inf: inf / inf leaves
+    one NaN entry in a factor->variable message (the oracle's own arithmetic, shared by every library of the engine); the first
+    round's residual is +inf by the header's rule (uniform -> NaN), a NaN that stays NaN has not moved, so the graph can still
+    settle; the marginals stay finite (nan_to_num after every product)."""
+    spec = clique_spec(3, 8)
+    pair = [f['table'] for f in spec['factors'] if len(f['vars']) == 2][1]
+    for what in ('nan', 'zero', 'inf'):
+        inputs = scaled_inputs(spec, 1.0, 3)
+        if what == 'zero':
+            inputs['tables'][pair][:] = 0.0
+        else:
+            inputs['tables'][pair][3, 5] = dict(nan=np.nan, inf=np.inf)[what]
+        w = walk(spec, inputs, max_rounds=6)
+        finite = all(np.isfinite(m).all() for m in w['msgs'].values())
+        assert all(np.isfinite(m).all() for m in w['marginals'].values())
+        if what == 'inf':
+            assert not finite and np.isposinf(w['history'][0]) and np.isfinite(w['history'][1:]).all()
+            assert w['rounds'] >= 2 and w['residual'] <= TOL
+        else:
+            assert finite and np.isfinite(w['history']).all()
+
+
+# ------------------------------------------------------------------------------------------------
+# the header's op rules, op by op: for programs no graph's schedule produces
+# ------------------------------------------------------------------------------------------------
+def run_ops(ops, srcs, sweeps, pair, unary, n_msgs, X, tol=TOL, max_rounds=50):
+    """include/mlbp_converge.h steps 0 to 3 on one graph's tables (pair [P][X][X], unary [U][X]) from uniform messages, with
+    no shortcut: every op of every round runs.  -> (msgs [n_msgs][X], history)."""
+    msgs = np.full((n_msgs, X), 1.0 / X)
+    history = []
+    while True:
+        res = 0.0
+        for first, count in np.asarray(sweeps).reshape(-1, 2):
+            for kind, a, b, c in np.asarray(ops).reshape(-1, 4)[first:first + count]:
+                if kind == 0:
+                    out = unary[a].copy()
+                elif kind == 1:
+                    out = pair[a].dot(msgs[b])
+                elif kind == 2:
+                    out = msgs[b].dot(pair[a])
+                else:
+                    out = np.full(X, 1.0 / X)
+                    for q in srcs[a:a + b]:
+                        out = np.nan_to_num(msgs[q] * out)
+                fresh = O.renormalize(out)
+                res = max(res, _delta(fresh, msgs[c]))
+                msgs[c] = fresh
+        history.append(res)
+        if res <= tol or len(history) >= max_rounds:
+            return msgs, history
+
+
+def two_rows_one_slot(ops):
+    """A program the host check admits and no schedule produces: the LAST unary op that writes the slot of the first unary op
+    reads the next unary slot instead, so the slot's content changes inside every round and none of its writers may be skipped."""
+    ops = np.array(ops).reshape(-1, 4).copy()
+    unary_ops = np.nonzero(ops[:, 0] == 0)[0]
+    slot = ops[unary_ops[0], 3]
+    writers = [o for o in unary_ops if ops[o, 3] == slot]
+    assert len(writers) >= 2
+    n_unary = 1 + ops[unary_ops, 1].max()
+    ops[writers[-1], 1] = (ops[writers[-1], 1] + 1) % n_unary
+    return ops, int(slot)
+
+
+def test_op_rules_are_the_walk_and_a_slot_with_two_rows_never_settles():
+    from macaronicusermodeling_amd.topology import GraphTopology
+    spec, inputs, walks, max_rounds = gpu_case('k3_x64')
+    topo = GraphTopology.from_spec(spec)
+    ops, srcs, sweeps = topo.compile_program(list(topo.var_ids))
+    pair, unary = helpers.batch_tables(spec, topo, [inputs[0]])
+    msgs, history = run_ops(ops, srcs, sweeps, pair, unary, topo.n_msgs, 64, max_rounds=max_rounds)
+    assert len(history) == walks[0]['rounds']
+    np.testing.assert_allclose(history, walks[0]['history'], rtol=0, atol=1e-12)
+    np.testing.assert_allclose(msgs, np.stack([walks[0]['msgs'][k] for k in topo.slot_keys()]), rtol=1e-12)
+    bad, slot = two_rows_one_slot(ops)
+    assert _V().check_program(bad, srcs, sweeps, topo.n_msgs, topo.P, topo.U) == 0
+    _, history = run_ops(bad, srcs, sweeps, pair, unary, topo.n_msgs, 64, max_rounds=6)
+    assert len(history) == 6 and min(history) > 1e-3 and abs(history[-1] - history[-2]) < 1e-6
+
+
+# ------------------------------------------------------------------------------------------------
+# C ABI of libmlbp_converge.so
+# ------------------------------------------------------------------------------------------------
+HEADER = os.path.join(ROOT, 'include', 'mlbp_converge.h')
+
+
+def _V():
+    from macaronicusermodeling_amd import converge
+    return converge
+
+
+def declared_functions():
+    text = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
+    return sorted(set(re.findall(r'\b(mlbp_converge_[a-z0-9_]+)\s*\(', text)))
+
+
+def test_every_declared_symbol_is_exported_and_bound_and_nothing_else():
+    V = _V()
+    names = declared_functions()
+    assert names == sorted(['mlbp_converge_f64', 'mlbp_converge_check_program', 'mlbp_converge_check_readout', 'mlbp_converge_pick_kernel',
+                            'mlbp_converge_last_kernel', 'mlbp_converge_arch', 'mlbp_converge_last_error'])
+    exported = sorted(n for n, (_, typ) in K._symbols(V.LIB_PATH).items() if n.startswith('mlbp_') and typ == K._STT_FUNC)
+    assert exported == names, set(exported) ^ set(names)
+    assert sorted(V.SIGNATURES) == names, set(V.SIGNATURES) ^ set(names)
+    raw = ctypes.CDLL(V.LIB_PATH)
+    for n in names:
+        assert hasattr(raw, n)
+    from macaronicusermodeling_amd import _ffi, logz, mapdecode, sample
+    for other in (_ffi, mapdecode, logz, sample):
+        assert not set(V.SIGNATURES) & set(other.SIGNATURES)
+    text = open(HEADER).read()
+    assert int(re.search(r'#define MLBP_CONVERGE_X64_LDS_BYTES (\d+)', text).group(1)) == V.X64_LDS_BYTES
+    assert int(re.search(r'#define MLBP_CONVERGE_MAX_X (\d+)', text).group(1)) == V.MAX_X
+    assert int(re.search(r'#define MLBP_CONVERGE_MAX_ROUNDS (\d+)', text).group(1)) == V.MAX_ROUNDS == 65535
+    for name, value in (('NONE', V.KERNEL_NONE), ('X64', V.KERNEL_X64), ('GENERIC', V.KERNEL_GENERIC)):
+        assert int(re.search(r'#define MLBP_CONVERGE_KERNEL_%s (\d+)' % name, text).group(1)) == value
+    # the struct's fields, in the header's order
+    body = re.sub(r'/\*.*?\*/', '', re.search(r'typedef struct mlbp_converge_args \{(.*?)\} mlbp_converge_args;', text, flags=re.S).group(1), flags=re.S)
+    fields = [n for decl in body.split(';') for n in re.findall(r'(\w+)\s*(?:,|$)', decl.strip())]
+    assert fields == [f[0] for f in V.ConvergeArgs._fields_], fields
+    # status codes and op kinds are guarded against the four other headers
+    guard = re.search(r'#if (.*?)\nenum \{ MLBP_OK', text, flags=re.S).group(1)
+    for other in ('MLBP_H', 'MLBP_MAP_H', 'MLBP_LOGZ_H', 'MLBP_SAMPLE_H'):
+        assert '!defined(%s)' % other in guard
+
+
+def _valid_args(V, X=64, n_msgs=27, n_vars=3, B=2):
+    """Arguments that pass every host-side check (the pointers are never dereferenced on the host)."""
+    a = V.ConvergeArgs()
+    a.B, a.X, a.n_msgs, a.P, a.U, a.n_vars = B, X, n_msgs, 3, 15, n_vars
+    a.n_ops, a.n_srcs, a.n_sweeps, a.n_pair_tables, a.n_unary_tables = 10, 4, 1, 6, 30
+    a.normalize_messages, a.init_messages, a.max_rounds, a.tol = 1, 1, 50, 1e-6
+    for name, typ in V.ConvergeArgs._fields_:
+        if typ is ctypes.c_void_p:
+            setattr(a, name, 4096)
+    return a
+
+
+def test_library_identity_and_refusals():
+    V = _V()
+    from macaronicusermodeling_amd import _ffi
+    assert V.lib.mlbp_converge_arch() == b'gfx950'
+    assert V.lib.mlbp_converge_last_kernel() in (V.KERNEL_NONE, V.KERNEL_X64, V.KERNEL_GENERIC)
+    assert V.lib.mlbp_converge_f64(None, None) == _ffi.MLBP_EINVAL and 'NULL' in V.last_error()
+    for field, value, word in (('B', 0, 'sizes'), ('X', 1, 'two states'),
+                               ('tol', -1e-9, 'tol'), ('tol', float('nan'), 'tol'), ('tol', float('inf'), 'tol'),
+                               ('max_rounds', 0, 'max_rounds'), ('max_rounds', 65536, 'max_rounds'), ('max_rounds', -1, 'max_rounds'),
+                               ('normalize_messages', 0, 'no scale'),
+                               ('ops', None, 'NULL'), ('in_off', None, 'NULL'), ('msgs', None, 'msgs'), ('rounds', None, 'rounds'),
+                               ('residual', None, 'residual'), ('pair_tab', None, 'pair_tab'), ('n_unary_tables', 0, 'unary_tables')):
+        a = _valid_args(V)
+        setattr(a, field, value)
+        assert V.lib.mlbp_converge_f64(ctypes.byref(a), None) == _ffi.MLBP_EINVAL, field
+        assert word in V.last_error(), (field, V.last_error())
+        assert V.lib.mlbp_converge_last_kernel() == V.KERNEL_NONE
+    a = _valid_args(V, X=1025)
+    assert V.lib.mlbp_converge_f64(ctypes.byref(a), None) == _ffi.MLBP_EUNSUPPORTED and '1024' in V.last_error()
+    with pytest.raises(V.ConvergeError):
+        V.check(_ffi.MLBP_EINVAL)
+
+
+def test_compute_entry_fails_loudly_without_a_gpu():
+    import torch
+    V = _V()
+    from macaronicusermodeling_amd import _ffi
+    if torch.cuda.is_available():
+        return                                                  # (the GPU module runs the entry for real)
+    for X, tol, max_rounds in ((64, 1e-6, 50), (128, 0.0, 1), (64, 0.0, 65535)):
+        a = _valid_args(V, X=X)
+        a.tol, a.max_rounds = tol, max_rounds
+        a.marginals = a.history = None                          # both are optional
+        assert V.lib.mlbp_converge_f64(ctypes.byref(a), None) == _ffi.MLBP_ENODEVICE
+        assert 'no CPU fallback' in V.last_error() and V.lib.mlbp_converge_last_kernel() == V.KERNEL_NONE
+
+
+def test_kernel_choice_is_the_rule_of_the_header():
+    V = _V()
+    from macaronicusermodeling_amd import _ffi
+
+    def rule(X, n_msgs):
+        return V.KERNEL_X64 if X == 64 and n_msgs * 512 + 4608 + 8 <= V.X64_LDS_BYTES else V.KERNEL_GENERIC
+    for X, n_msgs, n_vars in ((64, 15, 3), (64, 27, 3), (64, 150, 31), (64, 151, 31), (64, 155, 32), (64, 288, 12), (63, 27, 3), (65, 15, 3),
+                              (128, 27, 3), (2, 1, 1), (1024, 5, 2), (4, 12, 4)):
+        assert V.pick_kernel(X, n_msgs, n_vars) == rule(X, n_msgs), (X, n_msgs)
+    # the largest n_msgs that fits and the first that does not
+    assert V.pick_kernel(64, 150, 31) == V.KERNEL_X64 and V.pick_kernel(64, 151, 31) == V.KERNEL_GENERIC
+    assert V.lib.mlbp_converge_pick_kernel(1025, 5, 2) == _ffi.MLBP_EUNSUPPORTED
+    assert V.lib.mlbp_converge_pick_kernel(1, 5, 2) == _ffi.MLBP_EINVAL
+    assert V.lib.mlbp_converge_pick_kernel(64, 0, 2) == _ffi.MLBP_EINVAL and V.lib.mlbp_converge_pick_kernel(64, 5, 0) == _ffi.MLBP_EINVAL
+
+
+def test_program_checks_refuse_bad_indices_and_uncovered_slots():
+    V = _V()
+    from macaronicusermodeling_amd import _ffi
+    from macaronicusermodeling_amd.topology import GraphTopology
+    topo = GraphTopology.from_spec(C.user_spec(10, [1, 4, 7], 64, 64, seed=1))
+    ops, srcs, sweeps = topo.compile_program([1, 4, 7])
+
+    def check(ops=ops, srcs=srcs, sweeps=sweeps, t=topo):
+        return V.check_program(ops, srcs, sweeps, t.n_msgs, t.P, t.U)
+    assert check() == _ffi.MLBP_OK
+    kinds = ops[:, 0]
+    for row, col, value, word in ((0, 3, topo.n_msgs, 'destination'), (int(np.argmax(kinds == _ffi.OP_PAIR_TM)), 1, topo.P, 'pair slot'),
+                                  (int(np.argmax(kinds == _ffi.OP_PAIR_MT)), 2, -1, 'source slot'),
+                                  (int(np.argmax(kinds == _ffi.OP_UNARY)), 1, topo.U, 'unary slot'),
+                                  (int(np.argmax(kinds == _ffi.OP_VAR)), 2, len(srcs) + 1, 'srcs range'), (0, 0, 7, 'unknown kind')):
+        bad = ops.copy()
+        bad[row, col] = value
+        assert check(ops=bad) == _ffi.MLBP_EINVAL and word in V.last_error(), (word, V.last_error())
+    bad = sweeps.copy()
+    bad[-1, 1] += 1
+    assert check(sweeps=bad) == _ffi.MLBP_EINVAL and 'sweep' in V.last_error()
+    assert V.lib.mlbp_converge_check_program(None, 1, None, 0, None, 1, 1, 0, 0) == _ffi.MLBP_EINVAL and 'NULL' in V.last_error()
+    # coverage.  One root already reaches every slot of a connected graph (each edge is a (child, parent) pair of the schedule,
+    # sent both ways), so the uncovered slot is hand-made: every op that writes slot k is redirected to another slot ...
+    for rootseq in ([1], [1, 4, 7], [7]):
+        o, s, w = topo.compile_program(rootseq)
+        assert check(o, s, w) == _ffi.MLBP_OK
+    k = int(ops[int(np.argmax(kinds == _ffi.OP_UNARY)), 3])
+    other = int(ops[[i for i in range(len(ops)) if kinds[i] == _ffi.OP_UNARY and ops[i, 3] != k][0], 3])
+    bad = ops.copy()
+    bad[bad[:, 3] == k, 3] = other
+    assert check(ops=bad) == _ffi.MLBP_EINVAL and 'slot %d ' % k in V.last_error() and 'coverage' in V.last_error(), V.last_error()
+    # ... or the ops that write it lie outside every sweep's range
+    last = sweeps.copy()
+    only = int(ops[-1, 3])
+    if not (ops[:-1, 3] == only).any():
+        last[-1, 1] -= 1
+        assert check(sweeps=last) == _ffi.MLBP_EINVAL and 'slot %d ' % only in V.last_error()
+    # ... or the roots lie in one component of a graph with two
+    two = [s for s in C.schedule_topologies() if s['name'] == 'two_components'][0]
+    t2 = GraphTopology.from_spec(two)
+    o, s, w = t2.compile_program([0])
+    assert check(o, s, w, t=t2) == _ffi.MLBP_EINVAL and 'coverage' in V.last_error()
+    o, s, w = t2.compile_program([0, 10])
+    assert check(o, s, w, t=t2) == _ffi.MLBP_OK
+    # the read-out arrays
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).reshape(-1)          # noqa: E731
+
+    def readout(in_off=topo.in_off, in_slots=topo.in_slots):
+        return V.lib.mlbp_converge_check_readout(topo.n_vars, _ffi.i32ptr(i32(in_off)), _ffi.i32ptr(i32(in_slots)), topo.n_msgs)
+    assert readout() == _ffi.MLBP_OK
+    bad = topo.in_slots.copy(); bad[-1] = topo.n_msgs
+    assert readout(in_slots=bad) == _ffi.MLBP_EINVAL and 'slot' in V.last_error()
+    bad = topo.in_off.copy(); bad[1] = bad[2] + 1
+    assert readout(in_off=bad) == _ffi.MLBP_EINVAL and 'monotone' in V.last_error()
+    assert V.lib.mlbp_converge_check_readout(1, None, None, 1) == _ffi.MLBP_EINVAL and 'NULL' in V.last_error()
+
+
+# ------------------------------------------------------------------------------------------------
+# kernel inventory of libmlbp_converge.so: the rule of tests/test_kernel_inventory.py applied to the fifth library
+# ------------------------------------------------------------------------------------------------
+CSRC_CONVERGE = os.path.join(ROOT, 'macaronicusermodeling_amd', 'csrc_converge')
+
+
+def _kernels_of(path):
+    found = {K.decode_kernel(n) for n, (_, typ) in K._symbols(path).items() if typ == K._STT_OBJECT}
+    return found - {None}
+
+
+def converge_kernels():
+    """Every kernel instance libmlbp_converge.so holds, as kernel_inventory names them."""
+    return _kernels_of(_V().LIB_PATH)
+
+
+def test_converge_library_kernels_are_the_sources_kernels_and_each_has_a_case():
+    import test_gpu_converge as G
+    src = K.kernel_names(csrc=CSRC_CONVERGE)
+    assert src == {'converge_x64_kernel', 'converge_generic_kernel'}
+    compiled = converge_kernels()
+    assert compiled == {('converge_x64_kernel', (True,)), ('converge_x64_kernel', (False,)), ('converge_generic_kernel', ())}
+    assert set(G.CASES) == compiled, set(G.CASES) ^ compiled
+    for kern, tests in G.CASES.items():
+        assert tests, kern
+        for t in tests:
+            assert callable(getattr(G, t, None)), (kern, t)
+
+
+def test_the_other_libraries_hold_no_converge_kernel_and_the_sources_stay_apart():
+    from macaronicusermodeling_amd import logz, mapdecode, sample
+    assert not [k for k in K.all_compiled() if k[0].startswith('converge_')]
+    for other in (mapdecode, logz, sample):
+        assert not [k for k in _kernels_of(other.LIB_PATH) if k[0].startswith('converge_')]
+    names = K.kernel_names(csrc=CSRC_CONVERGE)
+    assert all(n.startswith('converge_') for n in names)
+    pkg = os.path.join(ROOT, 'macaronicusermodeling_amd')
+    for csrc in (K.CSRC, W.CSRC_MAP, os.path.join(pkg, 'csrc_logz'), os.path.join(pkg, 'csrc_sample')):
+        assert not names & K.kernel_names(csrc=csrc)
+    for f in os.listdir(CSRC_CONVERGE):
+        assert f.endswith(('.hip', '.h', '.o')), f
