@@ -8,25 +8,34 @@ import subprocess
 import sys
 
 PKG = os.path.dirname(os.path.abspath(__file__))
+INCLUDE = os.path.join(PKG, '..', 'include')
 CSRC = os.path.join(PKG, 'csrc')
-LIB = os.path.join(PKG, 'libmlbp.so')
-SOURCES = ['mlbp_host.cpp', 'mlbp_compile.cpp', 'mlbp_compile_shared.cpp', 'mlbp_program.cpp', 'mlbp_dispatch.cpp', 'mlbp_sweep.hip', 'mlbp_lean.hip', 'mlbp_shared.hip', 'mlbp_gemm.hip', 'mlbp_prims.hip', 'mlbp_grad.hip']
-# the max-product / MAP library (include/mlbp_map.h): its own sources, its own kernel inventory, the same flags
 CSRC_MAP = os.path.join(PKG, 'csrc_map')
-LIB_MAP = os.path.join(PKG, 'libmlbp_map.so')
-SOURCES_MAP = ['mlbp_map.hip']
-# the log-partition / joint-likelihood library (include/mlbp_logz.h): again its own sources and inventory, the same flags
 CSRC_LOGZ = os.path.join(PKG, 'csrc_logz')
-LIB_LOGZ = os.path.join(PKG, 'libmlbp_logz.so')
-SOURCES_LOGZ = ['mlbp_logz.hip']
-# the posterior-sampling library (include/mlbp_sample.h): its own sources and inventory, the same flags
 CSRC_SAMPLE = os.path.join(PKG, 'csrc_sample')
-LIB_SAMPLE = os.path.join(PKG, 'libmlbp_sample.so')
-SOURCES_SAMPLE = ['mlbp_sample.hip']
-# the sweeps-to-convergence library (include/mlbp_converge.h): its own sources and inventory, the same flags
 CSRC_CONVERGE = os.path.join(PKG, 'csrc_converge')
+LIB = os.path.join(PKG, 'libmlbp.so')
+LIB_MAP = os.path.join(PKG, 'libmlbp_map.so')
+LIB_LOGZ = os.path.join(PKG, 'libmlbp_logz.so')
+LIB_SAMPLE = os.path.join(PKG, 'libmlbp_sample.so')
 LIB_CONVERGE = os.path.join(PKG, 'libmlbp_converge.so')
+SOURCES = ['mlbp_host.cpp', 'mlbp_compile.cpp', 'mlbp_compile_shared.cpp', 'mlbp_program.cpp', 'mlbp_dispatch.cpp', 'mlbp_sweep.hip', 'mlbp_lean.hip', 'mlbp_shared.hip', 'mlbp_gemm.hip', 'mlbp_prims.hip', 'mlbp_grad.hip']
+SOURCES_MAP = ['mlbp_map.hip']
+SOURCES_LOGZ = ['mlbp_logz.hip']
+SOURCES_SAMPLE = ['mlbp_sample.hip']
 SOURCES_CONVERGE = ['mlbp_converge.hip']
+# csrc/ headers: the core library's, and what the side libraries share (mlbp_graph_device.h includes mlbp_device.h)
+HEADERS = ['mlbp_internal.h', 'mlbp_device.h']
+HEADERS_SIDE = ['mlbp_device.h', 'mlbp_graph_device.h', 'mlbp_graph_host.h']
+# (source dir, sources, csrc/ headers, public header, output): every library has its own sources and its own kernel
+# inventory; the flags are the same
+LIBRARIES = [
+    (CSRC, SOURCES, HEADERS, 'mlbp.h', LIB),
+    (CSRC_MAP, SOURCES_MAP, HEADERS_SIDE, 'mlbp_map.h', LIB_MAP),                        # max-product / MAP
+    (CSRC_LOGZ, SOURCES_LOGZ, HEADERS_SIDE, 'mlbp_logz.h', LIB_LOGZ),                    # log-partition / joint likelihood
+    (CSRC_SAMPLE, SOURCES_SAMPLE, HEADERS_SIDE, 'mlbp_sample.h', LIB_SAMPLE),            # posterior sampling
+    (CSRC_CONVERGE, SOURCES_CONVERGE, HEADERS_SIDE, 'mlbp_converge.h', LIB_CONVERGE),    # sweeps to convergence
+]
 FLAGS = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-fno-fast-math', '-Wall',
          '-Wno-unused-function']
 
@@ -59,17 +68,10 @@ def build(force=False, verbose=False):
     """Builds the five libraries; returns the path of libmlbp.so (the others lie beside it: LIB_MAP, LIB_LOGZ, LIB_SAMPLE,
     LIB_CONVERGE)."""
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    headers = [os.path.join(CSRC, 'mlbp_internal.h'), os.path.join(CSRC, 'mlbp_device.h'), os.path.join(PKG, '..', 'include', 'mlbp.h')]
-    lib = _build_one(hipcc, CSRC, SOURCES, headers, LIB, force, verbose)
-    headers_map = [os.path.join(CSRC, 'mlbp_device.h'), os.path.join(PKG, '..', 'include', 'mlbp_map.h')]
-    _build_one(hipcc, CSRC_MAP, SOURCES_MAP, headers_map, LIB_MAP, force, verbose)
-    headers_logz = [os.path.join(CSRC, 'mlbp_device.h'), os.path.join(PKG, '..', 'include', 'mlbp_logz.h')]
-    _build_one(hipcc, CSRC_LOGZ, SOURCES_LOGZ, headers_logz, LIB_LOGZ, force, verbose)
-    headers_sample = [os.path.join(CSRC, 'mlbp_device.h'), os.path.join(PKG, '..', 'include', 'mlbp_sample.h')]
-    _build_one(hipcc, CSRC_SAMPLE, SOURCES_SAMPLE, headers_sample, LIB_SAMPLE, force, verbose)
-    headers_converge = [os.path.join(CSRC, 'mlbp_device.h'), os.path.join(PKG, '..', 'include', 'mlbp_converge.h')]
-    _build_one(hipcc, CSRC_CONVERGE, SOURCES_CONVERGE, headers_converge, LIB_CONVERGE, force, verbose)
-    return lib
+    for csrc, sources, headers, public, lib in LIBRARIES:
+        deps = [os.path.join(CSRC, h) for h in headers] + [os.path.join(INCLUDE, public)]
+        _build_one(hipcc, csrc, sources, deps, lib, force, verbose)
+    return LIB
 
 
 if __name__ == '__main__':

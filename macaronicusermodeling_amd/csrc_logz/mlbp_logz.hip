@@ -11,7 +11,8 @@
 //                           recomputed from the staged messages (d_v is small), never divided out: messages hold zeros.
 //   logz_x64_shared_kernel  X = 64 and the caller claims shared tables: 16 graphs per workgroup.  Per pairwise factor the
 //                           workgroup checks that its graphs name ONE table; if so the table is read once as the 16-entry
-//                           register fragment of the max-product kernel (wave w owns rows 16w .. 16w+15) and contracted
+//                           register fragment of the sweep libraries (load_fragment of csrc/mlbp_graph_device.h: wave w owns
+//                           rows 16w .. 16w+15) and contracted
 //                           with the group's 16 pairs of leave-one-out vectors from LDS by vector FMAs; if not, every wave
 //                           walks its four graphs' own tables as logz_x64_kernel does.  Messages are read from global memory
 //                           (a variable's d_v messages are re-read d_v times within a few hundred cycles: L1 hits).
@@ -20,20 +21,19 @@
 //   logz_sum_kernel         the two batch sums, one workgroup, a fixed order.
 // Every sum is float64; every cross-lane sum is mlbp_dev::wave_sum, so a result does not depend on the launch.
 // No device-side mutable globals: everything comes through LogzDev.
+// The device helpers and host checks shared with the other side libraries are in csrc/mlbp_graph_device.h and
+// csrc/mlbp_graph_host.h.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
-#include <string>
-
 #include "../../include/mlbp_logz.h"
-#include "../csrc/mlbp_device.h"
+#define MLBP_GRAPH_NO_SWEEPS                // this library reads finished messages: mlbp_logz.h has no op kinds
+#include "../csrc/mlbp_graph_device.h"
+#include "../csrc/mlbp_graph_host.h"
 
 namespace {
 
-using namespace mlbp_dev;
+using namespace mlbp_graph;
 
-constexpr int WG = 256;
 constexpr int GROUP = MLBP_LOGZ_GROUP;
 
 struct LogzDev {
@@ -54,15 +54,6 @@ __device__ __forceinline__ void wave_lds_fence() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Every table index of graph g is inside its table array (wave-uniform: scalar loads).
-__device__ __forceinline__ bool tables_in_range(const LogzDev& d, int g) {
-  bool ok = true;
-  const const_i32p pt = as_const(d.pair_tab), ut = as_const(d.unary_tab);
-  for (int p = 0; p < d.P; ++p) ok &= (unsigned)pt[(size_t)g * d.P + p] < (unsigned)d.n_pair_tables;
-  for (int u = 0; u < d.U; ++u) ok &= (unsigned)ut[(size_t)g * d.U + u] < (unsigned)d.n_unary_tables;
-  return ok;
 }
 
 // score at the labels of graph g, by one wave (every lane returns it): NaN when a label is outside [0, X).
@@ -137,7 +128,7 @@ __global__ __launch_bounds__(WG) void logz_x64_kernel(LogzDev d) {
   double* vec = msg + (size_t)d.n_in * 64;                     // [4 waves][2][64] leave-one-out vectors of a pairwise factor
   double* part = vec + 512;                                    // [4] (+ padding) per-wave sums of log terms
   const int g = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  if (!tables_in_range(d, g)) {
+  if (!tables_in_range(d.pair_tab, d.P, d.n_pair_tables, d.unary_tab, d.U, d.n_unary_tables, g)) {
     if (wave == 0) write_outputs(d, g, 0.0, false, lane);
     return;
   }
@@ -178,17 +169,6 @@ __global__ __launch_bounds__(WG) void logz_x64_kernel(LogzDev d) {
 }
 
 // ---- X = 64, 16 graphs per workgroup, tables shared -------------------------------------------------
-// The 16 entries of a 64 x 64 table this thread owns: entry 2k + e = T[16 wave + 2k + (lane >> 5)][2 (lane & 31) + e].
-__device__ __forceinline__ void load_fragment(const double* table, int wave, int lane, double (&T)[16]) {
-  const double2* src = reinterpret_cast<const double2*>(table) + (size_t)(16 * wave) * 32 + lane;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const double2 v = src[(size_t)(2 * k) * 32];
-    T[2 * k] = v.x;
-    T[2 * k + 1] = v.y;
-  }
-}
-
 __global__ __launch_bounds__(WG) void logz_x64_shared_kernel(LogzDev d) {
   __shared__ __attribute__((aligned(16))) double NA[GROUP * 64];      // [graph][state] leave-one-out vector on table axis 0
   __shared__ __attribute__((aligned(16))) double NB[GROUP * 64];      // ... on axis 1
@@ -293,14 +273,6 @@ __global__ __launch_bounds__(WG) void logz_x64_shared_kernel(LogzDev d) {
 }
 
 // ---- any X -----------------------------------------------------------------------------------------
-__device__ __forceinline__ double block_sum(double v, double* scratch /*[4]*/) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (scratch[0] + scratch[1]) + (scratch[2] + scratch[3]);
-}
-
 __global__ __launch_bounds__(WG) void logz_generic_kernel(LogzDev d) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int X = d.X, Xp = (X + 1) & ~1;
@@ -308,7 +280,7 @@ __global__ __launch_bounds__(WG) void logz_generic_kernel(LogzDev d) {
   double* nb = na + Xp;                                        // [Xp]
   double* scratch = nb + Xp;                                   // [4]
   const int g = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  if (!tables_in_range(d, g)) {
+  if (!tables_in_range(d.pair_tab, d.P, d.n_pair_tables, d.unary_tab, d.U, d.n_unary_tables, g)) {
     if (wave == 0) write_outputs(d, g, 0.0, false, lane);
     return;
   }
@@ -367,19 +339,7 @@ __global__ __launch_bounds__(WG) void logz_sum_kernel(const double* log_z, const
 }
 
 // ---- host ----------------------------------------------------------------------------------------
-thread_local std::string g_last_error = "";
 thread_local int g_last_kernel = MLBP_LOGZ_KERNEL_NONE;
-
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_last_error = buf;
-  return code;
-}
 
 int64_t x64_lds_bytes(int64_t n_in) { return n_in * 512 + 4096 + 64; }
 
@@ -411,19 +371,16 @@ int mlbp_logz_pick_kernel(int32_t X, int32_t n_in_slots, int32_t n_vars, int32_t
 int mlbp_logz_check_readout(int32_t n_vars, const int32_t* in_off, const int32_t* in_slots, int32_t n_msgs, int32_t P,
                             const int32_t* pair_axis_var, const int32_t* pair_in_slot, int32_t U, const int32_t* unary_var,
                             const int32_t* unary_in_slot) {
-  if (!in_off || !in_slots) return fail(MLBP_EINVAL, "read-out: in_off or in_slots is NULL");
+  if (int e = check_in_slots_present(in_off, in_slots)) return e;
   if (n_vars <= 0 || n_msgs <= 0 || P < 0 || U < 0 || P + U <= 0 || (P > 0 && (!pair_axis_var || !pair_in_slot)) ||
       (U > 0 && (!unary_var || !unary_in_slot)))
     return fail(MLBP_EINVAL, "read-out: bad sizes (n_vars %d, n_msgs %d, P %d, U %d) or a NULL array", n_vars, n_msgs, P, U);
-  if (in_off[0] != 0) return fail(MLBP_EINVAL, "read-out: in_off[0] must be 0");
-  for (int v = 0; v < n_vars; ++v) {
-    if (in_off[v + 1] < in_off[v]) return fail(MLBP_EINVAL, "read-out: in_off not monotone at variable %d", v);
+  const int rc = check_in_slots(n_vars, in_off, in_slots, n_msgs, [&](int v) -> int {
     if ((int64_t)in_off[v + 1] > 2 * (int64_t)P + U)
       return fail(MLBP_EINVAL, "read-out: in_off[%d] = %d beyond the 2 P + U = %d in-slots", v + 1, in_off[v + 1], 2 * P + U);
-    for (int q = in_off[v]; q < in_off[v + 1]; ++q)
-      if (in_slots[q] < 0 || in_slots[q] >= n_msgs)
-        return fail(MLBP_EINVAL, "read-out: variable %d: slot %d out of [0,%d)", v, in_slots[q], n_msgs);
-  }
+    return MLBP_OK;
+  });
+  if (rc) return rc;
   if (in_off[n_vars] != 2 * P + U)
     return fail(MLBP_EINVAL, "read-out: in_off[n_vars] = %d, but 2 P + U = %d in-slots", in_off[n_vars], 2 * P + U);
   for (int i = 0; i < 2 * P; ++i) {
@@ -446,26 +403,20 @@ int mlbp_logz_f64(const mlbp_logz_args* a, void* stream) {
   if (!a) return fail(MLBP_EINVAL, "args is NULL");
   if (a->B <= 0 || a->n_msgs <= 0 || a->n_vars <= 0 || a->P < 0 || a->U < 0 || a->P + a->U <= 0)
     return fail(MLBP_EINVAL, "bad sizes: B %d, n_msgs %d, n_vars %d, P %d, U %d", a->B, a->n_msgs, a->n_vars, a->P, a->U);
-  if (a->X < 2) return fail(MLBP_EINVAL, "X = %d: a variable needs at least two states", a->X);
+  if (int e = check_states(a->X)) return e;
   const int64_t n_in = 2 * (int64_t)a->P + a->U;
   if (n_in > 0x7fffffff / 64) return fail(MLBP_EUNSUPPORTED, "2 P + U = %lld in-slots: too many", (long long)n_in);
   const int which = mlbp_logz_pick_kernel(a->X, (int32_t)n_in, a->n_vars, a->flags);
   if (which < 0) return which;
   if (!a->msgs) return fail(MLBP_EINVAL, "msgs is NULL");
-  if (!a->in_off || !a->in_slots) return fail(MLBP_EINVAL, "in_off or in_slots is NULL");
-  if (a->P > 0 && (!a->pair_tables || !a->pair_tab || !a->pair_axis_var || !a->pair_in_slot || a->n_pair_tables <= 0))
-    return fail(MLBP_EINVAL, "P = %d but pair_tables, pair_tab, pair_axis_var or pair_in_slot is NULL (or n_pair_tables <= 0)", a->P);
-  if (a->U > 0 && (!a->unary_tables || !a->unary_tab || !a->unary_var || !a->unary_in_slot || a->n_unary_tables <= 0))
-    return fail(MLBP_EINVAL, "U = %d but unary_tables, unary_tab, unary_var or unary_in_slot is NULL (or n_unary_tables <= 0)", a->U);
+  if (int e = check_args_in_slots(a)) return e;
+  if (int e = check_args_tables(a, !a->pair_axis_var || !a->pair_in_slot, "pair_tables, pair_tab, pair_axis_var or pair_in_slot",
+                                !a->unary_var || !a->unary_in_slot, "unary_tables, unary_tab, unary_var or unary_in_slot")) return e;
   if (!a->log_z && !a->score && !a->joint_logp) return fail(MLBP_EINVAL, "nothing to compute: log_z, score and joint_logp are NULL");
   if ((a->score || a->joint_logp) && !a->labels) return fail(MLBP_EINVAL, "score and joint_logp need labels");
   if (a->sum_out && !a->log_z) return fail(MLBP_EINVAL, "sum_out needs log_z");
-  if ((int64_t)a->n_msgs * a->X > 0x7fffffff / 2) return fail(MLBP_EUNSUPPORTED, "n_msgs * X = %lld too large", (long long)a->n_msgs * a->X);
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
-    (void)hipGetLastError();
-    return fail(MLBP_ENODEVICE, "no HIP device visible: libmlbp_logz.so has no CPU fallback");
-  }
+  if (int e = check_args_extent(a)) return e;
+  if (int e = check_device("libmlbp_logz.so")) return e;
   LogzDev d;
   d.pair_tables = a->pair_tables; d.pair_tab = a->pair_tab; d.unary_tables = a->unary_tables; d.unary_tab = a->unary_tab;
   d.msgs = a->msgs; d.in_off = a->in_off; d.in_slots = a->in_slots; d.pair_axis_var = a->pair_axis_var; d.unary_var = a->unary_var;

@@ -3,17 +3,13 @@
 //
 // Two kernels, chosen from (X, n_msgs, n_vars) by mlbp_sample_pick_kernel, both on a grid of (B, C) workgroups: workgroup
 // (g, c) serves graph g and draws its samples c, c + C, ...
-//   sample_x64_kernel<RESIDENT>  X = 64, four waves, messages in LDS for the whole launch -- the layout of
-//                                map_sweep_x64_kernel (csrc_map/mlbp_map.hip): a pairwise table is split over the 256 threads
-//                                as 16 entries each, wave w owns rows 16w .. 16w+15, lane l holds, for k = 0..7, the two entries
-//                                of row 16w + 2k + (l >> 5) in columns 2(l & 31), +1.  RESIDENT (P <= 3): all tables are loaded
-//                                once per workgroup and stay in registers over every step of every sample; otherwise the 16
-//                                entries are loaded per update (streamed).  The two contractions are sums:
-//                                  out = m^T.T : running sum over the thread's 8 rows for its two columns, the 8 partial vectors
-//                                                (4 waves x 2 row halves) meet in LDS and are added in a fixed order;
-//                                  out = T.m   : per row the two products, then a sum over the 32 lanes of the row half on DPP
-//                                                and through scalar registers.
-//                                A clamped variable is an int in LDS, applied to its outgoing messages as lane == x ? acc : 0.
+//   sample_x64_kernel<RESIDENT>  X = 64, four waves, messages in LDS for the whole launch.  A pairwise table is split over the
+//                                256 threads as 16 entries each (load_fragment of csrc/mlbp_graph_device.h, which also holds the
+//                                two contractions; here they run with SumOp).  RESIDENT (P <= 3): all tables are loaded once
+//                                per workgroup and stay in registers over every step of every sample; otherwise the 16 entries
+//                                are loaded per update (streamed).  A clamped variable is an int in LDS: a VAR op keeps
+//                                lane == x ? acc : 0 of its outgoing message (the generic kernel hands the shared step the same
+//                                int as its state_of).
 //                                The draw runs in wave 0 with lane = state: inclusive scan, total from lane 63, ballot of c > t.
 //                                The marginal of step 0 (no variable clamped yet: the same for every sample) is computed for the
 //                                workgroup's first sample and kept in LDS.
@@ -21,23 +17,18 @@
 //                                scan by one thread over the LDS copy of the marginal.  Correct first: the path for shapes
 //                                nobody times.
 // No device-side mutable globals: everything comes through SampleDev.
+// The host checks shared with the other side libraries are in csrc/mlbp_graph_host.h.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-#include <cstdarg>
-#include <cstdio>
-#include <mutex>
-#include <string>
 #include <vector>
 
 #include "../../include/mlbp_sample.h"
-#include "../csrc/mlbp_device.h"
+#include "../csrc/mlbp_graph_device.h"
+#include "../csrc/mlbp_graph_host.h"
 
 namespace {
 
-using namespace mlbp_dev;
-
-constexpr int WG = 256;
+using namespace mlbp_graph;
 
 struct SampleDev {
   const double* pair_tables; const int32_t* pair_tab;
@@ -51,15 +42,6 @@ struct SampleDev {
   int32_t normalize, B, S;
 };
 
-// Sum over each row of 16 lanes, the same bits in every lane of the row (the first four steps of mlbp_dev::wave_sum).
-__device__ __forceinline__ double row16_sum(double v) {
-  v += dpp_mov<0xB1>(v);
-  v += dpp_mov<0x4E>(v);
-  v += dpp_mov<0x141>(v);
-  v += dpp_mov<0x140>(v);
-  return v;
-}
-
 // Inclusive prefix sum over the 64 lanes in lane order (Hillis-Steele, six steps).
 __device__ __forceinline__ double wave_inclusive_scan(double v, int lane) {
 #pragma unroll
@@ -72,10 +54,7 @@ __device__ __forceinline__ double wave_inclusive_scan(double v, int lane) {
 
 // Every table index of graph g is inside its table array and every given state is -1 or a state (wave-uniform: scalar loads).
 __device__ __forceinline__ bool graph_in_range(const SampleDev& d, int g) {
-  bool ok = true;
-  const const_i32p pt = as_const(d.pair_tab), ut = as_const(d.unary_tab);
-  for (int p = 0; p < d.P; ++p) ok &= (unsigned)pt[(size_t)g * d.P + p] < (unsigned)d.n_pair_tables;
-  for (int u = 0; u < d.U; ++u) ok &= (unsigned)ut[(size_t)g * d.U + u] < (unsigned)d.n_unary_tables;
+  bool ok = tables_in_range(d.pair_tab, d.P, d.n_pair_tables, d.unary_tab, d.U, d.n_unary_tables, g);
   if (d.given) {
     const const_i32p gv = as_const(d.given) + (size_t)g * d.n_vars;
     for (int v = 0; v < d.n_vars; ++v) ok &= gv[v] >= -1 && gv[v] < d.X;
@@ -90,44 +69,6 @@ __device__ __forceinline__ void refuse_graph(const SampleDev& d, int g) {
     for (int v = threadIdx.x; v < d.n_vars; v += WG) out[v] = -1;
     if (threadIdx.x == 0) d.logq[(size_t)s * d.B + g] = __builtin_nan("");
   }
-}
-
-// The 16 entries of a 64 x 64 table this thread owns: entry 2k + e = T[16 wave + 2k + (lane >> 5)][2 (lane & 31) + e].
-__device__ __forceinline__ void load_fragment(const double* table, int wave, int lane, double (&T)[16]) {
-  const double2* src = reinterpret_cast<const double2*>(table) + (size_t)(16 * wave) * 32 + lane;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const double2 v = src[(size_t)(2 * k) * 32];
-    T[2 * k] = v.x;
-    T[2 * k + 1] = v.y;
-  }
-}
-
-// out[j] = sum_i m[i] * T[i][j]: the thread's two columns over its 8 rows -> part[2 wave + half][column].
-__device__ __forceinline__ void pair_mt_partial(const double (&T)[16], const double* m, double* part, int wave, int lane) {
-  const int h = lane >> 5;
-  double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const double mi = m[16 * wave + 2 * k + h];          // two addresses per wave: LDS broadcast
-    a0 += mi * T[2 * k];
-    a1 += mi * T[2 * k + 1];
-  }
-  reinterpret_cast<double2*>(part)[(2 * wave + h) * 32 + (lane & 31)] = make_double2(a0, a1);
-}
-
-// out[i] = sum_j T[i][j] * m[j]: the wave's 16 rows -> raw[16 wave .. 16 wave + 15].
-__device__ __forceinline__ void pair_tm_rows(const double (&T)[16], const double* m, double* raw, int wave, int lane) {
-  const double2 mm = reinterpret_cast<const double2*>(m)[lane & 31];
-  double2 mine = make_double2(0.0, 0.0);
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const double p = row16_sum(T[2 * k] * mm.x + T[2 * k + 1] * mm.y);
-    const double lo = read_lane(p, 0) + read_lane(p, 16);           // row 16 wave + 2k     (lanes 0..31)
-    const double hi = read_lane(p, 32) + read_lane(p, 48);          // row 16 wave + 2k + 1 (lanes 32..63)
-    if (lane == k) mine = make_double2(lo, hi);
-  }
-  if (lane < 8) reinterpret_cast<double2*>(raw)[8 * wave + lane] = mine;
 }
 
 template <bool RESIDENT>
@@ -179,17 +120,19 @@ __global__ __launch_bounds__(WG) void sample_x64_kernel(SampleDev d) {
           const int op0 = c_sweeps[2 * sw], nop = c_sweeps[2 * sw + 1];
           for (int o = op0; o < op0 + nop; ++o) {
             const int kind = c_ops[4 * o], a = c_ops[4 * o + 1], b = c_ops[4 * o + 2], c = c_ops[4 * o + 3];
+            // x64_step of mlbp_graph_device.h with the clamp, written out: through the helper this kernel alone ran 1.3 % slower
+            // (LAB_NOTES R14.4)
             if (kind == MLBP_OP_PAIR_TM || kind == MLBP_OP_PAIR_MT) {
               const double* m = msg + b * 64;
               const bool tm = kind == MLBP_OP_PAIR_TM;
               if (RESIDENT) {
-                if (a == 0) { if (tm) pair_tm_rows(R[0], m, raw, wave, lane); else pair_mt_partial(R[0], m, part, wave, lane); }
-                else if (a == 1) { if (tm) pair_tm_rows(R[1], m, raw, wave, lane); else pair_mt_partial(R[1], m, part, wave, lane); }
-                else { if (tm) pair_tm_rows(R[2], m, raw, wave, lane); else pair_mt_partial(R[2], m, part, wave, lane); }
+                if (a == 0) pair_contract<SumOp>(R[0], tm, m, part, raw, wave, lane);
+                else if (a == 1) pair_contract<SumOp>(R[1], tm, m, part, raw, wave, lane);
+                else pair_contract<SumOp>(R[2], tm, m, part, raw, wave, lane);
               } else {
                 double T[16];
                 load_fragment(d.pair_tables + (size_t)ptab[a] * 4096, wave, lane, T);
-                if (tm) pair_tm_rows(T, m, raw, wave, lane); else pair_mt_partial(T, m, part, wave, lane);
+                pair_contract<SumOp>(T, tm, m, part, raw, wave, lane);
               }
               __syncthreads();
               if (wave == 0) {
@@ -224,10 +167,7 @@ __global__ __launch_bounds__(WG) void sample_x64_kernel(SampleDev d) {
         if (k == 0 && have_m0) {
           m = m0[lane];
         } else {
-          double acc = uniform;
-          for (int q = in_off[v]; q < in_off[v + 1]; ++q) acc = mul_nan_to_num(msg[in_slots[q] * 64 + lane], acc);
-          const double total = wave_sum(acc);
-          m = total > 0.0 ? acc / total : uniform;
+          m = x64_marginal(msg, in_off, in_slots, v, lane);
           if (k == 0) m0[lane] = m;
         }
         if (d.cond_marginals) d.cond_marginals[(sg * d.n_vars + v) * 64 + lane] = m;
@@ -253,14 +193,6 @@ __global__ __launch_bounds__(WG) void sample_x64_kernel(SampleDev d) {
 }
 
 // ---- any X ---------------------------------------------------------------------------------------
-__device__ __forceinline__ double block_sum(double v, double* scratch /*[4]*/) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (scratch[0] + scratch[1]) + (scratch[2] + scratch[3]);
-}
-
 __global__ __launch_bounds__(WG) void sample_generic_kernel(SampleDev d) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int X = d.X;
@@ -268,19 +200,21 @@ __global__ __launch_bounds__(WG) void sample_generic_kernel(SampleDev d) {
   double* scratch = raw + ((X + 1) & ~1);                      // [4] block sums
   double* logq_s = scratch + 4;                                // [1] thread 0's running log q
   int32_t* clamp = reinterpret_cast<int32_t*>(logq_s + 1);     // [n_vars]
-  const int g = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int g = blockIdx.x, t = threadIdx.x;
   if (!graph_in_range(d, g)) {
     refuse_graph(d, g);
     return;
   }
   const const_i32p ptab = as_const(d.pair_tab) + (size_t)g * d.P, utab = as_const(d.unary_tab) + (size_t)g * d.U;
-  const const_i32p c_ops = as_const(d.ops), c_srcs = as_const(d.srcs), c_sweeps = as_const(d.sweeps);
+  const const_i32p c_ops = as_const(d.ops), c_sweeps = as_const(d.sweeps);
   const const_i32p in_off = as_const(d.in_off), in_slots = as_const(d.in_slots);
   const const_i32p slot_var = as_const(d.slot_var), order = as_const(d.order);
   const double uniform = 1.0 / (double)X;
   const bool norm = d.normalize != 0;
   // only this workgroup touches its messages
   double* msg = d.workspace + ((size_t)g * gridDim.y + blockIdx.y) * (size_t)d.n_msgs * X;
+  const StepGraph G = {d.pair_tables, ptab, d.unary_tables, utab, as_const(d.srcs), msg, nullptr, raw};
+  auto state_of = [&](int slot) { return clamp[slot_var[slot]]; };
   for (int s = blockIdx.y; s < d.S; s += gridDim.y) {
     for (int v = t; v < d.n_vars; v += WG) clamp[v] = -1;
     if (t == 0) logq_s[0] = 0.0;
@@ -293,59 +227,16 @@ __global__ __launch_bounds__(WG) void sample_generic_kernel(SampleDev d) {
         const int op0 = c_sweeps[2 * sw], nop = c_sweeps[2 * sw + 1];
         for (int o = op0; o < op0 + nop; ++o) {
           const int kind = c_ops[4 * o], a = c_ops[4 * o + 1], b = c_ops[4 * o + 2], c = c_ops[4 * o + 3];
-          if (kind == MLBP_OP_PAIR_TM) {
-            const double* T = d.pair_tables + (size_t)ptab[a] * X * X;
-            const double* m = msg + (size_t)b * X;
-            for (int row = wave; row < X; row += WG / 64) {
-              const double* Tr = T + (size_t)row * X;
-              double acc = 0.0;
-              for (int j = lane; j < X; j += 64) acc += Tr[j] * m[j];
-              acc = wave_sum(acc);
-              if (lane == 0) raw[row] = acc;
-            }
-          } else if (kind == MLBP_OP_PAIR_MT) {
-            const double* T = d.pair_tables + (size_t)ptab[a] * X * X;
-            const double* m = msg + (size_t)b * X;
-            for (int j = t; j < X; j += WG) {
-              double acc = 0.0;
-#pragma unroll 8
-              for (int i = 0; i < X; ++i) acc += m[i] * T[(size_t)i * X + j];
-              raw[j] = acc;
-            }
-          } else if (kind == MLBP_OP_VAR) {
-            const int x = clamp[slot_var[c]];
-            for (int j = t; j < X; j += WG) {
-              double acc = uniform;
-              for (int q = 0; q < b; ++q) acc = nan_to_num(msg[(size_t)c_srcs[a + q] * X + j] * acc);
-              raw[j] = (x >= 0 && j != x) ? 0.0 : acc;
-            }
-          } else {
-            const double* u = d.unary_tables + (size_t)utab[a] * X;
-            for (int j = t; j < X; j += WG) raw[j] = u[j];
-          }
-          __syncthreads();
-          double part = 0.0;
-          for (int j = t; j < X; j += WG) part += raw[j];
-          const double total = norm ? block_sum(part, scratch) : 0.0;
+          generic_step<SumOp>(G, X, uniform, kind, a, b, c, state_of);
           double* out = msg + (size_t)c * X;
-          for (int j = t; j < X; j += WG) out[j] = renorm(raw[j], total, uniform, norm);
-          __syncthreads();
+          generic_finish(raw, X, uniform, norm, scratch, [&](int j, double fresh) { out[j] = fresh; });
         }
       }
       // the marginal of v -> raw, the draw by thread 0
-      double part = 0.0;
-      for (int j = t; j < X; j += WG) {
-        double acc = uniform;
-        for (int q = in_off[v]; q < in_off[v + 1]; ++q) acc = nan_to_num(msg[(size_t)in_slots[q] * X + j] * acc);
-        raw[j] = acc;
-        part += acc;
-      }
-      const double total = block_sum(part, scratch);
-      for (int j = t; j < X; j += WG) {
-        const double mm = total > 0.0 ? raw[j] / total : uniform;
+      generic_marginal(msg, in_off, in_slots, v, X, uniform, raw, scratch, [&](int j, double mm) {
         raw[j] = mm;
         if (d.cond_marginals) d.cond_marginals[(sg * d.n_vars + v) * X + j] = mm;
-      }
+      });
       __syncthreads();
       if (t == 0) {
         int x = d.given ? d.given[(size_t)g * d.n_vars + v] : -1;
@@ -375,19 +266,7 @@ __global__ __launch_bounds__(WG) void sample_generic_kernel(SampleDev d) {
 }
 
 // ---- host ----------------------------------------------------------------------------------------
-thread_local std::string g_last_error = "";
 thread_local int g_last_kernel = MLBP_SAMPLE_KERNEL_NONE;
-
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_last_error = buf;
-  return code;
-}
 
 int64_t x64_lds_bytes(int32_t n_msgs, int32_t n_vars) {
   return (int64_t)n_msgs * 512 + 4608 + 512 + 4 * (((int64_t)n_vars + 3) & ~(int64_t)3);
@@ -395,24 +274,6 @@ int64_t x64_lds_bytes(int32_t n_msgs, int32_t n_vars) {
 
 size_t generic_lds_bytes(int32_t X, int32_t n_vars) {
   return (size_t)((X + 1) & ~1) * 8 + 5 * 8 + 4 * (size_t)n_vars;
-}
-
-// The X = 64 kernel asks for more than the default 64 KiB of dynamic LDS: its limit is raised once per device and instance
-// (a host-side attribute call, on the first -- eager -- call).
-int grant_x64_lds(const void* kernel, int instance) {
-  enum { MAX_DEVICES = 64 };
-  static std::atomic<bool> granted[MAX_DEVICES][2];
-  static std::mutex mu;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return fail(MLBP_EHIP, "hipGetDevice failed");
-  if (dev < 0 || dev >= MAX_DEVICES) return fail(MLBP_EUNSUPPORTED, "device index %d beyond %d", dev, (int)MAX_DEVICES);
-  if (granted[dev][instance].load(std::memory_order_acquire)) return MLBP_OK;
-  std::lock_guard<std::mutex> lock(mu);
-  if (granted[dev][instance].load(std::memory_order_relaxed)) return MLBP_OK;
-  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MLBP_SAMPLE_X64_LDS_BYTES);
-  if (e != hipSuccess) return fail(MLBP_EHIP, "raising the X = 64 kernel's LDS limit failed: %s", hipGetErrorString(e));
-  granted[dev][instance].store(true, std::memory_order_release);
-  return MLBP_OK;
 }
 
 }  // namespace
@@ -452,39 +313,16 @@ int mlbp_sample_check_program(const int32_t* ops, int32_t n_ops, const int32_t* 
   if (n_ops <= 0 || n_sweeps <= 0 || n_msgs <= 0 || n_vars <= 0 || P < 0 || U < 0 || n_srcs < 0 || (n_srcs > 0 && !srcs))
     return fail(MLBP_EINVAL, "program: bad sizes (n_ops %d, n_sweeps %d, n_msgs %d, n_vars %d, P %d, U %d, n_srcs %d) or srcs is NULL",
                 n_ops, n_sweeps, n_msgs, n_vars, P, U, n_srcs);
-  for (int o = 0; o < n_ops; ++o) {
-    const int kind = ops[4 * o], a = ops[4 * o + 1], b = ops[4 * o + 2], c = ops[4 * o + 3];
-    if (c < 0 || c >= n_msgs) return fail(MLBP_EINVAL, "op %d: destination slot %d out of [0,%d)", o, c, n_msgs);
-    switch (kind) {
-      case MLBP_OP_UNARY:
-        if (a < 0 || a >= U) return fail(MLBP_EINVAL, "op %d: unary slot %d out of [0,%d)", o, a, U);
-        break;
-      case MLBP_OP_PAIR_TM:
-      case MLBP_OP_PAIR_MT:
-        if (a < 0 || a >= P) return fail(MLBP_EINVAL, "op %d: pair slot %d out of [0,%d)", o, a, P);
-        if (b < 0 || b >= n_msgs) return fail(MLBP_EINVAL, "op %d: source slot %d out of [0,%d)", o, b, n_msgs);
-        if (b == c) return fail(MLBP_EINVAL, "op %d: source and destination slot coincide", o);
-        break;
-      case MLBP_OP_VAR:
-        if (a < 0 || b < 0 || (int64_t)a + b > n_srcs) return fail(MLBP_EINVAL, "op %d: srcs range [%d,%d) out of [0,%d)", o, a, a + b, n_srcs);
-        for (int q = a; q < a + b; ++q)
-          if (srcs[q] < 0 || srcs[q] >= n_msgs) return fail(MLBP_EINVAL, "op %d: source slot %d out of [0,%d)", o, srcs[q], n_msgs);
-        break;
-      default:
-        return fail(MLBP_EINVAL, "op %d: unknown kind %d", o, kind);
-    }
+  const int rc = check_program_indices(ops, n_ops, srcs, n_srcs, sweeps, n_sweeps, n_msgs, P, U, [&](int o, int kind, int c) -> int {
     if (kind == MLBP_OP_VAR) {
       if (slot_var[c] < 0 || slot_var[c] >= n_vars)
         return fail(MLBP_EINVAL, "op %d: destination slot %d of a variable update has no source variable (slot_var %d, n_vars %d)", o, c, slot_var[c], n_vars);
     } else if (slot_var[c] != -1) {
       return fail(MLBP_EINVAL, "op %d: destination slot %d of a factor update has slot_var %d, not -1", o, c, slot_var[c]);
     }
-  }
-  for (int s = 0; s < n_sweeps; ++s) {
-    const int first = sweeps[2 * s], cnt = sweeps[2 * s + 1];
-    if (first < 0 || cnt < 0 || (int64_t)first + cnt > n_ops)
-      return fail(MLBP_EINVAL, "sweep %d: op range [%d,%d) out of [0,%d)", s, first, first + cnt, n_ops);
-  }
+    return MLBP_OK;
+  });
+  if (rc) return rc;
   std::vector<char> seen((size_t)n_vars, 0);
   for (int k = 0; k < n_vars; ++k) {
     if (order[k] < 0 || order[k] >= n_vars || seen[order[k]])
@@ -495,37 +333,22 @@ int mlbp_sample_check_program(const int32_t* ops, int32_t n_ops, const int32_t* 
 }
 
 int mlbp_sample_check_readout(int32_t n_vars, const int32_t* in_off, const int32_t* in_slots, int32_t n_msgs) {
-  if (!in_off || !in_slots) return fail(MLBP_EINVAL, "read-out: in_off or in_slots is NULL");
-  if (n_vars <= 0 || n_msgs <= 0) return fail(MLBP_EINVAL, "read-out: bad sizes (n_vars %d, n_msgs %d)", n_vars, n_msgs);
-  if (in_off[0] != 0) return fail(MLBP_EINVAL, "read-out: in_off[0] must be 0");
-  for (int v = 0; v < n_vars; ++v) {
-    if (in_off[v + 1] < in_off[v]) return fail(MLBP_EINVAL, "read-out: in_off not monotone at variable %d", v);
-    for (int q = in_off[v]; q < in_off[v + 1]; ++q)
-      if (in_slots[q] < 0 || in_slots[q] >= n_msgs) return fail(MLBP_EINVAL, "read-out: variable %d: slot %d out of [0,%d)", v, in_slots[q], n_msgs);
-  }
-  return MLBP_OK;
+  return check_readout_in_slots(n_vars, in_off, in_slots, n_msgs);
 }
 
 int mlbp_sample_f64(const mlbp_sample_args* a, void* stream) {
   g_last_kernel = MLBP_SAMPLE_KERNEL_NONE;
-  if (!a) return fail(MLBP_EINVAL, "args is NULL");
-  if (a->B <= 0 || a->n_msgs <= 0 || a->n_vars <= 0 || a->P < 0 || a->U < 0 || a->n_ops <= 0 || a->n_sweeps <= 0 || a->n_srcs < 0)
-    return fail(MLBP_EINVAL, "bad sizes: B %d, n_msgs %d, n_vars %d, P %d, U %d, n_ops %d, n_sweeps %d, n_srcs %d", a->B, a->n_msgs,
-                a->n_vars, a->P, a->U, a->n_ops, a->n_sweeps, a->n_srcs);
+  if (int e = check_args_sizes(a)) return e;
   if (a->S <= 0) return fail(MLBP_EINVAL, "S = %d: at least one sample per graph", a->S);
-  if (a->X < 2) return fail(MLBP_EINVAL, "X = %d: a variable needs at least two states", a->X);
+  if (int e = check_states(a->X)) return e;
   const int which = mlbp_sample_pick_kernel(a->X, a->n_msgs, a->n_vars);
   if (which < 0) return which;
-  if (!a->ops || !a->sweeps || (a->n_srcs > 0 && !a->srcs)) return fail(MLBP_EINVAL, "ops, srcs or sweeps is NULL");
-  if (!a->in_off || !a->in_slots) return fail(MLBP_EINVAL, "in_off or in_slots is NULL");
+  if (int e = check_args_program(a)) return e;
   if (!a->slot_var || !a->order) return fail(MLBP_EINVAL, "slot_var or order is NULL");
   if (!a->uniforms) return fail(MLBP_EINVAL, "uniforms is NULL");
   if (!a->samples || !a->logq) return fail(MLBP_EINVAL, "samples or logq is NULL");
-  if (a->P > 0 && (!a->pair_tables || !a->pair_tab || a->n_pair_tables <= 0))
-    return fail(MLBP_EINVAL, "P = %d but pair_tables or pair_tab is NULL (or n_pair_tables <= 0)", a->P);
-  if (a->U > 0 && (!a->unary_tables || !a->unary_tab || a->n_unary_tables <= 0))
-    return fail(MLBP_EINVAL, "U = %d but unary_tables or unary_tab is NULL (or n_unary_tables <= 0)", a->U);
-  if ((int64_t)a->n_msgs * a->X > 0x7fffffff / 2) return fail(MLBP_EUNSUPPORTED, "n_msgs * X = %lld too large", (long long)a->n_msgs * a->X);
+  if (int e = check_args_tables(a)) return e;
+  if (int e = check_args_extent(a)) return e;
   const int C = mlbp_sample_chunks(a->B, a->S);
   if (C < 0) return C;
   if (C > 65535) return fail(MLBP_EUNSUPPORTED, "chunks = %d beyond the grid's second dimension", C);
@@ -537,11 +360,7 @@ int mlbp_sample_f64(const mlbp_sample_args* a, void* stream) {
     if (generic_lds_bytes(a->X, a->n_vars) > 65536)
       return fail(MLBP_EUNSUPPORTED, "n_vars = %d: the generic kernel's clamp states do not fit LDS", a->n_vars);
   }
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
-    (void)hipGetLastError();
-    return fail(MLBP_ENODEVICE, "no HIP device visible: libmlbp_sample.so has no CPU fallback");
-  }
+  if (int e = check_device("libmlbp_sample.so")) return e;
   SampleDev d;
   d.pair_tables = a->pair_tables; d.pair_tab = a->pair_tab; d.unary_tables = a->unary_tables; d.unary_tab = a->unary_tab;
   d.ops = a->ops; d.srcs = a->srcs; d.sweeps = a->sweeps;
@@ -556,7 +375,7 @@ int mlbp_sample_f64(const mlbp_sample_args* a, void* stream) {
   if (which == MLBP_SAMPLE_KERNEL_X64) {
     const bool resident = a->P <= 3;
     auto k = resident ? sample_x64_kernel<true> : sample_x64_kernel<false>;
-    if (int e = grant_x64_lds((const void*)k, resident ? 1 : 0)) return e;
+    if (int e = grant_x64_lds((const void*)k, resident ? 1 : 0, MLBP_SAMPLE_X64_LDS_BYTES)) return e;
     hipLaunchKernelGGL(k, dim3(a->B, C), dim3(WG), (size_t)x64_lds_bytes(a->n_msgs, a->n_vars), st, d);
   } else {
     hipLaunchKernelGGL(sample_generic_kernel, dim3(a->B, C), dim3(WG), generic_lds_bytes(a->X, a->n_vars), st, d);

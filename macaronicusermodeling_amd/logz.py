@@ -9,15 +9,13 @@ axis of every pairwise factor, and the factor->variable slot of every (factor, v
 the library validate them on the host, uploads them once and caches the device copies per (topology, device).
 """
 import ctypes as C
-import os
-import threading
 
 import numpy as np
 
-from . import _ffi
+from . import _ffi, _sidelib
+from ._sidelib import i32 as _i32, i32p as _i32p
 
-_PKG = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_PKG, 'libmlbp_logz.so')
+LIB_PATH = _sidelib.lib_path('mlbp_logz')
 
 KERNEL_NONE, KERNEL_X64, KERNEL_X64_SHARED, KERNEL_GENERIC = 0, 1, 2, 3
 X64_LDS_BYTES = 65536           # include/mlbp_logz.h MLBP_LOGZ_X64_LDS_BYTES
@@ -26,10 +24,8 @@ GROUP = 16                      # graphs per workgroup of the shared-table kerne
 SHARED_PAIR_TABLES = 1          # MLBP_LOGZ_SHARED_PAIR_TABLES
 
 
-class LogzError(RuntimeError):
-    def __init__(self, code, msg):
-        RuntimeError.__init__(self, 'libmlbp_logz error %d: %s' % (code, msg))
-        self.code = code
+class LogzError(_sidelib.SideError):
+    LIB = 'libmlbp_logz'
 
 
 class LogzArgs(C.Structure):
@@ -41,9 +37,6 @@ class LogzArgs(C.Structure):
                 ('labels', C.c_void_p), ('log_z', C.c_void_p), ('score', C.c_void_p), ('joint_logp', C.c_void_p), ('sum_out', C.c_void_p)]
 
 
-_i32p = C.POINTER(C.c_int32)
-_i32 = C.c_int32
-
 # name -> (restype, argtypes); mirrors include/mlbp_logz.h one to one (tests/test_logz_cpu.py checks that).
 SIGNATURES = {
     'mlbp_logz_f64': (C.c_int, [C.POINTER(LogzArgs), C.c_void_p]),
@@ -54,42 +47,12 @@ SIGNATURES = {
     'mlbp_logz_last_error': (C.c_char_p, []),
 }
 
-
-def _load():
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(
-            'libmlbp_logz.so not found at %s.  Build it with `python -m macaronicusermodeling_amd.build` '
-            '(hipcc, gfx950).  There is no CPU fallback.' % LIB_PATH)
-    import torch  # noqa: F401      (torch's HIP runtime must be the one mapped first: see _ffi._load)
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)          # AttributeError here = header / library mismatch
-        fn.restype = res
-        fn.argtypes = args
-    return lib
-
-
-lib = _load()
-
-
-def last_error():
-    return lib.mlbp_logz_last_error().decode('utf-8', 'replace')
-
-
-def check(rc):
-    """Raises LogzError for negative return codes; returns rc otherwise."""
-    if rc < 0:
-        raise LogzError(rc, last_error())
-    return rc
-
-
-def last_kernel():
-    """KERNEL_X64 / KERNEL_X64_SHARED / KERNEL_GENERIC: the kernel the calling thread's last call enqueued (host-side record)."""
-    return lib.mlbp_logz_last_kernel()
+lib = _sidelib.load(LIB_PATH, SIGNATURES)
+last_error, check, last_kernel, _pick_kernel = _sidelib.status_helpers(lib, LogzError)
 
 
 def pick_kernel(X, n_in_slots, n_vars, flags=0):
-    return check(lib.mlbp_logz_pick_kernel(int(X), int(n_in_slots), int(n_vars), int(flags)))
+    return _pick_kernel(X, n_in_slots, n_vars, flags)
 
 
 def readout_arrays(topo):
@@ -128,18 +91,9 @@ class Readout:
         self.pair_axis_var, self.unary_var, self.pair_in_slot, self.unary_in_slot = up(pav), up(uv), up(pis), up(uis)
 
 
-_readouts = {}
-_readouts_lock = threading.Lock()
-_READOUTS_MAX = 4096
+_readouts = _sidelib.Cache()
 
 
 def readout(topo, device):
-    """The cached Readout of (topology, device).  The topology is held by the cache entry, so its id stays its own."""
-    key = (id(topo), str(device))
-    with _readouts_lock:
-        hit = _readouts.get(key)
-        if hit is None:
-            if len(_readouts) >= _READOUTS_MAX:
-                _readouts.clear()
-            hit = _readouts[key] = (topo, Readout(topo, device))
-    return hit[1]
+    """The cached Readout of (topology, device)."""
+    return _readouts.get(topo, (str(device),), lambda: Readout(topo, device))

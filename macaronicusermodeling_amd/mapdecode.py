@@ -8,25 +8,21 @@ sum-product sweeps run -- has the library validate it on the host, uploads (ops,
 once, and caches the device copies per (topology, roots, device).
 """
 import ctypes as C
-import os
-import threading
 
 import numpy as np
 
-from . import _ffi
+from . import _ffi, _sidelib
+from ._sidelib import i32 as _i32, i32p as _i32p
 
-_PKG = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_PKG, 'libmlbp_map.so')
+LIB_PATH = _sidelib.lib_path('mlbp_map')
 
 KERNEL_NONE, KERNEL_X64, KERNEL_GENERIC = 0, 1, 2
 X64_LDS_BYTES = 81920           # include/mlbp_map.h MLBP_MAP_X64_LDS_BYTES
 MAX_X = 1024
 
 
-class MapError(RuntimeError):
-    def __init__(self, code, msg):
-        RuntimeError.__init__(self, 'libmlbp_map error %d: %s' % (code, msg))
-        self.code = code
+class MapError(_sidelib.SideError):
+    LIB = 'libmlbp_map'
 
 
 class MapArgs(C.Structure):
@@ -41,9 +37,6 @@ class MapArgs(C.Structure):
                 ('max_marginals', C.c_void_p), ('assignment', C.c_void_p), ('score', C.c_void_p)]
 
 
-_i32p = C.POINTER(C.c_int32)
-_i32 = C.c_int32
-
 # name -> (restype, argtypes); mirrors include/mlbp_map.h one to one (tests/test_map_cpu.py checks that).
 SIGNATURES = {
     'mlbp_map_sweep_f64': (C.c_int, [C.POINTER(MapArgs), C.c_void_p]),
@@ -55,42 +48,8 @@ SIGNATURES = {
     'mlbp_map_last_error': (C.c_char_p, []),
 }
 
-
-def _load():
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(
-            'libmlbp_map.so not found at %s.  Build it with `python -m macaronicusermodeling_amd.build` '
-            '(hipcc, gfx950).  There is no CPU fallback.' % LIB_PATH)
-    import torch  # noqa: F401      (torch's HIP runtime must be the one mapped first: see _ffi._load)
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)          # AttributeError here = header / library mismatch
-        fn.restype = res
-        fn.argtypes = args
-    return lib
-
-
-lib = _load()
-
-
-def last_error():
-    return lib.mlbp_map_last_error().decode('utf-8', 'replace')
-
-
-def check(rc):
-    """Raises MapError for negative return codes; returns rc otherwise."""
-    if rc < 0:
-        raise MapError(rc, last_error())
-    return rc
-
-
-def last_kernel():
-    """KERNEL_X64 / KERNEL_GENERIC: the kernel the calling thread's last map sweep enqueued (host-side record)."""
-    return lib.mlbp_map_last_kernel()
-
-
-def pick_kernel(X, n_msgs, n_vars):
-    return check(lib.mlbp_map_pick_kernel(int(X), int(n_msgs), int(n_vars)))
+lib = _sidelib.load(LIB_PATH, SIGNATURES)
+last_error, check, last_kernel, pick_kernel = _sidelib.status_helpers(lib, MapError)
 
 
 def readout_arrays(topo):
@@ -106,42 +65,23 @@ def readout_arrays(topo):
     return pav, uv
 
 
-class MapProgram:
+class MapProgram(_sidelib.Program):
     """Validated device copies of one root sequence's (ops, srcs, sweeps) and of the topology's read-out arrays."""
 
-    def __init__(self, topo, roots, device):
-        import torch
-        self.roots = tuple(int(r) for r in roots)
-        ops, srcs, sweeps = topo.compile_program(self.roots)
-        ops = np.ascontiguousarray(ops.reshape(-1), dtype=np.int32)
-        srcs_h = np.ascontiguousarray(srcs if len(srcs) else np.zeros(1), dtype=np.int32)
-        sweeps = np.ascontiguousarray(sweeps.reshape(-1), dtype=np.int32)
-        self.n_ops, self.n_srcs, self.n_sweeps = len(ops) // 4, len(srcs), len(sweeps) // 2
-        check(lib.mlbp_map_check_program(_ffi.i32ptr(ops), self.n_ops, _ffi.i32ptr(srcs_h), self.n_srcs, _ffi.i32ptr(sweeps),
-                                         self.n_sweeps, topo.n_msgs, topo.P, topo.U))
+    def check_host(self):
+        topo = self.topo
         pav, uv = readout_arrays(topo)
-        in_off = np.ascontiguousarray(topo.in_off, dtype=np.int32)
-        in_slots = np.ascontiguousarray(topo.in_slots, dtype=np.int32)
-        check(lib.mlbp_map_check_readout(topo.n_vars, _ffi.i32ptr(in_off), _ffi.i32ptr(in_slots), topo.n_msgs, topo.P,
-                                         _ffi.i32ptr(pav.reshape(-1)), topo.U, _ffi.i32ptr(uv)))
-        up = lambda a: torch.from_numpy(a).to(device)          # noqa: E731
-        self.ops, self.srcs, self.sweeps = up(ops), up(srcs_h), up(sweeps)
-        self.in_off, self.in_slots = up(in_off), up(in_slots)
-        self.pair_axis_var, self.unary_var = up(pav.reshape(-1).copy()), up(uv)
+        self._pav_h, self._uv_h = _sidelib.host_i32(pav), uv
+        check(lib.mlbp_map_check_program(*self.program_args()))
+        check(lib.mlbp_map_check_readout(*self.in_slot_args(), topo.P, _ffi.i32ptr(self._pav_h), topo.U, _ffi.i32ptr(uv)))
+
+    def upload(self):
+        self.pair_axis_var, self.unary_var = self._up(self._pav_h), self._up(self._uv_h)
 
 
-_programs = {}
-_programs_lock = threading.Lock()
-_PROGRAMS_MAX = 4096
+_programs = _sidelib.Cache()
 
 
 def program(topo, roots, device):
-    """The cached MapProgram of (topology, roots, device).  The topology is held by the cache entry, so its id stays its own."""
-    key = (id(topo), tuple(int(r) for r in roots), str(device))
-    with _programs_lock:
-        hit = _programs.get(key)
-        if hit is None:
-            if len(_programs) >= _PROGRAMS_MAX:
-                _programs.clear()
-            hit = _programs[key] = (topo, MapProgram(topo, roots, device))
-    return hit[1]
+    """The cached MapProgram of (topology, roots, device)."""
+    return _programs.program(MapProgram, topo, roots, device)

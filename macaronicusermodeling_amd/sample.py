@@ -10,15 +10,13 @@ device copies per (topology, roots, device).  The drawing order is an argument o
 `SampleProgram.order(var_ids)` validates and caches its device copy.
 """
 import ctypes as C
-import os
-import threading
 
 import numpy as np
 
-from . import _ffi
+from . import _ffi, _sidelib
+from ._sidelib import i32 as _i32, i32p as _i32p
 
-_PKG = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_PKG, 'libmlbp_sample.so')
+LIB_PATH = _sidelib.lib_path('mlbp_sample')
 
 KERNEL_NONE, KERNEL_X64, KERNEL_GENERIC = 0, 1, 2
 X64_LDS_BYTES = 81920           # include/mlbp_sample.h MLBP_SAMPLE_X64_LDS_BYTES
@@ -26,10 +24,8 @@ MAX_X = 1024
 MIN_WORKGROUPS = 512
 
 
-class SampleError(RuntimeError):
-    def __init__(self, code, msg):
-        RuntimeError.__init__(self, 'libmlbp_sample error %d: %s' % (code, msg))
-        self.code = code
+class SampleError(_sidelib.SideError):
+    LIB = 'libmlbp_sample'
 
 
 class SampleArgs(C.Structure):
@@ -45,9 +41,6 @@ class SampleArgs(C.Structure):
                 ('samples', C.c_void_p), ('logq', C.c_void_p), ('cond_marginals', C.c_void_p)]
 
 
-_i32p = C.POINTER(C.c_int32)
-_i32 = C.c_int32
-
 # name -> (restype, argtypes); mirrors include/mlbp_sample.h one to one (tests/test_sample_cpu.py checks that).
 SIGNATURES = {
     'mlbp_sample_f64': (C.c_int, [C.POINTER(SampleArgs), C.c_void_p]),
@@ -61,42 +54,8 @@ SIGNATURES = {
     'mlbp_sample_last_error': (C.c_char_p, []),
 }
 
-
-def _load():
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(
-            'libmlbp_sample.so not found at %s.  Build it with `python -m macaronicusermodeling_amd.build` '
-            '(hipcc, gfx950).  There is no CPU fallback.' % LIB_PATH)
-    import torch  # noqa: F401      (torch's HIP runtime must be the one mapped first: see _ffi._load)
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)          # AttributeError here = header / library mismatch
-        fn.restype = res
-        fn.argtypes = args
-    return lib
-
-
-lib = _load()
-
-
-def last_error():
-    return lib.mlbp_sample_last_error().decode('utf-8', 'replace')
-
-
-def check(rc):
-    """Raises SampleError for negative return codes; returns rc otherwise."""
-    if rc < 0:
-        raise SampleError(rc, last_error())
-    return rc
-
-
-def last_kernel():
-    """KERNEL_X64 / KERNEL_GENERIC: the kernel the calling thread's last sampling call enqueued (host-side record)."""
-    return lib.mlbp_sample_last_kernel()
-
-
-def pick_kernel(X, n_msgs, n_vars):
-    return check(lib.mlbp_sample_pick_kernel(int(X), int(n_msgs), int(n_vars)))
+lib = _sidelib.load(LIB_PATH, SIGNATURES)
+last_error, check, last_kernel, pick_kernel = _sidelib.status_helpers(lib, SampleError)
 
 
 def chunks(B, S):
@@ -119,28 +78,17 @@ def slot_var_array(topo):
     return sv
 
 
-class SampleProgram:
+class SampleProgram(_sidelib.Program):
     """Validated device copies of one root sequence's (ops, srcs, sweeps), of slot_var and of the topology's read-out arrays."""
 
-    def __init__(self, topo, roots, device):
-        import torch
-        self.topo, self.device = topo, device
-        self.roots = tuple(int(r) for r in roots)
-        ops, srcs, sweeps = topo.compile_program(self.roots)
-        self._ops_h = np.ascontiguousarray(ops.reshape(-1), dtype=np.int32)
-        self._srcs_h = np.ascontiguousarray(srcs if len(srcs) else np.zeros(1), dtype=np.int32)
-        self._sweeps_h = np.ascontiguousarray(sweeps.reshape(-1), dtype=np.int32)
-        self.n_ops, self.n_srcs, self.n_sweeps = len(self._ops_h) // 4, len(srcs), len(self._sweeps_h) // 2
-        self._slot_var_h = slot_var_array(topo)
+    def check_host(self):
+        self._slot_var_h = slot_var_array(self.topo)
         self._orders = {}
-        in_off = np.ascontiguousarray(topo.in_off, dtype=np.int32)
-        in_slots = np.ascontiguousarray(topo.in_slots, dtype=np.int32)
-        check(lib.mlbp_sample_check_readout(topo.n_vars, _ffi.i32ptr(in_off), _ffi.i32ptr(in_slots), topo.n_msgs))
-        self._up = lambda a: torch.from_numpy(a).to(device)          # noqa: E731
+        check(lib.mlbp_sample_check_readout(*self.in_slot_args()))
         self.order(None)                                           # validates the program, with the default order
-        self.ops, self.srcs, self.sweeps = self._up(self._ops_h), self._up(self._srcs_h), self._up(self._sweeps_h)
+
+    def upload(self):
         self.slot_var = self._up(self._slot_var_h)
-        self.in_off, self.in_slots = self._up(in_off), self._up(in_slots)
 
     def order(self, var_ids):
         """Device int32 [n_vars] of a drawing order given as variable ids (None: var_ids order), validated and cached."""
@@ -156,27 +104,16 @@ class SampleProgram:
                 idx = np.array([topo.var_index[v] for v in key], dtype=np.int32)
                 if len(idx) != topo.n_vars:
                     raise ValueError('order must list every variable once (%d ids, %d variables)' % (len(idx), topo.n_vars))
-            check(lib.mlbp_sample_check_program(_ffi.i32ptr(self._ops_h), self.n_ops, _ffi.i32ptr(self._srcs_h), self.n_srcs,
-                                                _ffi.i32ptr(self._sweeps_h), self.n_sweeps, topo.n_msgs, topo.P, topo.U, topo.n_vars,
-                                                _ffi.i32ptr(self._slot_var_h), _ffi.i32ptr(idx)))
+            check(lib.mlbp_sample_check_program(*self.program_args(), topo.n_vars, _ffi.i32ptr(self._slot_var_h), _ffi.i32ptr(idx)))
             if len(self._orders) >= 64:
                 self._orders.clear()
             self._orders[key] = self._up(idx)
         return self._orders[key]
 
 
-_programs = {}
-_programs_lock = threading.Lock()
-_PROGRAMS_MAX = 4096
+_programs = _sidelib.Cache()
 
 
 def program(topo, roots, device):
-    """The cached SampleProgram of (topology, roots, device).  The topology is held by the cache entry, so its id stays its own."""
-    key = (id(topo), tuple(int(r) for r in roots), str(device))
-    with _programs_lock:
-        hit = _programs.get(key)
-        if hit is None:
-            if len(_programs) >= _PROGRAMS_MAX:
-                _programs.clear()
-            hit = _programs[key] = (topo, SampleProgram(topo, roots, device))
-    return hit[1]
+    """The cached SampleProgram of (topology, roots, device)."""
+    return _programs.program(SampleProgram, topo, roots, device)
