@@ -473,6 +473,63 @@ class FactorGraphBatch:
         V.check(V.lib.mlbp_converge_f64(C.byref(a), _stream_ptr(self.device)))
         return (rounds, residual, hist) if history else (rounds, residual)
 
+    # ---- the model's true marginals and log Z (include/mlbp_cutset.h) --------------------------------
+    def exact_inference(self, labels=None, marginals=None, cutset=None):
+        """The TRUE log Z and marginals of every graph by cutset conditioning -- what sweep() and log_partition() approximate
+        on a loopy graph.  Returns (log_z [B], marginals [B][n_vars][X]) device tensors, or (log_z, marginals, joint_logp [B])
+        when `labels` ([B][n_vars] integers, GraphTopology.var_ids order) is given: joint_logp = score(labels) - log_z, the true
+        log-probability of the assignment.  marginals: optional contiguous float64 [B][n_vars][X] device tensor to write into.
+        cutset: a list of variable ids that replaces cutset.choose(topo); the pairwise factors among the other variables
+        must form a forest, and X^len(cutset) may not pass 65536 (CutsetError otherwise).  Any valid cutset gives the same
+        values up to rounding.  self.msgs is neither read nor written."""
+        from . import cutset as K
+        if self.pair_tables is not None and self.pair_tables.dtype != torch.float64:
+            raise NotImplementedError('exact_inference needs float64 pairwise tables')
+        topo = self.topo
+        if cutset is not None:
+            unknown = [v for v in cutset if v not in topo.var_index]
+            if unknown:
+                raise ValueError('cutset names unknown variable ids %r' % (unknown,))
+            cutset = [topo.var_index[v] for v in cutset]
+        pl = K.plan(topo, cutset, self.X, self.device)
+        a = K.CutsetArgs()
+        a.B, a.X, a.n_vars, a.P, a.U = self.B, self.X, topo.n_vars, topo.P, topo.U
+        a.n_cut, a.n_free, a.n_items, a.n_consts, a.n_forest = pl.n_cut, pl.n_free, pl.n_items, pl.n_consts, pl.n_forest
+        a.plan, a.plan_words = pl.dev.data_ptr(), len(pl.words)
+        if topo.P:
+            if self.pair_tables is None:
+                raise RuntimeError('set_pair_tables() first')
+            a.n_pair_tables = self.pair_tables.shape[0]
+            a.pair_tables, a.pair_tab = self.pair_tables.data_ptr(), self.pair_tab.data_ptr()
+        if topo.U:
+            if self.unary_tables is None:
+                raise RuntimeError('set_unary_tables() first')
+            a.n_unary_tables = self.unary_tables.shape[0]
+            a.unary_tables, a.unary_tab = self.unary_tables.data_ptr(), self.unary_tab.data_ptr()
+        if marginals is None:
+            marginals = torch.empty(self.B, topo.n_vars, self.X, dtype=torch.float64, device=self.device)
+        elif tuple(marginals.shape) != (self.B, topo.n_vars, self.X) or marginals.dtype != torch.float64 \
+                or marginals.device != self.device or not marginals.is_contiguous():
+            raise ValueError('marginals must be a contiguous float64 device tensor [B][n_vars][X]')
+        log_z = torch.empty(self.B, dtype=torch.float64, device=self.device)
+        a.log_z, a.marginals = log_z.data_ptr(), marginals.data_ptr()
+        joint = lab = None
+        if labels is not None:
+            if torch.is_tensor(labels) and labels.dtype == torch.int32 and labels.device == self.device and labels.is_contiguous():
+                lab = labels
+            else:
+                host = labels.cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
+                lab = torch.from_numpy(np.ascontiguousarray(host.astype(np.int64).astype(np.int32))).to(self.device)
+            if tuple(lab.shape) != (self.B, topo.n_vars):
+                raise ValueError('labels must be [B][n_vars]')
+            joint = torch.empty(self.B, dtype=torch.float64, device=self.device)
+            a.labels, a.joint_logp = lab.data_ptr(), joint.data_ptr()
+        need = K.workspace_bytes(self.B, self.X, topo.n_vars, topo.P, topo.U, pl.n_forest, pl.n_cut)
+        work = torch.empty(need // 8, dtype=torch.float64, device=self.device)
+        a.workspace, a.workspace_bytes = work.data_ptr(), need
+        K.check(K.lib.mlbp_cutset_f64(C.byref(a), _stream_ptr(self.device)))
+        return (log_z, marginals) if labels is None else (log_z, marginals, joint)
+
     def treelike_inference(self, iterations, roots):
         """`iterations` sweeps if the graph is loopy, else one (LBP.py:219); `roots` replaces the
         per-sweep random.sample draw (LBP.py:223).  Returns the number of sweeps run."""

@@ -48,6 +48,13 @@ def all_reduce_sum_(buf):
     return buf
 
 
+def all_reduce_max_(buf):
+    """In-place MAX all-reduce; a no-op without a process group."""
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        dist.all_reduce(buf, op=dist.ReduceOp.MAX)
+    return buf
+
+
 def world_size():
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
 

@@ -291,6 +291,21 @@ class UserGraphTrainer:
         log_z, joint = fb.log_partition(self.roots[:self.n_sweeps_run], init=True, labels=fb._labels)
         return joint.cpu().numpy(), log_z.cpu().numpy()
 
+    def exact_inference(self):
+        """How wrong the usual sweeps were for each instance, under the current thetas: host (log_z float64 [B] -- the model's
+        true log Z by FactorGraphBatch.exact_inference --, bethe_gap float64 [B] -- log_partition after the predict() schedule
+        minus log_z --, marginal_gap float64 [B] -- the largest |BP marginal - exact marginal| over variables and states --,
+        top_agrees bool [B] -- every word's top guess is the same --, joint_logp float64 [B] -- the true log-probability of the
+        stored labels).  Raises cutset.CutsetError(MLBP_EUNSUPPORTED) for a shape above the configuration limit."""
+        fb = self.batch
+        self.build_potentials()
+        log_z, exact, joint = fb.exact_inference(labels=fb._labels)
+        bethe = fb.log_partition(self.roots[:self.n_sweeps_run], init=True)
+        bp = fb.marginals()
+        gap = (bp - exact).abs().reshape(fb.B, -1).max(dim=1).values
+        agrees = (bp.argmax(dim=2) == exact.argmax(dim=2)).all(dim=1)
+        return (log_z.cpu().numpy(), (bethe - log_z).cpu().numpy(), gap.cpu().numpy(), agrees.cpu().numpy(), joint.cpu().numpy())
+
 
 def apply_update(theta_en_en, theta_en_de, stats, F_ee, F_ed, learning_rate, reg_param):
     """theta += sum_i lr (g_i - reg theta) = lr (sum_i g_i - n reg theta): the sum of the per-instance
@@ -871,6 +886,46 @@ class TiDirTrainer:
         mdist.all_reduce_sum_(tot)
         tot = tot.cpu().numpy()
         return per_instance, (int(tot[0]), int(tot[1]), int(tot[2]), float(tot[3]))
+
+    # ---- how wrong was it: the sweeps against the model's true values (include/mlbp_cutset.h) ---------
+    def exactness_report(self):
+        """-> (per_instance, totals, skipped).  per_instance[i], for instance i of this rank's shard in file order: (predicted
+        positions, exact log_z, Bethe gap, largest |BP marginal - exact marginal|, every top guess agrees) as
+        UserGraphTrainer.exact_inference gives them; an instance without a predicted word builds no graph and gives
+        ((), 0.0, 0.0, 0.0, True); an instance of a shape above the configuration limit gives (positions, None, None, None, None).
+        totals = (sentences compared, sentences skipped, sum of |Bethe gap|, largest marginal gap, sentences whose top guesses
+        all agree) over ALL ranks' instances, reduced once.  skipped: [(predicted positions, instances, reason)] of this rank's
+        shapes above the limit."""
+        from . import cutset as K
+        n = self._shard[1] - self._shard[0]
+        per_instance = [((), 0.0, 0.0, 0.0, True)] * n
+        seen = n_skipped = n_agree = 0
+        sum_gap = 0.0
+        worst = torch.zeros(1, dtype=torch.float64, device=self.device)
+        skipped = []
+        for key, tr in self.trainers.items():
+            rows = self.buckets[key]['rows']
+            try:
+                log_z, bethe_gap, marg_gap, agrees, _ = tr.exact_inference()
+            except K.CutsetError as e:
+                if e.code != _ffi.MLBP_EUNSUPPORTED:
+                    raise
+                skipped.append((tuple(key[1]), len(rows), str(e)))
+                n_skipped += len(rows)
+                for row in rows:
+                    per_instance[row['index']] = (tuple(key[1]), None, None, None, None)
+                continue
+            seen += len(rows)
+            sum_gap += float(np.abs(bethe_gap).sum())
+            n_agree += int(agrees.sum())
+            worst[0] = max(float(worst[0]), float(marg_gap.max()))
+            for b, row in enumerate(rows):
+                per_instance[row['index']] = (tuple(key[1]), float(log_z[b]), float(bethe_gap[b]), float(marg_gap[b]), bool(agrees[b]))
+        tot = torch.tensor([float(seen), float(n_skipped), sum_gap, float(n_agree)], dtype=torch.float64, device=self.device)
+        mdist.all_reduce_sum_(tot)
+        mdist.all_reduce_max_(worst)
+        tot = tot.cpu().numpy()
+        return per_instance, (int(tot[0]), int(tot[1]), float(tot[2]), float(worst[0]), int(tot[3])), skipped
 
     # ---- joint log-likelihood (log Z; the reference has only the sum of per-word log-marginals) ------
     def joint_log_likelihood(self):
