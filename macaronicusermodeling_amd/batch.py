@@ -530,6 +530,57 @@ class FactorGraphBatch:
         K.check(K.lib.mlbp_cutset_f64(C.byref(a), _stream_ptr(self.device)))
         return (log_z, marginals) if labels is None else (log_z, marginals, joint)
 
+    # ---- the exact MAP assignment and the max-marginals (include/mlbp_exactmap.h) ----------------------
+    def exact_map(self, max_marginals=None, cutset=None):
+        """The TRUE jointly most probable assignment of every graph by cutset conditioning -- what map_sweep() approximates
+        on a loopy graph.  Returns (assignment int32 [B][n_vars] in GraphTopology.var_ids order, score float64 [B]) device
+        tensors -- score: the log-potential of the assignment, map_sweep's score --, and with max_marginals=True or a
+        contiguous float64 [B][n_vars][X] device tensor to write into also that tensor: max_marginals[b][v][s] = the best
+        score of any assignment with variable v in state s (natural log; -inf where none has a positive potential).  Ties
+        are broken as include/mlbp_exactmap.h says; the bits of every output depend on the graph and the cutset alone.
+        cutset: as in exact_inference.  self.msgs is neither read nor written."""
+        from . import exactmap as K
+        if self.pair_tables is not None and self.pair_tables.dtype != torch.float64:
+            raise NotImplementedError('exact_map needs float64 pairwise tables')
+        topo = self.topo
+        if cutset is not None:
+            unknown = [v for v in cutset if v not in topo.var_index]
+            if unknown:
+                raise ValueError('cutset names unknown variable ids %r' % (unknown,))
+            cutset = [topo.var_index[v] for v in cutset]
+        pl = K.plan(topo, cutset, self.X, self.device)
+        a = K.ExactMapArgs()
+        a.B, a.X, a.n_vars, a.P, a.U = self.B, self.X, topo.n_vars, topo.P, topo.U
+        a.n_cut, a.n_free, a.n_items, a.n_consts, a.n_forest = pl.n_cut, pl.n_free, pl.n_items, pl.n_consts, pl.n_forest
+        a.plan, a.plan_words = pl.dev.data_ptr(), len(pl.words)
+        if topo.P:
+            if self.pair_tables is None:
+                raise RuntimeError('set_pair_tables() first')
+            a.n_pair_tables = self.pair_tables.shape[0]
+            a.pair_tables, a.pair_tab = self.pair_tables.data_ptr(), self.pair_tab.data_ptr()
+        if topo.U:
+            if self.unary_tables is None:
+                raise RuntimeError('set_unary_tables() first')
+            a.n_unary_tables = self.unary_tables.shape[0]
+            a.unary_tables, a.unary_tab = self.unary_tables.data_ptr(), self.unary_tab.data_ptr()
+        if max_marginals is True:
+            max_marginals = torch.empty(self.B, topo.n_vars, self.X, dtype=torch.float64, device=self.device)
+        elif max_marginals is False:
+            max_marginals = None
+        if max_marginals is not None:
+            if not torch.is_tensor(max_marginals) or tuple(max_marginals.shape) != (self.B, topo.n_vars, self.X) \
+                    or max_marginals.dtype != torch.float64 or max_marginals.device != self.device or not max_marginals.is_contiguous():
+                raise ValueError('max_marginals must be True or a contiguous float64 device tensor [B][n_vars][X]')
+            a.max_marginals = max_marginals.data_ptr()
+        assignment = torch.empty(self.B, topo.n_vars, dtype=torch.int32, device=self.device)
+        score = torch.empty(self.B, dtype=torch.float64, device=self.device)
+        a.assignment, a.score = assignment.data_ptr(), score.data_ptr()
+        need = K.workspace_bytes(self.B, self.X, topo.n_vars, topo.P, topo.U, pl.n_forest, pl.n_cut, max_marginals is not None)
+        work = torch.empty(need // 8, dtype=torch.float64, device=self.device)
+        a.workspace, a.workspace_bytes = work.data_ptr(), need
+        K.check(K.lib.mlbp_exactmap_f64(C.byref(a), _stream_ptr(self.device)))
+        return (assignment, score) if max_marginals is None else (assignment, score, max_marginals)
+
     def treelike_inference(self, iterations, roots):
         """`iterations` sweeps if the graph is loopy, else one (LBP.py:219); `roots` replaces the
         per-sweep random.sample draw (LBP.py:223).  Returns the number of sweeps run."""

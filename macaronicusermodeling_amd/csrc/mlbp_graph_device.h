@@ -1,5 +1,5 @@
 // Device helpers shared by the side libraries (libmlbp_map.so, libmlbp_logz.so, libmlbp_sample.so, libmlbp_converge.so,
-// libmlbp_cutset.so; gfx950 only): the reductions, the X = 64 table fragment and its two contractions, one sweep op in the X = 64 and in the generic
+// libmlbp_cutset.so, libmlbp_exactmap.so; gfx950 only): the reductions, the X = 64 table fragment and its two contractions, one sweep op in the X = 64 and in the generic
 // form, and a variable's marginal from its in-slots.  The contractions and the steps take the combining operation as a tag:
 // SumOp for sum-product, MaxOp for max-product.  Helpers only, no __global__ function: every library keeps its own kernels,
 // which own the round / sample loops, the read-out, the refusal and the LDS carve-up.  Not part of the ABI.

@@ -1,5 +1,5 @@
 // Host helpers shared by the side libraries (libmlbp_map.so, libmlbp_logz.so, libmlbp_sample.so, libmlbp_converge.so,
-// libmlbp_cutset.so): the
+// libmlbp_cutset.so, libmlbp_exactmap.so): the
 // thread's last error, the index checks of a sweep program and of the read-out arrays, the argument checks every compute
 // entry starts with, and the LDS grant of the X = 64 kernels.  Each library is one translation unit, so everything here is in
 // the anonymous namespace: each .so has its own g_last_error.  Not part of the ABI.

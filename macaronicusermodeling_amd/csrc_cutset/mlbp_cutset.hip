@@ -26,14 +26,11 @@
 #define MLBP_GRAPH_NO_SWEEPS                // this library runs no sweep program: mlbp_cutset.h has no op kinds
 #include "../csrc/mlbp_graph_device.h"
 #include "../csrc/mlbp_graph_host.h"
+#include "../csrc/mlbp_cutset_plan.h"       // the plan's layout and check, the power-of-two helpers: shared with libmlbp_exactmap.so
 
 namespace {
 
 using namespace mlbp_graph;
-
-constexpr int HEADER = MLBP_CUTSET_PLAN_HEADER;
-constexpr int EMPTY = -(1 << 28);           // the exponent of a partial sum that holds nothing yet
-constexpr int MIN_SHIFT = -4000;            // ldexp by less than this is zero for every finite double
 
 struct CutsetDev {
   const int32_t* plan;
@@ -45,68 +42,6 @@ struct CutsetDev {
   double* log_z; double* marginals; double* score; double* joint_logp;
   int32_t B, X, n_vars, P, U, n_cut, n_free, n_items, n_consts, n_forest, n_pair_tables, n_unary_tables, n_configs, chunks, parts;
 };
-
-// The sections of a packed plan behind its header; returns the number of words.  The sizes have been checked.
-template <class Ptr>
-struct PlanSections { Ptr cutset, order, parent, item_off, items, consts, pav, uvar, fslot; };
-
-template <class Ptr>
-__host__ __device__ inline int64_t carve_plan(Ptr plan, int n_vars, int P, int U, int n_cut, int n_free, int n_items, int n_consts,
-                                              PlanSections<Ptr>& s) {
-  int64_t w = HEADER;
-  s.cutset = plan + w; w += n_cut;
-  s.order = plan + w; w += n_free;
-  s.parent = plan + w; w += 2 * (int64_t)n_vars;
-  s.item_off = plan + w; w += (int64_t)n_vars + 1;
-  s.items = plan + w; w += 3 * (int64_t)n_items;
-  s.consts = plan + w; w += 4 * (int64_t)n_consts;
-  s.pav = plan + w; w += 2 * (int64_t)P;
-  s.uvar = plan + w; w += U;
-  s.fslot = plan + w; w += P;
-  return w;
-}
-
-inline int64_t plan_words(int64_t n_vars, int64_t P, int64_t U, int64_t n_cut, int64_t n_free, int64_t n_items, int64_t n_consts) {
-  return HEADER + n_cut + n_free + 2 * n_vars + n_vars + 1 + 3 * n_items + 4 * n_consts + 2 * P + U + P;
-}
-
-// ---- powers of two ---------------------------------------------------------------------------------
-// The exponent e that brings a positive normal x to x * 2^-e in [1, 2); 0 for zero, a negative number, NaN and +inf.
-__device__ __forceinline__ int exp_of(double x) {
-  if (!(x > 0.0) || x == __builtin_huge_val()) return 0;
-  return ((__double2hiint(x) >> 20) & 0x7ff) - 1023;
-}
-
-struct Scaled { double m; int e; };          // m * 2^e
-
-__device__ __forceinline__ void mul(Scaled& z, double v) {
-  z.m *= v;
-  const int e = exp_of(z.m);
-  z.m = ldexp(z.m, -e);
-  z.e += e;
-}
-
-// Max over the workgroup of non-negative values, the same bits in every thread (a NaN is passed over); two barriers.
-__device__ __forceinline__ double block_max(double v, double* scratch /*[4]*/) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmax(fmax(scratch[0], scratch[1]), fmax(scratch[2], scratch[3]));
-}
-
-// vec[0 .. X) times 2^-e, e the exponent of its largest entry; returns e.  The entries are visible on entry (a barrier
-// behind the writes); ends with a barrier.
-__device__ __forceinline__ int rescale(double* vec, int X, double* scratch) {
-  const int t = threadIdx.x;
-  double m = 0.0;
-  for (int j = t; j < X; j += WG) m = fmax(m, vec[j]);
-  const int e = exp_of(block_max(m, scratch));
-  if (e != 0)
-    for (int j = t; j < X; j += WG) vec[j] = ldexp(vec[j], -e);
-  __syncthreads();
-  return e;
-}
 
 // ---- contractions: out[i] = sum_j T[i][j] m[j] (tm) or out[j] = sum_i m[i] T[i][j]; a barrier behind the result ---------
 __device__ __forceinline__ void contract_stream(const double* T, int X, int te, bool tm, const double* m, double* out) {
@@ -331,13 +266,6 @@ __device__ __forceinline__ double wave_contract_x64(const double* table, bool tm
   return (a[0] + a[1]) + (a[2] + a[3]);
 }
 
-// v times 2^-e, e the exponent of the wave's largest entry; e is added to the tally.
-__device__ __forceinline__ double wave_rescale(double v, int& tally) {
-  const int e = exp_of(wave_max(fmax(v, 0.0)));
-  tally += e;
-  return e != 0 ? ldexp(v, -e) : v;
-}
-
 __global__ __launch_bounds__(WG) void cutset_x64_kernel(CutsetDev d) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int X = 64;
@@ -542,20 +470,6 @@ int64_t x64_lds_bytes(int64_t n_vars, int64_t P, int64_t U, int64_t n_forest) {
 }
 int64_t generic_lds_bytes(int64_t n_vars, int64_t P, int64_t U, int64_t X) { return vector_doubles(n_vars, X) * 8 + 64 + ints_bytes(P, U); }
 
-// X^n_cut, or -1 beyond MLBP_CUTSET_MAX_CONFIGS
-int64_t count_configs(int32_t X, int32_t n_cut) {
-  int64_t n = 1;
-  for (int q = 0; q < n_cut; ++q) {
-    n *= X;
-    if (n > MLBP_CUTSET_MAX_CONFIGS) return -1;
-  }
-  return n;
-}
-
-int too_many_configs(int32_t X, int32_t n_cut) {
-  return fail(MLBP_EUNSUPPORTED, "X^|C| = %d^%d configurations: at most %d are supported", X, n_cut, MLBP_CUTSET_MAX_CONFIGS);
-}
-
 }  // namespace
 
 extern "C" {
@@ -594,121 +508,7 @@ int64_t mlbp_cutset_workspace_bytes(int32_t B, int32_t X, int32_t n_vars, int32_
   return (int64_t)B * chunks * per * 8;
 }
 
-int mlbp_cutset_check_plan(const int32_t* plan, int32_t n_words, int32_t X) {
-  if (!plan || n_words < HEADER) return fail(MLBP_EINVAL, "plan: NULL or shorter than its header of %d words", HEADER);
-  const int n_vars = plan[0], P = plan[1], U = plan[2], n_cut = plan[3], n_free = plan[4], n_items = plan[5], n_consts = plan[6],
-            n_forest = plan[7];
-  if (n_vars <= 0 || P < 0 || U < 0 || P + U <= 0 || n_cut < 0 || n_free < 0 || n_items < 0 || n_consts < 0 || n_forest < 0 ||
-      (int64_t)n_cut + n_free != n_vars)
-    return fail(MLBP_EINVAL, "plan: bad header (n_vars %d, P %d, U %d, n_cut %d, n_free %d, n_items %d, n_consts %d, n_forest %d)", n_vars,
-                P, U, n_cut, n_free, n_items, n_consts, n_forest);
-  if (plan_words(n_vars, P, U, n_cut, n_free, n_items, n_consts) != n_words)
-    return fail(MLBP_EINVAL, "plan: header asks for %lld words, the array has %d", (long long)plan_words(n_vars, P, U, n_cut, n_free, n_items, n_consts),
-                n_words);
-  if (int e = check_states(X)) return e;
-  if (X > MLBP_CUTSET_MAX_X) return fail(MLBP_EUNSUPPORTED, "X = %d: at most %d states are supported", X, MLBP_CUTSET_MAX_X);
-  PlanSections<const int32_t*> s;
-  carve_plan(plan, n_vars, P, U, n_cut, n_free, n_items, n_consts, s);
-
-  std::vector<int> cutpos(n_vars, -1), pos(n_vars, -1);
-  for (int q = 0; q < n_cut; ++q) {
-    const int v = s.cutset[q];
-    if (v < 0 || v >= n_vars) return fail(MLBP_EINVAL, "plan: cutset entry %d: variable %d out of range [0,%d)", q, v, n_vars);
-    if (cutpos[v] >= 0) return fail(MLBP_EINVAL, "plan: cutset entry %d: variable %d is repeated", q, v);
-    cutpos[v] = q;
-  }
-  if (count_configs(X, n_cut) < 0) return too_many_configs(X, n_cut);
-  for (int i = 0; i < n_free; ++i) {
-    const int v = s.order[i];
-    if (v < 0 || v >= n_vars || cutpos[v] >= 0 || pos[v] >= 0)
-      return fail(MLBP_EINVAL, "plan: order entry %d: variable %d is out of range, in the cutset or repeated", i, v);
-    pos[v] = i;
-  }
-  for (int p = 0; p < P; ++p) {
-    const int a = s.pav[2 * p], b = s.pav[2 * p + 1];
-    if (a < 0 || a >= n_vars || b < 0 || b >= n_vars) return fail(MLBP_EINVAL, "plan: pair factor %d: variable out of range [0,%d)", p, n_vars);
-    if (a == b) return fail(MLBP_EINVAL, "plan: pair factor %d joins variable %d with itself", p, a);
-  }
-  for (int u = 0; u < U; ++u)
-    if (s.uvar[u] < 0 || s.uvar[u] >= n_vars) return fail(MLBP_EINVAL, "plan: unary factor %d: variable %d out of range [0,%d)", u, s.uvar[u], n_vars);
-
-  // the forest: every parent link joins a variable to a later one through a factor of its own
-  std::vector<int> pair_used(P, 0), unary_used(U, 0);
-  int slot = 0;
-  for (int v = 0; v < n_vars; ++v)
-    if (cutpos[v] >= 0 && (s.parent[2 * v] != -1 || s.parent[2 * v + 1] != -1))
-      return fail(MLBP_EINVAL, "plan: cutset variable %d has a parent link", v);
-  for (int i = 0; i < n_free; ++i) {
-    const int v = s.order[i], p = s.parent[2 * v], par = s.parent[2 * v + 1];
-    if (p == -1 && par == -1) continue;
-    if (p < 0 || p >= P || par < 0 || par >= n_vars || pos[par] <= i ||
-        !((s.pav[2 * p] == v && s.pav[2 * p + 1] == par) || (s.pav[2 * p] == par && s.pav[2 * p + 1] == v)))
-      return fail(MLBP_EINVAL, "plan: parent link of variable %d (factor %d, parent %d): the factor does not join the two or the parent does not come later", v, p, par);
-    if (pair_used[p]++) return fail(MLBP_EINVAL, "plan: pair factor %d is used twice", p);
-    if (s.fslot[p] != slot) return fail(MLBP_EINVAL, "plan: forest_slot[%d] = %d, expected %d", p, s.fslot[p], slot);
-    ++slot;
-  }
-  if (slot != n_forest) return fail(MLBP_EINVAL, "plan: n_forest = %d but %d parent links", n_forest, slot);
-  for (int p = 0; p < P; ++p) {
-    const int a = s.pav[2 * p], b = s.pav[2 * p + 1];
-    if (pair_used[p]) continue;
-    if (s.fslot[p] != -1) return fail(MLBP_EINVAL, "plan: forest_slot[%d] = %d for a factor that is no parent link", p, s.fslot[p]);
-    if (cutpos[a] >= 0 || cutpos[b] >= 0) continue;
-    // a factor between two free variables that is no parent link: walk both to their roots
-    std::string path_a = std::to_string(a), path_b;
-    std::vector<int> seen(n_vars, 0);
-    for (int x = a; x >= 0; x = s.parent[2 * x + 1]) seen[x] = 1;
-    int meet = b;
-    while (meet >= 0 && !seen[meet]) meet = s.parent[2 * meet + 1];
-    if (meet < 0) return fail(MLBP_EINVAL, "plan: pair factor %d joins two trees of the remainder: it is left out of the forest", p);
-    for (int x = a; x != meet; ) { x = s.parent[2 * x + 1]; path_a += " - " + std::to_string(x); }
-    for (int x = b; x != meet; x = s.parent[2 * x + 1]) path_b = " - " + std::to_string(x) + path_b;
-    return fail(MLBP_EINVAL, "plan: the remainder has a cycle through factor %d: variables %s%s - %d", p, path_a.c_str(), path_b.c_str(), a);
-  }
-
-  // items and consts: every other factor once, where its variables say
-  if (s.item_off[0] != 0) return fail(MLBP_EINVAL, "plan: item_off[0] must be 0");
-  for (int v = 0; v < n_vars; ++v) {
-    const int lo = s.item_off[v], hi = s.item_off[v + 1];
-    if (hi < lo || hi > n_items) return fail(MLBP_EINVAL, "plan: item_off not monotone or beyond the %d items at variable %d", n_items, v);
-    if (cutpos[v] >= 0 && hi != lo) return fail(MLBP_EINVAL, "plan: cutset variable %d has items", v);
-    for (int it = lo; it < hi; ++it) {
-      const int kind = s.items[3 * it], f = s.items[3 * it + 1], q = s.items[3 * it + 2];
-      if (kind == MLBP_CUTSET_ITEM_UNARY) {
-        if (f < 0 || f >= U || s.uvar[f] != v) return fail(MLBP_EINVAL, "plan: item %d: unary factor %d is not on variable %d", it, f, v);
-        if (unary_used[f]++) return fail(MLBP_EINVAL, "plan: unary factor %d is used twice", f);
-      } else if (kind == MLBP_CUTSET_ITEM_COL || kind == MLBP_CUTSET_ITEM_ROW) {
-        const int mine = kind == MLBP_CUTSET_ITEM_COL ? 0 : 1;
-        if (f < 0 || f >= P || q < 0 || q >= n_cut || s.pav[2 * f + mine] != v || s.pav[2 * f + 1 - mine] != s.cutset[q])
-          return fail(MLBP_EINVAL, "plan: item %d: pair factor %d does not join variable %d (axis %d) and cut position %d", it, f, v, mine, q);
-        if (pair_used[f]++) return fail(MLBP_EINVAL, "plan: pair factor %d is used twice", f);
-      } else {
-        return fail(MLBP_EINVAL, "plan: item %d: unknown kind %d", it, kind);
-      }
-    }
-  }
-  if (s.item_off[n_vars] != n_items) return fail(MLBP_EINVAL, "plan: item_off[n_vars] = %d, but %d items", s.item_off[n_vars], n_items);
-  for (int i = 0; i < n_consts; ++i) {
-    const int kind = s.consts[4 * i], f = s.consts[4 * i + 1], q0 = s.consts[4 * i + 2], q1 = s.consts[4 * i + 3];
-    if (q0 < 0 || q0 >= n_cut) return fail(MLBP_EINVAL, "plan: const %d: cut position %d out of range [0,%d)", i, q0, n_cut);
-    if (kind == MLBP_CUTSET_CONST_UNARY) {
-      if (f < 0 || f >= U || s.uvar[f] != s.cutset[q0]) return fail(MLBP_EINVAL, "plan: const %d: unary factor %d is not on cut position %d", i, f, q0);
-      if (unary_used[f]++) return fail(MLBP_EINVAL, "plan: unary factor %d is used twice", f);
-    } else if (kind == MLBP_CUTSET_CONST_PAIR) {
-      if (q1 < 0 || q1 >= n_cut) return fail(MLBP_EINVAL, "plan: const %d: cut position %d out of range [0,%d)", i, q1, n_cut);
-      if (f < 0 || f >= P || s.pav[2 * f] != s.cutset[q0] || s.pav[2 * f + 1] != s.cutset[q1])
-        return fail(MLBP_EINVAL, "plan: const %d: pair factor %d does not join cut positions %d and %d", i, f, q0, q1);
-      if (pair_used[f]++) return fail(MLBP_EINVAL, "plan: pair factor %d is used twice", f);
-    } else {
-      return fail(MLBP_EINVAL, "plan: const %d: unknown kind %d", i, kind);
-    }
-  }
-  for (int p = 0; p < P; ++p)
-    if (!pair_used[p]) return fail(MLBP_EINVAL, "plan: pair factor %d is left out", p);
-  for (int u = 0; u < U; ++u)
-    if (!unary_used[u]) return fail(MLBP_EINVAL, "plan: unary factor %d is left out", u);
-  return MLBP_OK;
-}
+int mlbp_cutset_check_plan(const int32_t* plan, int32_t n_words, int32_t X) { return check_packed_plan(plan, n_words, X); }
 
 int mlbp_cutset_f64(const mlbp_cutset_args* a, void* stream) {
   g_last_kernel = MLBP_CUTSET_KERNEL_NONE;

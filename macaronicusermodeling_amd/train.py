@@ -306,6 +306,27 @@ class UserGraphTrainer:
         agrees = (bp.argmax(dim=2) == exact.argmax(dim=2)).all(dim=1)
         return (log_z.cpu().numpy(), (bethe - log_z).cpu().numpy(), gap.cpu().numpy(), agrees.cpu().numpy(), joint.cpu().numpy())
 
+    def exact_decode(self):
+        """The TRUE jointly most probable set of guesses of every instance under the current thetas
+        (FactorGraphBatch.exact_map), and how decode() fared against it: host (assignment int64 [B][n_vars] word indices in
+        var_ids order, score float64 [B] -- its log-potential --, margin float64 [B] -- score minus the best score of any
+        assignment that differs in at least one word: the minimum over the words of score - the second-largest max-marginal
+        --, bp_agrees bool [B] -- map_sweep over the predict() schedule returned the same assignment --, shortfall float64
+        [B] >= 0 -- score minus map_sweep's score, 0 where they agree --, joint_logp float64 [B] -- the true log-probability
+        of the assignment, by exact_inference).  Raises exactmap.ExactMapError(MLBP_EUNSUPPORTED) for a shape above the
+        configuration limit."""
+        fb = self.batch
+        self.build_potentials()
+        x, score, mm = fb.exact_map(max_marginals=True)
+        second = mm.topk(2, dim=2).values[:, :, 1]
+        margin = (score[:, None] - second).min(dim=1).values
+        bp_x, bp_score = fb.map_sweep(self.roots[:self.n_sweeps_run], init=True, keep_messages=False)
+        agrees = (bp_x == x).all(dim=1)
+        shortfall = torch.where(agrees, torch.zeros_like(score), (score - bp_score).clamp(min=0.0))
+        joint = fb.exact_inference(labels=x)[2]
+        return (x.cpu().numpy().astype(np.int64), score.cpu().numpy(), margin.cpu().numpy(), agrees.cpu().numpy(),
+                shortfall.cpu().numpy(), joint.cpu().numpy())
+
 
 def apply_update(theta_en_en, theta_en_de, stats, F_ee, F_ed, learning_rate, reg_param):
     """theta += sum_i lr (g_i - reg theta) = lr (sum_i g_i - n reg theta): the sum of the per-instance
@@ -926,6 +947,49 @@ class TiDirTrainer:
         mdist.all_reduce_max_(worst)
         tot = tot.cpu().numpy()
         return per_instance, (int(tot[0]), int(tot[1]), float(tot[2]), float(worst[0]), int(tot[3])), skipped
+
+    # ---- which guesses are truly the best: exact joint decoding (include/mlbp_exactmap.h) ------------
+    def exact_decode(self):
+        """-> (guesses, counts, report, skipped).  guesses[i], for instance i of this rank's shard in file order: (predicted
+        positions, [en words], score, margin, joint_logp) as UserGraphTrainer.exact_decode gives them -- the set of guesses
+        that truly maximises the model, its log-potential, its lead over the best set that differs in a word and its true
+        log-probability; an instance without a predicted word builds no graph and gives ((), [], 0.0, 0.0, 0.0), one of a shape
+        above the configuration limit (positions, None, None, None, None).  counts: as decode() counts, over the exact
+        guesses.  report = (sentences compared, sentences where map_sweep decoded the same set, sum of shortfall, largest
+        shortfall) over ALL ranks' instances, reduced once.  skipped: [(predicted positions, instances, reason)] of this
+        rank's shapes above the limit.  decode() itself is what it was."""
+        from . import exactmap as K
+        n = self._shard[1] - self._shard[0]
+        guesses = [((), [], 0.0, 0.0, 0.0)] * n
+        counts = np.zeros(4, dtype=np.int64)
+        seen = n_agree = 0
+        sum_short = 0.0
+        worst = torch.zeros(1, dtype=torch.float64, device=self.device)
+        skipped = []
+        for key, tr in self.trainers.items():
+            rows = self.buckets[key]['rows']
+            try:
+                x, score, margin, agrees, shortfall, joint = tr.exact_decode()
+            except K.ExactMapError as e:
+                if e.code != _ffi.MLBP_EUNSUPPORTED:
+                    raise
+                skipped.append((tuple(key[1]), len(rows), str(e)))
+                for row in rows:
+                    guesses[row['index']] = (tuple(key[1]), None, None, None, None)
+                continue
+            hit = x == self.buckets[key]['var_labels']
+            counts += np.array([int(hit.all(axis=1).sum()), hit.shape[0], int(hit.sum()), hit.size], dtype=np.int64)
+            seen += len(rows)
+            n_agree += int(agrees.sum())
+            sum_short += float(shortfall.sum())
+            worst[0] = max(float(worst[0]), float(shortfall.max()))
+            for b, row in enumerate(rows):
+                guesses[row['index']] = (tuple(key[1]), [self.en[w] for w in x[b]], float(score[b]), float(margin[b]), float(joint[b]))
+        tot = torch.tensor([float(v) for v in counts] + [float(seen), float(n_agree), sum_short], dtype=torch.float64, device=self.device)
+        mdist.all_reduce_sum_(tot)
+        mdist.all_reduce_max_(worst)
+        tot = tot.cpu().numpy()
+        return (guesses, tuple(int(v) for v in tot[:4]), (int(tot[4]), int(tot[5]), float(tot[6]), float(worst[0])), skipped)
 
     # ---- joint log-likelihood (log Z; the reference has only the sum of per-word log-marginals) ------
     def joint_log_likelihood(self):
