@@ -581,6 +581,111 @@ class FactorGraphBatch:
         K.check(K.lib.mlbp_exactmap_f64(C.byref(a), _stream_ptr(self.device)))
         return (assignment, score) if max_marginals is None else (assignment, score, max_marginals)
 
+    # ---- the exact pair marginals and the true gradient (include/mlbp_exactgrad.h) ---------------------
+    def _exactgrad(self, cutset, marginals=None, pair_marginals=None, expect=None, grad=None, labels=None):
+        """One mlbp_exactgrad_f64 call: log_z [B], and whichever of the optional outputs is given (expect, grad: (ee, ed))."""
+        from . import exactgrad as K
+        if self.pair_tables is not None and self.pair_tables.dtype != torch.float64:
+            raise NotImplementedError('the exact pair marginals and gradient need float64 pairwise tables')
+        topo = self.topo
+        if cutset is not None:
+            unknown = [v for v in cutset if v not in topo.var_index]
+            if unknown:
+                raise ValueError('cutset names unknown variable ids %r' % (unknown,))
+            cutset = [topo.var_index[v] for v in cutset]
+        pl = K.plan(topo, cutset, self.X, self.device)
+        a = K.ExactGradArgs()
+        a.B, a.X, a.n_vars, a.P, a.U = self.B, self.X, topo.n_vars, topo.P, topo.U
+        a.n_cut, a.n_free, a.n_items, a.n_consts, a.n_forest = pl.n_cut, pl.n_free, pl.n_items, pl.n_consts, pl.n_forest
+        a.plan, a.plan_words = pl.dev.data_ptr(), len(pl.words)
+        if topo.P:
+            if self.pair_tables is None:
+                raise RuntimeError('set_pair_tables() first')
+            a.n_pair_tables = self.pair_tables.shape[0]
+            a.pair_tables, a.pair_tab = self.pair_tables.data_ptr(), self.pair_tab.data_ptr()
+        if topo.U:
+            if self.unary_tables is None:
+                raise RuntimeError('set_unary_tables() first')
+            a.n_unary_tables = self.unary_tables.shape[0]
+            a.unary_tables, a.unary_tab = self.unary_tables.data_ptr(), self.unary_tab.data_ptr()
+
+        def checked(t, shape, what):
+            if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != torch.float64 or t.device != self.device or not t.is_contiguous():
+                raise ValueError('%s must be a contiguous float64 device tensor %s' % (what, list(shape)))
+            return t.data_ptr()
+        if marginals is not None:
+            a.marginals = checked(marginals, (self.B, topo.n_vars, self.X), 'marginals')
+        if pair_marginals is not None:
+            a.pair_marginals = checked(pair_marginals, (self.B, topo.P, self.X, self.X), 'pair_marginals')
+        keep = []
+        if expect is not None or grad is not None:
+            if getattr(self, 'phi_en_en', None) is None:
+                raise RuntimeError('set_features() first')
+            if topo.U and getattr(self, '_unary_obs', None) is None:
+                raise RuntimeError('set_observations() first')
+            a.F_ee, a.F_ed, a.Vde = int(self.phi_en_en.shape[2]), int(self.phi_en_de.shape[2]), int(self.phi_en_de.shape[1])
+            a.phi_en_en, a.phi_en_en_w1, a.phi_en_de = self.phi_en_en.data_ptr(), self.phi_en_en_w1.data_ptr(), self.phi_en_de.data_ptr()
+            a.pair_phi, a.unary_kind = self._pair_phi.data_ptr(), self._unary_kind.data_ptr()
+            if topo.U:
+                a.unary_obs = self._unary_obs.data_ptr()
+            if expect is not None:
+                a.expect_ee, a.expect_ed = checked(expect[0], (self.B, a.F_ee), 'out_ee'), checked(expect[1], (self.B, a.F_ed), 'out_ed')
+            if grad is not None:
+                a.grad_ee, a.grad_ed = checked(grad[0], (self.B, a.F_ee), 'out_ee'), checked(grad[1], (self.B, a.F_ed), 'out_ed')
+                if labels is None:
+                    if getattr(self, '_labels', None) is None:
+                        raise RuntimeError('exact_gradient needs labels: pass them or set_observations() first')
+                    lab = self._labels
+                elif torch.is_tensor(labels) and labels.dtype == torch.int32 and labels.device == self.device and labels.is_contiguous():
+                    lab = labels
+                else:
+                    host = labels.cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
+                    lab = torch.from_numpy(np.ascontiguousarray(host.astype(np.int64).astype(np.int32))).to(self.device)
+                if tuple(lab.shape) != (self.B, topo.n_vars):
+                    raise ValueError('labels must be [B][n_vars]')
+                keep.append(lab)
+                a.labels = lab.data_ptr()
+        log_z = torch.empty(self.B, dtype=torch.float64, device=self.device)
+        a.log_z = log_z.data_ptr()
+        need = K.workspace_bytes(self.B, self.X, topo.n_vars, topo.P, topo.U, pl.n_forest, pl.n_cut)
+        work = torch.empty(need // 8, dtype=torch.float64, device=self.device)
+        a.workspace, a.workspace_bytes = work.data_ptr(), need
+        K.check(K.lib.mlbp_exactgrad_f64(C.byref(a), _stream_ptr(self.device)))
+        return log_z
+
+    def exact_pair_marginals(self, out=None, cutset=None):
+        """The TRUE marginal of every pairwise factor by cutset conditioning -- what pair_beliefs() approximates on a loopy
+        graph: float64 device tensor [B][P][X][X], out[b][p][i][j] = p(x_a = i, x_b = j) in the axes of factor p's table.
+        out: optional contiguous float64 [B][P][X][X] device tensor to write into; cutset: as in exact_inference.  self.msgs is
+        neither read nor written."""
+        if out is None:
+            out = torch.empty(self.B, self.topo.P, self.X, self.X, dtype=torch.float64, device=self.device)
+        self._exactgrad(cutset, pair_marginals=out)
+        return out
+
+    def exact_gradient(self, labels=None, out_ee=None, out_ed=None, pair_marginals=None, marginals=None, cutset=None, expect_only=False):
+        """The TRUE per-graph likelihood gradient -- what gradient() approximates from BP beliefs: (grad_ee [B][F_ee], grad_ed
+        [B][F_ed], log_z [B]) device tensors, grad = observed features at `labels` - expected features under the model's own
+        pair marginals and marginals (include/mlbp_exactgrad.h; the unary term uses the variable's true marginal, not the
+        reference's normalised table).  With tables exp(phi . theta) this is the derivative of exact_inference's joint_logp in
+        theta.  Features, selectors and observed columns are those of set_features() / set_observations(); labels=None uses
+        the labels of set_observations().  expect_only=True returns the expected features instead of the gradient and needs no
+        labels.  out_ee / out_ed, pair_marginals ([B][P][X][X]) and marginals ([B][n_vars][X]): optional contiguous float64
+        device tensors to write into (the last two are written only when given).  cutset: as in exact_inference.  self.msgs is
+        neither read nor written."""
+        self._need_f64_tables('exact_gradient')
+        if getattr(self, 'phi_en_en', None) is None:
+            raise RuntimeError('set_features() first')
+        F_ee, F_ed = int(self.phi_en_en.shape[2]), int(self.phi_en_de.shape[2])
+        if out_ee is None:
+            out_ee = torch.empty(self.B, F_ee, dtype=torch.float64, device=self.device)
+        if out_ed is None:
+            out_ed = torch.empty(self.B, F_ed, dtype=torch.float64, device=self.device)
+        out = (out_ee, out_ed)
+        log_z = self._exactgrad(cutset, marginals=marginals, pair_marginals=pair_marginals, expect=out if expect_only else None,
+                                grad=None if expect_only else out, labels=labels)
+        return out_ee, out_ed, log_z
+
     def treelike_inference(self, iterations, roots):
         """`iterations` sweeps if the graph is loopy, else one (LBP.py:219); `roots` replaces the
         per-sweep random.sample draw (LBP.py:223).  Returns the number of sweeps run."""

@@ -1,0 +1,92 @@
+"""ctypes binding of libmlbp_exactgrad.so (include/mlbp_exactgrad.h): the model's true pairwise marginals, expected features
+and likelihood gradient by cutset conditioning.
+
+The eighth library of the engine, with its own signature table.  There is no CPU fallback: the compute call on a machine
+without an MI355X returns MLBP_ENODEVICE, raised as ExactGradError.
+
+The call takes the packed plan of include/mlbp_cutset.h: `plan(topo, cutset, X, device)` derives it with cutset.choose /
+cutset.plan_words, has THIS library validate it on the host, uploads it once and caches the device copy.
+"""
+import ctypes as C
+
+from . import _ffi, _sidelib
+from . import cutset as _cutset
+from ._sidelib import i32 as _i32, i32p as _i32p
+
+LIB_PATH = _sidelib.lib_path('mlbp_exactgrad')
+
+KERNEL_NONE, KERNEL_X64, KERNEL_GENERIC = 0, 1, 2
+X64_MAX_FOREST = 2              # include/mlbp_exactgrad.h MLBP_EXACTGRAD_X64_MAX_FOREST
+MIN_WORKGROUPS = 256
+MAX_FEATURES = 64
+
+
+class ExactGradError(_sidelib.SideError):
+    LIB = 'libmlbp_exactgrad'
+
+
+class ExactGradArgs(C.Structure):
+    _fields_ = [('B', C.c_int32), ('X', C.c_int32), ('n_vars', C.c_int32), ('P', C.c_int32), ('U', C.c_int32),
+                ('n_cut', C.c_int32), ('n_free', C.c_int32), ('n_items', C.c_int32), ('n_consts', C.c_int32), ('n_forest', C.c_int32),
+                ('n_pair_tables', C.c_int32), ('n_unary_tables', C.c_int32),
+                ('plan_words', C.c_int32),
+                ('F_ee', C.c_int32), ('F_ed', C.c_int32), ('Vde', C.c_int32),
+                ('plan', C.c_void_p),
+                ('pair_tables', C.c_void_p), ('pair_tab', C.c_void_p), ('unary_tables', C.c_void_p), ('unary_tab', C.c_void_p),
+                ('phi_en_en', C.c_void_p), ('phi_en_en_w1', C.c_void_p), ('phi_en_de', C.c_void_p),
+                ('pair_phi', C.c_void_p), ('unary_kind', C.c_void_p), ('unary_obs', C.c_void_p),
+                ('labels', C.c_void_p),
+                ('workspace', C.c_void_p), ('workspace_bytes', C.c_int64),
+                ('log_z', C.c_void_p), ('marginals', C.c_void_p), ('pair_marginals', C.c_void_p),
+                ('expect_ee', C.c_void_p), ('expect_ed', C.c_void_p), ('grad_ee', C.c_void_p), ('grad_ed', C.c_void_p)]
+
+
+# name -> (restype, argtypes); mirrors include/mlbp_exactgrad.h one to one (tests/test_exactgrad_cpu.py checks that).
+SIGNATURES = {
+    'mlbp_exactgrad_f64': (C.c_int, [C.POINTER(ExactGradArgs), C.c_void_p]),
+    'mlbp_exactgrad_check_plan': (C.c_int, [_i32p, _i32, _i32]),
+    'mlbp_exactgrad_pick_kernel': (C.c_int, [_i32, _i32, _i32, _i32, _i32]),
+    'mlbp_exactgrad_chunks': (C.c_int, [_i32, _i32, _i32]),
+    'mlbp_exactgrad_workspace_bytes': (C.c_int64, [_i32, _i32, _i32, _i32, _i32, _i32, _i32]),
+    'mlbp_exactgrad_last_kernel': (C.c_int, []),
+    'mlbp_exactgrad_arch': (C.c_char_p, []),
+    'mlbp_exactgrad_last_error': (C.c_char_p, []),
+}
+
+lib = _sidelib.load(LIB_PATH, SIGNATURES)
+last_error, check, last_kernel, pick_kernel = _sidelib.status_helpers(lib, ExactGradError)
+
+
+def chunks(B, n_configs, kernel):
+    """C of the launch grid (B, C) for kernel = KERNEL_X64 or KERNEL_GENERIC."""
+    return check(lib.mlbp_exactgrad_chunks(int(B), int(n_configs), int(kernel)))
+
+
+def workspace_bytes(B, X, n_vars, P, U, n_forest, n_cut):
+    return check(lib.mlbp_exactgrad_workspace_bytes(int(B), int(X), int(n_vars), int(P), int(U), int(n_forest), int(n_cut)))
+
+
+class Plan:
+    """A plan validated by this library and its device copy (the fields of cutset.Plan)."""
+
+    def __init__(self, topo, cutset, X, device):
+        import torch
+        seen = set()
+        for v in cutset:
+            if not 0 <= int(v) < topo.n_vars or int(v) in seen:
+                raise ValueError('cutset names variable index %r twice or out of range' % (v,))
+            seen.add(int(v))
+        self.words = _cutset.plan_words(topo, cutset)
+        check(lib.mlbp_exactgrad_check_plan(_ffi.i32ptr(self.words), len(self.words), int(X)))
+        (self.n_vars, self.P, self.U, self.n_cut, self.n_free, self.n_items, self.n_consts, self.n_forest) = (int(w) for w in self.words[:8])
+        self.n_configs = int(X) ** self.n_cut
+        self.dev = torch.from_numpy(self.words).to(device) if device is not None else None
+
+
+_plans = _sidelib.Cache()
+
+
+def plan(topo, cutset, X, device):
+    """The cached Plan of (topology, cutset, X, device); cutset None: cutset.choose(topo)."""
+    cutset = tuple(_cutset.choose(topo) if cutset is None else (int(v) for v in cutset))
+    return _plans.get(topo, (cutset, int(X), str(device)), lambda: Plan(topo, cutset, X, device))

@@ -306,6 +306,52 @@ class UserGraphTrainer:
         agrees = (bp.argmax(dim=2) == exact.argmax(dim=2)).all(dim=1)
         return (log_z.cpu().numpy(), (bethe - log_z).cpu().numpy(), gap.cpu().numpy(), agrees.cpu().numpy(), joint.cpu().numpy())
 
+    def _plane_share(self, belief):
+        """The per-instance feature planes' share of the en_de gradient, host [B][F_ed]: for every plane cell (i, observed
+        column, k) of value v on a patched factor, v * ([label == i] - belief[row][i]).  belief: host [n_priv][X], the belief
+        of every private row's factor over its variable (what mlbp_patch_gradient_f64 adds from the normalised rows)."""
+        out = np.zeros((self.batch.B, self.F_ed))
+        off, ix, ik, iv, rgraph, rlabel, _ = self._patch_plan
+        for r in range(self.n_priv):
+            for q in range(off[r], off[r + 1]):
+                out[rgraph[r], ik[q]] += iv[q] * ((1.0 if rlabel[r] == ix[q] else 0.0) - belief[r, ix[q]])
+        return out
+
+    def _bp_gradient(self):
+        """What gradient() gives after the predict() schedule, planes included: host (bp_ee [B][F_ee], bp_ed [B][F_ed],
+        log-posterior [B]).  The potentials are already built."""
+        fb, topo = self.batch, self.topo
+        fb.sweep(self.roots[:self.n_sweeps_run], init=True, marginals=self._marg)
+        bp_ee, bp_ed = fb.gradient()
+        lp = torch.empty(fb.B, dtype=torch.float64, device=self.device)
+        _ffi.check(_ffi.lib.mlbp_log_posterior_f64(self._marg.data_ptr(), fb._labels.data_ptr(), fb.B, topo.n_vars, fb.X, lp.data_ptr(),
+                                                   _stream_ptr(self.device)))
+        bp_ee, bp_ed = bp_ee.cpu().numpy(), bp_ed.cpu().numpy()
+        if self.n_priv:                                         # the reference's unary belief: the normalised table alone
+            rows = self.unary_tables[self.priv_row0:self.priv_row0 + self.n_priv].cpu().numpy()
+            bp_ed = bp_ed + self._plane_share(rows / rows.sum(axis=1, keepdims=True))
+        return bp_ee, bp_ed, lp.cpu().numpy()
+
+    def exact_gradient(self):
+        """The gradient of the TRUE likelihood of each instance under the current thetas, beside the one the trainer follows:
+        host (g_ee float64 [B][F_ee], g_ed float64 [B][F_ed] -- observed minus expected features under the model's own pair
+        marginals and marginals, FactorGraphBatch.exact_gradient, the feature planes' share included: the derivative of
+        joint_logp in the thetas --, joint_logp float64 [B] -- the true log-probability of the stored labels --, bp_ee, bp_ed
+        -- what gradient() gives after the predict() schedule).  Raises exactgrad.ExactGradError(MLBP_EUNSUPPORTED) for a
+        shape above the configuration limit."""
+        fb, topo = self.batch, self.topo
+        self.build_potentials()
+        exact = torch.empty(fb.B, topo.n_vars, fb.X, dtype=torch.float64, device=self.device)
+        g_ee, g_ed, _ = fb.exact_gradient(marginals=exact)
+        joint = fb.exact_inference(labels=fb._labels)[2]
+        g_ee, g_ed = g_ee.cpu().numpy(), g_ed.cpu().numpy()
+        if self.n_priv:                                         # the true belief of a unary factor: its variable's marginal
+            exact = exact.cpu().numpy()
+            var_of = [int(topo.fac_var[2 * topo.unary_factors[u]]) for _, u in self._priv_rows]
+            g_ed = g_ed + self._plane_share(np.stack([exact[b_i, v] for (b_i, _), v in zip(self._priv_rows, var_of)]))
+        bp_ee, bp_ed, _ = self._bp_gradient()
+        return g_ee, g_ed, joint.cpu().numpy(), bp_ee, bp_ed
+
     def exact_decode(self):
         """The TRUE jointly most probable set of guesses of every instance under the current thetas
         (FactorGraphBatch.exact_map), and how decode() fared against it: host (assignment int64 [B][n_vars] word indices in
@@ -947,6 +993,75 @@ class TiDirTrainer:
         mdist.all_reduce_max_(worst)
         tot = tot.cpu().numpy()
         return per_instance, (int(tot[0]), int(tot[1]), float(tot[2]), float(worst[0]), int(tot[3])), skipped
+
+    # ---- how wrong is the gradient the trainer follows, and a step on the true likelihood (include/mlbp_exactgrad.h) -----
+    def _exact_statistics(self, on_limit='skip'):
+        """This rank's sums over its shard, host: (exact [F_ee + F_ed] -- the true gradient --, bp [F_ee + F_ed] -- the BP
+        gradient of the same instances --, sum of joint_logp, instances compared, fallback statistics [n_stat] of the shapes
+        above the configuration limit when on_limit == 'bp', skipped [(predicted positions, instances, reason)]); on_limit ==
+        'raise' lets the library's refusal of such a shape through."""
+        from . import exactgrad as K
+        F = self.n_stat - 2
+        exact, bp, fall = np.zeros(F), np.zeros(F), np.zeros(self.n_stat)
+        loglik, seen, skipped = 0.0, 0, []
+        for key, tr in self.trainers.items():
+            rows = self.buckets[key]['rows']
+            try:
+                g_ee, g_ed, joint, bp_ee, bp_ed = tr.exact_gradient()
+            except K.ExactGradError as e:
+                if e.code != _ffi.MLBP_EUNSUPPORTED or on_limit == 'raise':
+                    raise
+                skipped.append((tuple(key[1]), len(rows), str(e)))
+                if on_limit == 'bp':
+                    tr.build_potentials()
+                    bp_ee, bp_ed, lp = tr._bp_gradient()
+                    fall += np.concatenate([bp_ee.sum(axis=0), bp_ed.sum(axis=0), [lp.sum(), float(len(rows))]])
+                continue
+            seen += len(rows)
+            loglik += float(joint.sum())
+            exact += np.concatenate([g_ee.sum(axis=0), g_ed.sum(axis=0)])
+            bp += np.concatenate([bp_ee.sum(axis=0), bp_ed.sum(axis=0)])
+        return exact, bp, loglik, seen, fall, skipped
+
+    def gradient_report(self):
+        """-> (totals, skipped): how far the gradient step() and epoch() follow is from the gradient of the true likelihood,
+        under the current thetas.  totals = (exact [F_ee + F_ed] -- the true gradient summed over the instances compared,
+        UserGraphTrainer.exact_gradient --, bp [F_ee + F_ed] -- the BP gradient summed over the same instances --, their
+        cosine, |bp - exact| / |exact|, the true total log-likelihood of the stored labels, instances compared, instances
+        skipped) over ALL ranks' instances, reduced once.  skipped: [(predicted positions, instances, reason)] of this rank's
+        shapes above the configuration limit; an instance without a predicted word builds no graph and is not counted."""
+        exact, bp, loglik, seen, _, skipped = self._exact_statistics()
+        F = self.n_stat - 2
+        tot = torch.tensor(list(exact) + list(bp) + [loglik, float(seen), float(sum(s[1] for s in skipped))], dtype=torch.float64,
+                           device=self.device)
+        mdist.all_reduce_sum_(tot)
+        tot = tot.cpu().numpy()
+        exact, bp = tot[:F], tot[F:2 * F]
+        ne, nb = float(np.linalg.norm(exact)), float(np.linalg.norm(bp))
+        cosine = float(exact.dot(bp)) / (ne * nb) if ne > 0 and nb > 0 else float('nan')
+        rel = float(np.linalg.norm(bp - exact)) / ne if ne > 0 else float('nan')
+        return (exact, bp, cosine, rel, float(tot[2 * F]), int(tot[2 * F + 1]), int(tot[2 * F + 2])), skipped
+
+    def exact_step(self, learning_rate, reg_param, fallback=None):
+        """One eager, synchronous step on the TRUE likelihood over ALL ranks' shards: the statistics vector step() hands to
+        update_thetas -- [sum g_ee | sum g_ed | sum log-likelihood | count] -- with the exact gradient sums and the sum of
+        joint_logp in place of the BP ones, one all-reduce, one update of the global thetas.  A shape above the configuration
+        limit raises exactgrad.ExactGradError, or with fallback='bp' contributes its BP statistics (gradient and
+        log-posterior).  Returns (mean log-likelihood of the instances at the thetas they were evaluated under, instances that
+        fell back to BP, over all ranks).  Per-domain thetas are not supported.  Not captured into the step graph; step() and
+        epoch() are what they were."""
+        if self.domains:
+            raise NotImplementedError('exact_step does not update per-domain thetas')
+        if fallback not in (None, 'bp'):
+            raise ValueError("fallback is None or 'bp'")
+        exact, _, loglik, seen, fall, _ = self._exact_statistics('bp' if fallback == 'bp' else 'raise')
+        n = self.n_stat
+        stats = torch.tensor(list(exact) + [loglik, float(seen)] + list(fall), dtype=torch.float64, device=self.device)
+        mdist.all_reduce_sum_(stats)
+        n_fallback = int(stats[2 * n - 1].item())
+        stats = stats[:n] + stats[n:]
+        update_thetas(self, stats, learning_rate, reg_param, self.reg_param_ua_scale)
+        return float(stats[n - 2].item() / max(stats[n - 1].item(), 1.0)), n_fallback
 
     # ---- which guesses are truly the best: exact joint decoding (include/mlbp_exactmap.h) ------------
     def exact_decode(self):
