@@ -195,6 +195,106 @@ __device__ __forceinline__ void front(const double2 (&tab)[NT][4][2], const doub
   }
 }
 
+// ---- the paired form of a bundle's front half (PAIR_GATHER instances): an update is a GATHER -- the product of its source
+//      messages in the distribution the contraction needs, which depends on the direction only -- and a CONTRACTION of that
+//      product with the selected table; both members gather before either contracts ----
+struct Src { double2 a, b; };       // the lane's four entries of the product: T.m its two column pairs, m^T.T its four rows
+
+// The gathers of BOTH members of a bundle as one piece of straight-line code: the members are independent, so the second
+// one's LDS reads are in flight while the first one's products are formed, instead of behind its contraction.  uB may be the
+// empty member (UOP_NOP: sources at offset 0, nothing stored, the product unused).  Products and stores are those of contract<>:
+// ((s1 s2) s3) s4, no bit differs.
+__device__ __forceinline__ void gather_pair(char* wb, int uA, const int4& A0, const int4& A1, int uB, const int4& B0, const int4& B1,
+                                            const LaneGeo& G, Src& mA, Src& mB) {
+  const bool mtA = (uA & UOP_MT) != 0, mtB = (uB & UOP_MT) != 0;
+  const int a0 = mtA ? G.mt : G.tm0, a1 = mtA ? G.mt + 16 : G.tm1;
+  const int b0 = mtB ? G.mt : G.tm0, b1 = mtB ? G.mt + 16 : G.tm1;
+  mA.a = lds2(wb + A0.y + a0); mA.b = lds2(wb + A0.y + a1);
+  mB.a = lds2(wb + B0.y + b0); mB.b = lds2(wb + B0.y + b1);
+  {
+    const double2 pa = lds2(wb + A0.z + a0), pb = lds2(wb + A0.z + a1);
+    const double2 qa = lds2(wb + B0.z + b0), qb = lds2(wb + B0.z + b1);
+    mul2(mA.a, pa); mul2(mA.b, pb);
+    mul2(mB.a, qa); mul2(mB.b, qb);
+  }
+  // (sources 3-4: a member at a time, each under its own branch -- fetched together for both they would keep 48 registers
+  // alive and spill the three-table instance)
+  if (((uA >> UOP_NSRC_SHIFT) & 15) > 2) {
+    const double2 pa = lds2(wb + A0.w + a0), pb = lds2(wb + A0.w + a1);
+    const double2 ra = lds2(wb + A1.x + a0), rb = lds2(wb + A1.x + a1);
+    mul2(mA.a, pa); mul2(mA.b, pb);
+    mul2(mA.a, ra); mul2(mA.b, rb);
+  }
+  if (((uB >> UOP_NSRC_SHIFT) & 15) > 2) {
+    const double2 qa = lds2(wb + B0.w + b0), qb = lds2(wb + B0.w + b1);
+    const double2 sa = lds2(wb + B1.x + b0), sb = lds2(wb + B1.x + b1);
+    mul2(mB.a, qa); mul2(mB.b, qb);
+    mul2(mB.a, sa); mul2(mB.b, sb);
+  }
+  if ((uA & UOP_STORE_VF) && (mtA ? G.st_mt : G.st_tm)) {
+    *reinterpret_cast<double2*>(wb + A1.y + a0) = mA.a;
+    *reinterpret_cast<double2*>(wb + A1.y + a1) = mA.b;
+  }
+  if ((uB & UOP_STORE_VF) && (mtB ? G.st_mt : G.st_tm)) {
+    *reinterpret_cast<double2*>(wb + B1.y + b0) = mB.a;
+    *reinterpret_cast<double2*>(wb + B1.y + b1) = mB.b;
+  }
+}
+
+// (every sum is spelled out, with contraction off: the SECOND product rounded on its own, then the first, third and fourth fused
+// onto it -- the form the compiler gave `a * b + c * d + ...` while each direction formed its own products.  Left to it, which
+// product of a sum is rounded alone is its choice, and it changes when the two directions share a product, as they do behind
+// one gather: a result would depend on the instance that computed it)
+template <bool MT, typename TB>
+__device__ __forceinline__ void contract_gathered(const TB T, const Src m, const LaneGeo& G, char* redA) {
+#pragma clang fp contract(off)
+  if (MT) {
+    const double2 ma = m.a, mb = m.b;
+    double a00, a01, a10, a11;
+    { const double2 t0 = T(1, 0), t1 = T(1, 1); a00 = ma.y * t0.x; a01 = ma.y * t0.y; a10 = ma.y * t1.x; a11 = ma.y * t1.y; }
+#define MLBP_ROW(mv, r) { const double2 t0 = T(r, 0), t1 = T(r, 1); a00 = __builtin_fma(mv, t0.x, a00); a01 = __builtin_fma(mv, t0.y, a01); \
+                          a10 = __builtin_fma(mv, t1.x, a10); a11 = __builtin_fma(mv, t1.y, a11); }
+    MLBP_ROW(ma.x, 0)
+    MLBP_ROW(mb.x, 2)
+    MLBP_ROW(mb.y, 3)
+#undef MLBP_ROW
+    // rows: lane bit 3 (partner l ^ 8 keeps the other column pair in its register 0), lane bit 5, then the waves
+    a00 += dpp_mov<0x128>(a10);
+    a01 += dpp_mov<0x128>(a11);
+    *reinterpret_cast<double*>(redA + G.red_mt) = swapadd32(a00, a01);
+  } else {
+    const double2 m0 = m.a, m1 = m.b;
+    double v[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const double2 t0 = T(r, 0), t1 = T(r, 1);
+      v[r] = t0.y * m0.y;
+      v[r] = __builtin_fma(t0.x, m0.x, v[r]);
+      v[r] = __builtin_fma(t1.x, m1.x, v[r]);
+      v[r] = __builtin_fma(t1.y, m1.y, v[r]);
+    }
+    // columns: lane bit 4 (rows of 16 lanes exchange registers), lane bit 2 (select), lane bits 1 and 0 (plain)
+    const double u0 = swapadd16(v[0], v[2]), u1 = swapadd16(v[1], v[3]);
+    const double keep = G.up ? u1 : u0, send = G.up ? u0 : u1;
+    double w = keep + dpp_mov<0x141>(send);
+    w += dpp_mov<0xB1>(w);
+    w += dpp_mov<0x4E>(w);
+    *reinterpret_cast<double*>(redA + G.red_tm) = w;        // the four lanes of a quad hold (and store) the same row
+  }
+}
+
+template <int NT>
+__device__ __forceinline__ void front_gathered(const double2 (&tab)[NT][4][2], int u0, const Src m, const LaneGeo& G, char* redA) {
+  const int pslot = (u0 >> UOP_PSLOT_SHIFT) & 7;
+#pragma unroll
+  for (int p = 0; p < NT; ++p) {
+    if (p == pslot) {
+      if (u0 & UOP_MT) contract_gathered<true>(RegTable{tab[p]}, m, G, redA);
+      else contract_gathered<false>(RegTable{tab[p]}, m, G, redA);
+    }
+  }
+}
+
 // FactorGraph.get_unregularized_gradeint (LBP.py:301-320) for one graph, from what the workgroup still holds after its
 // sweeps: tables in registers (4 x 4 blocks), messages in LDS.  Pairwise factor (LBP.py:543-569, 592-619): beliefs =
 // normalize((c r^T) (.) T), gradient = phi[label cell] - sum_ij beliefs_ij phi_ij -- the scale of c and r cancels, so the
@@ -480,6 +580,11 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
   // (likewise the counted wait of phase A: its unconditional loads and the parked index word double <3, GRAD>'s spills, so the
   // GRAD instances keep conditional loads and the index check in a loop, and with them one wait for everything)
   constexpr bool EARLY = !GRAD;
+  // (PAIR_GATHER -- both members' gathers ahead of either contraction, gather_pair -- keeps two products alive across a
+  // contraction: taken by the three-table instances, where it costs neither scratch nor a wave per SIMD and is worth 2.6 % on the
+  // default workload (LAB_NOTES R18); the one- and two-table instances would lose a workgroup per CU, the wider ones have no registers
+  // left: profiles/r18a_lean_kernel_resources.txt)
+  constexpr bool PAIR_GATHER = !GRAD && NL == 0 && NT == 3;
   static_assert(!(GRAD && PADX), "the GRAD form of phase A loads whole rows: X = 64 only");
 
   LaneGeo G;
@@ -722,9 +827,14 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
   const int4* li = reinterpret_cast<const int4*>(limg);
   int4 A0 = li[0], A1 = li[1], B0 = li[2], B1 = li[3];
   for (int k = 0; k < f.n_bundles; ++k) {
-    const int4 nA0 = li[4 * k + 4], nA1 = li[4 * k + 5], nB0 = li[4 * k + 6], nB1 = li[4 * k + 7];     // the image is padded by one bundle
+    // the image is padded by one bundle.  (PAIR_GATHER asks for the next words behind its gathers: ahead of them, sixteen more
+    // registers are alive where the bundle's pressure peaks, and the third table spills)
+    int4 nA0, nA1, nB0, nB1;
+#define MLBP_FETCH_NEXT() (nA0 = li[4 * k + 4], nA1 = li[4 * k + 5], nB0 = li[4 * k + 6], nB1 = li[4 * k + 7])
+    if (!PAIR_GATHER) MLBP_FETCH_NEXT();
     const int fA = __builtin_amdgcn_readfirstlane(A0.x), fB = __builtin_amdgcn_readfirstlane(B0.x);
     if (fA & UOP_VAR) {
+      if (PAIR_GATHER) MLBP_FETCH_NEXT();
       // a lone variable update: the product, lane = state, the same in every wave; no contraction, no barrier
       // a product of more than four sources is a chain of links; the running product stays in a register between
       // them and only the last link stores (every wave stores the same value once: no read-modify-write of a slot
@@ -743,9 +853,17 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
       else work[(A1.y >> 3) + lane] = m;
     } else {
       char* redP = reinterpret_cast<char*>(red) + parity * 4096;
-      front<NT, NL>(tab, tl + t, wb, fA, A0, A1, G, redP);
       const bool two = !(fB & UOP_NOP);
-      if (two) front<NT, NL>(tab, tl + t, wb, fB, B0, B1, G, redP + 2048);
+      if (PAIR_GATHER) {
+        Src mA, mB;
+        gather_pair(wb, fA, A0, A1, fB, B0, B1, G, mA, mB);
+        MLBP_FETCH_NEXT();
+        front_gathered<NT>(tab, fA, mA, G, redP);
+        if (two) front_gathered<NT>(tab, fB, mB, G, redP + 2048);
+      } else {
+        front<NT, NL>(tab, tl + t, wb, fA, A0, A1, G, redP);
+        if (two) front<NT, NL>(tab, tl + t, wb, fB, B0, B1, G, redP + 2048);
+      }
       lds_barrier();
       const double* rd = reinterpret_cast<const double*>(redP);
       double rA = rd[lane];
@@ -759,6 +877,7 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
       parity ^= 1;
     }
     A0 = nA0; A1 = nA1; B0 = nB0; B1 = nB1;
+#undef MLBP_FETCH_NEXT
   }
   if (bad) {                                      // the same in every wave: the inputs were identical
     if (t == 0) f.bail[g] = 2;
