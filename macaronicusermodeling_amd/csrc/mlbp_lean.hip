@@ -87,6 +87,21 @@ struct LaneGeo {
 __device__ __forceinline__ double2 lds2(const char* p) { return *reinterpret_cast<const double2*>(p); }
 __device__ __forceinline__ void mul2(double2& a, const double2 b) { a.x *= b.x; a.y *= b.y; }
 
+// LDS by byte ADDRESS (the LDS_ADDR instances): an integer, formed from byte offsets by plain integer adds, cast once to an LDS
+// pointer.  As `char* + offset` every access pays an add of the array's base -- a literal zero the compiler does not fold.
+typedef double lds_v2d __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ int lds_addr(const void* p) { return (int)(size_t)(const __attribute__((address_space(3))) char*)p; }
+__device__ __forceinline__ double2 lds2_at(int a) {
+  const lds_v2d v = *(const __attribute__((address_space(3))) lds_v2d*)(size_t)(unsigned)a;
+  return make_double2(v.x, v.y);
+}
+__device__ __forceinline__ void lds2_put(int a, const double2 v) {
+  lds_v2d w; w.x = v.x; w.y = v.y;
+  *(__attribute__((address_space(3))) lds_v2d*)(size_t)(unsigned)a = w;
+}
+__device__ __forceinline__ double lds1_at(int a) { return *(const __attribute__((address_space(3))) double*)(size_t)(unsigned)a; }
+__device__ __forceinline__ void lds1_put(int a, double v) { *(__attribute__((address_space(3))) double*)(size_t)(unsigned)a = v; }
+
 // One table (T[r][k] = rows 4R + r, column pair k ^ b3) against one input vector; u = the micro-op's 8 words (scalars).
 // u0 = flags (wave-uniform scalar); s1..s4, vf = source / store byte offsets (same in every lane, kept in VGPRs).
 // A table held in registers, or -- the (NT+1)-th table of a 7-table graph -- in LDS as [r * 2 + k][thread] double2.
@@ -204,41 +219,54 @@ struct Src { double2 a, b; };       // the lane's four entries of the product: T
 // one's LDS reads are in flight while the first one's products are formed, instead of behind its contraction.  uB may be the
 // empty member (UOP_NOP: sources at offset 0, nothing stored, the product unused).  Products and stores are those of contract<>:
 // ((s1 s2) s3) s4, no bit differs.
+template <bool STORE_BRANCH, bool LDS_ADDR>
 __device__ __forceinline__ void gather_pair(char* wb, int uA, const int4& A0, const int4& A1, int uB, const int4& B0, const int4& B1,
                                             const LaneGeo& G, Src& mA, Src& mB) {
   const bool mtA = (uA & UOP_MT) != 0, mtB = (uB & UOP_MT) != 0;
   const int a0 = mtA ? G.mt : G.tm0, a1 = mtA ? G.mt + 16 : G.tm1;
   const int b0 = mtB ? G.mt : G.tm0, b1 = mtB ? G.mt + 16 : G.tm1;
-  mA.a = lds2(wb + A0.y + a0); mA.b = lds2(wb + A0.y + a1);
-  mB.a = lds2(wb + B0.y + b0); mB.b = lds2(wb + B0.y + b1);
+  auto rd = [&](int off) { return LDS_ADDR ? lds2_at(off) : lds2(wb + off); };
+  auto wr = [&](int off, const double2 v) { if (LDS_ADDR) lds2_put(off, v); else *reinterpret_cast<double2*>(wb + off) = v; };
+  mA.a = rd(A0.y + a0); mA.b = rd(A0.y + a1);
+  mB.a = rd(B0.y + b0); mB.b = rd(B0.y + b1);
   {
-    const double2 pa = lds2(wb + A0.z + a0), pb = lds2(wb + A0.z + a1);
-    const double2 qa = lds2(wb + B0.z + b0), qb = lds2(wb + B0.z + b1);
+    const double2 pa = rd(A0.z + a0), pb = rd(A0.z + a1);
+    const double2 qa = rd(B0.z + b0), qb = rd(B0.z + b1);
     mul2(mA.a, pa); mul2(mA.b, pb);
     mul2(mB.a, qa); mul2(mB.b, qb);
   }
   // (sources 3-4: a member at a time, each under its own branch -- fetched together for both they would keep 48 registers
   // alive and spill the three-table instance)
   if (((uA >> UOP_NSRC_SHIFT) & 15) > 2) {
-    const double2 pa = lds2(wb + A0.w + a0), pb = lds2(wb + A0.w + a1);
-    const double2 ra = lds2(wb + A1.x + a0), rb = lds2(wb + A1.x + a1);
+    const double2 pa = rd(A0.w + a0), pb = rd(A0.w + a1);
+    const double2 ra = rd(A1.x + a0), rb = rd(A1.x + a1);
     mul2(mA.a, pa); mul2(mA.b, pb);
     mul2(mA.a, ra); mul2(mA.b, rb);
   }
   if (((uB >> UOP_NSRC_SHIFT) & 15) > 2) {
-    const double2 qa = lds2(wb + B0.w + b0), qb = lds2(wb + B0.w + b1);
-    const double2 sa = lds2(wb + B1.x + b0), sb = lds2(wb + B1.x + b1);
+    const double2 qa = rd(B0.w + b0), qb = rd(B0.w + b1);
+    const double2 sa = rd(B1.x + b0), sb = rd(B1.x + b1);
     mul2(mB.a, qa); mul2(mB.b, qb);
     mul2(mB.a, sa); mul2(mB.b, sb);
   }
-  if ((uA & UOP_STORE_VF) && (mtA ? G.st_mt : G.st_tm)) {
-    *reinterpret_cast<double2*>(wb + A1.y + a0) = mA.a;
-    *reinterpret_cast<double2*>(wb + A1.y + a1) = mA.b;
+  if (STORE_BRANCH) {
+    // the wave-uniform flag first, as a scalar branch: two members in three store nothing, and pay no lane predicate for it
+    // (the empty asm keeps the compiler from folding the two conditions back into one lane mask; the lane predicate -- G.st_mt,
+    // G.st_tm -- straight from the thread index, so that nothing of it is prepared ahead of the branch)
+    const int t = threadIdx.x;
+    auto mine = [&](bool mt) { return (t & (mt ? 0x17 : 0xE8)) == 0; };        // (0xE8: lane bits 3 and 5 clear, in wave 0)
+    if (uA & UOP_STORE_VF) {
+      asm volatile("");
+      if (mine(mtA)) { wr(A1.y + a0, mA.a); wr(A1.y + a1, mA.b); }
+    }
+    if (uB & UOP_STORE_VF) {
+      asm volatile("");
+      if (mine(mtB)) { wr(B1.y + b0, mB.a); wr(B1.y + b1, mB.b); }
+    }
+    return;
   }
-  if ((uB & UOP_STORE_VF) && (mtB ? G.st_mt : G.st_tm)) {
-    *reinterpret_cast<double2*>(wb + B1.y + b0) = mB.a;
-    *reinterpret_cast<double2*>(wb + B1.y + b1) = mB.b;
-  }
+  if ((uA & UOP_STORE_VF) && (mtA ? G.st_mt : G.st_tm)) { wr(A1.y + a0, mA.a); wr(A1.y + a1, mA.b); }
+  if ((uB & UOP_STORE_VF) && (mtB ? G.st_mt : G.st_tm)) { wr(B1.y + b0, mB.a); wr(B1.y + b1, mB.b); }
 }
 
 // (every sum is spelled out, with contraction off: the SECOND product rounded on its own, then the first, third and fourth fused
@@ -519,6 +547,19 @@ __device__ __forceinline__ double rescale(double r, int& bad) {
   return __builtin_ldexp(r, 1023 - ((ref >> 20) & 0x7FF));
 }
 
+// The same with the "negative or non-finite" half of the verdict left to the caller: the lane's largest key so far goes into
+// `kmax`, to be looked at once behind the loop -- an OR over updates and lanes of `key >= KEY_BAD` IS `max(key) >= KEY_BAD`.  "No
+// normal entry" stays per update: its ballot picks the reference lane anyway, and its share of the verdict stays on the scalar
+// side -- `some` (start: all ones) is the minimum over the updates of the ballot's two halves OR-ed, zero once a ballot was empty.
+__device__ __forceinline__ double rescale_kmax(double r, unsigned& some, unsigned& kmax) {
+  const unsigned key = mag_key(r);
+  const unsigned long long normal = __ballot(key - KEY_MIN < KEY_BAD - KEY_MIN);
+  kmax = max(kmax, key);
+  some = min(some, (unsigned)normal | (unsigned)(normal >> 32));
+  const int ref = __builtin_amdgcn_readlane((int)key, normal ? __builtin_ctzll(normal) : 0);
+  return __builtin_ldexp(r, 1023 - ((ref >> 20) & 0x7FF));
+}
+
 // PADX: X = d.X < 64 states, vectors and tables zero-padded to 64 on the way in, the first X entries written back.
 // MULTI: the launch holds several GROUPS of graphs -- each group its own program (topology and root sequence), tables,
 // messages -- described by a device table; the workgroup looks its group up and from then on runs as if launched for
@@ -585,6 +626,12 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
   // default workload (LAB_NOTES R18); the one- and two-table instances would lose a workgroup per CU, the wider ones have no registers
   // left: profiles/r18a_lean_kernel_resources.txt)
   constexpr bool PAIR_GATHER = !GRAD && NL == 0 && NT == 3;
+  // (LAB_NOTES R19: instructions off a bundle's serial path, each taken where PAIR_GATHER is -- the other instances keep the
+  // parent's instructions.  STORE_BRANCH: the stored product under a scalar branch on its flag bit; ONE_VERDICT: rescale_kmax;
+  // LDS_ADDR: the main loop's LDS accesses by integer byte address, the array's base folded into the lane's offsets once)
+  constexpr bool STORE_BRANCH = PAIR_GATHER;
+  constexpr bool ONE_VERDICT = PAIR_GATHER;
+  constexpr bool LDS_ADDR = PAIR_GATHER;
   static_assert(!(GRAD && PADX), "the GRAD form of phase A loads whole rows: X = 64 only");
 
   LaneGeo G;
@@ -600,7 +647,9 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
     G.st_tm = wave == 0 && (lane & 0x28) == 0;
     G.st_mt = (lane & 0x17) == 0;
     G.wr_tm = (lane & 3) == 0;
+    if (LDS_ADDR) { const int base = lds_addr(work); G.tm0 += base; G.tm1 += base; G.mt += base; }     // gather_pair's only
   }
+  const int lane8 = LDS_ADDR ? lds_addr(work) + lane * 8 : 0;       // LDS_ADDR: the address of entry `lane` of message slot 0
 
   if (t == 0) f.bail[g] = 0;
   int g_kind = 0, g_obs = 0, g_lab = 0;           // GRAD: unary factor t's kind / observed column / label, parked until the
@@ -823,6 +872,7 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
   //      are read (broadcast) one bundle ahead ----
   char* wb = reinterpret_cast<char*>(work);
   int parity = 0, bad = 0;
+  unsigned kmax = 0, some = ~0u;               // ONE_VERDICT (rescale_kmax)
   double carry = 1.0;
   const int4* li = reinterpret_cast<const int4*>(limg);
   int4 A0 = li[0], A1 = li[1], B0 = li[2], B1 = li[3];
@@ -840,23 +890,25 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
       // them and only the last link stores (every wave stores the same value once: no read-modify-write of a slot
       // that another wave may still be writing)
       const int nsrc = (fA >> UOP_NSRC_SHIFT) & 15;
-      double m = work[(A0.y >> 3) + lane];
-      const double m2 = work[(A0.z >> 3) + lane];          // (padded with the all-ones slot, like a contraction's list)
+      double m = LDS_ADDR ? lds1_at(A0.y + lane8) : work[(A0.y >> 3) + lane];
+      const double m2 = LDS_ADDR ? lds1_at(A0.z + lane8) : work[(A0.z >> 3) + lane];          // (padded with the all-ones slot, like a contraction's list)
       if (fA & UOP_CARRY_IN) m *= carry;
       m *= m2;
       if (nsrc > 2) {
-        const double m3 = work[(A0.w >> 3) + lane], m4 = work[(A1.x >> 3) + lane];
+        const double m3 = LDS_ADDR ? lds1_at(A0.w + lane8) : work[(A0.w >> 3) + lane];
+        const double m4 = LDS_ADDR ? lds1_at(A1.x + lane8) : work[(A1.x >> 3) + lane];
         m *= m3;
         m *= m4;
       }
       if (fA & UOP_CARRY_OUT) carry = m;
+      else if (LDS_ADDR) lds1_put(A1.y + lane8, m);
       else work[(A1.y >> 3) + lane] = m;
     } else {
       char* redP = reinterpret_cast<char*>(red) + parity * 4096;
       const bool two = !(fB & UOP_NOP);
       if (PAIR_GATHER) {
         Src mA, mB;
-        gather_pair(wb, fA, A0, A1, fB, B0, B1, G, mA, mB);
+        gather_pair<STORE_BRANCH, LDS_ADDR>(wb, fA, A0, A1, fB, B0, B1, G, mA, mB);
         MLBP_FETCH_NEXT();
         front_gathered<NT>(tab, fA, mA, G, redP);
         if (two) front_gathered<NT>(tab, fB, mB, G, redP + 2048);
@@ -868,17 +920,20 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
       const double* rd = reinterpret_cast<const double*>(redP);
       double rA = rd[lane];
       if (fA & UOP_MT) rA = (rA + rd[64 + lane]) + (rd[128 + lane] + rd[192 + lane]);
-      work[(A1.z >> 3) + lane] = rescale(rA, bad);
+      if (LDS_ADDR) lds1_put(A1.z + lane8, ONE_VERDICT ? rescale_kmax(rA, some, kmax) : rescale(rA, bad));
+      else work[(A1.z >> 3) + lane] = ONE_VERDICT ? rescale_kmax(rA, some, kmax) : rescale(rA, bad);
       if (two) {
         double rB = rd[256 + lane];
         if (fB & UOP_MT) rB = (rB + rd[320 + lane]) + (rd[384 + lane] + rd[448 + lane]);
-        work[(B1.z >> 3) + lane] = rescale(rB, bad);
+        if (LDS_ADDR) lds1_put(B1.z + lane8, ONE_VERDICT ? rescale_kmax(rB, some, kmax) : rescale(rB, bad));
+        else work[(B1.z >> 3) + lane] = ONE_VERDICT ? rescale_kmax(rB, some, kmax) : rescale(rB, bad);
       }
       parity ^= 1;
     }
     A0 = nA0; A1 = nA1; B0 = nB0; B1 = nB1;
 #undef MLBP_FETCH_NEXT
   }
+  if (ONE_VERDICT) bad = some == 0 || __ballot(kmax >= KEY_BAD) != 0;
   if (bad) {                                      // the same in every wave: the inputs were identical
     if (t == 0) f.bail[g] = 2;
     return;
