@@ -64,6 +64,28 @@ __device__ __forceinline__ double swapadd32(double a, double b) {
   return __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
 }
 
+// The packed reductions (PACKED_NORM, PACKED_HOIST): the four DPP steps of wave_sum / wave_max_u32, which end with every lane of
+// a row of 16 holding the row's total.  On a vector packed n consecutive entries to the lane, behind the in-lane adds, they are
+// the tree's next four levels (lane ^ 1, lane ^ 2, the two mirrors pair the same partial sums as wave_sum's later steps do).
+__device__ __forceinline__ double row16_sum(double v) {
+  v += dpp_mov<0xB1>(v);
+  v += dpp_mov<0x4E>(v);
+  v += dpp_mov<0x141>(v);
+  v += dpp_mov<0x140>(v);
+  return v;
+}
+typedef int v4i __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ v4i sload4(const int32_t* p) {      // four consecutive words through the scalar data cache, 16-byte aligned
+  return *(const v4i __attribute__((address_space(4)))*)(uintptr_t)p;
+}
+__device__ __forceinline__ unsigned row16_max_u32(unsigned v) {
+  v = max(v, (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true));
+  v = max(v, (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, true));
+  v = max(v, (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x141, 0xF, 0xF, true));
+  v = max(v, (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x140, 0xF, 0xF, true));
+  return v;
+}
+
 // Workgroup-wide "any" with ONE barrier: each wave's ballot into its word of `votes`, the barrier, every thread reads the four
 // words.  (__syncthreads_or / __syncthreads_and compile to three barriers each; the three votes of a launch cost 1.0-1.4 %
 // of it that way.)  The four words must not be written again, by a later vote or as anything else, before every wave has
@@ -632,6 +654,13 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
   constexpr bool STORE_BRANCH = PAIR_GATHER;
   constexpr bool ONE_VERDICT = PAIR_GATHER;
   constexpr bool LDS_ADDR = PAIR_GATHER;
+  // (LAB_NOTES R20: the wave reductions outside the main loop on PACKED vectors -- a lane holds 4 (PACKED_NORM) or 2 (PACKED_HOIST)
+  // consecutive entries, the lowest levels of wave_sum's tree are in-lane adds, and the cross-lane levels serve four slots, or two
+  // rows, at once.  wave_sum IS the balanced pairwise tree over entries 0..63 in index order, so the totals have its bits.  Taken
+  // where PAIR_GATHER is, X = 64 only: PADX rows are shorter than a wave, GRAD keeps gst per row; the MULTI instance spills 20
+  // bytes with PACKED_HOIST and takes the tail alone: profiles/r20a_lean_kernel_resources.txt)
+  constexpr bool PACKED_NORM = PAIR_GATHER && !PADX;
+  constexpr bool PACKED_HOIST = PAIR_GATHER && !PADX && !MULTI;
   static_assert(!(GRAD && PADX), "the GRAD form of phase A loads whole rows: X = 64 only");
 
   LaneGeo G;
@@ -667,6 +696,12 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
   constexpr int HB = 8;                       // unary rows per wave held in registers; more go round again below
   double ur[HB];
   int uslot[HB], ufac[HB];
+  // PACKED_HOIST: two rows per wave instruction -- the lower half-wave row 2p, the upper one row 2p + 1, lane h of a half the
+  // entries 2h and 2h + 1 (an empty entry reads the first 512 bytes of the image)
+  const double* urow[HB];
+  double2 ur2[HB / 2];
+  const bool upper = lane >= 32;
+  const int h2 = 2 * (lane & 31);
   {
     const Words16 hl = sload16(img_hoist + wave * 2 * f.HL);      // this wave's (unary slot, message slot) pairs, -1 padded
 #pragma unroll
@@ -674,7 +709,14 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
       const int u = hl.w[2 * j];
       uslot[j] = hl.w[2 * j + 1];
       ufac[j] = u;
-      if (EARLY) {
+      if (PACKED_HOIST) {
+        // (the index word and the range check as below; the row's address stays a scalar)
+        int row = -1;
+        if (u >= 0) row = f.dense ? g * d.U + u : as_const(d.unary_tab)[(size_t)g * d.U + u];
+        const bool in = (unsigned)row < (unsigned)d.n_unary_tables;
+        if (u >= 0 && !in) ok = false;
+        urow[j] = in ? d.unary_tables + (size_t)row * 64 : nowhere;
+      } else if (EARLY) {
         // the index word of an entry that exists only (a scalar load, outside the count; a graph without unary factors brings
         // no unary_tab); an empty entry or a row out of range loads a value nobody uses -- uslot < 0 skips it, !ok skips the
         // graph; PADX lanes past X are zeroed where the row is used
@@ -692,6 +734,10 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
           else ur[j] = d.unary_tables[(size_t)row * X + lane];
         }
       }
+    }
+    if (PACKED_HOIST) {
+#pragma unroll
+      for (int p = 0; p < HB / 2; ++p) ur2[p] = *reinterpret_cast<const double2*>((upper ? urow[2 * p + 1] : urow[2 * p]) + h2);
     }
   }
   double2 tab[NT][4][2];
@@ -800,8 +846,27 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
   // whose total is not positive (all zero, or NaN) flags its graph like a zero-total update inside the sweeps (rescale): the
   // zero-sum -> uniform rule of LBP.py:655-657 acts, and every graph it acts on goes to the exact kernel -- one rule for the
   // prologue and the main loop, and exact_count counts all such graphs
+  if (PACKED_HOIST) {
+    // two rows a pass.  Level 1 of the tree is the in-lane add, levels 2-5 the DPP steps (a half-wave's 32 lanes then hold
+    // R0 + R1 in their first row of 16 and R2 + R3 in their second, R = a sum of 16 consecutive entries), level 6 adds the two.
+    // The quotient, the verdict and the store all stay in this layout
 #pragma unroll
-  for (int j = 0; j < HB; ++j) {
+    for (int p = 0; p < HB / 2; ++p) {
+      if (uslot[2 * p] >= 0 || uslot[2 * p + 1] >= 0) {
+        const int slot = upper ? uslot[2 * p + 1] : uslot[2 * p];
+        const double2 r = ur2[p];
+        const double q = row16_sum(r.x + r.y);
+        const double s = swapadd16(q, q);
+        const double2 m = make_double2(renorm(r.x, s, uniform, true), renorm(r.y, s, uniform, true));
+        if (slot >= 0) {
+          bad_key = max(bad_key, s > 0.0 ? max(mag_key(m.x), mag_key(m.y)) : KEY_BAD);
+          *reinterpret_cast<double2*>(work + slot * 64 + h2) = m;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < (PACKED_HOIST ? 0 : HB); ++j) {
     if (uslot[j] >= 0) {
       const double r = (!PADX || lane < X) ? ur[j] : 0.0;
       const double s = wave_sum(r);
@@ -944,6 +1009,10 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
   double marg[2] = {0.0, 0.0};
   if (EARLY) dense_ok = !f.dense || t >= d.P + d.U || dense_word == (t < d.P ? g * d.P + t : g * d.U + (t - d.P));
   bool bad_out = !dense_ok;
+  // PACKED_NORM: the first four words of the wave's written-slot list (16-byte aligned: every part of the image is a multiple of
+  // four words, WL too), one scalar load that lands while the read-out runs
+  v4i wq = {0, 0, 0, 0};
+  if (PACKED_NORM) wq = sload4(img_written + wave * f.WL);
   if (f.readout) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -979,7 +1048,24 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
   // ---- the deferred normalisations (only when the messages go back to memory): exactly the slots the program wrote,
   //      wave w takes its WL-entry list, four at a time ----
   if (f.keep || GRAD) {      // (GRAD: the same validity check guards the messages the gradient reads)
-    for (int j0 = 0; j0 < f.WL; j0 += 4) {
+    // PACKED_NORM: the four slots of a pass in one reduction -- lane group s = lane >> 4 takes the s-th listed slot, its lane c
+    // the entries 4c .. 4c + 3.  Levels 1-2 of the tree are in-lane adds, levels 3-6 the four DPP steps inside the group
+    for (int j0 = 0; PACKED_NORM && j0 < f.WL; j0 += 4) {
+      const v4i w = wq;                                             // (asked for a pass ahead: the first one ahead of the read-out)
+      if (j0 + 4 < f.WL) wq = sload4(img_written + wave * f.WL + j0 + 4);
+      const int slot = upper ? ((lane & 16) ? w.w : w.z) : ((lane & 16) ? w.y : w.x);
+      const int at = slot * 512 + (lane & 15) * 32;
+      double2 a = make_double2(1.0, 1.0), b = a;                    // (a padding entry: ones, nothing stored)
+      if (slot >= 0) { a = lds2(wb + at); b = lds2(wb + at + 16); }
+      const unsigned key = row16_max_u32(max(max(mag_key(a.x), mag_key(a.y)), max(mag_key(b.x), mag_key(b.y))));
+      bad_out |= key >= KEY_BAD || key < KEY_MIN;         // a variable product underflowed or vanished
+      const double s = row16_sum((a.x + a.y) + (b.x + b.y));
+      if (slot >= 0) {
+        *reinterpret_cast<double2*>(wb + at) = make_double2(a.x / s, a.y / s);
+        *reinterpret_cast<double2*>(wb + at + 16) = make_double2(b.x / s, b.y / s);
+      }
+    }
+    for (int j0 = 0; !PACKED_NORM && j0 < f.WL; j0 += 4) {
       const const_i32p wl = as_const(img_written + wave * f.WL + j0);
       int slot[4];
       double v[4], s[4];
