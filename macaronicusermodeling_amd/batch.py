@@ -325,13 +325,7 @@ class FactorGraphBatch:
         a.log_z = log_z.data_ptr()
         joint = lab = None
         if labels is not None:
-            if torch.is_tensor(labels) and labels.dtype == torch.int32 and labels.device == self.device and labels.is_contiguous():
-                lab = labels
-            else:
-                host = labels.cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
-                lab = torch.from_numpy(np.ascontiguousarray(host.astype(np.int64).astype(np.int32))).to(self.device)
-            if tuple(lab.shape) != (self.B, topo.n_vars):
-                raise ValueError('labels must be [B][n_vars]')
+            lab = self._labels_i32(labels)
             joint = torch.empty(self.B, dtype=torch.float64, device=self.device)
             a.labels, a.joint_logp = lab.data_ptr(), joint.data_ptr()
             if score is not None:
@@ -473,18 +467,13 @@ class FactorGraphBatch:
         V.check(V.lib.mlbp_converge_f64(C.byref(a), _stream_ptr(self.device)))
         return (rounds, residual, hist) if history else (rounds, residual)
 
-    # ---- the model's true marginals and log Z (include/mlbp_cutset.h) --------------------------------
-    def exact_inference(self, labels=None, marginals=None, cutset=None):
-        """The TRUE log Z and marginals of every graph by cutset conditioning -- what sweep() and log_partition() approximate
-        on a loopy graph.  Returns (log_z [B], marginals [B][n_vars][X]) device tensors, or (log_z, marginals, joint_logp [B])
-        when `labels` ([B][n_vars] integers, GraphTopology.var_ids order) is given: joint_logp = score(labels) - log_z, the true
-        log-probability of the assignment.  marginals: optional contiguous float64 [B][n_vars][X] device tensor to write into.
-        cutset: a list of variable ids that replaces cutset.choose(topo); the pairwise factors among the other variables
-        must form a forest, and X^len(cutset) may not pass 65536 (CutsetError otherwise).  Any valid cutset gives the same
-        values up to rounding.  self.msgs is neither read nor written."""
-        from . import cutset as K
+    # ---- what the three cutset-conditioning calls share -----------------------------------------------------
+    def _cutset_args(self, K, Args, cutset, refusal):
+        """(plan, args) of a call into binding K (cutset, exactmap, exactgrad): the cutset's variable ids translated, the plan
+        validated by K's library, and the sizes, plan and table fields of an Args() filled.  refusal: the message for pairwise
+        tables that are not float64."""
         if self.pair_tables is not None and self.pair_tables.dtype != torch.float64:
-            raise NotImplementedError('exact_inference needs float64 pairwise tables')
+            raise NotImplementedError(refusal)
         topo = self.topo
         if cutset is not None:
             unknown = [v for v in cutset if v not in topo.var_index]
@@ -492,7 +481,7 @@ class FactorGraphBatch:
                 raise ValueError('cutset names unknown variable ids %r' % (unknown,))
             cutset = [topo.var_index[v] for v in cutset]
         pl = K.plan(topo, cutset, self.X, self.device)
-        a = K.CutsetArgs()
+        a = Args()
         a.B, a.X, a.n_vars, a.P, a.U = self.B, self.X, topo.n_vars, topo.P, topo.U
         a.n_cut, a.n_free, a.n_items, a.n_consts, a.n_forest = pl.n_cut, pl.n_free, pl.n_items, pl.n_consts, pl.n_forest
         a.plan, a.plan_words = pl.dev.data_ptr(), len(pl.words)
@@ -506,6 +495,31 @@ class FactorGraphBatch:
                 raise RuntimeError('set_unary_tables() first')
             a.n_unary_tables = self.unary_tables.shape[0]
             a.unary_tables, a.unary_tab = self.unary_tables.data_ptr(), self.unary_tab.data_ptr()
+        return pl, a
+
+    def _labels_i32(self, labels):
+        """labels ([B][n_vars] integers, a tensor or an array) as a contiguous int32 device tensor."""
+        if torch.is_tensor(labels) and labels.dtype == torch.int32 and labels.device == self.device and labels.is_contiguous():
+            lab = labels
+        else:
+            host = labels.cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
+            lab = torch.from_numpy(np.ascontiguousarray(host.astype(np.int64).astype(np.int32))).to(self.device)
+        if tuple(lab.shape) != (self.B, self.topo.n_vars):
+            raise ValueError('labels must be [B][n_vars]')
+        return lab
+
+    # ---- the model's true marginals and log Z (include/mlbp_cutset.h) --------------------------------
+    def exact_inference(self, labels=None, marginals=None, cutset=None):
+        """The TRUE log Z and marginals of every graph by cutset conditioning -- what sweep() and log_partition() approximate
+        on a loopy graph.  Returns (log_z [B], marginals [B][n_vars][X]) device tensors, or (log_z, marginals, joint_logp [B])
+        when `labels` ([B][n_vars] integers, GraphTopology.var_ids order) is given: joint_logp = score(labels) - log_z, the true
+        log-probability of the assignment.  marginals: optional contiguous float64 [B][n_vars][X] device tensor to write into.
+        cutset: a list of variable ids that replaces cutset.choose(topo); the pairwise factors among the other variables
+        must form a forest, and X^len(cutset) may not pass 65536 (CutsetError otherwise).  Any valid cutset gives the same
+        values up to rounding.  self.msgs is neither read nor written."""
+        from . import cutset as K
+        topo = self.topo
+        pl, a = self._cutset_args(K, K.CutsetArgs, cutset, 'exact_inference needs float64 pairwise tables')
         if marginals is None:
             marginals = torch.empty(self.B, topo.n_vars, self.X, dtype=torch.float64, device=self.device)
         elif tuple(marginals.shape) != (self.B, topo.n_vars, self.X) or marginals.dtype != torch.float64 \
@@ -515,13 +529,7 @@ class FactorGraphBatch:
         a.log_z, a.marginals = log_z.data_ptr(), marginals.data_ptr()
         joint = lab = None
         if labels is not None:
-            if torch.is_tensor(labels) and labels.dtype == torch.int32 and labels.device == self.device and labels.is_contiguous():
-                lab = labels
-            else:
-                host = labels.cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
-                lab = torch.from_numpy(np.ascontiguousarray(host.astype(np.int64).astype(np.int32))).to(self.device)
-            if tuple(lab.shape) != (self.B, topo.n_vars):
-                raise ValueError('labels must be [B][n_vars]')
+            lab = self._labels_i32(labels)
             joint = torch.empty(self.B, dtype=torch.float64, device=self.device)
             a.labels, a.joint_logp = lab.data_ptr(), joint.data_ptr()
         need = K.workspace_bytes(self.B, self.X, topo.n_vars, topo.P, topo.U, pl.n_forest, pl.n_cut)
@@ -540,29 +548,8 @@ class FactorGraphBatch:
         are broken as include/mlbp_exactmap.h says; the bits of every output depend on the graph and the cutset alone.
         cutset: as in exact_inference.  self.msgs is neither read nor written."""
         from . import exactmap as K
-        if self.pair_tables is not None and self.pair_tables.dtype != torch.float64:
-            raise NotImplementedError('exact_map needs float64 pairwise tables')
         topo = self.topo
-        if cutset is not None:
-            unknown = [v for v in cutset if v not in topo.var_index]
-            if unknown:
-                raise ValueError('cutset names unknown variable ids %r' % (unknown,))
-            cutset = [topo.var_index[v] for v in cutset]
-        pl = K.plan(topo, cutset, self.X, self.device)
-        a = K.ExactMapArgs()
-        a.B, a.X, a.n_vars, a.P, a.U = self.B, self.X, topo.n_vars, topo.P, topo.U
-        a.n_cut, a.n_free, a.n_items, a.n_consts, a.n_forest = pl.n_cut, pl.n_free, pl.n_items, pl.n_consts, pl.n_forest
-        a.plan, a.plan_words = pl.dev.data_ptr(), len(pl.words)
-        if topo.P:
-            if self.pair_tables is None:
-                raise RuntimeError('set_pair_tables() first')
-            a.n_pair_tables = self.pair_tables.shape[0]
-            a.pair_tables, a.pair_tab = self.pair_tables.data_ptr(), self.pair_tab.data_ptr()
-        if topo.U:
-            if self.unary_tables is None:
-                raise RuntimeError('set_unary_tables() first')
-            a.n_unary_tables = self.unary_tables.shape[0]
-            a.unary_tables, a.unary_tab = self.unary_tables.data_ptr(), self.unary_tab.data_ptr()
+        pl, a = self._cutset_args(K, K.ExactMapArgs, cutset, 'exact_map needs float64 pairwise tables')
         if max_marginals is True:
             max_marginals = torch.empty(self.B, topo.n_vars, self.X, dtype=torch.float64, device=self.device)
         elif max_marginals is False:
@@ -585,29 +572,8 @@ class FactorGraphBatch:
     def _exactgrad(self, cutset, marginals=None, pair_marginals=None, expect=None, grad=None, labels=None):
         """One mlbp_exactgrad_f64 call: log_z [B], and whichever of the optional outputs is given (expect, grad: (ee, ed))."""
         from . import exactgrad as K
-        if self.pair_tables is not None and self.pair_tables.dtype != torch.float64:
-            raise NotImplementedError('the exact pair marginals and gradient need float64 pairwise tables')
         topo = self.topo
-        if cutset is not None:
-            unknown = [v for v in cutset if v not in topo.var_index]
-            if unknown:
-                raise ValueError('cutset names unknown variable ids %r' % (unknown,))
-            cutset = [topo.var_index[v] for v in cutset]
-        pl = K.plan(topo, cutset, self.X, self.device)
-        a = K.ExactGradArgs()
-        a.B, a.X, a.n_vars, a.P, a.U = self.B, self.X, topo.n_vars, topo.P, topo.U
-        a.n_cut, a.n_free, a.n_items, a.n_consts, a.n_forest = pl.n_cut, pl.n_free, pl.n_items, pl.n_consts, pl.n_forest
-        a.plan, a.plan_words = pl.dev.data_ptr(), len(pl.words)
-        if topo.P:
-            if self.pair_tables is None:
-                raise RuntimeError('set_pair_tables() first')
-            a.n_pair_tables = self.pair_tables.shape[0]
-            a.pair_tables, a.pair_tab = self.pair_tables.data_ptr(), self.pair_tab.data_ptr()
-        if topo.U:
-            if self.unary_tables is None:
-                raise RuntimeError('set_unary_tables() first')
-            a.n_unary_tables = self.unary_tables.shape[0]
-            a.unary_tables, a.unary_tab = self.unary_tables.data_ptr(), self.unary_tab.data_ptr()
+        pl, a = self._cutset_args(K, K.ExactGradArgs, cutset, 'the exact pair marginals and gradient need float64 pairwise tables')
 
         def checked(t, shape, what):
             if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != torch.float64 or t.device != self.device or not t.is_contiguous():
@@ -632,17 +598,9 @@ class FactorGraphBatch:
                 a.expect_ee, a.expect_ed = checked(expect[0], (self.B, a.F_ee), 'out_ee'), checked(expect[1], (self.B, a.F_ed), 'out_ed')
             if grad is not None:
                 a.grad_ee, a.grad_ed = checked(grad[0], (self.B, a.F_ee), 'out_ee'), checked(grad[1], (self.B, a.F_ed), 'out_ed')
-                if labels is None:
-                    if getattr(self, '_labels', None) is None:
-                        raise RuntimeError('exact_gradient needs labels: pass them or set_observations() first')
-                    lab = self._labels
-                elif torch.is_tensor(labels) and labels.dtype == torch.int32 and labels.device == self.device and labels.is_contiguous():
-                    lab = labels
-                else:
-                    host = labels.cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
-                    lab = torch.from_numpy(np.ascontiguousarray(host.astype(np.int64).astype(np.int32))).to(self.device)
-                if tuple(lab.shape) != (self.B, topo.n_vars):
-                    raise ValueError('labels must be [B][n_vars]')
+                if labels is None and getattr(self, '_labels', None) is None:
+                    raise RuntimeError('exact_gradient needs labels: pass them or set_observations() first')
+                lab = self._labels_i32(self._labels if labels is None else labels)
                 keep.append(lab)
                 a.labels = lab.data_ptr()
         log_z = torch.empty(self.B, dtype=torch.float64, device=self.device)

@@ -35,7 +35,7 @@ SOURCES_EXACTMAP = ['mlbp_exactmap.hip']
 SOURCES_EXACTGRAD = ['mlbp_exactgrad.hip']
 # csrc/ headers: the core library's, and what the side libraries share (mlbp_graph_device.h includes mlbp_device.h)
 HEADERS = ['mlbp_internal.h', 'mlbp_device.h']
-HEADERS_SIDE = ['mlbp_device.h', 'mlbp_graph_device.h', 'mlbp_graph_host.h', 'mlbp_cutset_plan.h']
+HEADERS_SIDE = ['mlbp_device.h', 'mlbp_graph_device.h', 'mlbp_graph_host.h', 'mlbp_cutset_plan.h', 'mlbp_cutset_walk.h']
 # (source dir, sources, csrc/ headers, public header, output): every library has its own sources and its own kernel
 # inventory; the flags are the same
 LIBRARIES = [

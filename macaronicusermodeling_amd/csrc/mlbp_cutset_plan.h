@@ -1,11 +1,14 @@
-// What the two cutset-conditioning libraries share (libmlbp_cutset.so, libmlbp_exactmap.so; gfx950 only): the layout of the
-// packed plan of include/mlbp_cutset.h and its validation, and the power-of-two arithmetic of the walks -- exponent
-// extraction, the (mantissa, exponent) pair, the rescaling of a vector by the exponent of its largest entry.  Helpers only,
-// no kernel: each library keeps its own.  Not part of the ABI.
+// What the three cutset-conditioning libraries share beside the walk itself (libmlbp_cutset.so, libmlbp_exactmap.so,
+// libmlbp_exactgrad.so; gfx950 only): the layout of the packed plan of include/mlbp_cutset.h and its validation, the kernel
+// arguments every walk reads (WalkDev), the power-of-two arithmetic of the walks -- exponent extraction, the (mantissa,
+// exponent) pair, the rescaling of a vector by the exponent of its largest entry -- and the host core: the LDS and vector
+// sizing, the kernel pick, the chunks rule, the shape checks of a compute entry and the filling of WalkDev.  The walk over
+// the configurations is mlbp_cutset_walk.h.  Helpers only, no kernel: each library keeps its own.  Not part of the ABI.
 // Include after include/mlbp_cutset.h (the plan's constants), mlbp_graph_device.h and mlbp_graph_host.h.
 #ifndef MLBP_CUTSET_PLAN_H
 #define MLBP_CUTSET_PLAN_H
 
+#include <climits>
 #include <string>
 #include <vector>
 
@@ -14,6 +17,7 @@ namespace mlbp_graph {
 constexpr int HEADER = MLBP_CUTSET_PLAN_HEADER;
 constexpr int EMPTY = -(1 << 28);           // the exponent of a partial result that holds nothing yet
 constexpr int MIN_SHIFT = -4000;            // ldexp by less than this is zero for every finite double
+constexpr int ROW = 65;                     // padded row of an X = 64 table in LDS
 
 // The sections of a packed plan behind its header; returns the number of words.  The sizes have been checked.
 template <class Ptr>
@@ -38,6 +42,16 @@ __host__ __device__ inline int64_t carve_plan(Ptr plan, int n_vars, int P, int U
 inline int64_t plan_words(int64_t n_vars, int64_t P, int64_t U, int64_t n_cut, int64_t n_free, int64_t n_items, int64_t n_consts) {
   return HEADER + n_cut + n_free + 2 * n_vars + n_vars + 1 + 3 * n_items + 4 * n_consts + 2 * P + U + P;
 }
+
+// What every kernel of the three libraries is handed: a library's own struct derives from it and adds its inputs and outputs.
+struct WalkDev {
+  const int32_t* plan;
+  const double* pair_tables; const int32_t* pair_tab;
+  const double* unary_tables; const int32_t* unary_tab;
+  double* partials;                          // [B][parts][the library's partial], parts = chunks (generic) or 4 chunks (X = 64)
+  double* vectors;                           // generic kernel, vectors not in LDS: [B][chunks][5 n_vars + 2][round_up(X, 2)]
+  int32_t B, X, n_vars, P, U, n_cut, n_free, n_items, n_consts, n_forest, n_pair_tables, n_unary_tables, n_configs, chunks, parts;
+};
 
 // X^n_cut, or -1 beyond MLBP_CUTSET_MAX_CONFIGS
 inline int64_t count_configs(int32_t X, int32_t n_cut) {
@@ -218,6 +232,100 @@ int check_packed_plan(const int32_t* plan, int32_t n_words, int32_t X) {
   for (int u = 0; u < U; ++u)
     if (!unary_used[u]) return fail(MLBP_EINVAL, "plan: unary factor %d is left out", u);
   return MLBP_OK;
+}
+
+// ---- the host core of a walk: sizing, kernel pick, chunks, the checks and the launch of a compute entry -----------------
+// The two walk kernels, as every library's header numbers them (MLBP_*_KERNEL_X64 / _GENERIC).
+constexpr int WALK_X64 = 1, WALK_GENERIC = 2;
+
+int64_t ints_bytes(int64_t P, int64_t U) { return 4 * ((P + U + 16 + 3) / 4 * 4); }
+int64_t vector_doubles(int64_t n_vars, int64_t X) { return (5 * n_vars + 2) * ((X + 1) / 2 * 2); }
+int64_t x64_lds_bytes(int64_t n_vars, int64_t P, int64_t U, int64_t n_forest) {
+  return n_forest * (64 * mlbp_graph::ROW * 8) + 21 * n_vars * 512 + 64 + ints_bytes(P, U);
+}
+int64_t generic_lds_bytes(int64_t n_vars, int64_t P, int64_t U, int64_t X) { return vector_doubles(n_vars, X) * 8 + 64 + ints_bytes(P, U); }
+
+// The rule of mlbp_cutset_pick_kernel; max_forest_x64: the most forest factors the library's X = 64 kernel takes.
+int pick_walk_kernel(int32_t X, int32_t n_vars, int32_t P, int32_t U, int32_t n_forest, int32_t max_forest_x64 = INT_MAX) {
+  if (X < 2 || n_vars <= 0 || P < 0 || U < 0 || n_forest < 0 || n_forest > P)
+    return fail(MLBP_EINVAL, "pick_kernel: X = %d, n_vars = %d, P = %d, U = %d, n_forest = %d", X, n_vars, P, U, n_forest);
+  if (X > MLBP_CUTSET_MAX_X) return fail(MLBP_EUNSUPPORTED, "X = %d: at most %d states are supported", X, MLBP_CUTSET_MAX_X);
+  if (X == 64 && n_forest <= max_forest_x64 && x64_lds_bytes(n_vars, P, U, n_forest) <= MLBP_CUTSET_X64_LDS_BYTES) return WALK_X64;
+  if (64 + ints_bytes(P, U) > MLBP_CUTSET_GENERIC_LDS_BYTES)
+    return fail(MLBP_EUNSUPPORTED, "P + U = %lld factors: their exponents do not fit the LDS budget", (long long)P + U);
+  return WALK_GENERIC;
+}
+
+// C of the grid (B, C): every walker (a workgroup, or the four waves of one) gets work until min_workgroups are in flight.
+int32_t walk_chunks(int32_t B, int32_t walkers, int32_t min_workgroups) {
+  const int32_t spread = (min_workgroups + B - 1) / B;
+  return walkers < spread ? walkers : spread;
+}
+
+// The doubles of a chunk in the workspace, `per` the library's partial: a partial per wave (X = 64), or the partial and, when
+// they do not fit the LDS, the generic kernel's vectors.
+int64_t chunk_doubles(int which, int64_t per, int64_t n_vars, int64_t P, int64_t U, int64_t X) {
+  if (which == WALK_X64) return 4 * per;
+  return per + (generic_lds_bytes(n_vars, P, U, X) > MLBP_CUTSET_GENERIC_LDS_BYTES ? vector_doubles(n_vars, X) : 0);
+}
+
+// The checks every compute entry starts with, over the library's args struct (the field names agree): sizes, states, the
+// library's kernel pick, the plan's words, the tables, own(a) -- the library's outputs and further inputs --, the number of
+// configurations, the extent.  Returns the kernel (WALK_*) or the status; *n_configs is set with the kernel.
+template <class Args, class Own>
+int check_walk_args(const Args* a, int (*pick)(int32_t, int32_t, int32_t, int32_t, int32_t), Own own, int64_t* n_configs) {
+  using namespace mlbp_graph;
+  if (!a) return fail(MLBP_EINVAL, "args is NULL");
+  if (a->B <= 0 || a->n_vars <= 0 || a->P < 0 || a->U < 0 || a->P + a->U <= 0 || a->n_cut < 0 || a->n_free < 0 || a->n_items < 0 ||
+      a->n_consts < 0 || (int64_t)a->n_cut + a->n_free != a->n_vars)
+    return fail(MLBP_EINVAL, "bad sizes: B %d, n_vars %d, P %d, U %d, n_cut %d, n_free %d, n_items %d, n_consts %d", a->B, a->n_vars, a->P,
+                a->U, a->n_cut, a->n_free, a->n_items, a->n_consts);
+  if (int e = check_states(a->X)) return e;
+  const int which = pick(a->X, a->n_vars, a->P, a->U, a->n_forest);
+  if (which < 0) return which;
+  if (!a->plan || plan_words(a->n_vars, a->P, a->U, a->n_cut, a->n_free, a->n_items, a->n_consts) != a->plan_words)
+    return fail(MLBP_EINVAL, "plan is NULL or plan_words = %d disagrees with the sizes", a->plan_words);
+  if (int e = check_args_tables(a)) return e;
+  if (int e = own(a)) return e;
+  *n_configs = count_configs(a->X, a->n_cut);
+  if (*n_configs < 0) return too_many_configs(a->X, a->n_cut);
+  if ((int64_t)a->n_vars * a->X > 0x7fffffff / 16) return fail(MLBP_EUNSUPPORTED, "n_vars * X = %lld too large", (long long)a->n_vars * a->X);
+  return which;
+}
+
+// `need`: the library's workspace_bytes of the call, or its status.
+template <class Args>
+int check_walk_workspace(const Args* a, int64_t need) {
+  if (need < 0) return (int)need;
+  if (!a->workspace || a->workspace_bytes < need)
+    return fail(MLBP_EINVAL, "workspace is NULL or workspace_bytes = %lld below the %lld the call needs", (long long)a->workspace_bytes, (long long)need);
+  return MLBP_OK;
+}
+
+// The fields of WalkDev from the args; the partials lead the workspace, the vectors are in LDS until generic_walk_lds says not.
+template <class Args>
+void fill_walk_dev(mlbp_graph::WalkDev& d, const Args* a, int64_t n_configs, int chunks, int which) {
+  d.plan = a->plan;
+  d.pair_tables = a->pair_tables; d.pair_tab = a->pair_tab; d.unary_tables = a->unary_tables; d.unary_tab = a->unary_tab;
+  d.partials = a->workspace;
+  d.vectors = nullptr;
+  d.B = a->B; d.X = a->X; d.n_vars = a->n_vars; d.P = a->P; d.U = a->U; d.n_cut = a->n_cut; d.n_free = a->n_free; d.n_items = a->n_items;
+  d.n_consts = a->n_consts; d.n_forest = a->n_forest; d.n_pair_tables = a->n_pair_tables; d.n_unary_tables = a->n_unary_tables;
+  d.n_configs = (int32_t)n_configs; d.chunks = chunks; d.parts = which == WALK_X64 ? 4 * chunks : chunks;
+}
+
+// The dynamic LDS of the generic walk kernel; vectors that do not fit go to `spill`, the library's place for them in the workspace.
+size_t generic_walk_lds(mlbp_graph::WalkDev& d, double* spill) {
+  const int64_t lds = generic_lds_bytes(d.n_vars, d.P, d.U, d.X);
+  if (lds <= MLBP_CUTSET_GENERIC_LDS_BYTES) return (size_t)lds;
+  d.vectors = spill;
+  return (size_t)(64 + ints_bytes(d.P, d.U));
+}
+
+// Behind a launch: `what` names the kernel in the message.
+int launched(const char* what) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? MLBP_OK : fail(MLBP_EHIP, "%s launch failed: %s", what, hipGetErrorString(e));
 }
 
 }  // namespace

@@ -2,14 +2,14 @@
 // (include/mlbp_exactgrad.h), gfx950 only, float64.
 //
 // Three kernels; the walk kernel is chosen from (X, n_vars, P, U, n_forest) by mlbp_exactgrad_pick_kernel:
-//   exactgrad_x64_kernel<NF>   X = 64, n_forest <= 2, NF = max(n_forest, 1): the walk of cutset_x64_kernel restated -- the forest's tables in LDS,
-//                              rows of 65, every WAVE its own configurations, lane = state, no workgroup barrier inside the walk
-//                              -- and beside it the wave's pair accumulators: the 64 x 64 sum of rank-1 updates of every forest
-//                              factor in registers (lane = column, 64 doubles per lane, 64 FMAs on v_readlane broadcasts per
-//                              configuration), the rows of the cutset-incident factors and the cells of the cutset-internal
-//                              ones in the wave's own partial in the workspace.
-//   exactgrad_generic_kernel   any X in [2, 1024]: the walk of cutset_generic_kernel restated, the workgroup one configuration at
-//                              a time; every pair accumulator in the workgroup's partial.
+//   exactgrad_x64_kernel<NF>   X = 64, n_forest <= 2, NF = max(n_forest, 1): the X = 64 walk of csrc/mlbp_cutset_walk.h in its sum
+//                              form -- the forest's tables in LDS, rows of 65, every WAVE its own configurations, lane = state,
+//                              no workgroup barrier inside the walk -- and around its steps the wave's pair accumulators: the
+//                              64 x 64 sum of rank-1 updates of every forest factor in registers (lane = column, 64 doubles per
+//                              lane, 64 FMAs on v_readlane broadcasts per configuration), the rows of the cutset-incident
+//                              factors and the cells of the cutset-internal ones in the wave's own partial in the workspace.
+//   exactgrad_generic_kernel   any X in [2, 1024]: the generic walk of csrc/mlbp_cutset_walk.h in its sum form, the workgroup one
+//                              configuration at a time; every pair accumulator in the workgroup's partial.
 //   exactgrad_combine_kernel   one workgroup per graph: adds the partials in index order, applies the rescaled table to the
 //                              forest factors, divides by Z, writes the requested tensors, contracts with phi eight features
 //                              at a time, forms the observed features at the labels and takes the one logarithm.
@@ -23,7 +23,8 @@
 #define MLBP_GRAPH_NO_SWEEPS                // this library runs no sweep program
 #include "../csrc/mlbp_graph_device.h"
 #include "../csrc/mlbp_graph_host.h"
-#include "../csrc/mlbp_cutset_plan.h"       // the plan's layout and check, the power-of-two helpers
+#include "../csrc/mlbp_cutset_plan.h"       // the plan's layout and check, the power-of-two helpers, the host core
+#include "../csrc/mlbp_cutset_walk.h"       // the walk
 
 namespace {
 
@@ -32,239 +33,66 @@ using namespace mlbp_graph;
 constexpr int MAXF = MLBP_EXACTGRAD_MAX_FEATURES;
 constexpr int FG = 8;                       // features contracted per pass of the combine kernel
 
-struct GradDev {
-  const int32_t* plan;
-  const double* pair_tables; const int32_t* pair_tab;
-  const double* unary_tables; const int32_t* unary_tab;
+struct GradDev : WalkDev {                   // partials: [B][parts][stride]: {sum mantissa, exponent, [n_vars][X], [P][X][X]}
   const double* phi_en_en; const double* phi_en_en_w1; const double* phi_en_de;
   const int32_t* pair_phi; const int32_t* unary_kind; const int32_t* unary_obs; const int32_t* labels;
-  double* partials;                          // [B][parts][stride]: {sum mantissa, exponent, [n_vars][X], [P][X][X]}
-  double* vectors;                           // generic kernel, vectors not in LDS: [B][chunks][5 n_vars + 2][round_up(X, 2)]
   double* log_z; double* marginals; double* pair_marginals; double* expect_ee; double* expect_ed; double* grad_ee; double* grad_ed;
   int64_t stride;
-  int32_t B, X, n_vars, P, U, n_cut, n_free, n_items, n_consts, n_forest, n_pair_tables, n_unary_tables, n_configs, chunks, parts;
   int32_t F_ee, F_ed, Vde;
 };
-
-// ---- contractions: out[i] = sum_j T[i][j] m[j] (tm) or out[j] = sum_i m[i] T[i][j]; a barrier behind the result ---------
-__device__ __forceinline__ void contract_stream(const double* T, int X, int te, bool tm, const double* m, double* out) {
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  if (tm) {
-    for (int row = wave; row < X; row += WG / 64) {
-      const double* Tr = T + (size_t)row * X;
-      double acc = 0.0;
-      for (int j = lane; j < X; j += 64) acc += ldexp(Tr[j], -te) * m[j];
-      acc = wave_sum(acc);
-      if (lane == 0) out[row] = acc;
-    }
-  } else {
-    for (int j = t; j < X; j += WG) {
-      double acc = 0.0;
-#pragma unroll 4
-      for (int i = 0; i < X; ++i) acc += m[i] * ldexp(T[(size_t)i * X + j], -te);
-      out[j] = acc;
-    }
-  }
-  __syncthreads();
-}
 
 // ---- any X: the workgroup walks a chunk's configurations ---------------------------------------------------
 __global__ __launch_bounds__(WG) void exactgrad_generic_kernel(GradDev d) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int X = d.X, Xp = (X + 1) & ~1;
-  const int g = blockIdx.x, k = blockIdx.y, t = threadIdx.x;
+  const int X = d.X, g = blockIdx.x, k = blockIdx.y, t = threadIdx.x;
   if (!tables_in_range(d.pair_tab, d.P, d.n_pair_tables, d.unary_tab, d.U, d.n_unary_tables, g)) return;
-  PlanSections<const_i32p> pl;
-  carve_plan(as_const(d.plan), d.n_vars, d.P, d.U, d.n_cut, d.n_free, d.n_items, d.n_consts, pl);
-  const const_i32p ptab = as_const(d.pair_tab) + (size_t)g * d.P, utab = as_const(d.unary_tab) + (size_t)g * d.U;
-  const int n_vars = d.n_vars, P = d.P, U = d.U, n_free = d.n_free, n_cut = d.n_cut;
-  const size_t XX = (size_t)X * X;
-
-  // LDS: [vectors, unless in the workspace] [scratch] [integers]
-  double* lds = reinterpret_cast<double*>(smem);
-  const size_t n_vec = (size_t)(5 * n_vars + 2) * Xp;
-  double* vec;
-  if (!d.vectors) {
-    vec = lds;
-    lds += n_vec;
-  } else {
-    vec = d.vectors + ((size_t)g * d.chunks + k) * n_vec;
-  }
-  double* scratch = lds;
-  lds += 8;
-  int* texp = reinterpret_cast<int*>(lds);                     // [P + U] exponent of every factor's table
-  int* st = texp + P + U;                                      // [16] states of the configuration
-  const size_t vs = (size_t)n_vars * Xp;
-  double* acc = vec;                                           // [n_vars][Xp] sum over configurations of Z_c m_c, mantissas
-  double* base = acc + vs;                                     // the product of a free variable's unary rows
-  double* bel = base + vs;                                     // a free variable's vector: upward, then its full belief
-  double* up = bel + vs;                                       // its message to its parent
-  double* dn = up + vs;                                        // its parent's message to it
-  double* raw = dn + vs;
-  double* excl = raw + Xp;
+  Generic G;
+  generic_open(G, d, g);
+  const size_t vs = generic_carve(G, d, g, k, smem), XX = G.XX;
+  const int Xp = G.Xp;
+  double* acc = G.acc;                                         // [n_vars][Xp] sum over configurations of Z_c m_c, mantissas
   double* out = d.partials + ((size_t)g * d.parts + k) * d.stride;
-  double* pacc = out + 2 + (size_t)n_vars * X;                 // [P][X][X] pair accumulators, mantissas under the sum's exponent
-
-  // every table's exponent
-  for (int f = 0; f < P + U; ++f) {
-    const double* T = f < P ? d.pair_tables + (size_t)ptab[f] * XX : d.unary_tables + (size_t)utab[f - P] * X;
-    const size_t n = f < P ? XX : (size_t)X;
-    double m = 0.0;
-    for (size_t i = t; i < n; i += WG) m = fmax(m, T[i]);
-    m = block_max(m, scratch);
-    if (t == 0) texp[f] = exp_of(m);
-  }
-  __syncthreads();
-  int e_fixed = 0;                                             // every factor enters every configuration once
-  for (int f = 0; f < P + U; ++f) e_fixed += texp[f];
+  double* pacc = out + 2 + (size_t)d.n_vars * X;               // [P][X][X] pair accumulators, mantissas under the sum's exponent
+  generic_setup(G);
   for (size_t i = t; i < vs; i += WG) acc[i] = 0.0;
-  for (int i = 0; i < n_free; ++i) {
-    const int v = pl.order[i];
-    for (int j = t; j < X; j += WG) {
-      double b = 1.0;
-      for (int it = pl.item_off[v]; it < pl.item_off[v + 1]; ++it)
-        if (pl.items[3 * it] == MLBP_CUTSET_ITEM_UNARY) {
-          const int u = pl.items[3 * it + 1];
-          b *= ldexp(d.unary_tables[(size_t)utab[u] * X + j], -texp[P + u]);
-        }
-      base[(size_t)v * Xp + j] = b;
-    }
-    __syncthreads();
-    e_fixed += rescale(base + (size_t)v * Xp, X, scratch);
-  }
-
-  // the free variable's configuration-free part times its cutset-incident rows and columns, at state j
-  auto local = [&](int v, int j) {
-    double b = base[(size_t)v * Xp + j];
-    for (int it = pl.item_off[v]; it < pl.item_off[v + 1]; ++it) {
-      const int kind = pl.items[3 * it];
-      if (kind == MLBP_CUTSET_ITEM_UNARY) continue;
-      const int p = pl.items[3 * it + 1], s = st[pl.items[3 * it + 2]];
-      const double* T = d.pair_tables + (size_t)ptab[p] * XX;
-      b *= ldexp(kind == MLBP_CUTSET_ITEM_COL ? T[(size_t)j * X + s] : T[(size_t)s * X + j], -texp[p]);
-    }
-    return b;
-  };
-  auto contract = [&](int p, bool tm, const double* m) {
-    contract_stream(d.pair_tables + (size_t)ptab[p] * XX, X, texp[p], tm, m, raw);
-  };
 
   Scaled sum = {0.0, EMPTY};                                   // sum of Z_c over this chunk
   for (int c = k; c < d.n_configs; c += d.chunks) {
-    __syncthreads();
-    if (t < n_cut) {
-      int r = c;
-      for (int q = 0; q < t; ++q) r /= X;
-      st[t] = r % X;
-    }
-    __syncthreads();
-    Scaled z = {1.0, e_fixed};
-    for (int i = 0; i < d.n_consts; ++i) {
-      const int f = pl.consts[4 * i + 1], s0 = st[pl.consts[4 * i + 2]];
-      if (pl.consts[4 * i] == MLBP_CUTSET_CONST_UNARY) {
-        mul(z, ldexp(d.unary_tables[(size_t)utab[f] * X + s0], -texp[P + f]));
-      } else {
-        const int s1 = st[pl.consts[4 * i + 3]];
-        mul(z, ldexp(d.pair_tables[(size_t)ptab[f] * XX + (size_t)s0 * X + s1], -texp[f]));
-      }
-    }
-    for (int i = 0; i < n_free; ++i) {
-      const int v = pl.order[i];
-      for (int j = t; j < X; j += WG) bel[(size_t)v * Xp + j] = local(v, j);
-    }
-    __syncthreads();
-
-    // leaves to roots
-    for (int i = 0; i < n_free; ++i) {
-      const int v = pl.order[i], p = pl.parent[2 * v];
-      double* bv = bel + (size_t)v * Xp;
-      z.e += rescale(bv, X, scratch);
-      if (p < 0) {
-        double s = 0.0;
-        for (int j = t; j < X; j += WG) s += bv[j];
-        mul(z, block_sum(s, scratch));
-      } else {
-        const int par = pl.parent[2 * v + 1];
-        contract(p, pl.pav[2 * p] != v, bv);
-        z.e += rescale(raw, X, scratch);
-        for (int j = t; j < X; j += WG) {
-          up[(size_t)v * Xp + j] = raw[j];
-          bel[(size_t)par * Xp + j] *= raw[j];
-        }
-        __syncthreads();
-      }
-    }
-    if (z.m == 0.0) continue;                                  // Z_c = 0: nothing to add
-
-    // Z_c joins the chunk's sum: the larger exponent is kept; the first Z_c clears the pair accumulators
-    if (z.e > sum.e) {
-      const bool first = sum.e == EMPTY;
-      const int shift = max(sum.e - z.e, MIN_SHIFT);
+    const Scaled z = generic_up<SumAlg>(G, c, G.up);
+    if (SumAlg::dead(z)) continue;                             // Z_c = 0: nothing to add
+    const double w = join_sum(sum, z, [&](int shift, bool first) {           // the first Z_c clears the pair accumulators
       for (size_t i = t; i < vs; i += WG) acc[i] = ldexp(acc[i], shift);
-      for (size_t i = t; i < (size_t)P * XX; i += WG) pacc[i] = first ? 0.0 : ldexp(pacc[i], shift);
-      sum.m = ldexp(sum.m, shift);
-      sum.e = z.e;
+      for (size_t i = t; i < (size_t)d.P * XX; i += WG) pacc[i] = first ? 0.0 : ldexp(pacc[i], shift);
       __syncthreads();
-    }
-    const double w = ldexp(z.m, max(z.e - sum.e, MIN_SHIFT));
-    sum.m += w;
-    if (t < n_cut) acc[(size_t)pl.cutset[t] * Xp + st[t]] += w;
+    });
+    if (t < d.n_cut) acc[(size_t)G.pl.cutset[t] * Xp + G.st[t]] += w;
     if (t == 0)
       for (int i = 0; i < d.n_consts; ++i)
-        if (pl.consts[4 * i] == MLBP_CUTSET_CONST_PAIR)          // a factor inside the cutset: its cell gains Z_c
-          pacc[(size_t)pl.consts[4 * i + 1] * XX + (size_t)st[pl.consts[4 * i + 2]] * X + st[pl.consts[4 * i + 3]]] += w;
-
-    // roots to leaves
-    for (int i = n_free - 1; i >= 0; --i) {
-      const int v = pl.order[i], p = pl.parent[2 * v];
-      double* bv = bel + (size_t)v * Xp;
-      if (p >= 0) {
-        const int par = pl.parent[2 * v + 1];
-        const bool par_has_parent = pl.parent[2 * par] >= 0;
-        for (int j = t; j < X; j += WG) {
-          double b = local(par, j);
-          if (par_has_parent) b *= dn[(size_t)par * Xp + j];
-          excl[j] = b;
-        }
-        for (int q = 0; q < n_free; ++q) {                     // the parent's other children
-          const int sib = pl.order[q];
-          if (sib == v || pl.parent[2 * sib + 1] != par) continue;
-          for (int j = t; j < X; j += WG) excl[j] *= up[(size_t)sib * Xp + j];
-        }
-        __syncthreads();
-        rescale(excl, X, scratch);
-        const bool v_on_axis0 = pl.pav[2 * p] == v;
-        contract(p, v_on_axis0, excl);
-        const int er = rescale(raw, X, scratch);
+        if (G.pl.consts[4 * i] == MLBP_CUTSET_CONST_PAIR)        // a factor inside the cutset: its cell gains Z_c
+          pacc[(size_t)G.pl.consts[4 * i + 1] * XX + (size_t)G.st[G.pl.consts[4 * i + 2]] * X + G.st[G.pl.consts[4 * i + 3]]] += w;
+    generic_down<SumAlg>(
+        G,
         // the forest factor's rank-1 update: a = bv (v's vector on the way up), b = excl, a^T T~ b = 2^er sum_i a[i] raw[i]
-        double s = 0.0;
-        for (int j = t; j < X; j += WG) s += bv[j] * raw[j];
-        const double coef = ldexp(w / block_sum(s, scratch), -er);
-        const double* v0 = v_on_axis0 ? bv : excl;
-        const double* v1 = v_on_axis0 ? excl : bv;
-        double* A = pacc + (size_t)p * XX;
-        for (int r = 0; r < X; ++r) {
-          const double ar = coef * v0[r];
-          for (int j = t; j < X; j += WG) A[(size_t)r * X + j] = fma(ar, v1[j], A[(size_t)r * X + j]);
-        }
-        __syncthreads();
-        for (int j = t; j < X; j += WG) {
-          dn[(size_t)v * Xp + j] = raw[j];
-          bv[j] *= raw[j];
-        }
-      }
-      double s = 0.0;
-      for (int j = t; j < X; j += WG) s += bv[j];
-      s = block_sum(s, scratch);
-      for (int j = t; j < X; j += WG) {
-        const double wm = w * (bv[j] / s);
-        acc[(size_t)v * Xp + j] += wm;
-        for (int it = pl.item_off[v]; it < pl.item_off[v + 1]; ++it)       // row s_q of every cutset-incident factor, [s_q][state of v]
-          if (pl.items[3 * it] != MLBP_CUTSET_ITEM_UNARY)
-            pacc[(size_t)pl.items[3 * it + 1] * XX + (size_t)st[pl.items[3 * it + 2]] * X + j] += wm;
-      }
-      __syncthreads();
-    }
+        [&](int p, bool v_on_axis0, const double* bv, const double* excl, int er) {
+          double s = 0.0;
+          for (int j = t; j < X; j += WG) s += bv[j] * G.raw[j];
+          const double coef = ldexp(w / block_sum(s, G.scratch), -er);
+          const double* v0 = v_on_axis0 ? bv : excl;
+          const double* v1 = v_on_axis0 ? excl : bv;
+          double* A = pacc + (size_t)p * XX;
+          for (int r = 0; r < X; ++r) {
+            const double ar = coef * v0[r];
+            for (int j = t; j < X; j += WG) A[(size_t)r * X + j] = fma(ar, v1[j], A[(size_t)r * X + j]);
+          }
+          __syncthreads();                                     // every thread has read all of bv before its entries change
+        },
+        [&](int v, int j, double x) {
+          const double wm = w * x;
+          acc[(size_t)v * Xp + j] += wm;
+          for (int it = G.pl.item_off[v]; it < G.pl.item_off[v + 1]; ++it)       // row s_q of every cutset-incident factor, [s_q][state of v]
+            if (G.pl.items[3 * it] != MLBP_CUTSET_ITEM_UNARY)
+              pacc[(size_t)G.pl.items[3 * it + 1] * XX + (size_t)G.st[G.pl.items[3 * it + 2]] * X + j] += wm;
+        });
   }
 
   __syncthreads();
@@ -273,29 +101,11 @@ __global__ __launch_bounds__(WG) void exactgrad_generic_kernel(GradDev d) {
     out[1] = (double)sum.e;
   }
   if (sum.e == EMPTY) return;
-  for (int v = 0; v < n_vars; ++v)
+  for (int v = 0; v < d.n_vars; ++v)
     for (int j = t; j < X; j += WG) out[2 + (size_t)v * X + j] = acc[(size_t)v * Xp + j];
 }
 
 // ---- X = 64: a wave per configuration ---------------------------------------------------------------------
-constexpr int ROW = 65;                     // padded row of an LDS table
-
-// The contraction of the padded LDS table with the wave's vector (m: the entry of this lane): lane i returns
-// sum_j T[i][j] m[j] (tm) or sum_i m[i] T[i][lane].  Four chains of 16 FMAs, added pairwise.
-__device__ __forceinline__ double wave_contract_x64(const double* table, bool tm, double m, int lane) {
-  double a[4] = {0.0, 0.0, 0.0, 0.0};
-  if (tm) {
-    const double* row = table + lane * ROW;
-#pragma unroll
-    for (int j = 0; j < 64; ++j) a[j & 3] = fma(row[j], read_lane(m, j), a[j & 3]);
-  } else {
-    const double* col = table + lane;
-#pragma unroll
-    for (int i = 0; i < 64; ++i) a[i & 3] = fma(read_lane(m, i), col[i * ROW], a[i & 3]);
-  }
-  return (a[0] + a[1]) + (a[2] + a[3]);
-}
-
 // R[i] += v0[i] * v1[lane]: the rank-1 update of a 64 x 64 accumulator held as 64 registers per lane (lane = column).
 __device__ __forceinline__ void rank1_x64(double (&R)[64], double v0, double v1) {
 #pragma unroll
@@ -305,113 +115,29 @@ __device__ __forceinline__ void rank1_x64(double (&R)[64], double v0, double v1)
 template <int NF>
 __global__ __launch_bounds__(WG) void exactgrad_x64_kernel(GradDev d) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int X = 64;
-    const int g = blockIdx.x, k = blockIdx.y, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int g = blockIdx.x, k = blockIdx.y, t = threadIdx.x, lane = t & 63, wave = t >> 6;
   if (!tables_in_range(d.pair_tab, d.P, d.n_pair_tables, d.unary_tab, d.U, d.n_unary_tables, g)) return;
-  PlanSections<const_i32p> pl;
-  carve_plan(as_const(d.plan), d.n_vars, d.P, d.U, d.n_cut, d.n_free, d.n_items, d.n_consts, pl);
-  const const_i32p ptab = as_const(d.pair_tab) + (size_t)g * d.P, utab = as_const(d.unary_tab) + (size_t)g * d.U;
-  const int n_vars = d.n_vars, P = d.P, U = d.U, n_free = d.n_free, n_cut = d.n_cut;
-
-  // LDS: [forest tables, rows of 65] [base] [4 waves x (acc, phi, bel, up, dn)] [scratch] [table exponents]
-  double* tabs = reinterpret_cast<double*>(smem);
-  double* base = tabs + (size_t)d.n_forest * 64 * ROW;         // [n_vars][64] the product of a variable's unary rows
-  const size_t vs = (size_t)n_vars * 64;
-  double* acc = base + vs + (size_t)wave * 5 * vs;             // this wave's: sum over its configurations of Z_c m_c, mantissas
-  double* phi = acc + vs;                                      // a free variable's own factors under the configuration
-  double* bel = phi + vs;                                      // its vector on the way up
-  double* up = bel + vs;                                       // its message to its parent
-  double* dn = up + vs;                                        // its parent's message to it
-  double* scratch = base + vs + 20 * vs;
-  int* texp = reinterpret_cast<int*>(scratch + 8);
+  X64 W;
+  x64_open(W, d, g, smem);
+  const int n_vars = d.n_vars, P = d.P;
+  double* acc = W.acc;                                         // this wave's: sum over its configurations of Z_c m_c, mantissas
   double* out = d.partials + ((size_t)g * d.parts + 4 * k + wave) * d.stride;
-  double* pacc = out + 2 + vs;                                 // [P][64][64] this wave's pair accumulators in its partial
-
-  for (int f = 0; f < P + U; ++f) {
-    const double* T = f < P ? d.pair_tables + (size_t)ptab[f] * 4096 : d.unary_tables + (size_t)utab[f - P] * 64;
-    const int n = f < P ? 4096 : 64;
-    double m = 0.0;
-    for (int i = t; i < n; i += WG) m = fmax(m, T[i]);
-    m = block_max(m, scratch);
-    if (t == 0) texp[f] = exp_of(m);
-  }
-  __syncthreads();
-  int e_fixed = 0;                                             // every factor enters every configuration once
-  for (int f = 0; f < P + U; ++f) e_fixed += texp[f];
-  for (int p = 0; p < P; ++p) {
-    const int s = pl.fslot[p];
-    if (s < 0) continue;
-    const double* T = d.pair_tables + (size_t)ptab[p] * 4096;
-    const int te = texp[p];
-    for (int i = t; i < 4096; i += WG) tabs[(size_t)s * 64 * ROW + (i >> 6) * ROW + (i & 63)] = ldexp(T[i], -te);
-  }
-  for (int v = 0; v < n_vars; ++v) {                           // the unary rows of every variable, free or cut, multiplied once
-    if (t < 64) {
-      double b = 1.0;
-      for (int u = 0; u < U; ++u)
-        if (pl.uvar[u] == v) b *= ldexp(d.unary_tables[(size_t)utab[u] * 64 + t], -texp[P + u]);
-      base[(size_t)v * 64 + t] = b;
-    }
-    __syncthreads();
-    e_fixed += rescale(base + (size_t)v * 64, X, scratch);
-  }
+  double* pacc = out + 2 + (size_t)n_vars * 64;                // [P][64][64] this wave's pair accumulators in its partial
   for (int v = 0; v < n_vars; ++v) acc[(size_t)v * 64 + lane] = 0.0;
   double R[NF][64];                                            // the forest factors' accumulators, [row][lane = column] in table axes
 #pragma unroll
   for (int s = 0; s < NF; ++s)
 #pragma unroll
     for (int i = 0; i < 64; ++i) R[s][i] = 0.0;
-  __syncthreads();                                             // the tables and base are read by every wave from here on
-
-  auto state = [&](int q, int c) { return (c >> (6 * q)) & 63; };
-  auto local = [&](int v, int c) {
-    double b = base[(size_t)v * 64 + lane];
-    for (int it = pl.item_off[v]; it < pl.item_off[v + 1]; ++it) {
-      const int kind = pl.items[3 * it];
-      if (kind == MLBP_CUTSET_ITEM_UNARY) continue;
-      const int p = pl.items[3 * it + 1], s = state(pl.items[3 * it + 2], c);
-      const double* T = d.pair_tables + (size_t)ptab[p] * 4096;
-      b *= ldexp(kind == MLBP_CUTSET_ITEM_COL ? T[lane * 64 + s] : T[s * 64 + lane], -texp[p]);
-    }
-    return b;
-  };
 
   Scaled sum = {0.0, EMPTY};                                   // sum of Z_c over this wave's configurations
   for (int c = 4 * k + wave; c < d.n_configs; c += 4 * d.chunks) {
-    Scaled z = {1.0, e_fixed};
-    for (int q = 0; q < n_cut; ++q) mul(z, base[(size_t)pl.cutset[q] * 64 + state(q, c)]);
-    for (int i = 0; i < d.n_consts; ++i) {
-      if (pl.consts[4 * i] != MLBP_CUTSET_CONST_PAIR) continue;
-      const int f = pl.consts[4 * i + 1], s0 = state(pl.consts[4 * i + 2], c), s1 = state(pl.consts[4 * i + 3], c);
-      mul(z, ldexp(d.pair_tables[(size_t)ptab[f] * 4096 + s0 * 64 + s1], -texp[f]));
-    }
-    for (int i = 0; i < n_free; ++i) {
-      const int v = pl.order[i];
-      bel[(size_t)v * 64 + lane] = phi[(size_t)v * 64 + lane] = local(v, c);
-    }
-    // leaves to roots
-    for (int i = 0; i < n_free; ++i) {
-      const int v = pl.order[i], p = pl.parent[2 * v];
-      const double x = wave_rescale(bel[(size_t)v * 64 + lane], z.e);
-      bel[(size_t)v * 64 + lane] = x;
-      if (p < 0) {
-        mul(z, wave_sum(x));
-      } else {
-        const int par = pl.parent[2 * v + 1];
-        const double r = wave_rescale(wave_contract_x64(tabs + (size_t)pl.fslot[p] * 64 * ROW, pl.pav[2 * p] != v, x, lane), z.e);
-        up[(size_t)v * 64 + lane] = r;
-        bel[(size_t)par * 64 + lane] *= r;
-      }
-    }
-    if (z.m == 0.0) continue;                                  // Z_c = 0: nothing to add
-
-    // Z_c joins the wave's sum: the larger exponent is kept; the first Z_c clears the accumulators in the partial
-    if (z.e > sum.e) {
-      const bool first = sum.e == EMPTY;
-      const int shift = max(sum.e - z.e, MIN_SHIFT);
+    const Scaled z = x64_up<SumAlg, true>(W, c);
+    if (SumAlg::dead(z)) continue;                             // Z_c = 0: nothing to add
+    const double w = join_sum(sum, z, [&](int shift, bool first) {           // the first Z_c clears the accumulators in the partial
       for (int v = 0; v < n_vars; ++v) acc[(size_t)v * 64 + lane] = ldexp(acc[(size_t)v * 64 + lane], shift);
       for (int p = 0; p < P; ++p) {
-        if (pl.fslot[p] >= 0) continue;
+        if (W.pl.fslot[p] >= 0) continue;
         double* A = pacc + (size_t)p * 4096;
         for (int i = lane; i < 4096; i += 64) A[i] = first ? 0.0 : ldexp(A[i], shift);
       }
@@ -419,53 +145,28 @@ __global__ __launch_bounds__(WG) void exactgrad_x64_kernel(GradDev d) {
       for (int s = 0; s < NF; ++s)
 #pragma unroll
         for (int i = 0; i < 64; ++i) R[s][i] = ldexp(R[s][i], shift);
-      sum.m = ldexp(sum.m, shift);
-      sum.e = z.e;
-    }
-    const double w = ldexp(z.m, max(z.e - sum.e, MIN_SHIFT));
-    sum.m += w;
-    for (int q = 0; q < n_cut; ++q)
-      if (lane == state(q, c)) acc[(size_t)pl.cutset[q] * 64 + lane] += w;
+    });
+    for (int q = 0; q < d.n_cut; ++q)
+      if (lane == x64_state(q, c)) acc[(size_t)W.pl.cutset[q] * 64 + lane] += w;
     for (int i = 0; i < d.n_consts; ++i) {                     // a factor inside the cutset: its cell gains Z_c
-      if (pl.consts[4 * i] != MLBP_CUTSET_CONST_PAIR) continue;
-      const int s0 = state(pl.consts[4 * i + 2], c), s1 = state(pl.consts[4 * i + 3], c);
-      if (lane == s1) pacc[(size_t)pl.consts[4 * i + 1] * 4096 + s0 * 64 + lane] += w;
+      if (W.pl.consts[4 * i] != MLBP_CUTSET_CONST_PAIR) continue;
+      const int s0 = x64_state(W.pl.consts[4 * i + 2], c), s1 = x64_state(W.pl.consts[4 * i + 3], c);
+      if (lane == s1) pacc[(size_t)W.pl.consts[4 * i + 1] * 4096 + s0 * 64 + lane] += w;
     }
-
-    // roots to leaves
-    for (int i = n_free - 1; i >= 0; --i) {
-      const int v = pl.order[i], p = pl.parent[2 * v];
-      double x = bel[(size_t)v * 64 + lane];
-      if (p >= 0) {
-        const int par = pl.parent[2 * v + 1];
-        double b = phi[(size_t)par * 64 + lane];
-        if (pl.parent[2 * par] >= 0) b *= dn[(size_t)par * 64 + lane];
-        for (int q = 0; q < n_free; ++q) {                     // the parent's other children
-          const int sib = pl.order[q];
-          if (sib != v && pl.parent[2 * sib + 1] == par) b *= up[(size_t)sib * 64 + lane];
-        }
-        int unused = 0, er = 0;
-        b = wave_rescale(b, unused);
-        const bool v_on_axis0 = pl.pav[2 * p] == v;
-        const int slot = pl.fslot[p];
-        const double r = wave_rescale(wave_contract_x64(tabs + (size_t)slot * 64 * ROW, v_on_axis0, b, lane), er);
-        dn[(size_t)v * 64 + lane] = r;
-        const double a = x;                                    // v's vector on the way up
-        x *= r;
-        const double total = wave_sum(x);                      // a^T T~ b = 2^er total
-        const double coef = ldexp(w / total, -er);
-        const double v0 = v_on_axis0 ? a : b, v1 = coef * (v_on_axis0 ? b : a);
-        if (slot == 0) rank1_x64(R[0], v0, v1);
-        else if (NF > 1 && slot == 1) rank1_x64(R[NF - 1], v0, v1);
-        x /= total;
-      } else {
-        x /= wave_sum(x);
+    for (int i = W.n_free - 1; i >= 0; --i) {
+      const X64Down s = x64_down_step<SumAlg, true>(W, i);
+      if (s.p >= 0) {                                          // the forest factor's rank-1 update
+        const double coef = ldexp(w / s.total, -s.er);
+        const double v0 = s.v_on_axis0 ? s.a : s.b, v1 = coef * (s.v_on_axis0 ? s.b : s.a);
+#pragma unroll
+        for (int f = 0; f < NF; ++f)                           // R is indexed by constants alone: it stays in registers
+          if (s.slot == f) rank1_x64(R[f], v0, v1);
       }
-      const double wm = w * x;
-      acc[(size_t)v * 64 + lane] += wm;
-      for (int it = pl.item_off[v]; it < pl.item_off[v + 1]; ++it)       // row s_q of every cutset-incident factor, [s_q][state of v]
-        if (pl.items[3 * it] != MLBP_CUTSET_ITEM_UNARY)
-          pacc[(size_t)pl.items[3 * it + 1] * 4096 + state(pl.items[3 * it + 2], c) * 64 + lane] += wm;
+      const double wm = w * s.x;
+      acc[(size_t)s.v * 64 + lane] += wm;
+      for (int it = W.pl.item_off[s.v]; it < W.pl.item_off[s.v + 1]; ++it)   // row s_q of every cutset-incident factor, [s_q][state of v]
+        if (W.pl.items[3 * it] != MLBP_CUTSET_ITEM_UNARY)
+          pacc[(size_t)W.pl.items[3 * it + 1] * 4096 + x64_state(W.pl.items[3 * it + 2], c) * 64 + lane] += wm;
     }
   }
 
@@ -476,16 +177,15 @@ __global__ __launch_bounds__(WG) void exactgrad_x64_kernel(GradDev d) {
   if (sum.e == EMPTY) return;                                  // an empty partial holds nothing else
   for (int v = 0; v < n_vars; ++v) out[2 + (size_t)v * 64 + lane] = acc[(size_t)v * 64 + lane];
   for (int p = 0; p < P; ++p) {
-    const int slot = pl.fslot[p];
+    const int slot = W.pl.fslot[p];
     if (slot < 0) continue;
     double* A = pacc + (size_t)p * 4096 + lane;
-    if (slot == 0) {
 #pragma unroll
-      for (int i = 0; i < 64; ++i) A[i * 64] = R[0][i];
-    } else if (NF > 1 && slot == 1) {
+    for (int f = 0; f < NF; ++f)
+      if (slot == f) {
 #pragma unroll
-      for (int i = 0; i < 64; ++i) A[i * 64] = R[NF - 1][i];
-    }
+        for (int i = 0; i < 64; ++i) A[i * 64] = R[f][i];
+      }
   }
 }
 
@@ -515,20 +215,10 @@ __global__ __launch_bounds__(WG) void exactgrad_combine_kernel(GradDev d) {
   PlanSections<const_i32p> pl;
   carve_plan(as_const(d.plan), d.n_vars, P, U, d.n_cut, d.n_free, d.n_items, d.n_consts, pl);
   const size_t XX = (size_t)X * X, stride = (size_t)d.stride;
-  const double* ws = d.partials + (size_t)g * d.parts * stride;
-  int emax = EMPTY;
-  for (int k = 0; k < d.parts; ++k) emax = max(emax, (int)ws[k * stride + 1]);
-  double Z = 0.0;
-  for (int k = 0; k < d.parts; ++k) Z += ldexp(ws[k * stride], max((int)ws[k * stride + 1] - emax, MIN_SHIFT));
+  const SumParts parts = read_sum_parts(d.partials + (size_t)g * d.parts * stride, stride, d.parts);
+  const double Z = parts.Z;
   // entry `at` of the partials (behind the two header words), summed in index order; an empty partial holds nothing
-  auto summed = [&](size_t at) {
-    double s = 0.0;
-    for (int k = 0; k < d.parts; ++k) {
-      const int e = (int)ws[k * stride + 1];
-      if (e != EMPTY) s += ldexp(ws[k * stride + 2 + at], max(e - emax, MIN_SHIFT));
-    }
-    return s;
-  };
+  auto summed = [&](size_t at) { return mlbp_graph::summed<true>(parts, at); };
   const size_t N = (size_t)d.n_vars * X;
   const double uniform = 1.0 / (double)X;
   if (d.marginals)
@@ -639,7 +329,7 @@ __global__ __launch_bounds__(WG) void exactgrad_combine_kernel(GradDev d) {
       }
     }
   }
-  d.log_z[g] = Z == 0.0 ? -__builtin_huge_val() : fma((double)emax, 0.693147180559945309417232121458, log(Z));
+  d.log_z[g] = Z == 0.0 ? -__builtin_huge_val() : fma((double)parts.emax, 0.693147180559945309417232121458, log(Z));
   for (int f = 0; f < F_ee; ++f) {
     if (d.expect_ee) d.expect_ee[(size_t)g * F_ee + f] = ex_ee[f];
     if (d.grad_ee) d.grad_ee[(size_t)g * F_ee + f] = bad ? nan : ob_ee[f] - ex_ee[f];
@@ -652,13 +342,7 @@ __global__ __launch_bounds__(WG) void exactgrad_combine_kernel(GradDev d) {
 
 // ---- host ----------------------------------------------------------------------------------------
 thread_local int g_last_kernel = MLBP_EXACTGRAD_KERNEL_NONE;
-
-int64_t ints_bytes(int64_t P, int64_t U) { return 4 * ((P + U + 16 + 3) / 4 * 4); }
-int64_t vector_doubles(int64_t n_vars, int64_t X) { return (5 * n_vars + 2) * ((X + 1) / 2 * 2); }
-int64_t x64_lds_bytes(int64_t n_vars, int64_t P, int64_t U, int64_t n_forest) {
-  return n_forest * 33280 + 21 * n_vars * 512 + 64 + ints_bytes(P, U);
-}
-int64_t generic_lds_bytes(int64_t n_vars, int64_t P, int64_t U, int64_t X) { return vector_doubles(n_vars, X) * 8 + 64 + ints_bytes(P, U); }
+static_assert(MLBP_EXACTGRAD_KERNEL_X64 == WALK_X64 && MLBP_EXACTGRAD_KERNEL_GENERIC == WALK_GENERIC, "the shared host core numbers the kernels");
 
 }  // namespace
 
@@ -669,22 +353,13 @@ const char* mlbp_exactgrad_last_error(void) { return g_last_error.c_str(); }
 int mlbp_exactgrad_last_kernel(void) { return g_last_kernel; }
 
 int mlbp_exactgrad_pick_kernel(int32_t X, int32_t n_vars, int32_t P, int32_t U, int32_t n_forest) {
-  if (X < 2 || n_vars <= 0 || P < 0 || U < 0 || n_forest < 0 || n_forest > P)
-    return fail(MLBP_EINVAL, "pick_kernel: X = %d, n_vars = %d, P = %d, U = %d, n_forest = %d", X, n_vars, P, U, n_forest);
-  if (X > MLBP_CUTSET_MAX_X) return fail(MLBP_EUNSUPPORTED, "X = %d: at most %d states are supported", X, MLBP_CUTSET_MAX_X);
-  if (X == 64 && n_forest <= MLBP_EXACTGRAD_X64_MAX_FOREST && x64_lds_bytes(n_vars, P, U, n_forest) <= MLBP_CUTSET_X64_LDS_BYTES)
-    return MLBP_EXACTGRAD_KERNEL_X64;
-  if (64 + ints_bytes(P, U) > MLBP_CUTSET_GENERIC_LDS_BYTES)
-    return fail(MLBP_EUNSUPPORTED, "P + U = %lld factors: their exponents do not fit the LDS budget", (long long)P + U);
-  return MLBP_EXACTGRAD_KERNEL_GENERIC;
+  return pick_walk_kernel(X, n_vars, P, U, n_forest, MLBP_EXACTGRAD_X64_MAX_FOREST);
 }
 
 int mlbp_exactgrad_chunks(int32_t B, int32_t n_configs, int32_t kernel) {
   if (B <= 0 || n_configs <= 0 || (kernel != MLBP_EXACTGRAD_KERNEL_X64 && kernel != MLBP_EXACTGRAD_KERNEL_GENERIC))
     return fail(MLBP_EINVAL, "chunks: B = %d, n_configs = %d, kernel = %d", B, n_configs, kernel);
-  const int32_t walkers = kernel == MLBP_EXACTGRAD_KERNEL_X64 ? (n_configs + 3) / 4 : n_configs;
-  const int32_t spread = (MLBP_EXACTGRAD_MIN_WORKGROUPS + B - 1) / B;
-  return walkers < spread ? walkers : spread;
+  return walk_chunks(B, kernel == MLBP_EXACTGRAD_KERNEL_X64 ? (n_configs + 3) / 4 : n_configs, MLBP_EXACTGRAD_MIN_WORKGROUPS);
 }
 
 int64_t mlbp_exactgrad_workspace_bytes(int32_t B, int32_t X, int32_t n_vars, int32_t P, int32_t U, int32_t n_forest, int32_t n_cut) {
@@ -695,30 +370,18 @@ int64_t mlbp_exactgrad_workspace_bytes(int32_t B, int32_t X, int32_t n_vars, int
   if (n_configs < 0) return too_many_configs(X, n_cut);
   const int chunks = mlbp_exactgrad_chunks(B, (int32_t)n_configs, which);
   if (chunks < 0) return chunks;
-  int64_t per = 2 + (int64_t)n_vars * X + (int64_t)P * X * X;
-  if (which == MLBP_EXACTGRAD_KERNEL_X64) per *= 4;            // a partial per wave
-  else if (generic_lds_bytes(n_vars, P, U, X) > MLBP_CUTSET_GENERIC_LDS_BYTES) per += vector_doubles(n_vars, X);
-  return (int64_t)B * chunks * per * 8;
+  return (int64_t)B * chunks * chunk_doubles(which, 2 + (int64_t)n_vars * X + (int64_t)P * X * X, n_vars, P, U, X) * 8;
 }
 
 int mlbp_exactgrad_check_plan(const int32_t* plan, int32_t n_words, int32_t X) { return check_packed_plan(plan, n_words, X); }
 
 int mlbp_exactgrad_f64(const mlbp_exactgrad_args* a, void* stream) {
   g_last_kernel = MLBP_EXACTGRAD_KERNEL_NONE;
-  if (!a) return fail(MLBP_EINVAL, "args is NULL");
-  if (a->B <= 0 || a->n_vars <= 0 || a->P < 0 || a->U < 0 || a->P + a->U <= 0 || a->n_cut < 0 || a->n_free < 0 || a->n_items < 0 ||
-      a->n_consts < 0 || (int64_t)a->n_cut + a->n_free != a->n_vars)
-    return fail(MLBP_EINVAL, "bad sizes: B %d, n_vars %d, P %d, U %d, n_cut %d, n_free %d, n_items %d, n_consts %d", a->B, a->n_vars, a->P,
-                a->U, a->n_cut, a->n_free, a->n_items, a->n_consts);
-  if (int e = check_states(a->X)) return e;
-  const int which = mlbp_exactgrad_pick_kernel(a->X, a->n_vars, a->P, a->U, a->n_forest);
-  if (which < 0) return which;
-  if (!a->plan || plan_words(a->n_vars, a->P, a->U, a->n_cut, a->n_free, a->n_items, a->n_consts) != a->plan_words)
-    return fail(MLBP_EINVAL, "plan is NULL or plan_words = %d disagrees with the sizes", a->plan_words);
-  if (int e = check_args_tables(a)) return e;
-  if (!a->log_z) return fail(MLBP_EINVAL, "log_z is NULL");
-  const bool want_grad = a->grad_ee || a->grad_ed, want_expect = want_grad || a->expect_ee || a->expect_ed;
-  if (want_expect) {
+  int64_t n_configs = 0;
+  const int which = check_walk_args(a, mlbp_exactgrad_pick_kernel, [](const mlbp_exactgrad_args* a) {
+    if (!a->log_z) return fail(MLBP_EINVAL, "log_z is NULL");
+    const bool want_grad = a->grad_ee || a->grad_ed;
+    if (!want_grad && !a->expect_ee && !a->expect_ed) return (int)MLBP_OK;
     if (!a->phi_en_en || !a->phi_en_en_w1 || !a->phi_en_de || a->F_ee < 1 || a->F_ed < 1 || a->Vde < 1 || (a->P > 0 && !a->pair_phi) ||
         (a->U > 0 && (!a->unary_kind || !a->unary_obs)))
       return fail(MLBP_EINVAL, "expect_* and grad_* need the feature inputs: phi_en_en, phi_en_en_w1, phi_en_de, pair_phi, unary_kind, unary_obs "
@@ -726,30 +389,21 @@ int mlbp_exactgrad_f64(const mlbp_exactgrad_args* a, void* stream) {
     if (a->F_ee > MAXF || a->F_ed > MAXF)
       return fail(MLBP_EUNSUPPORTED, "F_ee = %d, F_ed = %d: at most %d features each are supported", a->F_ee, a->F_ed, MAXF);
     if (want_grad && !a->labels) return fail(MLBP_EINVAL, "grad_* needs labels");
-  }
-  const int64_t n_configs = count_configs(a->X, a->n_cut);
-  if (n_configs < 0) return too_many_configs(a->X, a->n_cut);
+    return (int)MLBP_OK;
+  }, &n_configs);
+  if (which < 0) return which;
   const int chunks = mlbp_exactgrad_chunks(a->B, (int32_t)n_configs, which);
   if (chunks < 0) return chunks;
-  if ((int64_t)a->n_vars * a->X > 0x7fffffff / 16) return fail(MLBP_EUNSUPPORTED, "n_vars * X = %lld too large", (long long)a->n_vars * a->X);
-  const int64_t need = mlbp_exactgrad_workspace_bytes(a->B, a->X, a->n_vars, a->P, a->U, a->n_forest, a->n_cut);
-  if (need < 0) return (int)need;
-  if (!a->workspace || a->workspace_bytes < need)
-    return fail(MLBP_EINVAL, "workspace is NULL or workspace_bytes = %lld below the %lld the call needs", (long long)a->workspace_bytes, (long long)need);
+  if (int e = check_walk_workspace(a, mlbp_exactgrad_workspace_bytes(a->B, a->X, a->n_vars, a->P, a->U, a->n_forest, a->n_cut))) return e;
   if (int e = check_device("libmlbp_exactgrad.so")) return e;
+  const bool want_expect = a->grad_ee || a->grad_ed || a->expect_ee || a->expect_ed;
   GradDev d;
-  d.plan = a->plan;
-  d.pair_tables = a->pair_tables; d.pair_tab = a->pair_tab; d.unary_tables = a->unary_tables; d.unary_tab = a->unary_tab;
+  fill_walk_dev(d, a, n_configs, chunks, which);
   d.phi_en_en = a->phi_en_en; d.phi_en_en_w1 = a->phi_en_en_w1; d.phi_en_de = a->phi_en_de;
   d.pair_phi = a->pair_phi; d.unary_kind = a->unary_kind; d.unary_obs = a->unary_obs; d.labels = a->labels;
-  d.partials = a->workspace;
-  d.vectors = nullptr;
   d.log_z = a->log_z; d.marginals = a->marginals; d.pair_marginals = a->pair_marginals;
   d.expect_ee = a->expect_ee; d.expect_ed = a->expect_ed; d.grad_ee = a->grad_ee; d.grad_ed = a->grad_ed;
   d.stride = 2 + (int64_t)a->n_vars * a->X + (int64_t)a->P * a->X * a->X;
-  d.B = a->B; d.X = a->X; d.n_vars = a->n_vars; d.P = a->P; d.U = a->U; d.n_cut = a->n_cut; d.n_free = a->n_free; d.n_items = a->n_items;
-  d.n_consts = a->n_consts; d.n_forest = a->n_forest; d.n_pair_tables = a->n_pair_tables; d.n_unary_tables = a->n_unary_tables;
-  d.n_configs = (int32_t)n_configs; d.chunks = chunks; d.parts = which == MLBP_EXACTGRAD_KERNEL_X64 ? 4 * chunks : chunks;
   d.F_ee = want_expect ? a->F_ee : 0; d.F_ed = want_expect ? a->F_ed : 0; d.Vde = a->Vde;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(a->B, chunks);
@@ -764,18 +418,12 @@ int mlbp_exactgrad_f64(const mlbp_exactgrad_args* a, void* stream) {
       hipLaunchKernelGGL(exactgrad_x64_kernel<2>, grid, dim3(WG), lds, st, d);
     }
   } else {
-    int64_t lds = generic_lds_bytes(a->n_vars, a->P, a->U, a->X);
-    if (lds > MLBP_CUTSET_GENERIC_LDS_BYTES) {
-      d.vectors = a->workspace + (int64_t)a->B * chunks * d.stride;
-      lds = 64 + ints_bytes(a->P, a->U);
-    }
-    hipLaunchKernelGGL(exactgrad_generic_kernel, grid, dim3(WG), (size_t)lds, st, d);
+    const size_t lds = generic_walk_lds(d, a->workspace + (int64_t)a->B * chunks * d.stride);
+    hipLaunchKernelGGL(exactgrad_generic_kernel, grid, dim3(WG), lds, st, d);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(MLBP_EHIP, "exactgrad launch failed: %s", hipGetErrorString(e));
+  if (int e = launched("exactgrad")) return e;
   hipLaunchKernelGGL(exactgrad_combine_kernel, dim3(a->B), dim3(WG), 0, st, d);
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail(MLBP_EHIP, "combine launch failed: %s", hipGetErrorString(e));
+  if (int e = launched("combine")) return e;
   g_last_kernel = which;
   return MLBP_OK;
 }

@@ -8,6 +8,7 @@ plan the header describes -- elimination order, parent links, the cutset-inciden
 and `plan(topo, cutset, X, device)` has the library validate it on the host, uploads it once and caches the device copy.
 """
 import ctypes as C
+import sys
 
 import numpy as np
 
@@ -170,10 +171,15 @@ def plan_words(topo, cutset):
     return np.array(words, dtype=np.int32)
 
 
-class Plan:
-    """A validated plan and its device copy."""
+def check_plan(words, X):
+    """Raises CutsetError unless the packed plan `words` is valid for X states."""
+    check(lib.mlbp_cutset_check_plan(_ffi.i32ptr(words), len(words), int(X)))
 
-    def __init__(self, topo, cutset, X, device):
+
+class Plan:
+    """A validated plan and its device copy.  binding: the module (this one, exactmap or exactgrad) whose check_plan validates."""
+
+    def __init__(self, topo, cutset, X, device, binding=None):
         import torch
         seen = set()
         for v in cutset:
@@ -181,7 +187,7 @@ class Plan:
                 raise ValueError('cutset names variable index %r twice or out of range' % (v,))
             seen.add(int(v))
         self.words = plan_words(topo, cutset)
-        check(lib.mlbp_cutset_check_plan(_ffi.i32ptr(self.words), len(self.words), int(X)))
+        (binding or sys.modules[__name__]).check_plan(self.words, X)
         (self.n_vars, self.P, self.U, self.n_cut, self.n_free, self.n_items, self.n_consts, self.n_forest) = (int(w) for w in self.words[:8])
         self.n_configs = int(X) ** self.n_cut
         self.dev = torch.from_numpy(self.words).to(device) if device is not None else None
@@ -190,7 +196,8 @@ class Plan:
 _plans = _sidelib.Cache()
 
 
-def plan(topo, cutset, X, device):
-    """The cached Plan of (topology, cutset, X, device); cutset None: choose(topo)."""
+def plan(topo, cutset, X, device, binding=None):
+    """The cached Plan of (topology, cutset, X, device, validating binding); cutset None: choose(topo)."""
     cutset = tuple(choose(topo) if cutset is None else (int(v) for v in cutset))
-    return _plans.get(topo, (cutset, int(X), str(device)), lambda: Plan(topo, cutset, X, device))
+    key = (cutset, int(X), str(device), (binding or sys.modules[__name__]).__name__)
+    return _plans.get(topo, key, lambda: Plan(topo, cutset, X, device, binding))

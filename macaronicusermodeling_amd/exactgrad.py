@@ -8,6 +8,7 @@ The call takes the packed plan of include/mlbp_cutset.h: `plan(topo, cutset, X, 
 cutset.plan_words, has THIS library validate it on the host, uploads it once and caches the device copy.
 """
 import ctypes as C
+import sys
 
 from . import _ffi, _sidelib
 from . import cutset as _cutset
@@ -66,27 +67,16 @@ def workspace_bytes(B, X, n_vars, P, U, n_forest, n_cut):
     return check(lib.mlbp_exactgrad_workspace_bytes(int(B), int(X), int(n_vars), int(P), int(U), int(n_forest), int(n_cut)))
 
 
-class Plan:
-    """A plan validated by this library and its device copy (the fields of cutset.Plan)."""
-
-    def __init__(self, topo, cutset, X, device):
-        import torch
-        seen = set()
-        for v in cutset:
-            if not 0 <= int(v) < topo.n_vars or int(v) in seen:
-                raise ValueError('cutset names variable index %r twice or out of range' % (v,))
-            seen.add(int(v))
-        self.words = _cutset.plan_words(topo, cutset)
-        check(lib.mlbp_exactgrad_check_plan(_ffi.i32ptr(self.words), len(self.words), int(X)))
-        (self.n_vars, self.P, self.U, self.n_cut, self.n_free, self.n_items, self.n_consts, self.n_forest) = (int(w) for w in self.words[:8])
-        self.n_configs = int(X) ** self.n_cut
-        self.dev = torch.from_numpy(self.words).to(device) if device is not None else None
+def check_plan(words, X):
+    """Raises ExactGradError unless the packed plan `words` is valid for X states."""
+    check(lib.mlbp_exactgrad_check_plan(_ffi.i32ptr(words), len(words), int(X)))
 
 
-_plans = _sidelib.Cache()
+def Plan(topo, cutset, X, device):
+    """A plan validated by this library and its device copy: cutset.Plan."""
+    return _cutset.Plan(topo, cutset, X, device, sys.modules[__name__])
 
 
 def plan(topo, cutset, X, device):
     """The cached Plan of (topology, cutset, X, device); cutset None: cutset.choose(topo)."""
-    cutset = tuple(_cutset.choose(topo) if cutset is None else (int(v) for v in cutset))
-    return _plans.get(topo, (cutset, int(X), str(device)), lambda: Plan(topo, cutset, X, device))
+    return _cutset.plan(topo, cutset, X, device, sys.modules[__name__])
