@@ -467,9 +467,9 @@ class FactorGraphBatch:
         V.check(V.lib.mlbp_converge_f64(C.byref(a), _stream_ptr(self.device)))
         return (rounds, residual, hist) if history else (rounds, residual)
 
-    # ---- what the three cutset-conditioning calls share -----------------------------------------------------
+    # ---- what the four cutset-conditioning calls share -----------------------------------------------------
     def _cutset_args(self, K, Args, cutset, refusal):
-        """(plan, args) of a call into binding K (cutset, exactmap, exactgrad): the cutset's variable ids translated, the plan
+        """(plan, args) of a call into binding K (cutset, exactmap, exactgrad, exactsample): the cutset's variable ids translated, the plan
         validated by K's library, and the sizes, plan and table fields of an Args() filled.  refusal: the message for pairwise
         tables that are not float64."""
         if self.pair_tables is not None and self.pair_tables.dtype != torch.float64:
@@ -567,6 +567,48 @@ class FactorGraphBatch:
         a.workspace, a.workspace_bytes = work.data_ptr(), need
         K.check(K.lib.mlbp_exactmap_f64(C.byref(a), _stream_ptr(self.device)))
         return (assignment, score) if max_marginals is None else (assignment, score, max_marginals)
+
+    # ---- whole assignments drawn from the model itself (include/mlbp_exactsample.h) ---------------------
+    def exact_sample(self, n_samples=1, seed=None, uniforms=None, cutset=None, log_z=False, score=False):
+        """Draws n_samples whole assignments per graph from the MODEL ITSELF by cutset conditioning -- what sample() does only
+        on a tree: draw the cutset's joint state with probability Z_c / Z, solve the conditioned forest by one pass up, draw
+        the free variables from the roots down.  Returns (samples int32 [S][B][n_vars] in GraphTopology.var_ids order, logp
+        float64 [S][B]) device tensors; logp is the true log-probability of the draw, score(x) - log Z, on loopy graphs too
+        -- it equals exact_inference(labels=samples[s])'s joint_logp.  log_z=True appends log Z [B], score=True the
+        log-potential of every draw [S][B], in that order.  Exactly one of `seed` and `uniforms`, as in sample(): uniforms is
+        a contiguous float64 [S][B][n_vars] device tensor of numbers in [0, 1) (entry 0 draws the cutset's state, entries
+        1 .. len(cutset)-1 are not read, the rest draw the free variables); seed means torch.rand((S, B, n_vars),
+        dtype=float64, device=..., generator=torch.Generator(device).manual_seed(seed)).  cutset: as in exact_inference.  A
+        graph whose Z is zero or not finite gets samples -1 and logp NaN.  self.msgs is neither read nor written."""
+        from . import exactsample as K
+        if (seed is None) == (uniforms is None):
+            raise ValueError('give exactly one of seed and uniforms')
+        topo, S = self.topo, int(n_samples)
+        if S <= 0:
+            raise ValueError('n_samples must be positive')
+        pl, a = self._cutset_args(K, K.ExactSampleArgs, cutset, 'exact_sample needs float64 pairwise tables')
+        if uniforms is None:
+            gen = torch.Generator(self.device).manual_seed(int(seed))
+            uniforms = torch.rand((S, self.B, topo.n_vars), dtype=torch.float64, device=self.device, generator=gen)
+        elif (not torch.is_tensor(uniforms) or uniforms.dtype != torch.float64 or uniforms.device != self.device
+              or tuple(uniforms.shape) != (S, self.B, topo.n_vars) or not uniforms.is_contiguous()):
+            raise ValueError('uniforms must be a contiguous float64 device tensor [n_samples][B][n_vars]')
+        a.S, a.uniforms = S, uniforms.data_ptr()
+        samples = torch.empty(S, self.B, topo.n_vars, dtype=torch.int32, device=self.device)
+        logp = torch.empty(S, self.B, dtype=torch.float64, device=self.device)
+        a.samples, a.logp = samples.data_ptr(), logp.data_ptr()
+        out = [samples, logp]
+        if log_z:
+            out.append(torch.empty(self.B, dtype=torch.float64, device=self.device))
+            a.log_z = out[-1].data_ptr()
+        if score:
+            out.append(torch.empty(S, self.B, dtype=torch.float64, device=self.device))
+            a.score = out[-1].data_ptr()
+        need = K.workspace_bytes(self.B, S, self.X, topo.n_vars, topo.P, topo.U, pl.n_forest, pl.n_cut)
+        work = torch.empty(need // 8, dtype=torch.float64, device=self.device)
+        a.workspace, a.workspace_bytes = work.data_ptr(), need
+        K.check(K.lib.mlbp_exactsample_f64(C.byref(a), _stream_ptr(self.device)))
+        return tuple(out)
 
     # ---- the exact pair marginals and the true gradient (include/mlbp_exactgrad.h) ---------------------
     def _exactgrad(self, cutset, marginals=None, pair_marginals=None, expect=None, grad=None, labels=None):

@@ -1,4 +1,4 @@
-"""Builds libmlbp.so, libmlbp_map.so, libmlbp_logz.so, libmlbp_sample.so, libmlbp_converge.so, libmlbp_cutset.so, libmlbp_exactmap.so and libmlbp_exactgrad.so (gfx950 only) in-tree with hipcc.  `python -m macaronicusermodeling_amd.build`.
+"""Builds libmlbp.so, libmlbp_map.so, libmlbp_logz.so, libmlbp_sample.so, libmlbp_converge.so, libmlbp_cutset.so, libmlbp_exactmap.so, libmlbp_exactgrad.so and libmlbp_exactsample.so (gfx950 only) in-tree with hipcc.  `python -m macaronicusermodeling_amd.build`.
 
 hipcc cross-compiles without a GPU, so this runs in the build container; the resulting .so is
 git-ignored but travels to the GPU box with the working-tree snapshot.
@@ -17,6 +17,7 @@ CSRC_CONVERGE = os.path.join(PKG, 'csrc_converge')
 CSRC_CUTSET = os.path.join(PKG, 'csrc_cutset')
 CSRC_EXACTMAP = os.path.join(PKG, 'csrc_exactmap')
 CSRC_EXACTGRAD = os.path.join(PKG, 'csrc_exactgrad')
+CSRC_EXACTSAMPLE = os.path.join(PKG, 'csrc_exactsample')
 LIB = os.path.join(PKG, 'libmlbp.so')
 LIB_MAP = os.path.join(PKG, 'libmlbp_map.so')
 LIB_LOGZ = os.path.join(PKG, 'libmlbp_logz.so')
@@ -25,6 +26,7 @@ LIB_CONVERGE = os.path.join(PKG, 'libmlbp_converge.so')
 LIB_CUTSET = os.path.join(PKG, 'libmlbp_cutset.so')
 LIB_EXACTMAP = os.path.join(PKG, 'libmlbp_exactmap.so')
 LIB_EXACTGRAD = os.path.join(PKG, 'libmlbp_exactgrad.so')
+LIB_EXACTSAMPLE = os.path.join(PKG, 'libmlbp_exactsample.so')
 SOURCES = ['mlbp_host.cpp', 'mlbp_compile.cpp', 'mlbp_compile_shared.cpp', 'mlbp_program.cpp', 'mlbp_dispatch.cpp', 'mlbp_sweep.hip', 'mlbp_lean.hip', 'mlbp_shared.hip', 'mlbp_gemm.hip', 'mlbp_prims.hip', 'mlbp_grad.hip']
 SOURCES_MAP = ['mlbp_map.hip']
 SOURCES_LOGZ = ['mlbp_logz.hip']
@@ -33,6 +35,7 @@ SOURCES_CONVERGE = ['mlbp_converge.hip']
 SOURCES_CUTSET = ['mlbp_cutset.hip']
 SOURCES_EXACTMAP = ['mlbp_exactmap.hip']
 SOURCES_EXACTGRAD = ['mlbp_exactgrad.hip']
+SOURCES_EXACTSAMPLE = ['mlbp_exactsample.hip']
 # csrc/ headers: the core library's, and what the side libraries share (mlbp_graph_device.h includes mlbp_device.h)
 HEADERS = ['mlbp_internal.h', 'mlbp_device.h']
 HEADERS_SIDE = ['mlbp_device.h', 'mlbp_graph_device.h', 'mlbp_graph_host.h', 'mlbp_cutset_plan.h', 'mlbp_cutset_walk.h']
@@ -47,6 +50,7 @@ LIBRARIES = [
     (CSRC_CUTSET, SOURCES_CUTSET, HEADERS_SIDE, 'mlbp_cutset.h', LIB_CUTSET),            # exact inference by cutset conditioning
     (CSRC_EXACTMAP, SOURCES_EXACTMAP, HEADERS_SIDE + ['../../include/mlbp_cutset.h'], 'mlbp_exactmap.h', LIB_EXACTMAP),   # exact MAP by cutset conditioning
     (CSRC_EXACTGRAD, SOURCES_EXACTGRAD, HEADERS_SIDE + ['../../include/mlbp_cutset.h'], 'mlbp_exactgrad.h', LIB_EXACTGRAD),   # exact pair marginals and gradient
+    (CSRC_EXACTSAMPLE, SOURCES_EXACTSAMPLE, HEADERS_SIDE + ['../../include/mlbp_cutset.h'], 'mlbp_exactsample.h', LIB_EXACTSAMPLE),   # exact posterior sampling
 ]
 FLAGS = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-fno-fast-math', '-Wall',
          '-Wno-unused-function']
@@ -77,8 +81,8 @@ def _build_one(hipcc, csrc, sources, headers, lib, force, verbose):
 
 
 def build(force=False, verbose=False):
-    """Builds the eight libraries; returns the path of libmlbp.so (the others lie beside it: LIB_MAP, LIB_LOGZ, LIB_SAMPLE,
-    LIB_CONVERGE, LIB_CUTSET, LIB_EXACTMAP, LIB_EXACTGRAD)."""
+    """Builds the nine libraries; returns the path of libmlbp.so (the others lie beside it: LIB_MAP, LIB_LOGZ, LIB_SAMPLE,
+    LIB_CONVERGE, LIB_CUTSET, LIB_EXACTMAP, LIB_EXACTGRAD, LIB_EXACTSAMPLE)."""
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     for csrc, sources, headers, public, lib in LIBRARIES:
         deps = [os.path.join(CSRC, h) for h in headers] + [os.path.join(INCLUDE, public)]

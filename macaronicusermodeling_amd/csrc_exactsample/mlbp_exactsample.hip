@@ -1,0 +1,441 @@
+// libmlbp_exactsample.so: whole assignments drawn from the model itself by cutset conditioning (include/mlbp_exactsample.h),
+// gfx950 only, float64.  The sum form of the walk of csrc/mlbp_cutset_walk.h without its pass back; this file holds what the
+// library does around it -- every Z_c kept apart, their scan, the draw of a configuration and of the free variables from the
+// roots down.
+//
+// Five kernels, three launches per call; the form of the first and the third is chosen from (X, n_vars, P, U, n_forest) by
+// mlbp_exactsample_pick_kernel:
+//   exactsample_weights_x64_kernel      X = 64: the forest's tables in LDS (x64_open); every WAVE walks configurations of its own
+//                                       (x64_up<SumAlg, false>) and writes Z_c as a (mantissa, exponent) pair.
+//   exactsample_weights_generic_kernel  any X in [2, 1024]: the workgroup walks one configuration at a time (generic_up<SumAlg>).
+//   exactsample_scan_kernel             one workgroup per graph: the Z_c under the graph's largest exponent, their SEGMENTED
+//                                       prefix sums, log Z, and whether the graph can be drawn from at all.
+//   exactsample_draw_x64_kernel         X = 64: the tables in LDS for the whole launch; every WAVE draws samples of its own,
+//                                       lane = state, no workgroup barrier: binary search for the configuration, one pass up,
+//                                       then per free variable a DPP scan, a ballot and a readlane.
+//   exactsample_draw_generic_kernel     any X: one workgroup per (graph, sample chunk), tables streamed, block-wide scans.
+// No Z_c is merged with another before the scan and a sample is drawn by one wave or one workgroup, so the bits of a result are
+// a function of the graph, the cutset and the sample's uniforms alone.  Every scalar a workgroup or wave branches on comes out
+// of a reduction, a ballot or wave-uniform memory and has the same bits in every thread of it.
+// No device-side mutable globals: everything comes through SampleDev.
+#include <hip/hip_runtime.h>
+
+#include "../../include/mlbp_exactsample.h"
+#define MLBP_GRAPH_NO_SWEEPS                // this library runs no sweep program
+#include "../csrc/mlbp_graph_device.h"
+#include "../csrc/mlbp_graph_host.h"
+#include "../csrc/mlbp_cutset_plan.h"
+#include "../csrc/mlbp_cutset_walk.h"
+
+namespace {
+
+using namespace mlbp_graph;
+
+constexpr int HEAD = MLBP_EXACTSAMPLE_HEAD;
+constexpr double LN2 = 0.693147180559945309417232121458;
+
+struct SampleDev : WalkDev {                 // chunks: of the pass the copy is handed to
+  const double* uniforms;
+  double* zc;                                // [B][n_configs][2] Z_c as (mantissa, exponent)
+  double* scan;                              // [B][n_configs] W_c
+  double* head;                              // [B][HEAD] {E, W_last, usable, 0}
+  int32_t* samples; double* logp; double* log_z; double* score;
+  int32_t S;
+};
+
+// w_c: the mantissa of Z_c under the graph's exponent E.
+__device__ __forceinline__ double weight_of(const double* zc, int c, int E) {
+  return ldexp(zc[2 * c], max((int)zc[2 * c + 1] - E, MIN_SHIFT));
+}
+
+// The draw rule on the scanned weights (they never decrease): the lowest c with W_c > thr; when there is none, the lowest c
+// with W_c = W_last, which is the highest c of positive weight.  Always in [0, n).
+__device__ __forceinline__ int find_config(const double* W, int n, double thr, double last) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (W[mid] > thr) hi = mid; else lo = mid + 1;
+  }
+  if (lo < n) return lo;
+  lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (W[mid] >= last) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+
+// The configuration of sample `u` and its log-probability; with n_cut == 0 the one empty configuration.
+__device__ __forceinline__ int draw_config(const SampleDev& d, int g, double u0, double& logp) {
+  logp = 0.0;
+  if (d.n_cut == 0) return 0;
+  const double* head = d.head + (size_t)g * HEAD;
+  const double last = head[1];
+  const int c = find_config(d.scan + (size_t)g * d.n_configs, d.n_configs, u0 * last, last);
+  logp = log(weight_of(d.zc + (size_t)g * d.n_configs * 2, c, (int)head[0]) / last);
+  return c;
+}
+
+// A graph that cannot be drawn from: -1 / NaN for sample s.  By one wave (X = 64) or the workgroup; `first`, `step`: its threads.
+__device__ __forceinline__ void refuse_sample(const SampleDev& d, int g, int s, int first, int step) {
+  const size_t at = (size_t)s * d.B + g;
+  for (int v = first; v < d.n_vars; v += step) d.samples[at * d.n_vars + v] = -1;
+  if (first == 0) {
+    d.logp[at] = __builtin_nan("");
+    if (d.score) d.score[at] = __builtin_nan("");
+  }
+}
+
+// The log-potential of the assignment xs (LDS or memory, visible to this wave), by one wave: every lane returns it.
+__device__ __forceinline__ double wave_score(const SampleDev& d, const_i32p pav, const_i32p uvar, int g, const int* xs, int lane) {
+  const size_t X = (size_t)d.X;
+  double sc = 0.0;
+  for (int p = lane; p < d.P; p += 64) {
+    const int i = xs[pav[2 * p]], j = xs[pav[2 * p + 1]];
+    sc += log(d.pair_tables[(size_t)d.pair_tab[(size_t)g * d.P + p] * X * X + (size_t)i * X + j]);
+  }
+  for (int u = lane; u < d.U; u += 64) sc += log(d.unary_tables[(size_t)d.unary_tab[(size_t)g * d.U + u] * X + xs[uvar[u]]]);
+  return wave_sum(sc);
+}
+
+// ---- the weights pass: every Z_c of a chunk's configurations --------------------------------------------------
+__global__ __launch_bounds__(WG) void exactsample_weights_generic_kernel(SampleDev d) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int g = blockIdx.x, k = blockIdx.y, t = threadIdx.x;
+  if (!tables_in_range(d.pair_tab, d.P, d.n_pair_tables, d.unary_tab, d.U, d.n_unary_tables, g)) return;
+  Generic G;
+  generic_open(G, d, g);
+  generic_carve(G, d, g, k, smem);
+  generic_setup(G);
+  double* out = d.zc + (size_t)g * d.n_configs * 2;
+  for (int c = k; c < d.n_configs; c += d.chunks) {
+    const Scaled z = generic_up<SumAlg>(G, c, nullptr);
+    if (t == 0) {
+      out[2 * c] = z.m;
+      out[2 * c + 1] = (double)z.e;
+    }
+  }
+}
+
+__global__ __launch_bounds__(WG) void exactsample_weights_x64_kernel(SampleDev d) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int g = blockIdx.x, k = blockIdx.y, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  if (!tables_in_range(d.pair_tab, d.P, d.n_pair_tables, d.unary_tab, d.U, d.n_unary_tables, g)) return;
+  X64 W;
+  x64_open(W, d, g, smem);
+  double* out = d.zc + (size_t)g * d.n_configs * 2;
+  for (int c = 4 * k + wave; c < d.n_configs; c += 4 * d.chunks) {
+    const Scaled z = x64_up<SumAlg, false>(W, c);
+    if (lane == 0) {
+      out[2 * c] = z.m;
+      out[2 * c + 1] = (double)z.e;
+    }
+  }
+}
+
+// ---- the scan: a graph's Z_c -> E, W_c, log Z ------------------------------------------------------------------
+// SEGMENTED, as the header states it: thread t owns configurations [t L, (t + 1) L).
+__global__ __launch_bounds__(WG) void exactsample_scan_kernel(SampleDev d) {
+  __shared__ double seg[WG];
+  __shared__ double scratch[8];
+  const int g = blockIdx.x, t = threadIdx.x, n = d.n_configs;
+  double* head = d.head + (size_t)g * HEAD;
+  if (!tables_in_range(d.pair_tab, d.P, d.n_pair_tables, d.unary_tab, d.U, d.n_unary_tables, g)) {
+    if (t == 0) {
+      head[0] = 0.0; head[1] = __builtin_nan(""); head[2] = 0.0; head[3] = 0.0;
+      if (d.log_z) d.log_z[g] = __builtin_nan("");
+    }
+    return;
+  }
+  const double* zc = d.zc + (size_t)g * n * 2;
+  double* W = d.scan + (size_t)g * n;
+  constexpr double NONE = -1e300;
+  double em = NONE;                                            // the largest exponent of a positive Z_c
+  for (int c = t; c < n; c += WG)
+    if (zc[2 * c] > 0.0) em = fmax(em, zc[2 * c + 1]);
+  em = block_max(em, scratch);
+  const int E = em > NONE ? (int)em : 0;
+  const int L = (n + WG - 1) / WG, lo = min(n, t * L), hi = min(n, lo + L);
+  double tot = 0.0;
+  for (int c = lo; c < hi; ++c) tot += weight_of(zc, c, E);
+  seg[t] = tot;
+  __syncthreads();
+  double off = 0.0;
+  for (int s = 0; s < t; ++s) off += seg[s];
+  double local = 0.0;
+  for (int c = lo; c < hi; ++c) {
+    local += weight_of(zc, c, E);
+    W[c] = off + local;
+  }
+  if (t != WG - 1) return;
+  const double last = off + tot;                               // = W[n - 1]: the empty segments behind it add nothing
+  head[0] = (double)E;
+  head[1] = last;
+  head[2] = (last > 0.0 && last < __builtin_huge_val()) ? 1.0 : 0.0;
+  head[3] = 0.0;
+  if (d.log_z) d.log_z[g] = last == 0.0 ? -__builtin_huge_val() : fma((double)E, LN2, log(last));
+}
+
+// ---- X = 64: a wave per sample -------------------------------------------------------------------------------
+// WAVE prefix sums, as the header states them: lane i returns A_i.
+__device__ __forceinline__ double wave_scan(double v, int lane) {
+  v += dpp_mov<0x111>(v);                                      // row_shr:1, 2, 4, 8: a lane without a partner reads zero
+  v += dpp_mov<0x112>(v);
+  v += dpp_mov<0x114>(v);
+  v += dpp_mov<0x118>(v);
+  const double r0 = read_lane(v, 15), r1 = read_lane(v, 31), r2 = read_lane(v, 47);
+  const int row = lane >> 4;
+  const double before = row == 1 ? r0 : row == 2 ? r0 + r1 : (r0 + r1) + r2;
+  return row == 0 ? v : v + before;
+}
+
+// The draw rule on the wave's vector b (lane = state) with uniform u: the state, and the probability's two terms.
+__device__ __forceinline__ int wave_draw(double b, double u, int lane, double& num, double& total) {
+  const double A = wave_scan(b, lane);
+  total = read_lane(A, 63);
+  const double thr = u * total;
+  const unsigned long long live = __ballot(b > 0.0), cross = __ballot(A > thr && b > 0.0);
+  const int x = cross ? __ffsll(cross) - 1 : live ? 63 - __clzll(live) : 0;
+  num = read_lane(b, x);
+  return x;
+}
+
+__global__ __launch_bounds__(WG) void exactsample_draw_x64_kernel(SampleDev d) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int g = blockIdx.x, k = blockIdx.y, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int n_vars = d.n_vars, step = 4 * d.chunks;
+  if (d.head[(size_t)g * HEAD + 2] == 0.0) {                   // Z is zero or no finite number, or a table index is out of range
+    for (int s = 4 * k + wave; s < d.S; s += step) refuse_sample(d, g, s, lane, 64);
+    return;
+  }
+  X64 W;
+  x64_open(W, d, g, smem);
+  int* xi = reinterpret_cast<int*>(W.dn);                      // this wave's: the drawn states, for the score
+  for (int s = 4 * k + wave; s < d.S; s += step) {
+    const size_t at = (size_t)s * d.B + g;
+    const double* u = d.uniforms + at * n_vars;
+    double logp;
+    const int c = draw_config(d, g, u[0], logp);
+    x64_up<SumAlg, true>(W, c);                                // bel: every free variable's vector on the way up
+    int xs = 0;                                                // lane v: the state of variable v (n_vars <= 12 on this kernel)
+    for (int q = 0; q < d.n_cut; ++q)
+      if (lane == W.pl.cutset[q]) xs = x64_state(q, c);
+    for (int i = W.n_free - 1; i >= 0; --i) {
+      const int v = W.pl.order[i], p = W.pl.parent[2 * v];
+      double b = W.bel[(size_t)v * 64 + lane];
+      if (p >= 0) {
+        const int sp = __builtin_amdgcn_readlane(xs, W.pl.parent[2 * v + 1]);
+        const double* tab = W.tabs + (size_t)W.pl.fslot[p] * 64 * ROW;
+        b *= W.pl.pav[2 * p] == v ? tab[lane * ROW + sp] : tab[sp * ROW + lane];
+      }
+      double num, total;
+      const int x = wave_draw(b, u[d.n_cut + (W.n_free - 1 - i)], lane, num, total);
+      logp += log(num / total);
+      if (lane == v) xs = x;
+    }
+    if (lane < n_vars) {
+      d.samples[at * n_vars + lane] = xs;
+      xi[lane] = xs;
+    }
+    if (lane == 0) d.logp[at] = logp;
+    if (d.score) {
+      const double sc = wave_score(d, W.pl.pav, W.pl.uvar, g, xi, lane);
+      if (lane == 0) d.score[at] = sc;
+    }
+  }
+}
+
+// ---- any X: a workgroup per sample -----------------------------------------------------------------------------
+// The lowest of the workgroup's `lo` and the highest of its `hi`, the same in every thread; two barriers.
+__device__ __forceinline__ void block_min_max(unsigned& lo, unsigned& hi, double* scratch) {
+  unsigned* s = reinterpret_cast<unsigned*>(scratch);
+  const unsigned a = wave_max_u32(~lo), b = wave_max_u32(hi);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) {
+    s[threadIdx.x >> 6] = a;
+    s[4 + (threadIdx.x >> 6)] = b;
+  }
+  __syncthreads();
+  lo = ~max(max(s[0], s[1]), max(s[2], s[3]));
+  hi = max(max(s[4], s[5]), max(s[6], s[7]));
+}
+
+// The draw rule on a[0 .. n) (visible on entry) with uniform u, SEGMENTED prefix sums: thread t owns [t L, (t + 1) L).
+// seg: [number of segments <= n].  Reached by every thread; ends behind a barrier.
+__device__ __forceinline__ int block_draw(const double* a, int n, double u, double* seg, double* scratch, double& num, double& total) {
+  const int t = threadIdx.x;
+  const int L = (n + WG - 1) / WG, n_seg = (n + L - 1) / L, lo = min(n, t * L), hi = min(n, lo + L);
+  double tot = 0.0;
+  for (int j = lo; j < hi; ++j) tot += a[j];
+  if (t < n_seg) seg[t] = tot;
+  __syncthreads();
+  double off = 0.0, all = 0.0;
+  for (int s = 0; s < n_seg; ++s) {
+    if (s == t) off = all;
+    all += seg[s];
+  }
+  const double thr = u * all;
+  unsigned first = 0xffffffffu, last = 0;                      // the crossing index; 1 + the highest index of positive weight
+  double local = 0.0;
+  for (int j = lo; j < hi; ++j) {
+    local += a[j];
+    if (!(a[j] > 0.0)) continue;
+    last = (unsigned)j + 1;
+    if (first == 0xffffffffu && off + local > thr) first = (unsigned)j;
+  }
+  block_min_max(first, last, scratch);
+  const int x = first != 0xffffffffu ? (int)first : last ? (int)last - 1 : 0;
+  num = a[x];
+  total = all;
+  __syncthreads();                                             // seg and a are written again by the caller
+  return x;
+}
+
+__global__ __launch_bounds__(WG) void exactsample_draw_generic_kernel(SampleDev d) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int X = d.X, g = blockIdx.x, k = blockIdx.y, t = threadIdx.x, n_vars = d.n_vars;
+  if (d.head[(size_t)g * HEAD + 2] == 0.0) {                   // Z is zero or no finite number, or a table index is out of range
+    for (int s = k; s < d.S; s += d.chunks) refuse_sample(d, g, s, t, WG);
+    return;
+  }
+  Generic G;
+  generic_open(G, d, g);
+  generic_carve(G, d, g, k, smem);
+  const int Xp = G.Xp;
+  generic_setup(G);
+  int* xs = reinterpret_cast<int*>(G.acc);                     // [n_vars] the drawn states: the walk without its pass back leaves
+  double* seg = G.excl;                                        // acc and excl to the library
+  for (int s = k; s < d.S; s += d.chunks) {
+    const size_t at = (size_t)s * d.B + g;
+    const double* u = d.uniforms + at * n_vars;
+    double logp;
+    const int c = draw_config(d, g, u[0], logp);
+    generic_up<SumAlg>(G, c, nullptr);                         // bel: every free variable's vector on the way up; st: c's digits
+    if (t < d.n_cut) xs[G.pl.cutset[t]] = G.st[t];
+    __syncthreads();
+    for (int i = d.n_free - 1; i >= 0; --i) {
+      const int v = G.pl.order[i], p = G.pl.parent[2 * v];
+      const double* bv = G.bel + (size_t)v * Xp;
+      if (p < 0) {
+        for (int j = t; j < X; j += WG) G.raw[j] = bv[j];
+      } else {
+        const int sp = xs[G.pl.parent[2 * v + 1]];
+        const double* T = G.pair_tables + (size_t)G.ptab[p] * G.XX;
+        const int te = G.texp[p];
+        if (G.pl.pav[2 * p] == v)
+          for (int j = t; j < X; j += WG) G.raw[j] = bv[j] * ldexp(T[(size_t)j * X + sp], -te);
+        else
+          for (int j = t; j < X; j += WG) G.raw[j] = bv[j] * ldexp(T[(size_t)sp * X + j], -te);
+      }
+      __syncthreads();
+      double num, total;
+      const int x = block_draw(G.raw, X, u[d.n_cut + (d.n_free - 1 - i)], seg, G.scratch, num, total);
+      logp += log(num / total);
+      if (t == 0) xs[v] = x;
+      __syncthreads();
+    }
+    for (int v = t; v < n_vars; v += WG) d.samples[at * n_vars + v] = xs[v];
+    if (t == 0) d.logp[at] = logp;
+    if (d.score && t < 64) {
+      const double sc = wave_score(d, G.pl.pav, G.pl.uvar, g, xs, t);
+      if (t == 0) d.score[at] = sc;
+    }
+    __syncthreads();                                           // xs is written again by the next sample
+  }
+}
+
+// ---- host ----------------------------------------------------------------------------------------
+thread_local int g_last_kernel = MLBP_EXACTSAMPLE_KERNEL_NONE;
+static_assert(MLBP_EXACTSAMPLE_KERNEL_X64 == WALK_X64 && MLBP_EXACTSAMPLE_KERNEL_GENERIC == WALK_GENERIC, "the shared host core numbers the kernels");
+
+// Cd of the draw pass: the X = 64 kernel's four waves take a sample each.
+int draw_chunks(int which, int32_t B, int32_t S) {
+  return walk_chunks(B, which == WALK_X64 ? (S + 3) / 4 : S, MLBP_CUTSET_MIN_WORKGROUPS);
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* mlbp_exactsample_arch(void) { return "gfx950"; }
+const char* mlbp_exactsample_last_error(void) { return g_last_error.c_str(); }
+int mlbp_exactsample_last_kernel(void) { return g_last_kernel; }
+
+int mlbp_exactsample_pick_kernel(int32_t X, int32_t n_vars, int32_t P, int32_t U, int32_t n_forest) {
+  return pick_walk_kernel(X, n_vars, P, U, n_forest);
+}
+
+int mlbp_exactsample_chunks(int32_t B, int32_t n) {
+  if (B <= 0 || n <= 0) return fail(MLBP_EINVAL, "chunks: B = %d, n = %d", B, n);
+  return walk_chunks(B, n, MLBP_CUTSET_MIN_WORKGROUPS);
+}
+
+int64_t mlbp_exactsample_workspace_bytes(int32_t B, int32_t S, int32_t X, int32_t n_vars, int32_t P, int32_t U, int32_t n_forest,
+                                         int32_t n_cut) {
+  const int which = mlbp_exactsample_pick_kernel(X, n_vars, P, U, n_forest);
+  if (which < 0) return which;
+  if (n_cut < 0 || n_cut > n_vars) return fail(MLBP_EINVAL, "workspace: n_cut = %d with %d variables", n_cut, n_vars);
+  if (S <= 0) return fail(MLBP_EINVAL, "workspace: S = %d samples", S);
+  const int64_t n_configs = count_configs(X, n_cut);
+  if (n_configs < 0) return too_many_configs(X, n_cut);
+  const int cw = mlbp_exactsample_chunks(B, (int32_t)n_configs);
+  if (cw < 0) return cw;
+  const int cd = draw_chunks(which, B, S);
+  const bool spill = which == WALK_GENERIC && generic_lds_bytes(n_vars, P, U, X) > MLBP_CUTSET_GENERIC_LDS_BYTES;
+  return ((int64_t)B * n_configs * 3 + (int64_t)B * HEAD + (spill ? (int64_t)B * (cw > cd ? cw : cd) * vector_doubles(n_vars, X) : 0)) * 8;
+}
+
+int mlbp_exactsample_check_plan(const int32_t* plan, int32_t n_words, int32_t X) { return check_packed_plan(plan, n_words, X); }
+
+int mlbp_exactsample_f64(const mlbp_exactsample_args* a, void* stream) {
+  g_last_kernel = MLBP_EXACTSAMPLE_KERNEL_NONE;
+  int64_t n_configs = 0;
+  const int which = check_walk_args(a, mlbp_exactsample_pick_kernel, [](const mlbp_exactsample_args* a) {
+    if (a->S <= 0) return fail(MLBP_EINVAL, "bad sizes: S = %d samples", a->S);
+    if (!a->uniforms) return fail(MLBP_EINVAL, "uniforms is NULL");
+    if (!a->samples || !a->logp) return fail(MLBP_EINVAL, "samples or logp is NULL");
+    return (int)MLBP_OK;
+  }, &n_configs);
+  if (which < 0) return which;
+  const int cw = mlbp_exactsample_chunks(a->B, (int32_t)n_configs);
+  if (cw < 0) return cw;
+  const int cd = draw_chunks(which, a->B, a->S);
+  if (int e = check_walk_workspace(a, mlbp_exactsample_workspace_bytes(a->B, a->S, a->X, a->n_vars, a->P, a->U, a->n_forest, a->n_cut))) return e;
+  if (int e = check_device("libmlbp_exactsample.so")) return e;
+  SampleDev d;
+  fill_walk_dev(d, a, n_configs, cw, which);
+  d.uniforms = a->uniforms;
+  d.zc = a->workspace;
+  d.scan = d.zc + (int64_t)a->B * n_configs * 2;
+  d.head = d.scan + (int64_t)a->B * n_configs;
+  d.samples = a->samples; d.logp = a->logp; d.log_z = a->log_z; d.score = a->score;
+  d.S = a->S;
+  double* spill = d.head + (int64_t)a->B * HEAD;
+  hipStream_t st = (hipStream_t)stream;
+  (void)hipGetLastError();
+  SampleDev dd = d;                                            // the draw pass: its own number of chunks
+  dd.chunks = cd;
+  if (which == MLBP_EXACTSAMPLE_KERNEL_X64) {
+    const size_t lds = (size_t)x64_lds_bytes(a->n_vars, a->P, a->U, a->n_forest);
+    if (int e = grant_x64_lds((const void*)exactsample_weights_x64_kernel, 0, MLBP_CUTSET_X64_LDS_BYTES)) return e;
+    if (int e = grant_x64_lds((const void*)exactsample_draw_x64_kernel, 1, MLBP_CUTSET_X64_LDS_BYTES)) return e;
+    hipLaunchKernelGGL(exactsample_weights_x64_kernel, dim3(a->B, cw), dim3(WG), lds, st, d);
+    if (int e = launched("weights")) return e;
+    hipLaunchKernelGGL(exactsample_scan_kernel, dim3(a->B), dim3(WG), 0, st, d);
+    if (int e = launched("scan")) return e;
+    hipLaunchKernelGGL(exactsample_draw_x64_kernel, dim3(a->B, cd), dim3(WG), lds, st, dd);
+  } else {
+    const size_t lds = generic_walk_lds(d, spill);
+    dd.vectors = d.vectors;
+    hipLaunchKernelGGL(exactsample_weights_generic_kernel, dim3(a->B, cw), dim3(WG), lds, st, d);
+    if (int e = launched("weights")) return e;
+    hipLaunchKernelGGL(exactsample_scan_kernel, dim3(a->B), dim3(WG), 0, st, d);
+    if (int e = launched("scan")) return e;
+    hipLaunchKernelGGL(exactsample_draw_generic_kernel, dim3(a->B, cd), dim3(WG), lds, st, dd);
+  }
+  if (int e = launched("draw")) return e;
+  g_last_kernel = which;
+  return MLBP_OK;
+}
+
+}  // extern "C"

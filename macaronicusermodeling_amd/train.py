@@ -267,6 +267,15 @@ class UserGraphTrainer:
         samples, logq = self.batch.sample(self.roots[:self.n_sweeps_run], n_samples=n_samples, seed=seed, uniforms=uniforms, given=given)
         return samples.cpu().numpy().astype(np.int64), logq.cpu().numpy()
 
+    def exact_sample(self, n_samples=1, seed=None, uniforms=None):
+        """Whole sets of guesses drawn from the model ITSELF under the current thetas (FactorGraphBatch.exact_sample): host
+        (samples int64 [S][B][n_vars] word indices in var_ids order, logp float64 [S][B] -- the true log-probability of each
+        draw, score - log Z, on loopy sentence graphs too).  Exactly one of seed and uniforms.  Raises
+        exactsample.ExactSampleError(MLBP_EUNSUPPORTED) for a shape above the configuration limit."""
+        self.build_potentials()
+        samples, logp = self.batch.exact_sample(n_samples=n_samples, seed=seed, uniforms=uniforms)
+        return samples.cpu().numpy().astype(np.int64), logp.cpu().numpy()
+
     def convergence(self, tol=1e-6, max_rounds=50):
         """What stopping at the trainer's own n_sweeps_run sweeps cost each instance, under the current thetas: host (rounds
         int32 [B], residual float64 [B], gap float64 [B]).  rounds and residual are FactorGraphBatch.converge's over rounds of
@@ -930,6 +939,35 @@ class TiDirTrainer:
                 per_instance[row['index']] = (tuple(key[1]), [[self.en[w] for w in x[s, b]] for s in range(x.shape[0])],
                                               [float(logq[s, b]) for s in range(x.shape[0])])
         return per_instance
+
+    # ---- draws from the model itself (include/mlbp_exactsample.h) ----------------------------------------
+    def exact_sample(self, n_samples=1, seed=0):
+        """-> (per_instance, skipped).  per_instance[i], for instance i of this rank's shard in file order: (predicted
+        positions, [[en words] per sample], [logp per sample]) -- n_samples whole sets of guesses drawn from the model itself
+        for the sentence (UserGraphTrainer.exact_sample) and the true log-probability of each draw; an instance without a
+        predicted word builds no graph and gives ((), [], []), one of a shape above the configuration limit (positions, None,
+        None).  The i-th sentence shape in self.trainers order draws with seed `seed + i`, as sample() does.  skipped:
+        [(predicted positions, instances, reason)] of this rank's shapes above the limit.  Every rank draws for its own
+        shard: nothing is reduced."""
+        from . import exactsample as K
+        n = self._shard[1] - self._shard[0]
+        per_instance = [((), [], [])] * n
+        skipped = []
+        for i, (key, tr) in enumerate(self.trainers.items()):
+            rows = self.buckets[key]['rows']
+            try:
+                x, logp = tr.exact_sample(n_samples=n_samples, seed=int(seed) + i)
+            except K.ExactSampleError as e:
+                if e.code != _ffi.MLBP_EUNSUPPORTED:
+                    raise
+                skipped.append((tuple(key[1]), len(rows), str(e)))
+                for row in rows:
+                    per_instance[row['index']] = (tuple(key[1]), None, None)
+                continue
+            for b, row in enumerate(rows):
+                per_instance[row['index']] = (tuple(key[1]), [[self.en[w] for w in x[s, b]] for s in range(x.shape[0])],
+                                              [float(logp[s, b]) for s in range(x.shape[0])])
+        return per_instance, skipped
 
     # ---- sweeps to convergence (the reference stops at three sweeps and never looks) -------------------
     def convergence_report(self, tol=1e-6, max_rounds=50):
