@@ -467,9 +467,9 @@ class FactorGraphBatch:
         V.check(V.lib.mlbp_converge_f64(C.byref(a), _stream_ptr(self.device)))
         return (rounds, residual, hist) if history else (rounds, residual)
 
-    # ---- what the four cutset-conditioning calls share -----------------------------------------------------
+    # ---- what the five cutset-conditioning calls share -----------------------------------------------------
     def _cutset_args(self, K, Args, cutset, refusal):
-        """(plan, args) of a call into binding K (cutset, exactmap, exactgrad, exactsample): the cutset's variable ids translated, the plan
+        """(plan, args) of a call into binding K (cutset, exactmap, exactgrad, exactsample, exactmbest): the cutset's variable ids translated, the plan
         validated by K's library, and the sizes, plan and table fields of an Args() filled.  refusal: the message for pairwise
         tables that are not float64."""
         if self.pair_tables is not None and self.pair_tables.dtype != torch.float64:
@@ -567,6 +567,30 @@ class FactorGraphBatch:
         a.workspace, a.workspace_bytes = work.data_ptr(), need
         K.check(K.lib.mlbp_exactmap_f64(C.byref(a), _stream_ptr(self.device)))
         return (assignment, score) if max_marginals is None else (assignment, score, max_marginals)
+
+    # ---- the M best whole assignments, ranked (include/mlbp_exactmbest.h) ------------------------------------
+    def exact_mbest(self, m, cutset=None):
+        """The TRUE `m` jointly most probable assignments of every graph, best first, by cutset conditioning -- exact_map()
+        returns the first of them alone.  Returns (assignments int32 [B][m][n_vars] in GraphTopology.var_ids order, scores
+        float64 [B][m], n_found int32 [B]) device tensors: scores are the log-potentials of the rows, non-increasing;
+        n_found = min(m, the number of assignments of positive potential), and the rows from n_found on read -1 and -inf.
+        1 <= m <= 16.  The order among equal values is the one include/mlbp_exactmbest.h fixes; the bits of every output
+        depend on the graph, the cutset and m's prefix alone: the first rows of a longer list are the shorter list.
+        cutset: as in exact_inference.  self.msgs is neither read nor written."""
+        from . import exactmbest as K
+        if not 1 <= int(m) <= K.MAX_M:
+            raise ValueError('m must be in [1, %d]' % K.MAX_M)
+        topo, m = self.topo, int(m)
+        pl, a = self._cutset_args(K, K.ExactMbestArgs, cutset, 'exact_mbest needs float64 pairwise tables')
+        assignments = torch.empty(self.B, m, topo.n_vars, dtype=torch.int32, device=self.device)
+        scores = torch.empty(self.B, m, dtype=torch.float64, device=self.device)
+        n_found = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        a.M, a.assignments, a.scores, a.n_found = m, assignments.data_ptr(), scores.data_ptr(), n_found.data_ptr()
+        need = K.workspace_bytes(self.B, self.X, topo.n_vars, topo.P, topo.U, pl.n_forest, pl.n_cut, m)
+        work = torch.empty(need // 8, dtype=torch.float64, device=self.device)
+        a.workspace, a.workspace_bytes = work.data_ptr(), need
+        K.check(K.lib.mlbp_exactmbest_f64(C.byref(a), _stream_ptr(self.device)))
+        return assignments, scores, n_found
 
     # ---- whole assignments drawn from the model itself (include/mlbp_exactsample.h) ---------------------
     def exact_sample(self, n_samples=1, seed=None, uniforms=None, cutset=None, log_z=False, score=False):

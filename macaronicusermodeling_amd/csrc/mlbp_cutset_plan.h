@@ -88,6 +88,16 @@ __device__ __forceinline__ double block_max(double v, double* scratch /*[4]*/) {
   return fmax(fmax(scratch[0], scratch[1]), fmax(scratch[2], scratch[3]));
 }
 
+// The lowest of the workgroup's indices (0xffffffff: none), the same in every thread; two barriers.  Uses scratch[4 .. 6).
+__device__ __forceinline__ unsigned block_min_index(unsigned idx, double* scratch) {
+  unsigned* s = reinterpret_cast<unsigned*>(scratch + 4);
+  const unsigned k = wave_max_u32(~idx);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = k;
+  __syncthreads();
+  return ~max(max(s[0], s[1]), max(s[2], s[3]));
+}
+
 // vec[0 .. X) times 2^-e, e the exponent of its largest entry; returns e.  The entries are visible on entry (a barrier
 // behind the writes); ends with a barrier.
 __device__ __forceinline__ int rescale(double* vec, int X, double* scratch) {

@@ -58,16 +58,6 @@ __device__ __forceinline__ double shifted(double v, int shift) {
 }
 static_assert(MLBP_EXACTMAP_DROP_BELOW == 1000, "shifted() states the limit as a literal");
 
-// The lowest of the workgroup's indices (0xffffffff: none), the same in every thread; two barriers.  Uses scratch[4 .. 6).
-__device__ __forceinline__ unsigned block_min_index(unsigned idx, double* scratch) {
-  unsigned* s = reinterpret_cast<unsigned*>(scratch + 4);
-  const unsigned k = wave_max_u32(~idx);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = k;
-  __syncthreads();
-  return ~max(max(s[0], s[1]), max(s[2], s[3]));
-}
-
 // A partial's header: the best configuration of the walker and the reference exponent of its max-marginals.
 __device__ __forceinline__ void write_partial_header(double* out, const Best& best, int ref) {
   out[0] = best.m;

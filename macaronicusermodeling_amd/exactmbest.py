@@ -1,0 +1,88 @@
+"""ctypes binding of libmlbp_exactmbest.so (include/mlbp_exactmbest.h): the M jointly most probable assignments of every
+graph, ranked, by cutset conditioning, each with its score.
+
+The tenth library of the engine, with its own signature table.  There is no CPU fallback: the compute call on a machine
+without an MI355X returns MLBP_ENODEVICE, raised as ExactMbestError.
+
+The call takes the packed plan of include/mlbp_cutset.h: `plan(topo, cutset, X, device)` derives it with cutset.choose /
+cutset.plan_words, has THIS library validate it on the host, uploads it once and caches the device copy.
+"""
+import ctypes as C
+import sys
+
+from . import _ffi, _sidelib
+from . import cutset as _cutset
+from ._sidelib import i32 as _i32, i32p as _i32p
+
+LIB_PATH = _sidelib.lib_path('mlbp_exactmbest')
+
+KERNEL_NONE, KERNEL_X64, KERNEL_GENERIC = 0, 1, 2
+MAX_M = 16                      # include/mlbp_exactmbest.h MLBP_EXACTMBEST_MAX_M
+LISTS_FIXED = 384               # MLBP_EXACTMBEST_LISTS_FIXED
+
+
+class ExactMbestError(_sidelib.SideError):
+    LIB = 'libmlbp_exactmbest'
+
+
+class ExactMbestArgs(C.Structure):
+    _fields_ = [('B', C.c_int32), ('X', C.c_int32), ('n_vars', C.c_int32), ('P', C.c_int32), ('U', C.c_int32),
+                ('n_cut', C.c_int32), ('n_free', C.c_int32), ('n_items', C.c_int32), ('n_consts', C.c_int32), ('n_forest', C.c_int32),
+                ('n_pair_tables', C.c_int32), ('n_unary_tables', C.c_int32),
+                ('plan_words', C.c_int32),
+                ('M', C.c_int32),
+                ('plan', C.c_void_p),
+                ('pair_tables', C.c_void_p), ('pair_tab', C.c_void_p), ('unary_tables', C.c_void_p), ('unary_tab', C.c_void_p),
+                ('workspace', C.c_void_p), ('workspace_bytes', C.c_int64),
+                ('assignments', C.c_void_p), ('scores', C.c_void_p), ('n_found', C.c_void_p)]
+
+
+# name -> (restype, argtypes); mirrors include/mlbp_exactmbest.h one to one (tests/test_exactmbest_cpu.py checks that).
+SIGNATURES = {
+    'mlbp_exactmbest_f64': (C.c_int, [C.POINTER(ExactMbestArgs), C.c_void_p]),
+    'mlbp_exactmbest_check_plan': (C.c_int, [_i32p, _i32, _i32]),
+    'mlbp_exactmbest_pick_kernel': (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    'mlbp_exactmbest_chunks': (C.c_int, [_i32, _i32]),
+    'mlbp_exactmbest_lists_bytes': (C.c_int64, [_i32, _i32, _i32]),
+    'mlbp_exactmbest_workspace_bytes': (C.c_int64, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32]),
+    'mlbp_exactmbest_last_kernel': (C.c_int, []),
+    'mlbp_exactmbest_arch': (C.c_char_p, []),
+    'mlbp_exactmbest_last_error': (C.c_char_p, []),
+}
+
+lib = _sidelib.load(LIB_PATH, SIGNATURES)
+last_error, check, last_kernel, pick_kernel = _sidelib.status_helpers(lib, ExactMbestError)
+
+
+def kernels(code):
+    """(values kernel, lists kernel) of a pick_kernel / last_kernel code."""
+    return code & 15, code >> 4
+
+
+def chunks(B, n_configs):
+    """min(n_configs, ceil(512 / B)): C of the values grid (B, C)."""
+    return check(lib.mlbp_exactmbest_chunks(int(B), int(n_configs)))
+
+
+def lists_bytes(X, n_vars, M):
+    """The bytes of a lists task beside its fixed part: in LDS when they fit, else in the workspace."""
+    return check(lib.mlbp_exactmbest_lists_bytes(int(X), int(n_vars), int(M)))
+
+
+def workspace_bytes(B, X, n_vars, P, U, n_forest, n_cut, M):
+    return check(lib.mlbp_exactmbest_workspace_bytes(int(B), int(X), int(n_vars), int(P), int(U), int(n_forest), int(n_cut), int(M)))
+
+
+def check_plan(words, X):
+    """Raises ExactMbestError unless the packed plan `words` is valid for X states."""
+    check(lib.mlbp_exactmbest_check_plan(_ffi.i32ptr(words), len(words), int(X)))
+
+
+def Plan(topo, cutset, X, device):
+    """A plan validated by this library and its device copy: cutset.Plan."""
+    return _cutset.Plan(topo, cutset, X, device, sys.modules[__name__])
+
+
+def plan(topo, cutset, X, device):
+    """The cached Plan of (topology, cutset, X, device); cutset None: cutset.choose(topo)."""
+    return _cutset.plan(topo, cutset, X, device, binding=sys.modules[__name__])

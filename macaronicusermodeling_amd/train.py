@@ -382,6 +382,28 @@ class UserGraphTrainer:
         return (x.cpu().numpy().astype(np.int64), score.cpu().numpy(), margin.cpu().numpy(), agrees.cpu().numpy(),
                 shortfall.cpu().numpy(), joint.cpu().numpy())
 
+    def exact_nbest(self, m):
+        """The `m` TRULY most probable sets of guesses of every instance under the current thetas, ranked
+        (FactorGraphBatch.exact_mbest), with the true probability of each: host (assignments int64 [B][m][n_vars] word
+        indices in var_ids order, -1 in the rows a list does not have; scores float64 [B][m] -- the log-potentials, -inf
+        there --; logp float64 [B][m] = score - log Z, log Z from one exact_inference call; covered float64 [B] -- the mass
+        of the rows, sum exp(logp) --; label_rank int64 [B] -- the row that is the user's own labelled set of guesses, -1
+        when it is not among them --; bp_rank int64 [B] -- the row decode()'s set is, -1 likewise).  1 <= m <= 16.  Raises
+        exactmbest.ExactMbestError(MLBP_EUNSUPPORTED) for a shape above the configuration limit."""
+        fb = self.batch
+        self.build_potentials()
+        x, score, _ = fb.exact_mbest(m)
+        log_z = fb.exact_inference()[0]
+        bp_x, _ = fb.map_sweep(self.roots[:self.n_sweeps_run], init=True, keep_messages=False)
+        logp = score - log_z[:, None]
+        covered = logp.exp().sum(dim=1)
+
+        def rank_of(rows):
+            hit = (x == rows[:, None, :].to(x.dtype)).all(dim=2)
+            return torch.where(hit.any(dim=1), hit.to(torch.int64).argmax(dim=1), torch.full_like(hit[:, 0], -1, dtype=torch.int64))
+        return (x.cpu().numpy().astype(np.int64), score.cpu().numpy(), logp.cpu().numpy(), covered.cpu().numpy(),
+                rank_of(fb._labels).cpu().numpy(), rank_of(bp_x).cpu().numpy())
+
 
 def apply_update(theta_en_en, theta_en_de, stats, F_ee, F_ed, learning_rate, reg_param):
     """theta += sum_i lr (g_i - reg theta) = lr (sum_i g_i - n reg theta): the sum of the per-instance
@@ -1143,6 +1165,51 @@ class TiDirTrainer:
         mdist.all_reduce_max_(worst)
         tot = tot.cpu().numpy()
         return (guesses, tuple(int(v) for v in tot[:4]), (int(tot[4]), int(tot[5]), float(tot[6]), float(worst[0])), skipped)
+
+    # ---- the ranked list of whole sets of guesses (include/mlbp_exactmbest.h) ---------------------------
+    def exact_nbest(self, m):
+        """-> (per_sentence, totals, skipped).  per_sentence[i], for instance i of this rank's shard in file order: (predicted
+        positions, [[en words] per rank], [score], [logp]) -- the at most `m` sets of guesses the model truly ranks highest,
+        best first, their log-potentials and true log-probabilities (UserGraphTrainer.exact_nbest; the lists end where the
+        model has no further set of positive potential); an instance without a predicted word builds no graph and gives
+        ((), [], [], []), one of a shape above the configuration limit (positions, None, None, None).  totals = (sentences
+        compared, sum of `covered` -- the mass the lists hold --, recall [m]: recall[r] = sentences whose labelled set of
+        guesses sits at rank <= r, sentences whose decode() set is in the list) over ALL ranks' instances, reduced once.
+        skipped: as exact_decode gives it."""
+        from . import exactmbest as K
+        m = int(m)
+        if not 1 <= m <= K.MAX_M:
+            raise ValueError('m must be in [1, %d]' % K.MAX_M)
+        n = self._shard[1] - self._shard[0]
+        per_sentence = [((), [], [], [])] * n
+        recall = np.zeros(m)
+        seen = n_bp = 0
+        covered_sum = 0.0
+        skipped = []
+        for key, tr in self.trainers.items():
+            rows = self.buckets[key]['rows']
+            try:
+                x, score, logp, covered, label_rank, bp_rank = tr.exact_nbest(m)
+            except K.ExactMbestError as e:
+                if e.code != _ffi.MLBP_EUNSUPPORTED:
+                    raise
+                skipped.append((tuple(key[1]), len(rows), str(e)))
+                for row in rows:
+                    per_sentence[row['index']] = (tuple(key[1]), None, None, None)
+                continue
+            seen += len(rows)
+            n_bp += int((bp_rank >= 0).sum())
+            covered_sum += float(covered.sum())
+            for r in range(m):
+                recall[r] += int(((label_rank >= 0) & (label_rank <= r)).sum())
+            for b, row in enumerate(rows):
+                have = int((x[b, :, 0] >= 0).sum())
+                per_sentence[row['index']] = (tuple(key[1]), [[self.en[w] for w in x[b, r]] for r in range(have)],
+                                              [float(v) for v in score[b, :have]], [float(v) for v in logp[b, :have]])
+        tot = torch.tensor([float(seen), covered_sum, float(n_bp)] + [float(v) for v in recall], dtype=torch.float64, device=self.device)
+        mdist.all_reduce_sum_(tot)
+        tot = tot.cpu().numpy()
+        return per_sentence, (int(tot[0]), float(tot[1]), [int(v) for v in tot[3:]], int(tot[2])), skipped
 
     # ---- joint log-likelihood (log Z; the reference has only the sum of per-word log-marginals) ------
     def joint_log_likelihood(self):

@@ -1,0 +1,751 @@
+"""Exact M-best decoding by cutset conditioning without a GPU: the NumPy statement of include/mlbp_exactmbest.h pinned on
+exhaustive enumeration, its two lemmas, the gaps that make a ranked list comparable, the C ABI of libmlbp_exactmbest.so and the
+kernel inventory rule applied to the tenth library.
+
+References.  enum_top() is the log-domain enumeration of test_exactmap_cpu.reference -- one slice of the first variable at a
+time, so that X^n need not fit in memory -- keeping the n best of every slice, ordered by a stable sort: nothing of the
+algorithm under test is in it.  Statement states the header in NumPy, pass by pass: the max walk's V_c, the select, the list
+form of the pass up with its offer order, the fold's pruning, the decode by back-pointers, the merge.  Nothing is rescaled: the
+header's rescaling is by powers of two and changes no order.
+
+The gaps.  A ranked list is compared exactly only where ranks 0 .. M of the reference -- the (M + 1)-th included -- are GAP =
+1e-6 nats apart, the project's threshold (test_exactmap_cpu.GAP).  INPUTS lists every input of the GPU module and
+test_every_gpu_input_has_its_gaps asserts the gaps for every graph of every input: none is left out; the seeds were chosen so
+that it holds.  Where X^n can be enumerated the enumeration is the reference and the statement is held to it; elsewhere (K3 at
+X = 1024, the chain of 260) the statement, pinned on enumeration by the tests above it, is.  The dyadic inputs tie on purpose:
+there the rows must be pairwise distinct and the multiset of their scores enumeration's."""
+import ctypes
+import functools
+import os
+import re
+
+import numpy as np
+import pytest
+
+import cases as C
+import kernel_inventory as K
+import test_cutset_cpu as R
+import test_exactmap_cpu as E
+import test_map_cpu as W
+from conftest import ROOT
+from oracle import lbp_oracle as O
+
+GAP = E.GAP
+MAX_M = 16
+WIDE_SPAN = 600.0               # nats: a wide-range input keeps its M-th best this close to its best
+
+
+# ------------------------------------------------------------------------------------------------
+# enumeration
+# ------------------------------------------------------------------------------------------------
+def enum_top(g, inputs, n):
+    """[(score, {v: state})] of the at most n assignments of largest finite score, best first, ties in row-major order."""
+    order = list(g.var_order)
+    nv, X = len(order), g.X
+    with np.errstate(divide='ignore'):
+        logs = [(vs, np.log(T)) for vs, T in R._factor_arrays(g, inputs)]
+    v0, rest = order[0], order[1:]
+
+    def along(vec, v):
+        shape = [1] * (nv - 1)
+        shape[rest.index(v)] = X
+        return vec.reshape(shape)
+    found = []                                                  # (score, row-major index)
+    for s in range(X):
+        grid = np.zeros((X,) * (nv - 1))
+        for vs, L in logs:
+            if len(vs) == 1:
+                grid = grid + (L[s] if vs[0] == v0 else along(L, vs[0]))
+            elif vs[0] == v0:
+                grid = grid + along(L[s, :], vs[1])
+            elif vs[1] == v0:
+                grid = grid + along(L[:, s], vs[0])
+            else:
+                ia, ib = rest.index(vs[0]), rest.index(vs[1])
+                shape = [1] * (nv - 1)
+                shape[ia] = shape[ib] = X
+                grid = grid + (L if ia < ib else L.T).reshape(shape)
+        flat = np.asarray(grid, dtype=np.float64).reshape(-1)
+        k = min(n, flat.size)
+        cut = np.partition(flat, flat.size - k)[flat.size - k]  # the k-th largest: everything at or above it is kept
+        keep = np.nonzero((flat >= cut) & np.isfinite(flat))[0]
+        found += [(float(flat[i]), s * flat.size + int(i)) for i in keep]
+        found = sorted(found, key=lambda t: (-t[0], t[1]))[:n]
+    out = []
+    for score, index in sorted(found, key=lambda t: (-t[0], t[1]))[:n]:
+        out.append((score, dict(zip(order, (int(i) for i in np.unravel_index(index, (X,) * nv))))))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# the statement
+# ------------------------------------------------------------------------------------------------
+def top_rows(vals, M):
+    """Per row of vals [n][q], offered left to right: (the M largest positive values, 0 where there is none; their columns).
+    An offer stays behind every entry it does not exceed: a stable sort."""
+    vals = np.asarray(vals, dtype=np.float64)
+    if vals.shape[1] < M:
+        vals = np.concatenate([vals, np.zeros((vals.shape[0], M - vals.shape[1]))], axis=1)
+    with np.errstate(invalid='ignore'):
+        idx = np.argsort(-vals, axis=1, kind='stable')[:, :M]
+        out = np.take_along_axis(vals, idx, axis=1)
+        return np.where(out > 0, out, 0.0), idx
+
+
+class Statement:
+    """include/mlbp_exactmbest.h in NumPy for one graph and the cutset `cut` (variable ids; digit q of a configuration is the
+    state of cut[q]).  The forest is the one of cutset.plan_words: breadth-first from the lowest free variable of every tree,
+    `order` that walk reversed.  prune: a fold is offered only (a, b) with (a + 1) (b + 1) <= M."""
+
+    def __init__(self, g, inputs, cut, prune=True):
+        self.g, self.inputs, self.cut, self.X, self.prune = g, inputs, list(cut), g.X, prune
+        self.free = [v for v in g.var_order if v not in self.cut]
+        self.facs = R._factor_arrays(g, inputs)
+        self.edges = [(vs, T) for vs, T in self.facs if len(vs) == 2 and vs[0] not in self.cut and vs[1] not in self.cut]
+        self.parent, walk = {}, []
+        for root in self.free:
+            if root in self.parent:
+                continue
+            self.parent[root] = None
+            queue = [root]
+            while queue:
+                v = queue.pop(0)
+                walk.append(v)
+                for k, (vs, T) in enumerate(self.edges):
+                    if v in vs:
+                        w = vs[1] if vs[0] == v else vs[0]
+                        if w not in self.parent:
+                            self.parent[w] = (v, k)
+                            queue.append(w)
+        assert len(self.edges) == sum(1 for v in self.free if self.parent[v] is not None), 'the remainder has a cycle'
+        self.order = walk[::-1]
+        self.n_configs = self.X ** len(self.cut)
+
+    def states(self, c):
+        return {v: (c // self.X ** q) % self.X for q, v in enumerate(self.cut)}
+
+    def condition(self, c):
+        """(the constants' product, every free variable's local vector) under configuration c."""
+        s = self.states(c)
+        const, phi = 1.0, {v: np.ones(self.X) for v in self.free}
+        for vs, T in self.facs:
+            if len(vs) == 1:
+                if vs[0] in s:
+                    const = const * T[s[vs[0]]]
+                else:
+                    phi[vs[0]] = phi[vs[0]] * T
+            elif vs[0] in s and vs[1] in s:
+                const = const * T[s[vs[0]], s[vs[1]]]
+            elif vs[0] in s:
+                phi[vs[1]] = phi[vs[1]] * T[s[vs[0]], :]
+            elif vs[1] in s:
+                phi[vs[0]] = phi[vs[0]] * T[:, s[vs[1]]]
+        return const, phi
+
+    def table(self, v):
+        """[state of the parent][state of v] of v's forest factor."""
+        par, k = self.parent[v]
+        vs, T = self.edges[k]
+        return T.T if vs[0] == v else T
+
+    # ---- values: the max walk --------------------------------------------------------------------
+    def value(self, c):
+        const, bel = self.condition(c)
+        V = const
+        for v in self.order:
+            if self.parent[v] is None:
+                V = V * bel[v].max()
+            else:
+                par = self.parent[v][0]
+                bel[par] = bel[par] * (self.table(v) * bel[v][None, :]).max(axis=1)
+        return V
+
+    def values(self):
+        with np.errstate(invalid='ignore', over='ignore'):
+            return np.array([self.value(c) for c in range(self.n_configs)])
+
+    # ---- select ------------------------------------------------------------------------------------
+    def select(self, M):
+        V = self.values()
+        with np.errstate(invalid='ignore'):
+            return [int(c) for c in np.argsort(-V, kind='stable')[:M] if V[c] > 0]      # ties: the lower c
+
+    # ---- lists: the list form of the pass up, and the decode -------------------------------------
+    def pairs(self, M):
+        return [(a, b) for a in range(M) for b in range(M) if not self.prune or (a + 1) * (b + 1) <= M]
+
+    def lists(self, c, M):
+        """[(value, {v: state})]: the configuration's at most M candidates, best first."""
+        X = self.X
+        const, phi = self.condition(c)
+        L = {}
+        for v in self.free:                                     # start
+            L[v] = np.zeros((X, M))
+            L[v][:, 0] = phi[v]
+        F = np.zeros(M)
+        F[0] = const
+        pairs = self.pairs(M)
+        A, Bq = np.array([a for a, b in pairs]), np.array([b for a, b in pairs])
+        bpC, bpF, bpRoot, bpR = {}, {}, {}, {}
+        for v in self.order:
+            if self.parent[v] is None:
+                Rv, idx = top_rows(L[v].reshape(1, -1), M)                    # (j, k): j ascending, then k
+                bpRoot[v] = idx[0]
+                F, idx = top_rows((F[A] * Rv[0][Bq]).reshape(1, -1), M)         # fold: a ascending, then b
+                F, bpR[v] = F[0], idx[0]
+            else:
+                par = self.parent[v][0]
+                prod = (self.table(v)[:, :, None] * L[v][None, :, :]).reshape(X, X * M)   # contract: j ascending, then k
+                Cl, bpC[v] = top_rows(prod, M)
+                L[par], bpF[v] = top_rows(L[par][:, A] * Cl[:, Bq], M)          # fold
+        out = []
+        for k in range(M):                                      # decode
+            if not F[k] > 0:
+                break
+            x, rank, rf = self.states(c), {}, k
+            for v in reversed(self.order):
+                if self.parent[v] is None:
+                    a, b = pairs[bpR[v][rf]]
+                    rf = a
+                    jk = bpRoot[v][b]
+                else:
+                    par = self.parent[v][0]
+                    a, b = pairs[bpF[v][x[par], rank[par]]]
+                    rank[par] = a
+                    jk = bpC[v][x[par], b]
+                x[v], rank[v] = int(jk) // M, int(jk) % M
+            out.append((float(F[k]), x))
+        return out
+
+    # ---- merge -------------------------------------------------------------------------------------
+    def candidates(self, M):
+        """[(value, c, rank inside c, x)] of the selected configurations."""
+        return [(val, c, k, x) for c in self.select(M) for k, (val, x) in enumerate(self.lists(c, M))]
+
+    def run(self, M):
+        """([x {v: state}], [score]) of the at most M rows: by value, then the lower configuration, then the lower rank."""
+        rows = sorted(self.candidates(M), key=lambda t: (-t[0], t[1], t[2]))[:M]
+        return [t[3] for t in rows], [W.score_of(self.g, self.inputs, t[3]) for t in rows]
+
+
+def statement(g, inputs, cut, M, **kw):
+    return Statement(g, inputs, cut, **kw).run(M)
+
+
+def as_rows(g, xs):
+    return [[x[v] for v in g.var_order] for x in xs]
+
+
+def gaps_of(scores):
+    return [float(a - b) for a, b in zip(scores[:-1], scores[1:])]
+
+
+# ------------------------------------------------------------------------------------------------
+# the statement against enumeration
+# ------------------------------------------------------------------------------------------------
+SMALL = [('k3', lambda X: R.kn_spec(3, X)), ('k4', lambda X: R.kn_spec(4, X)), ('ring5', lambda X: C.ring_spec(5, X)),
+         ('star4', lambda X: C.star_spec(4, X)), ('forest', R.forest_spec), ('double_pair', R.double_pair_spec)]
+
+
+@pytest.mark.parametrize('name,make', SMALL, ids=[n for n, _ in SMALL])
+@pytest.mark.parametrize('X', [2, 3, 4])
+def test_statement_equals_enumeration(name, make, X):
+    """K3, K4, a ring, a branching tree, two components with an isolated variable, a double factor: rows equal and scores at
+    1e-12 for M = 1, 3, 16 -- 16 is above the 8 assignments of K3 at X = 2, where the list ends at n_found."""
+    spec = make(X)
+    g = O.Graph(spec)
+    cut = R.chosen_ids(spec)
+    for seed in (1, 2):
+        inputs = C.make_inputs(spec, seed, 'lognormal')
+        want = enum_top(g, inputs, MAX_M + 1)
+        total = X ** len(g.var_order)
+        assert len(want) == min(MAX_M + 1, total) and min(gaps_of([s for s, _ in want])) >= GAP
+        for M in (1, 3, 16):
+            xs, scores = statement(g, inputs, cut, M)
+            assert len(xs) == min(M, total), (name, X, M)      # n_found
+            assert as_rows(g, xs) == as_rows(g, [x for _, x in want[:M]]), (name, X, M, seed)
+            np.testing.assert_allclose(scores, [s for s, _ in want[:M]], rtol=1e-12)
+            full = statement(g, inputs, cut, M, prune=False)
+            assert as_rows(g, full[0]) == as_rows(g, xs)        # the pruned offers are the ones that could not enter
+
+
+def zero_inputs():
+    """(spec, [inputs]) of K3 at X = 2 with 8, 4, 2 and 0 assignments of positive potential."""
+    spec = R.kn_spec(3, 2)
+    a, b, c, d = (C.make_inputs(spec, 5, 'lognormal') for _ in range(4))
+    b['tables'][0][1, 0] = 0.0                                  # variable 0 cannot take state 1: four assignments left
+    c['tables'][0][1, 0] = 0.0
+    c['tables'][3][0, 1] = c['tables'][3][1, 0] = 0.0           # nor may variables 0 and 1 differ, whichever axis each is on: two
+    d['tables'][4][:] = 0.0                                     # an all-zero table: none
+    return spec, [a, b, c, d]
+
+
+def test_zero_rows_shorten_the_list():
+    """X = 2 with zeroed entries: fewer than M assignments of positive potential; an all-zero table leaves none."""
+    spec, inputs = zero_inputs()
+    g = O.Graph(spec)
+    for i, count in zip(inputs, (8, 4, 2, 0)):
+        want = enum_top(g, i, 17)
+        assert len(want) == count
+        xs, scores = statement(g, i, [0], 16)
+        assert as_rows(g, xs) == as_rows(g, [x for _, x in want])
+        np.testing.assert_allclose(scores, [s for s, _ in want], rtol=1e-12)
+    assert statement(g, inputs[3], [0], 16) == ([], [])
+
+
+def test_any_valid_cutset_gives_the_same_list():
+    spec = R.kn_spec(4, 4)
+    g = O.Graph(spec)
+    inputs = C.make_inputs(spec, 3, 'lognormal')
+    want = enum_top(g, inputs, 17)
+    assert min(gaps_of([s for s, _ in want])) >= GAP
+    for cut in ([0, 1], [3, 1], [2, 0, 1], [0, 1, 2, 3]):
+        assert as_rows(g, statement(g, inputs, cut, 16)[0]) == as_rows(g, [x for _, x in want[:16]]), cut
+    spec = C.chain_spec(5, 3)
+    g = O.Graph(spec)
+    inputs = C.make_inputs(spec, 3, 'lognormal')
+    want = enum_top(g, inputs, 16)
+    for cut in ([], [2], [4, 0]):
+        assert as_rows(g, statement(g, inputs, cut, 16)[0]) == as_rows(g, [x for _, x in want]), cut
+
+
+# ---- the two lemmas of the header -------------------------------------------------------------------------
+@pytest.mark.parametrize('name,make', SMALL[:3], ids=[n for n, _ in SMALL[:3]])
+def test_lemma_the_best_configurations_hold_the_best_assignments(name, make):
+    """(1): every one of the enumerated M best lies under one of the M configurations of largest V_c, and in its list."""
+    spec = make(4)
+    g = O.Graph(spec)
+    cut = R.chosen_ids(spec)
+    for M in (1, 3, 16):
+        inputs = C.make_inputs(spec, 7, 'lognormal')
+        st = Statement(g, inputs, cut)
+        chosen = st.select(M)
+        V = st.values()
+        assert len(chosen) == min(M, st.n_configs) and all(V[c] >= V[o] for c in chosen for o in range(st.n_configs) if o not in chosen)
+        held = {tuple(x[v] for v in g.var_order) for _, c, _, x in st.candidates(M)}
+        for score, x in enum_top(g, inputs, M):
+            assert sum(x[v] * g.X ** q for q, v in enumerate(cut)) in chosen
+            assert tuple(x[v] for v in g.var_order) in held, (name, M)
+            assert np.log(V[sum(x[v] * g.X ** q for q, v in enumerate(cut))]) >= score - 1e-9      # V_c bounds its assignments
+
+
+@pytest.mark.parametrize('make', [lambda: R.forest_spec(4), lambda: C.star_spec(5, 3), lambda: C.chain_spec(6, 3)], ids=['forest', 'star', 'chain'])
+def test_lemma_the_list_form_on_a_forest_equals_enumeration(make):
+    """(2): with nothing conditioned on, the one configuration's list IS the answer."""
+    spec = make()
+    g = O.Graph(spec)
+    inputs = C.make_inputs(spec, 11, 'lognormal')
+    want = enum_top(g, inputs, 17)
+    assert min(gaps_of([s for s, _ in want])) >= GAP
+    for M in (1, 2, 5, 16):
+        got = Statement(g, inputs, []).lists(0, M)
+        assert as_rows(g, [x for _, x in got]) == as_rows(g, [x for _, x in want[:M]]), M
+        np.testing.assert_allclose(np.log([v for v, _ in got]), [s for s, _ in want[:M]], rtol=1e-12, atol=1e-12)
+
+
+# ------------------------------------------------------------------------------------------------
+# every input of the GPU module: name -> (spec, [inputs], M, enumerate?)
+# ------------------------------------------------------------------------------------------------
+def _family(make, seeds, kind='lognormal', M=16, enum=True):
+    spec = make()
+    return spec, [C.make_inputs(spec, s, kind) for s in seeds], M, enum
+
+
+def wide_inputs(spec, seed, sigma):
+    rs = np.random.RandomState(seed)
+    n = 1 + max(f['table'] for f in spec['factors'])
+    shape = {f['table']: (spec['X'], spec['X']) if len(f['vars']) == 2 else (spec['X'], 1) for f in spec['factors']}
+    return dict(tables=[np.exp(sigma * rs.randn(*shape[t])) for t in range(n)])
+
+
+INPUTS = {
+    'k3_x64': lambda: _family(lambda: R.kn_spec(3, 64), range(8), 'uniform'),
+    'k3_x64_lognormal': lambda: _family(lambda: R.kn_spec(3, 64), range(8)),
+    'k4_x64': lambda: _family(lambda: R.kn_spec(4, 64), (1, 2, 3)),
+    'chain3_x64': lambda: _family(lambda: C.chain_spec(3, 64), range(4)),
+    'chain4_x64': lambda: _family(lambda: C.chain_spec(4, 64), (1,)),
+    'ring3_x2': lambda: _family(lambda: C.ring_spec(3, 2), (7, 8)),
+    'ring3_x5': lambda: _family(lambda: C.ring_spec(3, 5), (7, 8)),
+    'ring3_x65': lambda: _family(lambda: C.ring_spec(3, 65), (7, 8)),
+    'ring3_x257': lambda: _family(lambda: C.ring_spec(3, 257), (7, 8)),
+    'k3_x128': lambda: _family(lambda: R.kn_spec(3, 128), (1, 2)),
+    'ring5_x7': lambda: _family(lambda: C.ring_spec(5, 7), range(8)),
+    'k5_x7': lambda: _family(lambda: R.kn_spec(5, 7), (1, 2)),
+    'forest_x9': lambda: _family(lambda: R.forest_spec(9), (3, 4, 5)),
+    'double_pair_x6': lambda: _family(lambda: R.double_pair_spec(6), (3, 4, 5)),
+    'star4_x9': lambda: _family(lambda: C.star_spec(4, 9), (1, 2, 3)),                    # a hub with four children: list against list
+    'star3_x5': lambda: _family(lambda: C.star_spec(3, 5), (1, 2, 3)),
+    'star2_x64': lambda: _family(lambda: C.star_spec(2, 64), (1, 2, 3)),                  # the same at X = 64: two forest tables
+    'k3_x2_zeros': lambda: zero_inputs() + (16, True),                                    # 8, 4, 2 and 0 assignments of positive potential
+    'chain260_x2': lambda: _family(lambda: C.chain_spec(260, 2), (1, 2), enum=False),
+    'k3_x1024': lambda: _family(lambda: R.kn_spec(3, 1024), (9,), M=2, enum=False),
+    'k3_x64_wide': lambda: (R.kn_spec(3, 64), [wide_inputs(R.kn_spec(3, 64), s, 8.0) for s in (21, 22)], 16, True),
+    'ring5_x7_wide': lambda: (C.ring_spec(5, 7), [wide_inputs(C.ring_spec(5, 7), s, 20.0) for s in (21, 22)], 16, True),
+}
+WIDE = ('k3_x64_wide', 'ring5_x7_wide')
+
+
+@functools.lru_cache(maxsize=None)
+def family(name):
+    """(spec, [inputs], M, [(rows, scores)] per graph: the statement's list of M + 1, [enumeration's (score, x)] or None):
+    computed once per process and shared."""
+    spec, inputs, M, enum = INPUTS[name]()
+    g = O.Graph(spec)
+    cut = R.chosen_ids(spec)
+    stated = []
+    for i in inputs:
+        xs, scores = statement(g, i, cut, M + 1)
+        stated.append((as_rows(g, xs), scores))
+    return spec, inputs, M, stated, ([enum_top(g, i, M + 1) for i in inputs] if enum else None)
+
+
+@pytest.mark.parametrize('name', sorted(INPUTS))
+def test_every_gpu_input_has_its_gaps(name):
+    """No case is left out: in every graph the GPU module ranks, ranks 0 .. M are GAP apart -- by enumeration where X^n can be
+    enumerated, to which the statement is held here too, else by the statement."""
+    spec, inputs, M, stated, enumerated = family(name)
+    g = O.Graph(spec)
+    smallest, span = np.inf, 0.0
+    for b, (rows, scores) in enumerate(stated):
+        if enumerated is not None:
+            want = enumerated[b]
+            assert rows == as_rows(g, [x for _, x in want]), (name, b)
+            np.testing.assert_allclose(scores, [s for s, _ in want], rtol=1e-12)
+            scores = [s for s, _ in want]
+        assert len(scores) == (len(enumerated[b]) if enumerated is not None else M + 1), (name, b)
+        assert name == 'k3_x2_zeros' or len(scores) == min(M + 1, g.X ** len(g.var_order)), (name, b)
+        smallest = min([smallest] + gaps_of(scores))
+        span = max(span, scores[0] - scores[min(M, len(scores)) - 1]) if scores else span
+    print('%s: smallest of the %d gaps over %d graphs %.1e nats, the top %d span %.2f nats' % (name, M, len(stated), smallest, M, span))
+    assert smallest >= GAP, (name, smallest)
+    if name in WIDE:
+        assert span <= WIDE_SPAN, (name, span)
+
+
+TIDIR_M = 4                     # rows the GPU module asks the trainer for
+
+
+@functools.lru_cache(maxsize=None)
+def tidir_instances():
+    """{(shape key, instance): (graph, the statement's (rows, scores) of TIDIR_M + 1)} of every K1 to K4 instance of the clique
+    fixture under its own thetas -- the graphs TiDirTrainer.exact_nbest ranks in the GPU module; and the shapes above the limit."""
+    import tempfile
+    from helpers import tidir_gold, tidir_oracle_graph, write_tidir
+    from macaronicusermodeling_amd import tidir
+    gold = tidir_gold('tidir_cliques_reference')
+    with tempfile.TemporaryDirectory() as d:
+        paths = write_tidir(gold, d)
+        phi_ee, phi_w1, phi_ed = tidir.load_features(paths['phi.pmi'], paths['phi.pmi_w1'], paths['phi.ed'], paths['phi.ped'])
+    th_ee, th_ed = np.array(gold['theta_en_en']).reshape(1, -1), np.array(gold['theta_en_de']).reshape(1, -1)
+    buckets = tidir.bucket_instances([tidir.parse_instance(l) for l in gold['instances']], gold['vocab_en'], gold['vocab_de'])
+    out, too_large = {}, []
+    for key, b in sorted(buckets.items()):
+        if len(key[1]) >= 5:
+            too_large.append(key)
+            continue
+        for i in range(len(b['rows'])):
+            g, inputs, _, _ = tidir_oracle_graph(key, b, i, phi_ee, phi_w1, phi_ed, th_ee, th_ed)
+            xs, scores = statement(g, inputs, list(g.var_order)[:max(len(key[1]) - 2, 0)], TIDIR_M + 1)
+            out[(key, i)] = (g, as_rows(g, xs), scores)
+    return out, too_large
+
+
+def test_every_trainer_instance_has_its_gaps():
+    """The graphs the GPU module ranks through TiDirTrainer.exact_nbest: ranks 0 .. TIDIR_M of every K1 to K4 instance GAP apart,
+    no instance left out."""
+    instances, too_large = tidir_instances()
+    assert len(instances) >= 4 and too_large
+    smallest = np.inf
+    for (key, i), (g, rows, scores) in instances.items():
+        assert len(rows) == min(TIDIR_M + 1, g.X ** len(key[1])), (key, i)
+        smallest = min([smallest] + gaps_of(scores))
+    print('%d trainer instances: smallest of the %d gaps %.1e nats' % (len(instances), TIDIR_M, smallest))
+    assert smallest >= GAP
+
+
+@pytest.mark.parametrize('X', [4, 5, 64])
+def test_the_dyadic_inputs_tie_and_the_statement_lists_distinct_rows(X):
+    """Entries in {1/2, 1, 2}: every product is exact and most values tie.  The rows are pairwise distinct and their scores are
+    enumeration's M best as a multiset."""
+    spec = R.kn_spec(3, X)
+    g = O.Graph(spec)
+    for seed in range(3):
+        inputs = E.power_of_two_inputs(spec, seed, -1, 1)
+        want = [s for s, _ in enum_top(g, inputs, 16)]
+        assert min(gaps_of(want)) == 0.0                        # they do tie
+        xs, scores = statement(g, inputs, [0], 16)
+        assert len({tuple(r) for r in as_rows(g, xs)}) == 16
+        np.testing.assert_allclose(sorted(scores), sorted(want), rtol=1e-12, atol=1e-12)
+        assert all(a >= b - 1e-12 for a, b in zip(scores[:-1], scores[1:]))
+
+
+# ------------------------------------------------------------------------------------------------
+# C ABI of libmlbp_exactmbest.so
+# ------------------------------------------------------------------------------------------------
+HEADER = os.path.join(ROOT, 'include', 'mlbp_exactmbest.h')
+
+
+def _M():
+    from macaronicusermodeling_amd import exactmbest
+    return exactmbest
+
+
+def _ffi():
+    from macaronicusermodeling_amd import _ffi
+    return _ffi
+
+
+def declared_functions():
+    text = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
+    return sorted(set(re.findall(r'\b(mlbp_exactmbest_[a-z0-9_]+)\s*\(', text)))
+
+
+def test_every_declared_symbol_is_exported_and_bound_and_nothing_else():
+    M = _M()
+    names = declared_functions()
+    assert len(names) == 9 and 'mlbp_exactmbest_f64' in names
+    exported = sorted(n for n, (_, typ) in K._symbols(M.LIB_PATH).items() if n.startswith('mlbp_') and typ == K._STT_FUNC)
+    assert exported == names, set(exported) ^ set(names)
+    assert sorted(M.SIGNATURES) == names, set(M.SIGNATURES) ^ set(names)
+    raw = ctypes.CDLL(M.LIB_PATH)
+    for n in names:
+        assert hasattr(raw, n)
+    from macaronicusermodeling_amd import _ffi, converge, cutset, exactgrad, exactmap, exactsample, logz, mapdecode, sample
+    for other in (_ffi, mapdecode, logz, sample, converge, cutset, exactmap, exactgrad, exactsample):
+        assert not set(M.SIGNATURES) & set(other.SIGNATURES)
+    text = open(HEADER).read()
+    for name, value in (('KERNEL_NONE', M.KERNEL_NONE), ('KERNEL_X64', M.KERNEL_X64), ('KERNEL_GENERIC', M.KERNEL_GENERIC), ('MAX_M', M.MAX_M),
+                        ('LISTS_FIXED', M.LISTS_FIXED)):
+        assert int(re.search(r'#define MLBP_EXACTMBEST_%s (\d+)' % name, text).group(1)) == value, name
+    assert M.MAX_M == MAX_M
+    body = re.sub(r'/\*.*?\*/', '', re.search(r'typedef struct mlbp_exactmbest_args \{(.*?)\} mlbp_exactmbest_args;', text, flags=re.S).group(1), flags=re.S)
+    fields = [n for decl in body.split(';') for n in re.findall(r'(\w+)\s*(?:,|$)', decl.strip())]
+    assert fields == [f[0] for f in M.ExactMbestArgs._fields_], fields
+    for word in ('THIS DIFFERS', 'n_found = -1', '(a + 1) * (b + 1) <= M', 'MLBP_EXACTMBEST_DROP_BELOW'):     # what the issue asks the header to state
+        assert word in text, word
+
+
+def _valid_args(M, X=64, n_cut=1, m=16):
+    """Arguments of K3 that pass every host-side check (the pointers are never dereferenced on the host)."""
+    from macaronicusermodeling_amd import cutset
+    words = cutset.plan_words(R._topo(R.kn_spec(3, 4)), list(range(n_cut)))
+    a = M.ExactMbestArgs()
+    a.B, a.X, a.n_vars, a.P, a.U, a.M = 2, X, 3, 3, 3, m
+    a.n_cut, a.n_free, a.n_items, a.n_consts, a.n_forest = (int(w) for w in words[3:8])
+    a.n_pair_tables, a.n_unary_tables, a.plan_words = 6, 6, len(words)
+    for name, typ in M.ExactMbestArgs._fields_:
+        if typ is ctypes.c_void_p:
+            setattr(a, name, 4096)
+    a.workspace_bytes = 1 << 40
+    return a
+
+
+def test_library_identity_and_bad_arguments():
+    M, E_ = _M(), _ffi()
+    assert M.lib.mlbp_exactmbest_arch() == b'gfx950'
+    assert M.lib.mlbp_exactmbest_f64(None, None) == E_.MLBP_EINVAL and 'NULL' in M.last_error()
+    for field, value, word in (('B', 0, 'sizes'), ('X', 1, 'two states'), ('n_free', 1, 'sizes'), ('M', 0, 'rows'), ('M', 17, 'rows'), ('M', -1, 'rows'),
+                               ('plan', None, 'plan'), ('plan_words', 5, 'plan'), ('pair_tab', None, 'pair_tab'), ('n_unary_tables', 0, 'unary_tables'),
+                               ('assignments', None, 'assignments'), ('scores', None, 'scores'), ('n_found', None, 'n_found'),
+                               ('workspace', None, 'workspace'), ('workspace_bytes', 8, 'workspace')):
+        a = _valid_args(M)
+        setattr(a, field, value)
+        assert M.lib.mlbp_exactmbest_f64(ctypes.byref(a), None) == E_.MLBP_EINVAL, field
+        assert word in M.last_error(), (field, M.last_error())
+        assert M.lib.mlbp_exactmbest_last_kernel() == M.KERNEL_NONE
+    a = _valid_args(M, X=1025)
+    assert M.lib.mlbp_exactmbest_f64(ctypes.byref(a), None) == E_.MLBP_EUNSUPPORTED and '1024' in M.last_error()
+    a = _valid_args(M, X=1024, n_cut=2)
+    assert M.lib.mlbp_exactmbest_f64(ctypes.byref(a), None) == E_.MLBP_EUNSUPPORTED and 'configurations' in M.last_error()
+    with pytest.raises(M.ExactMbestError):
+        M.check(E_.MLBP_EINVAL)
+    for m in (0, 17):
+        assert M.lib.mlbp_exactmbest_pick_kernel(64, 3, 3, 3, 1, m) == E_.MLBP_EINVAL
+        assert M.lib.mlbp_exactmbest_lists_bytes(64, 3, m) == E_.MLBP_EINVAL
+        assert M.lib.mlbp_exactmbest_workspace_bytes(1, 64, 3, 3, 3, 1, 1, m) == E_.MLBP_EINVAL
+
+
+def test_compute_entry_fails_loudly_without_a_gpu():
+    import torch
+    M = _M()
+    if torch.cuda.is_available():
+        return                                                  # (the GPU module runs the entry for real)
+    for X in (64, 128, 1024):
+        for m in (1, 2, 16):
+            a = _valid_args(M, X=X, m=m)
+            assert M.lib.mlbp_exactmbest_f64(ctypes.byref(a), None) == _ffi().MLBP_ENODEVICE
+            assert 'no CPU fallback' in M.last_error() and M.lib.mlbp_exactmbest_last_kernel() == M.KERNEL_NONE
+
+
+def test_check_plan_is_the_shared_check():
+    """The plan's validation is stated once (csrc/mlbp_cutset_plan.h): the libraries refuse the same plans in the same words."""
+    from macaronicusermodeling_amd import cutset as S
+    M, E_ = _M(), _ffi()
+    topo = R._topo(R.kn_spec(4, 4))
+    good = S.plan_words(topo, [0, 1])
+    ring = S.plan_words(R._topo(C.ring_spec(5, 4)), [])
+    bad = good.copy()
+    bad[S.PLAN_HEADER] = 9
+    for words, X in ((good, 4), (good, 64), (good, 1024), (good, 1), (good[:-1], 4), (ring, 4), (bad, 4), (S.plan_words(topo, [0]), 4)):
+        w = np.ascontiguousarray(words, dtype=np.int32)
+        rc = M.lib.mlbp_exactmbest_check_plan(E_.i32ptr(w), len(w), X)
+        assert rc == S.lib.mlbp_cutset_check_plan(E_.i32ptr(w), len(w), X)
+        if rc:
+            assert M.last_error() == S.last_error() and M.last_error()
+    assert M.lib.mlbp_exactmbest_check_plan(None, 16, 4) == E_.MLBP_EINVAL and 'NULL' in M.last_error()
+    with pytest.raises(M.ExactMbestError, match='cycle'):
+        M.Plan(R._topo(C.ring_spec(5, 4)), [], 4, None)
+    with pytest.raises(M.ExactMbestError, match='configurations') as err:
+        M.Plan(R._topo(R.kn_spec(5, 4)), [0, 1, 2], 64, None)
+    assert err.value.code == E_.MLBP_EUNSUPPORTED
+    with pytest.raises(ValueError):
+        M.Plan(topo, [0, 0], 4, None)
+    assert M.plan(topo, [0, 1], 4, None) is M.plan(topo, [0, 1], 4, None) is not S.plan(topo, [0, 1], 4, None)
+
+
+def ints(P, U):
+    return 4 * ((P + U + 16 + 3) // 4 * 4)
+
+
+def lists_bytes(X, n_vars, m):
+    Xp, vl = (X + 1) // 2 * 2, X * m
+    return (8 * (n_vars * Xp + n_vars * vl + vl) + 4 * m * n_vars + 4 * n_vars * vl + 4 * n_vars * m + 7) // 8 * 8
+
+
+def values_rule(X, n_vars, P, U, n_forest):
+    from macaronicusermodeling_amd import cutset as S
+    M = _M()
+    return M.KERNEL_X64 if X == 64 and n_forest * 33280 + 21 * n_vars * 512 + 64 + ints(P, U) <= S.X64_LDS_BYTES else M.KERNEL_GENERIC
+
+
+def lists_rule(X, n_vars, P, U, n_forest, m):
+    """The X = 64 form where the values pass took its X = 64 kernel and four waves' lists fit behind x64_open's LDS."""
+    from macaronicusermodeling_amd import cutset as S
+    M = _M()
+    x64 = n_forest * 33280 + 21 * n_vars * 512 + 64 + ints(P, U)
+    fits = x64 + 4 * n_forest * m * 64 * 12 <= S.X64_LDS_BYTES
+    return M.KERNEL_X64 if values_rule(X, n_vars, P, U, n_forest) == M.KERNEL_X64 and fits else M.KERNEL_GENERIC
+
+
+def lists_in_workspace(X, n_vars, P, U, m, n_forest=None):
+    """The generic lists kernel's lists do not fit its LDS (n_forest given: and the call takes that kernel)."""
+    from macaronicusermodeling_amd import cutset as S
+    if n_forest is not None and lists_rule(X, n_vars, P, U, n_forest, m) != _M().KERNEL_GENERIC:
+        return False
+    return _M().LISTS_FIXED + ints(P, U) + lists_bytes(X, n_vars, m) > S.GENERIC_LDS_BYTES
+
+
+def test_kernel_choice_chunks_and_workspace_are_the_rules_of_the_header():
+    from macaronicusermodeling_amd import cutset as S
+    M, E_ = _M(), _ffi()
+
+    def vectors(n_vars, X):
+        return (5 * n_vars + 2) * ((X + 1) // 2 * 2) * 8
+
+    rule = values_rule
+
+    def walk_in_workspace(X, n_vars, P, U, n_forest):
+        return rule(X, n_vars, P, U, n_forest) == M.KERNEL_GENERIC and vectors(n_vars, X) + 64 + ints(P, U) > S.GENERIC_LDS_BYTES
+
+    def chunks(B, n):
+        return min(n, -(-S.MIN_WORKGROUPS // B))
+    shapes = ((64, 3, 3, 3, 1), (64, 4, 6, 4, 1), (64, 3, 2, 3, 2), (64, 4, 3, 4, 3), (64, 3, 3, 12, 1), (63, 3, 3, 3, 1), (2, 260, 259, 260, 259),
+              (257, 3, 3, 3, 1), (301, 3, 3, 3, 1), (1024, 3, 3, 3, 1), (7, 5, 5, 5, 3), (64, 5, 4, 5, 2), (64, 6, 5, 6, 2), (64, 9, 8, 9, 1), (64, 10, 9, 10, 1))
+    for shape in shapes:
+        for m in (1, 2, 16):
+            code = M.pick_kernel(*(shape + (m,)))
+            assert M.kernels(code) == (rule(*shape), lists_rule(*(shape + (m,)))) and code & 15 == S.pick_kernel(*shape), (shape, m)
+    # both sides of the X = 64 lists rule: K3 and K4 keep four waves' 16-lists on chip; a chain of three (two forest tables) does
+    # up to five rows and does not from six on
+    assert M.kernels(M.pick_kernel(64, 3, 3, 3, 1, 16)) == M.kernels(M.pick_kernel(64, 4, 6, 4, 1, 16)) == (M.KERNEL_X64, M.KERNEL_X64)
+    assert M.kernels(M.pick_kernel(64, 3, 2, 3, 2, 16)) == M.kernels(M.pick_kernel(64, 3, 2, 3, 2, 6)) == (M.KERNEL_X64, M.KERNEL_GENERIC)
+    assert M.kernels(M.pick_kernel(64, 3, 2, 3, 2, 1)) == M.kernels(M.pick_kernel(64, 3, 2, 3, 2, 5)) == (M.KERNEL_X64, M.KERNEL_X64)
+    assert 2 * 33280 + 21 * 3 * 512 + 64 + ints(2, 3) + 4 * 2 * 5 * 64 * 12 <= S.X64_LDS_BYTES < 2 * 33280 + 21 * 3 * 512 + 64 + ints(2, 3) + 4 * 2 * 6 * 64 * 12
+    assert M.lib.mlbp_exactmbest_pick_kernel(1025, 3, 3, 3, 1, 1) == E_.MLBP_EUNSUPPORTED
+    assert M.lib.mlbp_exactmbest_pick_kernel(1, 3, 3, 3, 1, 1) == E_.MLBP_EINVAL
+    assert M.lib.mlbp_exactmbest_pick_kernel(64, 3, 3, 3, 4, 1) == E_.MLBP_EINVAL
+    for B, n in ((1, 64), (1, 4096), (2, 4096), (3, 64), (8192, 64), (600, 64), (600, 7), (256, 3), (511, 4), (512, 4), (1, 1), (9, 65536)):
+        assert M.chunks(B, n) == chunks(B, n) == S.chunks(B, n), (B, n)
+    assert M.lib.mlbp_exactmbest_chunks(0, 1) == E_.MLBP_EINVAL and M.lib.mlbp_exactmbest_chunks(1, 0) == E_.MLBP_EINVAL
+    for X, n_vars, m in ((64, 3, 16), (64, 4, 16), (2, 260, 16), (1024, 3, 2), (5, 3, 1), (257, 3, 16), (65, 3, 16)):
+        assert M.lists_bytes(X, n_vars, m) == lists_bytes(X, n_vars, m), (X, n_vars, m)
+    # both sides of the lists' LDS rule: K3 and K4 at X = 64 keep 16-lists on chip, a ring of three at X = 65 too; at X = 257,
+    # for the chain of 260 and for K3 at X = 1024 (two rows) they go to the workspace
+    assert not lists_in_workspace(64, 3, 3, 3, 16) and not lists_in_workspace(64, 4, 6, 4, 16) and not lists_in_workspace(65, 3, 3, 3, 16)
+    assert lists_in_workspace(257, 3, 3, 3, 16) and lists_in_workspace(2, 260, 259, 260, 16) and lists_in_workspace(1024, 3, 3, 3, 2)
+    assert not walk_in_workspace(301, 3, 3, 3, 1) and walk_in_workspace(1024, 3, 3, 3, 1)
+    for B in (1, 3, 8192):
+        for shape in shapes:
+            X, n_vars, P, U, n_forest = shape
+            for n_cut in (0, 1, 2):
+                if X ** n_cut > S.MAX_CONFIGS or n_cut > n_vars:
+                    continue
+                for m in (1, 3, 16):
+                    n = X ** n_cut
+                    want = B * n * 2 + B * (m + 1) + B * m * m * 2 + (B * m * m * n_vars + 1) // 2
+                    if walk_in_workspace(*shape):
+                        want += B * chunks(B, n) * vectors(n_vars, X) // 8
+                    if lists_in_workspace(X, n_vars, P, U, m, n_forest):
+                        want += B * m * lists_bytes(X, n_vars, m) // 8
+                    assert M.workspace_bytes(B, X, n_vars, P, U, n_forest, n_cut, m) == want * 8, (B, shape, n_cut, m)
+    assert M.lib.mlbp_exactmbest_workspace_bytes(1, 64, 4, 6, 4, 1, 3, 1) == E_.MLBP_EUNSUPPORTED and 'configurations' in M.last_error()
+    assert M.lib.mlbp_exactmbest_workspace_bytes(0, 64, 3, 3, 3, 1, 1, 1) == E_.MLBP_EINVAL
+    assert M.workspace_bytes(8192, 1024, 40, 39, 40, 39, 0, 16) > 2 ** 31                       # 64-bit
+
+
+# ------------------------------------------------------------------------------------------------
+# kernel inventory of libmlbp_exactmbest.so: the rule of tests/test_kernel_inventory.py applied to the tenth library
+# ------------------------------------------------------------------------------------------------
+CSRC_EXACTMBEST = os.path.join(ROOT, 'macaronicusermodeling_amd', 'csrc_exactmbest')
+KERNELS = {'exactmbest_values_x64_kernel', 'exactmbest_values_generic_kernel', 'exactmbest_select_kernel',
+           'exactmbest_lists_x64_kernel', 'exactmbest_lists_generic_kernel', 'exactmbest_merge_kernel'}
+
+
+def test_exactmbest_library_kernels_are_the_sources_kernels_and_each_has_a_case():
+    import test_gpu_exactmbest as G
+    src = K.kernel_names(csrc=CSRC_EXACTMBEST)
+    assert src == KERNELS
+    compiled = R._kernels_of(_M().LIB_PATH)
+    assert compiled == {(name, ()) for name in src}
+    assert set(G.CASES) == compiled, set(G.CASES) ^ compiled
+    for kern, tests in G.CASES.items():
+        assert tests, kern
+        for t in tests:
+            assert callable(getattr(G, t, None)), (kern, t)
+    assert set(G.INPUTS_USED) == set(INPUTS), set(G.INPUTS_USED) ^ set(INPUTS)       # every input ranked there has its gaps here
+
+
+def test_the_other_libraries_hold_no_exactmbest_kernel_and_the_sources_stay_apart():
+    from macaronicusermodeling_amd import converge, cutset, exactgrad, exactmap, exactsample, logz, mapdecode, sample
+    import test_exactgrad_cpu
+    import test_exactsample_cpu
+    assert not [k for k in K.all_compiled() if k[0].startswith('exactmbest_')]
+    for other in (mapdecode, logz, sample, converge, cutset, exactmap, exactgrad, exactsample):
+        assert not [k for k in R._kernels_of(other.LIB_PATH) if k[0].startswith('exactmbest_')]
+    # and no kernel has appeared in a sibling: each still holds its own closed inventory
+    assert {n for n, _ in R._kernels_of(exactmap.LIB_PATH)} == K.kernel_names(csrc=E.CSRC_EXACTMAP)
+    assert {n for n, _ in R._kernels_of(cutset.LIB_PATH)} == K.kernel_names(csrc=R.CSRC_CUTSET)
+    assert {n for n, _ in R._kernels_of(exactsample.LIB_PATH)} == test_exactsample_cpu.KERNELS
+    assert {n for n, _ in R._kernels_of(exactgrad.LIB_PATH)} == K.kernel_names(csrc=test_exactgrad_cpu.CSRC_EXACTGRAD)
+    names = K.kernel_names(csrc=CSRC_EXACTMBEST)
+    assert all(n.startswith('exactmbest_') for n in names)
+    pkg = os.path.join(ROOT, 'macaronicusermodeling_amd')
+    for csrc in ('csrc', 'csrc_map', 'csrc_logz', 'csrc_sample', 'csrc_converge', 'csrc_cutset', 'csrc_exactmap', 'csrc_exactgrad', 'csrc_exactsample'):
+        assert not names & K.kernel_names(csrc=os.path.join(pkg, csrc))
+    for shared in ('mlbp_cutset_plan.h', 'mlbp_cutset_walk.h'):
+        assert '__global__' not in open(os.path.join(pkg, 'csrc', shared)).read()      # helpers only
+    for f in os.listdir(CSRC_EXACTMBEST):
+        assert f.endswith(('.hip', '.h', '.o')), f
+
+
+def test_build_lists_the_library_among_the_later_ones():
+    from macaronicusermodeling_amd import build as B
+    mine = [e for e in B.LATER_LIBRARIES if os.path.basename(e[4]) == 'libmlbp_exactmbest.so']
+    assert len(mine) == 1
+    csrc, sources, headers, public, lib = mine[0]
+    assert (os.path.basename(csrc), sources, public) == ('csrc_exactmbest', ['mlbp_exactmbest.hip'], 'mlbp_exactmbest.h')
+    assert headers == B.HEADERS_SIDE + ['../../include/mlbp_cutset.h']
+    assert os.path.dirname(lib) == os.path.dirname(B.LIB) and not set(e[4] for e in B.LATER_LIBRARIES) & set(e[4] for e in B.LIBRARIES)
+    for entry in B.LATER_LIBRARIES:
+        assert len(entry) == 5 and all(os.path.exists(os.path.join(entry[0], s)) for s in entry[1])
+        assert os.path.exists(os.path.join(B.INCLUDE, entry[3]))
