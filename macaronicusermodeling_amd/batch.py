@@ -21,6 +21,11 @@ from . import _ffi
 from .topology import GraphTopology
 
 
+# cutset_proposal(): the most bytes of sample()'s cond_marginals buffer ([S][B][n_vars][X] doubles) alive at once; the draws
+# are taken in slices of S that stay under it (one draw at the least)
+CUTSET_PROPOSAL_BYTES = 256 << 20
+
+
 def _stream_ptr(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
@@ -467,9 +472,9 @@ class FactorGraphBatch:
         V.check(V.lib.mlbp_converge_f64(C.byref(a), _stream_ptr(self.device)))
         return (rounds, residual, hist) if history else (rounds, residual)
 
-    # ---- what the five cutset-conditioning calls share -----------------------------------------------------
+    # ---- what the six cutset-conditioning calls share -----------------------------------------------------
     def _cutset_args(self, K, Args, cutset, refusal):
-        """(plan, args) of a call into binding K (cutset, exactmap, exactgrad, exactsample, exactmbest): the cutset's variable ids translated, the plan
+        """(plan, args) of a call into binding K (cutset, exactmap, exactgrad, exactsample, exactmbest, cutsetis): the cutset's variable ids translated, the plan
         validated by K's library, and the sizes, plan and table fields of an Args() filled.  refusal: the message for pairwise
         tables that are not float64."""
         if self.pair_tables is not None and self.pair_tables.dtype != torch.float64:
@@ -537,6 +542,112 @@ class FactorGraphBatch:
         a.workspace, a.workspace_bytes = work.data_ptr(), need
         K.check(K.lib.mlbp_cutset_f64(C.byref(a), _stream_ptr(self.device)))
         return (log_z, marginals) if labels is None else (log_z, marginals, joint)
+
+    # ---- log Z and marginals by cutset importance sampling (include/mlbp_cutsetis.h) -------------------
+    def cutset_proposal(self, roots, n_samples, seed=None, uniforms=None, cutset=None):
+        """The default proposal of cutset_estimate(): n_samples joint states of the cutset per graph, drawn by sample() --
+        sequential conditioning on loopy-BP marginals after sweep(roots, init=True) -- with the cutset variables first in
+        its order.  Returns (configs int32 [B][N][n_cut], log_q float64 [B][N]) device tensors: configs[b][i][q] is the state
+        of cutset variable q in draw i, log_q the natural log of the probability the sampler gave that joint state: the sum
+        over the cutset variables, in cutset order, of the log of the conditional marginal each was drawn from.  Exactly one
+        of `seed` and `uniforms`, as in sample() ([N][B][n_vars]; the columns behind the cutset's draw the free variables and
+        do not move configs or log_q).  sample() is called on slices of the draws so that its cond_marginals buffer stays
+        under CUTSET_PROPOSAL_BYTES; the uniforms are made once for the whole call and the result does not depend on the
+        bound.  cutset: as in exact_inference, without its limit on X^len(cutset).  On a tree configs is [B][N][0] and log_q 0."""
+        from . import cutset as K0, cutsetis as K
+        if (seed is None) == (uniforms is None):
+            raise ValueError('give exactly one of seed and uniforms')
+        topo, N = self.topo, int(n_samples)
+        if not 1 <= N <= K.MAX_LISTED:
+            raise ValueError('n_samples must be in [1, %d]' % K.MAX_LISTED)
+        pl, _ = self._cutset_args(K, K.CutsetisArgs, cutset, 'cutset_proposal needs float64 pairwise tables')
+        cut = [int(v) for v in pl.words[K0.PLAN_HEADER:K0.PLAN_HEADER + pl.n_cut]]
+        configs = torch.empty(self.B, N, pl.n_cut, dtype=torch.int32, device=self.device)
+        log_q = torch.zeros(self.B, N, dtype=torch.float64, device=self.device)
+        if not cut:
+            return configs, log_q
+        if uniforms is None:
+            gen = torch.Generator(self.device).manual_seed(int(seed))
+            uniforms = torch.rand((N, self.B, topo.n_vars), dtype=torch.float64, device=self.device, generator=gen)
+        elif (not torch.is_tensor(uniforms) or uniforms.dtype != torch.float64 or uniforms.device != self.device
+              or tuple(uniforms.shape) != (N, self.B, topo.n_vars) or not uniforms.is_contiguous()):
+            raise ValueError('uniforms must be a contiguous float64 device tensor [n_samples][B][n_vars]')
+        order = [topo.var_ids[v] for v in cut] + [topo.var_ids[v] for v in range(topo.n_vars) if v not in set(cut)]
+        step = max(1, CUTSET_PROPOSAL_BYTES // (self.B * topo.n_vars * self.X * 8))
+        cols = torch.tensor(cut, dtype=torch.int64, device=self.device)
+        for lo in range(0, N, step):
+            hi = min(N, lo + step)
+            cond = torch.empty(hi - lo, self.B, topo.n_vars, self.X, dtype=torch.float64, device=self.device)
+            samples, _ = self.sample(roots, hi - lo, uniforms=uniforms[lo:hi], order=order, cond_marginals=cond)
+            drawn = samples.index_select(2, cols)                                          # [S][B][n_cut]
+            p = cond.index_select(2, cols).gather(3, drawn.long().unsqueeze(3)).squeeze(3)
+            lq = p[:, :, 0].log()
+            for q in range(1, len(cut)):                       # one addition per cut position: the same bits for every slice
+                lq = lq + p[:, :, q].log()
+            configs[:, lo:hi] = drawn.permute(1, 0, 2)
+            log_q[:, lo:hi] = lq.t()
+        return configs, log_q
+
+    def cutset_estimate(self, roots=None, n_samples=None, seed=None, uniforms=None, configs=None, log_q=None, labels=None,
+                        marginals=None, cutset=None, log_w=False):
+        """An ESTIMATE of log Z and of the marginals of every graph by cutset importance sampling -- for the graphs whose
+        cutset has more joint states than exact_inference() sums (more than 65536: K5 and up at X = 64).  N joint states c_i of
+        the cutset are listed per graph with the log-probability a proposal q gave each; the conditioned forest is solved
+        exactly for every entry, as exact_inference() does for every configuration, and weighted by w_i = Z_c / q(c_i).
+        Returns (log_z_hat [B], marginals [B][n_vars][X], ess [B]) device tensors, then joint_logp [B] = score(labels) -
+        log_z_hat when `labels` is given, then log_w [B][N] = ln Z_c - log_q with log_w=True.
+        Either `configs` (int32 [B][N][n_cut], the state of every cutset variable in cutset order) and `log_q` (float64
+        [B][N]), or `roots`, `n_samples` and one of `seed` / `uniforms`, which go through cutset_proposal().
+        exp(log_z_hat) = mean of w_i is an unbiased estimate of Z for any proposal that is positive wherever Z_c is.  The
+        marginals are self-normalised, sum of w_i m_c / sum of w_i: consistent, not unbiased.  ess = (sum w)^2 / sum w^2 is the
+        effective sample size, N for a perfect proposal; the relative standard error of the estimate of Z it implies is
+        sqrt(1 / ess - 1 / N).  A graph with a state outside [0, X) or a log_q that is not finite gets NaN and keeps its
+        marginals.  cutset: as in exact_inference; at most 16 variables, no limit on X^len(cutset).  self.msgs is untouched."""
+        from . import cutsetis as K
+        topo = self.topo
+        if (configs is None) != (log_q is None):
+            raise ValueError('give configs and log_q together')
+        if configs is None:
+            if roots is None or n_samples is None:
+                raise ValueError('give configs and log_q, or roots, n_samples and one of seed / uniforms')
+            configs, log_q = self.cutset_proposal(roots, n_samples, seed=seed, uniforms=uniforms, cutset=cutset)
+        elif roots is not None or n_samples is not None or seed is not None or uniforms is not None:
+            raise ValueError('configs and log_q replace roots, n_samples, seed and uniforms')
+        pl, a = self._cutset_args(K, K.CutsetisArgs, cutset, 'cutset_estimate needs float64 pairwise tables')
+        if not torch.is_tensor(log_q) or log_q.dtype != torch.float64 or log_q.device != self.device or log_q.dim() != 2 \
+                or log_q.shape[0] != self.B or not log_q.is_contiguous():
+            raise ValueError('log_q must be a contiguous float64 device tensor [B][N]')
+        N = int(log_q.shape[1])
+        if not 1 <= N <= K.MAX_LISTED:
+            raise ValueError('N must be in [1, %d]' % K.MAX_LISTED)
+        if not torch.is_tensor(configs) or configs.dtype != torch.int32 or configs.device != self.device \
+                or tuple(configs.shape) != (self.B, N, pl.n_cut) or not configs.is_contiguous():
+            raise ValueError('configs must be a contiguous int32 device tensor [B][N][n_cut]')
+        if marginals is None:
+            marginals = torch.empty(self.B, topo.n_vars, self.X, dtype=torch.float64, device=self.device)
+        elif tuple(marginals.shape) != (self.B, topo.n_vars, self.X) or marginals.dtype != torch.float64 \
+                or marginals.device != self.device or not marginals.is_contiguous():
+            raise ValueError('marginals must be a contiguous float64 device tensor [B][n_vars][X]')
+        log_z_hat = torch.empty(self.B, dtype=torch.float64, device=self.device)
+        ess = torch.empty(self.B, dtype=torch.float64, device=self.device)
+        a.N, a.log_q = N, log_q.data_ptr()
+        if pl.n_cut:
+            a.configs = configs.data_ptr()
+        a.log_z_hat, a.marginals, a.ess = log_z_hat.data_ptr(), marginals.data_ptr(), ess.data_ptr()
+        out = [log_z_hat, marginals, ess]
+        lab = None
+        if labels is not None:
+            lab = self._labels_i32(labels)
+            out.append(torch.empty(self.B, dtype=torch.float64, device=self.device))
+            a.labels, a.joint_logp = lab.data_ptr(), out[-1].data_ptr()
+        if log_w:
+            out.append(torch.empty(self.B, N, dtype=torch.float64, device=self.device))
+            a.log_w = out[-1].data_ptr()
+        need = K.workspace_bytes(self.B, self.X, topo.n_vars, topo.P, topo.U, pl.n_forest, N)
+        work = torch.empty(need // 8, dtype=torch.float64, device=self.device)
+        a.workspace, a.workspace_bytes = work.data_ptr(), need
+        K.check(K.lib.mlbp_cutsetis_f64(C.byref(a), _stream_ptr(self.device)))
+        return tuple(out)
 
     # ---- the exact MAP assignment and the max-marginals (include/mlbp_exactmap.h) ----------------------
     def exact_map(self, max_marginals=None, cutset=None):

@@ -1,4 +1,4 @@
-"""Builds libmlbp.so, libmlbp_map.so, libmlbp_logz.so, libmlbp_sample.so, libmlbp_converge.so, libmlbp_cutset.so, libmlbp_exactmap.so, libmlbp_exactgrad.so, libmlbp_exactsample.so and libmlbp_exactmbest.so (gfx950 only) in-tree with hipcc.  `python -m macaronicusermodeling_amd.build`.
+"""Builds libmlbp.so, libmlbp_map.so, libmlbp_logz.so, libmlbp_sample.so, libmlbp_converge.so, libmlbp_cutset.so, libmlbp_exactmap.so, libmlbp_exactgrad.so, libmlbp_exactsample.so, libmlbp_exactmbest.so and libmlbp_cutsetis.so (gfx950 only) in-tree with hipcc.  `python -m macaronicusermodeling_amd.build`.
 
 hipcc cross-compiles without a GPU, so this runs in the build container; the resulting .so is
 git-ignored but travels to the GPU box with the working-tree snapshot.
@@ -19,6 +19,7 @@ CSRC_EXACTMAP = os.path.join(PKG, 'csrc_exactmap')
 CSRC_EXACTGRAD = os.path.join(PKG, 'csrc_exactgrad')
 CSRC_EXACTSAMPLE = os.path.join(PKG, 'csrc_exactsample')
 CSRC_EXACTMBEST = os.path.join(PKG, 'csrc_exactmbest')
+CSRC_CUTSETIS = os.path.join(PKG, 'csrc_cutsetis')
 LIB = os.path.join(PKG, 'libmlbp.so')
 LIB_MAP = os.path.join(PKG, 'libmlbp_map.so')
 LIB_LOGZ = os.path.join(PKG, 'libmlbp_logz.so')
@@ -29,6 +30,7 @@ LIB_EXACTMAP = os.path.join(PKG, 'libmlbp_exactmap.so')
 LIB_EXACTGRAD = os.path.join(PKG, 'libmlbp_exactgrad.so')
 LIB_EXACTSAMPLE = os.path.join(PKG, 'libmlbp_exactsample.so')
 LIB_EXACTMBEST = os.path.join(PKG, 'libmlbp_exactmbest.so')
+LIB_CUTSETIS = os.path.join(PKG, 'libmlbp_cutsetis.so')
 SOURCES = ['mlbp_host.cpp', 'mlbp_compile.cpp', 'mlbp_compile_shared.cpp', 'mlbp_program.cpp', 'mlbp_dispatch.cpp', 'mlbp_sweep.hip', 'mlbp_lean.hip', 'mlbp_shared.hip', 'mlbp_gemm.hip', 'mlbp_prims.hip', 'mlbp_grad.hip']
 SOURCES_MAP = ['mlbp_map.hip']
 SOURCES_LOGZ = ['mlbp_logz.hip']
@@ -39,6 +41,7 @@ SOURCES_EXACTMAP = ['mlbp_exactmap.hip']
 SOURCES_EXACTGRAD = ['mlbp_exactgrad.hip']
 SOURCES_EXACTSAMPLE = ['mlbp_exactsample.hip']
 SOURCES_EXACTMBEST = ['mlbp_exactmbest.hip']
+SOURCES_CUTSETIS = ['mlbp_cutsetis.hip']
 # csrc/ headers: the core library's, and what the side libraries share (mlbp_graph_device.h includes mlbp_device.h)
 HEADERS = ['mlbp_internal.h', 'mlbp_device.h']
 HEADERS_SIDE = ['mlbp_device.h', 'mlbp_graph_device.h', 'mlbp_graph_host.h', 'mlbp_cutset_plan.h', 'mlbp_cutset_walk.h']
@@ -58,6 +61,7 @@ LIBRARIES = [
 # libraries added since: the same tuple shape, built after LIBRARIES
 LATER_LIBRARIES = [
     (CSRC_EXACTMBEST, SOURCES_EXACTMBEST, HEADERS_SIDE + ['../../include/mlbp_cutset.h'], 'mlbp_exactmbest.h', LIB_EXACTMBEST),   # exact M-best decoding
+    (CSRC_CUTSETIS, SOURCES_CUTSETIS, HEADERS_SIDE + ['../../include/mlbp_cutset.h'], 'mlbp_cutsetis.h', LIB_CUTSETIS),   # cutset importance sampling: log Z and marginals beyond the exact limit
 ]
 FLAGS = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-fno-fast-math', '-Wall',
          '-Wno-unused-function']
@@ -88,8 +92,8 @@ def _build_one(hipcc, csrc, sources, headers, lib, force, verbose):
 
 
 def build(force=False, verbose=False):
-    """Builds the ten libraries; returns the path of libmlbp.so (the others lie beside it: LIB_MAP, LIB_LOGZ, LIB_SAMPLE,
-    LIB_CONVERGE, LIB_CUTSET, LIB_EXACTMAP, LIB_EXACTGRAD, LIB_EXACTSAMPLE, LIB_EXACTMBEST)."""
+    """Builds the eleven libraries; returns the path of libmlbp.so (the others lie beside it: LIB_MAP, LIB_LOGZ, LIB_SAMPLE,
+    LIB_CONVERGE, LIB_CUTSET, LIB_EXACTMAP, LIB_EXACTGRAD, LIB_EXACTSAMPLE, LIB_EXACTMBEST, LIB_CUTSETIS)."""
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     for csrc, sources, headers, public, lib in LIBRARIES + LATER_LIBRARIES:
         deps = [os.path.join(CSRC, h) for h in headers] + [os.path.join(INCLUDE, public)]

@@ -1,5 +1,5 @@
-// What the three cutset-conditioning libraries share beside the walk itself (libmlbp_cutset.so, libmlbp_exactmap.so,
-// libmlbp_exactgrad.so; gfx950 only): the layout of the packed plan of include/mlbp_cutset.h and its validation, the kernel
+// What the cutset-conditioning libraries share beside the walk itself (libmlbp_cutset.so, libmlbp_exactmap.so,
+// libmlbp_exactgrad.so and their later siblings; gfx950 only): the layout of the packed plan of include/mlbp_cutset.h and its validation, the kernel
 // arguments every walk reads (WalkDev), the power-of-two arithmetic of the walks -- exponent extraction, the (mantissa,
 // exponent) pair, the rescaling of a vector by the exponent of its largest entry -- and the host core: the LDS and vector
 // sizing, the kernel pick, the chunks rule, the shape checks of a compute entry and the filling of WalkDev.  The walk over
@@ -126,8 +126,16 @@ int too_many_configs(int32_t X, int32_t n_cut) {
   return fail(MLBP_EUNSUPPORTED, "X^|C| = %d^%d configurations: at most %d are supported", X, n_cut, MLBP_CUTSET_MAX_CONFIGS);
 }
 
-// The checks of mlbp_cutset_check_plan (include/mlbp_cutset.h): a host array, for X states.
-int check_packed_plan(const int32_t* plan, int32_t n_words, int32_t X) {
+// A library that walks a caller's list of configurations (listed) has no bound on X^|C|; its bound is the walk's own: the
+// generic walker keeps the states of a configuration in st[16].
+constexpr int MAX_LISTED_CUT = 16;
+int too_many_cut(int32_t n_cut) {
+  return fail(MLBP_EUNSUPPORTED, "|C| = %d cutset variables: a listed walk takes at most %d", n_cut, MAX_LISTED_CUT);
+}
+
+// The checks of mlbp_cutset_check_plan (include/mlbp_cutset.h): a host array, for X states.  listed: the configurations come
+// from a list, so X^|C| is not bounded and |C| is.
+int check_packed_plan(const int32_t* plan, int32_t n_words, int32_t X, bool listed = false) {
   using namespace mlbp_graph;
   if (!plan || n_words < HEADER) return fail(MLBP_EINVAL, "plan: NULL or shorter than its header of %d words", HEADER);
   const int n_vars = plan[0], P = plan[1], U = plan[2], n_cut = plan[3], n_free = plan[4], n_items = plan[5], n_consts = plan[6],
@@ -151,7 +159,7 @@ int check_packed_plan(const int32_t* plan, int32_t n_words, int32_t X) {
     if (cutpos[v] >= 0) return fail(MLBP_EINVAL, "plan: cutset entry %d: variable %d is repeated", q, v);
     cutpos[v] = q;
   }
-  if (count_configs(X, n_cut) < 0) return too_many_configs(X, n_cut);
+  if (listed ? n_cut > MAX_LISTED_CUT : count_configs(X, n_cut) < 0) return listed ? too_many_cut(n_cut) : too_many_configs(X, n_cut);
   for (int i = 0; i < n_free; ++i) {
     const int v = s.order[i];
     if (v < 0 || v >= n_vars || cutpos[v] >= 0 || pos[v] >= 0)
@@ -281,9 +289,11 @@ int64_t chunk_doubles(int which, int64_t per, int64_t n_vars, int64_t P, int64_t
 
 // The checks every compute entry starts with, over the library's args struct (the field names agree): sizes, states, the
 // library's kernel pick, the plan's words, the tables, own(a) -- the library's outputs and further inputs --, the number of
-// configurations, the extent.  Returns the kernel (WALK_*) or the status; *n_configs is set with the kernel.
+// configurations, the extent.  Returns the kernel (WALK_*) or the status; *n_configs is set with the kernel.  listed: the
+// configurations come from the caller's list -- |C| is bounded in the place of X^|C|, and *n_configs is left to the library.
 template <class Args, class Own>
-int check_walk_args(const Args* a, int (*pick)(int32_t, int32_t, int32_t, int32_t, int32_t), Own own, int64_t* n_configs) {
+int check_walk_args(const Args* a, int (*pick)(int32_t, int32_t, int32_t, int32_t, int32_t), Own own, int64_t* n_configs,
+                    bool listed = false) {
   using namespace mlbp_graph;
   if (!a) return fail(MLBP_EINVAL, "args is NULL");
   if (a->B <= 0 || a->n_vars <= 0 || a->P < 0 || a->U < 0 || a->P + a->U <= 0 || a->n_cut < 0 || a->n_free < 0 || a->n_items < 0 ||
@@ -297,8 +307,12 @@ int check_walk_args(const Args* a, int (*pick)(int32_t, int32_t, int32_t, int32_
     return fail(MLBP_EINVAL, "plan is NULL or plan_words = %d disagrees with the sizes", a->plan_words);
   if (int e = check_args_tables(a)) return e;
   if (int e = own(a)) return e;
-  *n_configs = count_configs(a->X, a->n_cut);
-  if (*n_configs < 0) return too_many_configs(a->X, a->n_cut);
+  if (listed) {
+    if (a->n_cut > MAX_LISTED_CUT) return too_many_cut(a->n_cut);
+  } else {
+    *n_configs = count_configs(a->X, a->n_cut);
+    if (*n_configs < 0) return too_many_configs(a->X, a->n_cut);
+  }
   if ((int64_t)a->n_vars * a->X > 0x7fffffff / 16) return fail(MLBP_EUNSUPPORTED, "n_vars * X = %lld too large", (long long)a->n_vars * a->X);
   return which;
 }

@@ -1,5 +1,6 @@
-// The walk over cutset configurations that libmlbp_cutset.so, libmlbp_exactmap.so and libmlbp_exactgrad.so share (gfx950
-// only, float64): for one configuration of the cutset variables, the pass from the leaves of the remaining forest to its roots
+// The walk over cutset configurations that libmlbp_cutset.so, libmlbp_exactmap.so, libmlbp_exactgrad.so and their later
+// siblings share (gfx950 only, float64; libmlbp_cutsetis.so walks a caller's list with it, see "where a configuration's states
+// come from"): for one configuration of the cutset variables, the pass from the leaves of the remaining forest to its roots
 // -- which yields Z_c, or V_c in the max form -- and the pass back, which yields every free variable's belief.  Stated once,
 // over an algebra (SumAlg, MaxAlg), in the two forms the libraries run: the generic walker (any X, the workgroup one
 // configuration at a time, tables streamed) and the X = 64 walker (tables in LDS, a wave per configuration, lane = state).
@@ -183,18 +184,35 @@ __device__ __forceinline__ double generic_local(const Generic& G, int v, int j) 
   return b;
 }
 
-// Configuration c, leaves to roots: returns Z_c (V_c); st holds the configuration's states, bel[v] is left holding every free
+// ---- where a configuration's states come from ------------------------------------------------------------------------
+// A walk reads the state of cut position q as state(q).  The exact libraries number the configurations, c in [0, X^|C|), and
+// decode c's digits (GenericCode, X64Code); libmlbp_cutsetis.so walks a caller's list, a row of n_cut states (ListedStates,
+// wave-uniform loads) -- no number, so no 32-bit limit on X^|C|.
+struct GenericCode {
+  int c, X;
+  __device__ __forceinline__ int operator()(int q) const {
+    int r = c;
+    for (int i = 0; i < q; ++i) r /= X;
+    return r % X;
+  }
+};
+struct X64Code {
+  int c;
+  __device__ __forceinline__ int operator()(int q) const { return (c >> (6 * q)) & 63; }
+};
+struct ListedStates {
+  const_i32p row;                            // [n_cut], checked against [0, X) by the caller
+  __device__ __forceinline__ int operator()(int q) const { return row[q]; }
+};
+
+// A configuration, leaves to roots: returns Z_c (V_c); st holds the configuration's states, bel[v] is left holding every free
 // variable's rescaled upward vector, up (unless NULL) its rescaled message to its parent.  Reached by every thread; the first
 // barrier stands behind the last reads of st and bel of the configuration before; ends behind a barrier.
-template <class Alg>
-__device__ __forceinline__ Scaled generic_up(const Generic& G, int c, double* up) {
+template <class Alg, class State>
+__device__ __forceinline__ Scaled generic_up(const Generic& G, State state, double* up) {
   const int t = threadIdx.x, X = G.X, Xp = G.Xp;
   __syncthreads();
-  if (t < G.n_cut) {
-    int r = c;
-    for (int q = 0; q < t; ++q) r /= X;
-    G.st[t] = r % X;
-  }
+  if (t < G.n_cut) G.st[t] = state(t);
   __syncthreads();
   Scaled z = {1.0, G.e_fixed};
   for (int i = 0; i < G.n_consts; ++i) {
@@ -231,6 +249,12 @@ __device__ __forceinline__ Scaled generic_up(const Generic& G, int c, double* up
     }
   }
   return z;
+}
+
+// Configuration number c: its digits base X.
+template <class Alg>
+__device__ __forceinline__ Scaled generic_up(const Generic& G, int c, double* up) {
+  return generic_up<Alg>(G, GenericCode{c, G.X}, up);
 }
 
 // The configuration of the last generic_up (with up = G.up), roots to leaves.  Both hooks are reached by every thread of the
@@ -346,18 +370,20 @@ __device__ __forceinline__ void x64_open(X64& W, const WalkDev& d, int g, char* 
 __device__ __forceinline__ int x64_state(int q, int c) { return (c >> (6 * q)) & 63; }
 
 // the free variable's configuration-free part times its cutset-incident rows and columns, at state `lane`
-__device__ __forceinline__ double x64_local(const X64& W, int v, int c) {
+template <class State>
+__device__ __forceinline__ double x64_local(const X64& W, int v, State state) {
   const int lane = W.lane;
   double b = W.base[(size_t)v * 64 + lane];
   for (int it = W.pl.item_off[v]; it < W.pl.item_off[v + 1]; ++it) {
     const int kind = W.pl.items[3 * it];
     if (kind == MLBP_CUTSET_ITEM_UNARY) continue;
-    const int p = W.pl.items[3 * it + 1], s = x64_state(W.pl.items[3 * it + 2], c);
+    const int p = W.pl.items[3 * it + 1], s = state(W.pl.items[3 * it + 2]);
     const double* T = W.pair_tables + (size_t)W.ptab[p] * 4096;
     b *= ldexp(kind == MLBP_CUTSET_ITEM_COL ? T[lane * 64 + s] : T[s * 64 + lane], -W.texp[p]);
   }
   return b;
 }
+__device__ __forceinline__ double x64_local(const X64& W, int v, int c) { return x64_local(W, v, X64Code{c}); }
 
 // The contraction of the padded LDS table with the wave's vector (m: the entry of this lane): lane i returns
 // Alg_j T[i][j] m[j] (tm) or Alg_i m[i] T[i][lane].  Four chains of 16 steps, joined pairwise.
@@ -376,21 +402,21 @@ __device__ __forceinline__ double wave_contract_x64(const double* table, bool tm
   return Alg::join(Alg::join(a[0], a[1]), Alg::join(a[2], a[3]));
 }
 
-// Configuration c by this wave, leaves to roots: returns Z_c (V_c).  With KEEP the wave's phi, bel and up are left holding what
+// A configuration by this wave, leaves to roots: returns Z_c (V_c).  With KEEP the wave's phi, bel and up are left holding what
 // x64_down_step reads; without, bel alone is used.  No barrier: every slot is written and read by the same lane.
-template <class Alg, bool KEEP>
-__device__ __forceinline__ Scaled x64_up(const X64& W, int c) {
+template <class Alg, bool KEEP, class State>
+__device__ __forceinline__ Scaled x64_up(const X64& W, State state) {
   const int lane = W.lane;
   Scaled z = {1.0, W.e_fixed};
-  for (int q = 0; q < W.n_cut; ++q) mul(z, W.base[(size_t)W.pl.cutset[q] * 64 + x64_state(q, c)]);
+  for (int q = 0; q < W.n_cut; ++q) mul(z, W.base[(size_t)W.pl.cutset[q] * 64 + state(q)]);
   for (int i = 0; i < W.n_consts; ++i) {
     if (W.pl.consts[4 * i] != MLBP_CUTSET_CONST_PAIR) continue;
-    const int f = W.pl.consts[4 * i + 1], s0 = x64_state(W.pl.consts[4 * i + 2], c), s1 = x64_state(W.pl.consts[4 * i + 3], c);
+    const int f = W.pl.consts[4 * i + 1], s0 = state(W.pl.consts[4 * i + 2]), s1 = state(W.pl.consts[4 * i + 3]);
     mul(z, ldexp(W.pair_tables[(size_t)W.ptab[f] * 4096 + s0 * 64 + s1], -W.texp[f]));
   }
   for (int i = 0; i < W.n_free; ++i) {
     const int v = W.pl.order[i];
-    const double b = x64_local(W, v, c);
+    const double b = x64_local(W, v, state);
     W.bel[(size_t)v * 64 + lane] = b;
     if (KEEP) W.phi[(size_t)v * 64 + lane] = b;
   }
@@ -408,6 +434,12 @@ __device__ __forceinline__ Scaled x64_up(const X64& W, int c) {
     }
   }
   return z;
+}
+
+// Configuration number c: six bits per cut position.
+template <class Alg, bool KEEP>
+__device__ __forceinline__ Scaled x64_up(const X64& W, int c) {
+  return x64_up<Alg, KEEP>(W, X64Code{c});
 }
 
 // One free variable of the pass back at X = 64: what x64_down_step leaves to the library.

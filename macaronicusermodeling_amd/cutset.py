@@ -177,7 +177,7 @@ def check_plan(words, X):
 
 
 class Plan:
-    """A validated plan and its device copy.  binding: the module (this one, exactmap, exactgrad, exactsample or exactmbest) whose check_plan validates."""
+    """A validated plan and its device copy.  binding: the module (this one, exactmap, exactgrad, exactsample, exactmbest or cutsetis) whose check_plan validates."""
 
     def __init__(self, topo, cutset, X, device, binding=None):
         import torch

@@ -315,6 +315,19 @@ class UserGraphTrainer:
         agrees = (bp.argmax(dim=2) == exact.argmax(dim=2)).all(dim=1)
         return (log_z.cpu().numpy(), (bethe - log_z).cpu().numpy(), gap.cpu().numpy(), agrees.cpu().numpy(), joint.cpu().numpy())
 
+    def estimated_inference(self, n_samples, seed):
+        """The sentence shapes exact_inference() refuses: an ESTIMATE of each instance's log Z under the current thetas by
+        cutset importance sampling (FactorGraphBatch.cutset_estimate with its default proposal over the predict() schedule):
+        host (log_z_hat float64 [B], ess float64 [B] -- the effective sample size out of n_samples --, bethe_gap float64 [B] --
+        log_partition after the predict() schedule minus log_z_hat --, marginals float64 [B][n_vars][X], self-normalised).
+        Raises cutsetis.CutsetisError(MLBP_EUNSUPPORTED) for a shape the estimating library refuses."""
+        fb = self.batch
+        self.build_potentials()
+        roots = self.roots[:self.n_sweeps_run]
+        log_z_hat, marg, ess = fb.cutset_estimate(roots, n_samples=n_samples, seed=seed)
+        bethe = fb.log_partition(roots, init=True)
+        return log_z_hat.cpu().numpy(), ess.cpu().numpy(), (bethe - log_z_hat).cpu().numpy(), marg.cpu().numpy()
+
     def _plane_share(self, belief):
         """The per-instance feature planes' share of the en_de gradient, host [B][F_ed]: for every plane cell (i, observed
         column, k) of value v on a patched factor, v * ([label == i] - belief[row][i]).  belief: host [n_priv][X], the belief
@@ -1053,6 +1066,63 @@ class TiDirTrainer:
         mdist.all_reduce_max_(worst)
         tot = tot.cpu().numpy()
         return per_instance, (int(tot[0]), int(tot[1]), float(tot[2]), float(worst[0]), int(tot[3])), skipped
+
+    # ---- and the longer sentences: log Z estimated by cutset importance sampling (include/mlbp_cutsetis.h) ---------------
+    def estimate_report(self, n_samples=256, seed=0):
+        """-> (per_instance, totals, skipped).  per_instance[i], for instance i of this rank's shard in file order: (predicted
+        positions, log_z_hat, the relative standard error of the estimate of Z that its effective sample size implies,
+        sqrt(1 / ess - 1 / n_samples), log_partition after the usual sweeps minus log_z_hat, the exact log_z where
+        exact_inference() accepts the shape, else None) as UserGraphTrainer.estimated_inference gives them; an instance
+        without a pairwise factor (at most one predicted word) is solved by the sweeps and gives ((positions), None, None,
+        None, None).  The i-th sentence shape in self.trainers order draws with seed `seed + i`, as sample() does.  totals =
+        (sentences estimated, sentences also solved exactly, sum and maximum of |log_z_hat - log_z| over those, sum of
+        ess / n_samples) over ALL ranks' instances, reduced once.  skipped: [(predicted positions, instances, reason)] of this
+        rank's shapes that the estimating library refuses -- none of the shapes the exact reports skip for their size."""
+        from . import cutset as K0, cutsetis as K
+        n = self._shard[1] - self._shard[0]
+        per_instance = [((), None, None, None, None)] * n
+        seen = both = 0
+        sum_err = sum_share = 0.0
+        worst = torch.zeros(1, dtype=torch.float64, device=self.device)
+        skipped = []
+        for i, (key, tr) in enumerate(self.trainers.items()):
+            rows = self.buckets[key]['rows']
+            if not tr.topo.P:
+                for row in rows:
+                    per_instance[row['index']] = (tuple(key[1]), None, None, None, None)
+                continue
+            try:
+                log_z_hat, ess, bethe_gap, _ = tr.estimated_inference(n_samples, int(seed) + i)
+            except K.CutsetisError as e:
+                if e.code != _ffi.MLBP_EUNSUPPORTED:
+                    raise
+                skipped.append((tuple(key[1]), len(rows), str(e)))
+                for row in rows:
+                    per_instance[row['index']] = (tuple(key[1]), None, None, None, None)
+                continue
+            try:
+                log_z = tr.exact_inference()[0]
+            except K0.CutsetError as e:
+                if e.code != _ffi.MLBP_EUNSUPPORTED:
+                    raise
+                log_z = None
+            with np.errstate(divide='ignore', invalid='ignore'):
+                rse = np.sqrt(np.maximum(1.0 / ess - 1.0 / float(n_samples), 0.0))
+            seen += len(rows)
+            sum_share += float(ess.sum()) / float(n_samples)
+            if log_z is not None:
+                err = np.abs(log_z_hat - log_z)
+                both += len(rows)
+                sum_err += float(err.sum())
+                worst[0] = max(float(worst[0]), float(err.max()))
+            for b, row in enumerate(rows):
+                per_instance[row['index']] = (tuple(key[1]), float(log_z_hat[b]), float(rse[b]), float(bethe_gap[b]),
+                                              None if log_z is None else float(log_z[b]))
+        tot = torch.tensor([float(seen), float(both), sum_err, sum_share], dtype=torch.float64, device=self.device)
+        mdist.all_reduce_sum_(tot)
+        mdist.all_reduce_max_(worst)
+        tot = tot.cpu().numpy()
+        return per_instance, (int(tot[0]), int(tot[1]), float(tot[2]), float(worst[0]), float(tot[3])), skipped
 
     # ---- how wrong is the gradient the trainer follows, and a step on the true likelihood (include/mlbp_exactgrad.h) -----
     def _exact_statistics(self, on_limit='skip'):
