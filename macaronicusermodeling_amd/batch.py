@@ -588,8 +588,93 @@ class FactorGraphBatch:
             log_q[:, lo:hi] = lq.t()
         return configs, log_q
 
+    # ---- the proposal drawn from the held messages (include/mlbp_cutdraw.h) -------------------------------------------
+    def _cutdraw_refuse(self, what):
+        if self.use_approx_inference:
+            raise NotImplementedError('sampling has no top-100 approximate form')
+        if self.pair_tables is not None and self.pair_tables.dtype != torch.float64:
+            raise NotImplementedError('%s needs float64 pairwise tables' % what)
+
+    def _cutdraw_plan(self, cutset):
+        """The draw plan of a cutset given as variable ids (None: cutset.choose)."""
+        from . import cutdraw as K
+        topo = self.topo
+        if cutset is not None:
+            unknown = [v for v in cutset if v not in topo.var_index]
+            if unknown:
+                raise ValueError('cutset names unknown variable ids %r' % (unknown,))
+            cutset = [topo.var_index[v] for v in cutset]
+        return K.plan(topo, cutset, self.X, self.device)
+
+    def _cutdraw(self, what, N, cutset, uniforms=None, configs_in=None):
+        """One call into libmlbp_cutdraw.so: (configs or None, log_q).  N: entries per graph."""
+        from . import cutdraw as K
+        self._cutdraw_refuse(what)
+        topo = self.topo
+        pl = self._cutdraw_plan(cutset)
+        shape = (self.B, N, pl.n_cut)
+        log_q = torch.zeros(self.B, N, dtype=torch.float64, device=self.device)
+        configs = None
+        if configs_in is None:
+            configs = torch.empty(shape, dtype=torch.int32, device=self.device)
+            if uniforms is not None and (not torch.is_tensor(uniforms) or uniforms.dtype != torch.float64 or uniforms.device != self.device
+                                         or tuple(uniforms.shape) != shape or not uniforms.is_contiguous()):
+                raise ValueError('uniforms must be a contiguous float64 device tensor [B][n_samples][n_cut]')
+        elif (not torch.is_tensor(configs_in) or configs_in.dtype != torch.int32 or configs_in.device != self.device
+              or tuple(configs_in.shape) != shape or not configs_in.is_contiguous()):
+            raise ValueError('configs must be a contiguous int32 device tensor [B][N][n_cut]')
+        if not pl.n_cut:                                        # a tree: the one empty configuration, nothing to launch
+            return configs, log_q
+        a = K.CutdrawArgs()
+        a.B, a.X, a.n_msgs, a.P, a.n_cut, a.N = self.B, self.X, topo.n_msgs, topo.P, pl.n_cut, N
+        a.plan, a.plan_words = pl.dev.data_ptr(), len(pl.words)
+        if topo.P:
+            if self.pair_tables is None:
+                raise RuntimeError('set_pair_tables() first')
+            a.n_pair_tables = self.pair_tables.shape[0]
+            a.pair_tables, a.pair_tab = self.pair_tables.data_ptr(), self.pair_tab.data_ptr()
+        a.msgs, a.log_q = self.msgs.data_ptr(), log_q.data_ptr()
+        if configs_in is None:
+            a.uniforms, a.configs = uniforms.data_ptr(), configs.data_ptr()
+        else:
+            a.configs_in = configs_in.data_ptr()
+        K.check(K.lib.mlbp_cutdraw_f64(C.byref(a), _stream_ptr(self.device)))
+        return configs, log_q
+
+    def cutset_draw(self, n_samples, seed=None, uniforms=None, cutset=None):
+        """The proposal of cutset_estimate(proposal='messages'): n_samples joint states of the cutset per graph drawn from the
+        messages self.msgs holds AS THEY STAND -- run sweep() or converge() first, as before marginals() -- in one launch and
+        without sweeping again.  The cutset variables are drawn in cutset order, each from the product of its incoming
+        messages with the messages from cutset variables already drawn replaced by the table's row or column at the drawn
+        state (include/mlbp_cutdraw.h).  Returns (configs int32 [B][N][n_cut], log_q float64 [B][N]) device tensors, the list
+        cutset_estimate(configs=..., log_q=...) takes.  Exactly one of `seed` and `uniforms`: uniforms is a contiguous float64
+        [B][N][n_cut] device tensor of numbers in [0, 1); seed means torch.rand((B, N, n_cut), dtype=float64, device=...,
+        generator=torch.Generator(device).manual_seed(seed)).  cutset: as in cutset_estimate.  The first cutset variable is
+        drawn from its loopy-BP marginal; on a tree with converged messages and a connected cutset the proposal is Z_c / Z
+        itself.  A tree (no cutset) gives configs [B][N][0] and log_q 0 without a launch.  self.msgs is read, not written."""
+        from . import cutdraw as K
+        if (seed is None) == (uniforms is None):
+            raise ValueError('give exactly one of seed and uniforms')
+        self._cutdraw_refuse('cutset_draw')
+        N = int(n_samples)
+        if not 1 <= N <= K.MAX_LISTED:
+            raise ValueError('n_samples must be in [1, %d]' % K.MAX_LISTED)
+        if uniforms is None:
+            gen = torch.Generator(self.device).manual_seed(int(seed))
+            uniforms = torch.rand((self.B, N, self._cutdraw_plan(cutset).n_cut), dtype=torch.float64, device=self.device, generator=gen)
+        return self._cutdraw('cutset_draw', N, cutset, uniforms=uniforms)
+
+    def cutset_logq(self, configs, cutset=None):
+        """log_q float64 [B][N] of the joint states `configs` (contiguous int32 [B][N][n_cut] device tensor) under the proposal
+        of cutset_draw() and the messages self.msgs holds: the second mode of include/mlbp_cutdraw.h.  Of a list cutset_draw()
+        drew it returns that call's log_q bit for bit; a state outside [0, X) gives NaN for its entry."""
+        from . import cutdraw as K
+        if not torch.is_tensor(configs) or configs.dim() != 3 or not 1 <= int(configs.shape[1]) <= K.MAX_LISTED:
+            raise ValueError('configs must be a contiguous int32 device tensor [B][N][n_cut] with N in [1, %d]' % K.MAX_LISTED)
+        return self._cutdraw('cutset_logq', int(configs.shape[1]), cutset, configs_in=configs)[1]
+
     def cutset_estimate(self, roots=None, n_samples=None, seed=None, uniforms=None, configs=None, log_q=None, labels=None,
-                        marginals=None, cutset=None, log_w=False):
+                        marginals=None, cutset=None, log_w=False, proposal='sample'):
         """An ESTIMATE of log Z and of the marginals of every graph by cutset importance sampling -- for the graphs whose
         cutset has more joint states than exact_inference() sums (more than 65536: K5 and up at X = 64).  N joint states c_i of
         the cutset are listed per graph with the log-probability a proposal q gave each; the conditioned forest is solved
@@ -602,12 +687,24 @@ class FactorGraphBatch:
         marginals are self-normalised, sum of w_i m_c / sum of w_i: consistent, not unbiased.  ess = (sum w)^2 / sum w^2 is the
         effective sample size, N for a perfect proposal; the relative standard error of the estimate of Z it implies is
         sqrt(1 / ess - 1 / N).  A graph with a state outside [0, X) or a log_q that is not finite gets NaN and keeps its
-        marginals.  cutset: as in exact_inference; at most 16 variables, no limit on X^len(cutset).  self.msgs is untouched."""
+        marginals.  cutset: as in exact_inference; at most 16 variables, no limit on X^len(cutset).  self.msgs is untouched.
+        proposal='messages' makes the list with cutset_draw() in the place of cutset_proposal(): n_samples and one of seed /
+        uniforms ([B][N][n_cut]) as cutset_draw() takes them.  Given `roots`, sweep(roots, init=True) runs first -- THAT WRITES
+        self.msgs --; with roots=None the messages self.msgs holds are used as they stand."""
         from . import cutsetis as K
         topo = self.topo
+        if proposal not in ('sample', 'messages'):
+            raise ValueError("proposal must be 'sample' or 'messages', not %r" % (proposal,))
         if (configs is None) != (log_q is None):
             raise ValueError('give configs and log_q together')
-        if configs is None:
+        if configs is None and proposal == 'messages':
+            if n_samples is None:
+                raise ValueError('give configs and log_q, or n_samples and one of seed / uniforms')
+            self._cutdraw_refuse('cutset_estimate')
+            if roots is not None:
+                self.sweep(roots, init=True)
+            configs, log_q = self.cutset_draw(n_samples, seed=seed, uniforms=uniforms, cutset=cutset)
+        elif configs is None:
             if roots is None or n_samples is None:
                 raise ValueError('give configs and log_q, or roots, n_samples and one of seed / uniforms')
             configs, log_q = self.cutset_proposal(roots, n_samples, seed=seed, uniforms=uniforms, cutset=cutset)

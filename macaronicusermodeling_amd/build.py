@@ -1,4 +1,4 @@
-"""Builds libmlbp.so, libmlbp_map.so, libmlbp_logz.so, libmlbp_sample.so, libmlbp_converge.so, libmlbp_cutset.so, libmlbp_exactmap.so, libmlbp_exactgrad.so, libmlbp_exactsample.so, libmlbp_exactmbest.so and libmlbp_cutsetis.so (gfx950 only) in-tree with hipcc.  `python -m macaronicusermodeling_amd.build`.
+"""Builds libmlbp.so, libmlbp_map.so, libmlbp_logz.so, libmlbp_sample.so, libmlbp_converge.so, libmlbp_cutset.so, libmlbp_exactmap.so, libmlbp_exactgrad.so, libmlbp_exactsample.so, libmlbp_exactmbest.so, libmlbp_cutsetis.so and libmlbp_cutdraw.so (gfx950 only) in-tree with hipcc.  `python -m macaronicusermodeling_amd.build`.
 
 hipcc cross-compiles without a GPU, so this runs in the build container; the resulting .so is
 git-ignored but travels to the GPU box with the working-tree snapshot.
@@ -20,6 +20,7 @@ CSRC_EXACTGRAD = os.path.join(PKG, 'csrc_exactgrad')
 CSRC_EXACTSAMPLE = os.path.join(PKG, 'csrc_exactsample')
 CSRC_EXACTMBEST = os.path.join(PKG, 'csrc_exactmbest')
 CSRC_CUTSETIS = os.path.join(PKG, 'csrc_cutsetis')
+CSRC_CUTDRAW = os.path.join(PKG, 'csrc_cutdraw')
 LIB = os.path.join(PKG, 'libmlbp.so')
 LIB_MAP = os.path.join(PKG, 'libmlbp_map.so')
 LIB_LOGZ = os.path.join(PKG, 'libmlbp_logz.so')
@@ -31,6 +32,7 @@ LIB_EXACTGRAD = os.path.join(PKG, 'libmlbp_exactgrad.so')
 LIB_EXACTSAMPLE = os.path.join(PKG, 'libmlbp_exactsample.so')
 LIB_EXACTMBEST = os.path.join(PKG, 'libmlbp_exactmbest.so')
 LIB_CUTSETIS = os.path.join(PKG, 'libmlbp_cutsetis.so')
+LIB_CUTDRAW = os.path.join(PKG, 'libmlbp_cutdraw.so')
 SOURCES = ['mlbp_host.cpp', 'mlbp_compile.cpp', 'mlbp_compile_shared.cpp', 'mlbp_program.cpp', 'mlbp_dispatch.cpp', 'mlbp_sweep.hip', 'mlbp_lean.hip', 'mlbp_shared.hip', 'mlbp_gemm.hip', 'mlbp_prims.hip', 'mlbp_grad.hip']
 SOURCES_MAP = ['mlbp_map.hip']
 SOURCES_LOGZ = ['mlbp_logz.hip']
@@ -42,9 +44,10 @@ SOURCES_EXACTGRAD = ['mlbp_exactgrad.hip']
 SOURCES_EXACTSAMPLE = ['mlbp_exactsample.hip']
 SOURCES_EXACTMBEST = ['mlbp_exactmbest.hip']
 SOURCES_CUTSETIS = ['mlbp_cutsetis.hip']
+SOURCES_CUTDRAW = ['mlbp_cutdraw.hip']
 # csrc/ headers: the core library's, and what the side libraries share (mlbp_graph_device.h includes mlbp_device.h)
 HEADERS = ['mlbp_internal.h', 'mlbp_device.h']
-HEADERS_SIDE = ['mlbp_device.h', 'mlbp_graph_device.h', 'mlbp_graph_host.h', 'mlbp_cutset_plan.h', 'mlbp_cutset_walk.h']
+HEADERS_SIDE = ['mlbp_device.h', 'mlbp_graph_device.h', 'mlbp_graph_host.h', 'mlbp_cutset_plan.h', 'mlbp_cutset_walk.h', 'mlbp_draw_device.h']
 # (source dir, sources, csrc/ headers, public header, output): every library has its own sources and its own kernel
 # inventory; the flags are the same
 LIBRARIES = [
@@ -62,6 +65,11 @@ LIBRARIES = [
 LATER_LIBRARIES = [
     (CSRC_EXACTMBEST, SOURCES_EXACTMBEST, HEADERS_SIDE + ['../../include/mlbp_cutset.h'], 'mlbp_exactmbest.h', LIB_EXACTMBEST),   # exact M-best decoding
     (CSRC_CUTSETIS, SOURCES_CUTSETIS, HEADERS_SIDE + ['../../include/mlbp_cutset.h'], 'mlbp_cutsetis.h', LIB_CUTSETIS),   # cutset importance sampling: log Z and marginals beyond the exact limit
+]
+# and since those: a third list, because the tests of the earlier libraries pin len(LIBRARIES) == 9 and
+# len(LIBRARIES) + len(LATER_LIBRARIES) == 11
+MORE_LIBRARIES = [
+    (CSRC_CUTDRAW, SOURCES_CUTDRAW, HEADERS_SIDE, 'mlbp_cutdraw.h', LIB_CUTDRAW),   # the cutset proposal drawn from held messages
 ]
 FLAGS = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-fno-fast-math', '-Wall',
          '-Wno-unused-function']
@@ -92,10 +100,10 @@ def _build_one(hipcc, csrc, sources, headers, lib, force, verbose):
 
 
 def build(force=False, verbose=False):
-    """Builds the eleven libraries; returns the path of libmlbp.so (the others lie beside it: LIB_MAP, LIB_LOGZ, LIB_SAMPLE,
-    LIB_CONVERGE, LIB_CUTSET, LIB_EXACTMAP, LIB_EXACTGRAD, LIB_EXACTSAMPLE, LIB_EXACTMBEST, LIB_CUTSETIS)."""
+    """Builds the twelve libraries; returns the path of libmlbp.so (the others lie beside it: LIB_MAP, LIB_LOGZ, LIB_SAMPLE,
+    LIB_CONVERGE, LIB_CUTSET, LIB_EXACTMAP, LIB_EXACTGRAD, LIB_EXACTSAMPLE, LIB_EXACTMBEST, LIB_CUTSETIS, LIB_CUTDRAW)."""
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    for csrc, sources, headers, public, lib in LIBRARIES + LATER_LIBRARIES:
+    for csrc, sources, headers, public, lib in LIBRARIES + LATER_LIBRARIES + MORE_LIBRARIES:
         deps = [os.path.join(CSRC, h) for h in headers] + [os.path.join(INCLUDE, public)]
         _build_one(hipcc, csrc, sources, deps, lib, force, verbose)
     return LIB

@@ -315,15 +315,23 @@ class UserGraphTrainer:
         agrees = (bp.argmax(dim=2) == exact.argmax(dim=2)).all(dim=1)
         return (log_z.cpu().numpy(), (bethe - log_z).cpu().numpy(), gap.cpu().numpy(), agrees.cpu().numpy(), joint.cpu().numpy())
 
-    def estimated_inference(self, n_samples, seed):
+    def estimated_inference(self, n_samples, seed, proposal='sample'):
         """The sentence shapes exact_inference() refuses: an ESTIMATE of each instance's log Z under the current thetas by
         cutset importance sampling (FactorGraphBatch.cutset_estimate with its default proposal over the predict() schedule):
         host (log_z_hat float64 [B], ess float64 [B] -- the effective sample size out of n_samples --, bethe_gap float64 [B] --
         log_partition after the predict() schedule minus log_z_hat --, marginals float64 [B][n_vars][X], self-normalised).
+        proposal='messages': log_partition over the predict() schedule runs FIRST and the list is drawn by
+        FactorGraphBatch.cutset_draw from the messages that call leaves -- the proposal then costs no sweep of its own.
         Raises cutsetis.CutsetisError(MLBP_EUNSUPPORTED) for a shape the estimating library refuses."""
         fb = self.batch
         self.build_potentials()
         roots = self.roots[:self.n_sweeps_run]
+        if proposal == 'messages':
+            bethe = fb.log_partition(roots, init=True)
+            log_z_hat, marg, ess = fb.cutset_estimate(n_samples=n_samples, seed=seed, proposal='messages')
+            return log_z_hat.cpu().numpy(), ess.cpu().numpy(), (bethe - log_z_hat).cpu().numpy(), marg.cpu().numpy()
+        if proposal != 'sample':
+            raise ValueError("proposal must be 'sample' or 'messages', not %r" % (proposal,))
         log_z_hat, marg, ess = fb.cutset_estimate(roots, n_samples=n_samples, seed=seed)
         bethe = fb.log_partition(roots, init=True)
         return log_z_hat.cpu().numpy(), ess.cpu().numpy(), (bethe - log_z_hat).cpu().numpy(), marg.cpu().numpy()
@@ -1068,13 +1076,14 @@ class TiDirTrainer:
         return per_instance, (int(tot[0]), int(tot[1]), float(tot[2]), float(worst[0]), int(tot[3])), skipped
 
     # ---- and the longer sentences: log Z estimated by cutset importance sampling (include/mlbp_cutsetis.h) ---------------
-    def estimate_report(self, n_samples=256, seed=0):
+    def estimate_report(self, n_samples=256, seed=0, proposal='sample'):
         """-> (per_instance, totals, skipped).  per_instance[i], for instance i of this rank's shard in file order: (predicted
         positions, log_z_hat, the relative standard error of the estimate of Z that its effective sample size implies,
         sqrt(1 / ess - 1 / n_samples), log_partition after the usual sweeps minus log_z_hat, the exact log_z where
         exact_inference() accepts the shape, else None) as UserGraphTrainer.estimated_inference gives them; an instance
         without a pairwise factor (at most one predicted word) is solved by the sweeps and gives ((positions), None, None,
-        None, None).  The i-th sentence shape in self.trainers order draws with seed `seed + i`, as sample() does.  totals =
+        None, None).  The i-th sentence shape in self.trainers order draws with seed `seed + i`, as sample() does; proposal:
+        'sample' or 'messages', handed to UserGraphTrainer.estimated_inference.  totals =
         (sentences estimated, sentences also solved exactly, sum and maximum of |log_z_hat - log_z| over those, sum of
         ess / n_samples) over ALL ranks' instances, reduced once.  skipped: [(predicted positions, instances, reason)] of this
         rank's shapes that the estimating library refuses -- none of the shapes the exact reports skip for their size."""
@@ -1092,7 +1101,7 @@ class TiDirTrainer:
                     per_instance[row['index']] = (tuple(key[1]), None, None, None, None)
                 continue
             try:
-                log_z_hat, ess, bethe_gap, _ = tr.estimated_inference(n_samples, int(seed) + i)
+                log_z_hat, ess, bethe_gap, _ = tr.estimated_inference(n_samples, int(seed) + i, proposal=proposal)
             except K.CutsetisError as e:
                 if e.code != _ffi.MLBP_EUNSUPPORTED:
                     raise

@@ -1,0 +1,532 @@
+"""The cutset proposal drawn from held messages, without a GPU: the NumPy statement of include/mlbp_cutdraw.h pinned on
+exhaustive enumeration, the draw plan, the C ABI of libmlbp_cutdraw.so, its host functions and the kernel inventory rule
+applied to the twelfth library.
+
+References.  `stated()` is the header in NumPy, written from the GraphTopology arrays (the in-slots, the facsets, the table
+axes) and not from the packed plan: the product of a position's base messages, the table rows at the states already drawn, a
+power of two after every multiplication, the draw rule on sequential prefix sums.  The properties the header claims are held
+against test_cutset_cpu.enumerate_exact's log-domain grid and the oracle's marginals; nothing of the code under test is in
+either.
+
+No test here or in the GPU module asserts a statistical accuracy: every assertion is a deterministic function of its inputs.
+FAMILIES lists every input family the GPU module holds against the statement; test_every_gpu_input_clears_its_boundaries
+asserts for each, with no exclusions, that every draw of the statement stays 1e-8 * total away from the prefix sums it is
+compared with -- so the device's other summation order cannot move a state -- and that every log_q is finite."""
+import ctypes
+import functools
+import itertools
+import os
+import re
+
+import numpy as np
+import pytest
+
+import cases as C
+import helpers
+import kernel_inventory as K
+import test_cutset_cpu as R
+from conftest import ROOT
+from oracle import lbp_oracle as O
+
+
+# ------------------------------------------------------------------------------------------------
+# the statement
+# ------------------------------------------------------------------------------------------------
+def items_of(topo, cut):
+    """Per position of `cut` (variable indices): (base message slots, rows [(pair slot, earlier position, this variable's
+    axis)]) from the in-slots of the marginal read-out, the facsets and the pair factors' axes."""
+    from macaronicusermodeling_amd import cutset as S
+    edges = S.pair_edges(topo)                                  # (variable on axis 0, variable on axis 1) by pair slot
+    out = []
+    for k, a in enumerate(cut):
+        base, rows = [], []
+        for n, j in enumerate(topo.facsets[a]):
+            slot = int(topo.in_slots[topo.in_off[a] + n])
+            if j in topo.pair_factors:
+                p = topo.pair_factors.index(j)
+                axis = 0 if edges[p][0] == a else 1
+                other = edges[p][1 - axis]
+                if other in cut[:k]:
+                    rows.append((p, cut.index(other), axis))
+                    continue
+            base.append(slot)
+        out.append((base, rows))
+    return out
+
+
+def pair_tables_of(spec, topo, inputs):
+    g = O.Graph(spec)
+    return [np.asarray(O.factor_table(g, inputs, g.by_id[topo.factor_ids[j]]), dtype=np.float64).reshape(spec['X'], spec['X'])
+            for j in topo.pair_factors]
+
+
+def _scaled(v):
+    """v times 2^-e, e the binary exponent of its largest entry (NaNs passed over); skipped when that is 0 or not finite."""
+    with np.errstate(invalid='ignore'):
+        m = np.fmax.reduce(v)
+    if not (m > 0.0) or not np.isfinite(m):
+        return v
+    e = max(int(np.frexp(m)[1]) - 1, -1023)
+    return np.ldexp(v, -e)
+
+
+def stated(spec, inputs, msgs, cutset, uniforms=None, configs_in=None):
+    """include/mlbp_cutdraw.h for one graph.  msgs: [n_msgs][X] in slot order; cutset: variable ids; uniforms [N][n_cut] or
+    configs_in [N][n_cut].  -> dict(configs int32 [N][n_cut], log_q [N], clear [N][n_cut]: the distance of thr from the
+    nearest prefix sum, over total (first mode))."""
+    topo = R._topo(spec)
+    X = spec['X']
+    cut = [topo.var_index[v] for v in cutset]
+    items = items_of(topo, cut)
+    tabs = pair_tables_of(spec, topo, inputs)
+    given = configs_in is not None
+    src = np.asarray(configs_in if given else uniforms).reshape(-1, len(cut))
+    N = len(src)
+    configs = np.zeros((N, len(cut)), dtype=np.int32)
+    log_q, clear = np.zeros(N), np.full((N, len(cut)), np.inf)
+    for i in range(N):
+        if given and ((src[i] < 0) | (src[i] >= X)).any():
+            configs[i], log_q[i] = src[i], np.nan
+            continue
+        lq = 0.0
+        for k, (base, rows) in enumerate(items):
+            v = np.array(msgs[base[0]], dtype=np.float64) if base else np.ones(X)
+            with np.errstate(invalid='ignore', over='ignore'):
+                for slot in base[1:]:
+                    v = _scaled(v * msgs[slot])
+                for p, j, axis in rows:
+                    c = int(configs[i, j])
+                    v = _scaled(v * (tabs[p][c, :] if axis == 1 else tabs[p][:, c]))
+                A = np.cumsum(v)
+                total = A[-1]
+                if given:
+                    s = int(src[i, k])
+                else:
+                    thr = src[i, k] * total
+                    cross, live = np.nonzero((A > thr) & (v > 0))[0], np.nonzero(v > 0)[0]
+                    s = int(cross[0]) if len(cross) else int(live[-1]) if len(live) else 0
+                    if total > 0:
+                        clear[i, k] = np.abs(A - thr).min() / total
+                configs[i, k] = s
+                with np.errstate(divide='ignore'):
+                    lq = lq + (-np.inf if total == 0 else np.log(v[s] / total))
+        log_q[i] = lq
+    return dict(configs=configs, log_q=log_q, clear=clear)
+
+
+def every_config(X, n_cut):
+    return np.array(list(itertools.product(range(X), repeat=n_cut)), dtype=np.int32).reshape(X ** n_cut, n_cut)
+
+
+def swept(spec, inputs, roots=None):
+    """(graph, oracle messages, [n_msgs][X] in slot order) after sweeps rooted at `roots` (default: every variable in turn)."""
+    return helpers.oracle_msgs(spec, inputs, list(O.Graph(spec).var_order) if roots is None else roots)
+
+
+def conditioned(g, inputs, cutset):
+    """(log Z, {configuration: log Z_c}) by enumeration."""
+    log_z, _, grid = R.enumerate_exact(g, inputs)
+    order = list(g.var_order)
+    out = {}
+    for c in itertools.product(range(g.X), repeat=len(cutset)):
+        ix = tuple(int(c[cutset.index(v)]) if v in cutset else slice(None) for v in order)
+        out[c] = R.logsumexp(np.asarray(grid[ix]))
+    return log_z, out
+
+
+# ------------------------------------------------------------------------------------------------
+# what the header claims, by enumeration
+# ------------------------------------------------------------------------------------------------
+SUMS = [('k4_x4', lambda: R.kn_spec(4, 4)), ('k5_x3', lambda: R.kn_spec(5, 3)), ('ring5_x4', lambda: C.ring_spec(5, 4))]
+
+
+@pytest.mark.parametrize('name,make', SUMS, ids=[n for n, _ in SUMS])
+def test_the_proposal_sums_to_one(name, make):
+    """Every configuration through the second mode: sum_c exp(log_q) = 1 at 1e-12, with the messages of the oracle's sweeps and
+    with arbitrary positive messages; and the drawn list's log_q is the second mode's of its states."""
+    spec = make()
+    cut = R.chosen_ids(spec)
+    configs = every_config(spec['X'], len(cut))
+    for seed in (1, 2):
+        inputs = C.make_inputs(spec, seed, 'lognormal')
+        _, _, msgs = swept(spec, inputs)
+        rs = np.random.RandomState(seed)
+        for m in (msgs, np.exp(2.0 * rs.randn(*msgs.shape))):
+            out = stated(spec, inputs, m, cut, configs_in=configs)
+            assert abs(np.exp(out['log_q']).sum() - 1.0) <= 1e-12, (name, seed)
+            assert np.ptp(out['log_q']) > 1e-3                  # not the uniform distribution
+            drawn = stated(spec, inputs, m, cut, uniforms=rs.rand(9, len(cut)))
+            again = stated(spec, inputs, m, cut, configs_in=drawn['configs'])
+            assert np.array_equal(again['log_q'], drawn['log_q'])
+
+
+def test_position_zero_is_the_bp_marginal():
+    """q summed over the later positions is the oracle's marginal of cutset[0], at 1e-12."""
+    for spec, cut in ((R.kn_spec(4, 4), [0, 1]), (R.kn_spec(4, 4), [1, 0]), (R.kn_spec(5, 3), [2, 0, 4]), (C.ring_spec(5, 4), [3])):
+        inputs = C.make_inputs(spec, 3, 'lognormal')
+        g, msgs, arr = swept(spec, inputs)
+        configs = every_config(spec['X'], len(cut))
+        q = np.exp(stated(spec, inputs, arr, cut, configs_in=configs)['log_q'])
+        first = np.array([q[configs[:, 0] == s].sum() for s in range(spec['X'])])
+        assert np.abs(first - O.marginal(g, msgs, cut[0])).max() <= 1e-12, (spec['name'], cut)
+
+
+def test_the_tree_identity_and_its_condition():
+    """On a tree with BP's fixed point and a connected cutset listed so that every variable has one earlier neighbour,
+    exp(log_q(c)) = Z_c / Z at 1e-10.  Two leaves of a star are not connected: the identity fails there by more than 1e-3."""
+    for spec, cut, holds in ((C.chain_spec(4, 4), [1, 2, 0], True), (C.star_spec(4, 4), [0, 2], True), (C.star_spec(4, 4), [1, 3], False)):
+        for seed in (1, 2):
+            inputs = C.make_inputs(spec, seed, 'lognormal')
+            g, _, arr = swept(spec, inputs)
+            log_z, log_zc = conditioned(g, inputs, cut)
+            configs = every_config(spec['X'], len(cut))
+            q = np.exp(stated(spec, inputs, arr, cut, configs_in=configs)['log_q'])
+            want = np.array([np.exp(log_zc[tuple(int(s) for s in c)] - log_z) for c in configs])
+            assert abs(q.sum() - 1) <= 1e-12 and abs(want.sum() - 1) <= 1e-10
+            gap = np.abs(q - want).max()
+            assert (gap <= 1e-10) if holds else (gap > 1e-3), (spec['name'], cut, gap)
+
+
+def test_edge_rules_of_the_statement():
+    """An empty conditional: state 0 and -inf, the later position drawn as usual.  A state outside [0, X): NaN.  A NaN message:
+    NaN and states in range.  Uniforms 1.0 and NaN: the highest state of positive weight."""
+    spec = R.kn_spec(4, 4)
+    inputs = C.make_inputs(spec, 1, 'lognormal')
+    _, _, msgs = swept(spec, inputs)
+    topo = R._topo(spec)
+    (_, rows) = items_of(topo, [0, 1])[1]
+    p, _, axis = rows[0]
+    f = topo.factor_ids[topo.pair_factors[p]]
+    dead = dict(tables=[t.copy() for t in inputs['tables']])
+    T = dead['tables'][O.Graph(spec).by_id[f]['table']]
+    if axis == 1:
+        T[2, :] = 0.0
+    else:
+        T[:, 2] = 0.0
+    out = stated(spec, dead, msgs, [0, 1], configs_in=np.array([[2, 1], [1, 1]]))
+    assert out['log_q'][0] == -np.inf and np.isfinite(out['log_q'][1])
+    out = stated(spec, inputs, msgs, [0, 1], configs_in=np.array([[4, 0], [0, -1], [3, 3]]))
+    assert np.isnan(out['log_q'][:2]).all() and np.isfinite(out['log_q'][2])
+    bad = msgs.copy()
+    bad[items_of(topo, [0, 1])[0][0][0], 1] = np.nan
+    out = stated(spec, inputs, bad, [0, 1], uniforms=np.array([[0.3, 0.6]]))
+    assert np.isnan(out['log_q']).all() and (out['configs'] >= 0).all() and (out['configs'] < 4).all()
+    out = stated(spec, inputs, msgs, [0, 1], uniforms=np.array([[1.0, np.nan]]))
+    assert (out['configs'] == 3).all() and np.isfinite(out['log_q']).all()
+
+
+# ------------------------------------------------------------------------------------------------
+# every input of the GPU module: name -> (spec, table kind, input seeds, cutset ids or None, N)
+# ------------------------------------------------------------------------------------------------
+INPUTS = {
+    'k3_x64': (lambda: R.kn_spec(3, 64), 'lognormal', (1, 2, 3), None, 5),                # one position: the base alone
+    'k4_x64_col': (lambda: R.kn_spec(4, 64), 'lognormal', (1, 2), [1, 0], 6),             # the column read
+    'k6_x64': (lambda: R.kn_spec(6, 64), 'lognormal', (1, 2), None, 7),                   # four positions, N no multiple of 4
+    'k9_x64': (lambda: R.kn_spec(9, 64), 'uniform', (1,), None, 3),                       # walkers without an entry
+    'k3_x64_n600': (lambda: R.kn_spec(3, 64), 'lognormal', (4,), None, 600),              # C = 512: the stride 4 C wraps
+    'ring3_x2': (lambda: C.ring_spec(3, 2), 'lognormal', (7, 8), None, 16),
+    'k5_x7': (lambda: R.kn_spec(5, 7), 'lognormal', (1, 2, 3), None, 9),
+    'k4_x33': (lambda: R.kn_spec(4, 33), 'lognormal', (1, 2), None, 5),
+    'ring3_x65': (lambda: C.ring_spec(3, 65), 'lognormal', (7, 8), None, 6),
+    'ring3_x257': (lambda: C.ring_spec(3, 257), 'lognormal', (7, 8), None, 4),
+    'k3_x1024': (lambda: R.kn_spec(3, 1024), 'uniform', (9,), None, 2),
+    'k4_x4': (lambda: R.kn_spec(4, 4), 'lognormal', (1, 2), None, 16),                    # the second mode lists all 16
+}
+
+
+@functools.lru_cache(maxsize=None)
+def family(name):
+    """(spec, [inputs], cutset ids, uniforms [B][N][n_cut], [the oracle's messages in slot order per graph]): computed once per
+    process and shared; nothing in it is changed by a test."""
+    make, kind, seeds, cutset, N = INPUTS[name]
+    spec = make()
+    cut = R.chosen_ids(spec) if cutset is None else list(cutset)
+    inputs = [C.make_inputs(spec, s, kind) for s in seeds]
+    uniforms = np.random.RandomState(100 + len(name)).rand(len(inputs), N, len(cut))
+    return spec, inputs, cut, uniforms, [swept(spec, i)[2] for i in inputs]
+
+
+@pytest.mark.parametrize('name', sorted(INPUTS))
+def test_every_gpu_input_clears_its_boundaries(name):
+    spec, inputs, cut, uniforms, msgs = family(name)
+    worst = np.inf
+    for b, i in enumerate(inputs):
+        out = stated(spec, i, msgs[b], cut, uniforms=uniforms[b])
+        assert np.isfinite(out['log_q']).all() and (out['configs'] >= 0).all() and (out['configs'] < spec['X']).all(), (name, b)
+        worst = min(worst, float(out['clear'].min()))
+    print('%s: the closest draw is %.1e * total from a prefix sum' % (name, worst))
+    assert worst >= 1e-8, (name, worst)
+
+
+# ------------------------------------------------------------------------------------------------
+# the draw plan
+# ------------------------------------------------------------------------------------------------
+def _M():
+    from macaronicusermodeling_amd import cutdraw
+    return cutdraw
+
+
+def _ffi():
+    from macaronicusermodeling_amd import _ffi
+    return _ffi
+
+
+def _sections(M, words):
+    n_cut, n_base, n_rows = (int(w) for w in words[3:6])
+    at = M.PLAN_HEADER
+    cut = [int(w) for w in words[at:at + n_cut]]; at += n_cut
+    base_off = [int(w) for w in words[at:at + n_cut + 1]]; at += n_cut + 1
+    slots = [int(w) for w in words[at:at + n_base]]; at += n_base
+    row_off = [int(w) for w in words[at:at + n_cut + 1]]; at += n_cut + 1
+    rows = [tuple(int(w) for w in words[at + 3 * r:at + 3 * r + 3]) for r in range(n_rows)]
+    assert at + 3 * n_rows == len(words)
+    return cut, base_off, slots, row_off, rows
+
+
+PLANS = [('k4', lambda: R.kn_spec(4, 4), [0, 1]), ('k4_col', lambda: R.kn_spec(4, 4), [1, 0]), ('k6', lambda: R.kn_spec(6, 4), [0, 1, 2, 3]),
+         ('k6_mixed', lambda: R.kn_spec(6, 4), [4, 1, 5, 0]), ('ring5', lambda: C.ring_spec(5, 4), [0]), ('chain4', lambda: C.chain_spec(4, 4), [1, 2, 0]),
+         ('star4', lambda: C.star_spec(4, 4), [0, 2]), ('double_pair', lambda: R.double_pair_spec(4), [0, 1]), ('tree', lambda: C.chain_spec(3, 4), [])]
+
+
+@pytest.mark.parametrize('name,make,cutset', PLANS, ids=[p[0] for p in PLANS])
+def test_plan_words_are_the_statements_items(name, make, cutset):
+    M = _M()
+    spec = make()
+    topo = R._topo(spec)
+    cut = [topo.var_index[v] for v in cutset]
+    words = M.plan_words(topo, cut)
+    assert words.dtype == np.int32 and [int(w) for w in words[:M.PLAN_HEADER]] == [topo.n_vars, topo.P, topo.n_msgs, len(cut)] + [int(w) for w in words[4:6]] + [0, 0]
+    M.check_plan(words, spec['X'], topo.n_msgs)
+    got_cut, base_off, slots, row_off, rows = _sections(M, words)
+    assert got_cut == cut
+    for k, (base, rws) in enumerate(items_of(topo, cut)):
+        assert slots[base_off[k]:base_off[k + 1]] == base, (name, k)
+        assert rows[row_off[k]:row_off[k + 1]] == rws, (name, k)
+    axes = {r[2] for r in rows}
+    if name == 'k4_col':
+        assert rows == [(0, 0, 0)]                               # variable 0 sits on axis 0 of the factor over (0, 1): T[s][c_0]
+    if name in ('k6', 'double_pair'):
+        assert axes == {0, 1}                                   # both orientations occur
+    if name == 'double_pair':
+        assert len(rows) == 2 and {r[0] for r in rows} == {0, 1} and {r[1] for r in rows} == {0}      # two factors, two items
+    if name == 'tree':
+        assert len(words) == M.PLAN_HEADER + 2 and not rows
+
+
+def test_check_plan_refuses_each_of_its_cases():
+    M, E_ = _M(), _ffi()
+    topo = R._topo(R.kn_spec(5, 4))
+    good = M.plan_words(topo, [0, 1, 2])
+    H = M.PLAN_HEADER
+    n_cut, n_base, n_rows = 3, int(good[4]), int(good[5])
+    base_off, slots, row_off, rows = H + n_cut, H + 2 * n_cut + 1, H + 2 * n_cut + 1 + n_base, H + 3 * n_cut + 2 + n_base
+    assert n_rows == 3 and len(good) == rows + 3 * n_rows
+
+    def rc(words, X=4, n_msgs=None):
+        w = np.ascontiguousarray(words, dtype=np.int32)
+        return M.lib.mlbp_cutdraw_check_plan(E_.i32ptr(w), len(w), X, topo.n_msgs if n_msgs is None else n_msgs)
+
+    def edited(at, value):
+        w = good.copy()
+        w[at] = value
+        return w
+    assert rc(good) == E_.MLBP_OK and rc(good, X=1024) == E_.MLBP_OK and rc(good, X=2) == E_.MLBP_OK
+    assert M.lib.mlbp_cutdraw_check_plan(None, 8, 4, 4) == E_.MLBP_EINVAL and 'NULL' in M.last_error()
+    for words, word in ((good[:-1], 'sizes give'), (good[:5], 'header'), (edited(0, 0), 'bad sizes'), (edited(3, -1), 'bad sizes'),
+                        (edited(H, 5), 'cutset[0]'), (edited(H, -1), 'cutset[0]'), (edited(H + 1, 0), 'twice'),
+                        (edited(base_off, 1), 'must be 0'), (edited(row_off, 1), 'must be 0'),
+                        (edited(base_off + 2, 0), 'base_off not monotone'), (edited(base_off + 1, n_base + 1), 'base_off not monotone'),
+                        (edited(row_off + 2, -1), 'row_off not monotone'), (edited(row_off + 2, n_rows + 1), 'row_off not monotone'),
+                        (edited(row_off + 3, n_rows - 1), 'end at'),
+                        (edited(slots, topo.n_msgs), 'message slot'), (edited(slots + 1, -1), 'message slot'),
+                        (edited(rows, topo.P), 'pair slot'), (edited(rows, -1), 'pair slot'),
+                        (edited(rows + 1, 1), 'not an earlier one'), (edited(rows + 1, -1), 'not an earlier one'),
+                        (edited(rows + 3 + 1, 2), 'not an earlier one'), (edited(rows + 2, 2), 'axis'), (edited(rows + 2, -1), 'axis')):
+        assert rc(words) == E_.MLBP_EINVAL, word
+        assert word in M.last_error(), (word, M.last_error())
+    assert rc(good, n_msgs=topo.n_msgs + 1) == E_.MLBP_EINVAL and 'message slots' in M.last_error()
+    assert rc(good, X=1) == E_.MLBP_EINVAL and 'two states' in M.last_error()
+    assert rc(good, X=1025) == E_.MLBP_EUNSUPPORTED and '1024' in M.last_error()
+    big = R._topo(R.kn_spec(19, 2))
+    w = M.plan_words(big, list(range(17)))
+    assert M.lib.mlbp_cutdraw_check_plan(E_.i32ptr(w), len(w), 2, big.n_msgs) == E_.MLBP_EUNSUPPORTED and 'at most 16' in M.last_error()
+    w = M.plan_words(big, list(range(16)))
+    assert M.lib.mlbp_cutdraw_check_plan(E_.i32ptr(w), len(w), 2, big.n_msgs) == E_.MLBP_OK
+    with pytest.raises(M.CutdrawError):
+        M.check_plan(good[:-1], 4, topo.n_msgs)
+
+
+def test_plan_is_cached_and_a_bad_cutset_fails_in_the_estimates_words():
+    from macaronicusermodeling_amd import cutsetis
+    M = _M()
+    topo = R._topo(R.kn_spec(5, 4))
+    assert M.plan(topo, [0, 1, 2], 4, None) is M.plan(topo, [0, 1, 2], 4, None) is M.plan(topo, None, 4, None)
+    assert M.plan(topo, [2, 1, 0], 4, None) is not M.plan(topo, [0, 1, 2], 4, None)
+    pl = M.plan(topo, [2, 1, 0], 64, None)
+    assert pl.n_cut == 3 and pl.cutset == (2, 1, 0) and pl.walk is cutsetis.plan(topo, [2, 1, 0], 64, None) and pl.dev is None
+    with pytest.raises(cutsetis.CutsetisError, match='cycle'):
+        M.plan(topo, [0, 1], 4, None)
+    with pytest.raises(ValueError):
+        M.plan(topo, [0, 0, 1], 4, None)
+    assert M.plan(R._topo(C.chain_spec(3, 4)), None, 4, None).n_cut == 0
+
+
+# ------------------------------------------------------------------------------------------------
+# C ABI of libmlbp_cutdraw.so
+# ------------------------------------------------------------------------------------------------
+HEADER = os.path.join(ROOT, 'include', 'mlbp_cutdraw.h')
+
+
+def declared_functions():
+    text = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
+    return sorted(set(re.findall(r'\b(mlbp_cutdraw_[a-z0-9_]+)\s*\(', text)))
+
+
+def test_every_declared_symbol_is_exported_and_bound_and_nothing_else():
+    M = _M()
+    names = declared_functions()
+    assert len(names) == 7 and 'mlbp_cutdraw_f64' in names
+    exported = sorted(n for n, (_, typ) in K._symbols(M.LIB_PATH).items() if n.startswith('mlbp_') and typ == K._STT_FUNC)
+    assert exported == names, set(exported) ^ set(names)
+    assert sorted(M.SIGNATURES) == names, set(M.SIGNATURES) ^ set(names)
+    raw = ctypes.CDLL(M.LIB_PATH)
+    for n in names:
+        assert hasattr(raw, n)
+    from macaronicusermodeling_amd import _ffi, converge, cutset, cutsetis, exactgrad, exactmap, exactmbest, exactsample, logz, mapdecode, sample
+    for other in (_ffi, mapdecode, logz, sample, converge, cutset, exactmap, exactgrad, exactsample, exactmbest, cutsetis):
+        assert not set(M.SIGNATURES) & set(other.SIGNATURES)
+    text = open(HEADER).read()
+    for name, value in (('KERNEL_NONE', M.KERNEL_NONE), ('KERNEL_X64', M.KERNEL_X64), ('KERNEL_GENERIC', M.KERNEL_GENERIC),
+                        ('MAX_LISTED', M.MAX_LISTED), ('MAX_CUT', M.MAX_CUT), ('MAX_X', M.MAX_X), ('MIN_WORKGROUPS', M.MIN_WORKGROUPS),
+                        ('PLAN_HEADER', M.PLAN_HEADER)):
+        assert int(re.search(r'#define MLBP_CUTDRAW_%s (\d+)' % name, text).group(1)) == value, name
+    assert (M.MAX_LISTED, M.MAX_CUT, M.MIN_WORKGROUPS) == (cutsetis.MAX_LISTED, cutsetis.MAX_CUT, cutsetis.MIN_WORKGROUPS) == (65536, 16, 512)
+    body = re.sub(r'/\*.*?\*/', '', re.search(r'typedef struct mlbp_cutdraw_args \{(.*?)\} mlbp_cutdraw_args;', text, flags=re.S).group(1), flags=re.S)
+    fields = [n for decl in body.split(';') for n in re.findall(r'(\w+)\s*(?:,|$)', decl.strip())]
+    assert fields == [f[0] for f in M.CutdrawArgs._fields_], fields
+    assert fields == ['B', 'X', 'n_msgs', 'P', 'n_cut', 'n_pair_tables', 'plan_words', 'N', 'plan', 'pair_tables', 'pair_tab', 'msgs', 'uniforms',
+                      'configs_in', 'configs', 'log_q']
+    flat = ' '.join(text.replace('*', ' ').split())
+    for word in ('is 1, for any positive messages', 'q(c) = Z_c / Z exactly', 'do not depend on B, N, the grid or the wave',
+                 'T[c_j][s] when a sits on axis 1', 'T[s][c_j] when a sits on axis 0', 'After EVERY multiplication', 'log_q = -inf',
+                 'n_cut = 0 is valid', 'There is no workspace', 'second mode'):
+        assert word in flat, word                               # what the issue asks the header to state
+
+
+def _valid_args(M, X=64, n_cut=1, N=16):
+    """Arguments that pass every host-side check (the pointers are never dereferenced on the host)."""
+    a = M.CutdrawArgs()
+    a.B, a.X, a.n_msgs, a.P, a.n_cut, a.n_pair_tables, a.N = 2, X, 9, 3, n_cut, 6, N
+    a.plan_words = M.PLAN_HEADER + 3 * n_cut + 2 + 3
+    for name, typ in M.CutdrawArgs._fields_:
+        if typ is ctypes.c_void_p:
+            setattr(a, name, 4096)
+    a.configs_in = None
+    return a
+
+
+def test_library_identity_and_bad_arguments():
+    M, E_ = _M(), _ffi()
+    assert M.lib.mlbp_cutdraw_arch() == b'gfx950'
+    assert M.lib.mlbp_cutdraw_f64(None, None) == E_.MLBP_EINVAL and 'NULL' in M.last_error()
+    for field, value, word in (('B', 0, 'sizes'), ('B', -2, 'sizes'), ('n_msgs', 0, 'sizes'), ('P', -1, 'sizes'), ('n_cut', -1, 'sizes'), ('X', 1, 'two states'),
+                               ('N', 0, 'list'), ('N', 65537, 'list'), ('N', -1, 'list'), ('plan', None, 'plan'), ('plan_words', 5, 'plan'),
+                               ('pair_tables', None, 'pair_tables'), ('pair_tab', None, 'pair_tab'), ('n_pair_tables', 0, 'n_pair_tables'),
+                               ('msgs', None, 'msgs'), ('log_q', None, 'log_q'), ('uniforms', None, 'uniforms'), ('configs', None, 'configs')):
+        a = _valid_args(M)
+        setattr(a, field, value)
+        assert M.lib.mlbp_cutdraw_f64(ctypes.byref(a), None) == E_.MLBP_EINVAL, field
+        assert word in M.last_error(), (field, M.last_error())
+        assert M.lib.mlbp_cutdraw_last_kernel() == M.KERNEL_NONE
+    a = _valid_args(M, X=1025)
+    assert M.lib.mlbp_cutdraw_f64(ctypes.byref(a), None) == E_.MLBP_EUNSUPPORTED and '1024' in M.last_error()
+    a = _valid_args(M, n_cut=17)
+    assert M.lib.mlbp_cutdraw_f64(ctypes.byref(a), None) == E_.MLBP_EUNSUPPORTED and 'at most 16' in M.last_error()
+    with pytest.raises(M.CutdrawError):
+        M.check(E_.MLBP_EINVAL)
+
+
+def test_compute_entry_fails_loudly_without_a_gpu():
+    """After its argument checks, in both modes and with the empty cutset."""
+    import torch
+    M = _M()
+    if torch.cuda.is_available():
+        return                                                  # (the GPU module runs the entry for real)
+    for X, n_cut, N in ((64, 1, 1), (64, 16, 65536), (7, 3, 64), (1024, 2, 2), (2, 0, 5)):
+        for given in (False, True):
+            a = _valid_args(M, X=X, n_cut=n_cut, N=N)
+            if given:
+                a.configs_in, a.uniforms, a.configs = 4096, None, None
+            assert M.lib.mlbp_cutdraw_f64(ctypes.byref(a), None) == _ffi().MLBP_ENODEVICE, (X, n_cut, N, M.last_error())
+            assert 'no CPU fallback' in M.last_error() and M.lib.mlbp_cutdraw_last_kernel() == M.KERNEL_NONE
+
+
+def test_kernel_choice_and_chunks_are_the_rules_of_the_header():
+    from macaronicusermodeling_amd import cutsetis
+    M, E_ = _M(), _ffi()
+    for X in (2, 3, 7, 33, 63, 65, 128, 257, 1024):
+        assert M.pick_kernel(X) == M.KERNEL_GENERIC, X
+    assert M.pick_kernel(64) == M.KERNEL_X64
+    assert M.lib.mlbp_cutdraw_pick_kernel(1025) == E_.MLBP_EUNSUPPORTED and M.lib.mlbp_cutdraw_pick_kernel(1) == E_.MLBP_EINVAL
+    for B, N in ((1, 64), (1, 600), (1, 65536), (2, 4096), (3, 5), (3, 64), (8192, 64), (600, 7), (511, 4), (512, 4), (1, 1), (1024, 1024)):
+        assert M.chunks(B, N) == min(N, -(-M.MIN_WORKGROUPS // B)) == cutsetis.chunks(B, N), (B, N)
+    for B, N in ((0, 1), (1, 0), (1, M.MAX_LISTED + 1), (1, -3)):
+        assert M.lib.mlbp_cutdraw_chunks(B, N) == E_.MLBP_EINVAL and 'N' in M.last_error()
+
+
+# ------------------------------------------------------------------------------------------------
+# kernel inventory of libmlbp_cutdraw.so: the rule of tests/test_kernel_inventory.py applied to the twelfth library
+# ------------------------------------------------------------------------------------------------
+PKG = os.path.join(ROOT, 'macaronicusermodeling_amd')
+CSRC_CUTDRAW = os.path.join(PKG, 'csrc_cutdraw')
+KERNELS = {'cutdraw_x64_kernel', 'cutdraw_generic_kernel'}
+
+
+def test_cutdraw_library_kernels_are_the_sources_kernels_and_each_has_a_case():
+    import test_gpu_cutdraw as G
+    src = K.kernel_names(csrc=CSRC_CUTDRAW)
+    assert src == KERNELS
+    compiled = R._kernels_of(_M().LIB_PATH)
+    assert compiled == {(name, ()) for name in src}
+    assert set(G.CASES) == compiled, set(G.CASES) ^ compiled
+    for kern, tests in G.CASES.items():
+        assert tests, kern
+        for t in tests:
+            assert callable(getattr(G, t, None)), (kern, t)
+    assert set(G.INPUTS_USED) == set(INPUTS), set(G.INPUTS_USED) ^ set(INPUTS)       # every input compared there is checked here
+    for name, test in G.INPUTS_USED.items():
+        assert callable(getattr(G, test, None)), (name, test)
+
+
+def test_the_other_libraries_hold_no_cutdraw_kernel_and_the_draw_helpers_hold_no_kernel():
+    from macaronicusermodeling_amd import converge, cutset, cutsetis, exactgrad, exactmap, exactmbest, exactsample, logz, mapdecode, sample
+    import test_exactsample_cpu
+    assert not [k for k in K.all_compiled() if k[0].startswith('cutdraw_')]
+    for other in (mapdecode, logz, sample, converge, cutset, exactmap, exactgrad, exactsample, exactmbest, cutsetis):
+        assert not [k for k in R._kernels_of(other.LIB_PATH) if k[0].startswith('cutdraw_')]
+    assert {n for n, _ in R._kernels_of(exactsample.LIB_PATH)} == test_exactsample_cpu.KERNELS      # the move left its inventory closed
+    names = K.kernel_names(csrc=CSRC_CUTDRAW)
+    assert all(n.startswith('cutdraw_') for n in names)
+    for csrc in ('csrc', 'csrc_map', 'csrc_logz', 'csrc_sample', 'csrc_converge', 'csrc_cutset', 'csrc_exactmap', 'csrc_exactgrad', 'csrc_exactsample',
+                 'csrc_exactmbest', 'csrc_cutsetis'):
+        assert not names & K.kernel_names(csrc=os.path.join(PKG, csrc))
+    shared = open(os.path.join(PKG, 'csrc', 'mlbp_draw_device.h')).read()
+    assert '__global__' not in shared                           # helpers only
+    for helper in ('wave_scan', 'wave_draw', 'block_min_max', 'block_draw'):
+        assert re.search(r'\b%s\(' % helper, shared), helper
+    mine = open(os.path.join(CSRC_CUTDRAW, 'mlbp_cutdraw.hip')).read()
+    assert 'mlbp_draw_device.h' in mine and 'mlbp_cutset.h' not in mine and 'mlbp_cutset_walk.h' not in mine
+    for f in os.listdir(CSRC_CUTDRAW):
+        assert f.endswith(('.hip', '.h', '.o')), f
+
+
+def test_build_lists_the_library():
+    """By membership, not by a total: the next library joins the list without touching this test."""
+    from macaronicusermodeling_amd import build as B
+    mine = [e for e in B.MORE_LIBRARIES if os.path.basename(e[4]) == 'libmlbp_cutdraw.so']
+    assert len(mine) == 1
+    csrc, sources, headers, public, lib = mine[0]
+    assert (os.path.basename(csrc), sources, public) == ('csrc_cutdraw', ['mlbp_cutdraw.hip'], 'mlbp_cutdraw.h')
+    assert headers == B.HEADERS_SIDE and 'mlbp_draw_device.h' in B.HEADERS_SIDE
+    assert os.path.dirname(lib) == os.path.dirname(B.LIB) and lib == _M().LIB_PATH
+    assert not set(e[4] for e in B.MORE_LIBRARIES) & set(e[4] for e in B.LIBRARIES + B.LATER_LIBRARIES)
