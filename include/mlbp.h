@@ -180,8 +180,37 @@ int mlbp_program_set_readout(mlbp_program* p, int32_t n_vars, const int32_t* in_
  * program handed from the scale-free kernel to the exact kernel (degenerate inputs: zero-sum
  * messages, negative or non-finite entries).  Diagnostic; results are exact either way. */
 int mlbp_program_exact_count(const mlbp_program* p, int32_t B);
+/* Synchronising: the per-graph flag bytes behind mlbp_program_exact_count, as the last default-variant launch left them: 0 = the
+ * fast kernel's result stands; else why the graph went to the exact kernel (lean kernel: 1 prologue, 2 main loop, 3 final pass).
+ * Writes min(B, graphs reserved) bytes to out (host) and returns their number.  Diagnostic. */
+int mlbp_program_bail_codes(const mlbp_program* p, int32_t B, uint8_t* out);
 /* The number of updates of the program's root sequence that MLBP_SWEEP_SKIP_UNCHANGED drops (0: the flag changes nothing). */
 int mlbp_program_skippable_updates(const mlbp_program* p);
+
+/* Run-time specialisation of the default X = 64 kernel.  That kernel interprets the program's micro-ops; for a program with
+ * three pairwise factors the library can compile the same kernel once more with the micro-ops as compile-time constants (hiprtc,
+ * for the device's architecture; libhiprtc.so is opened when first needed) and keep the module with the program until
+ * mlbp_program_destroy.  A single mlbp_sweep_f64 call of the program at X = 64 without a fused gradient then launches it;
+ * grouped calls, gradient-fused calls and X < 64 never do.  Results are the same bit for bit, and mlbp_last_sweep_kernel() is
+ * MLBP_KERNEL_LEAN either way.
+ *   Policy: the first such call with B >= 4096 on a stream that is not capturing compiles, synchronously, once per program
+ *   (a fraction of a second to a few seconds; smaller batches never pay it, a capture never contains it).  One attempt per
+ *   program: any failure -- no libhiprtc.so, a compile or load error -- leaves the interpreting kernel in charge for good.
+ *   MLBP_LEAN_SPECIALIZE=0 in the environment disables the automatic attempt (not mlbp_program_specialize).
+ *   Calls with MLBP_SWEEP_SKIP_UNCHANGED run the program's pruned twin, which always keeps the interpreting kernel: its launch
+ *   runs at the rate its tables arrive, and the static form measured 5 % slower there.
+ * mlbp_program_specialize: the attempt now, whatever B will be; MLBP_OK when the program is specialised, else MLBP_EUNSUPPORTED
+ *   with the reason.  Call it before capturing a small-batch call that should use it.
+ * mlbp_program_specialized: 1 = in use, 0 = not attempted (also for a NULL program), -1 = attempted and fell back
+ *   (mlbp_last_error() holds the reason).
+ * mlbp_lean_compile_count: run-time compilations this process has started (diagnostic).
+ * mlbp_lean_static_code: HOST only (no device needed) -- the code object of the static kernel for bundle words
+ *   [n_bundles][16] (MLBP_IMAGE_LEAN's image starts with them) compiled for `arch` ("gfx950"); returns its size in bytes and
+ *   writes min(size, cap) bytes to out. */
+int mlbp_program_specialize(mlbp_program* p);
+int mlbp_program_specialized(const mlbp_program* p);
+int mlbp_lean_compile_count(void);
+int mlbp_lean_static_code(const int32_t* bundles, int32_t n_bundles, const char* arch, char* out, int32_t cap);
 
 /* Synchronising read-and-reset of the program's device status word: 0 = clean; 1 = a kernel skipped
  * a graph because one of its table indices lay outside [0, n_*_tables) (instead of reading out of

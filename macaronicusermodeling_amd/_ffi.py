@@ -98,7 +98,12 @@ SIGNATURES = {
     'mlbp_program_reserve': (C.c_int, [_vp, _i32]),
     'mlbp_program_set_readout': (C.c_int, [_vp, _i32, _i32p, _i32p]),
     'mlbp_program_exact_count': (C.c_int, [_vp, _i32]),
+    'mlbp_program_bail_codes': (C.c_int, [_vp, _i32, _vp]),
     'mlbp_program_skippable_updates': (C.c_int, [_vp]),
+    'mlbp_program_specialize': (C.c_int, [_vp]),
+    'mlbp_program_specialized': (C.c_int, [_vp]),
+    'mlbp_lean_compile_count': (C.c_int, []),
+    'mlbp_lean_static_code': (C.c_int, [_i32p, _i32, C.c_char_p, _vp, _i32]),
     'mlbp_program_status': (C.c_int, [_vp]),
     'mlbp_set_sweep_variant': (C.c_int, [_i32]),
     'mlbp_sweep_f64': (C.c_int, [_vp, C.POINTER(SweepArgs), _vp]),

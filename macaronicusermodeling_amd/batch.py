@@ -57,9 +57,26 @@ class Program:
         """Graphs of the last launch that needed the exact kernel (mlbp_program_exact_count)."""
         return _ffi.check(_ffi.lib.mlbp_program_exact_count(self.handle, B))
 
+    def bail_codes(self, B):
+        """The per-graph flag bytes of the last launch as a uint8 array (mlbp_program_bail_codes): 0 = the fast kernel's result
+        stands, else why the graph went to the exact kernel."""
+        out = np.zeros(int(B), dtype=np.uint8)
+        n = _ffi.check(_ffi.lib.mlbp_program_bail_codes(self.handle, int(B), out.ctypes.data))
+        return out[:n]
+
     def skippable_updates(self):
         """Updates of the root sequence that skip_unchanged drops (mlbp_program_skippable_updates)."""
         return _ffi.check(_ffi.lib.mlbp_program_skippable_updates(self.handle))
+
+    def specialize(self):
+        """Compiles the program's micro-ops into the default X = 64 kernel now (mlbp_program_specialize); raises when the
+        program cannot be specialised."""
+        _ffi.check(_ffi.lib.mlbp_program_specialize(self.handle))
+
+    def specialized(self):
+        """1 = the last call's program runs its own compiled kernel, 0 = not attempted, -1 = attempted and fell back
+        (mlbp_program_specialized)."""
+        return int(_ffi.lib.mlbp_program_specialized(self.handle))
 
     def __del__(self):
         h = getattr(self, 'handle', None)

@@ -33,7 +33,7 @@ LIB_EXACTSAMPLE = os.path.join(PKG, 'libmlbp_exactsample.so')
 LIB_EXACTMBEST = os.path.join(PKG, 'libmlbp_exactmbest.so')
 LIB_CUTSETIS = os.path.join(PKG, 'libmlbp_cutsetis.so')
 LIB_CUTDRAW = os.path.join(PKG, 'libmlbp_cutdraw.so')
-SOURCES = ['mlbp_host.cpp', 'mlbp_compile.cpp', 'mlbp_compile_shared.cpp', 'mlbp_program.cpp', 'mlbp_dispatch.cpp', 'mlbp_sweep.hip', 'mlbp_lean.hip', 'mlbp_shared.hip', 'mlbp_gemm.hip', 'mlbp_prims.hip', 'mlbp_grad.hip']
+SOURCES = ['mlbp_host.cpp', 'mlbp_compile.cpp', 'mlbp_compile_shared.cpp', 'mlbp_program.cpp', 'mlbp_dispatch.cpp', 'mlbp_lean_jit.cpp', 'mlbp_sweep.hip', 'mlbp_lean.hip', 'mlbp_shared.hip', 'mlbp_gemm.hip', 'mlbp_prims.hip', 'mlbp_grad.hip']
 SOURCES_MAP = ['mlbp_map.hip']
 SOURCES_LOGZ = ['mlbp_logz.hip']
 SOURCES_SAMPLE = ['mlbp_sample.hip']
@@ -46,7 +46,11 @@ SOURCES_EXACTMBEST = ['mlbp_exactmbest.hip']
 SOURCES_CUTSETIS = ['mlbp_cutsetis.hip']
 SOURCES_CUTDRAW = ['mlbp_cutdraw.hip']
 # csrc/ headers: the core library's, and what the side libraries share (mlbp_graph_device.h includes mlbp_device.h)
-HEADERS = ['mlbp_internal.h', 'mlbp_device.h']
+HEADERS = ['mlbp_internal.h', 'mlbp_device.h', 'mlbp_uop.h', 'mlbp_lean_device.h']
+# The lean kernel's device headers, whose TEXT the library carries (mlbp_lean_jit.cpp compiles it at run time with one program's
+# micro-ops as constants): written into EMBED, a generated and git-ignored include file, before the core library is compiled
+EMBEDDED = ['mlbp_device.h', 'mlbp_uop.h', 'mlbp_lean_device.h']
+EMBED = os.path.join(CSRC, 'mlbp_lean_embed.inc')
 HEADERS_SIDE = ['mlbp_device.h', 'mlbp_graph_device.h', 'mlbp_graph_host.h', 'mlbp_cutset_plan.h', 'mlbp_cutset_walk.h', 'mlbp_draw_device.h']
 # (source dir, sources, csrc/ headers, public header, output): every library has its own sources and its own kernel
 # inventory; the flags are the same
@@ -82,6 +86,31 @@ def _stale(obj, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def _write_embed():
+    """EMBED: the EMBEDDED headers as raw string literals (rewritten only when its text would change: it is a dependency)."""
+    delim = 'MLBPEMBED'
+    out = ['// generated by build.py from %s: do not edit\n' % ', '.join(EMBEDDED), 'enum { MLBP_EMBED_N = %d };\n' % len(EMBEDDED),
+           'static const char* const MLBP_EMBED_NAMES[] = {%s};\n' % ', '.join('"%s"' % h for h in EMBEDDED),
+           'static const char* const MLBP_EMBED_TEXTS[] = {\n']
+    for h in EMBEDDED:
+        with open(os.path.join(CSRC, h)) as f:
+            text = f.read()
+        assert ')' + delim not in text
+        # (pieces of at most ~12 KB, concatenated by the compiler: no single literal near a compiler's length limit)
+        lines = text.splitlines(True)
+        pieces = [''.join(lines[i:i + 100]) for i in range(0, len(lines), 100)]
+        out.append(''.join('R"%s(%s)%s"\n' % (delim, p, delim) for p in pieces) + ',\n')
+    out.append('};\n')
+    new = ''.join(out)
+    old = None
+    if os.path.exists(EMBED):
+        with open(EMBED) as f:
+            old = f.read()
+    if new != old:
+        with open(EMBED, 'w') as f:
+            f.write(new)
+
+
 def _build_one(hipcc, csrc, sources, headers, lib, force, verbose):
     objs = []
     for src in sources:
@@ -103,6 +132,7 @@ def build(force=False, verbose=False):
     """Builds the twelve libraries; returns the path of libmlbp.so (the others lie beside it: LIB_MAP, LIB_LOGZ, LIB_SAMPLE,
     LIB_CONVERGE, LIB_CUTSET, LIB_EXACTMAP, LIB_EXACTGRAD, LIB_EXACTSAMPLE, LIB_EXACTMBEST, LIB_CUTSETIS, LIB_CUTDRAW)."""
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+    _write_embed()
     for csrc, sources, headers, public, lib in LIBRARIES + LATER_LIBRARIES + MORE_LIBRARIES:
         deps = [os.path.join(CSRC, h) for h in headers] + [os.path.join(INCLUDE, public)]
         _build_one(hipcc, csrc, sources, deps, lib, force, verbose)

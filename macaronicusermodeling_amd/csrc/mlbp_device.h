@@ -2,10 +2,13 @@
 #ifndef MLBP_DEVICE_H
 #define MLBP_DEVICE_H
 
+// (compiled at run time -- mlbp_lean_jit.cpp -- the compiler brings the HIP declarations itself and has no host header)
+#ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
 #include <cstdint>
+#endif
 
 namespace mlbp_dev {
 

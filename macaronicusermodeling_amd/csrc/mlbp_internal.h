@@ -3,9 +3,11 @@
 #ifndef MLBP_INTERNAL_H
 #define MLBP_INTERNAL_H
 
+#include <string>
 #include <vector>
 
 #include "../../include/mlbp.h"
+#include "mlbp_uop.h"
 
 namespace mlbp_dev { struct GradFusedDev; }
 
@@ -92,19 +94,8 @@ struct FusedProgram {
 };
 void build_fused_program(const int32_t* ops, const int32_t* srcs, const int32_t* sweeps, int n_sweeps, int n_msgs, FusedProgram& out);
 
-// Micro-op form of the lean X = 64 kernel (mlbp_lean.hip): operands are LDS byte offsets.
-// micro-op word 0
-constexpr int UOP_VAR = 1;          // bit 0: variable product only (stored, no contraction)
-constexpr int UOP_MT = 2;           // bit 1: out = m^T . T (else T . m)
-constexpr int UOP_PSLOT_SHIFT = 2;  // bits 2-4: pair slot (register-resident table; 0..7)
-constexpr int UOP_NOP = 32;         // bit 5: empty second slot of a bundle
-constexpr int UOP_STORE_VF = 64;    // bit 6: the variable->factor message is stored (word 5)
-constexpr int UOP_NSRC_SHIFT = 8;   // bits 8-11: number of sources (1..4)
-constexpr int UOP_CARRY_IN = 0x1000;   // a link of a long variable product: starts from the running product in registers
-constexpr int UOP_CARRY_OUT = 0x2000;  // ... and hands it on instead of storing it
-// micro-op words: 0 flags | 1-4 source byte offsets | 5 byte offset of the variable->factor message to store, or -1 |
-// 6 destination byte offset | 7 unused.  Source words past the count hold the all-ones ext slot.
-// A bundle = two micro-ops = 16 words = one s_load_dwordx16.
+// Micro-op form of the lean X = 64 kernel (mlbp_lean_device.h): operands are LDS byte offsets.  The words and the UOP_* bits
+// of word 0: mlbp_uop.h.
 struct LeanProgram {
   bool ok = false;
   const char* why = "";
@@ -123,6 +114,26 @@ int launch_lean_sweep(mlbp_program* prog, const mlbp_sweep_args* a, bool fuse_gr
 // The same for several (program, arguments) groups in one launch.  member: in, the groups offered; out, the groups launched
 // (a group that does not qualify is left out, not the call).
 int launch_lean_groups(mlbp_program* const* progs, const mlbp_sweep_args* args, int n_groups, void* stream, std::vector<char>& member);
+
+// Run-time specialisation of the lean kernel (mlbp_lean_jit.cpp): the static kernel of ONE program -- its bundle words compiled
+// in -- as a loaded module.  state: 0 not tried, 1 in use, -1 tried and fell back (why); there is one attempt per program.
+struct LeanJit {
+  void* module = nullptr;      // hipModule_t, unloaded with the program
+  void* function = nullptr;    // hipFunction_t of sweep_x64_lean_static_kernel
+  int state = 0;
+  double seconds = 0.0;        // what the attempt that succeeded took: compile and load
+  std::string why;
+};
+// The automatic policy: the first single X = 64 call of a P = 3 program with at least this many graphs, on a stream that is
+// not capturing, compiles (synchronously, once).  Below it a launch is under 0.1 ms and the saving a microsecond or two.
+constexpr int LEAN_JIT_MIN_BATCH = 4096;
+// Dynamic LDS of one lean launch of `prog` (mlbp_lean.hip): messages and ext slots, the reduction buffers, the micro-ops, the
+// seventh table of an X = 64 launch, the fused gradient's per-factor words.  The one statement of it: lean_plan asks for it and
+// lean_jit_specialize holds it against the 64 KB the static kernel's immediates can address.
+size_t lean_lds_bytes(const mlbp_program* prog, bool grad, bool padx);
+int lean_jit_specialize(mlbp_program* prog);                    // compiles unless tried before; returns the state
+void lean_jit_auto(mlbp_program* prog, int B, void* stream);    // the policy; MLBP_LEAN_SPECIALIZE=0 in the environment disables it
+void lean_jit_release(mlbp_program* prog);
 
 // Shared-table (MFMA) form, mlbp_shared.hip: 16 graphs per workgroup, messages kept as [state][graph]
 // tiles in LDS, only the "live" slots (read or written inside the sweeps) resident.
@@ -258,6 +269,7 @@ struct mlbp_program {
   mlbp::LeanProgram lean;
   mlbp::DeviceArray<int32_t> d_limage;   // LeanProgram::image
   mlbp::DeviceArray<int32_t> d_lreadout; // build_lean_readout
+  mlbp::LeanJit jit;             // the program's static kernel, when it has one (mlbp_lean_jit.cpp)
   mlbp::GroupTables gtables;     // group tables of mlbp_sweep_groups_f64 calls that name this program first (launch_lean_groups)
   mlbp::GroupTables stables;     // the same for the shared-table kernels (launch_shared_groups)
   // shared-table form (mlbp_shared.hip); the scratch below is allocated on first use

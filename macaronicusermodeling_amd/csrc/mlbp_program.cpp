@@ -250,6 +250,7 @@ int mlbp_program_create(const int32_t* ops, int32_t n_ops, const int32_t* srcs, 
 int mlbp_program_destroy(mlbp_program* p) {
   if (!p) return MLBP_OK;
   if (p->pruned) (void)mlbp_program_destroy(p->pruned);
+  mlbp::lean_jit_release(p);
   if (p->side_stream) (void)hipStreamDestroy((hipStream_t)p->side_stream);
   if (p->ev_fork) (void)hipEventDestroy((hipEvent_t)p->ev_fork);
   if (p->ev_join) (void)hipEventDestroy((hipEvent_t)p->ev_join);
@@ -302,6 +303,16 @@ int mlbp_program_exact_count(const mlbp_program* prog, int32_t B) {
   for (unsigned char c : h) { n += c ? 1 : 0; hist[c & 3]++; }
   fail(0, "exact-kernel graphs by reason: prologue %d, main loop %d, final pass %d (shared-table kernel: 2 = degenerate total, 4 -> counted under 0 = tables not shared)", hist[1], hist[2], hist[3]);
   return n;
+}
+
+int mlbp_program_bail_codes(const mlbp_program* prog, int32_t B, uint8_t* out) {
+  // Synchronising: the flag bytes themselves, of the program the last call ran
+  if (!prog || B < 0 || (B > 0 && !out)) return fail(MLBP_EINVAL, "mlbp_program_bail_codes: bad arguments");
+  if (prog->last_was_pruned && prog->pruned) prog = prog->pruned;
+  if ((size_t)B > prog->d_bail.bytes) B = (int32_t)prog->d_bail.bytes;
+  if (!prog->d_bail || B == 0) return 0;
+  HIP_TRY(hipMemcpy(out, prog->d_bail, (size_t)B, hipMemcpyDeviceToHost));
+  return B;
 }
 
 int mlbp_program_status(const mlbp_program* prog) {
