@@ -1,5 +1,5 @@
-"""What the ctypes bindings of the side libraries share (mapdecode, logz, sample, converge, cutset, exactmap, exactgrad, exactsample, exactmbest, cutsetis, cutdraw): loading a library against its
-signature table, its error class and status helpers, the per-topology cache of device copies, and the base of the
+"""What the ctypes bindings of the side libraries share (the binding modules of build.SIDE_LIBRARIES): loading a library
+against its signature table, its error class and status helpers, the per-topology cache of device copies, and the base of the
 `*Program` classes.  Each binding keeps its own SIGNATURES, constants and args struct: they mirror its header.
 """
 import ctypes as C
@@ -35,7 +35,7 @@ def load(path, signatures):
 
 
 class SideError(RuntimeError):
-    """Base of MapError, LogzError, SampleError, ConvergeError, CutsetError, ExactMapError, ExactGradError, ExactSampleError, ExactMbestError, CutsetisError, CutdrawError; LIB is the library's name without its suffix."""
+    """Base of the one error class of every binding of build.SIDE_LIBRARIES; LIB is the library's name without its suffix."""
     LIB = None
 
     def __init__(self, code, msg):

@@ -491,8 +491,8 @@ class FactorGraphBatch:
 
     # ---- what the six cutset-conditioning calls share -----------------------------------------------------
     def _cutset_args(self, K, Args, cutset, refusal):
-        """(plan, args) of a call into binding K (cutset, exactmap, exactgrad, exactsample, exactmbest, cutsetis): the cutset's variable ids translated, the plan
-        validated by K's library, and the sizes, plan and table fields of an Args() filled.  refusal: the message for pairwise
+        """(plan, args) of a call into binding K (cutset, or a plan-taking binding of build.SIDE_LIBRARIES): the cutset's
+        variable ids translated, the plan validated by K's library, and the sizes, plan and table fields of an Args() filled.  refusal: the message for pairwise
         tables that are not float64."""
         if self.pair_tables is not None and self.pair_tables.dtype != torch.float64:
             raise NotImplementedError(refusal)

@@ -40,7 +40,7 @@ class ConvergeArgs(C.Structure):
                 ('marginals', C.c_void_p), ('history', C.c_void_p)]
 
 
-# name -> (restype, argtypes); mirrors include/mlbp_converge.h one to one (tests/test_converge_cpu.py checks that).
+# name -> (restype, argtypes); mirrors include/mlbp_converge.h one to one (tests/test_side_libraries_cpu.py checks that).
 SIGNATURES = {
     'mlbp_converge_f64': (C.c_int, [C.POINTER(ConvergeArgs), C.c_void_p]),
     'mlbp_converge_check_program': (C.c_int, [_i32p, _i32, _i32p, _i32, _i32p, _i32, _i32, _i32, _i32]),

@@ -47,7 +47,7 @@ class CutdrawArgs(C.Structure):
                 ('log_q', C.c_void_p)]
 
 
-# name -> (restype, argtypes); mirrors include/mlbp_cutdraw.h one to one (tests/test_cutdraw_cpu.py checks that).
+# name -> (restype, argtypes); mirrors include/mlbp_cutdraw.h one to one (tests/test_side_libraries_cpu.py checks that).
 SIGNATURES = {
     'mlbp_cutdraw_f64': (C.c_int, [C.POINTER(CutdrawArgs), C.c_void_p]),
     'mlbp_cutdraw_check_plan': (C.c_int, [_i32p, _i32, _i32, _i32]),

@@ -44,7 +44,7 @@ class CutsetArgs(C.Structure):
                 ('log_z', C.c_void_p), ('marginals', C.c_void_p), ('score', C.c_void_p), ('joint_logp', C.c_void_p)]
 
 
-# name -> (restype, argtypes); mirrors include/mlbp_cutset.h one to one (tests/test_cutset_cpu.py checks that).
+# name -> (restype, argtypes); mirrors include/mlbp_cutset.h one to one (tests/test_side_libraries_cpu.py checks that).
 SIGNATURES = {
     'mlbp_cutset_f64': (C.c_int, [C.POINTER(CutsetArgs), C.c_void_p]),
     'mlbp_cutset_check_plan': (C.c_int, [_i32p, _i32, _i32]),
@@ -177,7 +177,8 @@ def check_plan(words, X):
 
 
 class Plan:
-    """A validated plan and its device copy.  binding: the module (this one, exactmap, exactgrad, exactsample, exactmbest or cutsetis) whose check_plan validates."""
+    """A validated plan and its device copy.  binding: the module whose check_plan validates -- this one, or a plan-taking
+    binding of build.SIDE_LIBRARIES."""
 
     def __init__(self, topo, cutset, X, device, binding=None):
         import torch
@@ -201,3 +202,24 @@ def plan(topo, cutset, X, device, binding=None):
     cutset = tuple(choose(topo) if cutset is None else (int(v) for v in cutset))
     key = (cutset, int(X), str(device), (binding or sys.modules[__name__]).__name__)
     return _plans.get(topo, key, lambda: Plan(topo, cutset, X, device, binding))
+
+
+def plan_functions(module_name):
+    """(check_plan, Plan, plan) of the plan-taking binding being imported as `module_name`: this module's three, with that
+    binding's library validating (its mlbp_<name>_check_plan, raised as its own error) and the binding in the cache key."""
+    binding = sys.modules[module_name]
+    entry = 'mlbp_%s_check_plan' % module_name.rsplit('.', 1)[-1]
+
+    def check_plan(words, X):
+        """Raises the binding's error unless the packed plan `words` is valid for X states."""
+        binding.check(getattr(binding.lib, entry)(_ffi.i32ptr(words), len(words), int(X)))
+
+    def bound_Plan(topo, cutset, X, device):
+        """A plan validated by the binding's library and its device copy: cutset.Plan."""
+        return Plan(topo, cutset, X, device, binding)
+
+    def bound_plan(topo, cutset, X, device):
+        """The cached Plan of (topology, cutset, X, device); cutset None: choose(topo)."""
+        return plan(topo, cutset, X, device, binding)
+
+    return check_plan, bound_Plan, bound_plan

@@ -9,9 +9,8 @@ cutset.plan_words, has THIS library validate it on the host -- no bound on X^|C|
 it once and caches the device copy.
 """
 import ctypes as C
-import sys
 
-from . import _ffi, _sidelib
+from . import _sidelib
 from . import cutset as _cutset
 from ._sidelib import i32 as _i32, i32p as _i32p
 
@@ -43,7 +42,7 @@ class CutsetisArgs(C.Structure):
                 ('score', C.c_void_p), ('joint_logp', C.c_void_p)]
 
 
-# name -> (restype, argtypes); mirrors include/mlbp_cutsetis.h one to one (tests/test_cutsetis_cpu.py checks that).
+# name -> (restype, argtypes); mirrors include/mlbp_cutsetis.h one to one (tests/test_side_libraries_cpu.py checks that).
 SIGNATURES = {
     'mlbp_cutsetis_f64': (C.c_int, [C.POINTER(CutsetisArgs), C.c_void_p]),
     'mlbp_cutsetis_check_plan': (C.c_int, [_i32p, _i32, _i32]),
@@ -68,16 +67,4 @@ def workspace_bytes(B, X, n_vars, P, U, n_forest, N):
     return check(lib.mlbp_cutsetis_workspace_bytes(int(B), int(X), int(n_vars), int(P), int(U), int(n_forest), int(N)))
 
 
-def check_plan(words, X):
-    """Raises CutsetisError unless the packed plan `words` is valid for X states."""
-    check(lib.mlbp_cutsetis_check_plan(_ffi.i32ptr(words), len(words), int(X)))
-
-
-def Plan(topo, cutset, X, device):
-    """A plan validated by this library and its device copy: cutset.Plan."""
-    return _cutset.Plan(topo, cutset, X, device, sys.modules[__name__])
-
-
-def plan(topo, cutset, X, device):
-    """The cached Plan of (topology, cutset, X, device); cutset None: cutset.choose(topo)."""
-    return _cutset.plan(topo, cutset, X, device, binding=sys.modules[__name__])
+check_plan, Plan, plan = _cutset.plan_functions(__name__)

@@ -8,9 +8,8 @@ The call takes the packed plan of include/mlbp_cutset.h: `plan(topo, cutset, X, 
 cutset.plan_words, has THIS library validate it on the host, uploads it once and caches the device copy.
 """
 import ctypes as C
-import sys
 
-from . import _ffi, _sidelib
+from . import _sidelib
 from . import cutset as _cutset
 from ._sidelib import i32 as _i32, i32p as _i32p
 
@@ -36,7 +35,7 @@ class ExactMapArgs(C.Structure):
                 ('assignment', C.c_void_p), ('score', C.c_void_p), ('max_marginals', C.c_void_p)]
 
 
-# name -> (restype, argtypes); mirrors include/mlbp_exactmap.h one to one (tests/test_exactmap_cpu.py checks that).
+# name -> (restype, argtypes); mirrors include/mlbp_exactmap.h one to one (tests/test_side_libraries_cpu.py checks that).
 SIGNATURES = {
     'mlbp_exactmap_f64': (C.c_int, [C.POINTER(ExactMapArgs), C.c_void_p]),
     'mlbp_exactmap_check_plan': (C.c_int, [_i32p, _i32, _i32]),
@@ -62,16 +61,4 @@ def workspace_bytes(B, X, n_vars, P, U, n_forest, n_cut, max_marginals):
                                                    1 if max_marginals else 0))
 
 
-def check_plan(words, X):
-    """Raises ExactMapError unless the packed plan `words` is valid for X states."""
-    check(lib.mlbp_exactmap_check_plan(_ffi.i32ptr(words), len(words), int(X)))
-
-
-def Plan(topo, cutset, X, device):
-    """A plan validated by this library and its device copy: cutset.Plan."""
-    return _cutset.Plan(topo, cutset, X, device, sys.modules[__name__])
-
-
-def plan(topo, cutset, X, device):
-    """The cached Plan of (topology, cutset, X, device); cutset None: cutset.choose(topo)."""
-    return _cutset.plan(topo, cutset, X, device, sys.modules[__name__])
+check_plan, Plan, plan = _cutset.plan_functions(__name__)

@@ -8,9 +8,8 @@ The call takes the packed plan of include/mlbp_cutset.h: `plan(topo, cutset, X, 
 cutset.plan_words, has THIS library validate it on the host, uploads it once and caches the device copy.
 """
 import ctypes as C
-import sys
 
-from . import _ffi, _sidelib
+from . import _sidelib
 from . import cutset as _cutset
 from ._sidelib import i32 as _i32, i32p as _i32p
 
@@ -37,7 +36,7 @@ class ExactMbestArgs(C.Structure):
                 ('assignments', C.c_void_p), ('scores', C.c_void_p), ('n_found', C.c_void_p)]
 
 
-# name -> (restype, argtypes); mirrors include/mlbp_exactmbest.h one to one (tests/test_exactmbest_cpu.py checks that).
+# name -> (restype, argtypes); mirrors include/mlbp_exactmbest.h one to one (tests/test_side_libraries_cpu.py checks that).
 SIGNATURES = {
     'mlbp_exactmbest_f64': (C.c_int, [C.POINTER(ExactMbestArgs), C.c_void_p]),
     'mlbp_exactmbest_check_plan': (C.c_int, [_i32p, _i32, _i32]),
@@ -73,16 +72,4 @@ def workspace_bytes(B, X, n_vars, P, U, n_forest, n_cut, M):
     return check(lib.mlbp_exactmbest_workspace_bytes(int(B), int(X), int(n_vars), int(P), int(U), int(n_forest), int(n_cut), int(M)))
 
 
-def check_plan(words, X):
-    """Raises ExactMbestError unless the packed plan `words` is valid for X states."""
-    check(lib.mlbp_exactmbest_check_plan(_ffi.i32ptr(words), len(words), int(X)))
-
-
-def Plan(topo, cutset, X, device):
-    """A plan validated by this library and its device copy: cutset.Plan."""
-    return _cutset.Plan(topo, cutset, X, device, sys.modules[__name__])
-
-
-def plan(topo, cutset, X, device):
-    """The cached Plan of (topology, cutset, X, device); cutset None: cutset.choose(topo)."""
-    return _cutset.plan(topo, cutset, X, device, binding=sys.modules[__name__])
+check_plan, Plan, plan = _cutset.plan_functions(__name__)

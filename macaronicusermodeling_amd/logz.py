@@ -37,7 +37,7 @@ class LogzArgs(C.Structure):
                 ('labels', C.c_void_p), ('log_z', C.c_void_p), ('score', C.c_void_p), ('joint_logp', C.c_void_p), ('sum_out', C.c_void_p)]
 
 
-# name -> (restype, argtypes); mirrors include/mlbp_logz.h one to one (tests/test_logz_cpu.py checks that).
+# name -> (restype, argtypes); mirrors include/mlbp_logz.h one to one (tests/test_side_libraries_cpu.py checks that).
 SIGNATURES = {
     'mlbp_logz_f64': (C.c_int, [C.POINTER(LogzArgs), C.c_void_p]),
     'mlbp_logz_check_readout': (C.c_int, [_i32, _i32p, _i32p, _i32, _i32, _i32p, _i32p, _i32, _i32p, _i32p]),

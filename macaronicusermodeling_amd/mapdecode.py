@@ -37,7 +37,7 @@ class MapArgs(C.Structure):
                 ('max_marginals', C.c_void_p), ('assignment', C.c_void_p), ('score', C.c_void_p)]
 
 
-# name -> (restype, argtypes); mirrors include/mlbp_map.h one to one (tests/test_map_cpu.py checks that).
+# name -> (restype, argtypes); mirrors include/mlbp_map.h one to one (tests/test_side_libraries_cpu.py checks that).
 SIGNATURES = {
     'mlbp_map_sweep_f64': (C.c_int, [C.POINTER(MapArgs), C.c_void_p]),
     'mlbp_map_check_program': (C.c_int, [_i32p, _i32, _i32p, _i32, _i32p, _i32, _i32, _i32, _i32]),

@@ -41,7 +41,7 @@ class SampleArgs(C.Structure):
                 ('samples', C.c_void_p), ('logq', C.c_void_p), ('cond_marginals', C.c_void_p)]
 
 
-# name -> (restype, argtypes); mirrors include/mlbp_sample.h one to one (tests/test_sample_cpu.py checks that).
+# name -> (restype, argtypes); mirrors include/mlbp_sample.h one to one (tests/test_side_libraries_cpu.py checks that).
 SIGNATURES = {
     'mlbp_sample_f64': (C.c_int, [C.POINTER(SampleArgs), C.c_void_p]),
     'mlbp_sample_check_program': (C.c_int, [_i32p, _i32, _i32p, _i32, _i32p, _i32, _i32, _i32, _i32, _i32, _i32p, _i32p]),

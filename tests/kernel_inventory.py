@@ -123,6 +123,17 @@ def decode_kernel(mangled):
     return ident, tuple(args)
 
 
+def kernels_of(path):
+    """Every kernel instance the shared object at `path` holds, as decode_kernel names them."""
+    found = {decode_kernel(n) for n, (_, typ) in _symbols(path).items() if typ == _STT_OBJECT}
+    return found - {None}
+
+
+def exported_functions(path):
+    """The sorted names of the mlbp_* functions the shared object at `path` exports."""
+    return sorted(n for n, (_, typ) in _symbols(path).items() if n.startswith('mlbp_') and typ == _STT_FUNC)
+
+
 _cache = {}
 
 

@@ -1,6 +1,6 @@
 """Sweeps to convergence without a GPU: the float64 NumPy walk the GPU tests compare against, pinned on things it does not
 define itself; the inputs of the GPU cases and the margin their exact `rounds` comparison relies on; the C ABI of
-libmlbp_converge.so and its host checks; and the kernel inventory rule applied to the fifth library.
+libmlbp_converge.so and its host checks (the contract it shares with the other side libraries is in tests/test_side_libraries_cpu.py).
 
 The walk is the semantics of include/mlbp_converge.h written with the oracle's own functions: schedule, initial messages and
 every update are oracle/lbp_oracle.py's (O._send, untouched); the walk only looks at a slot before and after each update.
@@ -22,7 +22,6 @@ import pytest
 
 import cases as C
 import helpers
-import kernel_inventory as K
 import test_map_cpu as W
 from conftest import ROOT
 from oracle import lbp_oracle as O
@@ -319,35 +318,14 @@ def _V():
     return converge
 
 
-def declared_functions():
-    text = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r'\b(mlbp_converge_[a-z0-9_]+)\s*\(', text)))
-
-
 def test_every_declared_symbol_is_exported_and_bound_and_nothing_else():
+    """What this library adds to the shared contract (tests/test_side_libraries_cpu.py: the bound functions are the declared
+    and the exported ones, the constants and the struct are the header's)."""
     V = _V()
-    names = declared_functions()
-    assert names == sorted(['mlbp_converge_f64', 'mlbp_converge_check_program', 'mlbp_converge_check_readout', 'mlbp_converge_pick_kernel',
-                            'mlbp_converge_last_kernel', 'mlbp_converge_arch', 'mlbp_converge_last_error'])
-    exported = sorted(n for n, (_, typ) in K._symbols(V.LIB_PATH).items() if n.startswith('mlbp_') and typ == K._STT_FUNC)
-    assert exported == names, set(exported) ^ set(names)
-    assert sorted(V.SIGNATURES) == names, set(V.SIGNATURES) ^ set(names)
-    raw = ctypes.CDLL(V.LIB_PATH)
-    for n in names:
-        assert hasattr(raw, n)
-    from macaronicusermodeling_amd import _ffi, logz, mapdecode, sample
-    for other in (_ffi, mapdecode, logz, sample):
-        assert not set(V.SIGNATURES) & set(other.SIGNATURES)
+    assert sorted(V.SIGNATURES) == sorted(['mlbp_converge_f64', 'mlbp_converge_check_program', 'mlbp_converge_check_readout', 'mlbp_converge_pick_kernel',
+                                           'mlbp_converge_last_kernel', 'mlbp_converge_arch', 'mlbp_converge_last_error'])
+    assert V.MAX_ROUNDS == 65535
     text = open(HEADER).read()
-    assert int(re.search(r'#define MLBP_CONVERGE_X64_LDS_BYTES (\d+)', text).group(1)) == V.X64_LDS_BYTES
-    assert int(re.search(r'#define MLBP_CONVERGE_MAX_X (\d+)', text).group(1)) == V.MAX_X
-    assert int(re.search(r'#define MLBP_CONVERGE_MAX_ROUNDS (\d+)', text).group(1)) == V.MAX_ROUNDS == 65535
-    for name, value in (('NONE', V.KERNEL_NONE), ('X64', V.KERNEL_X64), ('GENERIC', V.KERNEL_GENERIC)):
-        assert int(re.search(r'#define MLBP_CONVERGE_KERNEL_%s (\d+)' % name, text).group(1)) == value
-    # the struct's fields, in the header's order
-    body = re.sub(r'/\*.*?\*/', '', re.search(r'typedef struct mlbp_converge_args \{(.*?)\} mlbp_converge_args;', text, flags=re.S).group(1), flags=re.S)
-    fields = [n for decl in body.split(';') for n in re.findall(r'(\w+)\s*(?:,|$)', decl.strip())]
-    assert fields == [f[0] for f in V.ConvergeArgs._fields_], fields
     # status codes and op kinds are guarded against the four other headers
     guard = re.search(r'#if (.*?)\nenum \{ MLBP_OK', text, flags=re.S).group(1)
     for other in ('MLBP_H', 'MLBP_MAP_H', 'MLBP_LOGZ_H', 'MLBP_SAMPLE_H'):
@@ -475,46 +453,3 @@ def test_program_checks_refuse_bad_indices_and_uncovered_slots():
     bad = topo.in_off.copy(); bad[1] = bad[2] + 1
     assert readout(in_off=bad) == _ffi.MLBP_EINVAL and 'monotone' in V.last_error()
     assert V.lib.mlbp_converge_check_readout(1, None, None, 1) == _ffi.MLBP_EINVAL and 'NULL' in V.last_error()
-
-
-# ------------------------------------------------------------------------------------------------
-# kernel inventory of libmlbp_converge.so: the rule of tests/test_kernel_inventory.py applied to the fifth library
-# ------------------------------------------------------------------------------------------------
-CSRC_CONVERGE = os.path.join(ROOT, 'macaronicusermodeling_amd', 'csrc_converge')
-
-
-def _kernels_of(path):
-    found = {K.decode_kernel(n) for n, (_, typ) in K._symbols(path).items() if typ == K._STT_OBJECT}
-    return found - {None}
-
-
-def converge_kernels():
-    """Every kernel instance libmlbp_converge.so holds, as kernel_inventory names them."""
-    return _kernels_of(_V().LIB_PATH)
-
-
-def test_converge_library_kernels_are_the_sources_kernels_and_each_has_a_case():
-    import test_gpu_converge as G
-    src = K.kernel_names(csrc=CSRC_CONVERGE)
-    assert src == {'converge_x64_kernel', 'converge_generic_kernel'}
-    compiled = converge_kernels()
-    assert compiled == {('converge_x64_kernel', (True,)), ('converge_x64_kernel', (False,)), ('converge_generic_kernel', ())}
-    assert set(G.CASES) == compiled, set(G.CASES) ^ compiled
-    for kern, tests in G.CASES.items():
-        assert tests, kern
-        for t in tests:
-            assert callable(getattr(G, t, None)), (kern, t)
-
-
-def test_the_other_libraries_hold_no_converge_kernel_and_the_sources_stay_apart():
-    from macaronicusermodeling_amd import logz, mapdecode, sample
-    assert not [k for k in K.all_compiled() if k[0].startswith('converge_')]
-    for other in (mapdecode, logz, sample):
-        assert not [k for k in _kernels_of(other.LIB_PATH) if k[0].startswith('converge_')]
-    names = K.kernel_names(csrc=CSRC_CONVERGE)
-    assert all(n.startswith('converge_') for n in names)
-    pkg = os.path.join(ROOT, 'macaronicusermodeling_amd')
-    for csrc in (K.CSRC, W.CSRC_MAP, os.path.join(pkg, 'csrc_logz'), os.path.join(pkg, 'csrc_sample')):
-        assert not names & K.kernel_names(csrc=csrc)
-    for f in os.listdir(CSRC_CONVERGE):
-        assert f.endswith(('.hip', '.h', '.o')), f

@@ -23,7 +23,6 @@ import pytest
 
 import cases as C
 import helpers
-import kernel_inventory as K
 import test_cutset_cpu as R
 from conftest import ROOT
 from oracle import lbp_oracle as O
@@ -377,34 +376,14 @@ def test_plan_is_cached_and_a_bad_cutset_fails_in_the_estimates_words():
 HEADER = os.path.join(ROOT, 'include', 'mlbp_cutdraw.h')
 
 
-def declared_functions():
-    text = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r'\b(mlbp_cutdraw_[a-z0-9_]+)\s*\(', text)))
-
-
 def test_every_declared_symbol_is_exported_and_bound_and_nothing_else():
+    """What this library adds to the shared contract (tests/test_side_libraries_cpu.py: the bound functions are the declared
+    and the exported ones, the constants and the struct are the header's)."""
+    from macaronicusermodeling_amd import cutsetis
     M = _M()
-    names = declared_functions()
-    assert len(names) == 7 and 'mlbp_cutdraw_f64' in names
-    exported = sorted(n for n, (_, typ) in K._symbols(M.LIB_PATH).items() if n.startswith('mlbp_') and typ == K._STT_FUNC)
-    assert exported == names, set(exported) ^ set(names)
-    assert sorted(M.SIGNATURES) == names, set(M.SIGNATURES) ^ set(names)
-    raw = ctypes.CDLL(M.LIB_PATH)
-    for n in names:
-        assert hasattr(raw, n)
-    from macaronicusermodeling_amd import _ffi, converge, cutset, cutsetis, exactgrad, exactmap, exactmbest, exactsample, logz, mapdecode, sample
-    for other in (_ffi, mapdecode, logz, sample, converge, cutset, exactmap, exactgrad, exactsample, exactmbest, cutsetis):
-        assert not set(M.SIGNATURES) & set(other.SIGNATURES)
     text = open(HEADER).read()
-    for name, value in (('KERNEL_NONE', M.KERNEL_NONE), ('KERNEL_X64', M.KERNEL_X64), ('KERNEL_GENERIC', M.KERNEL_GENERIC),
-                        ('MAX_LISTED', M.MAX_LISTED), ('MAX_CUT', M.MAX_CUT), ('MAX_X', M.MAX_X), ('MIN_WORKGROUPS', M.MIN_WORKGROUPS),
-                        ('PLAN_HEADER', M.PLAN_HEADER)):
-        assert int(re.search(r'#define MLBP_CUTDRAW_%s (\d+)' % name, text).group(1)) == value, name
     assert (M.MAX_LISTED, M.MAX_CUT, M.MIN_WORKGROUPS) == (cutsetis.MAX_LISTED, cutsetis.MAX_CUT, cutsetis.MIN_WORKGROUPS) == (65536, 16, 512)
-    body = re.sub(r'/\*.*?\*/', '', re.search(r'typedef struct mlbp_cutdraw_args \{(.*?)\} mlbp_cutdraw_args;', text, flags=re.S).group(1), flags=re.S)
-    fields = [n for decl in body.split(';') for n in re.findall(r'(\w+)\s*(?:,|$)', decl.strip())]
-    assert fields == [f[0] for f in M.CutdrawArgs._fields_], fields
-    assert fields == ['B', 'X', 'n_msgs', 'P', 'n_cut', 'n_pair_tables', 'plan_words', 'N', 'plan', 'pair_tables', 'pair_tab', 'msgs', 'uniforms',
+    assert [f[0] for f in M.CutdrawArgs._fields_] == ['B', 'X', 'n_msgs', 'P', 'n_cut', 'n_pair_tables', 'plan_words', 'N', 'plan', 'pair_tables', 'pair_tab', 'msgs', 'uniforms',
                       'configs_in', 'configs', 'log_q']
     flat = ' '.join(text.replace('*', ' ').split())
     for word in ('is 1, for any positive messages', 'q(c) = Z_c / Z exactly', 'do not depend on B, N, the grid or the wave',
@@ -475,58 +454,22 @@ def test_kernel_choice_and_chunks_are_the_rules_of_the_header():
 
 
 # ------------------------------------------------------------------------------------------------
-# kernel inventory of libmlbp_cutdraw.so: the rule of tests/test_kernel_inventory.py applied to the twelfth library
+# kernel inventory: tests/test_side_libraries_cpu.py holds the shared rule; what the twelfth library added to it
 # ------------------------------------------------------------------------------------------------
 PKG = os.path.join(ROOT, 'macaronicusermodeling_amd')
-CSRC_CUTDRAW = os.path.join(PKG, 'csrc_cutdraw')
-KERNELS = {'cutdraw_x64_kernel', 'cutdraw_generic_kernel'}
 
 
 def test_cutdraw_library_kernels_are_the_sources_kernels_and_each_has_a_case():
     import test_gpu_cutdraw as G
-    src = K.kernel_names(csrc=CSRC_CUTDRAW)
-    assert src == KERNELS
-    compiled = R._kernels_of(_M().LIB_PATH)
-    assert compiled == {(name, ()) for name in src}
-    assert set(G.CASES) == compiled, set(G.CASES) ^ compiled
-    for kern, tests in G.CASES.items():
-        assert tests, kern
-        for t in tests:
-            assert callable(getattr(G, t, None)), (kern, t)
     assert set(G.INPUTS_USED) == set(INPUTS), set(G.INPUTS_USED) ^ set(INPUTS)       # every input compared there is checked here
     for name, test in G.INPUTS_USED.items():
         assert callable(getattr(G, test, None)), (name, test)
 
 
 def test_the_other_libraries_hold_no_cutdraw_kernel_and_the_draw_helpers_hold_no_kernel():
-    from macaronicusermodeling_amd import converge, cutset, cutsetis, exactgrad, exactmap, exactmbest, exactsample, logz, mapdecode, sample
-    import test_exactsample_cpu
-    assert not [k for k in K.all_compiled() if k[0].startswith('cutdraw_')]
-    for other in (mapdecode, logz, sample, converge, cutset, exactmap, exactgrad, exactsample, exactmbest, cutsetis):
-        assert not [k for k in R._kernels_of(other.LIB_PATH) if k[0].startswith('cutdraw_')]
-    assert {n for n, _ in R._kernels_of(exactsample.LIB_PATH)} == test_exactsample_cpu.KERNELS      # the move left its inventory closed
-    names = K.kernel_names(csrc=CSRC_CUTDRAW)
-    assert all(n.startswith('cutdraw_') for n in names)
-    for csrc in ('csrc', 'csrc_map', 'csrc_logz', 'csrc_sample', 'csrc_converge', 'csrc_cutset', 'csrc_exactmap', 'csrc_exactgrad', 'csrc_exactsample',
-                 'csrc_exactmbest', 'csrc_cutsetis'):
-        assert not names & K.kernel_names(csrc=os.path.join(PKG, csrc))
     shared = open(os.path.join(PKG, 'csrc', 'mlbp_draw_device.h')).read()
     assert '__global__' not in shared                           # helpers only
     for helper in ('wave_scan', 'wave_draw', 'block_min_max', 'block_draw'):
         assert re.search(r'\b%s\(' % helper, shared), helper
-    mine = open(os.path.join(CSRC_CUTDRAW, 'mlbp_cutdraw.hip')).read()
+    mine = open(os.path.join(PKG, 'csrc_cutdraw', 'mlbp_cutdraw.hip')).read()
     assert 'mlbp_draw_device.h' in mine and 'mlbp_cutset.h' not in mine and 'mlbp_cutset_walk.h' not in mine
-    for f in os.listdir(CSRC_CUTDRAW):
-        assert f.endswith(('.hip', '.h', '.o')), f
-
-
-def test_build_lists_the_library():
-    """By membership, not by a total: the next library joins the list without touching this test."""
-    from macaronicusermodeling_amd import build as B
-    mine = [e for e in B.MORE_LIBRARIES if os.path.basename(e[4]) == 'libmlbp_cutdraw.so']
-    assert len(mine) == 1
-    csrc, sources, headers, public, lib = mine[0]
-    assert (os.path.basename(csrc), sources, public) == ('csrc_cutdraw', ['mlbp_cutdraw.hip'], 'mlbp_cutdraw.h')
-    assert headers == B.HEADERS_SIDE and 'mlbp_draw_device.h' in B.HEADERS_SIDE
-    assert os.path.dirname(lib) == os.path.dirname(B.LIB) and lib == _M().LIB_PATH
-    assert not set(e[4] for e in B.MORE_LIBRARIES) & set(e[4] for e in B.LIBRARIES + B.LATER_LIBRARIES)

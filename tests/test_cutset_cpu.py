@@ -1,6 +1,6 @@
 """Exact inference by cutset conditioning without a GPU: the float64 references the GPU tests compare against, the NumPy
-statement of include/mlbp_cutset.h pinned on exhaustive enumeration, the cutset choice, the C ABI of libmlbp_cutset.so and the
-kernel inventory rule applied to the sixth library.
+statement of include/mlbp_cutset.h pinned on exhaustive enumeration, the cutset choice and the host checks of libmlbp_cutset.so
+(the contract it shares with the other side libraries is in tests/test_side_libraries_cpu.py).
 
 References.  enumerate_exact() is the log-domain grid of test_map_cpu.brute_force, then log-sum-exp and axis sums: nothing of
 the algorithm under test is in it.  Where X^n is too large, eliminate() sums variables out one at a time with einsum / matmul
@@ -9,17 +9,13 @@ condition() states the header's semantics in NumPy -- condition on every joint s
 up and one pass down, combine -- and must equal the grid for every graph family the GPU module uses."""
 import ctypes
 import itertools
-import os
-import re
 
 import numpy as np
 import pytest
 
 import cases as C
 import helpers
-import kernel_inventory as K
 import test_map_cpu as W
-from conftest import ROOT
 from oracle import lbp_oracle as O
 
 
@@ -360,38 +356,10 @@ def _ffi():
 # ------------------------------------------------------------------------------------------------
 # C ABI of libmlbp_cutset.so
 # ------------------------------------------------------------------------------------------------
-HEADER = os.path.join(ROOT, 'include', 'mlbp_cutset.h')
-
-
-def declared_functions():
-    text = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r'\b(mlbp_cutset_[a-z0-9_]+)\s*\(', text)))
-
-
 def test_every_declared_symbol_is_exported_and_bound_and_nothing_else():
-    S = _S()
-    names = declared_functions()
-    assert len(names) == 8 and 'mlbp_cutset_f64' in names
-    exported = sorted(n for n, (_, typ) in K._symbols(S.LIB_PATH).items() if n.startswith('mlbp_') and typ == K._STT_FUNC)
-    assert exported == names, set(exported) ^ set(names)
-    assert sorted(S.SIGNATURES) == names, set(S.SIGNATURES) ^ set(names)
-    raw = ctypes.CDLL(S.LIB_PATH)
-    for n in names:
-        assert hasattr(raw, n)
-    from macaronicusermodeling_amd import _ffi, converge, logz, mapdecode, sample
-    for other in (_ffi, mapdecode, logz, sample, converge):
-        assert not set(S.SIGNATURES) & set(other.SIGNATURES)
-    text = open(HEADER).read()
-    for name, value in (('X64_LDS_BYTES', S.X64_LDS_BYTES), ('GENERIC_LDS_BYTES', S.GENERIC_LDS_BYTES), ('MAX_X', S.MAX_X),
-                        ('MAX_CONFIGS', S.MAX_CONFIGS), ('MIN_WORKGROUPS', S.MIN_WORKGROUPS), ('PLAN_HEADER', S.PLAN_HEADER),
-                        ('KERNEL_NONE', S.KERNEL_NONE), ('KERNEL_X64', S.KERNEL_X64), ('KERNEL_GENERIC', S.KERNEL_GENERIC),
-                        ('ITEM_UNARY', S.ITEM_UNARY), ('ITEM_COL', S.ITEM_COL), ('ITEM_ROW', S.ITEM_ROW), ('CONST_UNARY', S.CONST_UNARY),
-                        ('CONST_PAIR', S.CONST_PAIR)):
-        assert int(re.search(r'#define MLBP_CUTSET_%s (\d+)' % name, text).group(1)) == value, name
-    assert S.MAX_CONFIGS == 65536
-    body = re.sub(r'/\*.*?\*/', '', re.search(r'typedef struct mlbp_cutset_args \{(.*?)\} mlbp_cutset_args;', text, flags=re.S).group(1), flags=re.S)
-    fields = [n for decl in body.split(';') for n in re.findall(r'(\w+)\s*(?:,|$)', decl.strip())]
-    assert fields == [f[0] for f in S.CutsetArgs._fields_], fields
+    """What this library adds to the shared contract (tests/test_side_libraries_cpu.py: the bound functions are the declared
+    and the exported ones, the constants and the struct are the header's)."""
+    assert _S().MAX_CONFIGS == 65536
 
 
 def _valid_args(S, X=64, n_cut=1):
@@ -576,41 +544,3 @@ def test_check_plan_refuses_each_of_its_cases():
         S.Plan(ring, [0, 0], 4, None)
     with pytest.raises(ValueError):
         S.Plan(ring, [5], 4, None)
-
-
-# ------------------------------------------------------------------------------------------------
-# kernel inventory of libmlbp_cutset.so: the rule of tests/test_kernel_inventory.py applied to the sixth library
-# ------------------------------------------------------------------------------------------------
-CSRC_CUTSET = os.path.join(ROOT, 'macaronicusermodeling_amd', 'csrc_cutset')
-
-
-def _kernels_of(path):
-    found = {K.decode_kernel(n) for n, (_, typ) in K._symbols(path).items() if typ == K._STT_OBJECT}
-    return found - {None}
-
-
-def test_cutset_library_kernels_are_the_sources_kernels_and_each_has_a_case():
-    import test_gpu_cutset as G
-    src = K.kernel_names(csrc=CSRC_CUTSET)
-    assert src == {'cutset_x64_kernel', 'cutset_generic_kernel', 'cutset_combine_kernel'}
-    compiled = _kernels_of(_S().LIB_PATH)
-    assert compiled == {(name, ()) for name in src}
-    assert set(G.CASES) == compiled, set(G.CASES) ^ compiled
-    for kern, tests in G.CASES.items():
-        assert tests, kern
-        for t in tests:
-            assert callable(getattr(G, t, None)), (kern, t)
-
-
-def test_the_other_libraries_hold_no_cutset_kernel_and_the_sources_stay_apart():
-    from macaronicusermodeling_amd import converge, logz, mapdecode, sample
-    assert not [k for k in K.all_compiled() if k[0].startswith('cutset_')]
-    for other in (mapdecode, logz, sample, converge):
-        assert not [k for k in _kernels_of(other.LIB_PATH) if k[0].startswith('cutset_')]
-    names = K.kernel_names(csrc=CSRC_CUTSET)
-    assert all(n.startswith('cutset_') for n in names)
-    pkg = os.path.join(ROOT, 'macaronicusermodeling_amd')
-    for csrc in ('csrc', 'csrc_map', 'csrc_logz', 'csrc_sample', 'csrc_converge'):
-        assert not names & K.kernel_names(csrc=os.path.join(pkg, csrc))
-    for f in os.listdir(CSRC_CUTSET):
-        assert f.endswith(('.hip', '.h', '.o')), f

@@ -22,7 +22,6 @@ import numpy as np
 import pytest
 
 import cases as C
-import kernel_inventory as K
 import test_cutset_cpu as R
 from conftest import ROOT
 from oracle import lbp_oracle as O
@@ -365,33 +364,14 @@ def _ffi():
     return _ffi
 
 
-def declared_functions():
-    text = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r'\b(mlbp_cutsetis_[a-z0-9_]+)\s*\(', text)))
-
-
 def test_every_declared_symbol_is_exported_and_bound_and_nothing_else():
+    """What this library adds to the shared contract (tests/test_side_libraries_cpu.py: the bound functions are the declared
+    and the exported ones, the integer constants and the struct are the header's)."""
+    from macaronicusermodeling_amd import cutset
     M = _M()
-    names = declared_functions()
-    assert len(names) == 8 and 'mlbp_cutsetis_f64' in names
-    exported = sorted(n for n, (_, typ) in K._symbols(M.LIB_PATH).items() if n.startswith('mlbp_') and typ == K._STT_FUNC)
-    assert exported == names, set(exported) ^ set(names)
-    assert sorted(M.SIGNATURES) == names, set(M.SIGNATURES) ^ set(names)
-    raw = ctypes.CDLL(M.LIB_PATH)
-    for n in names:
-        assert hasattr(raw, n)
-    from macaronicusermodeling_amd import _ffi, converge, cutset, exactgrad, exactmap, exactmbest, exactsample, logz, mapdecode, sample
-    for other in (_ffi, mapdecode, logz, sample, converge, cutset, exactmap, exactgrad, exactsample, exactmbest):
-        assert not set(M.SIGNATURES) & set(other.SIGNATURES)
     text = open(HEADER).read()
-    for name, value in (('KERNEL_NONE', M.KERNEL_NONE), ('KERNEL_X64', M.KERNEL_X64), ('KERNEL_GENERIC', M.KERNEL_GENERIC),
-                        ('MAX_LISTED', M.MAX_LISTED), ('MAX_CUT', M.MAX_CUT), ('MIN_WORKGROUPS', M.MIN_WORKGROUPS)):
-        assert int(re.search(r'#define MLBP_CUTSETIS_%s (\d+)' % name, text).group(1)) == value, name
     assert float(re.search(r'#define MLBP_CUTSETIS_MAX_ABS_LOG_Q (\S+)', text).group(1)) == M.MAX_ABS_LOG_Q
     assert M.MAX_LISTED == MAX_LISTED and M.MIN_WORKGROUPS == cutset.MIN_WORKGROUPS
-    body = re.sub(r'/\*.*?\*/', '', re.search(r'typedef struct mlbp_cutsetis_args \{(.*?)\} mlbp_cutsetis_args;', text, flags=re.S).group(1), flags=re.S)
-    fields = [n for decl in body.split(';') for n in re.findall(r'(\w+)\s*(?:,|$)', decl.strip())]
-    assert fields == [f[0] for f in M.CutsetisArgs._fields_], fields
     for word in ('k = rint(-log_q / ln 2)', 'ess = 0', 'sqrt(1 / ess - 1 / N)', 'consistent, not unbiased', 'n_vars * X + 3', 'n_cut = 0'):
         assert word in text, word                               # what the issue asks the header to state
 
@@ -533,59 +513,14 @@ def test_kernel_choice_chunks_and_workspace_are_the_rules_of_the_header():
 
 
 # ------------------------------------------------------------------------------------------------
-# kernel inventory of libmlbp_cutsetis.so: the rule of tests/test_kernel_inventory.py applied to the eleventh library
+# kernel inventory: tests/test_side_libraries_cpu.py holds the shared rule; what the eleventh library added to it
 # ------------------------------------------------------------------------------------------------
-CSRC_CUTSETIS = os.path.join(ROOT, 'macaronicusermodeling_amd', 'csrc_cutsetis')
-KERNELS = {'cutsetis_x64_kernel', 'cutsetis_generic_kernel', 'cutsetis_combine_kernel'}
-
-
 def test_cutsetis_library_kernels_are_the_sources_kernels_and_each_has_a_case():
     import test_gpu_cutsetis as G
-    src = K.kernel_names(csrc=CSRC_CUTSETIS)
-    assert src == KERNELS
-    compiled = R._kernels_of(_M().LIB_PATH)
-    assert compiled == {(name, ()) for name in src}
-    assert set(G.CASES) == compiled, set(G.CASES) ^ compiled
-    for kern, tests in G.CASES.items():
-        assert tests, kern
-        for t in tests:
-            assert callable(getattr(G, t, None)), (kern, t)
     assert set(G.INPUTS_USED) == set(INPUTS), set(G.INPUTS_USED) ^ set(INPUTS)       # every input compared there is checked here
 
 
 def test_the_other_libraries_hold_no_cutsetis_kernel_and_the_sources_stay_apart():
-    from macaronicusermodeling_amd import converge, cutset, exactgrad, exactmap, exactmbest, exactsample, logz, mapdecode, sample
-    import test_exactgrad_cpu
-    import test_exactmap_cpu
-    import test_exactmbest_cpu
-    import test_exactsample_cpu
-    assert not [k for k in K.all_compiled() if k[0].startswith('cutsetis_')]
-    for other in (mapdecode, logz, sample, converge, cutset, exactmap, exactgrad, exactsample, exactmbest):
-        assert not [k for k in R._kernels_of(other.LIB_PATH) if k[0].startswith('cutsetis_')]
-    # and no kernel has appeared in a sibling: each still holds its own closed inventory
-    assert {n for n, _ in R._kernels_of(cutset.LIB_PATH)} == K.kernel_names(csrc=R.CSRC_CUTSET)
-    assert {n for n, _ in R._kernels_of(exactmap.LIB_PATH)} == K.kernel_names(csrc=test_exactmap_cpu.CSRC_EXACTMAP)
-    assert {n for n, _ in R._kernels_of(exactgrad.LIB_PATH)} == K.kernel_names(csrc=test_exactgrad_cpu.CSRC_EXACTGRAD)
-    assert {n for n, _ in R._kernels_of(exactsample.LIB_PATH)} == test_exactsample_cpu.KERNELS
-    assert {n for n, _ in R._kernels_of(exactmbest.LIB_PATH)} == test_exactmbest_cpu.KERNELS
-    names = K.kernel_names(csrc=CSRC_CUTSETIS)
-    assert all(n.startswith('cutsetis_') for n in names)
     pkg = os.path.join(ROOT, 'macaronicusermodeling_amd')
-    for csrc in ('csrc', 'csrc_map', 'csrc_logz', 'csrc_sample', 'csrc_converge', 'csrc_cutset', 'csrc_exactmap', 'csrc_exactgrad', 'csrc_exactsample',
-                 'csrc_exactmbest'):
-        assert not names & K.kernel_names(csrc=os.path.join(pkg, csrc))
     for shared in ('mlbp_cutset_plan.h', 'mlbp_cutset_walk.h'):
         assert '__global__' not in open(os.path.join(pkg, 'csrc', shared)).read()      # helpers only
-    for f in os.listdir(CSRC_CUTSETIS):
-        assert f.endswith(('.hip', '.h', '.o')), f
-
-
-def test_build_lists_the_library_among_the_later_ones():
-    from macaronicusermodeling_amd import build as B
-    mine = [e for e in B.LATER_LIBRARIES if os.path.basename(e[4]) == 'libmlbp_cutsetis.so']
-    assert len(mine) == 1
-    csrc, sources, headers, public, lib = mine[0]
-    assert (os.path.basename(csrc), sources, public) == ('csrc_cutsetis', ['mlbp_cutsetis.hip'], 'mlbp_cutsetis.h')
-    assert headers == B.HEADERS_SIDE + ['../../include/mlbp_cutset.h']
-    assert os.path.dirname(lib) == os.path.dirname(B.LIB) and not set(e[4] for e in B.LATER_LIBRARIES) & set(e[4] for e in B.LIBRARIES)
-    assert len(B.LIBRARIES) + len(B.LATER_LIBRARIES) == 11

@@ -1,7 +1,7 @@
 """Exact pair marginals, expected features and the true gradient by cutset conditioning without a GPU: the float64 references
 the GPU tests compare against, the NumPy statement of include/mlbp_exactgrad.h pinned on exhaustive enumeration, the
-derivative identity, the gap that tells exact from BP, the C ABI of libmlbp_exactgrad.so and the kernel inventory rule applied
-to the eighth library.
+derivative identity, the gap that tells exact from BP and the host checks of libmlbp_exactgrad.so
+(the contract it shares with the other side libraries is in tests/test_side_libraries_cpu.py).
 
 References.  pair_marginals_enum() is the log-domain grid of test_cutset_cpu.enumerate_exact summed over the axes of the other
 variables: nothing of the algorithm under test is in it.  condition_pairs() states the header in NumPy -- condition on every
@@ -10,18 +10,14 @@ a row or column per cutset-incident factor, a cell per cutset-internal factor --
 header's contraction of pair marginals and marginals with phi."""
 import ctypes
 import itertools
-import os
-import re
 
 import numpy as np
 import pytest
 
 import cases as C
 import helpers
-import kernel_inventory as K
 import test_cutset_cpu as R
 import test_map_cpu as W
-from conftest import ROOT
 from oracle import lbp_oracle as O
 
 
@@ -360,9 +356,6 @@ def test_bp_factor_beliefs_are_not_the_pair_marginals():
 # ------------------------------------------------------------------------------------------------
 # C ABI of libmlbp_exactgrad.so
 # ------------------------------------------------------------------------------------------------
-HEADER = os.path.join(ROOT, 'include', 'mlbp_exactgrad.h')
-
-
 def _M():
     from macaronicusermodeling_amd import exactgrad
     return exactgrad
@@ -373,31 +366,10 @@ def _ffi():
     return _ffi
 
 
-def declared_functions():
-    text = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r'\b(mlbp_exactgrad_[a-z0-9_]+)\s*\(', text)))
-
-
 def test_every_declared_symbol_is_exported_and_bound_and_nothing_else():
+    """What this library adds to the shared contract (tests/test_side_libraries_cpu.py: the bound functions are the declared
+    and the exported ones, the constants and the struct are the header's)."""
     M = _M()
-    names = declared_functions()
-    assert len(names) == 8 and 'mlbp_exactgrad_f64' in names
-    exported = sorted(n for n, (_, typ) in K._symbols(M.LIB_PATH).items() if n.startswith('mlbp_') and typ == K._STT_FUNC)
-    assert exported == names, set(exported) ^ set(names)
-    assert sorted(M.SIGNATURES) == names, set(M.SIGNATURES) ^ set(names)
-    raw = ctypes.CDLL(M.LIB_PATH)
-    for n in names:
-        assert hasattr(raw, n)
-    from macaronicusermodeling_amd import _ffi, converge, cutset, exactmap, logz, mapdecode, sample
-    for other in (_ffi, mapdecode, logz, sample, converge, cutset, exactmap):
-        assert not set(M.SIGNATURES) & set(other.SIGNATURES)
-    text = open(HEADER).read()
-    for name, value in (('KERNEL_NONE', M.KERNEL_NONE), ('KERNEL_X64', M.KERNEL_X64), ('KERNEL_GENERIC', M.KERNEL_GENERIC),
-                        ('X64_MAX_FOREST', M.X64_MAX_FOREST), ('MIN_WORKGROUPS', M.MIN_WORKGROUPS), ('MAX_FEATURES', M.MAX_FEATURES)):
-        assert int(re.search(r'#define MLBP_EXACTGRAD_%s (\d+)' % name, text).group(1)) == value, name
-    body = re.sub(r'/\*.*?\*/', '', re.search(r'typedef struct mlbp_exactgrad_args \{(.*?)\} mlbp_exactgrad_args;', text, flags=re.S).group(1), flags=re.S)
-    fields = [n for decl in body.split(';') for n in re.findall(r'(\w+)\s*(?:,|$)', decl.strip())]
-    assert fields == [f[0] for f in M.ExactGradArgs._fields_], fields
     # the layout: 16 int32, then pointers, with the one int64 among them -- no padding anywhere
     assert M.ExactGradArgs.plan.offset == 64 and M.ExactGradArgs.workspace_bytes.offset == 64 + 13 * 8
     assert ctypes.sizeof(M.ExactGradArgs) == 64 + 21 * 8
@@ -579,39 +551,3 @@ def test_kernel_choice_chunks_and_workspace_are_the_rules_of_the_header():
     assert M.lib.mlbp_exactgrad_workspace_bytes(1, 1024, 3, 3, 3, 1, 2) == E.MLBP_EUNSUPPORTED
     assert M.lib.mlbp_exactgrad_workspace_bytes(0, 64, 3, 3, 3, 1, 1) == E.MLBP_EINVAL
     assert M.workspace_bytes(8192, 64, 3, 3, 3, 1, 1) > 2 ** 31                              # 64-bit
-
-
-# ------------------------------------------------------------------------------------------------
-# kernel inventory of libmlbp_exactgrad.so: the rule of tests/test_kernel_inventory.py applied to the eighth library
-# ------------------------------------------------------------------------------------------------
-CSRC_EXACTGRAD = os.path.join(ROOT, 'macaronicusermodeling_amd', 'csrc_exactgrad')
-
-
-def test_exactgrad_library_kernels_are_the_sources_kernels_and_each_has_a_case():
-    import test_gpu_exactgrad as G
-    src = K.kernel_names(csrc=CSRC_EXACTGRAD)
-    assert src == {'exactgrad_x64_kernel', 'exactgrad_generic_kernel', 'exactgrad_combine_kernel'}
-    compiled = R._kernels_of(_M().LIB_PATH)
-    assert compiled == {('exactgrad_x64_kernel', (1,)), ('exactgrad_x64_kernel', (2,)), ('exactgrad_generic_kernel', ()),
-                        ('exactgrad_combine_kernel', ())}
-    assert {name for name, _ in compiled} == src
-    assert set(G.CASES) == compiled, set(G.CASES) ^ compiled
-    for kern, tests in G.CASES.items():
-        assert tests, kern
-        for t in tests:
-            assert callable(getattr(G, t, None)), (kern, t)
-
-
-def test_the_other_libraries_hold_no_exactgrad_kernel_and_the_sources_stay_apart():
-    from macaronicusermodeling_amd import converge, cutset, exactmap, logz, mapdecode, sample
-    assert not [k for k in K.all_compiled() if k[0].startswith('exactgrad_')]
-    for other in (mapdecode, logz, sample, converge, cutset, exactmap):
-        assert not [k for k in R._kernels_of(other.LIB_PATH) if k[0].startswith('exactgrad_')]
-    names = K.kernel_names(csrc=CSRC_EXACTGRAD)
-    assert all(n.startswith('exactgrad_') for n in names)
-    pkg = os.path.join(ROOT, 'macaronicusermodeling_amd')
-    for csrc in ('csrc', 'csrc_map', 'csrc_logz', 'csrc_sample', 'csrc_converge', 'csrc_cutset', 'csrc_exactmap'):
-        found = K.kernel_names(csrc=os.path.join(pkg, csrc))
-        assert not names & found and not [n for n in found if n.startswith('exactgrad_')]
-    for f in os.listdir(CSRC_EXACTGRAD):
-        assert f.endswith(('.hip', '.h', '.o')), f

@@ -16,7 +16,6 @@ import ctypes
 import functools
 import itertools
 import os
-import re
 
 import numpy as np
 import pytest
@@ -347,9 +346,6 @@ def test_the_tie_rule_of_the_statement():
 # ------------------------------------------------------------------------------------------------
 # C ABI of libmlbp_exactmap.so
 # ------------------------------------------------------------------------------------------------
-HEADER = os.path.join(ROOT, 'include', 'mlbp_exactmap.h')
-
-
 def _M():
     from macaronicusermodeling_amd import exactmap
     return exactmap
@@ -358,33 +354,6 @@ def _M():
 def _ffi():
     from macaronicusermodeling_amd import _ffi
     return _ffi
-
-
-def declared_functions():
-    text = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r'\b(mlbp_exactmap_[a-z0-9_]+)\s*\(', text)))
-
-
-def test_every_declared_symbol_is_exported_and_bound_and_nothing_else():
-    M = _M()
-    names = declared_functions()
-    assert len(names) == 8 and 'mlbp_exactmap_f64' in names
-    exported = sorted(n for n, (_, typ) in K._symbols(M.LIB_PATH).items() if n.startswith('mlbp_') and typ == K._STT_FUNC)
-    assert exported == names, set(exported) ^ set(names)
-    assert sorted(M.SIGNATURES) == names, set(M.SIGNATURES) ^ set(names)
-    raw = ctypes.CDLL(M.LIB_PATH)
-    for n in names:
-        assert hasattr(raw, n)
-    from macaronicusermodeling_amd import _ffi, converge, cutset, logz, mapdecode, sample
-    for other in (_ffi, mapdecode, logz, sample, converge, cutset):
-        assert not set(M.SIGNATURES) & set(other.SIGNATURES)
-    text = open(HEADER).read()
-    for name, value in (('KERNEL_NONE', M.KERNEL_NONE), ('KERNEL_X64', M.KERNEL_X64), ('KERNEL_GENERIC', M.KERNEL_GENERIC),
-                        ('PARTIAL_HEADER', M.PARTIAL_HEADER), ('DROP_BELOW', M.DROP_BELOW)):
-        assert int(re.search(r'#define MLBP_EXACTMAP_%s (\d+)' % name, text).group(1)) == value, name
-    body = re.sub(r'/\*.*?\*/', '', re.search(r'typedef struct mlbp_exactmap_args \{(.*?)\} mlbp_exactmap_args;', text, flags=re.S).group(1), flags=re.S)
-    fields = [n for decl in body.split(';') for n in re.findall(r'(\w+)\s*(?:,|$)', decl.strip())]
-    assert fields == [f[0] for f in M.ExactMapArgs._fields_], fields
 
 
 def _valid_args(M, X=64, n_cut=1):
@@ -514,38 +483,10 @@ def test_kernel_choice_chunks_and_workspace_are_the_rules_of_the_header():
 
 
 # ------------------------------------------------------------------------------------------------
-# kernel inventory of libmlbp_exactmap.so: the rule of tests/test_kernel_inventory.py applied to the seventh library
+# kernel inventory: tests/test_side_libraries_cpu.py holds the shared rule; what the seventh library added to it
 # ------------------------------------------------------------------------------------------------
-CSRC_EXACTMAP = os.path.join(ROOT, 'macaronicusermodeling_amd', 'csrc_exactmap')
-
-
-def test_exactmap_library_kernels_are_the_sources_kernels_and_each_has_a_case():
-    import test_gpu_exactmap as G
-    src = K.kernel_names(csrc=CSRC_EXACTMAP)
-    assert src == {'exactmap_x64_kernel', 'exactmap_generic_kernel', 'exactmap_final_kernel'}
-    compiled = R._kernels_of(_M().LIB_PATH)
-    assert compiled == {('exactmap_x64_kernel', (False,)), ('exactmap_x64_kernel', (True,)), ('exactmap_generic_kernel', (False,)),
-                        ('exactmap_generic_kernel', (True,)), ('exactmap_final_kernel', ())}
-    assert {name for name, _ in compiled} == src
-    assert set(G.CASES) == compiled, set(G.CASES) ^ compiled
-    for kern, tests in G.CASES.items():
-        assert tests, kern
-        for t in tests:
-            assert callable(getattr(G, t, None)), (kern, t)
-
-
 def test_the_other_libraries_hold_no_exactmap_kernel_and_the_sources_stay_apart():
-    from macaronicusermodeling_amd import converge, cutset, logz, mapdecode, sample
-    assert not [k for k in K.all_compiled() if k[0].startswith('exactmap_')]
-    for other in (mapdecode, logz, sample, converge, cutset):
-        assert not [k for k in R._kernels_of(other.LIB_PATH) if k[0].startswith('exactmap_')]
-    names = K.kernel_names(csrc=CSRC_EXACTMAP)
-    assert all(n.startswith('exactmap_') for n in names)
     pkg = os.path.join(ROOT, 'macaronicusermodeling_amd')
-    for csrc in ('csrc', 'csrc_map', 'csrc_logz', 'csrc_sample', 'csrc_converge', 'csrc_cutset'):
-        assert not names & K.kernel_names(csrc=os.path.join(pkg, csrc))
     assert not K.kernel_names(csrc=os.path.join(pkg, 'csrc')) & {'check_packed_plan'}
     shared = open(os.path.join(pkg, 'csrc', 'mlbp_cutset_plan.h')).read()
     assert '__global__' not in shared                           # helpers only: the first library's inventory scans csrc/
-    for f in os.listdir(CSRC_EXACTMAP):
-        assert f.endswith(('.hip', '.h', '.o')), f

@@ -17,13 +17,11 @@ there the rows must be pairwise distinct and the multiset of their scores enumer
 import ctypes
 import functools
 import os
-import re
 
 import numpy as np
 import pytest
 
 import cases as C
-import kernel_inventory as K
 import test_cutset_cpu as R
 import test_exactmap_cpu as E
 import test_map_cpu as W
@@ -495,32 +493,11 @@ def _ffi():
     return _ffi
 
 
-def declared_functions():
-    text = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r'\b(mlbp_exactmbest_[a-z0-9_]+)\s*\(', text)))
-
-
 def test_every_declared_symbol_is_exported_and_bound_and_nothing_else():
-    M = _M()
-    names = declared_functions()
-    assert len(names) == 9 and 'mlbp_exactmbest_f64' in names
-    exported = sorted(n for n, (_, typ) in K._symbols(M.LIB_PATH).items() if n.startswith('mlbp_') and typ == K._STT_FUNC)
-    assert exported == names, set(exported) ^ set(names)
-    assert sorted(M.SIGNATURES) == names, set(M.SIGNATURES) ^ set(names)
-    raw = ctypes.CDLL(M.LIB_PATH)
-    for n in names:
-        assert hasattr(raw, n)
-    from macaronicusermodeling_amd import _ffi, converge, cutset, exactgrad, exactmap, exactsample, logz, mapdecode, sample
-    for other in (_ffi, mapdecode, logz, sample, converge, cutset, exactmap, exactgrad, exactsample):
-        assert not set(M.SIGNATURES) & set(other.SIGNATURES)
+    """What this library adds to the shared contract (tests/test_side_libraries_cpu.py: the bound functions are the declared
+    and the exported ones, the constants and the struct are the header's)."""
+    assert _M().MAX_M == MAX_M
     text = open(HEADER).read()
-    for name, value in (('KERNEL_NONE', M.KERNEL_NONE), ('KERNEL_X64', M.KERNEL_X64), ('KERNEL_GENERIC', M.KERNEL_GENERIC), ('MAX_M', M.MAX_M),
-                        ('LISTS_FIXED', M.LISTS_FIXED)):
-        assert int(re.search(r'#define MLBP_EXACTMBEST_%s (\d+)' % name, text).group(1)) == value, name
-    assert M.MAX_M == MAX_M
-    body = re.sub(r'/\*.*?\*/', '', re.search(r'typedef struct mlbp_exactmbest_args \{(.*?)\} mlbp_exactmbest_args;', text, flags=re.S).group(1), flags=re.S)
-    fields = [n for decl in body.split(';') for n in re.findall(r'(\w+)\s*(?:,|$)', decl.strip())]
-    assert fields == [f[0] for f in M.ExactMbestArgs._fields_], fields
     for word in ('THIS DIFFERS', 'n_found = -1', '(a + 1) * (b + 1) <= M', 'MLBP_EXACTMBEST_DROP_BELOW'):     # what the issue asks the header to state
         assert word in text, word
 
@@ -694,58 +671,14 @@ def test_kernel_choice_chunks_and_workspace_are_the_rules_of_the_header():
 
 
 # ------------------------------------------------------------------------------------------------
-# kernel inventory of libmlbp_exactmbest.so: the rule of tests/test_kernel_inventory.py applied to the tenth library
+# kernel inventory: tests/test_side_libraries_cpu.py holds the shared rule; what the tenth library added to it
 # ------------------------------------------------------------------------------------------------
-CSRC_EXACTMBEST = os.path.join(ROOT, 'macaronicusermodeling_amd', 'csrc_exactmbest')
-KERNELS = {'exactmbest_values_x64_kernel', 'exactmbest_values_generic_kernel', 'exactmbest_select_kernel',
-           'exactmbest_lists_x64_kernel', 'exactmbest_lists_generic_kernel', 'exactmbest_merge_kernel'}
-
-
 def test_exactmbest_library_kernels_are_the_sources_kernels_and_each_has_a_case():
     import test_gpu_exactmbest as G
-    src = K.kernel_names(csrc=CSRC_EXACTMBEST)
-    assert src == KERNELS
-    compiled = R._kernels_of(_M().LIB_PATH)
-    assert compiled == {(name, ()) for name in src}
-    assert set(G.CASES) == compiled, set(G.CASES) ^ compiled
-    for kern, tests in G.CASES.items():
-        assert tests, kern
-        for t in tests:
-            assert callable(getattr(G, t, None)), (kern, t)
     assert set(G.INPUTS_USED) == set(INPUTS), set(G.INPUTS_USED) ^ set(INPUTS)       # every input ranked there has its gaps here
 
 
 def test_the_other_libraries_hold_no_exactmbest_kernel_and_the_sources_stay_apart():
-    from macaronicusermodeling_amd import converge, cutset, exactgrad, exactmap, exactsample, logz, mapdecode, sample
-    import test_exactgrad_cpu
-    import test_exactsample_cpu
-    assert not [k for k in K.all_compiled() if k[0].startswith('exactmbest_')]
-    for other in (mapdecode, logz, sample, converge, cutset, exactmap, exactgrad, exactsample):
-        assert not [k for k in R._kernels_of(other.LIB_PATH) if k[0].startswith('exactmbest_')]
-    # and no kernel has appeared in a sibling: each still holds its own closed inventory
-    assert {n for n, _ in R._kernels_of(exactmap.LIB_PATH)} == K.kernel_names(csrc=E.CSRC_EXACTMAP)
-    assert {n for n, _ in R._kernels_of(cutset.LIB_PATH)} == K.kernel_names(csrc=R.CSRC_CUTSET)
-    assert {n for n, _ in R._kernels_of(exactsample.LIB_PATH)} == test_exactsample_cpu.KERNELS
-    assert {n for n, _ in R._kernels_of(exactgrad.LIB_PATH)} == K.kernel_names(csrc=test_exactgrad_cpu.CSRC_EXACTGRAD)
-    names = K.kernel_names(csrc=CSRC_EXACTMBEST)
-    assert all(n.startswith('exactmbest_') for n in names)
     pkg = os.path.join(ROOT, 'macaronicusermodeling_amd')
-    for csrc in ('csrc', 'csrc_map', 'csrc_logz', 'csrc_sample', 'csrc_converge', 'csrc_cutset', 'csrc_exactmap', 'csrc_exactgrad', 'csrc_exactsample'):
-        assert not names & K.kernel_names(csrc=os.path.join(pkg, csrc))
     for shared in ('mlbp_cutset_plan.h', 'mlbp_cutset_walk.h'):
         assert '__global__' not in open(os.path.join(pkg, 'csrc', shared)).read()      # helpers only
-    for f in os.listdir(CSRC_EXACTMBEST):
-        assert f.endswith(('.hip', '.h', '.o')), f
-
-
-def test_build_lists_the_library_among_the_later_ones():
-    from macaronicusermodeling_amd import build as B
-    mine = [e for e in B.LATER_LIBRARIES if os.path.basename(e[4]) == 'libmlbp_exactmbest.so']
-    assert len(mine) == 1
-    csrc, sources, headers, public, lib = mine[0]
-    assert (os.path.basename(csrc), sources, public) == ('csrc_exactmbest', ['mlbp_exactmbest.hip'], 'mlbp_exactmbest.h')
-    assert headers == B.HEADERS_SIDE + ['../../include/mlbp_cutset.h']
-    assert os.path.dirname(lib) == os.path.dirname(B.LIB) and not set(e[4] for e in B.LATER_LIBRARIES) & set(e[4] for e in B.LIBRARIES)
-    for entry in B.LATER_LIBRARIES:
-        assert len(entry) == 5 and all(os.path.exists(os.path.join(entry[0], s)) for s in entry[1])
-        assert os.path.exists(os.path.join(B.INCLUDE, entry[3]))

@@ -20,13 +20,11 @@ import ctypes
 import functools
 import itertools
 import os
-import re
 
 import numpy as np
 import pytest
 
 import cases as C
-import kernel_inventory as K
 import test_cutset_cpu as R
 import test_map_cpu as W
 from conftest import ROOT
@@ -376,30 +374,10 @@ def _ffi():
     return _ffi
 
 
-def declared_functions():
-    text = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r'\b(mlbp_exactsample_[a-z0-9_]+)\s*\(', text)))
-
-
 def test_every_declared_symbol_is_exported_and_bound_and_nothing_else():
-    M = _M()
-    names = declared_functions()
-    assert len(names) == 8 and 'mlbp_exactsample_f64' in names
-    exported = sorted(n for n, (_, typ) in K._symbols(M.LIB_PATH).items() if n.startswith('mlbp_') and typ == K._STT_FUNC)
-    assert exported == names, set(exported) ^ set(names)
-    assert sorted(M.SIGNATURES) == names, set(M.SIGNATURES) ^ set(names)
-    raw = ctypes.CDLL(M.LIB_PATH)
-    for n in names:
-        assert hasattr(raw, n)
-    from macaronicusermodeling_amd import _ffi, converge, cutset, exactgrad, exactmap, logz, mapdecode, sample
-    for other in (_ffi, mapdecode, logz, sample, converge, cutset, exactmap, exactgrad):
-        assert not set(M.SIGNATURES) & set(other.SIGNATURES)
+    """What this library adds to the shared contract (tests/test_side_libraries_cpu.py: the bound functions are the declared
+    and the exported ones, the constants and the struct are the header's)."""
     text = open(HEADER).read()
-    for name, value in (('KERNEL_NONE', M.KERNEL_NONE), ('KERNEL_X64', M.KERNEL_X64), ('KERNEL_GENERIC', M.KERNEL_GENERIC), ('HEAD', M.HEAD)):
-        assert int(re.search(r'#define MLBP_EXACTSAMPLE_%s (\d+)' % name, text).group(1)) == value, name
-    body = re.sub(r'/\*.*?\*/', '', re.search(r'typedef struct mlbp_exactsample_args \{(.*?)\} mlbp_exactsample_args;', text, flags=re.S).group(1), flags=re.S)
-    fields = [n for decl in body.split(';') for n in re.findall(r'(\w+)\s*(?:,|$)', decl.strip())]
-    assert fields == [f[0] for f in M.ExactSampleArgs._fields_], fields
     for word in ('given=', 'float32', 'grouped', 'MLBP_CUTSET_MAX_CONFIGS'):      # the "not done" list
         assert word in text[text.index('Not done'):text.index('#ifndef')], word
 
@@ -535,46 +513,9 @@ def test_kernel_choice_chunks_and_workspace_are_the_rules_of_the_header():
 
 
 # ------------------------------------------------------------------------------------------------
-# kernel inventory of libmlbp_exactsample.so: the rule of tests/test_kernel_inventory.py applied to the ninth library
+# kernel inventory: tests/test_side_libraries_cpu.py holds the shared rule; what the ninth library added to it
 # ------------------------------------------------------------------------------------------------
-CSRC_EXACTSAMPLE = os.path.join(ROOT, 'macaronicusermodeling_amd', 'csrc_exactsample')
-KERNELS = {'exactsample_weights_x64_kernel', 'exactsample_weights_generic_kernel', 'exactsample_scan_kernel',
-           'exactsample_draw_x64_kernel', 'exactsample_draw_generic_kernel'}
-
-
-def test_exactsample_library_kernels_are_the_sources_kernels_and_each_has_a_case():
-    import test_gpu_exactsample as G
-    src = K.kernel_names(csrc=CSRC_EXACTSAMPLE)
-    assert src == KERNELS
-    compiled = R._kernels_of(_M().LIB_PATH)
-    assert compiled == {(name, ()) for name in src}
-    assert set(G.CASES) == compiled, set(G.CASES) ^ compiled
-    for kern, tests in G.CASES.items():
-        assert tests, kern
-        for t in tests:
-            assert callable(getattr(G, t, None)), (kern, t)
-
-
 def test_the_other_libraries_hold_no_exactsample_kernel_and_the_sources_stay_apart():
-    from macaronicusermodeling_amd import converge, cutset, exactgrad, exactmap, logz, mapdecode, sample
-    assert not [k for k in K.all_compiled() if k[0].startswith('exactsample_')]
-    for other in (mapdecode, logz, sample, converge, cutset, exactmap, exactgrad):
-        assert not [k for k in R._kernels_of(other.LIB_PATH) if k[0].startswith('exactsample_')]
-    names = K.kernel_names(csrc=CSRC_EXACTSAMPLE)
-    assert all(n.startswith('exactsample_') for n in names)
     pkg = os.path.join(ROOT, 'macaronicusermodeling_amd')
-    for csrc in ('csrc', 'csrc_map', 'csrc_logz', 'csrc_sample', 'csrc_converge', 'csrc_cutset', 'csrc_exactmap', 'csrc_exactgrad'):
-        assert not names & K.kernel_names(csrc=os.path.join(pkg, csrc))
     for shared in ('mlbp_cutset_plan.h', 'mlbp_cutset_walk.h'):
         assert '__global__' not in open(os.path.join(pkg, 'csrc', shared)).read()      # helpers only
-    for f in os.listdir(CSRC_EXACTSAMPLE):
-        assert f.endswith(('.hip', '.h', '.o')), f
-
-
-def test_build_lists_nine_libraries():
-    from macaronicusermodeling_amd import build as B
-    assert len(B.LIBRARIES) == 9
-    csrc, sources, headers, public, lib = B.LIBRARIES[-1]
-    assert (os.path.basename(csrc), sources, public, os.path.basename(lib)) == ('csrc_exactsample', ['mlbp_exactsample.hip'], 'mlbp_exactsample.h',
-                                                                             'libmlbp_exactsample.so')
-    assert headers == B.HEADERS_SIDE + ['../../include/mlbp_cutset.h'] == B.LIBRARIES[-2][2]

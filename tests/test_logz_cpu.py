@@ -1,22 +1,18 @@
 """log Z and the joint log-likelihood without a GPU: the float64 NumPy statement of the formula the GPU tests compare against,
 pinned on exhaustive enumeration (trees) and on the Bethe free energy of the beliefs (loopy graphs); the C ABI of
-libmlbp_logz.so; and the kernel inventory rule applied to the third library.
+libmlbp_logz.so (the contract it shares with the other side libraries is in tests/test_side_libraries_cpu.py).
 
 The statement reads factor->variable messages only (include/mlbp_logz.h):
     log Z = sum_f log Z_f - sum_v (d_v - 1) log Z_v,    Z_f = the factor's table contracted with the leave-one-out products of
 its variables, Z_v = the sum of the product of all messages into v; products are pure products (no uniform 1/X, no nan_to_num).
 A variable with one factor has weight 0 and is left out.  Messages come from the oracle's own sweeps."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 
 import cases as C
-import kernel_inventory as K
 import test_map_cpu as W
-from conftest import ROOT
 from oracle import lbp_oracle as O
 
 
@@ -191,46 +187,9 @@ def test_message_form_is_the_bethe_value_on_loopy_graphs(name, make, seeds, root
 # ------------------------------------------------------------------------------------------------
 # C ABI of libmlbp_logz.so
 # ------------------------------------------------------------------------------------------------
-HEADER = os.path.join(ROOT, 'include', 'mlbp_logz.h')
-
-
 def _logz():
     from macaronicusermodeling_amd import logz
     return logz
-
-
-def declared_functions():
-    text = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r'\b(mlbp_logz_[a-z0-9_]+)\s*\(', text)))
-
-
-def test_every_declared_symbol_is_exported_and_bound_and_nothing_else():
-    L = _logz()
-    names = declared_functions()
-    assert len(names) == 6 and 'mlbp_logz_f64' in names
-    exported = sorted(n for n, (_, typ) in K._symbols(L.LIB_PATH).items() if n.startswith('mlbp_') and typ == K._STT_FUNC)
-    assert exported == names, set(exported) ^ set(names)
-    assert sorted(L.SIGNATURES) == names, set(L.SIGNATURES) ^ set(names)
-    raw = ctypes.CDLL(L.LIB_PATH)
-    for n in names:
-        assert hasattr(raw, n)
-    from macaronicusermodeling_amd import _ffi, mapdecode
-    assert not set(L.SIGNATURES) & set(_ffi.SIGNATURES) and not set(L.SIGNATURES) & set(mapdecode.SIGNATURES)
-    text = open(HEADER).read()
-    define = lambda name: int(re.search(r'#define %s (\d+)' % name, text).group(1))          # noqa: E731
-    assert define('MLBP_LOGZ_X64_LDS_BYTES') == L.X64_LDS_BYTES and define('MLBP_LOGZ_MAX_X') == L.MAX_X
-    assert define('MLBP_LOGZ_GROUP') == L.GROUP and define('MLBP_LOGZ_SHARED_PAIR_TABLES') == L.SHARED_PAIR_TABLES
-    assert [define('MLBP_LOGZ_KERNEL_' + k) for k in ('NONE', 'X64', 'X64_SHARED', 'GENERIC')] == \
-        [L.KERNEL_NONE, L.KERNEL_X64, L.KERNEL_X64_SHARED, L.KERNEL_GENERIC]
-    # the struct mirrors the header field for field
-    body = re.search(r'typedef struct mlbp_logz_args \{(.*?)\} mlbp_logz_args;', re.sub(r'/\*.*?\*/', '', text, flags=re.S), re.S).group(1)
-    fields = []
-    for decl in body.split(';'):
-        decl = decl.strip()
-        if decl:
-            kind = ctypes.c_void_p if '*' in decl else ctypes.c_int32
-            fields += [(n.strip().lstrip('*'), kind) for n in re.sub(r'^(const\s+)?\w+\s*\*?', '', decl, count=1).split(',')]
-    assert fields == [(n, t) for n, t in L.LogzArgs._fields_]
 
 
 def _valid_args(L, X=64):
@@ -358,41 +317,3 @@ def test_readout_arrays_follow_the_table_axes_and_f2v():
         f = by_id[topo.factor_ids[j]]
         assert topo.var_ids[uv[u]] == f['vars'][0] and keys[uis[u]] == ('F_%d' % f['id'], 'X_%d' % f['vars'][0])
     assert sorted(list(pis.reshape(-1)) + list(uis)) == sorted(int(s) for s in topo.in_slots)
-
-
-# ------------------------------------------------------------------------------------------------
-# kernel inventory of libmlbp_logz.so: the rule of tests/test_kernel_inventory.py applied to the third library
-# ------------------------------------------------------------------------------------------------
-CSRC_LOGZ = os.path.join(ROOT, 'macaronicusermodeling_amd', 'csrc_logz')
-
-
-def logz_kernels():
-    """Every kernel instance libmlbp_logz.so holds, as kernel_inventory names them."""
-    L = _logz()
-    found = {K.decode_kernel(n) for n, (_, typ) in K._symbols(L.LIB_PATH).items() if typ == K._STT_OBJECT}
-    return found - {None}
-
-
-def test_logz_library_kernels_are_the_sources_kernels_and_each_has_a_case():
-    import test_gpu_logz as G
-    src = K.kernel_names(csrc=CSRC_LOGZ)
-    assert src == {'logz_x64_kernel', 'logz_x64_shared_kernel', 'logz_generic_kernel', 'logz_sum_kernel'}
-    compiled = logz_kernels()
-    assert {name for name, _ in compiled} == src and len(compiled) == len(src)
-    import test_gpu_logz_edges as E
-    for module in (G, E):                                       # every kernel has a case in each of the two GPU modules
-        assert set(module.CASES) == compiled, set(module.CASES) ^ compiled
-        for kern, tests in module.CASES.items():
-            assert tests, kern
-            for t in tests:
-                assert callable(getattr(module, t, None)), (kern, t)
-
-
-def test_the_other_libraries_hold_no_logz_kernel_and_the_sources_stay_apart():
-    assert not [k for k in K.all_compiled() if k[0].startswith('logz_')]
-    assert not [k for k in W.map_kernels() if k[0].startswith('logz_')]
-    names = K.kernel_names(csrc=CSRC_LOGZ)
-    assert all(n.startswith('logz_') for n in names)
-    assert not names & K.kernel_names() and not names & K.kernel_names(csrc=W.CSRC_MAP)
-    for f in os.listdir(CSRC_LOGZ):
-        assert f.endswith(('.hip', '.h', '.o')), f

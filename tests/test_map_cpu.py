@@ -1,5 +1,6 @@
 """Max-product / MAP decoding without a GPU: the float64 NumPy walk the GPU tests compare against, pinned on exhaustive
-enumeration; the C ABI of libmlbp_map.so; and the kernel inventory rule applied to the second library.
+enumeration; and the host checks of libmlbp_map.so
+(the contract it shares with the other side libraries is in tests/test_side_libraries_cpu.py).
 
 The walk is FactorGraph.treelike_inference as oracle/lbp_oracle.py restates it, with ONE change: a pairwise
 factor-to-variable update takes max_j T[i][j] m[j] in place of the sum.  Schedule, initial messages, the variable update,
@@ -7,16 +8,12 @@ renormalisation and the product of incoming messages are the oracle's own functi
 the walk itself is pinned on brute force: log-potentials summed over the whole X^n grid and their argmax, which one sweep
 must reproduce on every tree."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 
 import cases as C
 import helpers
-import kernel_inventory as K
-from conftest import ROOT
 from oracle import lbp_oracle as O
 
 
@@ -180,34 +177,9 @@ def test_walk_never_beats_brute_force_on_loopy_graphs(name, make, seeds, roots):
 # ------------------------------------------------------------------------------------------------
 # C ABI of libmlbp_map.so
 # ------------------------------------------------------------------------------------------------
-HEADER = os.path.join(ROOT, 'include', 'mlbp_map.h')
-
-
 def _map():
     from macaronicusermodeling_amd import mapdecode
     return mapdecode
-
-
-def declared_functions():
-    text = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r'\b(mlbp_map_[a-z0-9_]+)\s*\(', text)))
-
-
-def test_every_declared_symbol_is_exported_and_bound_and_nothing_else():
-    M = _map()
-    names = declared_functions()
-    assert len(names) >= 6 and 'mlbp_map_sweep_f64' in names
-    exported = sorted(n for n, (_, typ) in K._symbols(M.LIB_PATH).items() if n.startswith('mlbp_') and typ == K._STT_FUNC)
-    assert exported == names, set(exported) ^ set(names)
-    assert sorted(M.SIGNATURES) == names, set(M.SIGNATURES) ^ set(names)
-    raw = ctypes.CDLL(M.LIB_PATH)
-    for n in names:
-        assert hasattr(raw, n)
-    from macaronicusermodeling_amd import _ffi
-    assert not set(M.SIGNATURES) & set(_ffi.SIGNATURES)          # the first library's table stays mlbp.h's mirror
-    text = open(HEADER).read()
-    assert int(re.search(r'#define MLBP_MAP_X64_LDS_BYTES (\d+)', text).group(1)) == M.X64_LDS_BYTES
-    assert int(re.search(r'#define MLBP_MAP_MAX_X (\d+)', text).group(1)) == M.MAX_X
 
 
 def _valid_args(M, X=64, n_msgs=27, n_vars=3):
@@ -334,38 +306,3 @@ def test_readout_arrays_follow_the_table_axes():
     hub = topo.var_index[0]
     assert sorted(int(r[0] == hub) for r in pav) == [0, 0, 1, 1] and all((r[0] == hub) != (r[1] == hub) for r in pav)
     assert list(uv) == [topo.var_index[by_id[topo.factor_ids[j]]['vars'][0]] for j in topo.unary_factors]
-
-
-# ------------------------------------------------------------------------------------------------
-# kernel inventory of libmlbp_map.so: the rule of tests/test_kernel_inventory.py applied to the second library
-# ------------------------------------------------------------------------------------------------
-CSRC_MAP = os.path.join(ROOT, 'macaronicusermodeling_amd', 'csrc_map')
-
-
-def map_kernels():
-    """Every kernel instance libmlbp_map.so holds, as kernel_inventory names them."""
-    M = _map()
-    found = {K.decode_kernel(n) for n, (_, typ) in K._symbols(M.LIB_PATH).items() if typ == K._STT_OBJECT}
-    return found - {None}
-
-
-def test_map_library_kernels_are_the_sources_kernels_and_each_has_a_case():
-    import test_gpu_map as G
-    src = K.kernel_names(csrc=CSRC_MAP)
-    assert src == {'map_sweep_x64_kernel', 'map_sweep_generic_kernel'}
-    compiled = map_kernels()
-    assert {name for name, _ in compiled} == src
-    import test_gpu_map_edges as E
-    for module in (G, E):                                       # every instance has a case in each of the two GPU modules
-        assert set(module.CASES) == compiled, set(module.CASES) ^ compiled
-        for kern, tests in module.CASES.items():
-            assert tests, kern
-            for t in tests:
-                assert callable(getattr(module, t, None)), (kern, t)
-
-
-def test_first_library_holds_no_map_kernel_and_the_sources_stay_apart():
-    assert not [k for k in K.all_compiled() if k[0].startswith('map_')]
-    assert not K.kernel_names() & K.kernel_names(csrc=CSRC_MAP)
-    for f in os.listdir(CSRC_MAP):
-        assert f.endswith(('.hip', '.h', '.o')), f

@@ -1,5 +1,6 @@
 """Posterior sampling without a GPU: the float64 NumPy walk the GPU tests compare against, pinned on exhaustive enumeration;
-the draw rule on dyadic marginals; the C ABI of libmlbp_sample.so; and the kernel inventory rule applied to the fourth library.
+the draw rule on dyadic marginals; and the host checks of libmlbp_sample.so
+(the contract it shares with the other side libraries is in tests/test_side_libraries_cpu.py).
 
 The walk is the semantics of include/mlbp_sample.h written with the oracle's own functions: schedule, initial messages,
 the product of incoming messages, the factor-to-variable update and renormalisation are oracle/lbp_oracle.py's;
@@ -9,17 +10,13 @@ log q(x) must equal log p(x) = grid[x] - logsumexp(grid) for EVERY assignment x 
 exact conditional read off the grid; on a loopy graph q must still be a distribution (sum to one) while differing from p."""
 import ctypes
 import itertools
-import os
-import re
 
 import numpy as np
 import pytest
 
 import cases as C
 import helpers
-import kernel_inventory as K
 import test_map_cpu as W
-from conftest import ROOT
 from oracle import lbp_oracle as O
 
 
@@ -317,42 +314,9 @@ def test_draw_rule_on_dyadic_marginals(X):
 # ------------------------------------------------------------------------------------------------
 # C ABI of libmlbp_sample.so
 # ------------------------------------------------------------------------------------------------
-HEADER = os.path.join(ROOT, 'include', 'mlbp_sample.h')
-
-
 def _S():
     from macaronicusermodeling_amd import sample
     return sample
-
-
-def declared_functions():
-    text = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r'\b(mlbp_sample_[a-z0-9_]+)\s*\(', text)))
-
-
-def test_every_declared_symbol_is_exported_and_bound_and_nothing_else():
-    S = _S()
-    names = declared_functions()
-    assert len(names) == 9 and 'mlbp_sample_f64' in names
-    exported = sorted(n for n, (_, typ) in K._symbols(S.LIB_PATH).items() if n.startswith('mlbp_') and typ == K._STT_FUNC)
-    assert exported == names, set(exported) ^ set(names)
-    assert sorted(S.SIGNATURES) == names, set(S.SIGNATURES) ^ set(names)
-    raw = ctypes.CDLL(S.LIB_PATH)
-    for n in names:
-        assert hasattr(raw, n)
-    from macaronicusermodeling_amd import _ffi, logz, mapdecode
-    for other in (_ffi, mapdecode, logz):
-        assert not set(S.SIGNATURES) & set(other.SIGNATURES)
-    text = open(HEADER).read()
-    assert int(re.search(r'#define MLBP_SAMPLE_X64_LDS_BYTES (\d+)', text).group(1)) == S.X64_LDS_BYTES
-    assert int(re.search(r'#define MLBP_SAMPLE_MAX_X (\d+)', text).group(1)) == S.MAX_X
-    assert int(re.search(r'#define MLBP_SAMPLE_MIN_WORKGROUPS (\d+)', text).group(1)) == S.MIN_WORKGROUPS
-    for name, value in (('NONE', S.KERNEL_NONE), ('X64', S.KERNEL_X64), ('GENERIC', S.KERNEL_GENERIC)):
-        assert int(re.search(r'#define MLBP_SAMPLE_KERNEL_%s (\d+)' % name, text).group(1)) == value
-    # the struct's fields, in the header's order
-    body = re.sub(r'/\*.*?\*/', '', re.search(r'typedef struct mlbp_sample_args \{(.*?)\} mlbp_sample_args;', text, flags=re.S).group(1), flags=re.S)
-    fields = [n for decl in body.split(';') for n in re.findall(r'(\w+)\s*(?:,|$)', decl.strip())]
-    assert fields == [f[0] for f in S.SampleArgs._fields_], fields
 
 
 def _valid_args(S, X=64, n_msgs=27, n_vars=3, B=2, n_samples=2):
@@ -494,48 +458,3 @@ def test_program_checks_refuse_what_would_index_outside_a_buffer():
     bad = topo.in_off.copy(); bad[1] = bad[2] + 1
     assert readout(in_off=bad) == _ffi.MLBP_EINVAL and 'monotone' in S.last_error()
     assert S.lib.mlbp_sample_check_readout(1, None, None, 1) == _ffi.MLBP_EINVAL and 'NULL' in S.last_error()
-
-
-# ------------------------------------------------------------------------------------------------
-# kernel inventory of libmlbp_sample.so: the rule of tests/test_kernel_inventory.py applied to the fourth library
-# ------------------------------------------------------------------------------------------------
-CSRC_SAMPLE = os.path.join(ROOT, 'macaronicusermodeling_amd', 'csrc_sample')
-
-
-def _kernels_of(path):
-    found = {K.decode_kernel(n) for n, (_, typ) in K._symbols(path).items() if typ == K._STT_OBJECT}
-    return found - {None}
-
-
-def sample_kernels():
-    """Every kernel instance libmlbp_sample.so holds, as kernel_inventory names them."""
-    return _kernels_of(_S().LIB_PATH)
-
-
-def test_sample_library_kernels_are_the_sources_kernels_and_each_has_a_case():
-    import test_gpu_sample as G
-    src = K.kernel_names(csrc=CSRC_SAMPLE)
-    assert src == {'sample_x64_kernel', 'sample_generic_kernel'}
-    compiled = sample_kernels()
-    assert {name for name, _ in compiled} == src
-    assert compiled == {('sample_x64_kernel', (True,)), ('sample_x64_kernel', (False,)), ('sample_generic_kernel', ())}
-    import test_gpu_sample_edges as E
-    for module in (G, E):                                       # every instance has a case in each of the two GPU modules
-        assert set(module.CASES) == compiled, set(module.CASES) ^ compiled
-        for kern, tests in module.CASES.items():
-            assert tests, kern
-            for t in tests:
-                assert callable(getattr(module, t, None)), (kern, t)
-
-
-def test_the_other_libraries_hold_no_sample_kernel_and_the_sources_stay_apart():
-    from macaronicusermodeling_amd import logz, mapdecode
-    assert not [k for k in K.all_compiled() if k[0].startswith('sample_')]
-    for other in (mapdecode, logz):
-        assert not [k for k in _kernels_of(other.LIB_PATH) if k[0].startswith('sample_')]
-    names = K.kernel_names(csrc=CSRC_SAMPLE)
-    assert all(n.startswith('sample_') for n in names)
-    for csrc in (K.CSRC, W.CSRC_MAP, os.path.join(ROOT, 'macaronicusermodeling_amd', 'csrc_logz')):
-        assert not names & K.kernel_names(csrc=csrc)
-    for f in os.listdir(CSRC_SAMPLE):
-        assert f.endswith(('.hip', '.h', '.o')), f
