@@ -51,6 +51,37 @@
  * A NaN, negative or +inf entry (a NaN is passed over by fmax, as in mlbp_map.h): that graph's states lie in [0, X), its score
  * and max-marginals are unspecified; the call returns and every other graph keeps its bits.  More than MLBP_CUTSET_MAX_CONFIGS
  * configurations: MLBP_EUNSUPPORTED.
+ *
+ * The listed mode: the max over LISTED cutset states (N > 0).  Beyond MLBP_CUTSET_MAX_CONFIGS configurations -- K5 and up at
+ * X = 64 -- the walk cannot visit every configuration; it can visit a caller's list of them, as mlbp_cutsetis_f64 does for the
+ * sum.  With N > 0 the call reads `configs`, N rows of n_cut states per graph (row i, entry q: the state of cutset[q]), and walks
+ * those rows in the place of the configurations c in [0, X^|C|).  V_i is the V_c above at configuration configs[g][i]: the
+ * conditioned forest is completed optimally for every entry, so the result is the best assignment among ALL assignments whose
+ * cutset state is listed -- a guarantee that needs no statistics: a list that holds the cutset state of an assignment x returns
+ * an assignment that scores no less than x, and the full list in index order returns the bits of the exact call.
+ *   Winner: the entry of largest V_i, compared as a (mantissa, exponent) pair; ties go to the lowest entry index i.  The tie
+ *   rule then continues as above: (2) roots take their lowest maximising state, (3) children walking `order` backwards.
+ *   assignment, score and entry are those of the winner.  The list may repeat a configuration.  n_cut == 0 is valid: there is
+ *   one empty configuration, configs is not read, and the call equals the exact call on a forest.
+ *   The bits of every output depend on the graph, the cutset and the list alone -- not on B, on the number of chunks, or on
+ *   which wave walked which entry.
+ *   Edge rules.  A state outside [0, X) anywhere in the graph's rows of configs: the graph is not computed -- assignment = -1,
+ *   score = NaN, entry = -1; every other graph keeps its bits.  A table index outside its array: as above, and entry = -1.
+ *   Every listed V_i zero: the all-zero rule above (the all-zero assignment, score = -inf), with entry = 0.
+ *   Limits.  0 <= N <= MLBP_EXACTMAP_MAX_LISTED (else MLBP_EINVAL); at most MLBP_EXACTMAP_MAX_CUT cutset variables, and no
+ *   bound on X^|C| (MLBP_EUNSUPPORTED beyond); N > 0 with max_marginals is MLBP_EUNSUPPORTED: a max over part of the state space
+ *   is no max-marginal.  The kernel pick is the rule below, unchanged.
+ *   Grid (B, C), C = mlbp_exactmap_chunks(B, N): workgroup (g, k) of the generic kernel walks entries k, k + C, ..., wave w of
+ *   workgroup (g, k) of the X = 64 kernel 4 k + w, 4 k + w + 4 C, ...; word 2 of a partial's header holds the entry index, and
+ *   exactmap_final_kernel re-solves the winning entry from its row of configs.
+ *   Workspace of a listed call, 8 times
+ *     B * parts * MLBP_EXACTMAP_PARTIAL_HEADER                                          parts = C (generic) or 4 C (X = 64)
+ *     + B * (2 n_vars + 1) * round_up(X, 2)                                             the final kernel's vectors
+ *     + B * C * (5 n_vars + 2) * round_up(X, 2)                                         when the generic kernel keeps its vectors there
+ *   mlbp_exactmap_workspace_bytes states the exact call alone; the compute entry checks this formula itself.
+ *   Plan.  mlbp_exactmap_check_plan keeps the exact call's bound on X^|C|; validate the plan of a listed call with
+ *   mlbp_cutsetis_check_plan (include/mlbp_cutsetis.h), whose bound is the listed one.
+ * With N == 0 every field of the listed mode is ignored (entry apart, see the struct) and the call is the exact call.
  */
 #ifndef MLBP_EXACTMAP_H
 #define MLBP_EXACTMAP_H
@@ -88,22 +119,28 @@ extern "C" {
 #define MLBP_EXACTMAP_KERNEL_GENERIC 2
 #define MLBP_EXACTMAP_PARTIAL_HEADER 4
 #define MLBP_EXACTMAP_DROP_BELOW 1000        /* a max-marginal below 2^-1000 of the graph's maximum reads -inf */
+#define MLBP_EXACTMAP_MAX_LISTED 65536       /* the most entries a list holds per graph */
+#define MLBP_EXACTMAP_MAX_CUT 16             /* the most cutset variables of a listed call */
 
 typedef struct mlbp_exactmap_args {
   int32_t B, X, n_vars, P, U;                /* graphs, states, variables, pairwise / unary factors */
   int32_t n_cut, n_free, n_items, n_consts, n_forest;      /* the plan's header, as mlbp_exactmap_check_plan saw it */
   int32_t n_pair_tables, n_unary_tables;
   int32_t plan_words;
+  int32_t N;                                 /* 0: the exact call; 1 .. MLBP_EXACTMAP_MAX_LISTED: entries listed per graph */
   const int32_t* plan;                       /* device [plan_words], validated by mlbp_exactmap_check_plan before upload */
   const double* pair_tables;                 /* device [n_pair_tables][X][X] row-major (NULL when P == 0) */
   const int32_t* pair_tab;                   /* device [B][P] table of graph g's pairwise factor p */
   const double* unary_tables;                /* device [n_unary_tables][X] (NULL when U == 0) */
   const int32_t* unary_tab;                  /* device [B][U] */
+  const int32_t* configs;                    /* listed call: device [B][N][n_cut], the state of cutset[q]; NULL when N == 0 or n_cut == 0 */
   double* workspace;                         /* device, workspace_bytes >= mlbp_exactmap_workspace_bytes(...) */
   int64_t workspace_bytes;
   int32_t* assignment;                       /* device [B][n_vars] */
   double* score;                             /* device [B] */
   double* max_marginals;                     /* optional device [B][n_vars][X] */
+  int32_t* entry;                            /* optional device [B]: the index of the winning list entry (listed call) or the
+                                                winning configuration index (exact call); -1 for a graph that is not computed */
 } mlbp_exactmap_args;
 
 /* Table indices are device data and are not checked on the host: see the edge rules above. */

@@ -793,6 +793,75 @@ class FactorGraphBatch:
         K.check(K.lib.mlbp_exactmap_f64(C.byref(a), _stream_ptr(self.device)))
         return (assignment, score) if max_marginals is None else (assignment, score, max_marginals)
 
+    # ---- the best assignment among listed cutset states (the listed mode of include/mlbp_exactmap.h) ----------
+    def cutset_map(self, configs, cutset=None, entry=False):
+        """The best assignment among ALL assignments whose cutset state is LISTED -- for the graphs whose cutset has more joint
+        states than exact_map() walks (more than 65536: K5 and up at X = 64).  configs: contiguous int32 [B][N][n_cut] device
+        tensor, configs[b][i][q] the state of cutset variable q (cutset order) in entry i; 1 <= N <= 65536.  For every entry
+        the conditioned forest is completed optimally, as exact_map() does for every configuration; the entry of the largest
+        value wins, ties to the lowest entry index, and then exact_map()'s tie rule.  Returns (assignment int32 [B][n_vars],
+        score float64 [B]) device tensors, and with entry=True also entry int32 [B], the index of the winning entry.  A list
+        that holds the cutset state of an assignment x returns a score no lower than x's; the full list in index order returns
+        exact_map()'s bits.  The list may repeat a configuration.  A graph with a state outside [0, X) in its list gets
+        assignment -1, score NaN and entry -1.  The bits depend on the graph, the cutset and the list alone.  cutset: as in
+        exact_inference; at most 16 variables, no limit on X^len(cutset).  On a tree configs is [B][N][0].  self.msgs is
+        neither read nor written."""
+        from . import cutsetis as KP, exactmap as K
+        topo = self.topo
+        pl, a = self._cutset_args(KP, K.ExactMapArgs, cutset, 'cutset_map needs float64 pairwise tables')       # the listed check of the plan
+        if not torch.is_tensor(configs) or configs.dtype != torch.int32 or configs.device != self.device or configs.dim() != 3 \
+                or configs.shape[0] != self.B or configs.shape[2] != pl.n_cut or not configs.is_contiguous():
+            raise ValueError('configs must be a contiguous int32 device tensor [B][N][n_cut]')
+        N = int(configs.shape[1])
+        if not 1 <= N <= K.MAX_LISTED:
+            raise ValueError('N must be in [1, %d]' % K.MAX_LISTED)
+        a.N = N
+        if pl.n_cut:
+            a.configs = configs.data_ptr()
+        assignment = torch.empty(self.B, topo.n_vars, dtype=torch.int32, device=self.device)
+        score = torch.empty(self.B, dtype=torch.float64, device=self.device)
+        a.assignment, a.score = assignment.data_ptr(), score.data_ptr()
+        won = None
+        if entry:
+            won = torch.empty(self.B, dtype=torch.int32, device=self.device)
+            a.entry = won.data_ptr()
+        need = K.listed_workspace_bytes(self.B, self.X, topo.n_vars, topo.P, topo.U, pl.n_forest, N)
+        work = torch.empty(need // 8, dtype=torch.float64, device=self.device)
+        a.workspace, a.workspace_bytes = work.data_ptr(), need
+        K.check(K.lib.mlbp_exactmap_f64(C.byref(a), _stream_ptr(self.device)))
+        return (assignment, score, won) if entry else (assignment, score)
+
+    def _search_list(self, roots, n_samples, seed, uniforms, cutset):
+        """The list of search_map(): (configs int32 [B][N][n_cut], map_sweep's assignment, its score)."""
+        from . import cutset as K0, cutsetis as KP
+        N = int(n_samples)
+        if not 1 <= N <= KP.MAX_LISTED:
+            raise ValueError('n_samples must be in [1, %d]' % KP.MAX_LISTED)
+        pl, _ = self._cutset_args(KP, KP.CutsetisArgs, cutset, 'search_map needs float64 pairwise tables')
+        cut = [int(v) for v in pl.words[K0.PLAN_HEADER:K0.PLAN_HEADER + pl.n_cut]]
+        x_bp, score_bp = self.map_sweep(roots, init=True)
+        configs = torch.empty(self.B, N, pl.n_cut, dtype=torch.int32, device=self.device)
+        if cut:
+            configs[:, 0] = x_bp.index_select(1, torch.tensor(cut, dtype=torch.int64, device=self.device))
+            if N > 1:
+                self.sweep(roots, init=True)                    # after map_sweep: both write self.msgs
+                drawn, _ = self.cutset_draw(N - 1, seed=None if uniforms is not None else seed, uniforms=uniforms, cutset=cutset)
+                configs[:, 1:] = drawn
+        return configs, x_bp, score_bp
+
+    def search_map(self, roots, n_samples=256, seed=0, uniforms=None, cutset=None):
+        """Search decoding beyond exact_map()'s limit: cutset_map() over a list made of the max-product answer and of draws
+        from the sum-product messages.  Entry 0 of the list is the cutset state of map_sweep(roots)'s assignment; entries 1 to
+        n_samples - 1 are cutset_draw(n_samples - 1, ...) on the messages of sweep(roots, init=True), which runs AFTER
+        map_sweep -- both write self.msgs.  Returns (assignment int32 [B][n_vars], score float64 [B], score_bp float64 [B])
+        device tensors, score_bp the score of map_sweep's assignment: score >= score_bp up to the rounding of the two sums of
+        logarithms, because the max-product assignment is among those the list admits.  n_samples = 1 is the optimal
+        completion of the max-product cutset state alone.  seed / uniforms ([B][n_samples - 1][n_cut]) as cutset_draw takes
+        them; uniforms replaces seed.  cutset: as in cutset_map."""
+        configs, _, score_bp = self._search_list(roots, n_samples, seed, uniforms, cutset)
+        assignment, score = self.cutset_map(configs, cutset=cutset)
+        return assignment, score, score_bp
+
     # ---- the M best whole assignments, ranked (include/mlbp_exactmbest.h) ------------------------------------
     def exact_mbest(self, m, cutset=None):
         """The TRUE `m` jointly most probable assignments of every graph, best first, by cutset conditioning -- exact_map()

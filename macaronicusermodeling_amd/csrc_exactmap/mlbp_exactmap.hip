@@ -13,6 +13,9 @@
 //                                caller's workspace.
 //   exactmap_final_kernel        one workgroup per graph: the best partial (ties: the lowest c), that configuration solved once
 //                                more with the tables streamed, the states by back-pointers, the logarithms.
+// A LISTED call (N > 0, never with MM) runs the same three kernels over the caller's list of cutset states: a walker's c is
+// then the index of a list entry and the states come from the entry's row of configs -- the generic kernel in a loop of its
+// own (ListedStates), the X = 64 kernel likewise (X64Packed), the final kernel re-solving the winning entry from its row.
 // Without MM a walk is the pass from the leaves to the roots alone.  Every scalar a workgroup or wave branches on comes out of a
 // reduction and has the same bits in every thread of it.  No sum is formed: a result does not depend on the launch at all.
 // No device-side mutable globals: everything comes through ExactDev.
@@ -36,6 +39,34 @@ struct ExactDev : WalkDev {                  // partials: [B][parts][per], per =
   double* fvec;                              // the final kernel's vectors: [B][2 n_vars + 1][round_up(X, 2)]
   int32_t* assignment; double* score; double* max_marginals;
   int32_t per;
+  const int32_t* configs;                    // a listed call with cutset variables: [B][n_configs][n_cut]; else NULL
+  int32_t* entry;                            // optional [B]
+};
+
+// A listed call (the header's listed mode): n_configs is N, a walker's c the index of a list entry, and the entry's states are
+// its row of configs (ListedStates) where the exact call decodes c.  Without cutset variables configs is NULL and the N entries
+// are the one empty configuration: the exact loop walks them as they are.  A walker that meets a row with a state outside
+// [0, X) stops there and marks its partial; the final kernel then refuses the graph.
+constexpr int BAD_ENTRY = -2;                // word 2 of such a partial
+
+__device__ __forceinline__ const_i32p listed_row(const ExactDev& d, int g, int i) {
+  return as_const(d.configs) + ((size_t)g * d.n_configs + i) * d.n_cut;
+}
+
+// the row's address is the same in every thread of the walker, and so is the answer
+__device__ __forceinline__ bool row_in_range(const_i32p row, int n_cut, int X) {
+  bool ok = true;
+  for (int q = 0; q < n_cut; ++q) ok &= (unsigned)row[q] < (unsigned)X;
+  return ok;
+}
+
+// The states of a listed entry in the X = 64 walk: lane q of `packed` holds the state of cut position q -- the entry's row in
+// one coalesced load -- and a position's state is one v_readlane, a scalar as X64Code's.  The listed loop is a call site of its
+// own: with the exact loop's source as it was, exact_map() keeps its time (one call site for both cost it 1 to 4 %).  With
+// ListedStates (scalar loads of the row) the second call site cost the instance a wave of occupancy: 106 scalar registers.
+struct X64Packed {
+  int packed;
+  __device__ __forceinline__ int operator()(int q) const { return __builtin_amdgcn_readlane(packed, q); }
 };
 
 // The best configuration so far: V = m * 2^e at configuration c; c < 0: nothing yet; m = 0: V is zero (or no number).
@@ -83,6 +114,20 @@ __global__ __launch_bounds__(WG) void exactmap_generic_kernel(ExactDev d) {
 
   Best best = {0.0, EMPTY, -1};
   int ref = EMPTY;                                             // the largest exponent of a positive V_c so far
+  if constexpr (!MM) {
+    if (d.configs) {                                           // a listed call: its own loop, the exact one below is as it was
+      for (int i = k; i < d.n_configs; i += d.chunks) {
+        const const_i32p row = listed_row(d, g, i);
+        if (!row_in_range(row, d.n_cut, X)) {
+          best.c = BAD_ENTRY;                                  // the graph is refused: nothing more to walk
+          break;
+        }
+        offer(best, generic_up<MaxAlg>(G, ListedStates{row}, nullptr), i);
+      }
+      if (t == 0) write_partial_header(d.partials + ((size_t)g * d.parts + k) * d.per, best, ref);
+      return;
+    }
+  }
   for (int c = k; c < d.n_configs; c += d.chunks) {
     const Scaled z = generic_up<MaxAlg>(G, c, MM ? G.up : nullptr);
     offer(best, z, c);
@@ -130,6 +175,20 @@ __global__ __launch_bounds__(WG) void exactmap_x64_kernel(ExactDev d) {
 
   Best best = {0.0, EMPTY, -1};
   int ref = EMPTY;                                             // the largest exponent of a positive V_c so far
+  if constexpr (!MM) {
+    if (d.configs) {                                           // a listed call: its own loop, the exact one below is as it was
+      for (int i = 4 * k + wave; i < d.n_configs; i += 4 * d.chunks) {
+        const int packed = lane < d.n_cut ? listed_row(d, g, i)[lane] : 0;
+        if (__any((unsigned)packed >= 64u)) {
+          best.c = BAD_ENTRY;                                  // the graph is refused: nothing more to walk
+          break;
+        }
+        offer(best, x64_up<MaxAlg, false>(W, X64Packed{packed}), i);
+      }
+      if (lane == 0) write_partial_header(d.partials + ((size_t)g * d.parts + 4 * k + wave) * d.per, best, ref);
+      return;
+    }
+  }
   for (int c = 4 * k + wave; c < d.n_configs; c += 4 * d.chunks) {
     const Scaled z = x64_up<MaxAlg, MM>(W, c);
     offer(best, z, c);
@@ -166,13 +225,23 @@ __global__ __launch_bounds__(WG) void exactmap_final_kernel(ExactDev d) {
   if (!tables_in_range(d.pair_tab, d.P, d.n_pair_tables, d.unary_tab, d.U, d.n_unary_tables, g)) {
     for (int v = t; v < n_vars; v += WG) xs[v] = -1;
     if (t == 0) d.score[g] = __builtin_nan("");
+    if (t == 0 && d.entry) d.entry[g] = -1;
     return;
   }
   const double* ws = d.partials + (size_t)g * d.parts * d.per;
 
-  // the best partial: the larger V, then the lower configuration index
+  // the best partial: the larger V, then the lower configuration index (of a listed call: the lower entry index)
   Best best = {0.0, EMPTY, -1};
   int ref = EMPTY;
+  bool bad = false;                                            // a listed call: a walker met a state outside [0, X)
+  if (d.configs)
+    for (int k = 0; k < d.parts; ++k) bad |= (int)ws[(size_t)k * d.per + 2] == BAD_ENTRY;
+  if (bad) {                                                   // the same in every thread: the graph is not computed
+    for (int v = t; v < n_vars; v += WG) xs[v] = -1;
+    if (t == 0) d.score[g] = __builtin_nan("");
+    if (t == 0 && d.entry) d.entry[g] = -1;
+    return;
+  }
   for (int k = 0; k < d.parts; ++k) {
     const double* w = ws + (size_t)k * d.per;
     const double m = w[0];
@@ -202,7 +271,8 @@ __global__ __launch_bounds__(WG) void exactmap_final_kernel(ExactDev d) {
   const bool positive = best.m > 0.0;                          // else every assignment has potential zero: all of them tie
   if (positive) {
     generic_setup(G);
-    generic_up<MaxAlg>(G, best.c, nullptr);
+    if (d.configs) generic_up<MaxAlg>(G, ListedStates{listed_row(d, g, best.c)}, nullptr);
+    else generic_up<MaxAlg>(G, best.c, nullptr);
     if (t < d.n_cut) xs[G.pl.cutset[t]] = G.st[t];
   } else {
     for (int v = t; v < n_vars; v += WG) xs[v] = 0;
@@ -255,11 +325,19 @@ __global__ __launch_bounds__(WG) void exactmap_final_kernel(ExactDev d) {
   for (int u = lane; u < d.U; u += 64) sc += log(d.unary_tables[(size_t)G.utab[u] * X + xs[G.pl.uvar[u]]]);
   sc = wave_sum(sc);
   if (lane == 0) d.score[g] = sc;
+  if (lane == 0 && d.entry) d.entry[g] = best.c;
 }
 
 // ---- host ----------------------------------------------------------------------------------------
 thread_local int g_last_kernel = MLBP_EXACTMAP_KERNEL_NONE;
 static_assert(MLBP_EXACTMAP_KERNEL_X64 == WALK_X64 && MLBP_EXACTMAP_KERNEL_GENERIC == WALK_GENERIC, "the shared host core numbers the kernels");
+static_assert(MLBP_EXACTMAP_MAX_CUT == MAX_LISTED_CUT, "the header states the shared walk's bound");
+
+// The header's workspace formula, exact or listed: `per` doubles in a partial, `chunks` = C of the grid.
+int64_t workspace_of(int which, int64_t B, int64_t chunks, int64_t per, int64_t n_vars, int64_t P, int64_t U, int64_t X) {
+  const int64_t Xp = (X + 1) / 2 * 2;
+  return (B * chunks * chunk_doubles(which, per, n_vars, P, U, X) + B * (2 * n_vars + 1) * Xp) * 8;
+}
 
 }  // namespace
 
@@ -287,29 +365,38 @@ int64_t mlbp_exactmap_workspace_bytes(int32_t B, int32_t X, int32_t n_vars, int3
   if (n_configs < 0) return too_many_configs(X, n_cut);
   const int chunks = mlbp_exactmap_chunks(B, (int32_t)n_configs);
   if (chunks < 0) return chunks;
-  const int64_t Xp = (X + 1) / 2 * 2;
-  const int64_t per = PART + (max_marginals ? (int64_t)n_vars * X : 0);
-  return ((int64_t)B * chunks * chunk_doubles(which, per, n_vars, P, U, X) + (int64_t)B * (2 * (int64_t)n_vars + 1) * Xp) * 8;
+  return workspace_of(which, B, chunks, PART + (max_marginals ? (int64_t)n_vars * X : 0), n_vars, P, U, X);
 }
 
 int mlbp_exactmap_check_plan(const int32_t* plan, int32_t n_words, int32_t X) { return check_packed_plan(plan, n_words, X); }
 
 int mlbp_exactmap_f64(const mlbp_exactmap_args* a, void* stream) {
   g_last_kernel = MLBP_EXACTMAP_KERNEL_NONE;
-  int64_t n_configs = 0;
+  const bool listed = a && a->N > 0;                           // the header's listed mode: the walk's entries are the list's
+  int64_t n_configs = listed ? a->N : 0;
   const int which = check_walk_args(a, mlbp_exactmap_pick_kernel, [](const mlbp_exactmap_args* a) {
-    return !a->assignment || !a->score ? fail(MLBP_EINVAL, "assignment or score is NULL") : (int)MLBP_OK;
-  }, &n_configs);
+    if (!a->assignment || !a->score) return fail(MLBP_EINVAL, "assignment or score is NULL");
+    if (a->N < 0 || a->N > MLBP_EXACTMAP_MAX_LISTED)
+      return fail(MLBP_EINVAL, "N = %d: a list holds 1 to %d configurations (0: the exact call)", a->N, MLBP_EXACTMAP_MAX_LISTED);
+    if (a->N > 0 && a->n_cut > 0 && !a->configs) return fail(MLBP_EINVAL, "configs is NULL in a listed call with cutset variables");
+    if (a->N > 0 && a->max_marginals)
+      return fail(MLBP_EUNSUPPORTED, "max_marginals with N = %d: the max over a list is no max-marginal", a->N);
+    return (int)MLBP_OK;
+  }, &n_configs, listed);
   if (which < 0) return which;
   const int chunks = mlbp_exactmap_chunks(a->B, (int32_t)n_configs);
   if (chunks < 0) return chunks;
   const bool mm = a->max_marginals != nullptr;
-  if (int e = check_walk_workspace(a, mlbp_exactmap_workspace_bytes(a->B, a->X, a->n_vars, a->P, a->U, a->n_forest, a->n_cut, mm))) return e;
+  const int64_t need = listed ? workspace_of(which, a->B, chunks, PART, a->n_vars, a->P, a->U, a->X)
+                              : mlbp_exactmap_workspace_bytes(a->B, a->X, a->n_vars, a->P, a->U, a->n_forest, a->n_cut, mm);
+  if (int e = check_walk_workspace(a, need)) return e;
   if (int e = check_device("libmlbp_exactmap.so")) return e;
   const int64_t Xp = (a->X + 1) / 2 * 2;
   ExactDev d;
   fill_walk_dev(d, a, n_configs, chunks, which);
   d.assignment = a->assignment; d.score = a->score; d.max_marginals = a->max_marginals;
+  d.configs = listed && a->n_cut > 0 ? a->configs : nullptr;
+  d.entry = a->entry;
   d.per = PART + (mm ? a->n_vars * a->X : 0);
   d.fvec = d.partials + (int64_t)a->B * d.parts * d.per;
   hipStream_t st = (hipStream_t)stream;

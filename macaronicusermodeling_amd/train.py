@@ -28,6 +28,7 @@ from .topology import GraphTopology
 
 # params and prediction files carry the adapt mode in their name (train_mp.py:654-656, 688-690)
 ADAPT_EXT = {'user': '.user_adapt', 'experience': '.exp_adapt', None: ''}
+SEARCH_ROSE = 1e-9              # search_decode: a score counts as risen above decode()'s beyond this, relative to max(1, |score|)
 
 
 class UserGraphTrainer:
@@ -402,6 +403,21 @@ class UserGraphTrainer:
         joint = fb.exact_inference(labels=x)[2]
         return (x.cpu().numpy().astype(np.int64), score.cpu().numpy(), margin.cpu().numpy(), agrees.cpu().numpy(),
                 shortfall.cpu().numpy(), joint.cpu().numpy())
+
+    def search_decode(self, n_samples=256, seed=0, with_list=False):
+        """The sentence shapes exact_decode() refuses, and the others beside it: the best set of guesses among those whose
+        cutset state is on a list of n_samples -- decode()'s own cutset state first, then draws from the sum-product messages
+        (FactorGraphBatch.search_map over the predict() schedule).  Host (assignment int64 [B][n_vars] word indices in
+        var_ids order, score float64 [B] -- its log-potential --, score_bp float64 [B] -- decode()'s score, never above score
+        but by the rounding of the two sums --, changed bool [B] -- the set differs from decode()'s); with_list also configs
+        int32 [B][n_samples][n_cut], the list that was walked.  Up to 16 cutset variables: nothing is refused for its
+        number of configurations."""
+        fb = self.batch
+        self.build_potentials()
+        configs, bp_x, bp_score = fb._search_list(self.roots[:self.n_sweeps_run], n_samples, seed, None, None)
+        x, score = fb.cutset_map(configs)
+        out = (x.cpu().numpy().astype(np.int64), score.cpu().numpy(), bp_score.cpu().numpy(), (bp_x != x).any(dim=1).cpu().numpy())
+        return out + (configs.cpu().numpy(),) if with_list else out
 
     def exact_nbest(self, m):
         """The `m` TRULY most probable sets of guesses of every instance under the current thetas, ranked
@@ -1244,6 +1260,30 @@ class TiDirTrainer:
         mdist.all_reduce_max_(worst)
         tot = tot.cpu().numpy()
         return (guesses, tuple(int(v) for v in tot[:4]), (int(tot[4]), int(tot[5]), float(tot[6]), float(worst[0])), skipped)
+
+    # ---- search decoding beyond the exact limit (the listed mode of include/mlbp_exactmap.h) -----------------
+    def search_decode(self, n_samples=256, seed=0):
+        """-> (guesses, counts).  guesses[i], for instance i of this rank's shard in file order: (predicted positions, [en
+        words], score, score - score_bp) as UserGraphTrainer.search_decode gives them -- the best set of guesses among those
+        whose cutset state is listed, its log-potential and its gain over decode()'s set; an instance without a predicted
+        word builds no graph and gives ((), [], 0.0, 0.0).  No shape is skipped for its number of configurations (up to 16
+        cutset variables): the sentences exact_decode() lists as skipped are decoded here, the others too, so the two
+        reports can be laid side by side.  The i-th sentence shape in self.trainers order draws with seed `seed + i`.
+        counts = (sentences decoded, sentences whose score rose above decode()'s by more than SEARCH_ROSE relative to
+        max(1, |score|) -- the rounding of the two sums of logarithms --, sentences whose words changed) over ALL ranks'
+        instances, reduced once."""
+        n = self._shard[1] - self._shard[0]
+        guesses = [((), [], 0.0, 0.0)] * n
+        counts = np.zeros(3, dtype=np.int64)
+        for i, (key, tr) in enumerate(self.trainers.items()):
+            x, score, score_bp, changed = tr.search_decode(n_samples=n_samples, seed=int(seed) + i)
+            rose = score - score_bp > SEARCH_ROSE * np.maximum(1.0, np.abs(score))
+            counts += np.array([len(score), int(rose.sum()), int(changed.sum())], dtype=np.int64)
+            for b, row in enumerate(self.buckets[key]['rows']):
+                guesses[row['index']] = (tuple(key[1]), [self.en[w] for w in x[b]], float(score[b]), float(score[b] - score_bp[b]))
+        tot = torch.tensor([float(v) for v in counts], dtype=torch.float64, device=self.device)
+        mdist.all_reduce_sum_(tot)
+        return guesses, tuple(int(v) for v in tot.cpu().numpy())
 
     # ---- the ranked list of whole sets of guesses (include/mlbp_exactmbest.h) ---------------------------
     def exact_nbest(self, m):
