@@ -30,6 +30,58 @@ def _stream_ptr(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+# ---- the argument checks every batch call shares (no device needed: tests/test_batch_args_cpu.py) --------------------------
+_DTYPE_WORD = {torch.float64: 'float64', torch.int32: 'int32'}
+
+
+def _device_tensor(t, shape, dtype, device, what, shape_text=None, message=None):
+    """t.data_ptr() of a caller's tensor that a kernel is about to read or write, after checking that it IS a tensor, of
+    `dtype`, on `device`, contiguous, and of `shape`: a tuple to be met exactly -- None admits any size on that axis -- or an
+    int, the least number of elements in any shape.  Anything else raises ValueError('<what> must be a contiguous <dtype>
+    device tensor <shape_text>'), or `message` where a call words it differently."""
+    ok = torch.is_tensor(t) and t.dtype == dtype and t.device == device and t.is_contiguous()
+    if ok and isinstance(shape, int):
+        ok = t.numel() >= shape
+    elif ok:
+        ok = t.dim() == len(shape) and all(s is None or s == d for s, d in zip(shape, t.shape))
+    if not ok:
+        raise ValueError(message or '%s must be a contiguous %s device tensor %s' % (what, _DTYPE_WORD[dtype], shape_text))
+    return t.data_ptr()
+
+
+def _rows_i32(rows, shape, device, what):
+    """rows (`shape` integers: a tensor, an array or nested lists) as a contiguous int32 tensor on `device`; one that already
+    is comes back as it is."""
+    if torch.is_tensor(rows) and rows.dtype == torch.int32 and rows.device == device and rows.is_contiguous():
+        out = rows
+    else:
+        host = rows.cpu().numpy() if torch.is_tensor(rows) else np.asarray(rows)
+        out = torch.from_numpy(np.ascontiguousarray(host.astype(np.int64).astype(np.int32))).to(device)
+    if tuple(out.shape) != tuple(shape):
+        raise ValueError('%s must be [B][n_vars]' % what)
+    return out
+
+
+def _listed_count(n, K, word='n_samples'):
+    """int(n), the entries per graph of a list handed to binding K: within [1, K.MAX_LISTED]."""
+    n = int(n)
+    if not 1 <= n <= K.MAX_LISTED:
+        raise ValueError('%s must be in [1, %d]' % (word, K.MAX_LISTED))
+    return n
+
+
+def _exactly_one(seed, uniforms):
+    if (seed is None) == (uniforms is None):
+        raise ValueError('give exactly one of seed and uniforms')
+
+
+def _fill_program(a, prog):
+    """The compiled root sequence and the in-slots of a _sidelib.Program into the args of a program-taking library."""
+    a.n_ops, a.n_srcs, a.n_sweeps = prog.n_ops, prog.n_srcs, prog.n_sweeps
+    a.ops, a.srcs, a.sweeps = prog.ops.data_ptr(), prog.srcs.data_ptr(), prog.sweeps.data_ptr()
+    a.in_off, a.in_slots = prog.in_off.data_ptr(), prog.in_slots.data_ptr()
+
+
 class Program:
     """Validated device-resident op list for one root sequence (mlbp_program_create)."""
 
@@ -262,6 +314,51 @@ class FactorGraphBatch:
         _ffi.check(_ffi.lib.mlbp_sweep_f64(prog.handle, C.byref(a), _stream_ptr(self.device)))
         return prog
 
+    # ---- what the calls into the side libraries share ---------------------------------------------------------
+    def _tensor(self, t, shape, what, shape_text=None, dtype=torch.float64, message=None):
+        return _device_tensor(t, shape, dtype, self.device, what, shape_text, message)
+
+    def _rows_i32(self, rows, what):
+        return _rows_i32(rows, (self.B, self.topo.n_vars), self.device, what)
+
+    def _fill_tables(self, a, pair=True, unary=True):
+        """The table fields of a side library's args; the tables must have been set."""
+        if pair and self.topo.P:
+            if self.pair_tables is None:
+                raise RuntimeError('set_pair_tables() first')
+            a.n_pair_tables = self.pair_tables.shape[0]
+            a.pair_tables, a.pair_tab = self.pair_tables.data_ptr(), self.pair_tab.data_ptr()
+        if unary and self.topo.U:
+            if self.unary_tables is None:
+                raise RuntimeError('set_unary_tables() first')
+            a.n_unary_tables = self.unary_tables.shape[0]
+            a.unary_tables, a.unary_tab = self.unary_tables.data_ptr(), self.unary_tab.data_ptr()
+
+    def _uniforms(self, seed, uniforms, shape, shape_text):
+        """The uniforms of a drawing call, float64 `shape`: the caller's, checked, or torch.rand from `seed`."""
+        _exactly_one(seed, uniforms)
+        if uniforms is None:
+            gen = torch.Generator(self.device).manual_seed(int(seed))
+            return torch.rand(shape, dtype=torch.float64, device=self.device, generator=gen)
+        self._tensor(uniforms, shape, 'uniforms', shape_text)
+        return uniforms
+
+    def _workspace(self, a, need):
+        """Allocates the `need` bytes a library asked for and states them in a; the caller holds the tensor until its launch
+        is enqueued."""
+        work = torch.empty(need // 8, dtype=torch.float64, device=self.device)
+        a.workspace, a.workspace_bytes = work.data_ptr(), need
+        return work
+
+    def _cutset_indices(self, cutset):
+        """A cutset given as variable ids as variable indices (None stays None: the library's own choice)."""
+        if cutset is None:
+            return None
+        unknown = [v for v in cutset if v not in self.topo.var_index]
+        if unknown:
+            raise ValueError('cutset names unknown variable ids %r' % (unknown,))
+        return [self.topo.var_index[v] for v in cutset]
+
     # ---- max-product: the jointly most probable assignment (include/mlbp_map.h) ------------------
     def map_sweep(self, roots, init=True, max_marginals=None, keep_messages=True):
         """Runs len(roots) MAX-product sweeps -- sweep()'s schedule with max_j in place of sum_j in every pairwise update --
@@ -279,28 +376,18 @@ class FactorGraphBatch:
         prog = M.program(topo, roots, self.device)
         a = M.MapArgs()
         a.B, a.X, a.n_msgs, a.P, a.U, a.n_vars = self.B, self.X, topo.n_msgs, topo.P, topo.U, topo.n_vars
-        a.n_ops, a.n_srcs, a.n_sweeps = prog.n_ops, prog.n_srcs, prog.n_sweeps
-        a.ops, a.srcs, a.sweeps = prog.ops.data_ptr(), prog.srcs.data_ptr(), prog.sweeps.data_ptr()
+        _fill_program(a, prog)
+        self._fill_tables(a)
         if topo.P:
-            if self.pair_tables is None:
-                raise RuntimeError('set_pair_tables() first')
-            a.n_pair_tables = self.pair_tables.shape[0]
-            a.pair_tables, a.pair_tab = self.pair_tables.data_ptr(), self.pair_tab.data_ptr()
             a.pair_axis_var = prog.pair_axis_var.data_ptr()
         if topo.U:
-            if self.unary_tables is None:
-                raise RuntimeError('set_unary_tables() first')
-            a.n_unary_tables = self.unary_tables.shape[0]
-            a.unary_tables, a.unary_tab = self.unary_tables.data_ptr(), self.unary_tab.data_ptr()
             a.unary_var = prog.unary_var.data_ptr()
         a.msgs = self.msgs.data_ptr()
         a.init_messages, a.normalize_messages = (1 if init else 0), (1 if self.normalize_messages else 0)
         a.write_messages = 1 if keep_messages else 0
-        a.in_off, a.in_slots = prog.in_off.data_ptr(), prog.in_slots.data_ptr()
         if max_marginals is not None:
-            if tuple(max_marginals.shape) != (self.B, topo.n_vars, self.X) or max_marginals.dtype != torch.float64:
-                raise ValueError('max_marginals must be float64 [B][n_vars][X]')
-            a.max_marginals = max_marginals.data_ptr()
+            a.max_marginals = self._tensor(max_marginals, (self.B, topo.n_vars, self.X), 'max_marginals',
+                                           message='max_marginals must be float64 [B][n_vars][X]')
         assignment = torch.empty(self.B, topo.n_vars, dtype=torch.int32, device=self.device)
         score = torch.empty(self.B, dtype=torch.float64, device=self.device)
         a.assignment, a.score = assignment.data_ptr(), score.data_ptr()
@@ -327,19 +414,12 @@ class FactorGraphBatch:
         ro = L.readout(topo, self.device)
         a = L.LogzArgs()
         a.B, a.X, a.n_msgs, a.P, a.U, a.n_vars = self.B, self.X, topo.n_msgs, topo.P, topo.U, topo.n_vars
+        self._fill_tables(a)
         if topo.P:
-            if self.pair_tables is None:
-                raise RuntimeError('set_pair_tables() first')
-            a.n_pair_tables = self.pair_tables.shape[0]
-            a.pair_tables, a.pair_tab = self.pair_tables.data_ptr(), self.pair_tab.data_ptr()
             a.pair_axis_var, a.pair_in_slot = ro.pair_axis_var.data_ptr(), ro.pair_in_slot.data_ptr()
             if getattr(self, 'pair_tables_shared', False):
                 a.flags |= L.SHARED_PAIR_TABLES
         if topo.U:
-            if self.unary_tables is None:
-                raise RuntimeError('set_unary_tables() first')
-            a.n_unary_tables = self.unary_tables.shape[0]
-            a.unary_tables, a.unary_tab = self.unary_tables.data_ptr(), self.unary_tab.data_ptr()
             a.unary_var, a.unary_in_slot = ro.unary_var.data_ptr(), ro.unary_in_slot.data_ptr()
         a.msgs = self.msgs.data_ptr()
         a.in_off, a.in_slots = ro.in_off.data_ptr(), ro.in_slots.data_ptr()
@@ -347,19 +427,15 @@ class FactorGraphBatch:
         a.log_z = log_z.data_ptr()
         joint = lab = None
         if labels is not None:
-            lab = self._labels_i32(labels)
+            lab = self._rows_i32(labels, 'labels')
             joint = torch.empty(self.B, dtype=torch.float64, device=self.device)
             a.labels, a.joint_logp = lab.data_ptr(), joint.data_ptr()
             if score is not None:
-                if score.dtype != torch.float64 or score.numel() < self.B or score.device != self.device:
-                    raise ValueError('score must be a float64 device tensor of B elements')
-                a.score = score.data_ptr()
+                a.score = self._tensor(score, self.B, 'score', message='score must be a float64 device tensor of B elements')
         elif score is not None:
             raise ValueError('score needs labels')
         if sum_out is not None:
-            if sum_out.dtype != torch.float64 or sum_out.numel() < 2 or sum_out.device != self.device:
-                raise ValueError('sum_out must be a float64 device tensor of two elements')
-            a.sum_out = sum_out.data_ptr()
+            a.sum_out = self._tensor(sum_out, 2, 'sum_out', message='sum_out must be a float64 device tensor of two elements')
         L.check(L.lib.mlbp_logz_f64(C.byref(a), _stream_ptr(self.device)))
         return log_z if labels is None else (log_z, joint)
 
@@ -379,56 +455,28 @@ class FactorGraphBatch:
             raise NotImplementedError('sampling has no top-100 approximate form')
         if self.pair_tables is not None and self.pair_tables.dtype != torch.float64:
             raise NotImplementedError('sampling needs float64 pairwise tables')
-        if (seed is None) == (uniforms is None):
-            raise ValueError('give exactly one of seed and uniforms')
+        _exactly_one(seed, uniforms)
         topo, S = self.topo, int(n_samples)
         if S <= 0:
             raise ValueError('n_samples must be positive')
-        if uniforms is None:
-            gen = torch.Generator(self.device).manual_seed(int(seed))
-            uniforms = torch.rand((S, self.B, topo.n_vars), dtype=torch.float64, device=self.device, generator=gen)
-        elif (not torch.is_tensor(uniforms) or uniforms.dtype != torch.float64 or uniforms.device != self.device
-              or tuple(uniforms.shape) != (S, self.B, topo.n_vars) or not uniforms.is_contiguous()):
-            raise ValueError('uniforms must be a contiguous float64 device tensor [n_samples][B][n_vars]')
+        uniforms = self._uniforms(seed, uniforms, (S, self.B, topo.n_vars), '[n_samples][B][n_vars]')
         prog = S_.program(topo, roots, self.device)
         a = S_.SampleArgs()
-        a.B, a.X, a.n_msgs, a.P, a.U, a.n_vars = self.B, self.X, topo.n_msgs, topo.P, topo.U, topo.n_vars
-        a.n_ops, a.n_srcs, a.n_sweeps, a.S = prog.n_ops, prog.n_srcs, prog.n_sweeps, S
-        a.ops, a.srcs, a.sweeps = prog.ops.data_ptr(), prog.srcs.data_ptr(), prog.sweeps.data_ptr()
-        if topo.P:
-            if self.pair_tables is None:
-                raise RuntimeError('set_pair_tables() first')
-            a.n_pair_tables = self.pair_tables.shape[0]
-            a.pair_tables, a.pair_tab = self.pair_tables.data_ptr(), self.pair_tab.data_ptr()
-        if topo.U:
-            if self.unary_tables is None:
-                raise RuntimeError('set_unary_tables() first')
-            a.n_unary_tables = self.unary_tables.shape[0]
-            a.unary_tables, a.unary_tab = self.unary_tables.data_ptr(), self.unary_tab.data_ptr()
+        a.B, a.X, a.n_msgs, a.P, a.U, a.n_vars, a.S = self.B, self.X, topo.n_msgs, topo.P, topo.U, topo.n_vars, S
+        _fill_program(a, prog)
+        self._fill_tables(a)
         a.normalize_messages = 1 if self.normalize_messages else 0
-        a.in_off, a.in_slots, a.slot_var = prog.in_off.data_ptr(), prog.in_slots.data_ptr(), prog.slot_var.data_ptr()
+        a.slot_var = prog.slot_var.data_ptr()
         a.order = prog.order(order).data_ptr()
         a.uniforms = uniforms.data_ptr()
         giv = None
         if given is not None:
-            if torch.is_tensor(given) and given.dtype == torch.int32 and given.device == self.device and given.is_contiguous():
-                giv = given
-            else:
-                host = given.cpu().numpy() if torch.is_tensor(given) else np.asarray(given)
-                giv = torch.from_numpy(np.ascontiguousarray(host.astype(np.int64).astype(np.int32))).to(self.device)
-            if tuple(giv.shape) != (self.B, topo.n_vars):
-                raise ValueError('given must be [B][n_vars]')
+            giv = self._rows_i32(given, 'given')
             a.given = giv.data_ptr()
         need = S_.workspace_bytes(self.B, S, self.X, topo.n_msgs, topo.n_vars)
-        work = None
-        if need:
-            work = torch.empty(need // 8, dtype=torch.float64, device=self.device)
-            a.workspace, a.workspace_bytes = work.data_ptr(), need
+        work = self._workspace(a, need) if need else None
         if cond_marginals is not None:
-            if tuple(cond_marginals.shape) != (S, self.B, topo.n_vars, self.X) or cond_marginals.dtype != torch.float64 \
-                    or cond_marginals.device != self.device or not cond_marginals.is_contiguous():
-                raise ValueError('cond_marginals must be a contiguous float64 device tensor [n_samples][B][n_vars][X]')
-            a.cond_marginals = cond_marginals.data_ptr()
+            a.cond_marginals = self._tensor(cond_marginals, (S, self.B, topo.n_vars, self.X), 'cond_marginals', '[n_samples][B][n_vars][X]')
         samples = torch.empty(S, self.B, topo.n_vars, dtype=torch.int32, device=self.device)
         logq = torch.empty(S, self.B, dtype=torch.float64, device=self.device)
         a.samples, a.logq = samples.data_ptr(), logq.data_ptr()
@@ -456,27 +504,13 @@ class FactorGraphBatch:
         prog = V.program(topo, topo.var_ids if roots is None else roots, self.device)
         a = V.ConvergeArgs()
         a.B, a.X, a.n_msgs, a.P, a.U, a.n_vars = self.B, self.X, topo.n_msgs, topo.P, topo.U, topo.n_vars
-        a.n_ops, a.n_srcs, a.n_sweeps = prog.n_ops, prog.n_srcs, prog.n_sweeps
-        a.ops, a.srcs, a.sweeps = prog.ops.data_ptr(), prog.srcs.data_ptr(), prog.sweeps.data_ptr()
-        if topo.P:
-            if self.pair_tables is None:
-                raise RuntimeError('set_pair_tables() first')
-            a.n_pair_tables = self.pair_tables.shape[0]
-            a.pair_tables, a.pair_tab = self.pair_tables.data_ptr(), self.pair_tab.data_ptr()
-        if topo.U:
-            if self.unary_tables is None:
-                raise RuntimeError('set_unary_tables() first')
-            a.n_unary_tables = self.unary_tables.shape[0]
-            a.unary_tables, a.unary_tab = self.unary_tables.data_ptr(), self.unary_tab.data_ptr()
+        _fill_program(a, prog)
+        self._fill_tables(a)
         a.normalize_messages, a.init_messages = 1, (1 if init else 0)
         a.max_rounds, a.tol = int(max_rounds), float(tol)
-        a.in_off, a.in_slots = prog.in_off.data_ptr(), prog.in_slots.data_ptr()
         a.msgs = self.msgs.data_ptr()
         if marginals is not None:
-            if tuple(marginals.shape) != (self.B, topo.n_vars, self.X) or marginals.dtype != torch.float64 \
-                    or marginals.device != self.device or not marginals.is_contiguous():
-                raise ValueError('marginals must be a contiguous float64 device tensor [B][n_vars][X]')
-            a.marginals = marginals.data_ptr()
+            a.marginals = self._tensor(marginals, (self.B, topo.n_vars, self.X), 'marginals', '[B][n_vars][X]')
         rounds = torch.empty(self.B, dtype=torch.int32, device=self.device)
         residual = torch.empty(self.B, dtype=torch.float64, device=self.device)
         a.rounds, a.residual = rounds.data_ptr(), residual.data_ptr()
@@ -497,38 +531,13 @@ class FactorGraphBatch:
         if self.pair_tables is not None and self.pair_tables.dtype != torch.float64:
             raise NotImplementedError(refusal)
         topo = self.topo
-        if cutset is not None:
-            unknown = [v for v in cutset if v not in topo.var_index]
-            if unknown:
-                raise ValueError('cutset names unknown variable ids %r' % (unknown,))
-            cutset = [topo.var_index[v] for v in cutset]
-        pl = K.plan(topo, cutset, self.X, self.device)
+        pl = K.plan(topo, self._cutset_indices(cutset), self.X, self.device)
         a = Args()
         a.B, a.X, a.n_vars, a.P, a.U = self.B, self.X, topo.n_vars, topo.P, topo.U
         a.n_cut, a.n_free, a.n_items, a.n_consts, a.n_forest = pl.n_cut, pl.n_free, pl.n_items, pl.n_consts, pl.n_forest
         a.plan, a.plan_words = pl.dev.data_ptr(), len(pl.words)
-        if topo.P:
-            if self.pair_tables is None:
-                raise RuntimeError('set_pair_tables() first')
-            a.n_pair_tables = self.pair_tables.shape[0]
-            a.pair_tables, a.pair_tab = self.pair_tables.data_ptr(), self.pair_tab.data_ptr()
-        if topo.U:
-            if self.unary_tables is None:
-                raise RuntimeError('set_unary_tables() first')
-            a.n_unary_tables = self.unary_tables.shape[0]
-            a.unary_tables, a.unary_tab = self.unary_tables.data_ptr(), self.unary_tab.data_ptr()
+        self._fill_tables(a)
         return pl, a
-
-    def _labels_i32(self, labels):
-        """labels ([B][n_vars] integers, a tensor or an array) as a contiguous int32 device tensor."""
-        if torch.is_tensor(labels) and labels.dtype == torch.int32 and labels.device == self.device and labels.is_contiguous():
-            lab = labels
-        else:
-            host = labels.cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
-            lab = torch.from_numpy(np.ascontiguousarray(host.astype(np.int64).astype(np.int32))).to(self.device)
-        if tuple(lab.shape) != (self.B, self.topo.n_vars):
-            raise ValueError('labels must be [B][n_vars]')
-        return lab
 
     # ---- the model's true marginals and log Z (include/mlbp_cutset.h) --------------------------------
     def exact_inference(self, labels=None, marginals=None, cutset=None):
@@ -544,19 +553,17 @@ class FactorGraphBatch:
         pl, a = self._cutset_args(K, K.CutsetArgs, cutset, 'exact_inference needs float64 pairwise tables')
         if marginals is None:
             marginals = torch.empty(self.B, topo.n_vars, self.X, dtype=torch.float64, device=self.device)
-        elif tuple(marginals.shape) != (self.B, topo.n_vars, self.X) or marginals.dtype != torch.float64 \
-                or marginals.device != self.device or not marginals.is_contiguous():
-            raise ValueError('marginals must be a contiguous float64 device tensor [B][n_vars][X]')
+        else:
+            self._tensor(marginals, (self.B, topo.n_vars, self.X), 'marginals', '[B][n_vars][X]')
+        a.marginals = marginals.data_ptr()
         log_z = torch.empty(self.B, dtype=torch.float64, device=self.device)
-        a.log_z, a.marginals = log_z.data_ptr(), marginals.data_ptr()
+        a.log_z = log_z.data_ptr()
         joint = lab = None
         if labels is not None:
-            lab = self._labels_i32(labels)
+            lab = self._rows_i32(labels, 'labels')
             joint = torch.empty(self.B, dtype=torch.float64, device=self.device)
             a.labels, a.joint_logp = lab.data_ptr(), joint.data_ptr()
-        need = K.workspace_bytes(self.B, self.X, topo.n_vars, topo.P, topo.U, pl.n_forest, pl.n_cut)
-        work = torch.empty(need // 8, dtype=torch.float64, device=self.device)
-        a.workspace, a.workspace_bytes = work.data_ptr(), need
+        work = self._workspace(a, K.workspace_bytes(self.B, self.X, topo.n_vars, topo.P, topo.U, pl.n_forest, pl.n_cut))
         K.check(K.lib.mlbp_cutset_f64(C.byref(a), _stream_ptr(self.device)))
         return (log_z, marginals) if labels is None else (log_z, marginals, joint)
 
@@ -572,23 +579,15 @@ class FactorGraphBatch:
         under CUTSET_PROPOSAL_BYTES; the uniforms are made once for the whole call and the result does not depend on the
         bound.  cutset: as in exact_inference, without its limit on X^len(cutset).  On a tree configs is [B][N][0] and log_q 0."""
         from . import cutset as K0, cutsetis as K
-        if (seed is None) == (uniforms is None):
-            raise ValueError('give exactly one of seed and uniforms')
-        topo, N = self.topo, int(n_samples)
-        if not 1 <= N <= K.MAX_LISTED:
-            raise ValueError('n_samples must be in [1, %d]' % K.MAX_LISTED)
+        _exactly_one(seed, uniforms)
+        topo, N = self.topo, _listed_count(n_samples, K)
         pl, _ = self._cutset_args(K, K.CutsetisArgs, cutset, 'cutset_proposal needs float64 pairwise tables')
         cut = [int(v) for v in pl.words[K0.PLAN_HEADER:K0.PLAN_HEADER + pl.n_cut]]
         configs = torch.empty(self.B, N, pl.n_cut, dtype=torch.int32, device=self.device)
         log_q = torch.zeros(self.B, N, dtype=torch.float64, device=self.device)
         if not cut:
             return configs, log_q
-        if uniforms is None:
-            gen = torch.Generator(self.device).manual_seed(int(seed))
-            uniforms = torch.rand((N, self.B, topo.n_vars), dtype=torch.float64, device=self.device, generator=gen)
-        elif (not torch.is_tensor(uniforms) or uniforms.dtype != torch.float64 or uniforms.device != self.device
-              or tuple(uniforms.shape) != (N, self.B, topo.n_vars) or not uniforms.is_contiguous()):
-            raise ValueError('uniforms must be a contiguous float64 device tensor [n_samples][B][n_vars]')
+        uniforms = self._uniforms(seed, uniforms, (N, self.B, topo.n_vars), '[n_samples][B][n_vars]')
         order = [topo.var_ids[v] for v in cut] + [topo.var_ids[v] for v in range(topo.n_vars) if v not in set(cut)]
         step = max(1, CUTSET_PROPOSAL_BYTES // (self.B * topo.n_vars * self.X * 8))
         cols = torch.tensor(cut, dtype=torch.int64, device=self.device)
@@ -615,16 +614,11 @@ class FactorGraphBatch:
     def _cutdraw_plan(self, cutset):
         """The draw plan of a cutset given as variable ids (None: cutset.choose)."""
         from . import cutdraw as K
-        topo = self.topo
-        if cutset is not None:
-            unknown = [v for v in cutset if v not in topo.var_index]
-            if unknown:
-                raise ValueError('cutset names unknown variable ids %r' % (unknown,))
-            cutset = [topo.var_index[v] for v in cutset]
-        return K.plan(topo, cutset, self.X, self.device)
+        return K.plan(self.topo, self._cutset_indices(cutset), self.X, self.device)
 
     def _cutdraw(self, what, N, cutset, uniforms=None, configs_in=None):
-        """One call into libmlbp_cutdraw.so: (configs or None, log_q).  N: entries per graph."""
+        """One call into libmlbp_cutdraw.so: (configs or None, log_q).  N: entries per graph; uniforms: [B][N][n_cut], checked
+        by the caller."""
         from . import cutdraw as K
         self._cutdraw_refuse(what)
         topo = self.topo
@@ -634,22 +628,14 @@ class FactorGraphBatch:
         configs = None
         if configs_in is None:
             configs = torch.empty(shape, dtype=torch.int32, device=self.device)
-            if uniforms is not None and (not torch.is_tensor(uniforms) or uniforms.dtype != torch.float64 or uniforms.device != self.device
-                                         or tuple(uniforms.shape) != shape or not uniforms.is_contiguous()):
-                raise ValueError('uniforms must be a contiguous float64 device tensor [B][n_samples][n_cut]')
-        elif (not torch.is_tensor(configs_in) or configs_in.dtype != torch.int32 or configs_in.device != self.device
-              or tuple(configs_in.shape) != shape or not configs_in.is_contiguous()):
-            raise ValueError('configs must be a contiguous int32 device tensor [B][N][n_cut]')
+        else:
+            self._tensor(configs_in, shape, 'configs', '[B][N][n_cut]', dtype=torch.int32)
         if not pl.n_cut:                                        # a tree: the one empty configuration, nothing to launch
             return configs, log_q
         a = K.CutdrawArgs()
         a.B, a.X, a.n_msgs, a.P, a.n_cut, a.N = self.B, self.X, topo.n_msgs, topo.P, pl.n_cut, N
         a.plan, a.plan_words = pl.dev.data_ptr(), len(pl.words)
-        if topo.P:
-            if self.pair_tables is None:
-                raise RuntimeError('set_pair_tables() first')
-            a.n_pair_tables = self.pair_tables.shape[0]
-            a.pair_tables, a.pair_tab = self.pair_tables.data_ptr(), self.pair_tab.data_ptr()
+        self._fill_tables(a, unary=False)
         a.msgs, a.log_q = self.msgs.data_ptr(), log_q.data_ptr()
         if configs_in is None:
             a.uniforms, a.configs = uniforms.data_ptr(), configs.data_ptr()
@@ -670,15 +656,10 @@ class FactorGraphBatch:
         drawn from its loopy-BP marginal; on a tree with converged messages and a connected cutset the proposal is Z_c / Z
         itself.  A tree (no cutset) gives configs [B][N][0] and log_q 0 without a launch.  self.msgs is read, not written."""
         from . import cutdraw as K
-        if (seed is None) == (uniforms is None):
-            raise ValueError('give exactly one of seed and uniforms')
+        _exactly_one(seed, uniforms)
         self._cutdraw_refuse('cutset_draw')
-        N = int(n_samples)
-        if not 1 <= N <= K.MAX_LISTED:
-            raise ValueError('n_samples must be in [1, %d]' % K.MAX_LISTED)
-        if uniforms is None:
-            gen = torch.Generator(self.device).manual_seed(int(seed))
-            uniforms = torch.rand((self.B, N, self._cutdraw_plan(cutset).n_cut), dtype=torch.float64, device=self.device, generator=gen)
+        N = _listed_count(n_samples, K)
+        uniforms = self._uniforms(seed, uniforms, (self.B, N, self._cutdraw_plan(cutset).n_cut), '[B][n_samples][n_cut]')
         return self._cutdraw('cutset_draw', N, cutset, uniforms=uniforms)
 
     def cutset_logq(self, configs, cutset=None):
@@ -728,38 +709,29 @@ class FactorGraphBatch:
         elif roots is not None or n_samples is not None or seed is not None or uniforms is not None:
             raise ValueError('configs and log_q replace roots, n_samples, seed and uniforms')
         pl, a = self._cutset_args(K, K.CutsetisArgs, cutset, 'cutset_estimate needs float64 pairwise tables')
-        if not torch.is_tensor(log_q) or log_q.dtype != torch.float64 or log_q.device != self.device or log_q.dim() != 2 \
-                or log_q.shape[0] != self.B or not log_q.is_contiguous():
-            raise ValueError('log_q must be a contiguous float64 device tensor [B][N]')
-        N = int(log_q.shape[1])
-        if not 1 <= N <= K.MAX_LISTED:
-            raise ValueError('N must be in [1, %d]' % K.MAX_LISTED)
-        if not torch.is_tensor(configs) or configs.dtype != torch.int32 or configs.device != self.device \
-                or tuple(configs.shape) != (self.B, N, pl.n_cut) or not configs.is_contiguous():
-            raise ValueError('configs must be a contiguous int32 device tensor [B][N][n_cut]')
+        a.log_q = self._tensor(log_q, (self.B, None), 'log_q', '[B][N]')
+        a.N = N = _listed_count(log_q.shape[1], K, 'N')
+        configs_ptr = self._tensor(configs, (self.B, N, pl.n_cut), 'configs', '[B][N][n_cut]', dtype=torch.int32)
+        if pl.n_cut:
+            a.configs = configs_ptr
         if marginals is None:
             marginals = torch.empty(self.B, topo.n_vars, self.X, dtype=torch.float64, device=self.device)
-        elif tuple(marginals.shape) != (self.B, topo.n_vars, self.X) or marginals.dtype != torch.float64 \
-                or marginals.device != self.device or not marginals.is_contiguous():
-            raise ValueError('marginals must be a contiguous float64 device tensor [B][n_vars][X]')
+        else:
+            self._tensor(marginals, (self.B, topo.n_vars, self.X), 'marginals', '[B][n_vars][X]')
+        a.marginals = marginals.data_ptr()
         log_z_hat = torch.empty(self.B, dtype=torch.float64, device=self.device)
         ess = torch.empty(self.B, dtype=torch.float64, device=self.device)
-        a.N, a.log_q = N, log_q.data_ptr()
-        if pl.n_cut:
-            a.configs = configs.data_ptr()
-        a.log_z_hat, a.marginals, a.ess = log_z_hat.data_ptr(), marginals.data_ptr(), ess.data_ptr()
+        a.log_z_hat, a.ess = log_z_hat.data_ptr(), ess.data_ptr()
         out = [log_z_hat, marginals, ess]
         lab = None
         if labels is not None:
-            lab = self._labels_i32(labels)
+            lab = self._rows_i32(labels, 'labels')
             out.append(torch.empty(self.B, dtype=torch.float64, device=self.device))
             a.labels, a.joint_logp = lab.data_ptr(), out[-1].data_ptr()
         if log_w:
             out.append(torch.empty(self.B, N, dtype=torch.float64, device=self.device))
             a.log_w = out[-1].data_ptr()
-        need = K.workspace_bytes(self.B, self.X, topo.n_vars, topo.P, topo.U, pl.n_forest, N)
-        work = torch.empty(need // 8, dtype=torch.float64, device=self.device)
-        a.workspace, a.workspace_bytes = work.data_ptr(), need
+        work = self._workspace(a, K.workspace_bytes(self.B, self.X, topo.n_vars, topo.P, topo.U, pl.n_forest, N))
         K.check(K.lib.mlbp_cutsetis_f64(C.byref(a), _stream_ptr(self.device)))
         return tuple(out)
 
@@ -780,16 +752,13 @@ class FactorGraphBatch:
         elif max_marginals is False:
             max_marginals = None
         if max_marginals is not None:
-            if not torch.is_tensor(max_marginals) or tuple(max_marginals.shape) != (self.B, topo.n_vars, self.X) \
-                    or max_marginals.dtype != torch.float64 or max_marginals.device != self.device or not max_marginals.is_contiguous():
-                raise ValueError('max_marginals must be True or a contiguous float64 device tensor [B][n_vars][X]')
-            a.max_marginals = max_marginals.data_ptr()
+            a.max_marginals = self._tensor(max_marginals, (self.B, topo.n_vars, self.X), 'max_marginals',
+                                           message='max_marginals must be True or a contiguous float64 device tensor [B][n_vars][X]')
         assignment = torch.empty(self.B, topo.n_vars, dtype=torch.int32, device=self.device)
         score = torch.empty(self.B, dtype=torch.float64, device=self.device)
         a.assignment, a.score = assignment.data_ptr(), score.data_ptr()
-        need = K.workspace_bytes(self.B, self.X, topo.n_vars, topo.P, topo.U, pl.n_forest, pl.n_cut, max_marginals is not None)
-        work = torch.empty(need // 8, dtype=torch.float64, device=self.device)
-        a.workspace, a.workspace_bytes = work.data_ptr(), need
+        work = self._workspace(a, K.workspace_bytes(self.B, self.X, topo.n_vars, topo.P, topo.U, pl.n_forest, pl.n_cut,
+                                                    max_marginals is not None))
         K.check(K.lib.mlbp_exactmap_f64(C.byref(a), _stream_ptr(self.device)))
         return (assignment, score) if max_marginals is None else (assignment, score, max_marginals)
 
@@ -809,15 +778,10 @@ class FactorGraphBatch:
         from . import cutsetis as KP, exactmap as K
         topo = self.topo
         pl, a = self._cutset_args(KP, K.ExactMapArgs, cutset, 'cutset_map needs float64 pairwise tables')       # the listed check of the plan
-        if not torch.is_tensor(configs) or configs.dtype != torch.int32 or configs.device != self.device or configs.dim() != 3 \
-                or configs.shape[0] != self.B or configs.shape[2] != pl.n_cut or not configs.is_contiguous():
-            raise ValueError('configs must be a contiguous int32 device tensor [B][N][n_cut]')
-        N = int(configs.shape[1])
-        if not 1 <= N <= K.MAX_LISTED:
-            raise ValueError('N must be in [1, %d]' % K.MAX_LISTED)
-        a.N = N
+        configs_ptr = self._tensor(configs, (self.B, None, pl.n_cut), 'configs', '[B][N][n_cut]', dtype=torch.int32)
+        a.N = N = _listed_count(configs.shape[1], K, 'N')
         if pl.n_cut:
-            a.configs = configs.data_ptr()
+            a.configs = configs_ptr
         assignment = torch.empty(self.B, topo.n_vars, dtype=torch.int32, device=self.device)
         score = torch.empty(self.B, dtype=torch.float64, device=self.device)
         a.assignment, a.score = assignment.data_ptr(), score.data_ptr()
@@ -825,18 +789,14 @@ class FactorGraphBatch:
         if entry:
             won = torch.empty(self.B, dtype=torch.int32, device=self.device)
             a.entry = won.data_ptr()
-        need = K.listed_workspace_bytes(self.B, self.X, topo.n_vars, topo.P, topo.U, pl.n_forest, N)
-        work = torch.empty(need // 8, dtype=torch.float64, device=self.device)
-        a.workspace, a.workspace_bytes = work.data_ptr(), need
+        work = self._workspace(a, K.listed_workspace_bytes(self.B, self.X, topo.n_vars, topo.P, topo.U, pl.n_forest, N))
         K.check(K.lib.mlbp_exactmap_f64(C.byref(a), _stream_ptr(self.device)))
         return (assignment, score, won) if entry else (assignment, score)
 
     def _search_list(self, roots, n_samples, seed, uniforms, cutset):
         """The list of search_map(): (configs int32 [B][N][n_cut], map_sweep's assignment, its score)."""
         from . import cutset as K0, cutsetis as KP
-        N = int(n_samples)
-        if not 1 <= N <= KP.MAX_LISTED:
-            raise ValueError('n_samples must be in [1, %d]' % KP.MAX_LISTED)
+        N = _listed_count(n_samples, KP)
         pl, _ = self._cutset_args(KP, KP.CutsetisArgs, cutset, 'search_map needs float64 pairwise tables')
         cut = [int(v) for v in pl.words[K0.PLAN_HEADER:K0.PLAN_HEADER + pl.n_cut]]
         x_bp, score_bp = self.map_sweep(roots, init=True)
@@ -880,9 +840,7 @@ class FactorGraphBatch:
         scores = torch.empty(self.B, m, dtype=torch.float64, device=self.device)
         n_found = torch.empty(self.B, dtype=torch.int32, device=self.device)
         a.M, a.assignments, a.scores, a.n_found = m, assignments.data_ptr(), scores.data_ptr(), n_found.data_ptr()
-        need = K.workspace_bytes(self.B, self.X, topo.n_vars, topo.P, topo.U, pl.n_forest, pl.n_cut, m)
-        work = torch.empty(need // 8, dtype=torch.float64, device=self.device)
-        a.workspace, a.workspace_bytes = work.data_ptr(), need
+        work = self._workspace(a, K.workspace_bytes(self.B, self.X, topo.n_vars, topo.P, topo.U, pl.n_forest, pl.n_cut, m))
         K.check(K.lib.mlbp_exactmbest_f64(C.byref(a), _stream_ptr(self.device)))
         return assignments, scores, n_found
 
@@ -899,18 +857,12 @@ class FactorGraphBatch:
         dtype=float64, device=..., generator=torch.Generator(device).manual_seed(seed)).  cutset: as in exact_inference.  A
         graph whose Z is zero or not finite gets samples -1 and logp NaN.  self.msgs is neither read nor written."""
         from . import exactsample as K
-        if (seed is None) == (uniforms is None):
-            raise ValueError('give exactly one of seed and uniforms')
+        _exactly_one(seed, uniforms)
         topo, S = self.topo, int(n_samples)
         if S <= 0:
             raise ValueError('n_samples must be positive')
         pl, a = self._cutset_args(K, K.ExactSampleArgs, cutset, 'exact_sample needs float64 pairwise tables')
-        if uniforms is None:
-            gen = torch.Generator(self.device).manual_seed(int(seed))
-            uniforms = torch.rand((S, self.B, topo.n_vars), dtype=torch.float64, device=self.device, generator=gen)
-        elif (not torch.is_tensor(uniforms) or uniforms.dtype != torch.float64 or uniforms.device != self.device
-              or tuple(uniforms.shape) != (S, self.B, topo.n_vars) or not uniforms.is_contiguous()):
-            raise ValueError('uniforms must be a contiguous float64 device tensor [n_samples][B][n_vars]')
+        uniforms = self._uniforms(seed, uniforms, (S, self.B, topo.n_vars), '[n_samples][B][n_vars]')
         a.S, a.uniforms = S, uniforms.data_ptr()
         samples = torch.empty(S, self.B, topo.n_vars, dtype=torch.int32, device=self.device)
         logp = torch.empty(S, self.B, dtype=torch.float64, device=self.device)
@@ -922,9 +874,7 @@ class FactorGraphBatch:
         if score:
             out.append(torch.empty(S, self.B, dtype=torch.float64, device=self.device))
             a.score = out[-1].data_ptr()
-        need = K.workspace_bytes(self.B, S, self.X, topo.n_vars, topo.P, topo.U, pl.n_forest, pl.n_cut)
-        work = torch.empty(need // 8, dtype=torch.float64, device=self.device)
-        a.workspace, a.workspace_bytes = work.data_ptr(), need
+        work = self._workspace(a, K.workspace_bytes(self.B, S, self.X, topo.n_vars, topo.P, topo.U, pl.n_forest, pl.n_cut))
         K.check(K.lib.mlbp_exactsample_f64(C.byref(a), _stream_ptr(self.device)))
         return tuple(out)
 
@@ -935,10 +885,8 @@ class FactorGraphBatch:
         topo = self.topo
         pl, a = self._cutset_args(K, K.ExactGradArgs, cutset, 'the exact pair marginals and gradient need float64 pairwise tables')
 
-        def checked(t, shape, what):
-            if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != torch.float64 or t.device != self.device or not t.is_contiguous():
-                raise ValueError('%s must be a contiguous float64 device tensor %s' % (what, list(shape)))
-            return t.data_ptr()
+        def checked(t, shape, what):                           # the message prints the sizes themselves
+            return self._tensor(t, shape, what, list(shape))
         if marginals is not None:
             a.marginals = checked(marginals, (self.B, topo.n_vars, self.X), 'marginals')
         if pair_marginals is not None:
@@ -960,14 +908,12 @@ class FactorGraphBatch:
                 a.grad_ee, a.grad_ed = checked(grad[0], (self.B, a.F_ee), 'out_ee'), checked(grad[1], (self.B, a.F_ed), 'out_ed')
                 if labels is None and getattr(self, '_labels', None) is None:
                     raise RuntimeError('exact_gradient needs labels: pass them or set_observations() first')
-                lab = self._labels_i32(self._labels if labels is None else labels)
+                lab = self._rows_i32(self._labels if labels is None else labels, 'labels')
                 keep.append(lab)
                 a.labels = lab.data_ptr()
         log_z = torch.empty(self.B, dtype=torch.float64, device=self.device)
         a.log_z = log_z.data_ptr()
-        need = K.workspace_bytes(self.B, self.X, topo.n_vars, topo.P, topo.U, pl.n_forest, pl.n_cut)
-        work = torch.empty(need // 8, dtype=torch.float64, device=self.device)
-        a.workspace, a.workspace_bytes = work.data_ptr(), need
+        work = self._workspace(a, K.workspace_bytes(self.B, self.X, topo.n_vars, topo.P, topo.U, pl.n_forest, pl.n_cut))
         K.check(K.lib.mlbp_exactgrad_f64(C.byref(a), _stream_ptr(self.device)))
         return log_z
 

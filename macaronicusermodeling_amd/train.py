@@ -31,6 +31,53 @@ ADAPT_EXT = {'user': '.user_adapt', 'experience': '.exp_adapt', None: ''}
 SEARCH_ROSE = 1e-9              # search_decode: a score counts as risen above decode()'s beyond this, relative to max(1, |score|)
 
 
+def _host(*tensors):
+    """The tensors' host arrays."""
+    return tuple(t.cpu().numpy() for t in tensors)
+
+
+# ---- what TiDirTrainer's reports share: one walk over the sentence shapes, one reduction (tests/test_batch_args_cpu.py) ------
+def _try(call, refused):
+    """(call(), None), or (None, e) for the error e of class `refused` (None: no class) whose code says the library does not
+    take this shape, MLBP_EUNSUPPORTED; every other error goes through."""
+    try:
+        return call(), None
+    except refused or () as e:
+        if e.code != _ffi.MLBP_EUNSUPPORTED:
+            raise
+        return None, e
+
+
+def _per_shape(trainers, buckets, call, out=None, row=None, placeholder=None, refused=None, skipped=None, on_refused=None):
+    """Walks the sentence shapes in `trainers` order and returns [(key, rows, result)] of the shapes that answered: result =
+    call(i, trainer), i the shape's position in that order -- counted over every shape, answered or not --, rows =
+    buckets[key]['rows'].  A shape whose call raises `refused` with MLBP_EUNSUPPORTED is noted in `skipped` as (predicted
+    positions, instances, reason), then handed to on_refused(trainer, rows) if given; a call may also return None to pass over its
+    shape unnoted.  With `out`, the per-instance list: out[row['index']] = (predicted positions,) + row(result, b) for instance b
+    of a shape that answered, (predicted positions,) + placeholder for the others."""
+    answered = []
+    for i, (key, tr) in enumerate(trainers.items()):
+        rows = buckets[key]['rows']
+        res, e = _try(lambda: call(i, tr), refused)
+        if e is not None:
+            skipped.append((tuple(key[1]), len(rows), str(e)))
+            if on_refused is not None:
+                on_refused(tr, rows)
+        for b, r in enumerate(rows if out is not None else ()):
+            out[r['index']] = (tuple(key[1]),) + (placeholder if res is None else row(res, b))
+        if res is not None:
+            answered.append((key, rows, res))
+    return answered
+
+
+def _reduced(device, sums, maxima=()):
+    """(sums, maxima) over ALL ranks as host float64 arrays: one fused all-reduce each (dist.all_reduce_sum_ / _max_), and none
+    for an empty `maxima`."""
+    tot = mdist.all_reduce_sum_(torch.tensor([float(v) for v in sums], dtype=torch.float64, device=device))
+    top = torch.tensor([float(v) for v in maxima], dtype=torch.float64, device=device)
+    return tot.cpu().numpy(), (mdist.all_reduce_max_(top) if len(maxima) else top).cpu().numpy()
+
+
 class UserGraphTrainer:
     def __init__(self, spec, var_labels, unary_obs, phi_en_en, phi_en_en_w1, phi_en_de, theta_en_en, theta_en_de,
                  device='cuda:0', sweeps=3, roots=None, planes=None, domains=None, theta_dom_en_en=None,
@@ -289,7 +336,7 @@ class UserGraphTrainer:
         settled = torch.empty_like(self._marg)
         rounds, residual = fb.converge(tol=tol, max_rounds=max_rounds, init=True, marginals=settled)
         gap = np.abs(stopped - settled.cpu().numpy()).reshape(fb.B, -1).max(axis=1)
-        return rounds.cpu().numpy(), residual.cpu().numpy(), gap
+        return _host(rounds, residual) + (gap,)
 
     def joint_log_likelihood(self):
         """How probable the model finds each instance's whole set of stored labels, under the current thetas: host
@@ -299,7 +346,7 @@ class UserGraphTrainer:
         fb = self.batch
         self.build_potentials()
         log_z, joint = fb.log_partition(self.roots[:self.n_sweeps_run], init=True, labels=fb._labels)
-        return joint.cpu().numpy(), log_z.cpu().numpy()
+        return _host(joint, log_z)
 
     def exact_inference(self):
         """How wrong the usual sweeps were for each instance, under the current thetas: host (log_z float64 [B] -- the model's
@@ -314,7 +361,7 @@ class UserGraphTrainer:
         bp = fb.marginals()
         gap = (bp - exact).abs().reshape(fb.B, -1).max(dim=1).values
         agrees = (bp.argmax(dim=2) == exact.argmax(dim=2)).all(dim=1)
-        return (log_z.cpu().numpy(), (bethe - log_z).cpu().numpy(), gap.cpu().numpy(), agrees.cpu().numpy(), joint.cpu().numpy())
+        return _host(log_z, bethe - log_z, gap, agrees, joint)
 
     def estimated_inference(self, n_samples, seed, proposal='sample'):
         """The sentence shapes exact_inference() refuses: an ESTIMATE of each instance's log Z under the current thetas by
@@ -330,12 +377,12 @@ class UserGraphTrainer:
         if proposal == 'messages':
             bethe = fb.log_partition(roots, init=True)
             log_z_hat, marg, ess = fb.cutset_estimate(n_samples=n_samples, seed=seed, proposal='messages')
-            return log_z_hat.cpu().numpy(), ess.cpu().numpy(), (bethe - log_z_hat).cpu().numpy(), marg.cpu().numpy()
-        if proposal != 'sample':
+        elif proposal != 'sample':
             raise ValueError("proposal must be 'sample' or 'messages', not %r" % (proposal,))
-        log_z_hat, marg, ess = fb.cutset_estimate(roots, n_samples=n_samples, seed=seed)
-        bethe = fb.log_partition(roots, init=True)
-        return log_z_hat.cpu().numpy(), ess.cpu().numpy(), (bethe - log_z_hat).cpu().numpy(), marg.cpu().numpy()
+        else:
+            log_z_hat, marg, ess = fb.cutset_estimate(roots, n_samples=n_samples, seed=seed)
+            bethe = fb.log_partition(roots, init=True)
+        return _host(log_z_hat, ess, bethe - log_z_hat, marg)
 
     def _plane_share(self, belief):
         """The per-instance feature planes' share of the en_de gradient, host [B][F_ed]: for every plane cell (i, observed
@@ -401,8 +448,7 @@ class UserGraphTrainer:
         agrees = (bp_x == x).all(dim=1)
         shortfall = torch.where(agrees, torch.zeros_like(score), (score - bp_score).clamp(min=0.0))
         joint = fb.exact_inference(labels=x)[2]
-        return (x.cpu().numpy().astype(np.int64), score.cpu().numpy(), margin.cpu().numpy(), agrees.cpu().numpy(),
-                shortfall.cpu().numpy(), joint.cpu().numpy())
+        return (x.cpu().numpy().astype(np.int64),) + _host(score, margin, agrees, shortfall, joint)
 
     def search_decode(self, n_samples=256, seed=0, with_list=False):
         """The sentence shapes exact_decode() refuses, and the others beside it: the best set of guesses among those whose
@@ -416,7 +462,7 @@ class UserGraphTrainer:
         self.build_potentials()
         configs, bp_x, bp_score = fb._search_list(self.roots[:self.n_sweeps_run], n_samples, seed, None, None)
         x, score = fb.cutset_map(configs)
-        out = (x.cpu().numpy().astype(np.int64), score.cpu().numpy(), bp_score.cpu().numpy(), (bp_x != x).any(dim=1).cpu().numpy())
+        out = (x.cpu().numpy().astype(np.int64),) + _host(score, bp_score, (bp_x != x).any(dim=1))
         return out + (configs.cpu().numpy(),) if with_list else out
 
     def exact_nbest(self, m):
@@ -438,8 +484,7 @@ class UserGraphTrainer:
         def rank_of(rows):
             hit = (x == rows[:, None, :].to(x.dtype)).all(dim=2)
             return torch.where(hit.any(dim=1), hit.to(torch.int64).argmax(dim=1), torch.full_like(hit[:, 0], -1, dtype=torch.int64))
-        return (x.cpu().numpy().astype(np.int64), score.cpu().numpy(), logp.cpu().numpy(), covered.cpu().numpy(),
-                rank_of(fb._labels).cpu().numpy(), rank_of(bp_x).cpu().numpy())
+        return (x.cpu().numpy().astype(np.int64),) + _host(score, logp, covered, rank_of(fb._labels), rank_of(bp_x))
 
 
 def apply_update(theta_en_en, theta_en_de, stats, F_ee, F_ed, learning_rate, reg_param):
@@ -963,6 +1008,26 @@ class TiDirTrainer:
                               self.theta_en_de.cpu().numpy().reshape(1, -1), d2t=self.domain_thetas())
         return history
 
+    # ---- what the reports below share ------------------------------------------------------------------
+    def _per_shape(self, call, empty=None, **how):
+        """-> (per-instance list, [(key, rows, result)]): module-level _per_shape over this rank's shapes.  The list (None
+        without `empty`) has one entry per instance of the shard in file order, `empty` for those that build no graph."""
+        out = None if empty is None else [empty] * (self._shard[1] - self._shard[0])
+        return out, _per_shape(self.trainers, self.buckets, call, out=out, **how)
+
+    def _reduced(self, sums, maxima=()):
+        return _reduced(self.device, sums, maxima)
+
+    def _hit_counts(self, key, x):
+        """decode()'s counts of one shape: (sentences all right, sentences, words right, words)."""
+        hit = x == self.buckets[key]['var_labels']
+        return np.array([int(hit.all(axis=1).sum()), hit.shape[0], int(hit.sum()), hit.size], dtype=np.int64)
+
+    def _draws_row(self, r, b):
+        """([[en words] per sample], [log-probability per sample]) of instance b from a shape's (samples [S][B][n_vars], logp [S][B])."""
+        x, logp = r
+        return [[self.en[w] for w in x[s, b]] for s in range(x.shape[0])], [float(logp[s, b]) for s in range(x.shape[0])]
+
     # ---- joint decoding (max-product; the reference has none) ---------------------------------------
     def decode(self):
         """-> (guesses, counts).  guesses[i], for instance i of this rank's shard in file order: (predicted positions, [en
@@ -970,18 +1035,10 @@ class TiDirTrainer:
         (UserGraphTrainer.decode) and its log-potential; an instance without a predicted word builds no graph and gives
         ((), [], 0.0).  counts = (sentences whose every predicted word equals the user's guess, sentences with a predicted
         word, predicted words equal to the user's guess, predicted words) over ALL ranks' instances, reduced once."""
-        n = self._shard[1] - self._shard[0]
-        guesses = [((), [], 0.0)] * n
-        counts = np.zeros(4, dtype=np.int64)
-        for key, tr in self.trainers.items():
-            x, score = tr.decode()
-            hit = x == self.buckets[key]['var_labels']
-            counts += np.array([int(hit.all(axis=1).sum()), hit.shape[0], int(hit.sum()), hit.size], dtype=np.int64)
-            for b, row in enumerate(self.buckets[key]['rows']):
-                guesses[row['index']] = (tuple(key[1]), [self.en[w] for w in x[b]], float(score[b]))
-        tot = torch.tensor([float(v) for v in counts], dtype=torch.float64, device=self.device)
-        mdist.all_reduce_sum_(tot)
-        return guesses, tuple(int(v) for v in tot.cpu().numpy())
+        guesses, shapes = self._per_shape(lambda i, tr: tr.decode(), empty=((), [], 0.0),
+                                          row=lambda r, b: ([self.en[w] for w in r[0][b]], float(r[1][b])))
+        counts = sum((self._hit_counts(key, x) for key, _, (x, _) in shapes), np.zeros(4, dtype=np.int64))
+        return guesses, tuple(int(v) for v in self._reduced(counts)[0])
 
     # ---- posterior sampling of whole sets of guesses (the reference has none) --------------------------
     def sample(self, n_samples=1, seed=0):
@@ -990,14 +1047,8 @@ class TiDirTrainer:
         (UserGraphTrainer.sample) and the log-probability of each draw under the sampler; an instance without a predicted
         word builds no graph and gives ((), [], []).  The i-th sentence shape in self.trainers order draws with seed
         `seed + i`.  Every rank draws for its own shard: nothing is reduced."""
-        n = self._shard[1] - self._shard[0]
-        per_instance = [((), [], [])] * n
-        for i, (key, tr) in enumerate(self.trainers.items()):
-            x, logq = tr.sample(n_samples=n_samples, seed=int(seed) + i)
-            for b, row in enumerate(self.buckets[key]['rows']):
-                per_instance[row['index']] = (tuple(key[1]), [[self.en[w] for w in x[s, b]] for s in range(x.shape[0])],
-                                              [float(logq[s, b]) for s in range(x.shape[0])])
-        return per_instance
+        return self._per_shape(lambda i, tr: tr.sample(n_samples=n_samples, seed=int(seed) + i), empty=((), [], []),
+                               row=self._draws_row)[0]
 
     # ---- draws from the model itself (include/mlbp_exactsample.h) ----------------------------------------
     def exact_sample(self, n_samples=1, seed=0):
@@ -1009,23 +1060,9 @@ class TiDirTrainer:
         [(predicted positions, instances, reason)] of this rank's shapes above the limit.  Every rank draws for its own
         shard: nothing is reduced."""
         from . import exactsample as K
-        n = self._shard[1] - self._shard[0]
-        per_instance = [((), [], [])] * n
         skipped = []
-        for i, (key, tr) in enumerate(self.trainers.items()):
-            rows = self.buckets[key]['rows']
-            try:
-                x, logp = tr.exact_sample(n_samples=n_samples, seed=int(seed) + i)
-            except K.ExactSampleError as e:
-                if e.code != _ffi.MLBP_EUNSUPPORTED:
-                    raise
-                skipped.append((tuple(key[1]), len(rows), str(e)))
-                for row in rows:
-                    per_instance[row['index']] = (tuple(key[1]), None, None)
-                continue
-            for b, row in enumerate(rows):
-                per_instance[row['index']] = (tuple(key[1]), [[self.en[w] for w in x[s, b]] for s in range(x.shape[0])],
-                                              [float(logp[s, b]) for s in range(x.shape[0])])
+        per_instance, _ = self._per_shape(lambda i, tr: tr.exact_sample(n_samples=n_samples, seed=int(seed) + i), empty=((), [], []),
+                                          row=self._draws_row, placeholder=(None, None), refused=K.ExactSampleError, skipped=skipped)
         return per_instance, skipped
 
     # ---- sweeps to convergence (the reference stops at three sweeps and never looks) -------------------
@@ -1034,21 +1071,16 @@ class TiDirTrainer:
         positions, rounds, residual, gap) as UserGraphTrainer.convergence gives them; an instance without a predicted word
         builds no graph and gives ((), 0, 0.0, 0.0).  totals = (sentences with a predicted word, sentences whose residual is
         still above tol after max_rounds, sum of rounds, sum of gap) over ALL ranks' instances, reduced once."""
-        n = self._shard[1] - self._shard[0]
-        per_instance = [((), 0, 0.0, 0.0)] * n
+        per_instance, shapes = self._per_shape(lambda i, tr: tr.convergence(tol=tol, max_rounds=max_rounds), empty=((), 0, 0.0, 0.0),
+                                               row=lambda r, b: (int(r[0][b]), float(r[1][b]), float(r[2][b])))
         seen = open_ = total_rounds = 0
         total_gap = 0.0
-        for key, tr in self.trainers.items():
-            rounds, residual, gap = tr.convergence(tol=tol, max_rounds=max_rounds)
+        for _, _, (rounds, residual, gap) in shapes:
             seen += rounds.shape[0]
             open_ += int((~(residual <= tol)).sum())
             total_rounds += int(rounds.sum())
             total_gap += float(gap.sum())
-            for b, row in enumerate(self.buckets[key]['rows']):
-                per_instance[row['index']] = (tuple(key[1]), int(rounds[b]), float(residual[b]), float(gap[b]))
-        tot = torch.tensor([float(seen), float(open_), float(total_rounds), total_gap], dtype=torch.float64, device=self.device)
-        mdist.all_reduce_sum_(tot)
-        tot = tot.cpu().numpy()
+        tot, _ = self._reduced([seen, open_, total_rounds, total_gap])
         return per_instance, (int(tot[0]), int(tot[1]), int(tot[2]), float(tot[3]))
 
     # ---- how wrong was it: the sweeps against the model's true values (include/mlbp_cutset.h) ---------
@@ -1061,35 +1093,19 @@ class TiDirTrainer:
         all agree) over ALL ranks' instances, reduced once.  skipped: [(predicted positions, instances, reason)] of this rank's
         shapes above the limit."""
         from . import cutset as K
-        n = self._shard[1] - self._shard[0]
-        per_instance = [((), 0.0, 0.0, 0.0, True)] * n
-        seen = n_skipped = n_agree = 0
-        sum_gap = 0.0
-        worst = torch.zeros(1, dtype=torch.float64, device=self.device)
         skipped = []
-        for key, tr in self.trainers.items():
-            rows = self.buckets[key]['rows']
-            try:
-                log_z, bethe_gap, marg_gap, agrees, _ = tr.exact_inference()
-            except K.CutsetError as e:
-                if e.code != _ffi.MLBP_EUNSUPPORTED:
-                    raise
-                skipped.append((tuple(key[1]), len(rows), str(e)))
-                n_skipped += len(rows)
-                for row in rows:
-                    per_instance[row['index']] = (tuple(key[1]), None, None, None, None)
-                continue
+        per_instance, shapes = self._per_shape(
+            lambda i, tr: tr.exact_inference(), empty=((), 0.0, 0.0, 0.0, True), placeholder=(None,) * 4, refused=K.CutsetError,
+            skipped=skipped, row=lambda r, b: (float(r[0][b]), float(r[1][b]), float(r[2][b]), bool(r[3][b])))
+        seen = n_agree = 0
+        sum_gap = worst = 0.0
+        for _, rows, (_, bethe_gap, marg_gap, agrees, _) in shapes:
             seen += len(rows)
             sum_gap += float(np.abs(bethe_gap).sum())
             n_agree += int(agrees.sum())
-            worst[0] = max(float(worst[0]), float(marg_gap.max()))
-            for b, row in enumerate(rows):
-                per_instance[row['index']] = (tuple(key[1]), float(log_z[b]), float(bethe_gap[b]), float(marg_gap[b]), bool(agrees[b]))
-        tot = torch.tensor([float(seen), float(n_skipped), sum_gap, float(n_agree)], dtype=torch.float64, device=self.device)
-        mdist.all_reduce_sum_(tot)
-        mdist.all_reduce_max_(worst)
-        tot = tot.cpu().numpy()
-        return per_instance, (int(tot[0]), int(tot[1]), float(tot[2]), float(worst[0]), int(tot[3])), skipped
+            worst = max(worst, float(marg_gap.max()))
+        tot, top = self._reduced([seen, sum(s[1] for s in skipped), sum_gap, n_agree], [worst])
+        return per_instance, (int(tot[0]), int(tot[1]), float(tot[2]), float(top[0]), int(tot[3])), skipped
 
     # ---- and the longer sentences: log Z estimated by cutset importance sampling (include/mlbp_cutsetis.h) ---------------
     def estimate_report(self, n_samples=256, seed=0, proposal='sample'):
@@ -1104,50 +1120,31 @@ class TiDirTrainer:
         ess / n_samples) over ALL ranks' instances, reduced once.  skipped: [(predicted positions, instances, reason)] of this
         rank's shapes that the estimating library refuses -- none of the shapes the exact reports skip for their size."""
         from . import cutset as K0, cutsetis as K
-        n = self._shard[1] - self._shard[0]
-        per_instance = [((), None, None, None, None)] * n
-        seen = both = 0
-        sum_err = sum_share = 0.0
-        worst = torch.zeros(1, dtype=torch.float64, device=self.device)
-        skipped = []
-        for i, (key, tr) in enumerate(self.trainers.items()):
-            rows = self.buckets[key]['rows']
+        def call(i, tr):
             if not tr.topo.P:
-                for row in rows:
-                    per_instance[row['index']] = (tuple(key[1]), None, None, None, None)
-                continue
-            try:
-                log_z_hat, ess, bethe_gap, _ = tr.estimated_inference(n_samples, int(seed) + i, proposal=proposal)
-            except K.CutsetisError as e:
-                if e.code != _ffi.MLBP_EUNSUPPORTED:
-                    raise
-                skipped.append((tuple(key[1]), len(rows), str(e)))
-                for row in rows:
-                    per_instance[row['index']] = (tuple(key[1]), None, None, None, None)
-                continue
-            try:
-                log_z = tr.exact_inference()[0]
-            except K0.CutsetError as e:
-                if e.code != _ffi.MLBP_EUNSUPPORTED:
-                    raise
-                log_z = None
+                return None
+            log_z_hat, ess, bethe_gap, _ = tr.estimated_inference(n_samples, int(seed) + i, proposal=proposal)
+            exact, _ = _try(tr.exact_inference, K0.CutsetError)          # above the exact limit: estimated alone
             with np.errstate(divide='ignore', invalid='ignore'):
                 rse = np.sqrt(np.maximum(1.0 / ess - 1.0 / float(n_samples), 0.0))
+            return log_z_hat, rse, bethe_gap, None if exact is None else exact[0], ess
+
+        skipped = []
+        per_instance, shapes = self._per_shape(
+            call, empty=((), None, None, None, None), placeholder=(None,) * 4, refused=K.CutsetisError, skipped=skipped,
+            row=lambda r, b: (float(r[0][b]), float(r[1][b]), float(r[2][b]), None if r[3] is None else float(r[3][b])))
+        seen = both = 0
+        sum_err = sum_share = worst = 0.0
+        for _, rows, (log_z_hat, _, _, log_z, ess) in shapes:
             seen += len(rows)
             sum_share += float(ess.sum()) / float(n_samples)
             if log_z is not None:
                 err = np.abs(log_z_hat - log_z)
                 both += len(rows)
                 sum_err += float(err.sum())
-                worst[0] = max(float(worst[0]), float(err.max()))
-            for b, row in enumerate(rows):
-                per_instance[row['index']] = (tuple(key[1]), float(log_z_hat[b]), float(rse[b]), float(bethe_gap[b]),
-                                              None if log_z is None else float(log_z[b]))
-        tot = torch.tensor([float(seen), float(both), sum_err, sum_share], dtype=torch.float64, device=self.device)
-        mdist.all_reduce_sum_(tot)
-        mdist.all_reduce_max_(worst)
-        tot = tot.cpu().numpy()
-        return per_instance, (int(tot[0]), int(tot[1]), float(tot[2]), float(worst[0]), float(tot[3])), skipped
+                worst = max(worst, float(err.max()))
+        tot, top = self._reduced([seen, both, sum_err, sum_share], [worst])
+        return per_instance, (int(tot[0]), int(tot[1]), float(tot[2]), float(top[0]), float(tot[3])), skipped
 
     # ---- how wrong is the gradient the trainer follows, and a step on the true likelihood (include/mlbp_exactgrad.h) -----
     def _exact_statistics(self, on_limit='skip'):
@@ -1159,19 +1156,15 @@ class TiDirTrainer:
         F = self.n_stat - 2
         exact, bp, fall = np.zeros(F), np.zeros(F), np.zeros(self.n_stat)
         loglik, seen, skipped = 0.0, 0, []
-        for key, tr in self.trainers.items():
-            rows = self.buckets[key]['rows']
-            try:
-                g_ee, g_ed, joint, bp_ee, bp_ed = tr.exact_gradient()
-            except K.ExactGradError as e:
-                if e.code != _ffi.MLBP_EUNSUPPORTED or on_limit == 'raise':
-                    raise
-                skipped.append((tuple(key[1]), len(rows), str(e)))
-                if on_limit == 'bp':
-                    tr.build_potentials()
-                    bp_ee, bp_ed, lp = tr._bp_gradient()
-                    fall += np.concatenate([bp_ee.sum(axis=0), bp_ed.sum(axis=0), [lp.sum(), float(len(rows))]])
-                continue
+
+        def bp_statistics(tr, rows):
+            tr.build_potentials()
+            bp_ee, bp_ed, lp = tr._bp_gradient()
+            fall[:] += np.concatenate([bp_ee.sum(axis=0), bp_ed.sum(axis=0), [lp.sum(), float(len(rows))]])
+
+        _, shapes = self._per_shape(lambda i, tr: tr.exact_gradient(), refused=None if on_limit == 'raise' else K.ExactGradError,
+                                    skipped=skipped, on_refused=bp_statistics if on_limit == 'bp' else None)
+        for _, rows, (g_ee, g_ed, joint, bp_ee, bp_ed) in shapes:
             seen += len(rows)
             loglik += float(joint.sum())
             exact += np.concatenate([g_ee.sum(axis=0), g_ed.sum(axis=0)])
@@ -1187,10 +1180,7 @@ class TiDirTrainer:
         shapes above the configuration limit; an instance without a predicted word builds no graph and is not counted."""
         exact, bp, loglik, seen, _, skipped = self._exact_statistics()
         F = self.n_stat - 2
-        tot = torch.tensor(list(exact) + list(bp) + [loglik, float(seen), float(sum(s[1] for s in skipped))], dtype=torch.float64,
-                           device=self.device)
-        mdist.all_reduce_sum_(tot)
-        tot = tot.cpu().numpy()
+        tot, _ = self._reduced(list(exact) + list(bp) + [loglik, seen, sum(s[1] for s in skipped)])
         exact, bp = tot[:F], tot[F:2 * F]
         ne, nb = float(np.linalg.norm(exact)), float(np.linalg.norm(bp))
         cosine = float(exact.dot(bp)) / (ne * nb) if ne > 0 and nb > 0 else float('nan')
@@ -1229,37 +1219,21 @@ class TiDirTrainer:
         shortfall) over ALL ranks' instances, reduced once.  skipped: [(predicted positions, instances, reason)] of this
         rank's shapes above the limit.  decode() itself is what it was."""
         from . import exactmap as K
-        n = self._shard[1] - self._shard[0]
-        guesses = [((), [], 0.0, 0.0, 0.0)] * n
+        skipped = []
+        guesses, shapes = self._per_shape(
+            lambda i, tr: tr.exact_decode(), empty=((), [], 0.0, 0.0, 0.0), placeholder=(None,) * 4, refused=K.ExactMapError,
+            skipped=skipped, row=lambda r, b: ([self.en[w] for w in r[0][b]], float(r[1][b]), float(r[2][b]), float(r[5][b])))
         counts = np.zeros(4, dtype=np.int64)
         seen = n_agree = 0
-        sum_short = 0.0
-        worst = torch.zeros(1, dtype=torch.float64, device=self.device)
-        skipped = []
-        for key, tr in self.trainers.items():
-            rows = self.buckets[key]['rows']
-            try:
-                x, score, margin, agrees, shortfall, joint = tr.exact_decode()
-            except K.ExactMapError as e:
-                if e.code != _ffi.MLBP_EUNSUPPORTED:
-                    raise
-                skipped.append((tuple(key[1]), len(rows), str(e)))
-                for row in rows:
-                    guesses[row['index']] = (tuple(key[1]), None, None, None, None)
-                continue
-            hit = x == self.buckets[key]['var_labels']
-            counts += np.array([int(hit.all(axis=1).sum()), hit.shape[0], int(hit.sum()), hit.size], dtype=np.int64)
+        sum_short = worst = 0.0
+        for key, rows, (x, _, _, agrees, shortfall, _) in shapes:
+            counts += self._hit_counts(key, x)
             seen += len(rows)
             n_agree += int(agrees.sum())
             sum_short += float(shortfall.sum())
-            worst[0] = max(float(worst[0]), float(shortfall.max()))
-            for b, row in enumerate(rows):
-                guesses[row['index']] = (tuple(key[1]), [self.en[w] for w in x[b]], float(score[b]), float(margin[b]), float(joint[b]))
-        tot = torch.tensor([float(v) for v in counts] + [float(seen), float(n_agree), sum_short], dtype=torch.float64, device=self.device)
-        mdist.all_reduce_sum_(tot)
-        mdist.all_reduce_max_(worst)
-        tot = tot.cpu().numpy()
-        return (guesses, tuple(int(v) for v in tot[:4]), (int(tot[4]), int(tot[5]), float(tot[6]), float(worst[0])), skipped)
+            worst = max(worst, float(shortfall.max()))
+        tot, top = self._reduced(list(counts) + [seen, n_agree, sum_short], [worst])
+        return (guesses, tuple(int(v) for v in tot[:4]), (int(tot[4]), int(tot[5]), float(tot[6]), float(top[0])), skipped)
 
     # ---- search decoding beyond the exact limit (the listed mode of include/mlbp_exactmap.h) -----------------
     def search_decode(self, n_samples=256, seed=0):
@@ -1272,18 +1246,14 @@ class TiDirTrainer:
         counts = (sentences decoded, sentences whose score rose above decode()'s by more than SEARCH_ROSE relative to
         max(1, |score|) -- the rounding of the two sums of logarithms --, sentences whose words changed) over ALL ranks'
         instances, reduced once."""
-        n = self._shard[1] - self._shard[0]
-        guesses = [((), [], 0.0, 0.0)] * n
+        guesses, shapes = self._per_shape(
+            lambda i, tr: tr.search_decode(n_samples=n_samples, seed=int(seed) + i), empty=((), [], 0.0, 0.0),
+            row=lambda r, b: ([self.en[w] for w in r[0][b]], float(r[1][b]), float(r[1][b] - r[2][b])))
         counts = np.zeros(3, dtype=np.int64)
-        for i, (key, tr) in enumerate(self.trainers.items()):
-            x, score, score_bp, changed = tr.search_decode(n_samples=n_samples, seed=int(seed) + i)
+        for _, _, (_, score, score_bp, changed) in shapes:
             rose = score - score_bp > SEARCH_ROSE * np.maximum(1.0, np.abs(score))
             counts += np.array([len(score), int(rose.sum()), int(changed.sum())], dtype=np.int64)
-            for b, row in enumerate(self.buckets[key]['rows']):
-                guesses[row['index']] = (tuple(key[1]), [self.en[w] for w in x[b]], float(score[b]), float(score[b] - score_bp[b]))
-        tot = torch.tensor([float(v) for v in counts], dtype=torch.float64, device=self.device)
-        mdist.all_reduce_sum_(tot)
-        return guesses, tuple(int(v) for v in tot.cpu().numpy())
+        return guesses, tuple(int(v) for v in self._reduced(counts)[0])
 
     # ---- the ranked list of whole sets of guesses (include/mlbp_exactmbest.h) ---------------------------
     def exact_nbest(self, m):
@@ -1299,35 +1269,25 @@ class TiDirTrainer:
         m = int(m)
         if not 1 <= m <= K.MAX_M:
             raise ValueError('m must be in [1, %d]' % K.MAX_M)
-        n = self._shard[1] - self._shard[0]
-        per_sentence = [((), [], [], [])] * n
+        def ranked(r, b):
+            x, score, logp = r[:3]
+            have = int((x[b, :, 0] >= 0).sum())
+            return ([[self.en[w] for w in x[b, k]] for k in range(have)], [float(v) for v in score[b, :have]],
+                    [float(v) for v in logp[b, :have]])
+
+        skipped = []
+        per_sentence, shapes = self._per_shape(lambda i, tr: tr.exact_nbest(m), empty=((), [], [], []), placeholder=(None,) * 3,
+                                               refused=K.ExactMbestError, skipped=skipped, row=ranked)
         recall = np.zeros(m)
         seen = n_bp = 0
         covered_sum = 0.0
-        skipped = []
-        for key, tr in self.trainers.items():
-            rows = self.buckets[key]['rows']
-            try:
-                x, score, logp, covered, label_rank, bp_rank = tr.exact_nbest(m)
-            except K.ExactMbestError as e:
-                if e.code != _ffi.MLBP_EUNSUPPORTED:
-                    raise
-                skipped.append((tuple(key[1]), len(rows), str(e)))
-                for row in rows:
-                    per_sentence[row['index']] = (tuple(key[1]), None, None, None)
-                continue
+        for _, rows, (_, _, _, covered, label_rank, bp_rank) in shapes:
             seen += len(rows)
             n_bp += int((bp_rank >= 0).sum())
             covered_sum += float(covered.sum())
             for r in range(m):
                 recall[r] += int(((label_rank >= 0) & (label_rank <= r)).sum())
-            for b, row in enumerate(rows):
-                have = int((x[b, :, 0] >= 0).sum())
-                per_sentence[row['index']] = (tuple(key[1]), [[self.en[w] for w in x[b, r]] for r in range(have)],
-                                              [float(v) for v in score[b, :have]], [float(v) for v in logp[b, :have]])
-        tot = torch.tensor([float(seen), covered_sum, float(n_bp)] + [float(v) for v in recall], dtype=torch.float64, device=self.device)
-        mdist.all_reduce_sum_(tot)
-        tot = tot.cpu().numpy()
+        tot, _ = self._reduced([seen, covered_sum, n_bp] + list(recall))
         return per_sentence, (int(tot[0]), float(tot[1]), [int(v) for v in tot[3:]], int(tot[2])), skipped
 
     # ---- joint log-likelihood (log Z; the reference has only the sum of per-word log-marginals) ------
@@ -1337,18 +1297,13 @@ class TiDirTrainer:
         (UserGraphTrainer.joint_log_likelihood) and the sentence graph's log Z; an instance without a predicted word builds
         no graph and gives ((), 0.0, 0.0).  totals = (sum of joint_logp, sentences with a predicted word) over ALL ranks'
         instances, reduced once."""
-        n = self._shard[1] - self._shard[0]
-        per_instance = [((), 0.0, 0.0)] * n
+        per_instance, shapes = self._per_shape(lambda i, tr: tr.joint_log_likelihood(), empty=((), 0.0, 0.0),
+                                               row=lambda r, b: (float(r[0][b]), float(r[1][b])))
         total, seen = 0.0, 0
-        for key, tr in self.trainers.items():
-            joint, log_z = tr.joint_log_likelihood()
+        for _, _, (joint, _) in shapes:
             total += float(joint.sum())
             seen += joint.shape[0]
-            for b, row in enumerate(self.buckets[key]['rows']):
-                per_instance[row['index']] = (tuple(key[1]), float(joint[b]), float(log_z[b]))
-        tot = torch.tensor([total, float(seen)], dtype=torch.float64, device=self.device)
-        mdist.all_reduce_sum_(tot)
-        tot = tot.cpu().numpy()
+        tot, _ = self._reduced([total, seen])
         return per_instance, (float(tot[0]), int(tot[1]))
 
     # ---- prediction pass (train_mp.py:310-343, 692-770) -------------------------------------------
