@@ -40,7 +40,7 @@
  *     process-wide fallback blocks: until exit), so a HIP graph captured earlier keeps replaying against valid memory whatever
  *     later calls ask for.  A program keeps one device copy per DISTINCT group table (up to 64; beyond that the oldest copy is
  *     overwritten and a graph captured on it must be captured again);
- *   - mlbp_set_sweep_variant and the status words behind mlbp_gradient_status are process-wide.
+ *   - mlbp_set_sweep_variant, mlbp_set_lean_walk and the status words behind mlbp_gradient_status are process-wide.
  */
 #ifndef MLBP_H
 #define MLBP_H
@@ -361,6 +361,25 @@ int mlbp_sweep_groups_f64(const mlbp_program* const* progs, const mlbp_sweep_arg
  * independent updates and skips updates whose result is overwritten unread); they agree to rounding.  Other values
  * (the kernel generations retired in round 3) return MLBP_EINVAL. */
 int mlbp_set_sweep_variant(int32_t variant);
+
+/* The order in which a launch of the default X <= 64 kernel (MLBP_KERNEL_LEAN) takes the graphs of its batch.  A workgroup owns
+ * one graph and reads no other's, so the order changes no result, bit for bit; it decides which graphs the last-level cache
+ * still holds when the same batch is swept again.
+ *   0     default: forward, workgroup i takes graph i;
+ *   1     backward: workgroup i takes graph B - 1 - i (a grouped launch is reversed as a whole);
+ *   2     alternate.  Every program starts forward and turns after each launch of that kernel it enqueues, so two consecutive
+ *         calls on a resident batch meet at the turn, where the second could find the first one's last graphs in cache.
+ *         A grouped launch (mlbp_sweep_groups_f64) walks in the direction of the first program named and turns that one.
+ *         Not the default: the kernel reads its tables with non-temporal loads, which the last-level cache of the MI355X does
+ *         not keep, and behind them the turn measured no gain (with plain loads it gains 4-5 %, and plain loads cost 10-14 %).
+ * The direction is an argument of the launch: a launch recorded into a HIP graph keeps the direction it was recorded with on
+ * every replay (replays do not alternate; that is the forward walk's cost and no more).
+ * Process-wide and read once per public call, like mlbp_set_sweep_variant; other values return MLBP_EINVAL.
+ * mlbp_lean_walk: the mode.  mlbp_last_lean_walk: diagnostic, the direction (0 or 1) of the last such launch the calling thread
+ * enqueued; 0 before the first. */
+int mlbp_set_lean_walk(int32_t mode);
+int mlbp_lean_walk(void);
+int mlbp_last_lean_walk(void);
 
 /* Diagnostic: which kernel family the calling thread's last mlbp_sweep_f64 enqueued first (the exact
  * kernel may follow it for flagged graphs); -1 before the first call.  After mlbp_sweep_groups_f64: the family of the call's

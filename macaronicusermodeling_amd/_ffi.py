@@ -106,6 +106,9 @@ SIGNATURES = {
     'mlbp_lean_static_code': (C.c_int, [_i32p, _i32, C.c_char_p, _vp, _i32]),
     'mlbp_program_status': (C.c_int, [_vp]),
     'mlbp_set_sweep_variant': (C.c_int, [_i32]),
+    'mlbp_set_lean_walk': (C.c_int, [_i32]),
+    'mlbp_lean_walk': (C.c_int, []),
+    'mlbp_last_lean_walk': (C.c_int, []),
     'mlbp_sweep_f64': (C.c_int, [_vp, C.POINTER(SweepArgs), _vp]),
     'mlbp_sweep_groups_f64': (C.c_int, [C.POINTER(_vp), C.POINTER(SweepArgs), _i32, _vp]),
     'mlbp_init_messages_f64': (C.c_int, [_vp, _i64, _i32, _vp]),

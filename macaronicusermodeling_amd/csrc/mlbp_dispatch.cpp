@@ -16,6 +16,11 @@ namespace {
 // mlbp_set_sweep_variant: 1 = the fast kernels with the exact kernel as fix-up (default), 3 = the exact / per-graph
 // kernels on every graph (the tests' reference on the same inputs).
 int g_sweep_variant = 1;
+// mlbp_set_lean_walk: the order in which a lean launch's workgroups take the graphs -- 0 forward (default), 1 backward, 2 each
+// program's launches in alternate directions (measured, LAB_NOTES R32: no gain behind non-temporal table loads, so not the
+// default).  Read once per public call, like the variant.
+int g_lean_walk = 0;
+thread_local int g_last_lean_walk = 0;     // mlbp_last_lean_walk()
 thread_local int g_last_kernel = -1;       // mlbp_last_sweep_kernel()
 thread_local int g_last_fused_gradient = 0; // mlbp_last_sweep_fused_gradient()
 
@@ -107,7 +112,7 @@ int sweep_tail(mlbp_program* prog, const mlbp_sweep_args* a, const SweepTail& t,
 
 // X = 64 with the exact kernel applicable: the shared-table kernel, else the lean kernel (variant 1 and no fast pass run yet),
 // then the exact kernel -- on the graphs the fast pass flagged, or on every graph.
-int sweep_x64(mlbp_program* prog, const mlbp_sweep_args* a, FastPass pass, int variant, void* stream) {
+int sweep_x64(mlbp_program* prog, const mlbp_sweep_args* a, FastPass pass, int variant, int walk, void* stream) {
   const bool offer_fast = pass == FAST_NONE && variant == 1;      // variant 3: the exact kernel on every graph
   bool launched = false;
   if (offer_fast) {                               // shared-table batches: 16 graphs per workgroup on the matrix cores
@@ -125,7 +130,7 @@ int sweep_x64(mlbp_program* prog, const mlbp_sweep_args* a, FastPass pass, int v
   tail.grad_done = exact_grad && (pass != FAST_SHARED || shared_grad);
   tail.grad_flagged = shared_grad && !exact_grad;
   if (offer_fast && pass == FAST_NONE) {          // default path: the lean scale-free kernel (mlbp_lean.hip)
-    if (int e = mlbp::launch_lean_sweep(prog, a, tail.grad_done, stream, &launched)) return e;
+    if (int e = mlbp::launch_lean_sweep(prog, a, tail.grad_done, walk, stream, &launched, &g_last_lean_walk)) return e;
     if (launched) pass = FAST_LEAN;
   }
   g_last_kernel = pass == FAST_SHARED ? MLBP_KERNEL_SHARED_MFMA : (pass == FAST_LEAN ? MLBP_KERNEL_LEAN : MLBP_KERNEL_EXACT);
@@ -136,13 +141,13 @@ int sweep_x64(mlbp_program* prog, const mlbp_sweep_args* a, FastPass pass, int v
 
 // Every other state count (and X = 64 graphs too large for the exact kernel's LDS): the lean kernel on zero-padded vectors for
 // X < 64, the batched contractions for shared tables at X > 64, the wide kernel, the generic kernel.
-int sweep_other_x(mlbp_program* prog, const mlbp_sweep_args* a, int variant, void* stream) {
+int sweep_other_x(mlbp_program* prog, const mlbp_sweep_args* a, int variant, int walk, void* stream) {
   const bool fast = variant == 1;
   bool lean_small = false, launched = false;
   // small state spaces: the lean X = 64 kernel on zero-padded vectors and tables (it starts from uniform messages itself); the
   // graphs it flags are redone by the generic kernel in its fix-up mode
   if (fast && a->X < 64)
-    if (int e = mlbp::launch_lean_sweep(prog, a, false, stream, &lean_small)) return e;
+    if (int e = mlbp::launch_lean_sweep(prog, a, false, walk, stream, &lean_small, &g_last_lean_walk)) return e;
   if (a->init_messages && !lean_small)
     if (int e = mlbp_init_messages_f64(a->msgs, (int64_t)a->B * prog->n_msgs, a->X, stream)) return e;
   if (fast && !lean_small) {                      // shared tables at a large state space: every contraction one MFMA launch over the batch
@@ -161,11 +166,11 @@ int sweep_other_x(mlbp_program* prog, const mlbp_sweep_args* a, int variant, voi
 }
 
 // One sweep call of (prog, a) -- checked; prog the program it runs -- behind `pass` (FAST_NONE: the call runs its own).
-// variant: mlbp_set_sweep_variant's, read once per public call.
-int run_sweep(mlbp_program* prog, const mlbp_sweep_args* a, FastPass pass, int variant, void* stream) {
+// variant, walk: mlbp_set_sweep_variant's and mlbp_set_lean_walk's, read once per public call.
+int run_sweep(mlbp_program* prog, const mlbp_sweep_args* a, FastPass pass, int variant, int walk, void* stream) {
   g_last_fused_gradient = 0;
-  if (mlbp::exact_x64_applies(prog, a)) return sweep_x64(prog, a, pass, variant, stream);
-  return sweep_other_x(prog, a, variant, stream);
+  if (mlbp::exact_x64_applies(prog, a)) return sweep_x64(prog, a, pass, variant, walk, stream);
+  return sweep_other_x(prog, a, variant, walk, stream);
 }
 
 // Behind launch_shared_groups: every member's fix-up pass in ONE launch (and, when the call carries gradients, one launch of
@@ -203,7 +208,7 @@ int mlbp_sweep_f64(const mlbp_program* handle, const mlbp_sweep_args* a, void* s
   // (the handle is const in the ABI; a call updates the program's scratch and redo flags: one stream at a time per program)
   mlbp_program* prog = effective_program(const_cast<mlbp_program*>(handle), a);
   if (int e = check_sweep_args(prog, a)) return e;
-  return run_sweep(prog, a, FAST_NONE, g_sweep_variant, stream);
+  return run_sweep(prog, a, FAST_NONE, g_sweep_variant, g_lean_walk, stream);
 }
 
 int mlbp_sweep_groups_f64(const mlbp_program* const* handles, const mlbp_sweep_args* args, int32_t n_groups, void* stream) {
@@ -215,7 +220,7 @@ int mlbp_sweep_groups_f64(const mlbp_program* const* handles, const mlbp_sweep_a
     if (int e = check_sweep_args(eff[k], &args[k])) return e;
   }
   mlbp_program* const* progs = eff.data();
-  const int variant = g_sweep_variant;
+  const int variant = g_sweep_variant, walk = g_lean_walk;
   // The fast kernels take what they can, in this order: the shared-table launch sequence, then one grouped lean launch over the
   // groups left; each is followed by the fix-up pass over the graphs it flagged.  The rest run one after the other exactly as
   // separate calls would.  A program joins one grouped launch at most (with its first group): two groups would share one set of
@@ -233,17 +238,17 @@ int mlbp_sweep_groups_f64(const mlbp_program* const* handles, const mlbp_sweep_a
       if (int e = finish_shared_groups(progs, args, n_groups, shared, stream, &done)) return e;
       for (int k = 0; k < n_groups && !done; ++k)
         if (shared[k])
-          if (int e = run_sweep(progs[k], &args[k], FAST_SHARED, variant, stream)) return e;
+          if (int e = run_sweep(progs[k], &args[k], FAST_SHARED, variant, walk, stream)) return e;
     }
     for (int k = 0; k < n_groups; ++k) lean[k] = first[k] && !shared[k];      // (lean_plan takes no pairwise-free group)
-    if (int e = mlbp::launch_lean_groups(progs, args, n_groups, stream, lean)) return e;
+    if (int e = mlbp::launch_lean_groups(progs, args, n_groups, walk, stream, lean, &g_last_lean_walk)) return e;
     for (int k = 0; k < n_groups; ++k)
       if (lean[k])
-        if (int e = run_sweep(progs[k], &args[k], FAST_LEAN, variant, stream)) return e;
+        if (int e = run_sweep(progs[k], &args[k], FAST_LEAN, variant, walk, stream)) return e;
   }
   for (int k = 0; k < n_groups; ++k)
     if (!shared[k] && !lean[k])
-      if (int e = run_sweep(progs[k], &args[k], FAST_NONE, variant, stream)) return e;
+      if (int e = run_sweep(progs[k], &args[k], FAST_NONE, variant, walk, stream)) return e;
   return MLBP_OK;
 }
 
@@ -253,6 +258,14 @@ int mlbp_set_sweep_variant(int32_t variant) {
   g_sweep_variant = variant;
   return MLBP_OK;
 }
+
+int mlbp_set_lean_walk(int32_t mode) {
+  if (mode < 0 || mode > 2) return fail(MLBP_EINVAL, "unknown lean walk mode %d (0 forward, 1 backward, 2 alternate)", mode);
+  g_lean_walk = mode;
+  return MLBP_OK;
+}
+int mlbp_lean_walk(void) { return g_lean_walk; }
+int mlbp_last_lean_walk(void) { return g_last_lean_walk; }
 
 int mlbp_last_sweep_kernel(void) { return g_last_kernel; }
 int mlbp_last_sweep_fused_gradient(void) { return g_last_fused_gradient; }

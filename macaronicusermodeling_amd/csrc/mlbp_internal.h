@@ -110,10 +110,14 @@ bool build_lean_readout(const LeanProgram& lp, int n_msgs, int n_vars, const int
 // Enqueues the lean scale-free kernel when it applies (sets *launched); flagged graphs are left in prog->d_bail.
 // fuse_gradient: the call's gradient runs as the kernel's epilogue (P <= 3, every unary message hoisted, F = (3, 6): the caller
 // has asked exact_kernel_fuses_gradient).
-int launch_lean_sweep(mlbp_program* prog, const mlbp_sweep_args* a, bool fuse_gradient, void* stream, bool* launched);
+// walk_mode: mlbp_set_lean_walk's, read once per public call; *walk: the direction of the launch (0 forward, 1 backward), written
+// when one is enqueued.
+int launch_lean_sweep(mlbp_program* prog, const mlbp_sweep_args* a, bool fuse_gradient, int walk_mode, void* stream, bool* launched,
+                      int* walk);
 // The same for several (program, arguments) groups in one launch.  member: in, the groups offered; out, the groups launched
 // (a group that does not qualify is left out, not the call).
-int launch_lean_groups(mlbp_program* const* progs, const mlbp_sweep_args* args, int n_groups, void* stream, std::vector<char>& member);
+int launch_lean_groups(mlbp_program* const* progs, const mlbp_sweep_args* args, int n_groups, int walk_mode, void* stream,
+                       std::vector<char>& member, int* walk);
 
 // Run-time specialisation of the lean kernel (mlbp_lean_jit.cpp): the static kernel of ONE program -- its bundle words compiled
 // in -- as a loaded module.  state: 0 not tried, 1 in use, -1 tried and fell back (why); there is one attempt per program.
@@ -270,6 +274,7 @@ struct mlbp_program {
   mlbp::DeviceArray<int32_t> d_limage;   // LeanProgram::image
   mlbp::DeviceArray<int32_t> d_lreadout; // build_lean_readout
   mlbp::LeanJit jit;             // the program's static kernel, when it has one (mlbp_lean_jit.cpp)
+  int lean_walk_next = 0;        // the direction of the program's next lean launch under mlbp_set_lean_walk(2): turned by each one
   mlbp::GroupTables gtables;     // group tables of mlbp_sweep_groups_f64 calls that name this program first (launch_lean_groups)
   mlbp::GroupTables stables;     // the same for the shared-table kernels (launch_shared_groups)
   // shared-table form (mlbp_shared.hip); the scratch below is allocated on first use

@@ -58,11 +58,19 @@ static int lean_plan(mlbp_program* prog, const mlbp_sweep_args* a, bool grad, bo
   // is NOT fused reads them from memory)
   const bool waived = (a->flags & MLBP_SWEEP_NO_MESSAGE_WRITEBACK) && !padx && (a->marginals || grad) && (!a->gradient || grad);
   f->keep = waived ? 0 : 1;                       // (small X: the read-out is a separate launch over the messages)
+  f->walk = -1;                                   // (the launch sets it: lean_walk_word)
   *ok = true;
   return MLBP_OK;
 }
 
 typedef void (*lean_fn)(SweepDev, LeanDev, const int32_t*, int, GradFusedDev);
+
+// The direction of the next lean launch of `prog` (LeanDev::walk) under mlbp_set_lean_walk's mode, and -- behind the launch --
+// the turn: in mode 2 consecutive launches of a program walk its batch in opposite directions, so the graphs at the turn are
+// wanted again while the last-level cache still holds them.  The direction is a kernel argument: a captured launch keeps its own.
+static int lean_walk_of(const mlbp_program* prog, int mode) { return mode == 2 ? prog->lean_walk_next : mode; }
+static int32_t lean_walk_word(int dir, int n_graphs) { return dir ? n_graphs - 1 : -1; }      // LeanDev::walk of a launch of n_graphs
+static void lean_walk_turn(mlbp_program* prog, int mode) { if (mode == 2) prog->lean_walk_next ^= 1; }
 
 template <bool MULTI>
 static lean_fn pick_lean(int P, bool padx) {
@@ -94,7 +102,8 @@ static lean_fn pick_lean_grad(int P) {
   }
 }
 
-int launch_lean_sweep(mlbp_program* prog, const mlbp_sweep_args* a, bool fuse_gradient, void* stream, bool* launched) {
+int launch_lean_sweep(mlbp_program* prog, const mlbp_sweep_args* a, bool fuse_gradient, int walk_mode, void* stream, bool* launched,
+                      int* walk) {
   *launched = false;
   SweepDev d;
   LeanDev f;
@@ -102,6 +111,8 @@ int launch_lean_sweep(mlbp_program* prog, const mlbp_sweep_args* a, bool fuse_gr
   bool ok = false;
   if (int e = lean_plan(prog, a, fuse_gradient, &ok, &d, &f, &lds)) return e;
   if (!ok) return MLBP_OK;
+  const int dir = lean_walk_of(prog, walk_mode);
+  f.walk = lean_walk_word(dir, a->B);
   GradFusedDev gf = {};
   if (fuse_gradient) fill_grad_fused(a->gradient, &gf);
   // a single, non-gradient X = 64 call of a three-table program: the program's static kernel (mlbp_lean_jit.cpp) when it has
@@ -114,6 +125,8 @@ int launch_lean_sweep(mlbp_program* prog, const mlbp_sweep_args* a, bool fuse_gr
       launch_log_record(prog->jit.function);
       HIP_TRY(hipModuleLaunchKernel((hipFunction_t)prog->jit.function, a->B, 1, 1, WG, 1, 1, (unsigned)lds, (hipStream_t)stream, params, nullptr));
       if (int e = launch_verdict("static lean sweep")) return e;
+      lean_walk_turn(prog, walk_mode);
+      *walk = dir;
       *launched = true;
       return MLBP_OK;
     }
@@ -123,6 +136,8 @@ int launch_lean_sweep(mlbp_program* prog, const mlbp_sweep_args* a, bool fuse_gr
   launch_begin();
   MLBP_LAUNCH(k, dim3(a->B), dim3(WG), lds, (hipStream_t)stream, d, f, nullptr, 0, gf);
   if (int e = launch_verdict("lean sweep")) return e;
+  lean_walk_turn(prog, walk_mode);
+  *walk = dir;
   *launched = true;
   return MLBP_OK;
 }
@@ -132,7 +147,10 @@ int launch_lean_sweep(mlbp_program* prog, const mlbp_sweep_args* a, bool fuse_gr
 // of them (none: nothing is launched).  The group table lives in a device buffer owned by the FIRST program of the call (like
 // its redo flags: one stream at a time per program) and is uploaded only when its contents differ from the last call's, so a
 // repeated call -- the trainer's every step -- is enqueue-only and can be captured into a HIP graph after one warm-up call.
-int launch_lean_groups(mlbp_program* const* progs, const mlbp_sweep_args* args, int n_groups, void* stream, std::vector<char>& member) {
+// The launch walks in the FIRST program's direction (mlbp_set_lean_walk) and turns that program alone.  *walk: the direction
+// launched, left alone when nothing is.
+int launch_lean_groups(mlbp_program* const* progs, const mlbp_sweep_args* args, int n_groups, int walk_mode, void* stream,
+                       std::vector<char>& member, int* walk) {
   std::vector<int32_t> table;
   size_t lds_max = 0;
   int p_max = 0, total = 0, n_in = 0;
@@ -170,9 +188,14 @@ int launch_lean_groups(mlbp_program* const* progs, const mlbp_sweep_args* args, 
   if (int e = group_table_device(progs[0]->gtables, table, stream, &d_gtable)) return e;
   lean_fn k = pick_lean<true>(p_max, false);
   if (int e = grant_lds((const void*)k, lds_max)) return e;
+  const int dir = lean_walk_of(progs[0], walk_mode);
+  f0.walk = lean_walk_word(dir, total);
   launch_begin();
   MLBP_LAUNCH(k, dim3(total), dim3(WG), lds_max, (hipStream_t)stream, d0, f0, d_gtable, n_in, GradFusedDev{});
-  return launch_verdict("grouped lean sweep");
+  if (int e = launch_verdict("grouped lean sweep")) return e;
+  lean_walk_turn(progs[0], walk_mode);
+  *walk = dir;
+  return MLBP_OK;
 }
 
 }  // namespace mlbp

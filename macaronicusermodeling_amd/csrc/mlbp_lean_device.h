@@ -31,11 +31,14 @@ namespace {
 
 constexpr int WG = 256;
 
-// Per-graph pairwise tables are read once: non-temporal loads, 12.5 -> 13.0 k iterations/s on the default workload.  (The
-// write-back and marginals by non-temporal stores had no measured effect; the unary rows stay plain loads.)  An immediately
+// Per-graph pairwise tables are read once: non-temporal loads, 12.5 -> 13.0 k iterations/s on the default workload (R4.12; plain
+// loads in their place cost 10-14 % on today's kernel, LAB_NOTES R32).  The unary rows stay plain loads.  An immediately
 // invoked lambda: as a __forceinline__ function the same load leaves the kernels with a different register allocation.
 typedef double nt_d2 __attribute__((ext_vector_type(2)));
 #define NT_LOAD2(p) ([&] { const nt_d2 v_ = __builtin_nontemporal_load(reinterpret_cast<const nt_d2*>(p)); return make_double2(v_.x, v_.y); }())
+// The X = 64 message write-back and the marginals of the first eight variables: written once, next read by another launch.
+// Non-temporal stores: 2-3 % on the default workload (LAB_NOTES R32; no effect on the kernel of R4.12).
+#define NT_STORE2(p, v) ([&] { nt_d2 x_; x_.x = (v).x; x_.y = (v).y; __builtin_nontemporal_store(x_, reinterpret_cast<nt_d2*>(p)); }())
 
 constexpr int GROUP_WORDS = 48;     // one group descriptor of a MULTI launch (see launch_lean_groups)
 // (micro-op words and the UOP_* bits of word 0: mlbp_internal.h, shared with build_lean_program in mlbp_compile.cpp)
@@ -47,6 +50,8 @@ struct LeanDev {
   const int32_t* readout; // [n_vars][16]: count, base slot, varying slots... (build_lean_readout) or NULL
   uint8_t* bail;          // [B]
   int32_t n_bundles, HL, n_cprod, WL, n_ext, init, dense, keep;
+  int32_t walk;           // -1: workgroup i takes graph i; else the launch's last graph L, and workgroup i takes graph L - i: the
+                          // launch walks the batch backward (mlbp_set_lean_walk)
 };
 
 // a' = [a.row0, b.row0, a.row2, b.row2], b' = [a.row1, b.row1, a.row3, b.row3] (rows of 16 lanes); a' + b'
@@ -690,7 +695,9 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
                                                                                              int n_groups, GradFusedDev gf) {
   constexpr bool STATIC = false;
 #endif
-  int g = blockIdx.x;
+  // (a workgroup owns its graph and reads no other's: which one it takes changes the order the batch streams in, and no result.
+  // Ahead of the group look-up, so a grouped launch is reversed as a whole)
+  int g = f.walk < 0 ? (int)blockIdx.x : f.walk - (int)blockIdx.x;
   if (MULTI) {
     // groups[k * GROUP_WORDS] = first graph of group k (ascending): the last k with start <= g
     int lo = 0, hi = n_groups - 1;
@@ -1191,7 +1198,7 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
   if (f.keep && !PADX) {
     const double2* src = reinterpret_cast<const double2*>(work);
     double2* dst = reinterpret_cast<double2*>(gm);
-    for (int i = t; i < d.n_msgs * 32; i += WG) dst[i] = src[i];
+    for (int i = t; i < d.n_msgs * 32; i += WG) NT_STORE2(dst + i, src[i]);
   } else if (f.keep) {
     for (int i = t; i < d.n_msgs * 64; i += WG)
       if ((i & 63) < X) gm[(size_t)(i >> 6) * X + (i & 63)] = work[i];
@@ -1200,7 +1207,7 @@ __global__ __launch_bounds__(WG, (NT >= 7 ? 1 : (NT >= 4 ? 2 : 3))) void sweep_x
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int v = wave + 4 * j;
-      if (v < d.n_vars) d.marginals[((size_t)g * d.n_vars + v) * 64 + lane] = marg[j];
+      if (v < d.n_vars) __builtin_nontemporal_store(marg[j], &d.marginals[((size_t)g * d.n_vars + v) * 64 + lane]);
     }
   }
   if (GRAD) {                 // (the verdict barrier above has published the final normalisation)

@@ -12,7 +12,7 @@ import sys
 from collections import defaultdict
 
 
-KERNELS = ['sweep_x64_lean_kernel', 'sweep_x64_sf_kernel', 'sweep_x64_fused_kernel', 'sweep_x64_shared_kernel', 'sweep_wide_kernel', 'sweep_generic_kernel',
+KERNELS = ['sweep_x64_lean_kernel', 'sweep_x64_lean_static_kernel', 'sweep_x64_sf_kernel', 'sweep_x64_fused_kernel', 'sweep_x64_shared_kernel', 'sweep_wide_kernel', 'sweep_generic_kernel',
            'sweep_x64_kernel', 'unary_writeback_kernel', 'table_fragments_kernel']
 
 
