@@ -65,8 +65,43 @@
  * as mlbp_cutset.h gives it; every other graph keeps its bits.  A uniform outside [0, 1) or NaN still draws a state in range.
  * Limits: X^n_cut <= MLBP_CUTSET_MAX_CONFIGS, X <= MLBP_CUTSET_MAX_X (MLBP_EUNSUPPORTED beyond).
  *
- * Not done: a `given=` argument (clamped variables); float32 tables; one grouped launch over several shapes; cutsets beyond
- * MLBP_CUTSET_MAX_CONFIGS configurations.
+ * THE LISTED MODE (N > 0): draws for the graphs whose cutset has more than MLBP_CUTSET_MAX_CONFIGS configurations, by
+ * sampling-importance-resampling over a caller's LIST of cutset states.  The caller lists N joint states of the cutset per
+ * graph, configs[g][i][q] = the state of cut position q in entry i, with log_q[g][i] = the natural logarithm of the probability
+ * a proposal gave that state (mlbp_cutsetis.h takes the same list; mlbp_cutdraw.h makes one).  N == 0 is the exact call above,
+ * whatever configs, log_q, entry and ess hold: they are not looked at.  In a listed call the plan is the one
+ * mlbp_cutsetis_check_plan admits: at most 16 cutset variables and no bound on X^n_cut.
+ *   1'. Weights.  Entry i has w_i = Z_{c_i} * exp(-log_q[i]), Z_c of the entry's states as above and exp(-log_q) = r 2^k by THE
+ *      formula of mlbp_cutsetis.h: k = rint(-log_q / ln 2), r = exp(-log_q - k ln 2); the product's mantissa is brought back to
+ *      [1, 2).  Every weight is kept apart as a (mantissa, exponent) pair; none is merged with another before the scan.
+ *   2'. Scan.  E = the largest exponent of a positive weight; w_i under E with the floor of step 1 (2^-4000); W_i = their
+ *      SEGMENTED prefix sums over n = N, in list order.  log_z reads log_z_hat = E ln 2 + log(W_last / N), the estimate of
+ *      mlbp_cutsetis.h (-inf when W_last == 0).  ess = W_last^2 / sum of w_i^2 under the same E (the squares of a thread's
+ *      segment added left to right, the segments' sums in order; 0 when W_last == 0): the effective size of the list, N when
+ *      every weight is equal.
+ *   3'. Draw.  uniforms[s][g][0] picks the entry by the draw rule on w: entry i with probability w_i / W_last; an entry of
+ *      weight zero is never drawn; the list may repeat a state.  The cutset variables take the entry's row of configs, the
+ *      free variables are drawn as in step 2 from uniforms[s][g][n_cut + k].  logp = log(w_i / W_last) + the sum of the
+ *      logarithms of the conditionals: the log-probability of the draw GIVEN THE LIST and the entry, so that
+ *          logp = score - log_q[entry] - (log_z_hat + log N)     up to rounding,
+ *      and score - log_z_hat is the estimate of log p(x) of the draw.  entry[s][g] is the drawn index.
+ *   n_cut == 0: every entry is the one empty configuration; configs is not read, entry 0 is reported, no uniform is spent on
+ *      it and samples and logp are the exact call's; log_z_hat and ess come from the listed weights.
+ * The draws follow sum_i (w_i / W_last) p(x | c_i), which tends to the model as N grows for a proposal that is positive
+ * wherever Z_c is; ess says how far the list is from that.  With the full list in index order and log_q = 0 every bit of
+ * samples, logp and score is the exact call's, and log_z_hat = log_z - log N.
+ * Edge rules of a listed call.  A state outside [0, X), a log_q that is not finite or beyond MLBP_CUTSETIS_MAX_ABS_LOG_Q in
+ * magnitude, a table index outside its array: the entry's weight is marked with a NaN mantissa -- it is never used as an index
+ * -- and the graph is refused alone: samples -1, entry -1, logp, score, log_z_hat and ess NaN.  Every listed weight zero:
+ * samples -1, entry -1, logp and score NaN, log_z_hat = -inf, ess = 0.  A weight that is no finite number (a NaN or +inf table
+ * entry): samples -1, entry -1, logp and score NaN, log_z_hat and ess no finite numbers.  Every other graph keeps its bits.
+ * Determinism of a listed call.  The bits of every output are a function of the graph, the cutset, the list and the sample's
+ * uniforms alone -- not of B, S, the graph's position in the batch or the grid.  A table times 2^k changes no sample and no bit
+ * of logp, entry or ess.
+ *
+ * Not done: a `given=` argument (clamped variables); float32 tables; one grouped launch over several shapes; the MODEL'S OWN
+ * distribution for cutsets beyond MLBP_CUTSET_MAX_CONFIGS configurations -- the listed mode draws from its estimate over a
+ * list; a list made inside the call.
  */
 #ifndef MLBP_EXACTSAMPLE_H
 #define MLBP_EXACTSAMPLE_H
@@ -98,6 +133,8 @@ extern "C" {
  *                                    in LDS when (5 n_vars + 2) * round_up(X, 2) * 8 + 64 + INTS <=
  *                                    MLBP_CUTSET_GENERIC_LDS_BYTES, else in the caller's workspace.
  * exactsample_scan_kernel, one workgroup per graph, brings the Z_c to the graph's largest exponent, scans them and writes log_z.
+ * A listed call enqueues the same three launches of the same five kernels with n_configs = N: the weights kernels walk the
+ * list's entries in a loop of their own, the scan adds ess, the draw kernels read the drawn entry's row.
  *
  * Grids.  With chunks(B, n) = mlbp_exactsample_chunks(B, n) = min(n, ceil(MLBP_CUTSET_MIN_WORKGROUPS / B)):
  *   weights pass  (B, Cw), Cw = chunks(B, n_configs): workgroup (g, k) of the generic kernel walks configurations k, k + Cw, ...,
@@ -109,6 +146,7 @@ extern "C" {
 #define MLBP_EXACTSAMPLE_KERNEL_X64 1
 #define MLBP_EXACTSAMPLE_KERNEL_GENERIC 2
 #define MLBP_EXACTSAMPLE_HEAD 4              /* doubles per graph between the scan and the draw pass */
+#define MLBP_EXACTSAMPLE_MAX_LISTED 65536    /* the most entries a listed call takes per graph */
 
 typedef struct mlbp_exactsample_args {
   int32_t B, X, n_vars, P, U;                /* graphs, states, variables, pairwise / unary factors */
@@ -116,21 +154,28 @@ typedef struct mlbp_exactsample_args {
   int32_t n_pair_tables, n_unary_tables;
   int32_t plan_words;
   int32_t S;                                 /* samples per graph */
+  int32_t N;                                 /* 0: the exact call; 1 .. MLBP_EXACTSAMPLE_MAX_LISTED: entries listed per graph */
   const int32_t* plan;                       /* device [plan_words], validated by mlbp_exactsample_check_plan before upload */
   const double* pair_tables;                 /* device [n_pair_tables][X][X] row-major (NULL when P == 0) */
   const int32_t* pair_tab;                   /* device [B][P] table of graph g's pairwise factor p */
   const double* unary_tables;                /* device [n_unary_tables][X] (NULL when U == 0) */
   const int32_t* unary_tab;                  /* device [B][U] */
   const double* uniforms;                    /* device [S][B][n_vars], each in [0, 1) */
+  const int32_t* configs;                    /* listed: device [B][N][n_cut] (NULL when n_cut == 0) */
+  const double* log_q;                       /* listed: device [B][N] */
   double* workspace;                         /* device, workspace_bytes >= mlbp_exactsample_workspace_bytes(...) */
   int64_t workspace_bytes;
   int32_t* samples;                          /* device [S][B][n_vars] */
   double* logp;                              /* device [S][B] */
   double* log_z;                             /* optional device [B] */
   double* score;                             /* optional device [S][B] */
+  int32_t* entry;                            /* listed, optional: device [S][B] the drawn entry */
+  double* ess;                               /* listed, optional: device [B] */
 } mlbp_exactsample_args;
 
-/* Table indices are device data and are not checked on the host: see the edge rules above. */
+/* Table indices, and a list's states and log_q, are device data and are not checked on the host: see the edge rules above.
+ * Host checks of a listed call: N in [1, MLBP_EXACTSAMPLE_MAX_LISTED] (MLBP_EINVAL), configs non-NULL when n_cut > 0, log_q
+ * non-NULL, n_cut <= 16 (MLBP_EUNSUPPORTED), the workspace. */
 int mlbp_exactsample_f64(const mlbp_exactsample_args* args, void* stream);
 
 /* Host only, no GPU needed: the checks of mlbp_cutset_check_plan, with its messages. */
@@ -147,7 +192,9 @@ int mlbp_exactsample_chunks(int32_t B, int32_t n);
  *   + B * MLBP_EXACTSAMPLE_HEAD                           per graph {E, W_last, usable, 0}
  *   + B * max(Cw, Cd) * (5 n_vars + 2) * round_up(X, 2)   when the generic kernels keep their vectors there
  * with n_configs = X^n_cut and Cw, Cd as above; a negative status as pick_kernel / chunks give it, MLBP_EINVAL for S <= 0,
- * MLBP_EUNSUPPORTED above MLBP_CUTSET_MAX_CONFIGS. */
+ * MLBP_EUNSUPPORTED above MLBP_CUTSET_MAX_CONFIGS.  This is the exact call's; a LISTED call needs the same sum with N in the
+ * place of n_configs -- B * N * 3 + B * MLBP_EXACTSAMPLE_HEAD {E, W_last, usable, sum of w^2} + the vectors' share with
+ * Cw = chunks(B, N) -- which the compute entry checks (the binding states it: exactsample.listed_workspace_bytes). */
 int64_t mlbp_exactsample_workspace_bytes(int32_t B, int32_t S, int32_t X, int32_t n_vars, int32_t P, int32_t U, int32_t n_forest,
                                          int32_t n_cut);
 

@@ -878,6 +878,86 @@ class FactorGraphBatch:
         K.check(K.lib.mlbp_exactsample_f64(C.byref(a), _stream_ptr(self.device)))
         return tuple(out)
 
+    # ---- draws beyond the exact limit: resampling listed cutset states (the listed mode of include/mlbp_exactsample.h) ----
+    def cutset_resample(self, configs, log_q, n_samples=1, seed=None, uniforms=None, cutset=None, log_z=False, score=False,
+                        entry=False, ess=False):
+        """Draws n_samples whole assignments per graph by sampling-importance-resampling over a LIST of cutset states -- for
+        the graphs whose cutset has more joint states than exact_sample() walks (more than 65536: K5 and up at X = 64).
+        configs: contiguous int32 [B][N][n_cut] device tensor, configs[b][i][q] the state of cutset variable q (cutset order)
+        in entry i; log_q: contiguous float64 [B][N], the natural log of the probability a proposal gave each entry -- the
+        list cutset_draw() and cutset_proposal() return and cutset_estimate() takes; 1 <= N <= 65536.  For every entry the
+        conditioned forest is solved exactly and weighted by w_i = Z_c / q(c_i); a draw picks entry i with probability
+        w_i / sum w, sets the cutset variables to its row and draws the free variables from the conditioned forest exactly, as
+        exact_sample() does.  Returns (samples int32 [S][B][n_vars], logp float64 [S][B]) device tensors, then with log_z=True
+        log_z_hat [B] (cutset_estimate()'s estimate of log Z on the same list), with score=True the log-potential of every
+        draw [S][B], with entry=True the drawn entry's index int32 [S][B], with ess=True the effective size of the list [B],
+        in that order.  logp is the log-probability of the draw GIVEN THE LIST and the entry: logp = score - log_q[entry] -
+        (log_z_hat + log N) up to rounding; score - log_z_hat estimates log p(x).  The draws follow a distribution that tends
+        to the model's as N grows; ess says how close the list is.  With the full list in index order and log_q = 0 the
+        samples, logp and score are exact_sample()'s bits.  Exactly one of `seed` and `uniforms`, as in exact_sample():
+        uniforms [S][B][n_vars], entry 0 picks the list entry, entries n_cut.. draw the free variables.  A graph with a state
+        outside [0, X) or a log_q that is not finite gets samples -1, entry -1 and NaN; one whose listed weights are all
+        zero samples -1, logp NaN, log_z_hat -inf, ess 0.  The list may repeat a state.  cutset: as in exact_inference; at
+        most 16 variables, no limit on X^len(cutset).  On a tree configs is [B][N][0].  self.msgs is neither read nor
+        written."""
+        from . import cutsetis as KP, exactsample as K
+        _exactly_one(seed, uniforms)
+        topo, S = self.topo, int(n_samples)
+        if S <= 0:
+            raise ValueError('n_samples must be positive')
+        pl, a = self._cutset_args(KP, K.ExactSampleArgs, cutset, 'cutset_resample needs float64 pairwise tables')   # the listed check of the plan
+        a.log_q = self._tensor(log_q, (self.B, None), 'log_q', '[B][N]')
+        a.N = N = _listed_count(log_q.shape[1], K, 'N')
+        configs_ptr = self._tensor(configs, (self.B, N, pl.n_cut), 'configs', '[B][N][n_cut]', dtype=torch.int32)
+        if pl.n_cut:
+            a.configs = configs_ptr
+        uniforms = self._uniforms(seed, uniforms, (S, self.B, topo.n_vars), '[n_samples][B][n_vars]')
+        a.S, a.uniforms = S, uniforms.data_ptr()
+        samples = torch.empty(S, self.B, topo.n_vars, dtype=torch.int32, device=self.device)
+        logp = torch.empty(S, self.B, dtype=torch.float64, device=self.device)
+        a.samples, a.logp = samples.data_ptr(), logp.data_ptr()
+        out = [samples, logp]
+        if log_z:
+            out.append(torch.empty(self.B, dtype=torch.float64, device=self.device))
+            a.log_z = out[-1].data_ptr()
+        if score:
+            out.append(torch.empty(S, self.B, dtype=torch.float64, device=self.device))
+            a.score = out[-1].data_ptr()
+        if entry:
+            out.append(torch.empty(S, self.B, dtype=torch.int32, device=self.device))
+            a.entry = out[-1].data_ptr()
+        if ess:
+            out.append(torch.empty(self.B, dtype=torch.float64, device=self.device))
+            a.ess = out[-1].data_ptr()
+        work = self._workspace(a, K.listed_workspace_bytes(self.B, S, self.X, topo.n_vars, topo.P, topo.U, pl.n_forest, N))
+        K.check(K.lib.mlbp_exactsample_f64(C.byref(a), _stream_ptr(self.device)))
+        return tuple(out)
+
+    def estimate_sample(self, roots=None, n_samples=1, n_list=256, seed=0, cutset=None, proposal='messages'):
+        """Whole sets of guesses for the sentences beyond exact_sample()'s limit: cutset_resample() over a list of n_list
+        cutset states drawn from loopy BP.  proposal='messages' makes the list with cutset_draw(n_list, seed=seed) on the
+        messages self.msgs holds; given `roots`, sweep(roots, init=True) runs first -- THAT WRITES self.msgs --, with roots=None
+        the messages are used as they stand.  proposal='sample' makes it with cutset_proposal(roots, n_list, seed=seed), which
+        needs roots and sweeps for every draw.  The draws' uniforms are torch.rand((n_samples, B, n_vars), dtype=float64,
+        device=..., generator=torch.Generator(device).manual_seed(seed + 1)).  Returns (samples int32 [S][B][n_vars],
+        logp_hat float64 [S][B], log_z_hat [B], ess [B]) device tensors: logp_hat = score - log_z_hat, the estimate of the
+        log-probability of every draw under the model (its error is log_z_hat's, the same for every draw of a graph);
+        ess / n_list near 1 says the list stands in well for the cutset's distribution."""
+        if proposal not in ('sample', 'messages'):
+            raise ValueError("proposal must be 'sample' or 'messages', not %r" % (proposal,))
+        if proposal == 'sample':
+            if roots is None:
+                raise ValueError("proposal='sample' needs roots")
+            configs, log_q = self.cutset_proposal(roots, n_list, seed=int(seed), cutset=cutset)
+        else:
+            self._cutdraw_refuse('estimate_sample')
+            if roots is not None:
+                self.sweep(roots, init=True)
+            configs, log_q = self.cutset_draw(n_list, seed=int(seed), cutset=cutset)
+        samples, _, log_z_hat, score, ess = self.cutset_resample(configs, log_q, n_samples=n_samples, seed=int(seed) + 1, cutset=cutset,
+                                                                 log_z=True, score=True, ess=True)
+        return samples, score - log_z_hat.unsqueeze(0), log_z_hat, ess
+
     # ---- the exact pair marginals and the true gradient (include/mlbp_exactgrad.h) ---------------------
     def _exactgrad(self, cutset, marginals=None, pair_marginals=None, expect=None, grad=None, labels=None):
         """One mlbp_exactgrad_f64 call: log_z [B], and whichever of the optional outputs is given (expect, grad: (ee, ed))."""

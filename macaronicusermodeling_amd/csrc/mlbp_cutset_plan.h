@@ -79,6 +79,16 @@ __device__ __forceinline__ void mul(Scaled& z, double v) {
   z.e += e;
 }
 
+// The weight of a listed entry, Z_c exp(-log_q), by the formula of include/mlbp_cutsetis.h: exp(-log_q) = r 2^k,
+// k = rint(-log_q / ln 2), r = exp(-log_q - k ln 2).  log_q = 0 leaves z as it is.
+__device__ __forceinline__ Scaled weighted(Scaled z, double lq) {
+  constexpr double ln2 = 0.693147180559945309417232121458;
+  const double k = rint(-lq / ln2);
+  mul(z, exp(-lq - k * ln2));
+  z.e += (int)k;
+  return z;
+}
+
 // Max over the workgroup of non-negative values, the same bits in every thread (a NaN is passed over); two barriers.
 __device__ __forceinline__ double block_max(double v, double* scratch /*[4]*/) {
   v = wave_max(v);

@@ -204,6 +204,12 @@ struct ListedStates {
   const_i32p row;                            // [n_cut], checked against [0, X) by the caller
   __device__ __forceinline__ int operator()(int q) const { return row[q]; }
 };
+// A listed entry in the X = 64 walk: lane q of `packed` holds the state of cut position q -- the entry's row in one coalesced
+// load, checked against [0, 64) by a ballot of the caller -- and a position's state is one v_readlane, a scalar as X64Code's.
+struct X64Packed {
+  int packed;
+  __device__ __forceinline__ int operator()(int q) const { return __builtin_amdgcn_readlane(packed, q); }
+};
 
 // A configuration, leaves to roots: returns Z_c (V_c); st holds the configuration's states, bel[v] is left holding every free
 // variable's rescaled upward vector, up (unless NULL) its rescaled message to its parent.  Reached by every thread; the first

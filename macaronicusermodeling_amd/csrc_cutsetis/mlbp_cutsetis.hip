@@ -45,14 +45,7 @@ __device__ __forceinline__ bool entry_ok(const_i32p row, int n_cut, int X, doubl
   return ok;
 }
 
-// Z_c exp(-log_q) by the header's formula: exp(-log_q) = r 2^k, k = rint(-log_q / ln 2), r = exp(-log_q - k ln 2).
-__device__ __forceinline__ Scaled weighted(Scaled z, double lq) {
-  const double k = rint(-lq / LN2);
-  mul(z, exp(-lq - k * LN2));
-  z.e += (int)k;
-  return z;
-}
-
+// Z_c exp(-log_q) by the header's formula: weighted() of csrc/mlbp_cutset_plan.h.
 __device__ __forceinline__ double log_of(const Scaled& w) { return fma((double)w.e, LN2, log(w.m)); }
 
 // A graph whose table indices are out of range is not walked: its log_w reads NaN.

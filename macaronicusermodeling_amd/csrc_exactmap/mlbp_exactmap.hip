@@ -60,14 +60,9 @@ __device__ __forceinline__ bool row_in_range(const_i32p row, int n_cut, int X) {
   return ok;
 }
 
-// The states of a listed entry in the X = 64 walk: lane q of `packed` holds the state of cut position q -- the entry's row in
-// one coalesced load -- and a position's state is one v_readlane, a scalar as X64Code's.  The listed loop is a call site of its
+// The states of a listed entry in the X = 64 walk: X64Packed of csrc/mlbp_cutset_walk.h.  The listed loop is a call site of its
 // own: with the exact loop's source as it was, exact_map() keeps its time (one call site for both cost it 1 to 4 %).  With
 // ListedStates (scalar loads of the row) the second call site cost the instance a wave of occupancy: 106 scalar registers.
-struct X64Packed {
-  int packed;
-  __device__ __forceinline__ int operator()(int q) const { return __builtin_amdgcn_readlane(packed, q); }
-};
 
 // The best configuration so far: V = m * 2^e at configuration c; c < 0: nothing yet; m = 0: V is zero (or no number).
 struct Best { double m; int e; int c; };

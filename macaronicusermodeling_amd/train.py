@@ -324,6 +324,18 @@ class UserGraphTrainer:
         samples, logp = self.batch.exact_sample(n_samples=n_samples, seed=seed, uniforms=uniforms)
         return samples.cpu().numpy().astype(np.int64), logp.cpu().numpy()
 
+    def estimated_sample(self, n_samples, n_list=256, seed=0, proposal='messages'):
+        """The sentence shapes exact_sample() refuses: whole sets of guesses drawn by resampling a list of n_list cutset states
+        under the current thetas (FactorGraphBatch.estimate_sample over the predict() schedule, which writes the batch's
+        messages): host (samples int64 [S][B][n_vars] word indices in var_ids order, logp_hat float64 [S][B] -- the estimate
+        score - log_z_hat of each draw's log-probability --, log_z_hat float64 [B], ess float64 [B] -- the effective size of
+        the list out of n_list).  proposal: 'messages' or 'sample', as FactorGraphBatch.estimate_sample takes it.  Raises
+        cutsetis.CutsetisError(MLBP_EUNSUPPORTED) for a shape the listed plan refuses (more than 16 cutset variables)."""
+        self.build_potentials()
+        samples, logp_hat, log_z_hat, ess = self.batch.estimate_sample(self.roots[:self.n_sweeps_run], n_samples=n_samples, n_list=n_list,
+                                                                       seed=seed, proposal=proposal)
+        return (samples.cpu().numpy().astype(np.int64),) + _host(logp_hat, log_z_hat, ess)
+
     def convergence(self, tol=1e-6, max_rounds=50):
         """What stopping at the trainer's own n_sweeps_run sweeps cost each instance, under the current thetas: host (rounds
         int32 [B], residual float64 [B], gap float64 [B]).  rounds and residual are FactorGraphBatch.converge's over rounds of
@@ -1063,6 +1075,25 @@ class TiDirTrainer:
         skipped = []
         per_instance, _ = self._per_shape(lambda i, tr: tr.exact_sample(n_samples=n_samples, seed=int(seed) + i), empty=((), [], []),
                                           row=self._draws_row, placeholder=(None, None), refused=K.ExactSampleError, skipped=skipped)
+        return per_instance, skipped
+
+    # ---- and draws for the longer sentences (the listed mode of include/mlbp_exactsample.h) ---------------------------------
+    def estimated_sample(self, n_samples=1, n_list=256, seed=0):
+        """-> (per_instance, skipped).  per_instance[i], for instance i of this rank's shard in file order: (predicted
+        positions, [[en words] per sample], [logp_hat per sample], ess / n_list) -- n_samples whole sets of guesses drawn for
+        the sentence by resampling a list of n_list cutset states (UserGraphTrainer.estimated_sample), the estimate of each
+        draw's log-probability and the share of the list that is effective; the shapes exact_sample() skips for their size
+        -- five and more predicted words -- are INCLUDED.  An instance without a predicted word builds no graph and gives
+        ((), [], [], None), one of a shape the listed plan refuses (positions, None, None, None).  The i-th sentence shape in
+        self.trainers order draws with seed `seed + 2 i` for its list and `seed + 2 i + 1` for its draws.  skipped:
+        [(predicted positions, instances, reason)] of this rank's shapes the listed plan refuses (more than 16 cutset
+        variables) -- none for the configuration limit.  Every rank draws for its own shard: nothing is reduced."""
+        from . import cutsetis as K
+        skipped = []
+        per_instance, _ = self._per_shape(
+            lambda i, tr: tr.estimated_sample(n_samples, n_list=n_list, seed=int(seed) + 2 * i), empty=((), [], [], None),
+            row=lambda r, b: self._draws_row(r[:2], b) + (float(r[3][b]) / float(n_list),), placeholder=(None, None, None),
+            refused=K.CutsetisError, skipped=skipped)
         return per_instance, skipped
 
     # ---- sweeps to convergence (the reference stops at three sweeps and never looks) -------------------

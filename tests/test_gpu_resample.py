@@ -1,0 +1,419 @@
+"""Draws beyond the exact limit on the GPU: the listed mode of libmlbp_exactsample.so (FactorGraphBatch.cutset_resample,
+estimate_sample and the trainers' estimated_sample) against the NumPy statement of tests/test_resample_cpu.py, against
+exact_sample() where the list is the full one, and against cutset_estimate() on the same list.
+
+Bars.  Samples and entries are compared exactly with the statement's: every input whose samples are compared is listed in
+test_resample_cpu.INPUTS, where the statement's smallest margin is asserted to be at least 1e-8 before any device is involved,
+none left out; the inputs built here assert theirs before the device's answer is looked at.  logp, log_z_hat and score:
+rtol 1e-10, the project's tolerance for sums taken in another order; ess: 1e-10 relative.  Bit-for-bit claims are the
+header's: the full list with log_q = 0 is exact_sample(); a graph's bits do not depend on B, S, its position or the grid; a
+table times 2^k moves no bit of samples, logp, entry or ess; exact_sample() itself computes what it computed before the listed
+mode existed (tests/golden/exactsample_exact_bits.json, recorded on the library as it was).  No test asserts a statistical
+accuracy."""
+import json
+import os
+
+import numpy as np
+import pytest
+
+import cases as C
+import test_cutset_cpu as R
+import test_cutsetis_cpu as K
+import test_exactsample_cpu as E
+import test_resample_cpu as L
+from helpers import batch_tables, tidir_gold, write_tidir
+from oracle import lbp_oracle as O
+
+torch = pytest.importorskip('torch')
+pytestmark = pytest.mark.gpu
+
+X64, GENERIC = 1, 2
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'exactsample_exact_bits.json')
+
+
+def _M():
+    from macaronicusermodeling_amd import exactsample
+    return exactsample
+
+
+def _batch(spec, inputs_list, tables=None, pair_tab=None, unary_tab=None, B=None):
+    from macaronicusermodeling_amd.batch import FactorGraphBatch
+    from macaronicusermodeling_amd.topology import GraphTopology
+    topo = GraphTopology.from_spec(spec)
+    assert topo.var_ids == O.Graph(spec).var_order
+    fb = FactorGraphBatch(topo, spec['X'], len(inputs_list) if B is None else B)
+    pair, unary = batch_tables(spec, topo, inputs_list) if tables is None else tables
+    if topo.P:
+        fb.set_pair_tables(pair, pair_tab)
+    if topo.U:
+        fb.set_unary_tables(unary, unary_tab)
+    return fb
+
+
+def _dev(fb, a, dtype=None):
+    return torch.from_numpy(np.ascontiguousarray(a if dtype is None else np.asarray(a).astype(dtype))).to(fb.device)
+
+
+def _run(fb, configs, log_q, uniforms, kernel=None):
+    """configs [B][N][n_cut], log_q [B][N], uniforms [S][B][n_vars] (numpy) -> dict(x, logp, log_z_hat, score, entry, ess)."""
+    S = uniforms.shape[0]
+    msgs_before = fb.msgs.clone()
+    x, logp, log_z_hat, score, entry, ess = fb.cutset_resample(_dev(fb, configs, np.int32), _dev(fb, log_q), n_samples=S, uniforms=_dev(fb, uniforms),
+                                                               log_z=True, score=True, entry=True, ess=True)
+    ran = _M().last_kernel()
+    torch.cuda.synchronize()
+    assert x.dtype == torch.int32 and tuple(x.shape) == (S, fb.B, fb.topo.n_vars)
+    assert entry.dtype == torch.int32 and tuple(entry.shape) == tuple(logp.shape) == tuple(score.shape) == (S, fb.B)
+    assert tuple(log_z_hat.shape) == tuple(ess.shape) == (fb.B,) and logp.dtype == ess.dtype == torch.float64
+    assert torch.equal(fb.msgs.view(torch.int64), msgs_before.view(torch.int64))          # self.msgs is left untouched (bits)
+    if kernel is not None:
+        assert ran == kernel, ran
+    return dict(x=x.cpu().numpy(), logp=logp.cpu().numpy(), log_z_hat=log_z_hat.cpu().numpy(), score=score.cpu().numpy(),
+                entry=entry.cpu().numpy(), ess=ess.cpu().numpy())
+
+
+def _compare(name, got, runs):
+    """The device's answer against the statement's runs, one per graph."""
+    wrong = []
+    for b, r in enumerate(runs):
+        if not (np.array_equal(got['x'][:, b], r['samples']) and np.array_equal(got['entry'][:, b], r['entry'])):
+            wrong.append((b, got['x'][:, b].tolist(), r['samples'].tolist(), got['entry'][:, b].tolist(), r['entry'].tolist()))
+            continue
+        np.testing.assert_allclose(got['logp'][:, b], r['logp'], rtol=1e-10, err_msg='%s graph %d' % (name, b))
+        np.testing.assert_allclose(got['score'][:, b], r['score'], rtol=1e-10)
+        np.testing.assert_allclose(got['log_z_hat'][b], r['log_z_hat'], rtol=1e-10)
+        np.testing.assert_allclose(got['ess'][b], r['ess'], rtol=1e-10)
+    assert not wrong, (name, wrong[:4])
+
+
+def _identity(got, log_q, n_cut):
+    """logp = score - log_q[entry] - (log_z_hat + ln N), the header's identity (with cutset variables)."""
+    if not n_cut:
+        return
+    N = log_q.shape[1]
+    lq = np.take_along_axis(log_q, got['entry'].T.astype(np.int64), axis=1).T                # [S][B]
+    want = got['score'] - lq - (got['log_z_hat'] + np.log(N))[None, :]
+    assert (np.abs(got['logp'] - want) <= 1e-10 * np.maximum(1.0, np.abs(want))).all()
+
+
+def _case(name, kernel):
+    spec, inputs, cut, configs, log_q, uniforms, runs, _ = L.family(name)
+    L.check_margin(name, runs)                                  # the CPU module asserts it too: before the device is looked at
+    fb = _batch(spec, inputs)
+    got = _run(fb, configs, log_q, uniforms, kernel=kernel)
+    _compare(name, got, runs)
+    _identity(got, log_q, len(cut))
+    return fb, got
+
+
+# ---- against the statement ------------------------------------------------------------------------------
+@pytest.mark.parametrize('name', ['k3_x64_full', 'k3_x64_n7', 'k5_x64_n5', 'k5_x64_n37'])
+def test_x64_kernel_equals_the_statement(name):
+    """K3 with B = 3: the full list of 64 and a list of 7; K5 with B = 3, three cutset variables, beyond the exact limit:
+    N = 5 and N = 37, ragged against the 4 C waves of the weights grid."""
+    M = _M()
+    N = L.INPUTS[name][3]
+    assert M.chunks(3, N) == N and (name.startswith('k3') or N % 4)
+    fb, _ = _case(name, X64)
+    if name.startswith('k5'):
+        with pytest.raises(M.ExactSampleError, match='configurations'):
+            fb.exact_sample(n_samples=1, seed=0)
+
+
+def test_x64_kernel_with_one_chunk_and_waves_without_an_entry():
+    """K5 with B = 600 and N = 3: C = 1, so the fourth wave of every workgroup has no entry; three sets of tables shared
+    by the 600 graphs, every graph with a list of its own."""
+    M = _M()
+    B, N = 600, 3
+    assert M.chunks(B, N) == 1 and M.chunks(B, 1) == 1
+    spec, inputs, cut, configs, log_q, uniforms, runs = L.shared_tables_family(B, N)
+    L.check_margin('k5_x64_b600', runs)                         # the CPU module asserts it too: before the device is looked at
+    topo = _batch(spec, inputs[:1]).topo
+    index = np.arange(B) % 3
+    ptab = np.arange(3 * topo.P).reshape(-1, topo.P)[index]
+    utab = np.arange(3 * topo.U).reshape(-1, topo.U)[index]
+    fb = _batch(spec, inputs, batch_tables(spec, topo, inputs), ptab, utab, B=B)
+    got = _run(fb, configs, log_q, uniforms, kernel=X64)
+    _compare('k5_x64_b600', got, runs)
+    _identity(got, log_q, len(cut))
+
+
+@pytest.mark.parametrize('name', ['k4_x5_full', 'k4_x5_n300', 'k6_x3', 'chain4_x64', 'star4_x8'])
+def test_generic_kernel_equals_the_statement(name):
+    """K4 at X = 5: the full list of 25, and N = 300 with B = 2 (the SEGMENTED scan with L = 2); K6 at X = 3; a chain of four
+    at X = 64, which takes the generic kernel by the LDS rule, and a star: no cutset variable, configs [B][N][0]."""
+    M = _M()
+    fb, got = _case(name, GENERIC)
+    assert M.last_kernel() == M.KERNEL_GENERIC
+    if name == 'chain4_x64':
+        assert M.pick_kernel(64, 4, 3, 4, 3) == M.KERNEL_GENERIC and M.pick_kernel(64, 3, 2, 3, 2) == M.KERNEL_X64
+    if name in ('chain4_x64', 'star4_x8'):                      # entry 0, and the exact call's samples and logp
+        spec, inputs, cut, configs, log_q, uniforms, _, _ = L.family(name)
+        assert cut == [] and configs.shape[2] == 0 and (got['entry'] == 0).all()
+        x, logp = fb.exact_sample(n_samples=uniforms.shape[0], uniforms=_dev(fb, uniforms))
+        assert np.array_equal(x.cpu().numpy(), got['x']) and np.array_equal(logp.cpu().numpy(), got['logp'])
+
+
+# ---- the full list is the exact call ----------------------------------------------------------------------
+@pytest.mark.parametrize('name,kernel', [('k3_x64_full', X64), ('k4_x5_full', GENERIC)], ids=['x64', 'generic'])
+def test_the_full_list_with_log_q_zero_is_exact_sample_bit_for_bit(name, kernel):
+    spec, inputs, cut, configs, log_q, uniforms, _, _ = L.family(name)
+    assert not log_q.any() and np.array_equal(configs[0], K.full_list(spec['X'], len(cut)))
+    fb = _batch(spec, inputs)
+    got = _run(fb, configs, log_q, uniforms, kernel=kernel)
+    x, logp, log_z, score = fb.exact_sample(n_samples=uniforms.shape[0], uniforms=_dev(fb, uniforms), log_z=True, score=True)
+    assert _M().last_kernel() == kernel
+    assert np.array_equal(got['x'], x.cpu().numpy()) and np.array_equal(got['logp'], logp.cpu().numpy())
+    assert np.array_equal(got['score'], score.cpu().numpy())
+    cut_pos = [list(O.Graph(spec).var_order).index(v) for v in cut]
+    assert np.array_equal(got['entry'], sum(got['x'][:, :, p].astype(np.int64) * spec['X'] ** q for q, p in enumerate(cut_pos)))
+    np.testing.assert_allclose(got['log_z_hat'], log_z.cpu().numpy() - np.log(configs.shape[1]), rtol=1e-12)
+
+
+# ---- the estimate on the same list ------------------------------------------------------------------------
+@pytest.mark.parametrize('name,kernel', [('k3_x64_n7', X64), ('k5_x64_n37', X64), ('k4_x5_n300', GENERIC), ('k6_x3', GENERIC)])
+def test_log_z_hat_and_ess_are_cutset_estimates(name, kernel):
+    """log_z_hat and ess against cutset_estimate(configs, log_q) at 1e-10, and against the sums its log_w imply."""
+    spec, inputs, _, configs, log_q, uniforms, _, _ = L.family(name)
+    fb = _batch(spec, inputs)
+    got = _run(fb, configs, log_q, uniforms, kernel=kernel)
+    log_z_hat, _, ess, log_w = fb.cutset_estimate(configs=_dev(fb, configs, np.int32), log_q=_dev(fb, log_q), log_w=True)
+    np.testing.assert_allclose(got['log_z_hat'], log_z_hat.cpu().numpy(), rtol=1e-10)
+    np.testing.assert_allclose(got['ess'], ess.cpu().numpy(), rtol=1e-10)
+    log_w = log_w.cpu().numpy()
+    top = log_w.max(axis=1, keepdims=True)
+    w = np.exp(log_w - top)
+    np.testing.assert_allclose(got['log_z_hat'], top[:, 0] + np.log(w.sum(axis=1) / log_w.shape[1]), rtol=1e-10)
+    np.testing.assert_allclose(got['ess'], w.sum(axis=1) ** 2 / (w * w).sum(axis=1), rtol=1e-10)
+    # logp's entry term is the entry's share of the sum
+    share = np.take_along_axis(np.log(w / w.sum(axis=1, keepdims=True)), got['entry'].T.astype(np.int64), axis=1).T
+    assert (got['logp'] <= share + 1e-10 * np.maximum(1.0, np.abs(share))).all()       # the conditionals' logs are <= 0
+
+
+# ---- bits -----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('name,kernel', [('k5_x64_n37', X64), ('k4_x5_n300', GENERIC)], ids=['x64', 'generic'])
+def test_bits_do_not_depend_on_batch_size_position_sample_count_or_chunks(name, kernel):
+    """A graph alone (B = 1: its entries spread over many chunks) and at position 599 of B = 600 (one chunk); S = 1 against
+    the first sample of S = 9 (another chunk count of the draw pass)."""
+    M = _M()
+    spec, inputs, cut, configs, log_q, _, _, _ = L.family(name)
+    n, N = len(spec['var_ids']), configs.shape[1]
+    rs = np.random.RandomState(78)
+    u600, u9 = rs.rand(2, 600, n), rs.rand(9, 1, n)
+    alone = _run(_batch(spec, inputs[1:2]), configs[1:2], log_q[1:2], np.ascontiguousarray(u600[:, 599:600]), kernel=kernel)
+    topo = _batch(spec, inputs[:1]).topo
+    index = np.arange(600) % len(inputs)
+    index[599] = 1
+    ptab = np.arange(len(inputs) * topo.P).reshape(-1, topo.P)[index]
+    utab = np.arange(len(inputs) * topo.U).reshape(-1, topo.U)[index]
+    big = _run(_batch(spec, inputs, batch_tables(spec, topo, inputs), ptab, utab, B=600), configs[index], log_q[index], u600, kernel=kernel)
+    assert M.chunks(1, N) != M.chunks(600, N)
+    for key in ('x', 'logp', 'score', 'entry'):
+        assert np.array_equal(big[key][:, 599], alone[key][:, 0]), key
+    assert big['log_z_hat'][599] == alone['log_z_hat'][0] and big['ess'][599] == alone['ess'][0]
+    assert (big['x'] >= 0).all() and np.isfinite(big['logp']).all()
+    one = _run(_batch(spec, inputs[1:2]), configs[1:2], log_q[1:2], u9[:1], kernel=kernel)
+    nine = _run(_batch(spec, inputs[1:2]), configs[1:2], log_q[1:2], u9, kernel=kernel)
+    for key in ('x', 'logp', 'score', 'entry'):
+        assert np.array_equal(nine[key][:1], one[key]), key
+    assert np.array_equal(nine['log_z_hat'], one['log_z_hat']) and np.array_equal(nine['ess'], one['ess'])
+
+
+@pytest.mark.parametrize('name,kernel', [('k5_x64_n37', X64), ('k6_x3', GENERIC)], ids=['x64', 'generic'])
+def test_power_of_two_scaling(name, kernel):
+    """Tables times 2^+-300: no bit of samples, logp, entry or ess moves; log_z_hat and score move by k ln 2."""
+    spec, inputs, _, configs, log_q, uniforms, _, _ = L.family(name)
+    fb = _batch(spec, inputs)
+    base = _run(fb, configs, log_q, uniforms, kernel=kernel)
+    pair, unary = batch_tables(spec, fb.topo, inputs)
+    P, U = fb.topo.P, fb.topo.U
+    for pk, uk in (({0: 300}, {}), ({P - 1: -300}, {}), ({}, {0: 300}), ({1: 300, 2: -300}, {1: -300})):
+        p2, u2 = pair.copy(), unary.copy()
+        for b in range(len(inputs)):
+            for p, k in pk.items():
+                p2[b * P + p] = np.ldexp(p2[b * P + p], k)
+            for u, k in uk.items():
+                u2[b * U + u] = np.ldexp(u2[b * U + u], k)
+        got = _run(_batch(spec, inputs, (p2, u2)), configs, log_q, uniforms, kernel=kernel)
+        shift = (sum(pk.values()) + sum(uk.values())) * np.log(2.0)
+        for key in ('x', 'logp', 'entry', 'ess'):
+            assert np.array_equal(got[key], base[key]), (name, key, pk, uk)
+        np.testing.assert_allclose(got['log_z_hat'], base['log_z_hat'] + shift, rtol=1e-12, atol=1e-12)
+        np.testing.assert_allclose(got['score'], base['score'] + shift, rtol=1e-12, atol=1e-12)
+
+
+# ---- edges ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('name,kernel', [('k5_x64_n5', X64), ('k6_x3', GENERIC)], ids=['x64', 'generic'])
+def test_one_refused_graph_leaves_the_others_their_bits(name, kernel):
+    """A state outside [0, X) (both sides), a NaN log_q, a log_q out of range, an all-zero table and a table index outside
+    its array: that graph alone is refused, as the header says; the others keep the bits of the base run."""
+    spec, inputs, _, configs, log_q, uniforms, _, _ = L.family(name)
+    X, B = spec['X'], 8
+    pick = [i % len(inputs) for i in range(B)]
+    inputs = [inputs[i] for i in pick]
+    configs, log_q, uniforms = configs[pick].copy(), log_q[pick].copy(), np.ascontiguousarray(uniforms[:, pick])
+    base = _run(_batch(spec, inputs), configs, log_q, uniforms, kernel=kernel)
+    assert (base['x'] >= 0).all()
+    N = configs.shape[1]
+    configs[0, N - 1, 1] = X                                    # graph 0: a state one past the range, in the last entry
+    configs[1, 0, 2] = -1                                       # graph 1: a negative state
+    log_q[2, N // 2] = np.nan                                   # graph 2: a NaN log_q
+    log_q[3, 1] = -2.0e6                                        # graph 3: a log_q beyond MLBP_CUTSETIS_MAX_ABS_LOG_Q
+    pair, unary = batch_tables(spec, _batch(spec, inputs[:1]).topo, inputs)
+    P = len(pair) // B
+    pair = pair.copy()
+    pair[4 * P + 1][:] = 0.0                                    # graph 4: an all-zero table -- every listed weight is zero
+    fb = _batch(spec, inputs, (pair, unary))
+    fb.pair_tab[5, 0] = fb.pair_tables.shape[0]                 # graph 5: a table index outside the array
+    got = _run(fb, configs, log_q, uniforms, kernel=kernel)
+    for b in (0, 1, 2, 3, 5):
+        assert (got['x'][:, b] == -1).all() and (got['entry'][:, b] == -1).all(), b
+        assert np.isnan(got['logp'][:, b]).all() and np.isnan(got['score'][:, b]).all() and np.isnan(got['log_z_hat'][b]) and np.isnan(got['ess'][b]), b
+    assert (got['x'][:, 4] == -1).all() and (got['entry'][:, 4] == -1).all() and np.isnan(got['logp'][:, 4]).all() and np.isnan(got['score'][:, 4]).all()
+    assert got['log_z_hat'][4] == -np.inf and got['ess'][4] == 0.0
+    for b in (6, 7):
+        for key in ('x', 'logp', 'score', 'entry'):
+            assert np.array_equal(got[key][:, b], base[key][:, b]), (key, b)
+        assert got['log_z_hat'][b] == base['log_z_hat'][b] and got['ess'][b] == base['ess'][b]
+
+
+def test_arguments_are_checked():
+    M = _M()
+    spec, inputs, _, configs, log_q, uniforms, _, _ = L.family('k5_x64_n5')
+    fb = _batch(spec, inputs)
+    c, q, u = _dev(fb, configs, np.int32), _dev(fb, log_q), _dev(fb, uniforms)
+    with pytest.raises(ValueError, match='exactly one'):
+        fb.cutset_resample(c, q, n_samples=3, seed=0, uniforms=u)
+    with pytest.raises(ValueError, match='exactly one'):
+        fb.cutset_resample(c, q, n_samples=3)
+    with pytest.raises(ValueError):
+        fb.cutset_resample(c, q, n_samples=0, seed=0)
+    with pytest.raises(ValueError, match='configs'):
+        fb.cutset_resample(c[:, :4], q, n_samples=1, seed=0)
+    with pytest.raises(ValueError, match='configs'):
+        fb.cutset_resample(c.long(), q, n_samples=1, seed=0)
+    with pytest.raises(ValueError, match='log_q'):
+        fb.cutset_resample(c, q.float(), n_samples=1, seed=0)
+    with pytest.raises(ValueError):
+        fb.cutset_resample(c, q, n_samples=2, uniforms=u)        # the shape is [3][B][n_vars]
+    with pytest.raises(ValueError, match='proposal'):
+        fb.estimate_sample(list(O.Graph(spec).var_order), proposal='other')
+    x, logp = fb.cutset_resample(c, q, n_samples=3, seed=11)    # seed: the documented torch.rand call
+    gen = torch.Generator(fb.device).manual_seed(11)
+    x2, logp2 = fb.cutset_resample(c, q, n_samples=3, uniforms=torch.rand((3, fb.B, fb.topo.n_vars), dtype=torch.float64, device=fb.device, generator=gen))
+    assert torch.equal(x, x2) and torch.equal(logp.view(torch.int64), logp2.view(torch.int64))
+    wide = C.user_spec(10, [1, 4, 7], 256, 64, seed=1)          # float32 tables exist at X = 256 and 512 alone
+    fb32 = _batch(wide, [C.make_inputs(wide, 1)])
+    fb32.set_pair_tables(fb32.pair_tables, dtype=torch.float32)
+    with pytest.raises(NotImplementedError):
+        fb32.cutset_resample(torch.zeros(1, 2, 1, dtype=torch.int32, device=fb32.device), torch.zeros(1, 2, dtype=torch.float64, device=fb32.device),
+                             n_samples=1, seed=0)
+    assert M.MAX_LISTED == 65536
+
+
+# ---- capture --------------------------------------------------------------------------------------------
+def test_capture_and_replay_with_changed_tables_list_and_uniforms():
+    """After one eager call the listed call is captured; a replay gives the bits of the eager call, and after the tables, the
+    list and the uniforms are overwritten in place the bits of an eager call on the new ones."""
+    spec, inputs, _, configs, log_q, uniforms, _, _ = L.family('k5_x64_n37')
+    fb = _batch(spec, inputs[:2])
+    first = _run(fb, configs[:2], log_q[:2], np.ascontiguousarray(uniforms[:, :2]), kernel=X64)
+    other_in = [inputs[2], inputs[0]]
+    other_args = (configs[[2, 0]], log_q[[2, 0]], np.ascontiguousarray(uniforms[:, [2, 0]]))
+    other = _run(_batch(spec, other_in), *other_args, kernel=X64)
+    assert not np.array_equal(first['x'], other['x'])
+    c, q, u = _dev(fb, configs[:2], np.int32), _dev(fb, log_q[:2]), _dev(fb, np.ascontiguousarray(uniforms[:, :2]))
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        outs = fb.cutset_resample(c, q, n_samples=u.shape[0], uniforms=u, log_z=True, score=True, entry=True, ess=True)
+    pair, unary = batch_tables(spec, fb.topo, other_in)
+    for want in (first, other):
+        for t in outs:
+            t.fill_(-5)
+        graph.replay()
+        torch.cuda.synchronize()
+        for t, key in zip(outs, ('x', 'logp', 'log_z_hat', 'score', 'entry', 'ess')):
+            assert np.array_equal(t.cpu().numpy(), want[key]), key
+        fb.pair_tables.copy_(torch.from_numpy(pair))
+        fb.unary_tables.copy_(torch.from_numpy(unary))
+        c.copy_(torch.from_numpy(other_args[0].astype(np.int32)))
+        q.copy_(torch.from_numpy(other_args[1]))
+        u.copy_(torch.from_numpy(other_args[2]))
+
+
+# ---- estimate_sample and the trainers -------------------------------------------------------------------
+@pytest.mark.parametrize('proposal', ['messages', 'sample'])
+def test_estimate_sample_is_the_list_then_the_resampling(proposal):
+    """estimate_sample() on K5 at X = 64: the documented list, the documented uniforms, logp_hat = score - log_z_hat."""
+    spec = R.kn_spec(5, 64)
+    inputs = [C.make_inputs(spec, 60 + s) for s in range(3)]
+    roots = list(O.Graph(spec).var_order)
+    fb = _batch(spec, inputs)
+    fb.initialize()
+    x, logp_hat, log_z_hat, ess = fb.estimate_sample(roots, n_samples=4, n_list=16, seed=7, proposal=proposal)
+    assert _M().last_kernel() == X64
+    fb2 = _batch(spec, inputs)
+    fb2.initialize()
+    if proposal == 'messages':
+        fb2.sweep(roots, init=True)
+        configs, log_q = fb2.cutset_draw(16, seed=7)
+    else:
+        configs, log_q = fb2.cutset_proposal(roots, 16, seed=7)
+    u = torch.rand((4, fb2.B, fb2.topo.n_vars), dtype=torch.float64, device=fb2.device, generator=torch.Generator(fb2.device).manual_seed(8))
+    x2, _, lz2, score2, ess2 = fb2.cutset_resample(configs, log_q, n_samples=4, uniforms=u, log_z=True, score=True, ess=True)
+    assert torch.equal(x, x2) and torch.equal(log_z_hat, lz2) and torch.equal(ess, ess2)
+    assert torch.equal(logp_hat, score2 - lz2.unsqueeze(0))
+    assert (x >= 0).all() and torch.isfinite(logp_hat).all() and ((ess >= 1.0 - 1e-9) & (ess <= 16.0 + 1e-9)).all()
+    if proposal == 'messages':                                  # roots=None: the messages as they stand
+        x3, lp3, _, _ = fb.estimate_sample(None, n_samples=4, n_list=16, seed=7)
+        assert torch.equal(x, x3) and torch.equal(logp_hat, lp3)
+    else:
+        with pytest.raises(ValueError, match='roots'):
+            fb.estimate_sample(None, n_samples=1, proposal='sample')
+
+
+def test_trainers_estimated_sample(tmp_path):
+    """TiDirTrainer.estimated_sample() on the clique fixture (K1 to K12 at X = 64): every instance's row is its shape's
+    UserGraphTrainer.estimated_sample(), which is the batch's estimate_sample() over the predict() schedule; K5 and up are in
+    the result and nothing is skipped for the configuration limit, which exact_sample() still reports."""
+    from test_gpu_cliques import _trainer
+    gold = tidir_gold('tidir_cliques_reference')
+    paths = write_tidir(gold, str(tmp_path))
+    tt = _trainer(paths, gold)
+    S, N, seed = 2, 8, 21
+    per_instance, skipped = tt.estimated_sample(n_samples=S, n_list=N, seed=seed)
+    assert skipped == [] and len(per_instance) == 11
+    sizes = set()
+    for k, (key, tr) in enumerate(tt.trainers.items()):
+        x, logp_hat, log_z_hat, ess = tr.estimated_sample(S, n_list=N, seed=seed + 2 * k)
+        B = tr.batch.B
+        assert x.dtype == np.int64 and x.shape == (S, B, len(key[1])) and logp_hat.shape == (S, B) and log_z_hat.shape == ess.shape == (B,)
+        assert (x >= 0).all() and np.isfinite(logp_hat).all() and (ess >= 1.0 - 1e-9).all() and (ess <= N + 1e-9).all()
+        tr.build_potentials()
+        bx, blp, blz, bess = tr.batch.estimate_sample(tr.roots[:tr.n_sweeps_run], n_samples=S, n_list=N, seed=seed + 2 * k)
+        assert np.array_equal(bx.cpu().numpy(), x) and np.array_equal(blp.cpu().numpy(), logp_hat)
+        assert np.array_equal(blz.cpu().numpy(), log_z_hat) and np.array_equal(bess.cpu().numpy(), ess)
+        for i, row in enumerate(tt.buckets[key]['rows']):
+            positions, words, logps, share = per_instance[row['index']]
+            assert positions == tuple(key[1]) and words == [[tt.en[w] for w in x[s, i]] for s in range(S)]
+            assert logps == [float(logp_hat[s, i]) for s in range(S)] and share == float(ess[i]) / N
+        sizes.add(len(key[1]))
+    assert max(sizes) >= 12 and {5, 8} <= sizes and min(sizes) <= 4
+    _, exact_skipped = tt.exact_sample(n_samples=1, seed=0)
+    assert exact_skipped and all('configurations' in s[2] for s in exact_skipped)       # (what exact_sample() skips it still skips)
+
+
+# ---- the exact path is what it was -----------------------------------------------------------------------
+@pytest.mark.parametrize('name', ['k3_x64', 'k3_x64_lognormal', 'k4_x64'])
+def test_exact_sample_computes_the_bits_it_computed_before(name):
+    """exact_sample() on the K3 and K4 inputs of tests/test_gpu_exactsample.py (they pass through the statement there, as they
+    always have): every bit of samples, logp, log_z and score is the one recorded on the library before it had a listed mode."""
+    with open(GOLDEN) as f:
+        want = json.load(f)[name]
+    spec, inputs, cut, uniforms, _, _ = E.family(name)
+    fb = _batch(spec, inputs)
+    x, logp, log_z, score = fb.exact_sample(n_samples=uniforms.shape[0], uniforms=_dev(fb, uniforms), cutset=cut, log_z=True, score=True)
+    assert _M().last_kernel() == X64
+    assert x.cpu().numpy().tolist() == want['x']
+    for t, key in ((logp, 'logp'), (log_z, 'log_z'), (score, 'score')):
+        assert [v.hex() for v in t.cpu().numpy().reshape(-1).tolist()] == want[key], key
