@@ -59,6 +59,45 @@
  * Determinism.  The bits of a graph's outputs are a function of the graph, the cutset and C (below): every partial is
  * written by one wave (X = 64) or one workgroup (generic), the partials are added in index order, every cross-lane sum has a
  * fixed shape, and there is no floating-point atomic.
+ *
+ * The LISTED mode (mlbp_exactgrad_listed_args below, N > 0): an ESTIMATE of everything above beyond the exact limit.  The call is handed a list of N joint states
+ * of the cutset per graph -- configs[g][i][q] the state of cutset[q] in entry i, log_q[g][i] the natural log of the probability
+ * a proposal gave the entry; the list libmlbp_cutdraw.so draws and libmlbp_cutsetis.so takes -- and walks the list's entries in
+ * the place of the X^n_cut configurations.  The bound is on the cutset's size (MLBP_EXACTGRAD_MAX_CUT) and on N
+ * (MLBP_EXACTGRAD_MAX_LISTED), not on X^n_cut; the plan is validated by mlbp_cutsetis_check_plan, which states that bound.
+ * Semantics: the self-normalised estimator of mlbp_cutsetis.h applied to every output.  With
+ *   w_i = Z_{c_i} exp(-log_q[i])              by the one formula of mlbp_cutsetis.h ("Range"), a (mantissa, exponent) pair
+ *   log_z          = log_z_hat = ln(sum_i w_i / N)
+ *   marginals, pair_marginals, expect_*  = sum_i w_i (the conditional quantity under c_i) / sum_i w_i
+ *   grad_*         = observed_* - expect_*
+ * The kernels are the exact call's and do what they do there, with w_i where Z_c stands, entry i's row where the digits of the
+ * configuration number stand, and the entry index where the configuration number stands: wave w of workgroup (g, k) of the
+ * X = 64 kernel walks entries 4 k + w, 4 k + w + 4 C, ..., workgroup (g, k) of the generic kernel entries k, k + C, ..., C by the
+ * chunks rule below with N for n_configs; every walker writes a partial of its own, the combine kernel adds them in index order
+ * and divides the sum by N for log_z_hat.  Hence:
+ *   - a list that holds every configuration in index order with log_q = 0 returns the exact call's bits in every output but
+ *     log_z, which is ln(Z / N) = log_z - ln N up to the rounding of one division and one logarithm;
+ *   - a table times 2^k moves no bit of the normalised outputs (log_z_hat moves by k ln 2);
+ *   - the bits depend on the graph, the cutset, the list and C -- a function of B and N -- alone: not on the graph's position in
+ *     the batch, on the other graphs or on B at an equal C.  At another C the walkers group the entries differently and the
+ *     sums are the same numbers added in another order (measured: 1e-16 apart).
+ * The walk kernel is the exact call's, by the same rule of (X, n_vars, P, U, n_forest): K5 to K9 at X = 64 run on the X = 64
+ * kernel, K10 and up and every other X on the generic one.
+ * exp(log_z_hat) is an unbiased estimate of Z for a proposal that is positive wherever Z_c is; the normalised outputs are
+ * consistent, not unbiased.  The list may repeat a configuration.  n_cut == 0 is valid: every entry is the one empty
+ * configuration and `configs` is not read.
+ * Edge rules of a list, as in mlbp_cutsetis.h.  A state outside [0, X) in the graph's rows of `configs`, or a log_q that is no
+ * finite number or whose magnitude passes MLBP_CUTSETIS_MAX_ABS_LOG_Q (1e6): the graph is refused alone -- log_z, expect_* and
+ * grad_* NaN, its pair_marginals and marginals left as they were; every other graph keeps its bits.  An entry is validated
+ * before the first address is formed from it: in the exact call a state is a digit of the configuration number and always in
+ * range, here it is caller data that selects rows and cells of the accumulators in global memory.  The walker that meets such
+ * an entry stops and leaves a NaN as its partial's sum, which is how the combine kernel learns of it; a NaN or +inf table
+ * entry that a listed configuration reads and that makes the sum a NaN is refused the same way (the exact call leaves such a
+ * graph's outputs unspecified).  Every weight zero: the Z = 0 rule above, log_z_hat = -inf.  A walker without an entry (N
+ * smaller than the walkers of its graph) writes an empty partial and touches nothing else.
+ * Workspace of a listed call: the formula below with the listed C.  A partial costs X * X doubles per pairwise factor: K5 at
+ * X = 64 (ten factors) is 2 + 320 + 40960 doubles = 330 256 bytes, and with four partials per graph (the X = 64 kernel, B large
+ * enough for C = 1) a batch of 8192 graphs needs 10.8 GB.  A caller that cannot spare it splits the batch.
  */
 #ifndef MLBP_EXACTGRAD_H
 #define MLBP_EXACTGRAD_H
@@ -89,7 +128,7 @@ extern "C" {
  *
  * Grid (B, C), C = mlbp_exactgrad_chunks(B, n_configs, kernel) =
  *   min(n_walkers, ceil(MLBP_EXACTGRAD_MIN_WORKGROUPS / B)),   n_walkers = ceil(n_configs / 4) (X = 64) or n_configs (generic):
- * a partial costs X * X doubles per pairwise factor here, so no wave is given a partial without a configuration, and a graph
+ * a partial costs X * X doubles per pairwise factor here, so no workgroup is given partials without a configuration, and a graph
  * is spread over one workgroup per CU, not two.  Workgroup (g, k) of the generic kernel walks configurations k, k + C, ...;
  * wave w of workgroup (g, k) of the X = 64 kernel walks 4 k + w, 4 k + w + 4 C, ... and writes partial 4 k + w: the four waves'
  * accumulators are NOT merged on chip.  A partial is
@@ -105,6 +144,8 @@ extern "C" {
 #define MLBP_EXACTGRAD_X64_MAX_FOREST 2
 #define MLBP_EXACTGRAD_MIN_WORKGROUPS 256
 #define MLBP_EXACTGRAD_MAX_FEATURES 64       /* F_ee and F_ed, each */
+#define MLBP_EXACTGRAD_MAX_LISTED 65536      /* entries per graph of a listed call */
+#define MLBP_EXACTGRAD_MAX_CUT 16            /* cutset variables of a listed call: the walk keeps a configuration's states in 16 integers */
 
 typedef struct mlbp_exactgrad_args {
   int32_t B, X, n_vars, P, U;                /* graphs, states, variables, pairwise / unary factors */
@@ -135,10 +176,22 @@ typedef struct mlbp_exactgrad_args {
   double* grad_ed;                           /* optional device [B][F_ed] */
 } mlbp_exactgrad_args;
 
+/* The arguments of a LISTED call: the exact call's, and the list behind them.  mlbp_exactgrad_args itself keeps the layout and
+ * the size it has always had; a listed call hands mlbp_exactgrad_f64 the address of `args` below with args.plan_words NEGATED
+ * (-plan_words: no exact call has one below zero), which tells the library that the list lies behind the struct it was handed.
+ * N == 0 there is the exact call once more: configs and log_q are not looked at, whatever they hold. */
+typedef struct mlbp_exactgrad_listed_args {
+  mlbp_exactgrad_args args;                  /* as in the exact call, but for the sign of plan_words */
+  const int32_t* configs;                    /* device [B][N][n_cut], the state of cutset[q] (may be NULL when n_cut == 0) */
+  const double* log_q;                       /* device [B][N], ln of the proposal's probability of the entry */
+  int32_t N;                                 /* 0: the exact call; 1 .. MLBP_EXACTGRAD_MAX_LISTED: entries listed per graph */
+} mlbp_exactgrad_listed_args;
+
 /* Table indices, labels, observed columns and selectors are device data and are not checked on the host: see the edge rules.
  * MLBP_EINVAL: bad sizes, a missing array, a requested expect_* or grad_* without the feature inputs (F_ee, F_ed, Vde >= 1),
- * a requested grad_* without labels, a workspace that is too small.  MLBP_EUNSUPPORTED: X > MLBP_CUTSET_MAX_X, X^n_cut >
- * MLBP_CUTSET_MAX_CONFIGS, F_ee or F_ed > MLBP_EXACTGRAD_MAX_FEATURES. */
+ * a requested grad_* without labels, a workspace that is too small, N outside [0, MLBP_EXACTGRAD_MAX_LISTED], a listed call
+ * without log_q or (n_cut > 0) without configs.  MLBP_EUNSUPPORTED: X > MLBP_CUTSET_MAX_X, X^n_cut > MLBP_CUTSET_MAX_CONFIGS
+ * (the exact call) or n_cut > MLBP_EXACTGRAD_MAX_CUT (a listed call), F_ee or F_ed > MLBP_EXACTGRAD_MAX_FEATURES. */
 int mlbp_exactgrad_f64(const mlbp_exactgrad_args* args, void* stream);
 
 /* Host only, no GPU needed: the checks of mlbp_cutset_check_plan, with its messages. */
@@ -154,7 +207,8 @@ int mlbp_exactgrad_chunks(int32_t B, int32_t n_configs, int32_t kernel);
 /* Host only: bytes of workspace a call needs, 8 times
  *   B * parts * (2 + n_vars * X + P * X * X)            parts = C (generic) or 4 C (X = 64)
  *   + B * C * (5 n_vars + 2) * round_up(X, 2)           when the generic kernel keeps its vectors there
- * with n_configs = X^n_cut; a negative status as pick_kernel / chunks give it, MLBP_EUNSUPPORTED above MLBP_CUTSET_MAX_CONFIGS. */
+ * with n_configs = X^n_cut; a negative status as pick_kernel / chunks give it, MLBP_EUNSUPPORTED above MLBP_CUTSET_MAX_CONFIGS.
+ * This states the exact call; a listed call needs the same formula with C = mlbp_exactgrad_chunks(B, N, kernel). */
 int64_t mlbp_exactgrad_workspace_bytes(int32_t B, int32_t X, int32_t n_vars, int32_t P, int32_t U, int32_t n_forest, int32_t n_cut);
 
 /* Host-side record of the walk kernel the calling thread's last mlbp_exactgrad_f64 enqueued (MLBP_EXACTGRAD_KERNEL_*; NONE

@@ -959,11 +959,25 @@ class FactorGraphBatch:
         return samples, score - log_z_hat.unsqueeze(0), log_z_hat, ess
 
     # ---- the exact pair marginals and the true gradient (include/mlbp_exactgrad.h) ---------------------
-    def _exactgrad(self, cutset, marginals=None, pair_marginals=None, expect=None, grad=None, labels=None):
-        """One mlbp_exactgrad_f64 call: log_z [B], and whichever of the optional outputs is given (expect, grad: (ee, ed))."""
+    def _exactgrad(self, cutset, marginals=None, pair_marginals=None, expect=None, grad=None, labels=None, listed=None):
+        """One mlbp_exactgrad_f64 call: log_z [B], and whichever of the optional outputs is given (expect, grad: (ee, ed)).
+        listed: (configs, log_q) of a listed call, which returns log_z_hat in the place of log_z."""
         from . import exactgrad as K
         topo = self.topo
-        pl, a = self._cutset_args(K, K.ExactGradArgs, cutset, 'the exact pair marginals and gradient need float64 pairwise tables')
+        if listed is None:
+            pl, a = self._cutset_args(K, K.ExactGradArgs, cutset, 'the exact pair marginals and gradient need float64 pairwise tables')
+        else:
+            from . import cutsetis as KP
+            tail = K.listed_args()()                            # mlbp_exactgrad_listed_args: the exact call's args, then the list
+            pl, a = self._cutset_args(KP, lambda: tail.args, cutset,                      # the listed check of the plan
+                                      'the estimated pair marginals and gradient need float64 pairwise tables')
+            configs, log_q = listed
+            tail.log_q = self._tensor(log_q, (self.B, None), 'log_q', '[B][N]')
+            tail.N = N = _listed_count(log_q.shape[1], K, 'N')
+            configs_ptr = self._tensor(configs, (self.B, N, pl.n_cut), 'configs', '[B][N][n_cut]', dtype=torch.int32)
+            if pl.n_cut:
+                tail.configs = configs_ptr
+            a.plan_words = -a.plan_words                        # the header's sign of a list behind the struct
 
         def checked(t, shape, what):                           # the message prints the sizes themselves
             return self._tensor(t, shape, what, list(shape))
@@ -993,7 +1007,8 @@ class FactorGraphBatch:
                 a.labels = lab.data_ptr()
         log_z = torch.empty(self.B, dtype=torch.float64, device=self.device)
         a.log_z = log_z.data_ptr()
-        work = self._workspace(a, K.workspace_bytes(self.B, self.X, topo.n_vars, topo.P, topo.U, pl.n_forest, pl.n_cut))
+        shape = (self.B, self.X, topo.n_vars, topo.P, topo.U, pl.n_forest)
+        work = self._workspace(a, K.workspace_bytes(*shape + (pl.n_cut,)) if listed is None else K.listed_workspace_bytes(*shape + (N,)))
         K.check(K.lib.mlbp_exactgrad_f64(C.byref(a), _stream_ptr(self.device)))
         return log_z
 
@@ -1029,6 +1044,65 @@ class FactorGraphBatch:
         log_z = self._exactgrad(cutset, marginals=marginals, pair_marginals=pair_marginals, expect=out if expect_only else None,
                                 grad=None if expect_only else out, labels=labels)
         return out_ee, out_ed, log_z
+
+    # ---- the gradient beyond the exact limit: listed cutset states (the listed mode of include/mlbp_exactgrad.h) ----------
+    def cutset_pair_marginals(self, configs, log_q, out=None, cutset=None):
+        """An ESTIMATE of the marginal of every pairwise factor over a LIST of cutset states -- for the graphs whose cutset has
+        more joint states than exact_pair_marginals() walks (more than 65536: K5 and up at X = 64): float64 device tensor
+        [B][P][X][X] in the axes of each factor's table.  configs (int32 [B][N][n_cut]) and log_q (float64 [B][N]) are the list
+        cutset_draw() and cutset_proposal() return and cutset_estimate() takes; every entry's conditioned forest is solved
+        exactly and weighted by w_i = Z_c / q(c_i), and the result is sum of w_i M_p|c_i / sum of w_i: self-normalised, consistent,
+        not unbiased.  The full list in index order with log_q = 0 returns exact_pair_marginals()'s bits.  A graph with a state
+        outside [0, X) or a log_q that is not finite keeps what `out` held.  out: optional contiguous float64 [B][P][X][X]
+        device tensor to write into; cutset: as in exact_inference, at most 16 variables, no limit on X^len(cutset).
+        self.msgs is neither read nor written."""
+        if out is None:
+            out = torch.empty(self.B, self.topo.P, self.X, self.X, dtype=torch.float64, device=self.device)
+        self._exactgrad(cutset, pair_marginals=out, listed=(configs, log_q))
+        return out
+
+    def cutset_gradient(self, configs, log_q, labels=None, out_ee=None, out_ed=None, pair_marginals=None, marginals=None, cutset=None,
+                        expect_only=False):
+        """An ESTIMATE of the per-graph likelihood gradient over a LIST of cutset states -- exact_gradient() for the graphs
+        beyond its limit: (grad_ee [B][F_ee], grad_ed [B][F_ed], log_z_hat [B]) device tensors.  The expected features are
+        formed from the self-normalised estimates of the pair marginals and marginals (cutset_pair_marginals(),
+        cutset_estimate()): grad = observed features at `labels` - sum of w_i E[features | c_i] / sum of w_i; log_z_hat =
+        ln(mean of w_i) is cutset_estimate()'s estimate of log Z on the same list.  configs, log_q: as in
+        cutset_pair_marginals(); the other arguments as in exact_gradient().  The full list in index order with log_q = 0
+        returns exact_gradient()'s bits and log_z - ln N.  A graph with a state outside [0, X) or a log_q that is not finite gets
+        NaN and keeps its pair_marginals and marginals; one whose listed weights are all zero gets exact_gradient()'s Z = 0
+        answer.  The bits depend on the graph, the cutset and the list alone.  self.msgs is neither read nor written."""
+        self._need_f64_tables('cutset_gradient')
+        if getattr(self, 'phi_en_en', None) is None:
+            raise RuntimeError('set_features() first')
+        F_ee, F_ed = int(self.phi_en_en.shape[2]), int(self.phi_en_de.shape[2])
+        if out_ee is None:
+            out_ee = torch.empty(self.B, F_ee, dtype=torch.float64, device=self.device)
+        if out_ed is None:
+            out_ed = torch.empty(self.B, F_ed, dtype=torch.float64, device=self.device)
+        out = (out_ee, out_ed)
+        log_z_hat = self._exactgrad(cutset, marginals=marginals, pair_marginals=pair_marginals, expect=out if expect_only else None,
+                                    grad=None if expect_only else out, labels=labels, listed=(configs, log_q))
+        return out_ee, out_ed, log_z_hat
+
+    def estimate_gradient(self, roots=None, n_list=256, seed=0, cutset=None, proposal='messages', labels=None):
+        """The gradient for the sentences beyond exact_gradient()'s limit: cutset_gradient() over a list of n_list cutset states
+        drawn from loopy BP, made as estimate_sample() makes its list.  proposal='messages': cutset_draw(n_list, seed=seed) on
+        the messages self.msgs holds; given `roots`, sweep(roots, init=True) runs first -- THAT WRITES self.msgs --, with
+        roots=None the messages are used as they stand.  proposal='sample': cutset_proposal(roots, n_list, seed=seed), which
+        needs roots and sweeps for every draw.  Returns (grad_ee [B][F_ee], grad_ed [B][F_ed], log_z_hat [B]) device tensors."""
+        if proposal not in ('sample', 'messages'):
+            raise ValueError("proposal must be 'sample' or 'messages', not %r" % (proposal,))
+        if proposal == 'sample':
+            if roots is None:
+                raise ValueError("proposal='sample' needs roots")
+            configs, log_q = self.cutset_proposal(roots, n_list, seed=int(seed), cutset=cutset)
+        else:
+            self._cutdraw_refuse('estimate_gradient')
+            if roots is not None:
+                self.sweep(roots, init=True)
+            configs, log_q = self.cutset_draw(n_list, seed=int(seed), cutset=cutset)
+        return self.cutset_gradient(configs, log_q, labels=labels, cutset=cutset)
 
     def treelike_inference(self, iterations, roots):
         """`iterations` sweeps if the graph is loopy, else one (LBP.py:219); `roots` replaces the

@@ -80,14 +80,23 @@ __device__ __forceinline__ void mul(Scaled& z, double v) {
 }
 
 // The weight of a listed entry, Z_c exp(-log_q), by the formula of include/mlbp_cutsetis.h: exp(-log_q) = r 2^k,
-// k = rint(-log_q / ln 2), r = exp(-log_q - k ln 2).  log_q = 0 leaves z as it is.
-__device__ __forceinline__ Scaled weighted(Scaled z, double lq) {
+// k = rint(-log_q / ln 2), r = exp(-log_q - k ln 2).  log_q = 0 leaves z as it is.  In two steps, for a kernel that wants the
+// exponential taken before its walk, where fewer registers are live: weighted(z, lq) = weighted(z, proposal_factor(lq)).
+struct ProposalFactor { double r; int k; };
+
+__device__ __forceinline__ ProposalFactor proposal_factor(double lq) {
   constexpr double ln2 = 0.693147180559945309417232121458;
   const double k = rint(-lq / ln2);
-  mul(z, exp(-lq - k * ln2));
-  z.e += (int)k;
+  return {exp(-lq - k * ln2), (int)k};
+}
+
+__device__ __forceinline__ Scaled weighted(Scaled z, const ProposalFactor& f) {
+  mul(z, f.r);
+  z.e += f.k;
   return z;
 }
+
+__device__ __forceinline__ Scaled weighted(Scaled z, double lq) { return weighted(z, proposal_factor(lq)); }
 
 // Max over the workgroup of non-negative values, the same bits in every thread (a NaN is passed over); two barriers.
 __device__ __forceinline__ double block_max(double v, double* scratch /*[4]*/) {

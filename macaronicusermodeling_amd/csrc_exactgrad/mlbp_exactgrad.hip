@@ -16,10 +16,14 @@
 // A global accumulator entry is only ever touched by one lane (X = 64: entry [row][lane] by `lane`), or by threads of one
 // workgroup with a barrier between two touches (generic); there is no atomic.  Every scalar a wave or workgroup branches on comes
 // out of a reduction and has the same bits in every thread of it.
+// A LISTED call (mlbp_exactgrad_listed_args with N > 0: the header's listed mode) runs the same three kernels over the caller's list of cutset states: a walker's
+// c is then the index of a list entry, its weight Z_c exp(-log_q) (weighted() of csrc/mlbp_cutset_plan.h) and its states the
+// entry's row of configs, checked before they index anything; the combine kernel divides the sum by N for log_z_hat.
 // No device-side mutable globals: everything comes through GradDev.
 #include <hip/hip_runtime.h>
 
 #include "../../include/mlbp_exactgrad.h"
+#include "../../include/mlbp_cutsetis.h"    // MLBP_CUTSETIS_MAX_ABS_LOG_Q: the range of a list's log_q
 #define MLBP_GRAPH_NO_SWEEPS                // this library runs no sweep program
 #include "../csrc/mlbp_graph_device.h"
 #include "../csrc/mlbp_graph_host.h"
@@ -39,7 +43,37 @@ struct GradDev : WalkDev {                   // partials: [B][parts][stride]: {s
   double* log_z; double* marginals; double* pair_marginals; double* expect_ee; double* expect_ed; double* grad_ee; double* grad_ed;
   int64_t stride;
   int32_t F_ee, F_ed, Vde;
+  int32_t listed;                            // a listed call: n_configs is N, and the two below are the caller's; else 0 and NULL
+  const int32_t* configs;                    // [B][N][n_cut], NULL without cutset variables
+  const double* log_q;                       // [B][N]
 };
+
+// ---- a listed call: where an entry's states and weight come from ----------------------------------------------
+// An entry of a list is checked before anything is indexed by it.  The generic kernel reads the state of cut position q through
+// ONE functor in both modes (EntryStates), so its walk has one call site.  The X = 64 kernel has a loop for each mode, the exact
+// one the text it always was: with one loop over a shared functor -- a scalar select between the digits of c and a v_readlane, or
+// the digits of c laid out one per lane -- the exact call at K4 ran 2.6 % and 3.1 % slower than before, with two it does not.
+__device__ __forceinline__ const_i32p listed_row(const GradDev& d, int g, int i) {
+  return as_const(d.configs) + ((size_t)g * d.n_configs + i) * d.n_cut;
+}
+
+__device__ __forceinline__ bool log_q_ok(double lq) { return fabs(lq) <= MLBP_CUTSETIS_MAX_ABS_LOG_Q; }     // false for a NaN
+
+// The generic kernel takes an entry's factor exp(-log_q) = r 2^k OUT OF LINE.  Inlined into its loop, the nine coefficients of the
+// exponential's polynomial are hoisted out of the loop and held in 18 vector registers across the whole walk: 90 registers and
+// five waves per SIMD against the 61 and seven of the exact-only kernel.  Behind a call they live in the callee alone (72, seven
+// waves, no scratch).  The X = 64 kernels have the room and take it inline: a call there would have to save the accumulators.
+__device__ __attribute__((noinline)) ProposalFactor generic_entry_factor(double lq) { return proposal_factor(lq); }
+
+// Generic kernel: the row of the entry (a listed call with cutset variables), else c's digits.
+struct EntryStates {
+  const_i32p row; int c, X;
+  __device__ __forceinline__ int operator()(int q) const { return row ? row[q] : GenericCode{c, X}(q); }
+};
+
+// The partial of a walker that met an entry it may not walk: a NaN sum under exponent 0, which makes the graph's Z a NaN in the
+// combine kernel -- its sign of a refused list.
+__device__ __forceinline__ Scaled refused() { return {__builtin_nan(""), 0}; }
 
 // ---- any X: the workgroup walks a chunk's configurations ---------------------------------------------------
 __global__ __launch_bounds__(WG) void exactgrad_generic_kernel(GradDev d) {
@@ -57,8 +91,24 @@ __global__ __launch_bounds__(WG) void exactgrad_generic_kernel(GradDev d) {
   for (size_t i = t; i < vs; i += WG) acc[i] = 0.0;
 
   Scaled sum = {0.0, EMPTY};                                   // sum of Z_c over this chunk
-  for (int c = k; c < d.n_configs; c += d.chunks) {
-    const Scaled z = generic_up<SumAlg>(G, c, G.up);
+  for (int c = k; c < d.n_configs; c += d.chunks) {            // a listed call: c is the index of an entry
+    EntryStates states = {nullptr, c, X};
+    ProposalFactor pf = {1.0, 0};
+    if (d.listed) {                                            // the same in every thread: the entry's address is
+      const double lq = d.log_q[(size_t)g * d.n_configs + c];
+      bool ok = log_q_ok(lq);
+      if (d.n_cut > 0) {
+        states.row = listed_row(d, g, c);
+        for (int q = 0; q < d.n_cut; ++q) ok &= (unsigned)states.row[q] < (unsigned)X;
+      }
+      if (!ok) {                                               // before st holds a state of it: st indexes the pair accumulators
+        sum = refused();
+        break;
+      }
+      pf = generic_entry_factor(lq);
+    }
+    Scaled z = generic_up<SumAlg>(G, states, G.up);
+    if (d.listed) z = weighted(z, pf);
     if (SumAlg::dead(z)) continue;                             // Z_c = 0: nothing to add
     const double w = join_sum(sum, z, [&](int shift, bool first) {           // the first Z_c clears the pair accumulators
       for (size_t i = t; i < vs; i += WG) acc[i] = ldexp(acc[i], shift);
@@ -131,6 +181,57 @@ __global__ __launch_bounds__(WG) void exactgrad_x64_kernel(GradDev d) {
     for (int i = 0; i < 64; ++i) R[s][i] = 0.0;
 
   Scaled sum = {0.0, EMPTY};                                   // sum of Z_c over this wave's configurations
+  if (d.listed) {                                              // a listed call: a loop of its own, the exact one below is as it was
+    for (int c = 4 * k + wave; c < d.n_configs; c += 4 * d.chunks) {         // c: the index of an entry; its weight where Z_c stands
+      const X64Packed state = {lane < d.n_cut ? listed_row(d, g, c)[lane] : 0};   // lane q: the state of cut position q
+      ProposalFactor pf = {1.0, 0};
+      {                                                          // (in this form the <2> instance allocates without a spill copy)
+        const double lq = d.log_q[(size_t)g * d.n_configs + c];
+        if (__any((unsigned)state.packed >= 64u) || !log_q_ok(lq)) {           // before a state of it selects a row or a cell
+          sum = refused();
+          break;
+        }
+        pf = proposal_factor(lq);                                // here, not behind the walk: fewer registers are live there
+      }
+      Scaled z = x64_up<SumAlg, true>(W, state);
+      z = weighted(z, pf);
+      if (SumAlg::dead(z)) continue;                             // Z_c = 0: nothing to add
+      const double w = join_sum(sum, z, [&](int shift, bool first) {           // the first Z_c clears the accumulators in the partial
+        for (int v = 0; v < n_vars; ++v) acc[(size_t)v * 64 + lane] = ldexp(acc[(size_t)v * 64 + lane], shift);
+        for (int p = 0; p < P; ++p) {
+          if (W.pl.fslot[p] >= 0) continue;
+          double* A = pacc + (size_t)p * 4096;
+          for (int i = lane; i < 4096; i += 64) A[i] = first ? 0.0 : ldexp(A[i], shift);
+        }
+#pragma unroll
+        for (int s = 0; s < NF; ++s)
+#pragma unroll
+          for (int i = 0; i < 64; ++i) R[s][i] = ldexp(R[s][i], shift);
+      });
+      for (int q = 0; q < d.n_cut; ++q)
+        if (lane == state(q)) acc[(size_t)W.pl.cutset[q] * 64 + lane] += w;
+      for (int i = 0; i < d.n_consts; ++i) {                     // a factor inside the cutset: its cell gains Z_c
+        if (W.pl.consts[4 * i] != MLBP_CUTSET_CONST_PAIR) continue;
+        const int s0 = state(W.pl.consts[4 * i + 2]), s1 = state(W.pl.consts[4 * i + 3]);
+        if (lane == s1) pacc[(size_t)W.pl.consts[4 * i + 1] * 4096 + s0 * 64 + lane] += w;
+      }
+      for (int i = W.n_free - 1; i >= 0; --i) {
+        const X64Down s = x64_down_step<SumAlg, true>(W, i);
+        if (s.p >= 0) {                                          // the forest factor's rank-1 update
+          const double coef = ldexp(w / s.total, -s.er);
+          const double v0 = s.v_on_axis0 ? s.a : s.b, v1 = coef * (s.v_on_axis0 ? s.b : s.a);
+#pragma unroll
+          for (int f = 0; f < NF; ++f)                           // R is indexed by constants alone: it stays in registers
+            if (s.slot == f) rank1_x64(R[f], v0, v1);
+        }
+        const double wm = w * s.x;
+        acc[(size_t)s.v * 64 + lane] += wm;
+        for (int it = W.pl.item_off[s.v]; it < W.pl.item_off[s.v + 1]; ++it)   // row s_q of every cutset-incident factor, [s_q][state of v]
+          if (W.pl.items[3 * it] != MLBP_CUTSET_ITEM_UNARY)
+            pacc[(size_t)W.pl.items[3 * it + 1] * 4096 + state(W.pl.items[3 * it + 2]) * 64 + lane] += wm;
+      }
+    }
+  } else                                                       // the exact call: the loop it has always run
   for (int c = 4 * k + wave; c < d.n_configs; c += 4 * d.chunks) {
     const Scaled z = x64_up<SumAlg, true>(W, c);
     if (SumAlg::dead(z)) continue;                             // Z_c = 0: nothing to add
@@ -198,7 +299,7 @@ __global__ __launch_bounds__(WG) void exactgrad_combine_kernel(GradDev d) {
   const bool want_expect = d.expect_ee || d.expect_ed || d.grad_ee || d.grad_ed;
   const bool want_grad = d.grad_ee || d.grad_ed;
   const double nan = __builtin_nan("");
-  if (!tables_in_range(d.pair_tab, P, d.n_pair_tables, d.unary_tab, U, d.n_unary_tables, g)) {
+  auto refuse = [&]() {                                        // the graph is not computed: NaN, its tensors left as they were
     if (t == 0) {
       d.log_z[g] = nan;
       for (int f = 0; f < F_ee; ++f) {
@@ -210,6 +311,9 @@ __global__ __launch_bounds__(WG) void exactgrad_combine_kernel(GradDev d) {
         if (d.grad_ed) d.grad_ed[(size_t)g * F_ed + f] = nan;
       }
     }
+  };
+  if (!tables_in_range(d.pair_tab, P, d.n_pair_tables, d.unary_tab, U, d.n_unary_tables, g)) {
+    refuse();
     return;
   }
   PlanSections<const_i32p> pl;
@@ -217,6 +321,10 @@ __global__ __launch_bounds__(WG) void exactgrad_combine_kernel(GradDev d) {
   const size_t XX = (size_t)X * X, stride = (size_t)d.stride;
   const SumParts parts = read_sum_parts(d.partials + (size_t)g * d.parts * stride, stride, d.parts);
   const double Z = parts.Z;
+  if (d.listed && Z != Z) {                                    // a walker refused an entry of the list (the same in every thread)
+    refuse();
+    return;
+  }
   // entry `at` of the partials (behind the two header words), summed in index order; an empty partial holds nothing
   auto summed = [&](size_t at) { return mlbp_graph::summed<true>(parts, at); };
   const size_t N = (size_t)d.n_vars * X;
@@ -329,7 +437,9 @@ __global__ __launch_bounds__(WG) void exactgrad_combine_kernel(GradDev d) {
       }
     }
   }
-  d.log_z[g] = Z == 0.0 ? -__builtin_huge_val() : fma((double)parts.emax, 0.693147180559945309417232121458, log(Z));
+  // a listed call: log_z_hat, the logarithm of the MEAN weight
+  d.log_z[g] = Z == 0.0 ? -__builtin_huge_val()
+                        : fma((double)parts.emax, 0.693147180559945309417232121458, log(d.listed ? Z / (double)d.n_configs : Z));
   for (int f = 0; f < F_ee; ++f) {
     if (d.expect_ee) d.expect_ee[(size_t)g * F_ee + f] = ex_ee[f];
     if (d.grad_ee) d.grad_ee[(size_t)g * F_ee + f] = bad ? nan : ob_ee[f] - ex_ee[f];
@@ -343,6 +453,7 @@ __global__ __launch_bounds__(WG) void exactgrad_combine_kernel(GradDev d) {
 // ---- host ----------------------------------------------------------------------------------------
 thread_local int g_last_kernel = MLBP_EXACTGRAD_KERNEL_NONE;
 static_assert(MLBP_EXACTGRAD_KERNEL_X64 == WALK_X64 && MLBP_EXACTGRAD_KERNEL_GENERIC == WALK_GENERIC, "the shared host core numbers the kernels");
+static_assert(MLBP_EXACTGRAD_MAX_CUT == MAX_LISTED_CUT, "a listed walk's bound on the cutset is the shared one");
 
 }  // namespace
 
@@ -362,24 +473,43 @@ int mlbp_exactgrad_chunks(int32_t B, int32_t n_configs, int32_t kernel) {
   return walk_chunks(B, kernel == MLBP_EXACTGRAD_KERNEL_X64 ? (n_configs + 3) / 4 : n_configs, MLBP_EXACTGRAD_MIN_WORKGROUPS);
 }
 
+// The header's workspace formula over n walked entries: the configurations of the exact call, the list's of a listed one.
+static int64_t workspace_of(int which, int32_t B, int64_t n, int32_t X, int32_t n_vars, int32_t P, int32_t U) {
+  const int chunks = mlbp_exactgrad_chunks(B, (int32_t)n, which);
+  if (chunks < 0) return chunks;
+  return (int64_t)B * chunks * chunk_doubles(which, 2 + (int64_t)n_vars * X + (int64_t)P * X * X, n_vars, P, U, X) * 8;
+}
+
 int64_t mlbp_exactgrad_workspace_bytes(int32_t B, int32_t X, int32_t n_vars, int32_t P, int32_t U, int32_t n_forest, int32_t n_cut) {
   const int which = mlbp_exactgrad_pick_kernel(X, n_vars, P, U, n_forest);
   if (which < 0) return which;
   if (n_cut < 0 || n_cut > n_vars) return fail(MLBP_EINVAL, "workspace: n_cut = %d with %d variables", n_cut, n_vars);
   const int64_t n_configs = count_configs(X, n_cut);
   if (n_configs < 0) return too_many_configs(X, n_cut);
-  const int chunks = mlbp_exactgrad_chunks(B, (int32_t)n_configs, which);
-  if (chunks < 0) return chunks;
-  return (int64_t)B * chunks * chunk_doubles(which, 2 + (int64_t)n_vars * X + (int64_t)P * X * X, n_vars, P, U, X) * 8;
+  return workspace_of(which, B, n_configs, X, n_vars, P, U);
 }
 
 int mlbp_exactgrad_check_plan(const int32_t* plan, int32_t n_words, int32_t X) { return check_packed_plan(plan, n_words, X); }
 
 int mlbp_exactgrad_f64(const mlbp_exactgrad_args* a, void* stream) {
   g_last_kernel = MLBP_EXACTGRAD_KERNEL_NONE;
-  int64_t n_configs = 0;
-  const int which = check_walk_args(a, mlbp_exactgrad_pick_kernel, [](const mlbp_exactgrad_args* a) {
+  // a negative plan_words: the struct is the `args` of a mlbp_exactgrad_listed_args and the list lies behind it
+  const mlbp_exactgrad_listed_args* list = a && a->plan_words < 0 ? reinterpret_cast<const mlbp_exactgrad_listed_args*>(a) : nullptr;
+  mlbp_exactgrad_args plain;
+  if (list) {
+    plain = *a;
+    plain.plan_words = -plain.plan_words;
+    a = &plain;
+    if (list->N < 0 || list->N > MLBP_EXACTGRAD_MAX_LISTED)
+      return fail(MLBP_EINVAL, "N = %d: a list holds 1 to %d configurations (0: the exact call)", list->N, MLBP_EXACTGRAD_MAX_LISTED);
+  }
+  const bool listed = list && list->N > 0;                     // the header's listed mode: the walk's entries are the list's
+  int64_t n_configs = listed ? list->N : 0;
+  const int which = check_walk_args(a, mlbp_exactgrad_pick_kernel, [listed, list](const mlbp_exactgrad_args* a) {
     if (!a->log_z) return fail(MLBP_EINVAL, "log_z is NULL");
+    if (listed && a->n_cut > 0 && a->n_cut <= MLBP_EXACTGRAD_MAX_CUT && !list->configs)
+      return fail(MLBP_EINVAL, "configs is NULL in a listed call with cutset variables");
+    if (listed && !list->log_q) return fail(MLBP_EINVAL, "log_q is NULL in a listed call");
     const bool want_grad = a->grad_ee || a->grad_ed;
     if (!want_grad && !a->expect_ee && !a->expect_ed) return (int)MLBP_OK;
     if (!a->phi_en_en || !a->phi_en_en_w1 || !a->phi_en_de || a->F_ee < 1 || a->F_ed < 1 || a->Vde < 1 || (a->P > 0 && !a->pair_phi) ||
@@ -390,11 +520,11 @@ int mlbp_exactgrad_f64(const mlbp_exactgrad_args* a, void* stream) {
       return fail(MLBP_EUNSUPPORTED, "F_ee = %d, F_ed = %d: at most %d features each are supported", a->F_ee, a->F_ed, MAXF);
     if (want_grad && !a->labels) return fail(MLBP_EINVAL, "grad_* needs labels");
     return (int)MLBP_OK;
-  }, &n_configs);
+  }, &n_configs, listed);
   if (which < 0) return which;
   const int chunks = mlbp_exactgrad_chunks(a->B, (int32_t)n_configs, which);
   if (chunks < 0) return chunks;
-  if (int e = check_walk_workspace(a, mlbp_exactgrad_workspace_bytes(a->B, a->X, a->n_vars, a->P, a->U, a->n_forest, a->n_cut))) return e;
+  if (int e = check_walk_workspace(a, workspace_of(which, a->B, n_configs, a->X, a->n_vars, a->P, a->U))) return e;
   if (int e = check_device("libmlbp_exactgrad.so")) return e;
   const bool want_expect = a->grad_ee || a->grad_ed || a->expect_ee || a->expect_ed;
   GradDev d;
@@ -405,6 +535,9 @@ int mlbp_exactgrad_f64(const mlbp_exactgrad_args* a, void* stream) {
   d.expect_ee = a->expect_ee; d.expect_ed = a->expect_ed; d.grad_ee = a->grad_ee; d.grad_ed = a->grad_ed;
   d.stride = 2 + (int64_t)a->n_vars * a->X + (int64_t)a->P * a->X * a->X;
   d.F_ee = want_expect ? a->F_ee : 0; d.F_ed = want_expect ? a->F_ed : 0; d.Vde = a->Vde;
+  d.listed = listed;                                           // N == 0: the two fields are not looked at, whatever they hold
+  d.configs = listed && a->n_cut > 0 ? list->configs : nullptr;
+  d.log_q = listed ? list->log_q : nullptr;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(a->B, chunks);
   (void)hipGetLastError();

@@ -442,6 +442,35 @@ class UserGraphTrainer:
         bp_ee, bp_ed, _ = self._bp_gradient()
         return g_ee, g_ed, joint.cpu().numpy(), bp_ee, bp_ed
 
+    def estimated_gradient(self, n_list=256, seed=0, proposal='messages'):
+        """The sentence shapes exact_gradient() refuses: an ESTIMATE of the gradient of the true likelihood of each instance
+        under the current thetas over a list of n_list cutset states (FactorGraphBatch.cutset_gradient, the feature planes'
+        share from the estimated marginals included): host (g_ee float64 [B][F_ee], g_ed float64 [B][F_ed], joint_logp_hat
+        float64 [B] -- the log-potential of the stored labels minus log_z_hat --, log_z_hat float64 [B]).  log_partition over
+        the predict() schedule runs first: it gives the labels' log-potential and leaves the messages the list is drawn from
+        (proposal='messages': FactorGraphBatch.cutset_draw(n_list, seed=seed)); proposal='sample' draws the list with
+        cutset_proposal(), which sweeps again for every draw.  Raises cutsetis.CutsetisError(MLBP_EUNSUPPORTED) for a shape the
+        listed plan refuses (more than 16 cutset variables)."""
+        if proposal not in ('sample', 'messages'):
+            raise ValueError("proposal must be 'sample' or 'messages', not %r" % (proposal,))
+        fb, topo = self.batch, self.topo
+        self.build_potentials()
+        roots = self.roots[:self.n_sweeps_run]
+        score = torch.empty(fb.B, dtype=torch.float64, device=self.device)
+        fb.log_partition(roots, init=True, labels=fb._labels, score=score)
+        if proposal == 'messages':
+            configs, log_q = fb.cutset_draw(n_list, seed=int(seed))
+        else:
+            configs, log_q = fb.cutset_proposal(roots, n_list, seed=int(seed))
+        est = torch.empty(fb.B, topo.n_vars, fb.X, dtype=torch.float64, device=self.device)
+        g_ee, g_ed, log_z_hat = fb.cutset_gradient(configs, log_q, marginals=est)
+        g_ee, g_ed = g_ee.cpu().numpy(), g_ed.cpu().numpy()
+        if self.n_priv:                                         # as exact_gradient(): the unary factor's belief is its variable's marginal
+            est = est.cpu().numpy()
+            var_of = [int(topo.fac_var[2 * topo.unary_factors[u]]) for _, u in self._priv_rows]
+            g_ed = g_ed + self._plane_share(np.stack([est[b_i, v] for (b_i, _), v in zip(self._priv_rows, var_of)]))
+        return g_ee, g_ed, (score - log_z_hat).cpu().numpy(), log_z_hat.cpu().numpy()
+
     def exact_decode(self):
         """The TRUE jointly most probable set of guesses of every instance under the current thetas
         (FactorGraphBatch.exact_map), and how decode() fared against it: host (assignment int64 [B][n_vars] word indices in
@@ -1238,6 +1267,73 @@ class TiDirTrainer:
         stats = stats[:n] + stats[n:]
         update_thetas(self, stats, learning_rate, reg_param, self.reg_param_ua_scale)
         return float(stats[n - 2].item() / max(stats[n - 1].item(), 1.0)), n_fallback
+
+    # ---- and a step for every sentence: the gradient estimated beyond the exact limit (the listed mode of include/mlbp_exactgrad.h) ----
+    def estimated_step(self, learning_rate, reg_param, n_list=256, seed=0, proposal='messages'):
+        """exact_step() for EVERY sentence: the same statistics vector and single all-reduce, where a shape the exact call
+        admits contributes UserGraphTrainer.exact_gradient() and every other shape UserGraphTrainer.estimated_gradient(n_list,
+        seed + i, proposal) -- i its position in self.trainers order --, its joint_logp_hat in the place of joint_logp.  No
+        sentence falls back to BP and none is skipped; a shape the listed plan refuses (more than 16 cutset variables) raises
+        cutsetis.CutsetisError.  On a file whose shapes the exact call admits it IS exact_step(): the same thetas bit for bit.
+        Returns (mean log-likelihood of the instances at the thetas they were evaluated under -- estimated where the gradient
+        is --, instances estimated, over all ranks).  Per-domain thetas are not supported.  Not captured into the step graph."""
+        from . import exactgrad as K
+        if self.domains:
+            raise NotImplementedError('estimated_step does not update per-domain thetas')
+        n = self.n_stat
+
+        def call(i, tr):
+            exact, e = _try(tr.exact_gradient, K.ExactGradError)
+            if e is None:
+                return exact[:3] + (0,)
+            return tr.estimated_gradient(n_list=n_list, seed=int(seed) + i, proposal=proposal)[:3] + (1,)
+        _, shapes = self._per_shape(call)
+        grad, tail = np.zeros(n - 2), np.zeros(n)
+        loglik, seen = 0.0, 0
+        for _, rows, (g_ee, g_ed, joint, estimated) in shapes:
+            seen += len(rows)
+            loglik += float(joint.sum())
+            grad += np.concatenate([g_ee.sum(axis=0), g_ed.sum(axis=0)])
+            tail[n - 1] += estimated * len(rows)
+        stats = torch.tensor(list(grad) + [loglik, float(seen)] + list(tail), dtype=torch.float64, device=self.device)
+        mdist.all_reduce_sum_(stats)
+        n_estimated = int(stats[2 * n - 1].item())
+        stats = stats[:n] + torch.cat([stats[n:2 * n - 1], torch.zeros(1, dtype=torch.float64, device=self.device)])
+        update_thetas(self, stats, learning_rate, reg_param, self.reg_param_ua_scale)
+        return float(stats[n - 2].item() / max(stats[n - 1].item(), 1.0)), n_estimated
+
+    def estimated_gradient_report(self, n_list=256, seed=0):
+        """-> totals: the estimated gradient over ALL shapes under the current thetas, and how far it is from the true one
+        where the exact call exists.  totals = (estimate [F_ee + F_ed] -- UserGraphTrainer.estimated_gradient(n_list, seed + i)
+        summed over every instance --, exact [F_ee + F_ed] -- UserGraphTrainer.exact_gradient() summed over the instances of
+        the shapes it admits --, the estimate summed over those same instances, the cosine of the last two, |estimate - exact|
+        / |exact| of the same, sum of joint_logp_hat over every instance, instances, instances also solved exactly) over ALL
+        ranks' instances, reduced once.  The two distances are figures to record: nothing bounds them."""
+        from . import exactgrad as K
+        F = self.n_stat - 2
+
+        def call(i, tr):
+            est = tr.estimated_gradient(n_list=n_list, seed=int(seed) + i)
+            exact, _ = _try(tr.exact_gradient, K.ExactGradError)           # above the exact limit: estimated alone
+            return est[:3] + (None if exact is None else exact[:2],)
+        _, shapes = self._per_shape(call)
+        est, exact, est_on = np.zeros(F), np.zeros(F), np.zeros(F)
+        loglik, seen, both = 0.0, 0, 0
+        for _, rows, (g_ee, g_ed, joint_hat, x) in shapes:
+            g = np.concatenate([g_ee.sum(axis=0), g_ed.sum(axis=0)])
+            seen += len(rows)
+            loglik += float(joint_hat.sum())
+            est += g
+            if x is not None:
+                both += len(rows)
+                est_on += g
+                exact += np.concatenate([x[0].sum(axis=0), x[1].sum(axis=0)])
+        tot, _ = self._reduced(list(est) + list(exact) + list(est_on) + [loglik, seen, both])
+        est, exact, est_on = tot[:F], tot[F:2 * F], tot[2 * F:3 * F]
+        ne, no = float(np.linalg.norm(exact)), float(np.linalg.norm(est_on))
+        cosine = float(exact.dot(est_on)) / (ne * no) if ne > 0 and no > 0 else float('nan')
+        rel = float(np.linalg.norm(est_on - exact)) / ne if ne > 0 else float('nan')
+        return est, exact, est_on, cosine, rel, float(tot[3 * F]), int(tot[3 * F + 1]), int(tot[3 * F + 2])
 
     # ---- which guesses are truly the best: exact joint decoding (include/mlbp_exactmap.h) ------------
     def exact_decode(self):
