@@ -88,6 +88,44 @@
  * every other graph keeps its bits.  A NaN, negative or +inf entry: that graph's states lie in [0, X) or are -1, its scores
  * and n_found are unspecified; the call returns and every other graph keeps its bits.  More than MLBP_CUTSET_MAX_CONFIGS
  * configurations: MLBP_EUNSUPPORTED.  M outside [1, MLBP_EXACTMBEST_MAX_M]: MLBP_EINVAL.
+ *
+ * The listed mode: the M best over LISTED cutset states (N > 0).  Beyond MLBP_CUTSET_MAX_CONFIGS configurations -- K5 and up at
+ * X = 64 -- the walk cannot visit every configuration; it can visit a caller's list of them, as the listed mode of
+ * mlbp_exactmap_f64 does for the maximum.  With N > 0 the call reads `configs`, N rows of n_cut states per graph (row i, entry
+ * q: the state of cutset[q]), and walks those rows in the place of the configurations c in [0, X^|C|): "configuration" in facts
+ * (1) and (2) above reads "entry".  V_i is the V_c above at configuration configs[g][i]; every assignment whose cutset state is
+ * entry i scores at most V_i, and under one entry the remainder is a forest, which the list form solves exactly.  So the rows
+ * are the TRUE M best among ALL assignments of positive potential whose cutset state equals some listed row -- a guarantee that
+ * needs no statistics --, best first and pairwise distinct; n_found = min(M, their number); the rows behind it read -1 / -inf.
+ *   Duplicates.  A list may repeat a cutset state (a search list draws with replacement).  An entry whose row equals the row of
+ *   an entry of lower index is IGNORED: the first occurrence counts, so no row of the result repeats.  V_i is a function of the
+ *   graph, the cutset and the row alone, so equal rows have equal V bits: the select closes the duplicates of a taken entry
+ *   inside its scans -- an open entry whose V pair equals the pair of the at most M taken entries is compared with them row
+ *   against row, and rows are compared nowhere else.  The select stays at M rounds however many repeats the list holds.
+ *   Order.  Candidates go by value descending, compared as (mantissa, exponent) pairs; ties go to the lower entry index, then
+ *   to the lower rank inside the entry.  The prefix property in M holds unchanged.  Row 0 is the listed mlbp_exactmap_f64's
+ *   answer on the same list wherever the best set is not tied inside its entry, and entries[0] its `entry`.  The full list in
+ *   index order returns the exact call's rows, scores and n_found in every bit, and entries equal to the configuration numbers.
+ *   The bits of every output depend on the graph, the cutset, the list and M's prefix alone -- not on B, the position in the
+ *   batch, shared or unique tables, the chunk count or which wave walked what.
+ *   Edge rules.  A state outside [0, X) anywhere in the graph's rows of configs: the graph is not computed -- n_found = -1, its
+ *   assignments -1, its scores NaN, its entries -1; every other graph keeps its bits.  A state is validated BEFORE it forms an
+ *   address: by a ballot over the packed row in the X = 64 values kernel, by a loop over the row in the generic one; such an entry
+ *   gets a marker in the place of its V pair, the select refuses the graph on it, and the lists pass reads rows of graphs that
+ *   were not refused alone.  A table index outside its array: as above, and entries -1.  n_cut == 0 is valid: there is one empty
+ *   configuration, configs is not read, and the call equals the exact call on a forest (entries 0).
+ *   Limits.  0 <= N <= MLBP_EXACTMBEST_MAX_LISTED (else MLBP_EINVAL); at most MLBP_EXACTMBEST_MAX_CUT cutset variables and no
+ *   bound on X^|C| (MLBP_EUNSUPPORTED beyond).  The kernel pick is the rule below, unchanged.
+ *   Grid of the values pass (B, C), C = mlbp_exactmbest_chunks(B, N): workgroup (g, k) of the generic kernel walks entries k,
+ *   k + C, ..., wave w of workgroup (g, k) of the X = 64 kernel 4 k + w, 4 k + w + 4 C, ...; V_i is written apart as a pair into
+ *   slot i.  The select runs over the N entries by entry index; both lists kernels read the selected entry's row from configs
+ *   where they decode c; the merge breaks ties by entry index and writes `entries`.
+ *   Workspace of a listed call: the formula of mlbp_exactmbest_workspace_bytes below with N in the place of n_configs and
+ *   C = mlbp_exactmbest_chunks(B, N).  mlbp_exactmbest_workspace_bytes states the exact call alone; the compute entry checks
+ *   this formula itself.
+ *   Plan.  mlbp_exactmbest_check_plan keeps the exact call's bound on X^|C|; validate the plan of a listed call with
+ *   mlbp_cutsetis_check_plan (include/mlbp_cutsetis.h), whose bound is the listed one.
+ * With N == 0 every field of the listed mode is ignored (entries apart, see the struct) and the call is the exact call.
  */
 #ifndef MLBP_EXACTMBEST_H
 #define MLBP_EXACTMBEST_H
@@ -132,6 +170,8 @@ extern "C" {
 #define MLBP_EXACTMBEST_MAX_M 16
 #define MLBP_EXACTMBEST_DROP_BELOW 1000      /* a list entry of rank >= 1 below 2^-1000 of its vector's largest is dropped */
 #define MLBP_EXACTMBEST_LISTS_FIXED 384      /* the lists kernel's LDS beside INTS and its lists: scratch, F, R */
+#define MLBP_EXACTMBEST_MAX_LISTED 65536     /* the most entries a list holds per graph */
+#define MLBP_EXACTMBEST_MAX_CUT 16           /* the most cutset variables of a listed call */
 
 typedef struct mlbp_exactmbest_args {
   int32_t B, X, n_vars, P, U;                /* graphs, states, variables, pairwise / unary factors */
@@ -139,6 +179,7 @@ typedef struct mlbp_exactmbest_args {
   int32_t n_pair_tables, n_unary_tables;
   int32_t plan_words;
   int32_t M;                                 /* rows asked for, 1 .. MLBP_EXACTMBEST_MAX_M */
+  int32_t N;                                 /* 0: the exact call; 1 .. MLBP_EXACTMBEST_MAX_LISTED: entries listed per graph */
   const int32_t* plan;                       /* device [plan_words], validated by mlbp_exactmbest_check_plan before upload */
   const double* pair_tables;                 /* device [n_pair_tables][X][X] row-major (NULL when P == 0) */
   const int32_t* pair_tab;                   /* device [B][P] table of graph g's pairwise factor p */
@@ -149,6 +190,10 @@ typedef struct mlbp_exactmbest_args {
   int32_t* assignments;                      /* device [B][M][n_vars] */
   double* scores;                            /* device [B][M] */
   int32_t* n_found;                          /* device [B] */
+  const int32_t* configs;                    /* listed call: device [B][N][n_cut], the state of cutset[q]; NULL when N == 0 or n_cut == 0 */
+  int32_t* entries;                          /* optional device [B][M]: the index of the list entry every row lies under (listed
+                                                call) or its configuration number (exact call); -1 for the rows at or beyond
+                                                n_found and for a graph that is not computed */
 } mlbp_exactmbest_args;
 
 /* Table indices are device data and are not checked on the host: see the edge rules above. */

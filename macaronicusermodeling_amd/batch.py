@@ -844,6 +844,51 @@ class FactorGraphBatch:
         K.check(K.lib.mlbp_exactmbest_f64(C.byref(a), _stream_ptr(self.device)))
         return assignments, scores, n_found
 
+    # ---- the M best among listed cutset states (the listed mode of include/mlbp_exactmbest.h) ------------------
+    def cutset_mbest(self, configs, m, cutset=None, entries=False):
+        """The TRUE `m` best assignments among ALL assignments whose cutset state is LISTED, best first -- for the graphs whose
+        cutset has more joint states than exact_mbest() walks (K5 and up at X = 64).  configs: contiguous int32 [B][N][n_cut]
+        device tensor as cutset_map() takes it; 1 <= N <= 65536, 1 <= m <= 16.  Returns (assignments int32 [B][m][n_vars],
+        scores float64 [B][m], n_found int32 [B]) device tensors as exact_mbest() does, and with entries=True also entries
+        int32 [B][m]: the index of the list entry every row lies under, -1 behind n_found.  An entry whose cutset state repeats
+        that of an entry of lower index is ignored, so the rows are pairwise distinct; ties go to the lower entry index, then to
+        the lower rank inside the entry.  Row 0 is cutset_map()'s answer on the same list; the full list in index order
+        returns exact_mbest()'s bits.  A graph with a state outside [0, X) in its list gets n_found -1, assignments -1,
+        scores NaN and entries -1.  The bits depend on the graph, the cutset, the list and m's prefix alone.  cutset: as in
+        cutset_map.  self.msgs is neither read nor written."""
+        from . import cutsetis as KP, exactmbest as K
+        if not 1 <= int(m) <= K.MAX_M:
+            raise ValueError('m must be in [1, %d]' % K.MAX_M)
+        topo, m = self.topo, int(m)
+        pl, a = self._cutset_args(KP, K.ExactMbestArgs, cutset, 'cutset_mbest needs float64 pairwise tables')    # the listed check of the plan
+        configs_ptr = self._tensor(configs, (self.B, None, pl.n_cut), 'configs', '[B][N][n_cut]', dtype=torch.int32)
+        a.N = N = _listed_count(configs.shape[1], K, 'N')
+        if pl.n_cut:
+            a.configs = configs_ptr
+        assignments = torch.empty(self.B, m, topo.n_vars, dtype=torch.int32, device=self.device)
+        scores = torch.empty(self.B, m, dtype=torch.float64, device=self.device)
+        n_found = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        a.M, a.assignments, a.scores, a.n_found = m, assignments.data_ptr(), scores.data_ptr(), n_found.data_ptr()
+        under = None
+        if entries:
+            under = torch.empty(self.B, m, dtype=torch.int32, device=self.device)
+            a.entries = under.data_ptr()
+        work = self._workspace(a, K.listed_workspace_bytes(self.B, self.X, topo.n_vars, topo.P, topo.U, pl.n_forest, N, m))
+        K.check(K.lib.mlbp_exactmbest_f64(C.byref(a), _stream_ptr(self.device)))
+        return (assignments, scores, n_found, under) if entries else (assignments, scores, n_found)
+
+    def search_mbest(self, roots, m, n_samples=256, seed=0, uniforms=None, cutset=None):
+        """Ranked search decoding beyond exact_mbest()'s limit: cutset_mbest() over search_map()'s list -- entry 0 the cutset
+        state of map_sweep(roots)'s assignment, entries 1 to n_samples - 1 cutset_draw() draws on the messages of
+        sweep(roots, init=True); both write self.msgs.  Returns (assignments int32 [B][m][n_vars], scores float64 [B][m],
+        n_found int32 [B], score_bp float64 [B]) device tensors, score_bp the score of map_sweep's assignment:
+        scores[:, 0] >= score_bp up to the rounding of the two sums of logarithms, because the max-product assignment is among
+        those the list admits.  The rows are the true m best among the assignments whose cutset state was listed; the draws
+        repeat states, and a repeat counts once.  seed / uniforms and cutset: as in search_map."""
+        configs, _, score_bp = self._search_list(roots, n_samples, seed, uniforms, cutset)
+        assignments, scores, n_found = self.cutset_mbest(configs, m, cutset=cutset)
+        return assignments, scores, n_found, score_bp
+
     # ---- whole assignments drawn from the model itself (include/mlbp_exactsample.h) ---------------------
     def exact_sample(self, n_samples=1, seed=None, uniforms=None, cutset=None, log_z=False, score=False):
         """Draws n_samples whole assignments per graph from the MODEL ITSELF by cutset conditioning -- what sample() does only

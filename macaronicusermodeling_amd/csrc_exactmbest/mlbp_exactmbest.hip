@@ -15,6 +15,10 @@
 //                                     per state, tables streamed; the candidates decoded by back-pointers, a thread each.
 //   exactmbest_merge_kernel           one workgroup per graph, a thread per candidate: its rank by counting, the rows, the
 //                                     logarithms.
+// A LISTED call (N > 0, the header's listed mode) runs the same six kernels over the caller's list of cutset states: a
+// configuration's number is then the index of a list entry and the states come from the entry's row of configs -- the values
+// kernels in loops of their own (ListedStates, X64Packed), the select over the entries with the duplicate rule, the lists
+// kernels reading the selected entry's row where they decode c, the merge breaking ties by entry index.
 // No sum is formed and nothing is merged before the merge, so the bits of a result are a function of the graph, the cutset and
 // M's prefix alone.  Every scalar a workgroup branches on comes out of a reduction or workgroup-uniform memory and has the same
 // bits in every thread of it.  No device-side mutable globals: everything comes through MbestDev.
@@ -46,6 +50,35 @@ struct MbestDev : WalkDev {
   int32_t x64_bytes, wave_bytes;             // the X = 64 lists kernel: x64_open's LDS, and a wave's own behind it
   int32_t* assignments; double* scores; int32_t* n_found;
   int32_t M;
+  const int32_t* configs;                    // a listed call with cutset variables: [B][n_configs][n_cut]; else NULL
+  int32_t* entries;                          // optional [B][M]
+};
+
+// A listed call: n_configs is N, a configuration's number the index of a list entry, and the entry's states are its row of
+// configs where the exact call decodes c.  Without cutset variables configs is NULL and the list is the one empty configuration:
+// the host hands over n_configs = 1 and every kernel runs as in the exact call.  A values walker that meets a row with a state
+// outside [0, X) writes BAD_ENTRY in the place of the pair's exponent, before any state forms an address; the select then
+// refuses the graph (REFUSED in the place of the number of selected entries) and no lists task reads a row of it.
+constexpr double BAD_ENTRY = 1e300;          // no exponent reads so
+constexpr int REFUSED = -1;
+
+__device__ __forceinline__ const_i32p listed_row(const MbestDev& d, int g, int i) {
+  return as_const(d.configs) + ((size_t)g * d.n_configs + i) * d.n_cut;
+}
+
+// the row's address is the same in every thread of the walker, and so is the answer
+__device__ __forceinline__ bool row_in_range(const_i32p row, int n_cut, int X) {
+  bool ok = true;
+  for (int q = 0; q < n_cut; ++q) ok &= (unsigned)row[q] < (unsigned)X;
+  return ok;
+}
+
+// Where the X = 64 lists kernel takes the state of cut position q: lane q of `packed` (the selected entry's row, a listed call)
+// or the digits of c.  A scalar either way.
+struct X64Selected {
+  int packed, c;
+  bool listed;
+  __device__ __forceinline__ int operator()(int q) const { return listed ? __builtin_amdgcn_readlane(packed, q) : x64_state(q, c); }
 };
 
 // Does the pair a exceed the pair b?  A pair without a positive mantissa exceeds nothing.
@@ -129,6 +162,24 @@ __global__ __launch_bounds__(WG) void exactmbest_values_generic_kernel(MbestDev 
   generic_carve(G, d, g, k, smem);
   generic_setup(G);
   double* out = d.vc + (size_t)g * d.n_configs * 2;
+  if (d.configs) {                                             // a listed call: its own loop, the exact one below is as it was
+    for (int i = k; i < d.n_configs; i += d.chunks) {
+      const const_i32p row = listed_row(d, g, i);
+      if (!row_in_range(row, d.n_cut, d.X)) {
+        if (t == 0) {
+          out[2 * i] = 0.0;
+          out[2 * i + 1] = BAD_ENTRY;
+        }
+        continue;
+      }
+      const Scaled z = generic_up<MaxAlg>(G, ListedStates{row}, nullptr);
+      if (t == 0) {
+        out[2 * i] = z.m;
+        out[2 * i + 1] = (double)z.e;
+      }
+    }
+    return;
+  }
   for (int c = k; c < d.n_configs; c += d.chunks) {
     const Scaled z = generic_up<MaxAlg>(G, c, nullptr);
     if (t == 0) {
@@ -145,6 +196,19 @@ __global__ __launch_bounds__(WG) void exactmbest_values_x64_kernel(MbestDev d) {
   X64 W;
   x64_open(W, d, g, smem);
   double* out = d.vc + (size_t)g * d.n_configs * 2;
+  if (d.configs) {                                             // a listed call: its own loop, the exact one below is as it was
+    for (int i = 4 * k + wave; i < d.n_configs; i += 4 * d.chunks) {
+      const int packed = lane < d.n_cut ? listed_row(d, g, i)[lane] : 0;
+      const bool bad = __any((unsigned)packed >= 64u);
+      Scaled z = {0.0, 0};
+      if (!bad) z = x64_up<MaxAlg, false>(W, X64Packed{packed});
+      if (lane == 0) {
+        out[2 * i] = bad ? 0.0 : z.m;
+        out[2 * i + 1] = bad ? BAD_ENTRY : (double)z.e;
+      }
+    }
+    return;
+  }
   for (int c = 4 * k + wave; c < d.n_configs; c += 4 * d.chunks) {
     const Scaled z = x64_up<MaxAlg, false>(W, c);
     if (lane == 0) {
@@ -169,6 +233,58 @@ __global__ __launch_bounds__(WG) void exactmbest_select_kernel(MbestDev d) {
   constexpr double NONE = -1e300;
   double pm = 0.0, pe = 0.0;                                   // the configuration taken last
   int pc = -1, found = 0;
+  if (d.configs) {                                             // a listed call: its own rounds, the exact ones below are as they were
+    // An entry whose row equals the row of an entry of lower index is ignored.  Equal rows have equal V bits and the lower
+    // index is taken first, so a duplicate is an open entry whose pair equals the pair taken last and whose row equals the row
+    // of one of the entries taken with that pair: taken[same .. r).  Rows are compared nowhere else.
+    __shared__ int taken[MAXM];
+    int bad = 0;
+    for (int c = t; c < n; c += WG) bad |= vc[2 * c + 1] == BAD_ENTRY;
+    if (block_max(bad ? 1.0 : 0.0, scratch) > 0.0) {           // a state outside [0, X): the graph is not computed
+      if (t == 0) sel[M] = (double)REFUSED;
+      return;
+    }
+    int same = 0;
+    for (int r = 0; r < M; ++r) {
+      auto open = [&](int c, double m, double e) {
+        if (!(m > 0.0)) return false;
+        if (pc < 0 || e < pe || (e == pe && m < pm)) return true;
+        if (!(e == pe && m == pm && c > pc)) return false;
+        const const_i32p row = listed_row(d, g, c);
+        for (int k = same; k < r; ++k) {
+          const const_i32p other = listed_row(d, g, taken[k]);
+          bool equal = true;
+          for (int q = 0; q < d.n_cut; ++q) equal &= row[q] == other[q];
+          if (equal) return false;
+        }
+        return true;
+      };
+      double be = NONE;
+      for (int c = t; c < n; c += WG)
+        if (open(c, vc[2 * c], vc[2 * c + 1])) be = fmax(be, vc[2 * c + 1]);
+      be = block_max(be, scratch);
+      if (!(be > NONE)) break;
+      double bm = 0.0;
+      for (int c = t; c < n; c += WG)
+        if (vc[2 * c + 1] == be && open(c, vc[2 * c], be)) bm = fmax(bm, vc[2 * c]);
+      bm = block_max(bm, scratch);
+      unsigned bc = 0xffffffffu;
+      for (int c = t; c < n; c += WG)
+        if (vc[2 * c + 1] == be && vc[2 * c] == bm && open(c, bm, be)) { bc = (unsigned)c; break; }
+      bc = block_min_index(bc, scratch);
+      if (bc == 0xffffffffu) break;
+      if (t == 0) {
+        sel[r] = (double)bc;
+        taken[r] = (int)bc;
+      }
+      if (!(bm == pm && be == pe)) same = r;
+      pm = bm; pe = be; pc = (int)bc;
+      ++found;
+      __syncthreads();                                         // taken[r]: read by every thread's scans of the next round
+    }
+    if (t == 0) sel[M] = (double)found;
+    return;
+  }
   for (int r = 0; r < M; ++r) {
     // is c behind the last one taken?
     auto open = [&](int c, double m, double e) {
@@ -237,7 +353,7 @@ __global__ __launch_bounds__(WG) void exactmbest_lists_generic_kernel(MbestDev d
   if (t < G.n_cut) {
     int q = c;
     for (int i = 0; i < t; ++i) q /= X;
-    G.st[t] = q % X;
+    G.st[t] = d.configs ? listed_row(d, g, c)[t] : q % X;      // a listed call: the selected entry's row, validated by the values pass
   }
   __syncthreads();
   Scaled z = {1.0, G.e_fixed};                                 // the configuration's constants, as generic_up takes them
@@ -451,16 +567,18 @@ __global__ __launch_bounds__(WG) void exactmbest_lists_x64_kernel(MbestDev d) {
 
   for (int r = 4 * kb + wave; r < n_sel; r += 4 * d.chunks) {
     const int c = (int)d.sel[(size_t)g * (M + 1) + r];
+    // a listed call: lane q holds the state of cut position q of the selected entry, validated by the values pass
+    const X64Selected state = {d.configs && lane < W.n_cut ? listed_row(d, g, c)[lane] : 0, c, d.configs != nullptr};
     Scaled z = {1.0, W.e_fixed};                               // the configuration's constants, as x64_up takes them
-    for (int q = 0; q < W.n_cut; ++q) mul(z, W.base[(size_t)W.pl.cutset[q] * 64 + x64_state(q, c)]);
+    for (int q = 0; q < W.n_cut; ++q) mul(z, W.base[(size_t)W.pl.cutset[q] * 64 + state(q)]);
     for (int i = 0; i < W.n_consts; ++i) {
       if (W.pl.consts[4 * i] != MLBP_CUTSET_CONST_PAIR) continue;
-      const int f = W.pl.consts[4 * i + 1], s0 = x64_state(W.pl.consts[4 * i + 2], c), s1 = x64_state(W.pl.consts[4 * i + 3], c);
+      const int f = W.pl.consts[4 * i + 1], s0 = state(W.pl.consts[4 * i + 2]), s1 = state(W.pl.consts[4 * i + 3]);
       mul(z, ldexp(W.pair_tables[(size_t)W.ptab[f] * 4096 + s0 * 64 + s1], -W.texp[f]));
     }
     for (int i = 0; i < W.n_free; ++i) {
       const int v = W.pl.order[i];
-      W.bel[(size_t)v * 64 + lane] = x64_local(W, v, c);
+      W.bel[(size_t)v * 64 + lane] = x64_local(W, v, state);
     }
     if (lane < n_vars) lslot[lane] = -1;
     double Fm = lane == 0 ? z.m : 0.0;                         // F: lane k holds entry k
@@ -557,7 +675,7 @@ __global__ __launch_bounds__(WG) void exactmbest_lists_x64_kernel(MbestDev d) {
       for (int v = 0; v < n_vars; ++v) xs[v] = -1;
       continue;
     }
-    for (int q = 0; q < W.n_cut; ++q) xs[W.pl.cutset[q]] = x64_state(q, c);
+    for (int q = 0; q < W.n_cut; ++q) xs[W.pl.cutset[q]] = state(q);
     int rf = lane;                                             // the rank in F as it stood behind the root at hand
     for (int i = W.n_free - 1; i >= 0; --i) {
       const int v = W.pl.order[i], p = W.pl.parent[2 * v];
@@ -586,9 +704,13 @@ __global__ __launch_bounds__(WG) void exactmbest_merge_kernel(MbestDev d) {
   const int X = d.X, M = d.M, n_vars = d.n_vars;
   int32_t* rows = d.assignments + (size_t)g * M * n_vars;
   double* scores = d.scores + (size_t)g * M;
-  if (!tables_in_range(d.pair_tab, d.P, d.n_pair_tables, d.unary_tab, d.U, d.n_unary_tables, g)) {
+  int32_t* entries = d.entries ? d.entries + (size_t)g * M : nullptr;
+  // a table index outside its array, or (a listed call) a state outside [0, X): the graph is not computed
+  if (!tables_in_range(d.pair_tab, d.P, d.n_pair_tables, d.unary_tab, d.U, d.n_unary_tables, g) ||
+      (int)d.sel[(size_t)g * (M + 1) + M] == REFUSED) {
     for (int i = t; i < M * n_vars; i += WG) rows[i] = -1;
     if (t < M) scores[t] = __builtin_nan("");
+    if (t < M && entries) entries[t] = -1;
     if (t == 0) d.n_found[g] = -1;
     return;
   }
@@ -612,7 +734,9 @@ __global__ __launch_bounds__(WG) void exactmbest_merge_kernel(MbestDev d) {
   if (mine && ahead < M) {
     const int32_t* xs = d.cxs + ((size_t)g * n + t) * n_vars;
     for (int v = 0; v < n_vars; ++v) rows[(size_t)ahead * n_vars + v] = xs[v];
+    if (entries) entries[ahead] = c;
   }
+  if (entries && t >= found && t < M) entries[t] = -1;
   for (int i = t; i < (M - found) * n_vars; i += WG) rows[(size_t)found * n_vars + i] = -1;
   if (t == 0) d.n_found[g] = found;
   __syncthreads();
@@ -656,6 +780,24 @@ int pick_lists_kernel(int values, int64_t n_vars, int64_t P, int64_t U, int64_t 
   return values == WALK_X64 && x64_lds_bytes(n_vars, P, U, n_forest) + 4 * x64_wave_bytes(n_forest, M) <= MLBP_CUTSET_X64_LDS_BYTES ? WALK_X64 : WALK_GENERIC;
 }
 
+int64_t lists_bytes_of(int64_t X, int64_t n_vars, int64_t M) {
+  const int64_t Xp = (X + 1) / 2 * 2, vl = X * M;
+  const int64_t bytes = 8 * (n_vars * Xp + n_vars * vl + vl) + 4 * M * n_vars + 4 * n_vars * vl + 4 * n_vars * M;
+  return (bytes + 7) / 8 * 8;
+}
+
+// The header's workspace formula over n walked configurations in `chunks` chunks: X^|C| of an exact call, N of a listed one.
+// `which` is the library's kernel pick, so the sizes have been checked.
+int64_t workspace_of(int which, int64_t B, int64_t X, int64_t n_vars, int64_t P, int64_t U, int64_t n, int64_t chunks, int64_t M) {
+  const int64_t lb = lists_bytes_of(X, n_vars, M);
+  const bool spill_walk = (which & 15) == WALK_GENERIC && generic_lds_bytes(n_vars, P, U, X) > MLBP_CUTSET_GENERIC_LDS_BYTES;
+  const bool spill_lists = which >> 4 == WALK_GENERIC && lists_fixed_bytes(P, U) + lb > MLBP_CUTSET_GENERIC_LDS_BYTES;
+  return (B * n * 2 + B * (M + 1) + B * M * M * 2 + (B * M * M * n_vars + 1) / 2 +
+          (spill_walk ? B * chunks * vector_doubles(n_vars, X) : 0) + (spill_lists ? B * M * lb / 8 : 0)) * 8;
+}
+
+static_assert(MLBP_EXACTMBEST_MAX_CUT == MAX_LISTED_CUT, "the header states the shared walk's bound");
+
 }  // namespace
 
 extern "C" {
@@ -681,9 +823,7 @@ int mlbp_exactmbest_chunks(int32_t B, int32_t n_configs) {
 int64_t mlbp_exactmbest_lists_bytes(int32_t X, int32_t n_vars, int32_t M) {
   if (X < 2 || n_vars <= 0) return fail(MLBP_EINVAL, "lists_bytes: X = %d, n_vars = %d", X, n_vars);
   if (int e = check_m(M)) return e;
-  const int64_t Xp = (X + 1) / 2 * 2, vl = (int64_t)X * M;
-  const int64_t bytes = 8 * ((int64_t)n_vars * Xp + n_vars * vl + vl) + 4 * (int64_t)M * n_vars + 4 * n_vars * vl + 4 * (int64_t)n_vars * M;
-  return (bytes + 7) / 8 * 8;
+  return lists_bytes_of(X, n_vars, M);
 }
 
 int64_t mlbp_exactmbest_workspace_bytes(int32_t B, int32_t X, int32_t n_vars, int32_t P, int32_t U, int32_t n_forest, int32_t n_cut,
@@ -695,32 +835,38 @@ int64_t mlbp_exactmbest_workspace_bytes(int32_t B, int32_t X, int32_t n_vars, in
   if (n_configs < 0) return too_many_configs(X, n_cut);
   const int chunks = mlbp_exactmbest_chunks(B, (int32_t)n_configs);
   if (chunks < 0) return chunks;
-  const int64_t lb = mlbp_exactmbest_lists_bytes(X, n_vars, M);
-  const bool spill_walk = (which & 15) == WALK_GENERIC && generic_lds_bytes(n_vars, P, U, X) > MLBP_CUTSET_GENERIC_LDS_BYTES;
-  const bool spill_lists = which >> 4 == WALK_GENERIC && lists_fixed_bytes(P, U) + lb > MLBP_CUTSET_GENERIC_LDS_BYTES;
-  return ((int64_t)B * n_configs * 2 + (int64_t)B * (M + 1) + (int64_t)B * M * M * 2 + ((int64_t)B * M * M * n_vars + 1) / 2 +
-          (spill_walk ? (int64_t)B * chunks * vector_doubles(n_vars, X) : 0) + (spill_lists ? (int64_t)B * M * lb / 8 : 0)) * 8;
+  return workspace_of(which, B, X, n_vars, P, U, n_configs, chunks, M);
 }
 
 int mlbp_exactmbest_check_plan(const int32_t* plan, int32_t n_words, int32_t X) { return check_packed_plan(plan, n_words, X); }
 
 int mlbp_exactmbest_f64(const mlbp_exactmbest_args* a, void* stream) {
   g_last_kernel = MLBP_EXACTMBEST_KERNEL_NONE;
-  int64_t n_configs = 0;
+  const bool listed = a && a->N > 0;                           // the header's listed mode: the walk's entries are the list's
+  int64_t n_configs = listed ? a->N : 0;
   const int values = check_walk_args(a, [](int32_t X, int32_t n_vars, int32_t P, int32_t U, int32_t n_forest) {
     return pick_walk_kernel(X, n_vars, P, U, n_forest);
   }, [](const mlbp_exactmbest_args* a) {
     if (int e = check_m(a->M)) return e;
     if (!a->assignments || !a->scores || !a->n_found) return fail(MLBP_EINVAL, "assignments, scores or n_found is NULL");
+    if (a->N < 0 || a->N > MLBP_EXACTMBEST_MAX_LISTED)
+      return fail(MLBP_EINVAL, "N = %d: a list holds 1 to %d configurations (0: the exact call)", a->N, MLBP_EXACTMBEST_MAX_LISTED);
+    if (a->N > 0 && a->n_cut > 0 && !a->configs) return fail(MLBP_EINVAL, "configs is NULL in a listed call with cutset variables");
     return (int)MLBP_OK;
-  }, &n_configs);
+  }, &n_configs, listed);
   if (values < 0) return values;
   const int which = mlbp_exactmbest_pick_kernel(a->X, a->n_vars, a->P, a->U, a->n_forest, a->M);
   if (which < 0) return which;
-  const int chunks = mlbp_exactmbest_chunks(a->B, (int32_t)n_configs);
+  int chunks = mlbp_exactmbest_chunks(a->B, (int32_t)n_configs);
   if (chunks < 0) return chunks;
-  if (int e = check_walk_workspace(a, mlbp_exactmbest_workspace_bytes(a->B, a->X, a->n_vars, a->P, a->U, a->n_forest, a->n_cut, a->M))) return e;
+  const int64_t need = listed ? workspace_of(which, a->B, a->X, a->n_vars, a->P, a->U, n_configs, chunks, a->M)
+                              : mlbp_exactmbest_workspace_bytes(a->B, a->X, a->n_vars, a->P, a->U, a->n_forest, a->n_cut, a->M);
+  if (int e = check_walk_workspace(a, need)) return e;
   if (int e = check_device("libmlbp_exactmbest.so")) return e;
+  if (listed && a->n_cut == 0) {                               // the one empty configuration, whatever N: the exact call on a forest
+    n_configs = 1;
+    chunks = 1;
+  }
   const int64_t B = a->B, M = a->M, lb = mlbp_exactmbest_lists_bytes(a->X, a->n_vars, a->M);
   MbestDev d;
   fill_walk_dev(d, a, n_configs, chunks, values);
@@ -731,6 +877,8 @@ int mlbp_exactmbest_f64(const mlbp_exactmbest_args* a, void* stream) {
   double* spill = d.cval + B * M * M * 2 + (B * M * M * a->n_vars + 1) / 2;
   d.assignments = a->assignments; d.scores = a->scores; d.n_found = a->n_found;
   d.M = a->M;
+  d.configs = listed && a->n_cut > 0 ? a->configs : nullptr;
+  d.entries = a->entries;
   d.lists = nullptr;
   d.lists_bytes = lb;
   d.x64_bytes = d.wave_bytes = 0;

@@ -527,6 +527,26 @@ class UserGraphTrainer:
             return torch.where(hit.any(dim=1), hit.to(torch.int64).argmax(dim=1), torch.full_like(hit[:, 0], -1, dtype=torch.int64))
         return (x.cpu().numpy().astype(np.int64),) + _host(score, logp, covered, rank_of(fb._labels), rank_of(bp_x))
 
+    def search_nbest(self, m, n_samples=256, seed=0, with_list=False):
+        """The sentence shapes exact_nbest() refuses, and the others beside it: the `m` best sets of guesses among those
+        whose cutset state is on search_decode()'s list, ranked (FactorGraphBatch.cutset_mbest over that list).  Host
+        (assignments int64 [B][m][n_vars] word indices in var_ids order, -1 in the rows a list does not have; scores float64
+        [B][m], -inf there; n_found int64 [B]; label_rank int64 [B] -- the row that is the user's own labelled set of guesses,
+        -1 when it is not among them --; bp_rank int64 [B] -- the row decode()'s set is: its cutset state is entry 0 of the
+        list, so it is -1 only where m sets under the listed states score above it).  No logp: entry 0 of the list is no draw
+        from a proposal, so the list carries no unbiased log Z.  with_list also configs int32 [B][n_samples][n_cut], the list
+        that was walked.  1 <= m <= 16; up to 16 cutset variables, nothing is refused for its number of configurations."""
+        fb = self.batch
+        self.build_potentials()
+        configs, bp_x, _ = fb._search_list(self.roots[:self.n_sweeps_run], n_samples, seed, None, None)
+        x, score, n_found = fb.cutset_mbest(configs, m)
+
+        def rank_of(rows):
+            hit = (x == rows[:, None, :].to(x.dtype)).all(dim=2)
+            return torch.where(hit.any(dim=1), hit.to(torch.int64).argmax(dim=1), torch.full_like(hit[:, 0], -1, dtype=torch.int64))
+        out = (x.cpu().numpy().astype(np.int64),) + _host(score, n_found.to(torch.int64), rank_of(fb._labels), rank_of(bp_x))
+        return out + (configs.cpu().numpy(),) if with_list else out
+
 
 def apply_update(theta_en_en, theta_en_de, stats, F_ee, F_ed, learning_rate, reg_param):
     """theta += sum_i lr (g_i - reg theta) = lr (sum_i g_i - n reg theta): the sum of the per-instance
@@ -1416,6 +1436,39 @@ class TiDirTrainer:
                 recall[r] += int(((label_rank >= 0) & (label_rank <= r)).sum())
         tot, _ = self._reduced([seen, covered_sum, n_bp] + list(recall))
         return per_sentence, (int(tot[0]), float(tot[1]), [int(v) for v in tot[3:]], int(tot[2])), skipped
+
+    # ---- the ranked list beyond the exact limit (the listed mode of include/mlbp_exactmbest.h) ----------------
+    def search_nbest(self, m, n_samples=256, seed=0):
+        """-> (per_sentence, totals).  per_sentence[i], for instance i of this rank's shard in file order: (predicted
+        positions, [[en words] per rank], [score]) -- the at most `m` best sets of guesses among those whose cutset state is
+        on search_decode()'s list, best first, and their log-potentials (UserGraphTrainer.search_nbest); an instance without
+        a predicted word builds no graph and gives ((), [], []).  No shape is skipped for its number of configurations (up to
+        16 cutset variables): the sentences with five and more predicted words that exact_nbest() lists as skipped are ranked
+        here, the others too.  The i-th sentence shape in self.trainers order draws with seed `seed + i`.  totals =
+        (sentences ranked, recall [m]: recall[r] = sentences whose labelled set of guesses sits at rank <= r, sentences whose
+        decode() set is in the list) over ALL ranks' instances, reduced once.  No logp is returned: entry 0 of a list is
+        decode()'s cutset state and no draw from a proposal, so the list carries no unbiased log Z."""
+        from . import exactmbest as K
+        m = int(m)
+        if not 1 <= m <= K.MAX_M:
+            raise ValueError('m must be in [1, %d]' % K.MAX_M)
+
+        def ranked(r, b):
+            x, score, n_found = r[:3]
+            have = max(int(n_found[b]), 0)
+            return [[self.en[w] for w in x[b, k]] for k in range(have)], [float(v) for v in score[b, :have]]
+
+        per_sentence, shapes = self._per_shape(lambda i, tr: tr.search_nbest(m, n_samples=n_samples, seed=int(seed) + i),
+                                               empty=((), [], []), row=ranked)
+        recall = np.zeros(m)
+        seen = n_bp = 0
+        for _, rows, (_, _, _, label_rank, bp_rank) in shapes:
+            seen += len(rows)
+            n_bp += int((bp_rank >= 0).sum())
+            for r in range(m):
+                recall[r] += int(((label_rank >= 0) & (label_rank <= r)).sum())
+        tot, _ = self._reduced([seen, n_bp] + list(recall))
+        return per_sentence, (int(tot[0]), [int(v) for v in tot[2:]], int(tot[1]))
 
     # ---- joint log-likelihood (log Z; the reference has only the sum of per-word log-marginals) ------
     def joint_log_likelihood(self):
