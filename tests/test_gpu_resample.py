@@ -54,12 +54,12 @@ def _dev(fb, a, dtype=None):
     return torch.from_numpy(np.ascontiguousarray(a if dtype is None else np.asarray(a).astype(dtype))).to(fb.device)
 
 
-def _run(fb, configs, log_q, uniforms, kernel=None):
+def _run(fb, configs, log_q, uniforms, kernel=None, cutset=None):
     """configs [B][N][n_cut], log_q [B][N], uniforms [S][B][n_vars] (numpy) -> dict(x, logp, log_z_hat, score, entry, ess)."""
     S = uniforms.shape[0]
     msgs_before = fb.msgs.clone()
     x, logp, log_z_hat, score, entry, ess = fb.cutset_resample(_dev(fb, configs, np.int32), _dev(fb, log_q), n_samples=S, uniforms=_dev(fb, uniforms),
-                                                               log_z=True, score=True, entry=True, ess=True)
+                                                               cutset=cutset, log_z=True, score=True, entry=True, ess=True)
     ran = _M().last_kernel()
     torch.cuda.synchronize()
     assert x.dtype == torch.int32 and tuple(x.shape) == (S, fb.B, fb.topo.n_vars)
