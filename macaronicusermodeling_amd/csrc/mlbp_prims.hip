@@ -16,6 +16,7 @@ namespace {
 constexpr auto need_device = mlbp::check_device;
 
 using mlbp_dev::ranks_above;
+using mlbp_dev::wave_sum;
 using mlbp_dev::wave_sum_xor;
 
 // C[b][i][j] = sum_k A[b][i][k] * B[b][k][j].  One wavefront per output element: lanes stride over
@@ -195,9 +196,9 @@ __global__ void potentials_multi_kernel(PotentialsJobs js) {
       const double v = exp(acc);
       if (pot) pot[e] = v;
       if (pot_t) pot_t[(int64_t)j * 64 + lane] = v;
-      const double Z = wave_sum_xor(v);
+      const double Z = wave_sum(v);                 // (wave_sum, not the butterfly: the order unary_expectations_kernel adds in, so the two give one set of bits)
       for (int k = 0; k < J.F && k < 8; ++k) {          // (the features are read again, from L1: kept in an array indexed at run time they live in scratch)
-        const double s = wave_sum_xor(v * ph[k]);
+        const double s = wave_sum(v * ph[k]);
         if (lane == 0) ex[(int64_t)j * 8 + k] = Z > 0.0 ? s / Z : 0.0;          // au.normalize: zero-sum -> 0
       }
     }

@@ -458,6 +458,28 @@ __device__ __forceinline__ void shared_gradient_epilogue(Dev& d, const int wg) {
   double fr0[16], fr1[16];
   if (DIRECT && t == 0) *reinterpret_cast<double2*>(reinterpret_cast<char*>(lds) + d.lds_bytes - 16) = make_double2(uniform, uniform);
   __syncthreads();
+  // Direct form: a tile carries its producer's magnitude (the table's, once per tile), and c (.) (W . r) multiplies three of them --
+  // tables at 2^-400 gave S = Z = 0 with nothing flagged.  So every message tile the epilogue reads first loses the power of two
+  // of its own total, in place (exact, and a per-graph scale like any other: it cancels in S / Z).  The totals' rows are still
+  // intact here, and nothing behind the epilogue reads a message tile (the marginals are staged in the constant products').
+  // Thread t takes double2 t of each tile: two states of graph t & 15 (tile_index).
+  if constexpr (DIRECT) {
+    const const_i32p cs0 = as_const(d.gr.c_slot), rs0 = as_const(d.gr.r_slot);
+    for (int q = 0; q < 2 * d.P; ++q) {
+      const int slot = (q & 1) ? cs0[q >> 1] : rs0[q >> 1];
+      if ((unsigned)slot >= (unsigned)d.n_msgs || !((img[d.off_written + (slot >> 5)] >> (slot & 31)) & 1)) continue;
+      const int tl = img[d.off_vftile + slot];
+      if (tl < 0) continue;
+      const double2* tp = reinterpret_cast<const double2*>(tot + tl * 64 + (t & 15) * 4);
+      const double2 ta = tp[0], tb = tp[1];
+      const int e = -total_exponent((ta.x + ta.y) + (tb.x + tb.y));
+      double2* p = reinterpret_cast<double2*>(tiles + (size_t)tl * TILE) + t;
+      double2 v = *p;
+      v.x = __builtin_ldexp(v.x, e); v.y = __builtin_ldexp(v.y, e);
+      *p = v;
+    }
+    __syncthreads();
+  }
   // factors per pass -- memory form: two tiles each, one tile of partial sums; direct form: what the totals' rows and the spare LDS
   // behind them hold (per factor 256 partial sums + 48 per-graph terms)
   const int NP = DIRECT ? min(NPMAX, (int)((d.lds_bytes - 16 - (size_t)d.n_res * TILE * sizeof(double)) / ((256 + 48) * sizeof(double)))) : min(NPMAX, (d.n_res - 1) >> 1);

@@ -195,7 +195,7 @@ _w('gradient_shared_x128', kind='gradient', spec='user_k3', X=128, B=19, layout=
 class _Group:
     """One batch of a workload: its spec, per-graph oracle inputs, device batch and outputs."""
 
-    def __init__(self, w, seed):
+    def __init__(self, w, seed, mutate=None):
         from macaronicusermodeling_amd.batch import FactorGraphBatch
         from macaronicusermodeling_amd.topology import GraphTopology
         X, B = w['X'], w['B']
@@ -256,6 +256,8 @@ class _Group:
                 t = [f for f in spec['factors'] if len(f['vars']) == 1][0]['table']
                 inputs[b]['tables'] = list(inputs[b]['tables'])
                 inputs[b]['tables'][t] = inputs[b]['tables'][t] * 0.0
+        if mutate:                            # (a caller's own inputs or edits, in place, before anything is derived from them)
+            mutate(inputs)
         self.inputs = inputs
         g = self.g = O.Graph(spec)
         pair, unary = batch_tables(spec, topo, inputs)
