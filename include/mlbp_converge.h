@@ -1,5 +1,6 @@
 /* mlbp_converge.h -- C ABI of libmlbp_converge.so: sum-product sweeps run to convergence, with a per-graph residual and a
- * per-graph early exit inside one launch (AMD Instinct MI355X, gfx950, float64).
+ * per-graph early exit inside one launch (AMD Instinct MI355X, gfx950, float64); the same for max-product sweeps, with the
+ * decoded assignment, as a mode of the one compute call.
  *
  * The fifth library of the engine.  libmlbp.so, libmlbp_map.so, libmlbp_logz.so and libmlbp_sample.so all run a FIXED number
  * of sweeps; none tells the caller whether the messages it reads are at a fixed point.  This one repeats the program's sweeps
@@ -37,6 +38,22 @@
  * every op of the program that names its destination slot is a UNARY op of the same unary slot -- it establishes that from the
  * op list itself at the start of the launch, for programs of up to 2048 ops.  The bits and the residuals are those of running
  * the op.  The generic kernel runs every op of every round.
+ *
+ * MAX-PRODUCT MODE (max_product != 0): every round runs with the update rules of mlbp_map.h -- a pairwise update takes max_j
+ * (max_i) where step 1 takes sum_j (sum_i); the maximum is fmax, which ignores a NaN entry; renorm still divides by the sum of
+ * the vector.  Steps 0, 2 and 3, rounds, residual, history, the X = 64 unary skip and the refusal of a graph with a table index
+ * out of range are as above, and `marginals` returns the same normalised product of the incoming messages, which is now the
+ * max-marginal.  Max-product need not settle: a graph that oscillates runs max_rounds rounds and says so in its residual.
+ * With `assignment` and `score` the call also decodes from the final messages, the read-out of mlbp_map.h:
+ *   assignment[g][v] = the argmax of v's max-marginal, ties to the lowest index;
+ *   score[g]         = sum over factors of log(table entry at the assignment), the tables as given,
+ * bit for bit what mlbp_map_sweep_f64 returns from the same messages.  pair_axis_var and unary_var are device data: a call whose
+ * arrays name a variable outside [0, n_vars) computes no graph (every graph is refused, below).  A refused graph gets
+ * assignment -1 and score NaN beside rounds -1 and residual NaN.
+ * Host checks of the new fields, all MLBP_EINVAL: with max_product, `assignment` without `score` or the reverse; either of them
+ * with P > 0 and pair_axis_var NULL, or with U > 0 and unary_var NULL; `assignment` or `score` without max_product (this last
+ * one is looked at once a device is known to be there: without one the call returns MLBP_ENODEVICE as it always did).  All of
+ * the new fields zero or NULL is the sum-product call above, every bit as it was.
  */
 #ifndef MLBP_CONVERGE_H
 #define MLBP_CONVERGE_H
@@ -94,6 +111,11 @@ typedef struct mlbp_converge_args {
   double* residual;                          /* device [B] */
   double* marginals;                         /* optional device [B][n_vars][X] */
   double* history;                           /* optional device [B][max_rounds] */
+  int32_t max_product;                       /* non-zero: the rounds run max-product (see above); 0: sum-product */
+  int32_t* assignment;                       /* optional device [B][n_vars]; max_product only, together with score */
+  double* score;                             /* optional device [B] */
+  const int32_t* pair_axis_var;              /* device [P][2] variable index on table axis 0 / 1 (with assignment, P > 0) */
+  const int32_t* unary_var;                  /* device [U] variable index of every unary factor (with assignment, U > 0) */
 } mlbp_converge_args;
 
 /* Table indices are device data and are not checked on the host.  A graph that names a table outside [0, n_pair_tables) /

@@ -493,13 +493,27 @@ class FactorGraphBatch:
         messages are left in self.msgs: marginals(), log_partition(roots=None), pair_beliefs() and gradient() then read the
         converged messages.  init=False continues from what self.msgs holds; marginals: optional [B][n_vars][X] device tensor.
         tol = 0 stops only at an exact fixed point (a tree reaches one in its second round)."""
+        return self._converge('converge', roots, tol, max_rounds, init, marginals, 'marginals', history, decode=False)
+
+    def map_converge(self, roots=None, tol=1e-6, max_rounds=50, init=True, max_marginals=None, history=False):
+        """converge() with MAX-product rounds -- map_sweep()'s updates, repeated until a whole round changes no message entry by
+        more than tol, graph by graph, in one launch -- and map_sweep()'s decode from the final messages.  Returns (assignment
+        int32 [B][n_vars], score float64 [B], rounds int32 [B], residual float64 [B]) device tensors, plus history float64
+        [B][max_rounds] with history=True.  residual <= tol says the messages the assignment was read from had settled;
+        max-product need not settle, and a graph that oscillates runs max_rounds rounds.  One round from uniform messages is
+        map_sweep(roots) bit for bit.  The final messages are left in self.msgs; init=False continues from what it holds;
+        max_marginals: optional [B][n_vars][X] device tensor.  Refuses what converge() refuses."""
+        return self._converge('map_converge', roots, tol, max_rounds, init, max_marginals, 'max_marginals', history, decode=True)
+
+    def _converge(self, what, roots, tol, max_rounds, init, marginals, marginals_word, history, decode):
+        """The one call of libmlbp_converge.so: sum-product rounds, or (decode) max-product rounds and the decoded assignment."""
         from . import converge as V
         if self.use_approx_inference:
-            raise NotImplementedError('converge has no top-100 approximate form')
+            raise NotImplementedError('%s has no top-100 approximate form' % what)
         if self.pair_tables is not None and self.pair_tables.dtype != torch.float64:
-            raise NotImplementedError('converge needs float64 pairwise tables')
+            raise NotImplementedError('%s needs float64 pairwise tables' % what)
         if not self.normalize_messages:
-            raise ValueError('converge needs normalised messages: a residual on unnormalised messages has no scale')
+            raise ValueError('%s needs normalised messages: a residual on unnormalised messages has no scale' % what)
         topo = self.topo
         prog = V.program(topo, topo.var_ids if roots is None else roots, self.device)
         a = V.ConvergeArgs()
@@ -510,18 +524,28 @@ class FactorGraphBatch:
         a.max_rounds, a.tol = int(max_rounds), float(tol)
         a.msgs = self.msgs.data_ptr()
         if marginals is not None:
-            a.marginals = self._tensor(marginals, (self.B, topo.n_vars, self.X), 'marginals', '[B][n_vars][X]')
+            a.marginals = self._tensor(marginals, (self.B, topo.n_vars, self.X), marginals_word, '[B][n_vars][X]')
         rounds = torch.empty(self.B, dtype=torch.int32, device=self.device)
         residual = torch.empty(self.B, dtype=torch.float64, device=self.device)
         a.rounds, a.residual = rounds.data_ptr(), residual.data_ptr()
-        hist = None
+        out = (rounds, residual)
+        if decode:
+            assignment = torch.empty(self.B, topo.n_vars, dtype=torch.int32, device=self.device)
+            score = torch.empty(self.B, dtype=torch.float64, device=self.device)
+            a.max_product, a.assignment, a.score = 1, assignment.data_ptr(), score.data_ptr()
+            if topo.P:
+                a.pair_axis_var = prog.pair_axis_var.data_ptr()
+            if topo.U:
+                a.unary_var = prog.unary_var.data_ptr()
+            out = (assignment, score) + out
         if history:
             if not 1 <= int(max_rounds) <= V.MAX_ROUNDS:
                 raise ValueError('max_rounds must be in [1, %d]' % V.MAX_ROUNDS)
             hist = torch.empty(self.B, int(max_rounds), dtype=torch.float64, device=self.device)
             a.history = hist.data_ptr()
+            out = out + (hist,)
         V.check(V.lib.mlbp_converge_f64(C.byref(a), _stream_ptr(self.device)))
-        return (rounds, residual, hist) if history else (rounds, residual)
+        return out
 
     # ---- what the six cutset-conditioning calls share -----------------------------------------------------
     def _cutset_args(self, K, Args, cutset, refusal):
@@ -793,13 +817,20 @@ class FactorGraphBatch:
         K.check(K.lib.mlbp_exactmap_f64(C.byref(a), _stream_ptr(self.device)))
         return (assignment, score, won) if entry else (assignment, score)
 
-    def _search_list(self, roots, n_samples, seed, uniforms, cutset):
-        """The list of search_map(): (configs int32 [B][N][n_cut], map_sweep's assignment, its score)."""
+    def _search_list(self, roots, n_samples, seed, uniforms, cutset, entry0='sweeps', tol=1e-6, max_rounds=50):
+        """The list of search_map(): (configs int32 [B][N][n_cut], the assignment of entry 0, its score[s]).  entry0 =
+        'sweeps': map_sweep's assignment and its score; 'settled': map_converge's, and the scores are the pair (map_converge's,
+        map_sweep's)."""
         from . import cutset as K0, cutsetis as KP
+        if entry0 not in ('sweeps', 'settled'):
+            raise ValueError("entry0 must be 'sweeps' or 'settled'")
         N = _listed_count(n_samples, KP)
         pl, _ = self._cutset_args(KP, KP.CutsetisArgs, cutset, 'search_map needs float64 pairwise tables')
         cut = [int(v) for v in pl.words[K0.PLAN_HEADER:K0.PLAN_HEADER + pl.n_cut]]
         x_bp, score_bp = self.map_sweep(roots, init=True)
+        if entry0 == 'settled':
+            x_bp, settled = self.map_converge(roots, tol=tol, max_rounds=max_rounds, init=True)[:2]
+            score_bp = (settled, score_bp)
         configs = torch.empty(self.B, N, pl.n_cut, dtype=torch.int32, device=self.device)
         if cut:
             configs[:, 0] = x_bp.index_select(1, torch.tensor(cut, dtype=torch.int64, device=self.device))
@@ -809,7 +840,7 @@ class FactorGraphBatch:
                 configs[:, 1:] = drawn
         return configs, x_bp, score_bp
 
-    def search_map(self, roots, n_samples=256, seed=0, uniforms=None, cutset=None):
+    def search_map(self, roots, n_samples=256, seed=0, uniforms=None, cutset=None, entry0='sweeps', tol=1e-6, max_rounds=50):
         """Search decoding beyond exact_map()'s limit: cutset_map() over a list made of the max-product answer and of draws
         from the sum-product messages.  Entry 0 of the list is the cutset state of map_sweep(roots)'s assignment; entries 1 to
         n_samples - 1 are cutset_draw(n_samples - 1, ...) on the messages of sweep(roots, init=True), which runs AFTER
@@ -817,10 +848,13 @@ class FactorGraphBatch:
         device tensors, score_bp the score of map_sweep's assignment: score >= score_bp up to the rounding of the two sums of
         logarithms, because the max-product assignment is among those the list admits.  n_samples = 1 is the optimal
         completion of the max-product cutset state alone.  seed / uniforms ([B][n_samples - 1][n_cut]) as cutset_draw takes
-        them; uniforms replaces seed.  cutset: as in cutset_map."""
-        configs, _, score_bp = self._search_list(roots, n_samples, seed, uniforms, cutset)
+        them; uniforms replaces seed.  cutset: as in cutset_map.
+        entry0='settled' takes entry 0 from map_converge(roots, tol, max_rounds) in the place of map_sweep(roots): the call then
+        returns (assignment, score, score_settled, score_bp), score >= score_settled in the same sense, and score_bp still
+        map_sweep's score, so that a caller sees both.  The default call is untouched by this."""
+        configs, _, score_bp = self._search_list(roots, n_samples, seed, uniforms, cutset, entry0, tol, max_rounds)
         assignment, score = self.cutset_map(configs, cutset=cutset)
-        return assignment, score, score_bp
+        return (assignment, score) + (score_bp if entry0 == 'settled' else (score_bp,))
 
     # ---- the M best whole assignments, ranked (include/mlbp_exactmbest.h) ------------------------------------
     def exact_mbest(self, m, cutset=None):
@@ -877,17 +911,18 @@ class FactorGraphBatch:
         K.check(K.lib.mlbp_exactmbest_f64(C.byref(a), _stream_ptr(self.device)))
         return (assignments, scores, n_found, under) if entries else (assignments, scores, n_found)
 
-    def search_mbest(self, roots, m, n_samples=256, seed=0, uniforms=None, cutset=None):
+    def search_mbest(self, roots, m, n_samples=256, seed=0, uniforms=None, cutset=None, entry0='sweeps', tol=1e-6, max_rounds=50):
         """Ranked search decoding beyond exact_mbest()'s limit: cutset_mbest() over search_map()'s list -- entry 0 the cutset
         state of map_sweep(roots)'s assignment, entries 1 to n_samples - 1 cutset_draw() draws on the messages of
         sweep(roots, init=True); both write self.msgs.  Returns (assignments int32 [B][m][n_vars], scores float64 [B][m],
         n_found int32 [B], score_bp float64 [B]) device tensors, score_bp the score of map_sweep's assignment:
         scores[:, 0] >= score_bp up to the rounding of the two sums of logarithms, because the max-product assignment is among
         those the list admits.  The rows are the true m best among the assignments whose cutset state was listed; the draws
-        repeat states, and a repeat counts once.  seed / uniforms and cutset: as in search_map."""
-        configs, _, score_bp = self._search_list(roots, n_samples, seed, uniforms, cutset)
+        repeat states, and a repeat counts once.  seed / uniforms and cutset: as in search_map; so is entry0='settled', which
+        returns (assignments, scores, n_found, score_settled, score_bp) with scores[:, 0] >= score_settled."""
+        configs, _, score_bp = self._search_list(roots, n_samples, seed, uniforms, cutset, entry0, tol, max_rounds)
         assignments, scores, n_found = self.cutset_mbest(configs, m, cutset=cutset)
-        return assignments, scores, n_found, score_bp
+        return (assignments, scores, n_found) + (score_bp if entry0 == 'settled' else (score_bp,))
 
     # ---- whole assignments drawn from the model itself (include/mlbp_exactsample.h) ---------------------
     def exact_sample(self, n_samples=1, seed=None, uniforms=None, cutset=None, log_z=False, score=False):

@@ -37,7 +37,9 @@ class ConvergeArgs(C.Structure):
                 ('pair_tables', C.c_void_p), ('pair_tab', C.c_void_p), ('unary_tables', C.c_void_p), ('unary_tab', C.c_void_p),
                 ('in_off', C.c_void_p), ('in_slots', C.c_void_p),
                 ('msgs', C.c_void_p), ('rounds', C.c_void_p), ('residual', C.c_void_p),
-                ('marginals', C.c_void_p), ('history', C.c_void_p)]
+                ('marginals', C.c_void_p), ('history', C.c_void_p),
+                ('max_product', C.c_int32), ('assignment', C.c_void_p), ('score', C.c_void_p),
+                ('pair_axis_var', C.c_void_p), ('unary_var', C.c_void_p)]
 
 
 # name -> (restype, argtypes); mirrors include/mlbp_converge.h one to one (tests/test_side_libraries_cpu.py checks that).
@@ -63,8 +65,22 @@ def check_program(ops, srcs, sweeps, n_msgs, P, U):
                                            int(n_msgs), int(P), int(U))
 
 
+def decode_arrays(topo):
+    """(pair_axis_var [P][2], unary_var [U]) int32, what the max-product mode's decode reads: the variable index on table axis
+    0 / 1 of every pairwise factor (fac_dim) and the variable of every unary factor, in pair-slot / unary-slot order."""
+    pav = np.zeros((max(topo.P, 1), 2), dtype=np.int32)
+    for p, j in enumerate(topo.pair_factors):
+        for k in range(2):
+            pav[p, topo.fac_dim[2 * j + k]] = topo.fac_var[2 * j + k]
+    uv = np.zeros(max(topo.U, 1), dtype=np.int32)
+    for u, j in enumerate(topo.unary_factors):
+        uv[u] = topo.fac_var[2 * j]
+    return pav, uv
+
+
 class ConvergeProgram(_sidelib.Program):
-    """Validated device copies of one root sequence's (ops, srcs, sweeps) -- one round -- and of the topology's read-out arrays."""
+    """Validated device copies of one root sequence's (ops, srcs, sweeps) -- one round -- and of the topology's read-out arrays,
+    the decode's among them."""
 
     def __init__(self, topo, roots, device):
         roots = tuple(int(r) for r in roots)
@@ -76,6 +92,11 @@ class ConvergeProgram(_sidelib.Program):
     def check_host(self):
         check(lib.mlbp_converge_check_program(*self.program_args()))
         check(lib.mlbp_converge_check_readout(*self.in_slot_args()))
+        pav, uv = decode_arrays(self.topo)
+        self._pav_h, self._uv_h = _sidelib.host_i32(pav), uv
+
+    def upload(self):
+        self.pair_axis_var, self.unary_var = self._up(self._pav_h), self._up(self._uv_h)
 
 
 _programs = _sidelib.Cache()

@@ -41,6 +41,11 @@ struct ConvergeDev {
   double tol;
   int32_t n_sweeps, n_msgs, P, U, X, n_vars, n_pair_tables, n_unary_tables;
   int32_t init, max_rounds, n_ops;
+  // max-product mode: the tag of the round loop, and the decode of mlbp_map.h from the final messages (assignment and score come
+  // together, and only with max_product)
+  int32_t max_product;
+  const int32_t* pair_axis_var; const int32_t* unary_var;
+  int32_t* assignment; double* score;
 };
 
 // |new - old| of one entry (mlbp_converge.h step 2): an entry that is NaN before and after has not moved (0); NaN on one side
@@ -95,12 +100,27 @@ __device__ __forceinline__ bool unary_once(unsigned mask, int o) {
   return ((unsigned)__builtin_amdgcn_readlane((int)mask, o & 63) >> (o >> 6)) & 1u;
 }
 
-// What a refused graph returns (mlbp_converge.h): rounds -1, residual NaN, its history row NaN; messages and marginals untouched.
+// The variables the decode's index arrays name are variables of the graph (device data, like the table indices; wave-uniform:
+// scalar loads).  Without a decode nothing is read.
+__device__ __forceinline__ bool decode_in_range(const ConvergeDev& d) {
+  if (!d.assignment) return true;
+  bool ok = true;
+  const const_i32p pav = as_const(d.pair_axis_var), uv = as_const(d.unary_var);
+  for (int i = 0; i < 2 * d.P; ++i) ok &= (unsigned)pav[i] < (unsigned)d.n_vars;
+  for (int u = 0; u < d.U; ++u) ok &= (unsigned)uv[u] < (unsigned)d.n_vars;
+  return ok;
+}
+
+// What a refused graph returns (mlbp_converge.h): rounds -1, residual NaN, its history row NaN, assignment -1 and score NaN;
+// messages and marginals untouched.
 __device__ __forceinline__ void refuse_graph(const ConvergeDev& d, int g) {
   if (threadIdx.x == 0) {
     d.rounds[g] = -1;
     d.residual[g] = __builtin_nan("");
+    if (d.score) d.score[g] = __builtin_nan("");
   }
+  if (d.assignment)
+    for (int v = threadIdx.x; v < d.n_vars; v += WG) d.assignment[(size_t)g * d.n_vars + v] = -1;
   if (d.history)
     for (int r = threadIdx.x; r < d.max_rounds; r += WG) d.history[(size_t)g * d.max_rounds + r] = __builtin_nan("");
 }
@@ -123,7 +143,7 @@ __global__ __launch_bounds__(WG) void converge_x64_kernel(ConvergeDev d) {
   double* raw = part + 512;                                    // [64] un-normalised result of a T.m update
   double* res_word = raw + 64;                                 // [1] the round's residual, read by every thread
   const int g = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  if (!tables_in_range(d.pair_tab, d.P, d.n_pair_tables, d.unary_tab, d.U, d.n_unary_tables, g)) {
+  if (!tables_in_range(d.pair_tab, d.P, d.n_pair_tables, d.unary_tab, d.U, d.n_unary_tables, g) || !decode_in_range(d)) {
     refuse_graph(d, g);
     return;                                                    // (block-uniform: the whole workgroup leaves)
   }
@@ -161,6 +181,31 @@ __global__ __launch_bounds__(WG) void converge_x64_kernel(ConvergeDev d) {
 
   int rounds = 0;
   double res = 0.0;
+  if (d.max_product) {                                         // (workgroup-uniform) the same rounds over MaxOp, a loop of its own
+    while (true) {
+      rmax = 0.0;
+      for (int sw = 0; sw < d.n_sweeps; ++sw) {
+        const int op0 = c_sweeps[2 * sw], nop = c_sweeps[2 * sw + 1];
+        for (int o = op0; o < op0 + nop; ++o) {
+          const int kind = c_ops[4 * o], a = c_ops[4 * o + 1], b = c_ops[4 * o + 2], c = c_ops[4 * o + 3];
+          if (kind == MLBP_OP_UNARY && rounds > 0 && unary_once(once_mask, o)) continue;
+          x64_step<MaxOp, RESIDENT>(G, R, kind, a, b, c, wave, lane, FreeState(), finish);
+        }
+      }
+      if (wave == 0) {                                         // the residual and the stop: as in the sum loop below
+        const double r = wave_max(rmax);
+        if (lane == 0) {
+          res_word[0] = r;
+          if (d.history) d.history[(size_t)g * d.max_rounds + rounds] = r;
+        }
+      }
+      __syncthreads();
+      res = res_word[0];
+      ++rounds;
+      if (res <= d.tol || rounds >= d.max_rounds) break;
+      __syncthreads();
+    }
+  } else
   while (true) {                                               // every thread takes the same number of turns: see below
     rmax = 0.0;
     for (int sw = 0; sw < d.n_sweeps; ++sw) {
@@ -193,6 +238,29 @@ __global__ __launch_bounds__(WG) void converge_x64_kernel(ConvergeDev d) {
     for (int v = wave; v < d.n_vars; v += WG / 64)             // one variable per wave, lane = state
       d.marginals[((size_t)g * d.n_vars + v) * 64 + lane] = x64_marginal(msg, in_off, in_slots, v, lane);
   }
+  if (d.assignment) {
+    // The decode of map_sweep_x64_kernel, op for op, so that the same messages give the same bits: one variable per wave, lane =
+    // state, the lowest lane at the wave's maximum; then wave 0 adds the log table entries.  The assignment lives in `part`, free
+    // since the last round (the host admits n_vars <= 1024 here: part holds 1024 words).
+    int32_t* xs = reinterpret_cast<int32_t*>(part);
+    for (int v = wave; v < d.n_vars; v += WG / 64) {
+      const double mm = x64_marginal(msg, in_off, in_slots, v, lane);
+      const unsigned long long at_max = __ballot(mm == wave_max(mm));
+      if (lane == 0) xs[v] = at_max ? __builtin_ctzll(at_max) : 0;           // ties go to the lowest index
+    }
+    __syncthreads();
+    for (int v = t; v < d.n_vars; v += WG) d.assignment[(size_t)g * d.n_vars + v] = xs[v];
+    if (wave == 0) {
+      double sc = 0.0;
+      for (int p = lane; p < d.P; p += 64) {
+        const int i = xs[d.pair_axis_var[2 * p]], j = xs[d.pair_axis_var[2 * p + 1]];
+        sc += log(d.pair_tables[(size_t)ptab[p] * 4096 + i * 64 + j]);
+      }
+      for (int u = lane; u < d.U; u += 64) sc += log(d.unary_tables[(size_t)utab[u] * 64 + xs[d.unary_var[u]]]);
+      sc = wave_sum(sc);
+      if (lane == 0) d.score[g] = sc;
+    }
+  }
 }
 
 // ---- any X ---------------------------------------------------------------------------------------
@@ -202,8 +270,10 @@ __global__ __launch_bounds__(WG) void converge_generic_kernel(ConvergeDev d) {
   double* raw = reinterpret_cast<double*>(smem);               // [X] (X rounded up to even)
   double* scratch = raw + ((X + 1) & ~1);                      // [4] block sums
   double* wave_res = scratch + 4;                              // [4] the waves' maxima of the round
+  int32_t* best_i = reinterpret_cast<int32_t*>(wave_res + 4);  // the decode only: [4] per-wave lowest index at the maximum
+  int32_t* xs = best_i + 4;                                    //                  [n_vars] the assignment
   const int g = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  if (!tables_in_range(d.pair_tab, d.P, d.n_pair_tables, d.unary_tab, d.U, d.n_unary_tables, g)) {
+  if (!tables_in_range(d.pair_tab, d.P, d.n_pair_tables, d.unary_tab, d.U, d.n_unary_tables, g) || !decode_in_range(d)) {
     refuse_graph(d, g);
     return;
   }
@@ -219,6 +289,31 @@ __global__ __launch_bounds__(WG) void converge_generic_kernel(ConvergeDev d) {
   __syncthreads();
   int rounds = 0;
   double res = 0.0;
+  if (d.max_product) {                                         // (workgroup-uniform) the same rounds over MaxOp, a loop of its own
+    while (true) {
+      double rmax = 0.0;
+      for (int sw = 0; sw < d.n_sweeps; ++sw) {
+        const int op0 = c_sweeps[2 * sw], nop = c_sweeps[2 * sw + 1];
+        for (int o = op0; o < op0 + nop; ++o) {
+          const int kind = c_ops[4 * o], a = c_ops[4 * o + 1], b = c_ops[4 * o + 2], c = c_ops[4 * o + 3];
+          generic_step<MaxOp>(G, X, uniform, kind, a, b, c, FreeState());
+          double* out = msg + (size_t)c * X;
+          generic_finish(raw, X, uniform, true, scratch, [&](int j, double fresh) {
+            rmax = fmax(rmax, entry_delta(fresh, out[j]));
+            out[j] = fresh;
+          });
+        }
+      }
+      rmax = wave_max(rmax);                                   // the residual and the stop: as in the sum loop below
+      if (lane == 0) wave_res[wave] = rmax;
+      __syncthreads();
+      res = fmax(fmax(wave_res[0], wave_res[1]), fmax(wave_res[2], wave_res[3]));
+      if (t == 0 && d.history) d.history[(size_t)g * d.max_rounds + rounds] = res;
+      ++rounds;
+      if (res <= d.tol || rounds >= d.max_rounds) break;
+      __syncthreads();
+    }
+  } else
   while (true) {
     double rmax = 0.0;                                         // over the entries this thread writes
     for (int sw = 0; sw < d.n_sweeps; ++sw) {
@@ -251,6 +346,41 @@ __global__ __launch_bounds__(WG) void converge_generic_kernel(ConvergeDev d) {
       __syncthreads();
     }
   }
+  if (d.assignment) {
+    // The decode of map_sweep_generic_kernel, op for op.  wave_res is free since the last round: the waves' maxima go there.
+    __syncthreads();                                           // (every thread has read wave_res)
+    const double ninf = -__builtin_huge_val();
+    for (int v = 0; v < d.n_vars; ++v) {
+      double best = ninf;
+      int at = 0x7fffffff;
+      generic_marginal(msg, in_off, in_slots, v, X, uniform, raw, scratch, [&](int j, double mm) {
+        if (mm > best) { best = mm; at = j; }                  // ascending j and a strict compare: the lowest index wins
+      });
+      const double wbest = wave_max(best);
+      int cand = best == wbest ? at : 0x7fffffff;
+#pragma unroll
+      for (int m = 32; m >= 1; m >>= 1) cand = min(cand, __shfl_xor(cand, m, 64));
+      if (lane == 0) { wave_res[wave] = wbest; best_i[wave] = cand; }
+      __syncthreads();
+      if (t == 0) {
+        double bv = wave_res[0];
+        int bi = best_i[0];
+        for (int w = 1; w < WG / 64; ++w)
+          if (wave_res[w] > bv || (wave_res[w] == bv && best_i[w] < bi)) { bv = wave_res[w]; bi = best_i[w]; }
+        xs[v] = bi < X ? bi : 0;
+      }
+      __syncthreads();
+    }
+    for (int v = t; v < d.n_vars; v += WG) d.assignment[(size_t)g * d.n_vars + v] = xs[v];
+    double sc = 0.0;
+    for (int p = t; p < d.P; p += WG) {
+      const int i = xs[d.pair_axis_var[2 * p]], j = xs[d.pair_axis_var[2 * p + 1]];
+      sc += log(d.pair_tables[(size_t)ptab[p] * X * X + (size_t)i * X + j]);
+    }
+    for (int u = t; u < d.U; u += WG) sc += log(d.unary_tables[(size_t)utab[u] * X + xs[d.unary_var[u]]]);
+    sc = block_sum(sc, scratch);
+    if (t == 0) d.score[g] = sc;
+  }
 }
 
 // ---- host ----------------------------------------------------------------------------------------
@@ -259,6 +389,9 @@ thread_local int g_last_kernel = MLBP_CONVERGE_KERNEL_NONE;
 int64_t x64_lds_bytes(int32_t n_msgs) { return (int64_t)n_msgs * 512 + 4608 + 8; }
 
 size_t generic_lds_bytes(int32_t X) { return (size_t)((X + 1) & ~1) * 8 + 8 * 8; }
+
+// What the generic kernel's decode adds behind that: four candidate indices and the assignment.
+size_t generic_decode_lds_bytes(int32_t n_vars) { return 4 * 4 + 4 * (size_t)n_vars; }
 
 }  // namespace
 
@@ -307,7 +440,20 @@ int mlbp_converge_f64(const mlbp_converge_args* a, void* stream) {
   if (!a->rounds || !a->residual) return fail(MLBP_EINVAL, "rounds or residual is NULL");
   if (int e = check_args_tables(a)) return e;
   if (int e = check_args_extent(a)) return e;
+  const bool decode = a->assignment || a->score;
+  if (a->max_product && decode) {
+    if (!a->assignment) return fail(MLBP_EINVAL, "score without assignment: the decode returns both");
+    if (!a->score) return fail(MLBP_EINVAL, "assignment without score: the decode returns both");
+    if (a->P > 0 && !a->pair_axis_var) return fail(MLBP_EINVAL, "P = %d and assignment given but pair_axis_var is NULL", a->P);
+    if (a->U > 0 && !a->unary_var) return fail(MLBP_EINVAL, "U = %d and assignment given but unary_var is NULL", a->U);
+    if (which == MLBP_CONVERGE_KERNEL_X64 && a->n_vars > 1024)
+      return fail(MLBP_EUNSUPPORTED, "n_vars = %d: the X = 64 kernel's assignment holds at most 1024 variables", a->n_vars);
+    if (which == MLBP_CONVERGE_KERNEL_GENERIC && generic_lds_bytes(a->X) + generic_decode_lds_bytes(a->n_vars) > 65536)
+      return fail(MLBP_EUNSUPPORTED, "n_vars = %d: the generic kernel's assignment does not fit LDS", a->n_vars);
+  }
   if (int e = check_device("libmlbp_converge.so")) return e;
+  // (behind the device check: a call that sets every pointer and no mode has always reached it)
+  if (!a->max_product && decode) return fail(MLBP_EINVAL, "assignment or score without max_product: the sum-product rounds decode nothing");
   ConvergeDev d;
   d.pair_tables = a->pair_tables; d.pair_tab = a->pair_tab; d.unary_tables = a->unary_tables; d.unary_tab = a->unary_tab;
   d.ops = a->ops; d.srcs = a->srcs; d.sweeps = a->sweeps;
@@ -317,6 +463,8 @@ int mlbp_converge_f64(const mlbp_converge_args* a, void* stream) {
   d.n_sweeps = a->n_sweeps; d.n_msgs = a->n_msgs; d.P = a->P; d.U = a->U; d.X = a->X; d.n_vars = a->n_vars;
   d.n_pair_tables = a->n_pair_tables; d.n_unary_tables = a->n_unary_tables;
   d.init = a->init_messages != 0; d.max_rounds = a->max_rounds; d.n_ops = a->n_ops;
+  d.max_product = a->max_product != 0;
+  d.pair_axis_var = a->pair_axis_var; d.unary_var = a->unary_var; d.assignment = a->assignment; d.score = a->score;
   hipStream_t st = (hipStream_t)stream;
   (void)hipGetLastError();
   if (which == MLBP_CONVERGE_KERNEL_X64) {
@@ -325,7 +473,8 @@ int mlbp_converge_f64(const mlbp_converge_args* a, void* stream) {
     if (int e = grant_x64_lds((const void*)k, resident ? 1 : 0, MLBP_CONVERGE_X64_LDS_BYTES)) return e;
     hipLaunchKernelGGL(k, dim3(a->B), dim3(WG), (size_t)x64_lds_bytes(a->n_msgs), st, d);
   } else {
-    hipLaunchKernelGGL(converge_generic_kernel, dim3(a->B), dim3(WG), generic_lds_bytes(a->X), st, d);
+    const size_t lds = generic_lds_bytes(a->X) + (decode ? generic_decode_lds_bytes(a->n_vars) : 0);
+    hipLaunchKernelGGL(converge_generic_kernel, dim3(a->B), dim3(WG), lds, st, d);
   }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(MLBP_EHIP, "converge launch failed: %s", hipGetErrorString(e));

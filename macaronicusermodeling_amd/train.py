@@ -306,6 +306,19 @@ class UserGraphTrainer:
         assignment, score = self.batch.map_sweep(self.roots[:self.n_sweeps_run], init=True, keep_messages=False)
         return assignment.cpu().numpy().astype(np.int64), score.cpu().numpy()
 
+    def settled_decode(self, tol=1e-6, max_rounds=50, with_changed=False):
+        """decode() run until its messages stop moving (FactorGraphBatch.map_converge; a round is the predict() schedule, so
+        the first round is decode() itself): host (assignment int64 [B][n_vars] word indices in var_ids order, score float64
+        [B], rounds int32 [B], residual float64 [B] -- residual <= tol: the set was read from settled messages --, gain
+        float64 [B] -- score minus decode()'s score; max-product promises no sign for it); with_changed also changed bool [B],
+        the set differs from decode()'s."""
+        fb, roots = self.batch, self.roots[:self.n_sweeps_run]
+        self.build_potentials()
+        bp_x, bp_score = fb.map_sweep(roots, init=True, keep_messages=False)
+        x, score, rounds, residual = fb.map_converge(roots, tol=tol, max_rounds=max_rounds, init=True)
+        out = (x.cpu().numpy().astype(np.int64),) + _host(score, rounds, residual, score - bp_score)
+        return out + _host((bp_x != x).any(dim=1)) if with_changed else out
+
     def sample(self, n_samples=1, seed=None, uniforms=None, given=None):
         """Whole sets of guesses drawn from the model under the current thetas (sequential conditioning over the predict()
         schedule, FactorGraphBatch.sample): host (samples int64 [S][B][n_vars] word indices in var_ids order, logq float64
@@ -1100,6 +1113,35 @@ class TiDirTrainer:
                                           row=lambda r, b: ([self.en[w] for w in r[0][b]], float(r[1][b])))
         counts = sum((self._hit_counts(key, x) for key, _, (x, _) in shapes), np.zeros(4, dtype=np.int64))
         return guesses, tuple(int(v) for v in self._reduced(counts)[0])
+
+    def settled_decode(self, tol=1e-6, max_rounds=50):
+        """-> (guesses, totals, reached).  guesses[i], for instance i of this rank's shard in file order: (predicted positions,
+        [en words], score, rounds, residual, gain over decode()) as UserGraphTrainer.settled_decode gives them; an instance
+        without a predicted word builds no graph and gives ((), [], 0.0, 0, 0.0, 0.0).  totals = (sentences decoded, sentences
+        whose residual is at most tol, sentences whose score rose above decode()'s by more than SEARCH_ROSE relative to
+        max(1, |score|), sentences whose score fell by more than that, sentences whose words changed).  reached = (sentences
+        of the shapes exact_map() answers, those whose settled set is exact_map()'s, sum and largest of exact_map()'s score
+        minus the settled score); the sentences of five and more predicted words are decoded and counted in totals, not in
+        reached.  Over ALL ranks' instances, reduced once."""
+        from . import exactmap as K
+
+        def call(i, tr):
+            r = tr.settled_decode(tol=tol, max_rounds=max_rounds, with_changed=True)
+            best, _ = _try(lambda: tr.batch.exact_map(), K.ExactMapError)          # (the potentials are built)
+            return r + (None if best is None else (best[0].cpu().numpy().astype(np.int64), best[1].cpu().numpy()),)
+        guesses, shapes = self._per_shape(
+            call, empty=((), [], 0.0, 0, 0.0, 0.0),
+            row=lambda r, b: ([self.en[w] for w in r[0][b]], float(r[1][b]), int(r[2][b]), float(r[3][b]), float(r[4][b])))
+        sums, worst = np.zeros(8), 0.0
+        for _, _, (x, score, _, residual, gain, changed, best) in shapes:
+            bar = SEARCH_ROSE * np.maximum(1.0, np.abs(score))
+            sums[:5] += [len(score), int((residual <= tol).sum()), int((gain > bar).sum()), int((gain < -bar).sum()), int(changed.sum())]
+            if best is not None:
+                short = np.where((best[0] == x).all(axis=1), 0.0, np.maximum(best[1] - score, 0.0))
+                sums[5:] += [len(score), int((best[0] == x).all(axis=1).sum()), float(short.sum())]
+                worst = max(worst, float(short.max()))
+        tot, top = self._reduced(sums, [worst])
+        return guesses, tuple(int(v) for v in tot[:5]), (int(tot[5]), int(tot[6]), float(tot[7]), float(top[0]))
 
     # ---- posterior sampling of whole sets of guesses (the reference has none) --------------------------
     def sample(self, n_samples=1, seed=0):
